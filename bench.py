@@ -27,6 +27,13 @@ copies in rank order), `--comm lib` an RCCL all-reduce issued by the library, `-
 torch.distributed issues it between two library calls. `--comm auto` (default) tries them in that order: a transport
 that raises, leaves the ranks with different duals, fails the host-side check of the summed injections or fails in the
 timed region is given up in place and named in the line (`comm.transports_given_up`).
+
+--dump-outputs DIR: after the timed region, rank 0 writes what its engine hands a caller after the last timed step as
+DIR/<name>.npy (float64): P, D, C, E (primal, agents x T), lam, mu, rho (duals), inj, avg_U, avg_K, flow, cost
+(consensus) and residuals (lambda, mu, rho residual, iteration); arrays that are empty for the workload (the line terms on
+a copper plate, D/C/E without storages) are not written. The problem is seeded, so the same arguments give the
+same inputs on every run. Above 64 MB in all, P and D/C/E are cut to one fixed, seeded sample of rows each, whose
+indices are written as <name>_rows.npy.
 """
 import argparse
 import json
@@ -162,6 +169,35 @@ def cpu_baseline(pp, gamma, w_flow, synth, budget_s=14.0):
     return out
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(eng, out_dir, budget=DUMP_BYTES):
+    """--dump-outputs: the engine's outputs as DIR/<name>.npy (module docstring); returns the names written."""
+    import numpy as np
+    P, D, C, E = eng.get_primal()
+    lam, mu, rho = eng.get_duals()
+    inj, avg_u, avg_k, flow, cost = eng.get_consensus()
+    small = dict(lam=lam, mu=mu, rho=rho, inj=inj, avg_U=avg_u, avg_K=avg_k, flow=flow, cost=np.array([cost]),
+                 residuals=np.array(eng.get_residuals(), dtype=np.float64))
+    rows = dict(P=P, D=D, C=C, E=E)
+    left = budget - 128 * 2 * (len(small) + len(rows)) - sum(a.nbytes for a in small.values())     # (128: one .npy header)
+    need = sum(a.shape[0] * (a.shape[1] + 1) * 8 for a in rows.values())     # (+1: the index of a kept row)
+    out = dict(small)
+    for name, a in rows.items():
+        if need > left and a.shape[0] > 0:
+            k = max(1, int(a.shape[0] * left / need))
+            idx = np.sort(np.random.default_rng(20220720).choice(a.shape[0], size=k, replace=False))
+            out[name], out[name + "_rows"] = a[idx], idx.astype(np.float64)
+        else:
+            out[name] = a
+    out = {name: a for name, a in out.items() if a.size}          # (no lines: mu, rho, avg_U, avg_K, flow are empty)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(out)
+
+
 def self_launch(args, argv, child_cmd=None, min_budget=20.0):
     """--gpus N without a launcher: start the N ranks as children (this process never touches the GPU), relay
     rank 0's JSON line. A run that hangs is killed at the deadline and retried on the next communication mode.
@@ -254,6 +290,8 @@ def main():
     ap.add_argument("--force-sharded", action="store_true", help="debug: drive the sharded (all-reduce) path even on one rank")
     ap.add_argument("--launch-timeout", type=float, default=150.0,
                     help="self-launched multi-GPU run: budget in seconds for ALL attempts together (the first may use 60 %% of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write rank 0's outputs of the last timed step as DIR/<name>.npy (at most 64 MB)")
     args = ap.parse_args()
     if args.no_side:
         args.no_also = args.no_cpu_baseline = True
@@ -491,6 +529,7 @@ def main():
         dt = float(tt.item())
     it_after, _ = sync()
     assert it_after == 1 + args.warmup + args.steps, (it_after, args.warmup, args.steps)
+    dumped = dump_outputs(eng, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     fails = eng.solver_failures()
     if use_lib_comm:
         w_, r_, g_ = eng.comm_info()
@@ -817,6 +856,8 @@ def main():
             out["errors"] = side_errors
         if not sharded and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pp, gamma, w_flow, synth)
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if dist is not None:
         eng.close()              # (communicator teardown while every rank is still there)

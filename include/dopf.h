@@ -113,8 +113,9 @@ typedef struct dopf_params {
                                    iteration faster than the GPU retires it, and plain launches are RCCL's best-trodden path) */
 #define DOPF_F_COMM_P2P    1024  /* dopf_multi_*: the consensus sum by the peer exchange (dopf_xchg_* below) instead of RCCL.
                                    (Rehearsals that put several shards on ONE device: every shard's stream then needs a hardware
-                                   queue of its own — GPU_MAX_HW_QUEUES — or a waiting exchange kernel sits in front of the peer
-                                   it waits for and the wait times out. One shard per device cannot run into that.)        */
+                                   queue of its own (HIP's default of four covers three shards) or a waiting exchange kernel
+                                   sits in front of the peer it waits for and the wait times out. One shard per device cannot
+                                   run into that.)                                                                          */
 #define DOPF_F_NO_TAIL_FUSE 4096  /* one node, no lines, single-GPU chain: keep the consensus sums and the dual step as launches of
                                    their own (k_reduce, k_dual_price_small) instead of finishing the iteration inside the
                                    x-update launch (integer accumulators + the last block's tail) */

@@ -1,4 +1,4 @@
-"""Started by tests/test_gpu_multi.py (GPU_MAX_HW_QUEUES=8, nothing else alive in the process): the peer exchange of
+"""Started by tests/test_gpu_multi.py (nothing else alive in the process): the peer exchange of
 dopf_multi_* with several shards on ONE device. See the test's docstring."""
 import ctypes as C
 import gc

@@ -20,7 +20,7 @@ SLICES = [
     ("fuzz_parity", 260, 411, {}, "one-step parity on random small cases (networks and copper plates, ragged shapes)"),
     ("fuzz_free", 110, 412, {}, "free runs side by side: warm starts, certificates, hand-over to the scan body"),
     ("fuzz_lean", 60, 413, {}, "the lean copper-plate storage body vs oracle and vs the general body"),
-    ("fuzz_sharded", 110, 414, {"GPU_MAX_HW_QUEUES": "8"}, "2-3 shards on one device vs a single context"),
+    ("fuzz_sharded", 110, 414, {}, "2-3 shards on one device vs a single context"),
     ("fuzz_quiet", 45, 415, {}, "the quiet network chain (no k_slack launch) bit for bit against the chain it replaces"),
     ("fuzz_net_wide", 10, 416, {}, "wide networks: 12-300 nodes, up to 400 lines, 24-192 steps"),
     ("fuzz_oracle", 40, 417, {"ORACLE_MODE": "0"}, "HIP vs the LITERAL mode of the oracle (term-by-term QP, interior point)"),

@@ -226,10 +226,10 @@ def test_peer_exchange_shards_on_one_device(hip_api):
     against a single context on a network and two copper plates (trajectory to rounding, replicated state bitwise equal
     on all shards), a consensus vector of several 2048-double chunks, the stop at iteration 476, a peer that never sends.
     Its own process because shards that share one device need a hardware queue each — a waiting exchange kernel must not
-    sit in the queue in front of the peer it waits for — so the child runs with GPU_MAX_HW_QUEUES=8 and nothing else
-    alive; one shard per device, the real thing, cannot run into that."""
+    sit in the queue in front of the peer it waits for — so the child runs with nothing else alive, and HIP's default
+    number of hardware queues covers its three shards; one shard per device, the real thing, cannot run into that."""
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "p2p_worker.py")
-    r = subprocess.run([sys.executable, worker], env=dict(os.environ, GPU_MAX_HW_QUEUES="8", DOPF_XCHG_TIMEOUT_MS="4000"),
+    r = subprocess.run([sys.executable, worker], env=dict(os.environ, DOPF_XCHG_TIMEOUT_MS="4000"),
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "p2p worker: ok" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-1500:])
     for line in ("equal network 2", "equal network 3", "equal copper plate 3", "equal copper plate T96 2", "three-launch exchange ok", "chunks ok", "reduce-scatter ok", "comm-quiet ok", "stop ok", "missing peer ok"):
