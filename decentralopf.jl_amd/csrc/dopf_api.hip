@@ -304,8 +304,13 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         if (p->sto_node[s] < 0 || p->sto_node[s] >= p->N) return fail(nullptr, DOPF_E_INVALID, "sto_node[%d] out of range", s);
     if ((int64_t)p->G * p->T > (int64_t)1 << 40) return fail(nullptr, DOPF_E_INVALID, "problem too large");
     Launch lc{};
-    if (p->S > 0 && !sto_config_supported(p->T, &lc))
-        return fail(nullptr, DOPF_E_UNSUPPORTED, "storage kernel supports T <= 512 (got %d)", p->T);
+    if (p->S > 0 && !sto_config_supported(p->T, &lc)) {
+        if (!(q->flags & (DOPF_F_LONG_HORIZON | DOPF_F_DEBUG_LONG_STO)))
+            return fail(nullptr, DOPF_E_UNSUPPORTED, "storage kernel supports T <= 512 (got %d); longer horizons need DOPF_F_LONG_HORIZON", p->T);
+        lc.stoLong = 1;
+    }
+    if (p->S > 0 && (q->flags & DOPF_F_DEBUG_LONG_STO)) lc.stoLong = 1;
+    if (lc.stoLong) { lc.stoLPS = 64; lc.stoNCH = 8; }         // (not read by the long body; keeps the one-wave paths' choices off)
     if (2 * p->L > 4096) return fail(nullptr, DOPF_E_UNSUPPORTED, "table kernel supports L <= 2048 (got %d)", p->L);   // 4 * 2L doubles of LDS
 
     if (int rc1 = check_one_runtime(nullptr)) return rc1;
@@ -357,12 +362,13 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         const double a0 = v.w_prox + v.gamma;
         v.cp_ia = 1.0 / a0; v.cp_idet = 1.0 / (a0 * a0 - v.gamma * v.gamma); v.cp_s2 = 2.0 / (a0 + v.gamma);
     }
-    v.use_warm = (S > 0 && lc.stoNCH <= 3 && !(q->flags & DOPF_F_NO_WARM_START)) ? 1 : 0;
+    v.use_warm = (S > 0 && lc.stoNCH <= 3 && !(q->flags & DOPF_F_NO_WARM_START)) ? 1 : 0;     // (the long body: NCH 8, off)
     // The lean active-set body (sto_lean.h): 32-bit element offsets; on a network only where the storage blocks outnumber the
     // chip's resident slots several times — its gain is instruction count, and a grid of one resident round is bound by one
     // block's latency chain, which is no shorter (configs[3]: 114 us against 120 at 100 k agents; its 12.5 k share 43.3 against 41.1).
     v.stoLean = ((q->flags & DOPF_F_STO_GENERAL) || (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
                  (L > 0 && (long long)S * lc.stoLPS / 256 < 1024)) ? 0 : 1;
+    if (lc.stoLong) v.stoLean = 0;
     v.genTT = std::min(T, 512);
     v.genR = 512 / v.genTT;
     v.genTT2 = (L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
@@ -462,6 +468,7 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
             const int passes = (units + slots - 1) / slots;
             if (passes >= 2 && (units + passes - 1) / passes >= (slots * 4) / 5) schunk = std::max(schunk, passes * NG);
         }
+        if (lc.stoLong) schunk = 1;         // the long body: one block per storage
         make_items(snode, N, schunk, sitems, nsb, nsib);
         v.stoChunk = (N == 1 && !exp_env("DOPF_NO_STO_CHUNK")) ? schunk : 0;
     }
@@ -838,6 +845,7 @@ int dopf_iterate_timed(dopf_ctx *c, int32_t n_iters, dopf_timing *out)
     out->quiet = v.quiet ? 1 : 0;
     out->sto_lean = (v.stoLean && v.S > 0 && v.use_warm) ? 1 : 0;
     out->persist = persist_on(c) ? 1 : 0;
+    out->sto_long = (c->lc.stoLong && v.S > 0) ? 1 : 0;
     return DOPF_OK;
 }
 

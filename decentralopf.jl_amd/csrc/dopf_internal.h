@@ -215,6 +215,7 @@ __device__ __forceinline__ void status_update(const DevView &v, double r0, doubl
 
 struct Launch {
     int stoLPS, stoNCH;
+    int stoLong;                    // the storages run on the long-horizon body (sto_long.h: DOPF_F_LONG_HORIZON beyond T = 512, DOPF_F_DEBUG_LONG_STO)
 };
 
 // the central reference's view (kernels_central.hip): the context's arrays (P, D, C, E, items, partial sums, cons) plus the

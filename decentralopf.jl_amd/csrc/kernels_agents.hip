@@ -2160,6 +2160,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
 
 }  // namespace dopf
 #include "sto_lean.h"
+#include "sto_long.h"
 namespace dopf {
 
 // The scan body as a function of its own (networks): called by k_sto_warm for the rare item the active-set body leaves
@@ -2450,6 +2451,11 @@ void launch_net_agents(const DevView &v, const Launch &lc, hipStream_t s)
 void launch_sto_update(const DevView &v, const Launch &lc, hipStream_t s)
 {
     if (v.nStoItems == 0) return;
+    if (lc.stoLong) {                       // DOPF_F_LONG_HORIZON (sto_long.h): one block per item, any horizon
+        if (v.L > 0) hipLaunchKernelGGL((k_sto_long<true>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
+        else hipLaunchKernelGGL((k_sto_long<false>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
+        return;
+    }
 #define DOPF_CASE(LPS_, NCH_) if (lc.stoLPS == LPS_ && lc.stoNCH == NCH_) { launch_sto_t<LPS_, NCH_>(v, s); return; }
     DOPF_CASE(8, 1) DOPF_CASE(8, 2) DOPF_CASE(8, 3)
     DOPF_CASE(16, 3)

@@ -123,6 +123,7 @@ function dopf_check_multi(rc::Cint, m::Ptr{Cvoid})
 end
 
 const DOPF_F_COMM_P2P = 1024      # include/dopf.h
+const DOPF_F_LONG_HORIZON = 2097152  # include/dopf.h
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -134,6 +135,8 @@ sharded over that many devices inside the library, one RCCL all-reduce per itera
 `flags = DOPF_F_COMM_P2P`, the library's peer exchange: direct stores into the other devices' memory, no collective
 library, a few microseconds instead of tens for the small vector of a copper plate), `record`, and the
 reference's literals `w_flow = 10`, `w_prox = 1`, `eps = 1e-3`, `mask_thr = 1e-2`.
+Storages on horizons beyond 512 timesteps (an hourly year: T = 8 760) need `flags = DOPF_F_LONG_HORIZON`
+(the long-horizon storage body; without the flag the library refuses them). Flags combine with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,

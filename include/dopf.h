@@ -138,6 +138,9 @@ typedef struct dopf_params {
 #define DOPF_F_PERSIST 1048576 /* copper plates whose x-update is one launch with every block resident (config1, config2): run the
                                   * iterations of a dopf_iterate call in launches of up to 16 ITERATIONS each — the grid stays, the tail block
                                   * publishes the new prices to the other blocks (csrc/agents_persist.h; round 4 experiment) */
+#define DOPF_F_LONG_HORIZON 2097152 /* storages on horizons beyond T = 512 (without it dopf_create refuses them): solved by the long-horizon
+                                  * body (csrc/sto_long.h: one block per storage, the horizon in tiles of 2048 timesteps, no limit on T but
+                                  * device memory) on the separate-launch chain. For T <= 512 the flag changes nothing. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -146,6 +149,8 @@ typedef struct dopf_params {
                                    hand-over to the scan body is exercised in every kernel variant                        */
 #define DOPF_F_DEBUG_ROOT_CAP 128 /* tests: the scan kernel's root search gives up after 2 iterations instead of
                                    80, so that the DOPF_E_SOLVER path can be exercised                        */
+#define DOPF_F_DEBUG_LONG_STO 4194304 /* tests: the storages run on the long-horizon body at every T, also T <= 512, so that it can be
+                                   compared with the one-wave bodies where those are trusted                    */
 
 /* Fill q with the reference's defaults (values above). */
 void dopf_default_params(dopf_params *q);
@@ -248,6 +253,7 @@ typedef struct dopf_timing {
     int32_t sto_lean;       /* 1: the storages of this problem are solved by the lean active-set body (csrc/sto_lean.h) */
     int32_t persist;        /* 1: dopf_iterate runs several iterations per launch on this context (DOPF_F_PERSIST; this timed call itself
                                launches iteration by iteration) */
+    int32_t sto_long;       /* 1: the storages ran on the long-horizon body (csrc/sto_long.h: DOPF_F_LONG_HORIZON, DOPF_F_DEBUG_LONG_STO) */
 } dopf_timing;
 int dopf_iterate_timed(dopf_ctx *ctx, int32_t n_iters, dopf_timing *out);
 /* DOPF_F_TIME_CALLS: milliseconds between the first launch of the last dopf_iterate call and the end of its last one, on the
