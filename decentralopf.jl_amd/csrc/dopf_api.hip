@@ -109,71 +109,166 @@ void make_items(const std::vector<int> &node_sorted, int N, int chunk, std::vect
     node_item_beg[N] = (int)items.size();
 }
 
+// the wide chain (net_wide.h): beyond 2048 lines, where k_tables' LDS (4 * 2L doubles) runs out, or at any L on request
+bool wide_chain(int L, unsigned flags) { return 2 * L > 4096 || (L > 0 && (flags & DOPF_F_DEBUG_WIDE_NET)); }
+
+// the quiet chain's dual/price kernel stages every partial row of its timestep in LDS: up to 96 KB of them
+bool quiet_rows_fit(int rows) { return rows > 0 && (size_t)rows * sizeof(double) <= 96 * 1024; }
+
+// agents per node -> work items of at most `chunk` agents that never cross a node boundary (make_items)
+int count_items(const std::vector<int> &per_node, int chunk)
+{
+    int n = 0;
+    for (int a : per_node) n += (a + chunk - 1) / chunk;
+    return n;
+}
+
+// XCD (of eight) whose blocks write generator item i's partial row (networks; storage item k: k % 8). k_net_agents: storages first
+int gen_row_xcd(const Plan &p, int i) { return ((p.fuseNet ? p.nStoItems : 0) + i) % 8; }
+
+// The problem's sizes and what plan_chain needs of its data
+struct Shape {
+    int N, L, T, G, S;
+    std::vector<int> gen_at, sto_at;    // generators / storages per node
+    int ki, kc;                         // fraction bits the fixed-point sums of the one-launch tail would keep (injection, cost)
+};
+
+// The launch chain of a context, decided once: dopf_create builds the items and rows from it, the launch functions
+// switch on it. No HIP call, no allocation. cus: the device's CUs (0: unknown). dopf_create has refused T > 512 without
+// DOPF_F_LONG_HORIZON and L > 2048 without DOPF_F_WIDE_NETWORK.
+Plan plan_chain(const Shape &sh, unsigned flags, int cus)
+{
+    const int N = sh.N, L = sh.L, T = sh.T, G = sh.G, S = sh.S;
+    Plan p{};
+    if (S > 0 && (!sto_config_supported(T, &p) || (flags & DOPF_F_DEBUG_LONG_STO))) p.stoLong = 1;
+    if (p.stoLong) { p.stoLPS = 64; p.stoNCH = 8; }         // (not read by the long body; keeps the one-wave paths' choices off)
+    p.wideNet = wide_chain(L, flags) ? 1 : 0;
+    p.useWarm = S > 0 && p.stoNCH <= 3 && !(flags & DOPF_F_NO_WARM_START);     // (the long body: NCH 8, off)
+    // The lean active-set body (sto_lean.h): 32-bit element offsets; on a network only where the storage blocks outnumber the
+    // chip's resident slots several times — its gain is instruction count, and a grid of one resident round is bound by one
+    // block's latency chain, which is no shorter (configs[3]: 114 us against 120 at 100 k agents; its 12.5 k share 43.3 against 41.1).
+    p.stoLean = !((flags & DOPF_F_STO_GENERAL) || (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
+                  (L > 0 && (long long)S * p.stoLPS / 256 < 1024)) && !p.stoLong;
+    p.genTT = std::min(T, 512);
+    p.genR = 512 / p.genTT;
+    p.genTT2 = (L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
+    p.fuseAgents = p.genTT2 > 0 && p.genTT2 <= 256 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS));
+    if (p.fuseAgents) {
+        // one launch for all agents pays while its fixed cost matters and every storage block is resident from
+        // the start (3 blocks of 256 per CU at the storage code's register count); see k_agents
+        const int ng = 256 / p.stoLPS;
+        const int sch = (std::max(ng, (S + 2047) / 2048) + ng - 1) / ng * ng;
+        const long long sto_blocks = (S + sch - 1) / sch + N - 1;
+        if (sto_blocks > 3 * 256 || (long long)G * T > (8ll << 20)) p.fuseAgents = false;
+    }
+    p.genR2 = p.genTT2 ? (p.fuseAgents ? 256 : 512) / p.genTT2 : 0;
+    // networks: generators and storages in one launch (k_net_agents) unless the storages run on a stream of their own
+    p.genTT256 = std::max(1, std::min((std::min(T, 512) + 1) / 2, 256 / p.genR));
+    p.fuseNet = L > 0 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS)) &&
+                p.genR * p.genTT256 <= 256;          // (T = 1: the 512-thread tiling has more agent lanes than such a block has threads)
+    // One-launch iterations (kernels_agents.hip, "the tail of the iteration inside the x-update launch"): the fixed-point sums need
+    // 8 fraction bits of the injection and a non-negative exponent of the cost (64 bits = sign + 53 value bits + the 10-bit arrival count)
+    const bool pairs = p.genTT2 > 0 && (S == 0 || p.useWarm) && G + S > 0;       // pair kernels / k_agents / k_sto
+    p.tail = N == 1 && L == 0 && pairs && sh.ki >= 8 && sh.kc >= 0 &&
+             !(flags & (DOPF_F_NO_TAIL_FUSE | DOPF_F_OVERLAP_AGENTS));          // (two streams: the storage launch does not follow the generators')
+
+    // work items
+    const int R = p.genTT2 ? p.genR2 : p.genR;
+    // ~2048 blocks fill the chip several times over; in the fused launch the generator blocks share the wave slots with
+    // the storage blocks and ~1536 somewhat larger ones come out ahead (measured on config2: 25.7 -> 24.0 us)
+    // (with lines ~1024 blocks: the 118-node share 93.8 -> 87.3 us per iteration, config3 at full size 204 -> 203)
+    // (networks, one launch for all agents: the generator blocks pass through the ~230 wave slots the storage blocks leave
+    // free at that kernel's register count — ~512 larger ones: the 118-node share 51.6 -> 49.5 us per iteration)
+    int target_items = p.fuseAgents ? 1536 : (L > 0 ? ((p.fuseNet && !(flags & DOPF_F_NET_SMALL_ITEMS)) ? 512 : 1024) : 2048);
+    if (const char *e = exp_env("DOPF_GEN_TARGET_ITEMS")) target_items = std::max(1, atoi(e));     // (experiments)
+    // streaming generator blocks (fused launch, one node): an item is ONE batch of loads, <= kGenStreamRows rows per lane
+    const bool stream = p.fuseAgents && N == 1;
+    if (stream) target_items = std::max(target_items, (G + kGenStreamRows * R - 1) / (kGenStreamRows * R));
+    int chunk = std::max(R, (G + target_items - 1) / target_items);
+    chunk = (chunk + R - 1) / R * R;
+    if (stream) chunk = std::min(chunk, kGenStreamRows * R);
+    p.genItem = chunk;
+    // (on short blocks the skip test costs more than the rows it saves: measured on config1/config2)
+    p.genSkip = (p.genTT2 > 0 && chunk >= 8 * R && !(flags & DOPF_F_NO_ROW_SKIP)) ? 1 : 0;
+    const int NG = S > 0 ? 256 / p.stoLPS : 1;
+    int sto_target = 2048;
+    const char *sto_env = exp_env("DOPF_STO_TARGET_ITEMS");
+    if (sto_env) sto_target = std::max(1, atoi(sto_env));     // (experiments)
+    int schunk = std::max(NG, (S + sto_target - 1) / sto_target);
+    schunk = (schunk + NG - 1) / NG * NG;
+    // Big copper plates (the storage solve is a launch of its own: config4): as many passes per block as make the launch ONE
+    // resident round — 3 blocks of 256 threads per CU at the storage code's register count — instead of several rounds of
+    // shorter blocks (the blocks' fixed cost — entry, constants, the block's sums — is paid per block, and a round's last
+    // blocks leave wave slots idle): config4 1 421 items of 2 passes -> 711 of 4: 78.7 -> 76.8 us per iteration. Only when that
+    // round is well filled (a half-empty round of long blocks loses: 569 blocks of 5 passes 84.3 us).
+    if (!p.fuseAgents && L == 0 && N == 1 && S > 0 && !sto_env) {
+        const int slots = 3 * (cus > 0 ? cus : 256) - 8, units = (S + NG - 1) / NG;
+        const int passes = (units + slots - 1) / slots;
+        if (passes >= 2 && (units + passes - 1) / passes >= (slots * 4) / 5) schunk = std::max(schunk, passes * NG);
+    }
+    if (p.stoLong) schunk = 1;         // the long body: one block per storage
+    p.stoItem = schunk;
+    p.nGenItems = count_items(sh.gen_at, chunk);
+    p.nStoItems = count_items(sh.sto_at, schunk);
+    if (p.fuseAgents && N == 1 && !p.genSkip && chunk <= kGenStreamRows * p.genR2) {
+        // as many generator blocks as find a wave slot next to the storage blocks (3 blocks of 256 per CU at the fused
+        // kernel's register count): all resident from the start; at least a quarter of the chip
+        int nb = 3 * 256 - p.nStoItems - (p.tail ? 1 : 0);        // (tail in the launch: one slot for the tail block)
+        if (const char *e = exp_env("DOPF_GEN_BLOCKS")) nb = atoi(e);          // (experiments)
+        p.genBlocks = std::min(p.nGenItems, std::max(nb, 192));
+    }
+    if ((p.nGenItems + p.nStoItems) / kAccRep + 2 > 1000) p.tail = false;     // (the 10-bit arrival count of a replica slot)
+    {   // several iterations per launch: every block of the fused launch must be resident at once — 3 blocks of 256 threads per CU at
+        // the kernel's register count, as many CUs as this device has (a grid that does not fit would time out, not hang)
+        const bool full = T == p.stoLPS * p.stoNCH && p.stoLPS <= 32;
+        p.persist = (flags & DOPF_F_PERSIST) && p.tail && p.fuseAgents && p.genBlocks > 0 && !p.genSkip && p.stoLean && full && S > 0 &&
+                    p.nStoItems + p.genBlocks + 1 <= 3 * cus;
+    }
+    if (L > 0) {        // rows of the transposed partial sums per timestep (DevView::part_T): each XCD's rows padded to 16
+        int cnt[8] = {};
+        for (int i = 0; i < p.nGenItems; ++i) ++cnt[gen_row_xcd(p, i)];
+        for (int k = 0; k < p.nStoItems; ++k) cnt[k % 8] += 2;
+        for (int x = 0; x < 8; ++x) p.rowsT += (cnt[x] + 15) / 16 * 16;
+    }
+
+    // the consensus step
+    const size_t NT = (size_t)N * T, LT = (size_t)L * T, n1 = std::max(NT, LT);
+    if (p.wideNet) p.consensus = Consensus::Wide;
+    else if (n1 <= kSmallConsensus) p.consensus = Consensus::Small;
+    else if (L > 0 && L <= 256 && N <= 256) p.consensus = Consensus::T1024;
+    else if ((size_t)std::max(N, 3 * L) * sizeof(double) <= 48 * 1024) p.consensus = Consensus::DualT;
+    else p.consensus = Consensus::Generic;
+    p.sliceDual = p.consensus == Consensus::Small && NT <= 256;       // k_dual_price_small: 8 chunks of 32 entries
+    if (p.consensus == Consensus::T1024) {
+        // networks whose dual step is the one-launch kernel: it builds the tables too, with as many waves as find LDS scratch
+        // (<= 8) next to its own ~30 KB
+        const size_t per_wave = (4 * (size_t)(2 * L) + 1) * sizeof(double), own = 25 * 1024 + (4 * (size_t)N + 3 * (size_t)L) * sizeof(double);
+        p.tablesInDual = (int)std::min<size_t>(8, (128 * 1024 - std::min<size_t>(own, 128 * 1024)) / per_wave);
+        // the same kernel forms the slack sums of its timestep (see DevView::slackInDual); DOPF_F_NO_TAIL_FUSE keeps the
+        // k_reduce launch (the chain a sharded context runs: bitwise comparisons against it)
+        p.slackDual = !(flags & DOPF_F_NO_TAIL_FUSE);
+    }
+    // ... and, while no line is flagged, the node sums too (the quiet chain: no k_slack launch; DevView::quiet, dopf_iterate)
+    // (up to 32 rows per node: one batch of the eight lanes' four loads. configs[3] at full size has 25 and is where the gain
+    // ends — the node sums cost the dual kernel what k_slack and its boundary cost, 119.3 us per iteration either way)
+    p.quiet = p.slackDual && !(flags & (DOPF_F_KEEP_DELTAS | DOPF_F_NO_QUIET)) && quiet_rows_fit(p.rowsT);
+    // the same chain on a peer exchange (k_slack stays: its node sums are what is exchanged): a function of the problem's shape and
+    // the flags only — every rank decides alike
+    p.commQuiet = p.slackDual && !(flags & (DOPF_F_KEEP_DELTAS | DOPF_F_NO_QUIET));
+
+    // every launch family has kernels for a prefix of kStoPairs (kernels_agents.hip: with_sto_pair)
+    if (S > 0 && !p.stoLong) {
+        int at = 0;
+        while (at < kAllPairs && !(kStoPairs[at][0] == p.stoLPS && kStoPairs[at][1] == p.stoNCH)) ++at;
+        if (at >= (p.persist ? kPersistPairs : (p.fuseAgents || p.fuseNet) ? kFusedPairs : kAllPairs))
+            p.refusal = "no storage kernel is instantiated for this horizon and chain";
+    }
+    return p;
+}
+
 }  // namespace
 
 namespace dopf {
-
-// single: the single-GPU dopf_iterate path (nothing reads cons between the reduce and the dual step)
-// the quiet chain's dual/price kernel stages every partial row of its timestep in LDS: up to 96 KB of them
-static bool quiet_rows_fit(int rows) { return rows > 0 && (size_t)rows * sizeof(double) <= 96 * 1024; }
-
-static bool slice_dual(const DevView &v, bool single)
-{
-    if (v.wideNet) return false;           // (the wide chain's reduce adds every node's slices itself)
-    const size_t NT = (size_t)v.N * v.T, LT = (size_t)v.L * v.T;
-    return single && std::max(NT, LT) <= kSmallConsensus && NT <= 256;     // k_dual_price_small: 8 chunks of 32 entries
-}
-
-// the whole tail of the iteration rides in the x-update launch (k_agents / k_sto / the generator kernel): true single-GPU chain only
-static bool tail_fused(const dopf_ctx *c, bool single)
-{
-    // no communicator, or a peer exchange that lives inside the tail block (copper plates; set up by dopf_xchg_init)
-    return single && c->v.tailDev != nullptr && (c->comm == nullptr || c->tail_xchg);
-}
-
-// comm_quiet: a context on a peer exchange, networks whose dual step is the one-launch kernel, no line flagged at the last look
-// (dopf_iterate): the single-GPU three-launch chain with the exchange of the node sums between k_slack and the dual/price
-// kernel — no k_reduce launch (DevView::slackGlobal)
-void enqueue_local(dopf_ctx *c, bool single, bool quiet, bool comm_quiet)
-{
-    DevView v = c->v;
-    v.sliceDual = slice_dual(v, single) ? 1 : 0;
-    v.tail = tail_fused(c, single) ? v.tailDev : nullptr;
-    v.slackInDual = (single || comm_quiet) && v.slackDualOk;
-    v.slackGlobal = comm_quiet ? 1 : 0;
-    v.quiet = single && v.slackInDual && quiet;
-    launch_tables(v, c->main);
-    const bool fork = v.nGenItems > 0 && v.nStoItems > 0 && (c->q.flags & DOPF_F_OVERLAP_AGENTS);
-    if (v.fuseAgents) {
-        launch_agents_fused(v, c->lc, c->main);
-    } else if (v.fuseNet) {
-        launch_net_agents(v, c->lc, c->main);
-    } else if (fork) {
-        hipEventRecord(c->evFork, c->main);
-        hipStreamWaitEvent(c->side, c->evFork, 0);
-        launch_sto_update(v, c->lc, c->side);
-        hipEventRecord(c->evJoin, c->side);
-        launch_gen_update(v, c->main);
-        hipStreamWaitEvent(c->main, c->evJoin, 0);
-    } else {
-        launch_gen_update(v, c->main);
-        launch_sto_update(v, c->lc, c->main);
-    }
-    if (v.tail) return;                    // sums, dual step and stop test happened in the launch above
-    if (!v.quiet) launch_slack(v, c->main);
-    if (!v.slackInDual) launch_reduce(v, c->main);
-}
-
-void enqueue_apply(dopf_ctx *c, bool single, const XchgView *xd, bool quiet, bool comm_quiet)
-{
-    if (tail_fused(c, single)) return;
-    DevView v = c->v;
-    v.sliceDual = slice_dual(v, single) ? 1 : 0;
-    v.slackInDual = (single || comm_quiet) && v.slackDualOk;
-    v.slackGlobal = comm_quiet ? 1 : 0;
-    v.quiet = single && v.slackInDual && quiet;
-    launch_dual(v, c->main, xd);
-}
 
 void drop_graphs(dopf_ctx *c)
 {
@@ -207,35 +302,124 @@ int read_status(dopf_ctx *c)
 
 namespace {
 
-// one iteration of the chain on the context's stream; a sharded context (dopf_comm_init) puts the all-reduce
-// of the consensus buffer between the local sums and the dual step
-int enqueue_iteration(dopf_ctx *c, bool quiet = false)
+// The per-call part of the chain, from the plan, the communicator's state and whether the quiet chain runs (quiet: quiet_allowed
+// and no line flagged at the last look). outside: dopf_local_update / dopf_apply_consensus, iterations driven from outside.
+struct Step {
+    DevView v;                  // the context's view with the per-launch fields: sliceDual, tail, slackInDual, slackGlobal, quiet
+    bool like_single;           // the single-GPU chain: no communicator, or a peer exchange inside a kernel of that chain
+    const XchgView *xd;         // copper plate + peer exchange: the one-block dual kernel (or the tail block) exchanges the vector
+    bool comm_quiet;            // networks on a peer exchange, no line flagged: k_slack's node sums are exchanged, the dual/price
+                                // kernel forms the slack sums behind the exchange — no k_reduce (DevView::slackGlobal)
+};
+
+Step make_step(const dopf_ctx *c, bool quiet, bool outside = false)
 {
-    const bool single = c->comm == nullptr;
-    // copper plate + peer exchange: the one-block dual kernel exchanges the vector itself — the single-GPU chain, no extra launch
-    const XchgView *xd = comm_xchg(c);
-    if (xd && !(c->v.L == 0 && slice_dual(c->v, true)) && !c->tail_xchg) xd = nullptr;
-    const bool like_single = single || xd != nullptr;        // (tail_xchg: the launch's tail block exchanges; nothing else is launched)
-    // networks on a peer exchange while no line is flagged: k_slack's node sums are exchanged, the slack sums are formed behind
-    // the exchange by the dual/price kernel — three launches + the exchange (DevView::slackGlobal)
-    const XchgView *xn = comm_xchg(c);
-    const bool comm_quiet = quiet && !like_single && xn != nullptr && c->comm_quiet_ok;
-    enqueue_local(c, like_single, quiet && single, comm_quiet);
-    if (comm_quiet) launch_xchg(c->v, *xn, c->main, true);
-    else if (!like_single) { const int rc = comm_enqueue_allreduce(c); if (rc) return rc; }
-    enqueue_apply(c, like_single, xd, quiet && single, comm_quiet);
+    const Plan &p = c->plan;
+    const bool single = c->comm == nullptr && !outside;
+    const XchgView *x = outside ? nullptr : comm_xchg(c);
+    Step st{};
+    st.xd = x && ((c->v.L == 0 && p.sliceDual) || c->tail_xchg) ? x : nullptr;
+    st.like_single = single || st.xd != nullptr;
+    st.comm_quiet = quiet && !st.like_single && x != nullptr && p.commQuiet;
+    st.v = c->v;
+    DevView &v = st.v;
+    v.sliceDual = st.like_single && p.sliceDual;
+    v.tail = st.like_single && c->v.tailDev && (c->comm == nullptr || c->tail_xchg) ? c->v.tailDev : nullptr;
+    v.slackInDual = (st.like_single || st.comm_quiet) && p.slackDual;
+    v.slackGlobal = st.comm_quiet ? 1 : 0;
+    v.quiet = single && v.slackInDual && quiet;
+    return st;
+}
+
+// the quiet chain may run now: the plan allows it and, on a communicator, a peer exchange serves it (not the tail block's)
+bool quiet_allowed(const dopf_ctx *c)
+{
+    return c->comm ? c->plan.commQuiet && comm_xchg(c) != nullptr && !c->tail_xchg : c->plan.quiet;
+}
+
+// after a status read: a quiet chain that parked itself (its dual step flagged a line; the iterations behind it were no-ops) is
+// released, and *parked says so; otherwise, unless halted, c->quiet records "no line flagged". (That record tests the plan only,
+// not the exchange: quiet_allowed tests the exchange when the next chain is picked, and dopf_debug_quiet reports the record.)
+int settle_quiet(dopf_ctx *c, bool *parked)
+{
+    *parked = c->host_st.halt == 2;
+    if (*parked) {
+        HIPCHK(c, hipMemsetAsync(&c->v.st->halt, 0, sizeof(int), c->main));
+        c->host_st.halt = 0;
+        c->quiet = false;
+        ++c->quiet_parked;
+    } else if (!c->host_st.halt) {
+        c->quiet = (c->comm ? c->plan.commQuiet : c->plan.quiet) && c->host_st.walk_last == 0;
+    }
+    return DOPF_OK;
+}
+
+// dopf_iterate_timed's events between the stages of an iteration, E_N per iteration
+enum { E_T0, E_T1, E_G0, E_G1, E_S0, E_S1, E_K0, E_K1, E_R1, E_D1, E_X0, E_X1, E_N };
+
+void enqueue_local(dopf_ctx *c, const Step &st, const hipEvent_t *ev = nullptr)
+{
+    const DevView &v = st.v;
+    const Plan &p = c->plan;
+    auto mark = [&](int k, hipStream_t s) { if (ev) hipEventRecord(ev[k], s); };
+    mark(E_T0, c->main);
+    launch_tables(v, p, c->main);
+    mark(E_T1, c->main);
+    const bool fork = v.nGenItems > 0 && v.nStoItems > 0 && (c->q.flags & DOPF_F_OVERLAP_AGENTS);     // (no fused launch then)
+    if (fork) {
+        hipEventRecord(c->evFork, c->main);
+        hipStreamWaitEvent(c->side, c->evFork, 0);
+        mark(E_S0, c->side);
+        launch_sto_update(v, p, c->side);
+        mark(E_S1, c->side);
+        hipEventRecord(c->evJoin, c->side);
+    }
+    mark(E_G0, c->main);
+    if (p.fuseAgents) launch_agents_fused(v, p, c->main);
+    else if (p.fuseNet) launch_net_agents(v, p, c->main);
+    else launch_gen_update(v, c->main);
+    mark(E_G1, c->main);
+    if (fork) {
+        hipStreamWaitEvent(c->main, c->evJoin, 0);
+    } else {
+        mark(E_S0, c->main);
+        if (!p.fuseAgents && !p.fuseNet) launch_sto_update(v, p, c->main);
+        mark(E_S1, c->main);
+    }
+    mark(E_K0, c->main);                    // (v.tail: sums, dual step and stop test happened in the launch above)
+    if (!v.tail && !v.quiet) launch_slack(v, c->main);
+    mark(E_K1, c->main);
+    if (!v.tail && !v.slackInDual) launch_reduce(v, p, c->main);
+    mark(E_R1, c->main);
+}
+
+void enqueue_apply(dopf_ctx *c, const Step &st, const hipEvent_t *ev = nullptr)
+{
+    if (!st.v.tail) launch_dual(st.v, c->plan, c->main, st.xd);
+    if (ev) for (int k : {E_D1, E_X0, E_X1}) hipEventRecord(ev[k], c->main);
+}
+
+// one iteration of the chain on the context's stream; a sharded context (dopf_comm_init) puts the all-reduce
+// of the consensus buffer between the local sums and the dual step. ev: dopf_iterate_timed's events for this iteration.
+int enqueue_iteration(dopf_ctx *c, bool quiet = false, const hipEvent_t *ev = nullptr)
+{
+    const Step st = make_step(c, quiet);
+    enqueue_local(c, st, ev);
+    if (st.comm_quiet) launch_xchg(c->v, *comm_xchg(c), c->main, true);
+    else if (!st.like_single) { const int rc = comm_enqueue_allreduce(c); if (rc) return rc; }
+    enqueue_apply(c, st, ev);
     return DOPF_OK;
 }
 
 // several iterations in one launch (agents_persist.h): the single-GPU one-launch copper-plate chain only
-bool persist_on(const dopf_ctx *c) { return c->v.persistOk && c->comm == nullptr && c->v.tailDev != nullptr; }
+bool persist_on(const dopf_ctx *c) { return c->plan.persist && c->comm == nullptr; }
 
 void enqueue_persist(dopf_ctx *c, int iters)
 {
     DevView v = c->v;
     v.tail = v.tailDev;
     v.persistIters = iters;
-    launch_agents_persist(v, c->lc, c->main);
+    launch_agents_persist(v, c->plan, c->main);
 }
 
 int build_graph(dopf_ctx *c, int iters, hipGraphExec_t *out, bool quiet = false)
@@ -304,21 +488,13 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     for (int s = 0; s < p->S; ++s)
         if (p->sto_node[s] < 0 || p->sto_node[s] >= p->N) return fail(nullptr, DOPF_E_INVALID, "sto_node[%d] out of range", s);
     if ((int64_t)p->G * p->T > (int64_t)1 << 40) return fail(nullptr, DOPF_E_INVALID, "problem too large");
-    Launch lc{};
-    if (p->S > 0 && !sto_config_supported(p->T, &lc)) {
-        if (!(q->flags & (DOPF_F_LONG_HORIZON | DOPF_F_DEBUG_LONG_STO)))
-            return fail(nullptr, DOPF_E_UNSUPPORTED, "storage kernel supports T <= 512 (got %d); longer horizons need DOPF_F_LONG_HORIZON", p->T);
-        lc.stoLong = 1;
-    }
-    if (p->S > 0 && (q->flags & DOPF_F_DEBUG_LONG_STO)) lc.stoLong = 1;
-    if (lc.stoLong) { lc.stoLPS = 64; lc.stoNCH = 8; }         // (not read by the long body; keeps the one-wave paths' choices off)
-    if (2 * p->L > 4096) {                  // k_tables: 4 * 2L doubles of LDS
-        if (!(q->flags & (DOPF_F_WIDE_NETWORK | DOPF_F_DEBUG_WIDE_NET)))
-            return fail(nullptr, DOPF_E_UNSUPPORTED, "table kernel supports L <= 2048 (got %d); wider networks need DOPF_F_WIDE_NETWORK", p->L);
-        lc.wideNet = 1;
-    }
-    if (p->L > 0 && (q->flags & DOPF_F_DEBUG_WIDE_NET)) lc.wideNet = 1;
-    if (lc.wideNet) {
+    Plan probe{};
+    if (p->S > 0 && !sto_config_supported(p->T, &probe) && !(q->flags & (DOPF_F_LONG_HORIZON | DOPF_F_DEBUG_LONG_STO)))
+        return fail(nullptr, DOPF_E_UNSUPPORTED, "storage kernel supports T <= 512 (got %d); longer horizons need DOPF_F_LONG_HORIZON", p->T);
+    if (2 * p->L > 4096 && !(q->flags & (DOPF_F_WIDE_NETWORK | DOPF_F_DEBUG_WIDE_NET)))
+        return fail(nullptr, DOPF_E_UNSUPPORTED, "table kernel supports L <= 2048 (got %d); wider networks need DOPF_F_WIDE_NETWORK", p->L);
+    const bool wide = wide_chain(p->L, q->flags);
+    if (wide) {
         // the kernels index the PTDF (l + L*n) and the line state (l + L*t) in 32-bit ints (net_wide.h, k_slack, line_term)
         if ((int64_t)p->L * p->N >= ((int64_t)1 << 31) || (int64_t)p->L * p->T >= ((int64_t)1 << 31) || (int64_t)p->L >= ((int64_t)1 << 29))
             return fail(nullptr, DOPF_E_UNSUPPORTED, "wide chain needs L*N and L*T below 2^31 (L=%d N=%d T=%d)", p->L, p->N, p->T);
@@ -337,13 +513,12 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     if (!c) return fail(nullptr, DOPF_E_NOMEM, "out of host memory");
     c->device = dev;
     c->q = *q;
-    c->lc = lc;
     DeviceGuard guard(dev);
     int rc = DOPF_OK;
     auto bail = [&](int code) { strncpy(g_create_err, c->err, 511); dopf_destroy(c); return code; };
 #define TRY(x) do { rc = (x); if (rc) return bail(rc); } while (0)
 #define HIPTRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(c, DOPF_E_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); return bail(DOPF_E_DEVICE); } } while (0)
-    if (lc.wideNet) {
+    if (wide) {
         // the wide chain keeps the worst-case table layout: tb_beta, tb_psi 2L, tb_slope 2L + 1 doubles, psi0 and m per
         // (n,t), and the slack partials part_U / part_K L doubles each per (n,t). Checked before anything is allocated or launched.
         const unsigned long long nt = (unsigned long long)p->N * p->T, l2 = 2ull * p->L;
@@ -378,7 +553,6 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     v.max_iters = q->max_iters;
     v.rootCap = (q->flags & DOPF_F_DEBUG_ROOT_CAP) ? 2 : 80;
     v.keepDeltas = (q->flags & DOPF_F_KEEP_DELTAS) ? 1 : 0;
-    v.wideNet = lc.wideNet;
     v.debugLeave = (q->flags & DOPF_F_DEBUG_LEAVE) ? 1 : 0;
     const int A = q->n_agents_global > 0 ? q->n_agents_global : G + S;
     v.invA = A > 0 ? 1.0 / (double)A : 0.0;
@@ -387,33 +561,6 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         const double a0 = v.w_prox + v.gamma;
         v.cp_ia = 1.0 / a0; v.cp_idet = 1.0 / (a0 * a0 - v.gamma * v.gamma); v.cp_s2 = 2.0 / (a0 + v.gamma);
     }
-    v.use_warm = (S > 0 && lc.stoNCH <= 3 && !(q->flags & DOPF_F_NO_WARM_START)) ? 1 : 0;     // (the long body: NCH 8, off)
-    // The lean active-set body (sto_lean.h): 32-bit element offsets; on a network only where the storage blocks outnumber the
-    // chip's resident slots several times — its gain is instruction count, and a grid of one resident round is bound by one
-    // block's latency chain, which is no shorter (configs[3]: 114 us against 120 at 100 k agents; its 12.5 k share 43.3 against 41.1).
-    v.stoLean = ((q->flags & DOPF_F_STO_GENERAL) || (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
-                 (L > 0 && (long long)S * lc.stoLPS / 256 < 1024)) ? 0 : 1;
-    if (lc.stoLong) v.stoLean = 0;
-    v.genTT = std::min(T, 512);
-    v.genR = 512 / v.genTT;
-    v.genTT2 = (L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
-    v.fuseAgents = (v.genTT2 > 0 && v.genTT2 <= 256 && G > 0 && S > 0 && v.use_warm &&
-                    !(q->flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS))) ? 1 : 0;
-    if (v.fuseAgents) {
-        // one launch for all agents pays while its fixed cost matters and every storage block is resident from
-        // the start (3 blocks of 256 per CU at the storage code's register count); see k_agents
-        const int ng = 256 / lc.stoLPS;
-        const int sch = (std::max(ng, (S + 2047) / 2048) + ng - 1) / ng * ng;
-        const long long sto_blocks = (S + sch - 1) / sch + N - 1;
-        if (sto_blocks > 3 * 256 || (long long)G * T > (8ll << 20)) v.fuseAgents = 0;
-    }
-    v.genR2 = v.genTT2 ? (v.fuseAgents ? 256 : 512) / v.genTT2 : 0;
-    v.coldInWarm = (L > 0 && v.use_warm && !exp_env("DOPF_SPLIT_COLD")) ? 1 : 0;
-    // networks: generators and storages in one launch (k_net_agents) unless the storages run on a stream of their own
-    v.genTT256 = std::max(1, std::min((std::min(T, 512) + 1) / 2, 256 / v.genR));
-    v.fuseNet = (L > 0 && G > 0 && S > 0 && v.coldInWarm && !(c->q.flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS)) &&
-                 v.genR * v.genTT256 <= 256 &&          // (T = 1: the 512-thread tiling has more agent lanes than such a block has threads)
-                 !exp_env("DOPF_NO_NET_FUSE")) ? 1 : 0;
 
     // sort agents by node (stable), remember the permutation
     c->gen_perm.resize(G);
@@ -433,70 +580,38 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     for (int i = 0; i < G; ++i) if (!(gpm[i] >= 0)) { fail(c, DOPF_E_INVALID, "negative generator capacity"); return bail(DOPF_E_INVALID); }
     for (int i = 0; i < S; ++i) if (!(spm[i] >= 0) || !(sem[i] >= 0)) { fail(c, DOPF_E_INVALID, "negative storage capacity"); return bail(DOPF_E_INVALID); }
 
+    // the chain
+    Shape sh{N, L, T, G, S, std::vector<int>(N, 0), std::vector<int>(N, 0), -1, -1};
+    for (int i = 0; i < G; ++i) ++sh.gen_at[gnode[i]];
+    for (int i = 0; i < S; ++i) ++sh.sto_at[snode[i]];
     TailView tvh{};
-    bool tail_ok = false;
     {
-        // One-launch iterations (kernels_agents.hip, "the tail of the iteration inside the x-update launch"): fixed-point scales
-        // from the problem's bounds — |sum of net injections| <= sum of pmax (a storage's D - C lies in [-pmax, pmax]),
-        // |cost| <= T * sum |mc| pmax (storages: 2 pmax) — so that no accumulator can overflow
-        // (64 bits = sign + 53 value bits + the 10-bit arrival count).
+        // One-launch iterations: fixed-point scales from the problem's bounds — |sum of net injections| <= sum of pmax (a storage's
+        // D - C lies in [-pmax, pmax]), |cost| <= T * sum |mc| pmax (storages: 2 pmax) — so that no accumulator can overflow
         long double bi = 1.0L, bc = 1.0L;
         for (int i = 0; i < G; ++i) { bi += gpm[i]; bc += (long double)T * std::fabs(gmc[i]) * gpm[i]; }
         for (int i = 0; i < S; ++i) { bi += spm[i]; bc += (long double)T * std::fabs(smc[i]) * 2.0 * spm[i]; }
-        const bool fin = std::isfinite((double)bi) && std::isfinite((double)bc);
-        const int ki = fin ? 52 - (int)std::ceil(std::log2((double)bi)) : -1, kc = fin ? 52 - (int)std::ceil(std::log2((double)bc)) : -1;
-        const bool chain = v.genTT2 > 0 && (S == 0 || v.use_warm) && G + S > 0;       // pair kernels / k_agents / k_sto
-        tail_ok = (N == 1 && L == 0 && chain && ki >= 8 && kc >= 0 &&
-                    !(q->flags & (DOPF_F_NO_TAIL_FUSE | DOPF_F_OVERLAP_AGENTS)) &&       // (two streams: the storage launch does not follow the generators')
-                    !exp_env("DOPF_NO_TAIL_FUSE")) ? 1 : 0;
-        tvh.accStride = (T + 1 + 15) / 16 * 16;                   // replicas on 128-byte lines of their own
-        tvh.scaleInj = std::ldexp(1.0, std::max(0, std::min(ki, 60))); tvh.invInj = 1.0 / tvh.scaleInj;
-        tvh.scaleCost = std::ldexp(1.0, std::max(0, std::min(kc, 60))); tvh.invCost = 1.0 / tvh.scaleCost;
-    }
-    std::vector<Item> gitems, sitems;
-    int max_node_rows = 1;
-    std::vector<int> ngb, nsb, ngib, nsib, row_of_pos, pos_of_row;
-    {
-        const int R = v.genTT2 ? v.genR2 : v.genR;
-        // ~2048 blocks fill the chip several times over; in the fused launch the generator blocks share the wave slots with
-        // the storage blocks and ~1536 somewhat larger ones come out ahead (measured on config2: 25.7 -> 24.0 us)
-        // (with lines ~1024 blocks: the 118-node share 93.8 -> 87.3 us per iteration, config3 at full size 204 -> 203)
-        // (networks, one launch for all agents: the generator blocks pass through the ~230 wave slots the storage blocks leave
-        // free at that kernel's register count — ~512 larger ones: the 118-node share 51.6 -> 49.5 us per iteration)
-        int target_items = v.fuseAgents ? 1536 : (L > 0 ? ((v.fuseNet && !(q->flags & DOPF_F_NET_SMALL_ITEMS)) ? 512 : 1024) : 2048);
-        if (const char *e = exp_env("DOPF_GEN_TARGET_ITEMS")) target_items = std::max(1, atoi(e));     // (experiments)
-        // streaming generator blocks (fused launch, one node): an item is ONE batch of loads, <= kGenStreamRows rows per lane
-        const bool stream = v.fuseAgents && N == 1 && !exp_env("DOPF_NO_GEN_STREAM");
-        if (stream) target_items = std::max(target_items, (G + kGenStreamRows * R - 1) / (kGenStreamRows * R));
-        int chunk = std::max(R, (G + target_items - 1) / target_items);
-        chunk = (chunk + R - 1) / R * R;
-        if (stream) chunk = std::min(chunk, kGenStreamRows * R);
-        make_items(gnode, N, chunk, gitems, ngb, ngib);
-        v.genChunk = N == 1 ? chunk : 0;
-        // (on short blocks the skip test costs more than the rows it saves: measured on config1/config2)
-        v.genSkip = (v.genTT2 > 0 && chunk >= 8 * R && !(q->flags & DOPF_F_NO_ROW_SKIP)) ? 1 : 0;
-        const int NG = S > 0 ? 256 / lc.stoLPS : 1;
-        int sto_target = 2048;
-        if (const char *e = exp_env("DOPF_STO_TARGET_ITEMS")) sto_target = std::max(1, atoi(e));     // (experiments)
-        int schunk = std::max(NG, (S + sto_target - 1) / sto_target);
-        schunk = (schunk + NG - 1) / NG * NG;
-        // Big copper plates (the storage solve is a launch of its own: config4): as many passes per block as make the launch ONE
-        // resident round — 3 blocks of 256 threads per CU at the storage code's register count — instead of several rounds of
-        // shorter blocks (the blocks' fixed cost — entry, constants, the block's sums — is paid per block, and a round's last
-        // blocks leave wave slots idle): config4 1 421 items of 2 passes -> 711 of 4: 78.7 -> 76.8 us per iteration. Only when that
-        // round is well filled (a half-empty round of long blocks loses: 569 blocks of 5 passes 84.3 us).
-        if (!v.fuseAgents && L == 0 && N == 1 && S > 0 && !exp_env("DOPF_STO_TARGET_ITEMS")) {
-            int cus = 256;
-            hipDeviceProp_t prop{};
-            if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-            const int slots = 3 * cus - 8, units = (S + NG - 1) / NG;
-            const int passes = (units + slots - 1) / slots;
-            if (passes >= 2 && (units + passes - 1) / passes >= (slots * 4) / 5) schunk = std::max(schunk, passes * NG);
+        if (std::isfinite((double)bi) && std::isfinite((double)bc)) {
+            sh.ki = 52 - (int)std::ceil(std::log2((double)bi));
+            sh.kc = 52 - (int)std::ceil(std::log2((double)bc));
         }
-        if (lc.stoLong) schunk = 1;         // the long body: one block per storage
-        make_items(snode, N, schunk, sitems, nsb, nsib);
-        v.stoChunk = (N == 1 && !exp_env("DOPF_NO_STO_CHUNK")) ? schunk : 0;
+        tvh.accStride = (T + 1 + 15) / 16 * 16;                   // replicas on 128-byte lines of their own
+        tvh.scaleInj = std::ldexp(1.0, std::max(0, std::min(sh.ki, 60))); tvh.invInj = 1.0 / tvh.scaleInj;
+        tvh.scaleCost = std::ldexp(1.0, std::max(0, std::min(sh.kc, 60))); tvh.invCost = 1.0 / tvh.scaleCost;
     }
+    hipDeviceProp_t prop{};
+    const int cus = hipGetDeviceProperties(&prop, c->device) == hipSuccess ? prop.multiProcessorCount : 0;
+    const Plan &pl = c->plan = plan_chain(sh, q->flags, cus);
+    if (pl.refusal) { fail(c, DOPF_E_UNSUPPORTED, "%s (T=%d)", pl.refusal, T); return bail(DOPF_E_UNSUPPORTED); }
+    v.use_warm = pl.useWarm; v.genSkip = pl.genSkip; v.genBlocks = v.genRows = pl.genBlocks; v.tablesInDual = pl.tablesInDual;
+    v.genTT = pl.genTT; v.genR = pl.genR; v.genTT2 = pl.genTT2; v.genR2 = pl.genR2; v.genTT256 = pl.genTT256;
+    v.genChunk = N == 1 ? pl.genItem : 0; v.stoChunk = N == 1 ? pl.stoItem : 0;
+
+    // work items and rows
+    std::vector<Item> gitems, sitems;
+    std::vector<int> ngb, nsb, ngib, nsib, row_of_pos, pos_of_row;
+    make_items(gnode, N, pl.genItem, gitems, ngb, ngib);
+    make_items(snode, N, pl.stoItem, sitems, nsb, nsib);
     v.maxNodeAgents = 0;
     for (int n = 0; n < N; ++n) v.maxNodeAgents = std::max(v.maxNodeAgents, (ngb[n + 1] - ngb[n]) + (nsb[n + 1] - nsb[n]));
     v.nGenItems = (int)gitems.size();
@@ -508,7 +623,7 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         std::vector<int> xcd((size_t)v.rowsN, 0), cnt(8, 0), beg(9, 0);
         for (int i = 0; i < v.nGenItems; ++i) {
             gitems[i].row = i + 2 * nsib[gitems[i].node];
-            xcd[(size_t)gitems[i].row] = ((v.fuseNet ? v.nStoItems : 0) + i) % 8;          // (k_net_agents: storage blocks in front)
+            xcd[(size_t)gitems[i].row] = gen_row_xcd(pl, i);
         }
         for (int k = 0; k < v.nStoItems; ++k) {
             sitems[k].row = ngib[sitems[k].node + 1] + 2 * k;
@@ -516,36 +631,18 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         }
         for (int g = 0; g < v.rowsN; ++g) ++cnt[(size_t)xcd[(size_t)g]];
         for (int x = 0; x < 8; ++x) beg[(size_t)x + 1] = beg[(size_t)x] + (cnt[(size_t)x] + 15) / 16 * 16;
-        v.rowsT = beg[8];
+        v.rowsT = beg[8];           // (= pl.rowsT)
         row_of_pos.assign((size_t)std::max(v.rowsT, 1), -1); pos_of_row.assign((size_t)std::max(v.rowsN, 1), 0);
         std::vector<int> fillp(beg.begin(), beg.begin() + 8);
         for (int g = 0; g < v.rowsN; ++g) { const int p_ = fillp[(size_t)xcd[(size_t)g]]++; row_of_pos[(size_t)p_] = g; pos_of_row[(size_t)g] = p_; }
         for (int i = 0; i < v.nGenItems; ++i) gitems[i].row = pos_of_row[(size_t)gitems[i].row];
         for (int k = 0; k < v.nStoItems; ++k) sitems[k].row = pos_of_row[(size_t)sitems[k].row];       // (the warm-start row: the next position)
     }
-    v.genBlocks = 0;
-    if (v.fuseAgents && v.genChunk > 0 && !v.genSkip && v.genChunk <= kGenStreamRows * v.genR2 && !exp_env("DOPF_NO_GEN_STREAM")) {
-        // as many generator blocks as find a wave slot next to the storage blocks (3 blocks of 256 per CU at the fused
-        // kernel's register count): all resident from the start; at least a quarter of the chip
-        int nb = 3 * 256 - v.nStoItems - (tail_ok ? 1 : 0);        // (tail in the launch: one slot for the tail block)
-        if (const char *e = exp_env("DOPF_GEN_BLOCKS")) nb = atoi(e);          // (experiments)
-        v.genBlocks = std::min(v.nGenItems, std::max(nb, 192));
-    }
-    v.genRows = v.genBlocks;
-    {   // several iterations per launch: every block of the fused launch must be resident at once — 3 blocks of 256 threads per CU at
-        // the kernel's register count, as many CUs as this device has (a grid that does not fit would time out, not hang)
-        hipDeviceProp_t prop{};
-        const bool known = hipGetDeviceProperties(&prop, c->device) == hipSuccess;
-        const bool full = T == lc.stoLPS * lc.stoNCH && lc.stoLPS <= 32;
-        v.persistOk = ((q->flags & DOPF_F_PERSIST) && tail_ok && v.fuseAgents && v.genBlocks > 0 && !v.genSkip && v.stoLean && full && S > 0 &&
-                       known && v.nStoItems + v.genBlocks + 1 <= 3 * prop.multiProcessorCount) ? 1 : 0;
-    }
     {
         // level-1 reduce blocks per node: ~16 items per block, at most 64 (and N*RB blocks in total)
         int max_items = 1;
         for (int n = 0; n < N; ++n)      // storage items: scan + warm rows; generators: items, or (one node, streaming) blocks
             max_items = std::max(max_items, (v.genRows > 0 ? v.genRows : ngib[n + 1] - ngib[n]) + 2 * (nsib[n + 1] - nsib[n]));
-        max_node_rows = max_items;
         v.reduceRB = std::max(1, std::min(64, (max_items + 31) / 32));
         // Networks: nodes x timestep chunks already give hundreds of blocks, and more than one block per node means the
         // two-level sum — an agent-scope release (a write-back of the XCD's L2) and a ticket in EVERY block. configs[3] at full
@@ -553,6 +650,14 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         // node walks up to 128 rows (four passes of its 8 x 4 loads in flight) before a second one is worth its ticket.
         if ((long long)N * ((T + 31) / 32) >= 128) v.reduceRB = std::max(1, std::min(64, (max_items + 127) / 128));
     }
+    {   // dynamic LDS of k_dual_price_t1024: q[N] | d[L] | G[L] | S[L] | the rows of its timestep (quiet chain), later the tables'
+        // scratch | sd[N] win[N] na[N]
+        const size_t scratch = (size_t)pl.tablesInDual * (4 * (size_t)v.M2 + 1);
+        v.dualRowsOff = N + 3 * L;
+        v.dualSdOff = v.dualRowsOff + (int)std::max(scratch, (size_t)(quiet_rows_fit(v.rowsT) ? v.rowsN : 0));
+        v.dualLdsBytes = (int)(((size_t)v.dualSdOff + 3 * (size_t)N) * sizeof(double));
+    }
+    HIPTRY(raise_lds_limits(v, pl));
 
     const size_t NT = (size_t)N * T, LT = (size_t)L * T;
     TRY(dev_upload(c, &v.demand, std::vector<double>(p->demand, p->demand + NT)));
@@ -619,50 +724,15 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     TRY(dev_alloc(c, &v.part2, (size_t)N * v.reduceRB * T)); TRY(dev_alloc(c, &v.part2_cost, v.reduceRB));
     TRY(dev_alloc(c, &v.reduce_ticket, (size_t)N * ((T + 31) / 32)));
     TRY(dev_alloc(c, &v.dual_ticket, 1));
-    if ((v.nGenItems + v.nStoItems) / kAccRep + 2 > 1000) tail_ok = false;   // (the 10-bit arrival count of a replica slot)
-    if (tail_ok) {
+    if (pl.tail) {
         TRY(dev_alloc(c, &tvh.acc, (size_t)2 * kAccRep * tvh.accStride));
-        tvh.expect = (v.fuseAgents && v.genBlocks > 0 && !v.genSkip ? v.genBlocks : v.nGenItems) + v.nStoItems;
+        tvh.expect = (pl.fuseAgents && v.genBlocks > 0 && !v.genSkip ? v.genBlocks : v.nGenItems) + v.nStoItems;
         TailView *tvd = nullptr;
         TRY(dev_alloc(c, &tvd, 1, false));
         HIPTRY(hipMemcpy(tvd, &tvh, sizeof tvh, hipMemcpyHostToDevice));
         v.tailDev = tvd;
     }
-    v.splitDual = exp_env("DOPF_SPLIT_DUAL") ? 1 : 0;
-    {
-        // networks whose dual step is the one-launch kernel (k_dual_price_t1024: <= 256 lines and nodes, consensus state beyond the
-        // one-block kernel): it builds the tables too, with as many waves as find LDS scratch (<= 8) next to its own ~30 KB
-        const size_t n1 = std::max(NT, LT);
-        const size_t per_wave = (4 * (size_t)v.M2 + 1) * sizeof(double), own = 25 * 1024 + (4 * (size_t)N + 3 * (size_t)L) * sizeof(double);
-        int tw = 0;
-        if (L > 0 && L <= 256 && N <= 256 && n1 > kSmallConsensus && !v.splitDual && !exp_env("DOPF_TABLES_LAUNCH"))
-            tw = (int)std::min<size_t>(8, (128 * 1024 - std::min<size_t>(own, 128 * 1024)) / per_wave);
-        v.tablesInDual = tw;
-        {   // its dynamic LDS: q[N] | d[L] | G[L] | S[L] | the rows of its timestep (quiet chain), later the tables' scratch | sd[N] win[N] na[N]
-            const size_t scratch = (size_t)tw * (4 * (size_t)v.M2 + 1);
-            v.dualRowsOff = N + 3 * L;
-            v.dualSdOff = v.dualRowsOff + (int)std::max(scratch, (size_t)(quiet_rows_fit(v.rowsT) ? v.rowsN : 0));
-            v.dualLdsBytes = (int)(((size_t)v.dualSdOff + 3 * (size_t)N) * sizeof(double));
-        }
-        // the same kernel forms the slack sums of its timestep (see DevView::slackInDual); DOPF_F_NO_TAIL_FUSE keeps the
-        // k_reduce launch (the chain a sharded context runs: bitwise comparisons against it)
-        v.slackDualOk = L > 0 && L <= 256 && N <= 256 && n1 > kSmallConsensus && !v.splitDual && !(q->flags & DOPF_F_NO_TAIL_FUSE) &&
-                        !exp_env("DOPF_REDUCE_LAUNCH");
-        // ... and, while no line is flagged, the node sums too (the quiet chain: no k_slack launch; DevView::quiet, dopf_iterate)
-        // (up to 32 rows per node: one batch of the eight lanes' four loads. configs[3] at full size has 25 and is where the gain
-        // ends — the node sums cost the dual kernel what k_slack and its boundary cost, 119.3 us per iteration either way)
-        c->quiet_ok = v.slackDualOk && !(q->flags & DOPF_F_KEEP_DELTAS) && quiet_rows_fit(v.rowsT) &&
-                      !(q->flags & DOPF_F_NO_QUIET);
-        // the same chain on a peer exchange (k_slack stays: its node sums are what is exchanged): a function of the problem's shape and
-        // the flags only — every rank decides alike
-        c->comm_quiet_ok = v.slackDualOk && !(q->flags & (DOPF_F_KEEP_DELTAS | DOPF_F_NO_QUIET));
-        if (v.wideNet) {        // the wide chain (net_wide.h): separate launches, no one-launch dual/price kernel, no quiet chain
-            v.tablesInDual = 0;
-            v.slackDualOk = 0;
-            c->quiet_ok = c->comm_quiet_ok = false;
-        }
-    }
-    if (v.wideNet) {
+    if (pl.wideNet) {
         std::vector<double> na(N);
         for (int n = 0; n < N; ++n) na[n] = (double)((ngb[n + 1] - ngb[n]) + (nsb[n + 1] - nsb[n]));
         TRY(dev_upload(c, &v.node_na, na));
@@ -677,7 +747,7 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     st0.res_set = -1;
     HIPTRY(hipMemcpyAsync(v.st, &st0, sizeof st0, hipMemcpyHostToDevice, c->main));
     // "no result yet" state: zeros everywhere, injection = -demand (helpers/results.jl:14-73)
-    launch_derive(v, c->main, false);     // all-zero primal state: the consensus buffer is already zero
+    launch_derive(v, pl, c->main, false);     // all-zero primal state: the consensus buffer is already zero
     HIPTRY(hipGetLastError());
     HIPTRY(hipStreamSynchronize(c->main));
     c->host_st = st0;
@@ -752,7 +822,7 @@ int dopf_iterate(dopf_ctx *c, int32_t n_iters, int32_t *iters_done, int32_t *con
         // the quiet chain (networks, no line flagged at the last look: no k_slack launch) has graphs of its own, built when first used
         // (on a peer exchange: the chain without k_reduce, see enqueue_iteration — every rank takes the same decision from the same
         // replicated status word at the same iteration)
-        bool quiet = c->quiet && (c->comm == nullptr ? c->quiet_ok : (c->comm_quiet_ok && comm_xchg(c) != nullptr && !c->tail_xchg));
+        const bool quiet = c->quiet && quiet_allowed(c);
         if (quiet && !eager && !c->graphs_q_valid) {
             int rc = build_graph(c, 1, &c->graph1q, true);
             if (rc == DOPF_OK) rc = build_graph(c, kMid, &c->graphMq, true);
@@ -774,18 +844,11 @@ int dopf_iterate(dopf_ctx *c, int32_t n_iters, int32_t *iters_done, int32_t *con
         if (timed && left == 0) HIPCHK(c, hipEventRecord(c->evT1, c->main));
         const int rc = read_status(c);
         if (rc) return rc;
-        if (c->host_st.halt == 2) {
-            // the quiet chain parked itself: its last dual step flagged a line, the iterations behind it were no-ops. Release the
-            // device, go back to the chain with k_slack and feed what is left of the slice again.
-            HIPCHK(c, hipMemsetAsync(&c->v.st->halt, 0, sizeof(int), c->main));
-            c->host_st.halt = 0;
-            c->quiet = false;
-            ++c->quiet_parked;
-            left += asked - (c->host_st.iters_total - total_before);
-            continue;
-        }
+        bool parked = false;
+        if (const int rc2 = settle_quiet(c, &parked)) return rc2;
+        // parked: back to the chain with k_slack, and what is left of the slice is fed again
+        if (parked) { left += asked - (c->host_st.iters_total - total_before); continue; }
         if (c->host_st.halt) break;
-        c->quiet = (c->comm == nullptr ? c->quiet_ok : c->comm_quiet_ok) && c->host_st.walk_last == 0;
     }
     c->last_call_ms = -1.0;
     if (timed && left == 0) {
@@ -804,13 +867,8 @@ int dopf_iterate_timed(dopf_ctx *c, int32_t n_iters, dopf_timing *out)
 {
     if (!c || !out || n_iters < 1 || n_iters > 4096) return fail(c, DOPF_E_INVALID, "bad argument");
     DeviceGuard guard(c->device);
-    DevView v = c->v;
     if (c->comm) return fail(c, DOPF_E_INVALID, "dopf_iterate_timed drives the single-GPU chain: not on a context joined to a communicator");
-    v.sliceDual = slice_dual(v, true) ? 1 : 0;
-    v.tail = tail_fused(c, true) ? v.tailDev : nullptr;
-    v.slackInDual = v.slackDualOk;
-    v.quiet = v.slackInDual && c->quiet_ok && c->quiet;        // (the chain dopf_iterate would launch now)
-    enum { E_T0, E_T1, E_G0, E_G1, E_S0, E_S1, E_K0, E_K1, E_R1, E_D1, E_X0, E_X1, E_N };
+    const bool quiet = c->quiet && quiet_allowed(c);          // (the chain dopf_iterate would launch now)
     struct Events {                                     // destroyed on every way out
         std::vector<hipEvent_t> v;
         ~Events() { for (auto e : v) if (e) hipEventDestroy(e); }
@@ -818,44 +876,12 @@ int dopf_iterate_timed(dopf_ctx *c, int32_t n_iters, dopf_timing *out)
     evs.v.assign((size_t)n_iters * E_N, nullptr);
     std::vector<hipEvent_t> &ev = evs.v;
     for (auto &e : ev) HIPCHK(c, hipEventCreate(&e));
-    const bool fork = v.nGenItems > 0 && v.nStoItems > 0 && (c->q.flags & DOPF_F_OVERLAP_AGENTS);
-    for (int i = 0; i < n_iters; ++i) {
-        hipEvent_t *e = &ev[(size_t)i * E_N];
-        hipEventRecord(e[E_T0], c->main);
-        launch_tables(v, c->main);
-        hipEventRecord(e[E_T1], c->main);
-        hipStream_t ss = fork ? c->side : c->main;
-        if (fork) { hipEventRecord(c->evFork, c->main); hipStreamWaitEvent(c->side, c->evFork, 0); }
-        hipEventRecord(e[E_G0], c->main);
-        if (v.fuseAgents) launch_agents_fused(v, c->lc, c->main);
-        else if (v.fuseNet) launch_net_agents(v, c->lc, c->main);
-        else launch_gen_update(v, c->main);
-        hipEventRecord(e[E_G1], c->main);
-        hipEventRecord(e[E_S0], ss);
-        if (!v.fuseAgents && !v.fuseNet) launch_sto_update(v, c->lc, ss);
-        hipEventRecord(e[E_S1], ss);
-        if (fork) { hipEventRecord(c->evJoin, c->side); hipStreamWaitEvent(c->main, c->evJoin, 0); }
-        hipEventRecord(e[E_K0], c->main);
-        if (!v.tail && !v.quiet) launch_slack(v, c->main);
-        hipEventRecord(e[E_K1], c->main);
-        if (!v.tail && !v.slackInDual) launch_reduce(v, c->main);
-        hipEventRecord(e[E_R1], c->main);
-        if (!v.tail) launch_dual(v, c->main);
-        hipEventRecord(e[E_D1], c->main);
-        hipEventRecord(e[E_X0], c->main);
-        hipEventRecord(e[E_X1], c->main);
-    }
+    for (int i = 0; i < n_iters; ++i) (void)enqueue_iteration(c, quiet, &ev[(size_t)i * E_N]);     // (no communicator: nothing to fail)
     HIPCHK(c, hipGetLastError());
     int rc = read_status(c);
     if (rc) return rc;
-    if (c->host_st.halt == 2) {            // the quiet chain parked itself inside the timed iterations (the ones behind were no-ops)
-        HIPCHK(c, hipMemsetAsync(&c->v.st->halt, 0, sizeof(int), c->main));
-        c->host_st.halt = 0;
-        c->quiet = false;
-        ++c->quiet_parked;
-    } else if (!c->host_st.halt) {
-        c->quiet = c->quiet_ok && c->host_st.walk_last == 0;
-    }
+    bool parked = false;
+    if ((rc = settle_quiet(c, &parked))) return rc;
     if (c->side) HIPCHK(c, hipStreamSynchronize(c->side));
     memset(out, 0, sizeof *out);
     auto ms = [&](hipEvent_t a, hipEvent_t b) { float f = 0.f; hipEventElapsedTime(&f, a, b); return (double)f; };
@@ -873,14 +899,17 @@ int dopf_iterate_timed(dopf_ctx *c, int32_t n_iters, dopf_timing *out)
     const double inv = 1.0 / n_iters;
     out->tables_ms *= inv; out->gen_ms *= inv; out->sto_ms *= inv; out->slack_ms *= inv;
     out->reduce_ms *= inv; out->dual_ms *= inv; out->iter_ms *= inv; out->empty_ms *= inv;
+    const Plan &p = c->plan;
+    const Step st = make_step(c, quiet);
+    const DevView &v = st.v;
     out->iters = n_iters;
-    out->agents_fused = v.fuseAgents || v.fuseNet;
+    out->agents_fused = p.fuseAgents || p.fuseNet;
     out->tail_fused = v.tail ? 1 : 0;
     out->slack_in_dual = (!v.tail && v.slackInDual) ? 1 : 0;
     out->quiet = v.quiet ? 1 : 0;
-    out->sto_lean = (v.stoLean && v.S > 0 && v.use_warm) ? 1 : 0;
+    out->sto_lean = (p.stoLean && v.S > 0 && v.use_warm) ? 1 : 0;
     out->persist = persist_on(c) ? 1 : 0;
-    out->sto_long = (c->lc.stoLong && v.S > 0) ? 1 : 0;
+    out->sto_long = (p.stoLong && v.S > 0) ? 1 : 0;
     return DOPF_OK;
 }
 
@@ -889,7 +918,7 @@ int dopf_local_update(dopf_ctx *c)
     if (!c) return DOPF_E_INVALID;
     DeviceGuard guard(c->device);
     c->quiet = false;                      // (iterations driven from outside: the next dopf_iterate looks at the flags before it trusts them)
-    enqueue_local(c, false);
+    enqueue_local(c, make_step(c, false, true));
     HIPCHK(c, hipGetLastError());
     return DOPF_OK;
 }
@@ -899,7 +928,7 @@ int dopf_apply_consensus(dopf_ctx *c)
     if (!c) return DOPF_E_INVALID;
     DeviceGuard guard(c->device);
     c->quiet = false;
-    enqueue_apply(c, false);
+    enqueue_apply(c, make_step(c, false, true));
     HIPCHK(c, hipGetLastError());
     return DOPF_OK;
 }
@@ -1146,7 +1175,7 @@ int dopf_set_state(dopf_ctx *c, const double *P, const double *D, const double *
     st.resbits[0] = st.resbits[1] = st.resbits[2] = 0;
     memset(st.resbits2, 0, sizeof st.resbits2);
     HIPCHK(c, hipMemcpy(v.st, &st, sizeof st, hipMemcpyHostToDevice));
-    launch_derive(v, c->main, true);
+    launch_derive(v, c->plan, c->main, true);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->host_st = st;
@@ -1264,7 +1293,7 @@ int dopf_debug_table(dopf_ctx *c, int32_t n, int32_t t, double *beta, double *ps
 int dopf_wide_net(const dopf_ctx *c, int32_t *out)
 {
     if (!c || !out) return DOPF_E_INVALID;
-    *out = c->v.wideNet ? 1 : 0;
+    *out = c->plan.wideNet ? 1 : 0;
     return DOPF_OK;
 }
 
@@ -1292,7 +1321,7 @@ int dopf_debug_quiet(dopf_ctx *c, int64_t *out3)
 {
     if (!c || !out3) return DOPF_E_INVALID;
     // (a context on a communicator: the chain without k_reduce on a peer exchange, DevView::slackGlobal)
-    out3[0] = (c->comm ? (c->comm_quiet_ok && comm_xchg(c) != nullptr && !c->tail_xchg) : c->quiet_ok) ? 1 : 0;
+    out3[0] = quiet_allowed(c) ? 1 : 0;
     out3[1] = c->quiet ? 1 : 0; out3[2] = (int64_t)c->quiet_parked;
     return DOPF_OK;
 }

@@ -23,8 +23,8 @@
 
 namespace dopf {
 
-// Tuning knobs of the experiments (item counts, block counts, launch splits) are environment variables
-// of builds with -DDOPF_EXPERIMENTS only; the shipped library does not change kernel selection on ambient environment.
+// Sizing knobs of the experiments (item and block counts, the exchange's rendezvous wait) are environment
+// variables of builds with -DDOPF_EXPERIMENTS only; none of them chooses a kernel. plan_chain reads them (and the exchange its own).
 #ifdef DOPF_EXPERIMENTS
 inline const char *exp_env(const char *name) { return getenv(name); }
 #else
@@ -79,7 +79,6 @@ struct DevView {
     int genRows;                    // > 0: (one node) the generators' partial sums are this many rows, one per streaming block, not one per item
     int genBlocks;                  // > 0 (needs genChunk): the fused launch has this many generator blocks, each walking items b, b + genBlocks, ...
     int debugLeave;                 // DOPF_F_DEBUG_LEAVE (tests)
-    int coldInWarm;                 // networks: k_sto_warm calls the scan body itself for what it leaves over (no k_sto_update launch)
     double *part_T;                 // networks (L > 0): the items' partial injection sums TRANSPOSED, [t][row] with rowsT rows per timestep — node by node
     int rowsT;                      // (a node's generator items, then two rows per storage item: scan partial, warm-start partial). The block of the
                                     // dual/price kernel that owns timestep t reads ALL rows of t as one contiguous vector (the quiet chain: no k_slack
@@ -93,7 +92,6 @@ struct DevView {
     int dualLdsBytes;               // scratch) and the vectors behind them start, and its size
     int tablesInDual;               // > 0 (networks on the one-launch dual/price kernel): that kernel builds the breakpoint tables of its
                                     // timestep itself, with this many waves; no k_tables launch
-    int splitDual;                  // (experiments, DOPF_SPLIT_DUAL=1) networks: dual and price steps as two launches
     int stoChunk;                   // > 0: one node, storage item i = storages [i*stoChunk, (i+1)*stoChunk)
     int genChunk;                   // > 0: one node, generator item i = rows [i*genChunk, (i+1)*genChunk) (no item look-up)
     int genSkip;                    // pair kernel with row skipping (blocks sweep >= 8 passes of agents)
@@ -104,7 +102,6 @@ struct DevView {
     int slackInDual;                // per launch (networks on the one-launch dual/price kernel, single-GPU chain): k_slack stores the node
                                     // sums and the cost itself, the dual/price block of timestep t forms the slack sums of its lines from the
                                     // PTDF rows it reads anyway — no k_reduce launch
-    int slackDualOk;                // the problem and the flags allow that
     int slackGlobal;                // per launch (contexts on a peer exchange, no line flagged): the chain of slackInDual with the exchange of
                                     // the node sums between k_slack and the dual/price kernel — that kernel then takes the nodes' injection
                                     // changes from the SUMMED injections (this iteration's minus the previous one's, both replicated) and counts
@@ -112,11 +109,7 @@ struct DevView {
     int quiet;                      // per launch (with slackInDual): the quiet chain — no line is flagged, k_slack is not launched, the dual/price
                                     // kernel forms the node sums too
     int genTT256;                   // networks, fused launch: column tiling of a 256-thread generator block with the same R as genR
-    int fuseNet;                    // networks: generators + storages in one launch (k_net_agents), single-GPU chain
-    int fuseAgents;                 // copper plate, even T: generators + storages in one launch (k_agents, 256-thread blocks)
     int use_warm;                   // storage warm-start kernel runs first; the scan kernel serves its failures
-    int stoLean;                    // copper plates whose horizon fills the lane groups: the lean active-set body (sto_lean.h)
-    int persistOk;                  // DOPF_F_PERSIST and a grid whose blocks are all resident at once: several iterations per launch (agents_persist.h)
     int persistIters;               // per launch: iterations this launch runs
     int max_iters;
     int keepDeltas;                 // DOPF_F_KEEP_DELTAS: dltG / dltS are written for every timestep (diagnostic getters)
@@ -168,8 +161,6 @@ struct DevView {
     int *reduce_ticket;                             // [n]
     double *cons;
     Status *st;
-    int wideNet;                                    // the wide chain (net_wide.h): tables, dual / price steps and line slack sums with LDS
-                                                    // that does not grow with N or L; the one-launch and quiet chains are off
     const double *node_na;                          // wide chain: [n] agents at node n as a number (k_reduce's naL, read from memory)
 };
 
@@ -216,11 +207,34 @@ __device__ __forceinline__ void status_update(const DevView &v, double r0, doubl
     status_update(v, status_load(v), r0, r1, r2);
 }
 
-struct Launch {
-    int stoLPS, stoNCH;
-    int stoLong;                    // the storages run on the long-horizon body (sto_long.h: DOPF_F_LONG_HORIZON beyond T = 512, DOPF_F_DEBUG_LONG_STO)
-    int wideNet;                    // the consensus kernels run on the wide chain (net_wide.h: DOPF_F_WIDE_NETWORK beyond L = 2048, DOPF_F_DEBUG_WIDE_NET)
+// The consensus step (dual update, prices, stop test): k_dual_price_small (state <= kSmallConsensus entries), k_dual_price_t1024
+// (networks, N and L <= 256), k_dual_t + k_price_t (a timestep's vectors in 48 KB of LDS), k_dual + k_price, the wide chain (net_wide.h)
+enum class Consensus : int { Small, T1024, DualT, Generic, Wide };
+
+// The launch chain of a context: every create-time choice of which kernels run, made once by plan_chain
+// (dopf_api.hip). Kernels read the parts they need from DevView; the rest is read by the host's launch functions only.
+struct Plan {
+    const char *refusal;            // non-null: no kernel instantiation serves this problem (DOPF_E_UNSUPPORTED)
+    int stoLPS, stoNCH;             // storage lane group: lanes per storage x timesteps per lane (sto_config_supported)
+    int stoLong;                    // the long-horizon storage body (sto_long.h: DOPF_F_LONG_HORIZON beyond T = 512, DOPF_F_DEBUG_LONG_STO)
+    int wideNet;                    // the wide chain (net_wide.h: DOPF_F_WIDE_NETWORK beyond L = 2048, DOPF_F_DEBUG_WIDE_NET): no one-launch,
+                                    // quiet or tail chain
+    Consensus consensus;
+    bool sliceDual;                 // the one-block dual kernel may add k_reduce's slices itself (DevView::sliceDual)
+    bool useWarm, stoLean;          // storage warm start (DevView::use_warm); the lean active-set body (sto_lean.h)
+    bool fuseAgents, fuseNet;       // generators + storages in one launch: k_agents (copper plate, even T), k_net_agents (networks)
+    bool tail, persist;             // the tail of the iteration in the x-update launch (DevView::tailDev); DOPF_F_PERSIST (agents_persist.h)
+    bool slackDual;                 // the one-launch dual/price kernel may form the slack sums: no k_reduce (DevView::slackInDual)
+    bool quiet, commQuiet;          // the quiet chain may run: single GPU (DevView::quiet), on a peer exchange (DevView::slackGlobal)
+    int genTT, genR, genTT2, genR2, genTT256, genSkip, genBlocks, tablesInDual;     // (DevView)
+    int genItem, stoItem;           // agents per generator / storage work item
+    int nGenItems, nStoItems, rowsT;
 };
+
+// (lanes per storage, timesteps per lane) of the one-wave storage bodies. A launch family is instantiated for a prefix of the list:
+// k_agents_p for kPersistPairs, k_agents / k_net_agents for kFusedPairs, the storage launches for all.
+constexpr int kStoPairs[][2] = {{8, 1}, {8, 2}, {8, 3}, {16, 3}, {32, 3}, {64, 3}, {64, 6}, {64, 8}};
+constexpr int kPersistPairs = 5, kFusedPairs = 6, kAllPairs = 8;
 
 // the central reference's view (kernels_central.hip): the context's arrays (P, D, C, E, items, partial sums, cons) plus the
 // multipliers, running sums and step sizes of the primal-dual iteration
@@ -244,16 +258,17 @@ void central_launch_scale_copy(double *dst, const double *src, double scale, siz
 
 // kernels_agents.hip
 void launch_gen_update(const DevView &v, hipStream_t s);
-void launch_sto_update(const DevView &v, const Launch &lc, hipStream_t s);
-void launch_net_agents(const DevView &v, const Launch &lc, hipStream_t s);
-void launch_agents_fused(const DevView &v, const Launch &lc, hipStream_t s);
-void launch_agents_persist(const DevView &v, const Launch &lc, hipStream_t s);        // v.persistIters iterations in one launch
-bool sto_config_supported(int T, Launch *lc);
+void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
+void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);
+void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s);
+void launch_agents_persist(const DevView &v, const Plan &p, hipStream_t s);        // v.persistIters iterations in one launch
+bool sto_config_supported(int T, Plan *p);
 int debug_timeline(unsigned long long *out, int n);     // DOPF_STATS builds: per-wave stamps of the storage body
 // kernels_consensus.hip
-void launch_tables(const DevView &v, hipStream_t s);
+hipError_t raise_lds_limits(const DevView &v, const Plan &p);        // dopf_create, on the context's device: the dynamic LDS the plan's kernels need
+void launch_tables(const DevView &v, const Plan &p, hipStream_t s);
 void launch_slack(const DevView &v, hipStream_t s);
-void launch_reduce(const DevView &v, hipStream_t s);
+void launch_reduce(const DevView &v, const Plan &p, hipStream_t s);
 // Peer exchange (dopf_comm.hip sets it up): every rank owns a receive area [2 parities][world source ranks][n doubles] plus
 // flags [2][world][chunks]; data[r] / flags[r] are rank r's areas as addressable from THIS device (own allocation, a peer
 // device of the same process, or an IPC mapping of another process's allocation).
@@ -271,9 +286,9 @@ struct XchgView {
 };
 void launch_xchg(const DevView &v, const XchgView &x, hipStream_t s, bool inj_only = false);   // cons <- sum over ranks of cons (rank order);
 //      // inj_only: just the chunks that hold the node sums and the cost (the slack sums are formed behind the exchange: slackGlobal)
-void launch_dual(const DevView &v, hipStream_t s, const XchgView *xd = nullptr);   // xd: peer exchange inside the one-block kernel
+void launch_dual(const DevView &v, const Plan &p, hipStream_t s, const XchgView *xd = nullptr);   // xd: peer exchange inside the one-block kernel
 //      // consensus -> duals, residuals, prices, status
-void launch_derive(const DevView &v, hipStream_t s, bool from_primal);
+void launch_derive(const DevView &v, const Plan &p, hipStream_t s, bool from_primal);
 void launch_derive_level(const DevView &v, hipStream_t s);            // E = cumsum(C - D) into v.E
 void launch_penalty_sums(const DevView &v, double *out /* [3][N][T], device */, hipStream_t s);   // Result.penalty_term, per node
 void launch_node_results(const DevView &v, double *gen, double *dis, double *chg, hipStream_t s);   // [n + N*t] each, device pointers   // consensus -> inj/s/flow/price (no dual step)

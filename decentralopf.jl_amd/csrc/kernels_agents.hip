@@ -11,6 +11,8 @@
 //               price of each constant-price segment comes from a safeguarded Newton iteration.
 // Both kernels also produce the per-item partial sums of the agents' net injection and cost
 // (the agent loop of Result(...), src/structures/results.jl:72-106) in a fixed order.
+#include <type_traits>
+
 #include "dopf_internal.h"
 
 #ifdef DOPF_INLINE_CALLS
@@ -2184,7 +2186,7 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_sto_warm(DevView v)
     const int left = LEAN ? sto_lean_body<LPS, NCH, false, false, true, false>(v, blockIdx.x, v.st->halt)
                           : sto_warm_body<LPS, NCH, LINES>(v, blockIdx.x, v.st->halt);         // ends on a __syncthreads
     if (left < 0) return;                                                               // halted
-    if (LINES && v.coldInWarm) {
+    if (LINES) {                                 // the scan body for what the warm start left over: no k_sto_update launch
         if (left == 0) {                         // (what the scan body writes when there is nothing for it)
             const int row = v.sto_items[blockIdx.x].row;
             for (int t = threadIdx.x; t < v.T; t += 256) v.part_T[(size_t)t * v.rowsT + row] = 0.0;
@@ -2206,14 +2208,8 @@ template <int LPS, int NCH, bool LEAN>
 __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
 {
     const int nS = v.nStoItems;
-#ifdef DOPF_NET_GEN_FIRST            // (experiment: generator blocks in front)
-    const int nG_ = (int)gridDim.x - nS;
-    const bool isGen = (int)blockIdx.x < nG_;
-    const int gi = blockIdx.x, si = (int)blockIdx.x - nG_;
-#else
     const bool isGen = (int)blockIdx.x >= nS;
     const int gi = (int)blockIdx.x - nS, si = blockIdx.x;
-#endif
 #if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
     if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
 #endif
@@ -2340,128 +2336,103 @@ int debug_timeline(unsigned long long *out, int n)
 #endif
 }
 
-bool sto_config_supported(int T, Launch *lc)
+bool sto_config_supported(int T, Plan *p)
 {
     // lane group x consecutive timesteps per lane; 3 timesteps per lane keeps the kernel at 2 waves/SIMD
-    if (T <= 24) { lc->stoLPS = 8; lc->stoNCH = (T + 7) / 8; return true; }
-    if (T <= 48) { lc->stoLPS = 16; lc->stoNCH = 3; return true; }
-    if (T <= 96) { lc->stoLPS = 32; lc->stoNCH = 3; return true; }
-    if (T <= 192) { lc->stoLPS = 64; lc->stoNCH = 3; return true; }
-    if (T <= 384) { lc->stoLPS = 64; lc->stoNCH = 6; return true; }
-    if (T <= 512) { lc->stoLPS = 64; lc->stoNCH = 8; return true; }
+    if (T <= 24) { p->stoLPS = 8; p->stoNCH = (T + 7) / 8; return true; }
+    if (T <= 48) { p->stoLPS = 16; p->stoNCH = 3; return true; }
+    if (T <= 96) { p->stoLPS = 32; p->stoNCH = 3; return true; }
+    if (T <= 192) { p->stoLPS = 64; p->stoNCH = 3; return true; }
+    if (T <= 384) { p->stoLPS = 64; p->stoNCH = 6; return true; }
+    if (T <= 512) { p->stoLPS = 64; p->stoNCH = 8; return true; }
     return false;
 }
 
+// f(LPS, NCH) for the plan's lane group, as std::integral_constant arguments, over the first NP pairs of kStoPairs only: a launch
+// family is instantiated for exactly those. plan_chain refuses a lane group that the families it chose do not cover.
+template <int NP, int I = 0, class F>
+static void with_sto_pair(const Plan &p, F &&f)
+{
+    if constexpr (I < NP) {
+        if (p.stoLPS == kStoPairs[I][0] && p.stoNCH == kStoPairs[I][1])
+            f(std::integral_constant<int, kStoPairs[I][0]>{}, std::integral_constant<int, kStoPairs[I][1]>{});
+        else
+            with_sto_pair<NP, I + 1>(p, f);
+    }
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument (both are instantiated)
+template <class F>
+static void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 template <int LPS, int NCH>
-static void launch_sto_t(const DevView &v, hipStream_t s)
+static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
 {
     if (v.use_warm && v.L == 0) {            // (NCH <= 3 whenever the warm start is on)
         constexpr int NC = NCH <= 3 ? NCH : 3;
-#ifdef DOPF_NO_FULLT
-        const bool full = false;
-#else
-        const bool full = v.T == LPS * NC;
-#endif
-        if (v.stoLean) {
-            if (v.tail) { if (full) hipLaunchKernelGGL((k_sto_l<LPS, NC, true, true>), dim3(v.nStoItems + 1), dim3(256), 0, s, v);
-                          else hipLaunchKernelGGL((k_sto_l<LPS, NC, true, false>), dim3(v.nStoItems + 1), dim3(256), 0, s, v); }
-            else { if (full) hipLaunchKernelGGL((k_sto_l<LPS, NC, false, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
-                   else hipLaunchKernelGGL((k_sto_l<LPS, NC, false, false>), dim3(v.nStoItems), dim3(256), 0, s, v); }
-            return;
-        }
-        if (v.tail) {
-            if (full) hipLaunchKernelGGL((k_sto<LPS, NC, false, true, true>), dim3(v.nStoItems + 1), dim3(256), 0, s, v);
-            else hipLaunchKernelGGL((k_sto<LPS, NC, false, true, false>), dim3(v.nStoItems + 1), dim3(256), 0, s, v);
-        } else {
-            if (full) hipLaunchKernelGGL((k_sto<LPS, NC, false, false, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
-            else hipLaunchKernelGGL((k_sto<LPS, NC, false, false, false>), dim3(v.nStoItems), dim3(256), 0, s, v);
-        }
+        const dim3 grid(v.nStoItems + (v.tail ? 1 : 0));
+        with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NC, [&](auto full) {
+            constexpr bool TL = decltype(tail)::value, FU = decltype(full)::value;
+            if (p.stoLean) hipLaunchKernelGGL((k_sto_l<LPS, NC, TL, FU>), grid, dim3(256), 0, s, v);
+            else hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU>), grid, dim3(256), 0, s, v);
+        }); });
         return;
     }
-    // with lines the two kernels stay apart: fused, the warm part runs 40 % slower (255 VGPRs, measured)
+    // with lines the two kernels stay apart: fused, the warm part runs 40 % slower (255 VGPRs, measured); k_sto_warm calls the scan
+    // body itself for what it leaves over
     if (v.use_warm) {
-        if (v.stoLean && v.L > 0) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        if (p.stoLean) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        return;
     }
-    if (v.use_warm && v.L > 0 && v.coldInWarm) return;            // the warm kernel has called the scan body where needed
     if (v.L > 0) hipLaunchKernelGGL((k_sto_update<LPS, NCH, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
     else hipLaunchKernelGGL((k_sto_update<LPS, NCH, false>), dim3(v.nStoItems), dim3(256), 0, s, v);
 }
 
 template <int LPS, int NCH>
-static void launch_agents_t(const DevView &v, hipStream_t s)
+static void launch_agents_t(const DevView &v, const Plan &p, hipStream_t s)
 {
     const dim3 grid(v.nStoItems + (v.genBlocks > 0 && !v.genSkip ? v.genBlocks : v.nGenItems) + (v.tail ? 1 : 0));
-#ifdef DOPF_NO_FULLT
-    const bool fullA = false;
-#else
-    const bool fullA = v.T == LPS * NCH;
-#endif
-    if (v.stoLean) {
-#define DOPF_AGL(SKIP_, TAIL_) { if (fullA) hipLaunchKernelGGL((k_agents_l<LPS, NCH, SKIP_, TAIL_, true>), grid, dim3(256), 0, s, v); \
-                               else hipLaunchKernelGGL((k_agents_l<LPS, NCH, SKIP_, TAIL_, false>), grid, dim3(256), 0, s, v); }
-        if (v.tail) { if (v.genSkip) DOPF_AGL(true, true) else DOPF_AGL(false, true) }
-        else { if (v.genSkip) DOPF_AGL(true, false) else DOPF_AGL(false, false) }
-#undef DOPF_AGL
-        return;
-    }
-#define DOPF_AG(SKIP_, TAIL_) { if (fullA) hipLaunchKernelGGL((k_agents<LPS, NCH, SKIP_, TAIL_, true>), grid, dim3(256), 0, s, v); \
-                              else hipLaunchKernelGGL((k_agents<LPS, NCH, SKIP_, TAIL_, false>), grid, dim3(256), 0, s, v); }
-    if (v.tail) {
-        if (v.genSkip) DOPF_AG(true, true) else DOPF_AG(false, true)
-    } else {
-        if (v.genSkip) DOPF_AG(true, false) else DOPF_AG(false, false)
-    }
-#undef DOPF_AG
+    with_bool(v.genSkip, [&](auto skip) { with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NCH, [&](auto full) {
+        constexpr bool SK = decltype(skip)::value, TL = decltype(tail)::value, FU = decltype(full)::value;
+        if (p.stoLean) hipLaunchKernelGGL((k_agents_l<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
+        else hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
+    }); }); });
 }
 
-void launch_agents_fused(const DevView &v, const Launch &lc, hipStream_t s)
+void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s)
 {
-#define DOPF_CASE(LPS_, NCH_) if (lc.stoLPS == LPS_ && lc.stoNCH == NCH_) { launch_agents_t<LPS_, NCH_>(v, s); return; }
-    DOPF_CASE(8, 1) DOPF_CASE(8, 2) DOPF_CASE(8, 3)
-    DOPF_CASE(16, 3)
-    DOPF_CASE(32, 3)
-    DOPF_CASE(64, 3)
-#undef DOPF_CASE
+    with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) { launch_agents_t<decltype(lps)::value, decltype(nch)::value>(v, p, s); });
 }
 
-void launch_agents_persist(const DevView &v, const Launch &lc, hipStream_t s)
+void launch_agents_persist(const DevView &v, const Plan &p, hipStream_t s)
 {
     const dim3 grid(v.nStoItems + v.genBlocks + 1);
-#define DOPF_CASE(LPS_, NCH_) if (lc.stoLPS == LPS_ && lc.stoNCH == NCH_) { hipLaunchKernelGGL((k_agents_p<LPS_, NCH_>), grid, dim3(256), 0, s, v); return; }
-    DOPF_CASE(8, 1) DOPF_CASE(8, 2) DOPF_CASE(8, 3)
-    DOPF_CASE(16, 3)
-    DOPF_CASE(32, 3)
-#undef DOPF_CASE
+    with_sto_pair<kPersistPairs>(p, [&](auto lps, auto nch) { hipLaunchKernelGGL((k_agents_p<decltype(lps)::value, decltype(nch)::value>), grid, dim3(256), 0, s, v); });
 }
 
-void launch_net_agents(const DevView &v, const Launch &lc, hipStream_t s)
+void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s)
 {
     const dim3 grid(v.nStoItems + v.nGenItems);
-#define DOPF_CASE(LPS_, NCH_) if (lc.stoLPS == LPS_ && lc.stoNCH == NCH_) { \
-        if (v.stoLean) hipLaunchKernelGGL((k_net_agents<LPS_, NCH_, true>), grid, dim3(256), 0, s, v); \
-        else hipLaunchKernelGGL((k_net_agents<LPS_, NCH_, false>), grid, dim3(256), 0, s, v); return; }
-    DOPF_CASE(8, 1) DOPF_CASE(8, 2) DOPF_CASE(8, 3)
-    DOPF_CASE(16, 3)
-    DOPF_CASE(32, 3)
-    DOPF_CASE(64, 3)
-#undef DOPF_CASE
+    with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) {
+        if (p.stoLean) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
+        else hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false>), grid, dim3(256), 0, s, v);
+    });
 }
 
-void launch_sto_update(const DevView &v, const Launch &lc, hipStream_t s)
+void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s)
 {
     if (v.nStoItems == 0) return;
-    if (lc.stoLong) {                       // DOPF_F_LONG_HORIZON (sto_long.h): one block per item, any horizon
+    if (p.stoLong) {                        // DOPF_F_LONG_HORIZON (sto_long.h): one block per item, any horizon
         if (v.L > 0) hipLaunchKernelGGL((k_sto_long<true>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
         else hipLaunchKernelGGL((k_sto_long<false>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
         return;
     }
-#define DOPF_CASE(LPS_, NCH_) if (lc.stoLPS == LPS_ && lc.stoNCH == NCH_) { launch_sto_t<LPS_, NCH_>(v, s); return; }
-    DOPF_CASE(8, 1) DOPF_CASE(8, 2) DOPF_CASE(8, 3)
-    DOPF_CASE(16, 3)
-    DOPF_CASE(32, 3)
-    DOPF_CASE(64, 3) DOPF_CASE(64, 6) DOPF_CASE(64, 8)
-#undef DOPF_CASE
+    with_sto_pair<kAllPairs>(p, [&](auto lps, auto nch) { launch_sto_t<decltype(lps)::value, decltype(nch)::value>(v, p, s); });
 }
 
 }  // namespace dopf

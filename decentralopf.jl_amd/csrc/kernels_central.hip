@@ -321,7 +321,7 @@ void central_launch_iteration(const CentralView &c, const DevView &vreduce, hipS
     central_launch_price(c, c.yb, c.yf, 1.0, s);
     if (v.nGenItems) hipLaunchKernelGGL(kc_gen<true>, dim3(v.nGenItems), dim3(512), 0, s, c, (const double *)nullptr, 1.0);
     if (v.nStoItems) hipLaunchKernelGGL(kc_sto<true>, dim3(v.nStoItems), dim3(256), 0, s, c, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 1.0);
-    launch_reduce(vreduce, s);
+    launch_reduce(vreduce, Plan{}, s);            // (nodal sums and cost: k_reduce, whatever chain the context runs)
     hipLaunchKernelGGL(kc_dual<true>, dim3(v.T), dim3(256), 2 * (size_t)v.N * sizeof(double), s, c, (const double *)nullptr, (const double *)nullptr, 1.0);
 }
 
@@ -332,7 +332,7 @@ void central_launch_metrics(const CentralView &c, const DevView &vreduce, const 
     central_launch_price(c, yb, yf, scale, s);
     if (v.nGenItems) hipLaunchKernelGGL(kc_gen<false>, dim3(v.nGenItems), dim3(512), 0, s, c, XP, scale);
     if (v.nStoItems) hipLaunchKernelGGL(kc_sto<false>, dim3(v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
-    launch_reduce(vreduce, s);
+    launch_reduce(vreduce, Plan{}, s);            // (nodal sums and cost: k_reduce, whatever chain the context runs)
     hipLaunchKernelGGL(kc_dual<false>, dim3(v.T), dim3(256), 2 * (size_t)v.N * sizeof(double), s, c, yb, yf, scale);
 }
 

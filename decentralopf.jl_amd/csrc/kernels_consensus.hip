@@ -13,8 +13,6 @@
 //   k_derive_* rebuild the consensus state from a primal state handed in by dopf_set_state
 #include <algorithm>
 
-#include <atomic>
-
 #include "dopf_internal.h"
 
 namespace dopf {
@@ -192,26 +190,12 @@ __global__ __launch_bounds__(64) void k_tables(DevView v)
     build_table(v, n, t, shm);
 }
 
-// A function attribute belongs to the CURRENT device: "raised once per process" leaves every other device of a dopf_multi_* run
-// (or of a process with contexts on several GPUs) at the default limit, and the launch fails there. One bit per device, under a
-// lock (for_each_shard launches from one host thread per shard).
-static bool first_time_on_this_device(std::atomic<unsigned long long> &mask)
+void launch_tables(const DevView &v, const Plan &p, hipStream_t s)
 {
-    int dev = 0;
-    hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    return (mask.fetch_or(bit) & bit) == 0ull;
-}
-
-void launch_tables(const DevView &v, hipStream_t s)
-{
-    if (v.L == 0 || v.tablesInDual) return;  // (tablesInDual: the dual/price kernel builds the tables of its timestep itself)
-    if (v.wideNet) { launch_tables_wide(v, s); return; }        // (L > 0 here)
-    const size_t shm = (size_t)(4 * v.M2 + 1) * sizeof(double);
-    static std::atomic<unsigned long long> big_lds{0ull};
-    if (shm > 64 * 1024 && first_time_on_this_device(big_lds))     // worst case (every kink inside the window) needs 4 * 2L doubles
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_tables), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(k_tables, dim3(v.N * v.T), dim3(64), shm, s, v);
+    if (v.L == 0 || p.tablesInDual) return;  // (tablesInDual: the dual/price kernel builds the tables of its timestep itself)
+    if (p.wideNet) { launch_tables_wide(v, s); return; }
+    // worst case (every kink inside the window) needs 4 * 2L doubles: above 64 KB the limit is raised at dopf_create (raise_lds_limits)
+    hipLaunchKernelGGL(k_tables, dim3(v.N * v.T), dim3(64), (size_t)(4 * v.M2 + 1) * sizeof(double), s, v);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -644,9 +628,9 @@ __global__ __launch_bounds__(256) void k_reduce(DevView v)
 }
 
 
-void launch_reduce(const DevView &v, hipStream_t s)
+void launch_reduce(const DevView &v, const Plan &p, hipStream_t s)
 {
-    if (v.wideNet && v.L > 0) { launch_reduce_wide(v, s); return; }     // (dopf_central_solve reduces with a view of L = 0: k_reduce below)
+    if (p.wideNet) { launch_reduce_wide(v, s); return; }
     const int TC = (v.T + 31) / 32;
     const int blocks = v.N * v.reduceRB * TC + (v.L > 0 ? 2 * v.T * ((v.L + 63) / 64) : 0);
     hipLaunchKernelGGL(k_reduce, dim3(blocks), dim3(256), v.L > 0 ? 3 * (size_t)v.N * sizeof(double) : 0, s, v);
@@ -1689,7 +1673,7 @@ __global__ __launch_bounds__(256) void k_dual_price_small(DevView v, XchgView x)
         // the ones the two-level kernel produces
         const int RB = v.reduceRB, N = v.N, T = v.T, R = 8;
         const int r = tid >> 5, tt = tid & 31;            // 8 slice lanes x 32 entries, as in k_reduce
-        // N*T <= 256 here (slice_dual() in dopf_api.hip): up to 8 chunks of 32 entries, every load of every chunk
+        // N*T <= 256 here (Plan::sliceDual, plan_chain in dopf_api.hip): up to 8 chunks of 32 entries, every load of every chunk
         // issued before the first use, ONE barrier
         double sc[8];
 #pragma unroll
@@ -1761,44 +1745,63 @@ __global__ __launch_bounds__(256) void k_dual_price_small(DevView v, XchgView x)
 #include "net_wide.h"
 namespace dopf {
 
-// dynamic LDS of k_dual_price_t1024: its own vectors, plus table scratch for tablesInDual waves / the rows of its timestep (dopf_create)
-static size_t t1024_lds(const DevView &v)
+// A function attribute belongs to the device that is current when it is set: dopf_create sets the ones its plan needs on the
+// context's device, before anything is launched or captured.
+hipError_t raise_lds_limits(const DevView &v, const Plan &p)
 {
-    const size_t bytes = (size_t)v.dualLdsBytes;
-    static std::atomic<unsigned long long> raised{0ull};
-    if (bytes > 48 * 1024 && first_time_on_this_device(raised)) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_dual_price_t1024<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_dual_price_t1024<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_dual_price_t1024<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_dual_price_t1024<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    hipError_t e = hipSuccess;
+    if (p.consensus == Consensus::T1024 && v.dualLdsBytes > 48 * 1024) {
+        // its own vectors, plus table scratch for tablesInDual waves / the rows of its timestep (dopf_create)
+        const void *k[] = {reinterpret_cast<const void *>(k_dual_price_t1024<true>), reinterpret_cast<const void *>(k_dual_price_t1024<true, true>),
+                           reinterpret_cast<const void *>(k_dual_price_t1024<true, true, true>), reinterpret_cast<const void *>(k_dual_price_t1024<false>)};
+        for (const void *f : k)
+            if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     }
-    return bytes;
+    if (v.L > 0 && !p.tablesInDual && !p.wideNet && (size_t)(4 * v.M2 + 1) * sizeof(double) > 64 * 1024 && e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_tables), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return e;
 }
 
-void launch_dual(const DevView &v, hipStream_t s, const XchgView *xd)
+// the consensus step as the plan chose it: UPDATE = the dual update (launch_dual), or prices and the derived state only (launch_derive)
+template <bool UPDATE>
+static void launch_consensus(const DevView &v, const Plan &p, hipStream_t s, const XchgView *xd)
 {
     const size_t NT = (size_t)v.N * v.T, LT = (size_t)v.L * v.T;
     const size_t n1 = NT > LT ? NT : LT;
-    if (v.wideNet && v.L > 0) { launch_dual_wide<true>(v, s); return; }
-    if (n1 <= kSmallConsensus) {
-        if (xd) hipLaunchKernelGGL((k_dual_price_small<true, true>), dim3(1), dim3(256), 0, s, v, *xd);
-        else hipLaunchKernelGGL((k_dual_price_small<true, false>), dim3(1), dim3(256), 0, s, v, XchgView{});
+    switch (p.consensus) {
+    case Consensus::Wide:
+        launch_dual_wide<UPDATE>(v, s);
+        return;
+    case Consensus::Small:
+        if constexpr (UPDATE) {
+            if (xd) { hipLaunchKernelGGL((k_dual_price_small<true, true>), dim3(1), dim3(256), 0, s, v, *xd); return; }
+        }
+        hipLaunchKernelGGL((k_dual_price_small<UPDATE, false>), dim3(1), dim3(256), 0, s, v, XchgView{});
+        return;
+    case Consensus::T1024: {
+        const size_t lds = (size_t)v.dualLdsBytes;
+        if constexpr (UPDATE) {
+            if (v.slackInDual && v.quiet) { hipLaunchKernelGGL((k_dual_price_t1024<true, true, true>), dim3(v.T), dim3(1024), lds, s, v); return; }
+            if (v.slackInDual) { hipLaunchKernelGGL((k_dual_price_t1024<true, true>), dim3(v.T), dim3(1024), lds, s, v); return; }
+        }
+        hipLaunchKernelGGL(k_dual_price_t1024<UPDATE>, dim3(v.T), dim3(1024), lds, s, v);
         return;
     }
-    if (v.L > 0 && v.L <= 256 && v.N <= 256 && !v.splitDual) {
-        if (v.slackInDual && v.quiet) hipLaunchKernelGGL((k_dual_price_t1024<true, true, true>), dim3(v.T), dim3(1024), t1024_lds(v), s, v);
-        else if (v.slackInDual) hipLaunchKernelGGL((k_dual_price_t1024<true, true>), dim3(v.T), dim3(1024), t1024_lds(v), s, v);
-        else hipLaunchKernelGGL(k_dual_price_t1024<true>, dim3(v.T), dim3(1024), t1024_lds(v), s, v);
+    case Consensus::DualT:
+        hipLaunchKernelGGL(k_dual_t<UPDATE>, dim3(v.T * (v.L > 0 ? (v.L + 63) / 64 : 1)), dim3(256), (size_t)v.N * sizeof(double), s, v);
+        hipLaunchKernelGGL(k_price_t<UPDATE>, dim3(v.T), dim3(256), 3 * (size_t)v.L * sizeof(double), s, v);
+        return;
+    case Consensus::Generic:
+        if (v.L > 0) hipMemsetAsync(v.walk_any, 0, sizeof(int) * v.T, s);
+        hipLaunchKernelGGL(k_dual<UPDATE>, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, v);
+        hipLaunchKernelGGL(k_price<UPDATE>, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, s, v);
         return;
     }
-    if ((size_t)std::max(v.N, 3 * v.L) * sizeof(double) <= 48 * 1024) {
-        hipLaunchKernelGGL(k_dual_t<true>, dim3(v.T * (v.L > 0 ? (v.L + 63) / 64 : 1)), dim3(256), (size_t)v.N * sizeof(double), s, v);
-        hipLaunchKernelGGL(k_price_t<true>, dim3(v.T), dim3(256), 3 * (size_t)v.L * sizeof(double), s, v);
-        return;
-    }
-    if (v.L > 0) hipMemsetAsync(v.walk_any, 0, sizeof(int) * v.T, s);
-    hipLaunchKernelGGL(k_dual<true>, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, v);
-    hipLaunchKernelGGL(k_price<true>, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, s, v);
+}
+
+void launch_dual(const DevView &v, const Plan &p, hipStream_t s, const XchgView *xd)
+{
+    launch_consensus<true>(v, p, s, xd);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1903,31 +1906,14 @@ void launch_node_results(const DevView &v, double *gen, double *dis, double *chg
     hipLaunchKernelGGL(k_node_results, dim3(v.N * ((v.T + 31) / 32)), dim3(256), 0, s, v, gen, dis, chg);
 }
 
-void launch_derive(const DevView &v, hipStream_t s, bool from_primal)
+void launch_derive(const DevView &v, const Plan &p, hipStream_t s, bool from_primal)
 {
-    const size_t NT = (size_t)v.N * v.T, LT = (size_t)v.L * v.T;
-    const size_t n1 = NT > LT ? NT : LT;
+    const size_t NT = (size_t)v.N * v.T;
     if (from_primal) {        // serial over a node's agents: fine for tests / resume, not a hot path
         hipLaunchKernelGGL(k_derive_cons, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, s, v);
         if (v.S > 0) hipLaunchKernelGGL(k_derive_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v);
     }
-    if (v.wideNet && v.L > 0) { launch_dual_wide<false>(v, s); return; }
-    if (n1 <= kSmallConsensus) {
-        hipLaunchKernelGGL((k_dual_price_small<false, false>), dim3(1), dim3(256), 0, s, v, XchgView{});
-        return;
-    }
-    if (v.L > 0 && v.L <= 256 && v.N <= 256 && !v.splitDual) {
-        hipLaunchKernelGGL(k_dual_price_t1024<false>, dim3(v.T), dim3(1024), t1024_lds(v), s, v);
-        return;
-    }
-    if ((size_t)std::max(v.N, 3 * v.L) * sizeof(double) <= 48 * 1024) {
-        hipLaunchKernelGGL(k_dual_t<false>, dim3(v.T * (v.L > 0 ? (v.L + 63) / 64 : 1)), dim3(256), (size_t)v.N * sizeof(double), s, v);
-        hipLaunchKernelGGL(k_price_t<false>, dim3(v.T), dim3(256), 3 * (size_t)v.L * sizeof(double), s, v);
-        return;
-    }
-    if (v.L > 0) hipMemsetAsync(v.walk_any, 0, sizeof(int) * v.T, s);
-    hipLaunchKernelGGL(k_dual<false>, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, v);
-    hipLaunchKernelGGL(k_price<false>, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, s, v);
+    launch_consensus<false>(v, p, s, nullptr);
 }
 
 }  // namespace dopf
