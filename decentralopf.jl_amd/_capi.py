@@ -75,7 +75,7 @@ F_XCHG_OWNER = 65536
 F_XCHG_ALLGATHER = 131072
 F_NO_TAIL_XCHG = 262144
 F_NET_SMALL_ITEMS = 524288
-F_PERSIST = 1048576
+F_PERSIST = 1048576  # retired: accepted, has no effect
 F_LONG_HORIZON = 2097152
 F_DEBUG_LONG_STO = 4194304
 F_WIDE_NETWORK = 8388608

@@ -26,6 +26,7 @@ namespace {
 #define DOPF_UNROLL 16
 #endif
 constexpr int kUnroll = DOPF_UNROLL, kMid = 4;
+constexpr int kGraphIters[3] = {kUnroll, kMid, 1};      // iterations per launch of dopf_ctx::graphs[*].g, in launch order
 constexpr int kCheckEvery = 512;
 thread_local char g_create_err[512];
 
@@ -218,12 +219,6 @@ Plan plan_chain(const Shape &sh, unsigned flags, int cus)
         p.genBlocks = std::min(p.nGenItems, std::max(nb, 192));
     }
     if ((p.nGenItems + p.nStoItems) / kAccRep + 2 > 1000) p.tail = false;     // (the 10-bit arrival count of a replica slot)
-    {   // several iterations per launch: every block of the fused launch must be resident at once — 3 blocks of 256 threads per CU at
-        // the kernel's register count, as many CUs as this device has (a grid that does not fit would time out, not hang)
-        const bool full = T == p.stoLPS * p.stoNCH && p.stoLPS <= 32;
-        p.persist = (flags & DOPF_F_PERSIST) && p.tail && p.fuseAgents && p.genBlocks > 0 && !p.genSkip && p.stoLean && full && S > 0 &&
-                    p.nStoItems + p.genBlocks + 1 <= 3 * cus;
-    }
     if (L > 0) {        // rows of the transposed partial sums per timestep (DevView::part_T): each XCD's rows padded to 16
         int cnt[8] = {};
         for (int i = 0; i < p.nGenItems; ++i) ++cnt[gen_row_xcd(p, i)];
@@ -260,7 +255,7 @@ Plan plan_chain(const Shape &sh, unsigned flags, int cus)
     if (S > 0 && !p.stoLong) {
         int at = 0;
         while (at < kAllPairs && !(kStoPairs[at][0] == p.stoLPS && kStoPairs[at][1] == p.stoNCH)) ++at;
-        if (at >= (p.persist ? kPersistPairs : (p.fuseAgents || p.fuseNet) ? kFusedPairs : kAllPairs))
+        if (at >= ((p.fuseAgents || p.fuseNet) ? kFusedPairs : kAllPairs))
             p.refusal = "no storage kernel is instantiated for this horizon and chain";
     }
     return p;
@@ -272,14 +267,13 @@ namespace dopf {
 
 void drop_graphs(dopf_ctx *c)
 {
-    if (c->graph1) hipGraphExecDestroy(c->graph1);
-    if (c->graphM) hipGraphExecDestroy(c->graphM);
-    if (c->graphU) hipGraphExecDestroy(c->graphU);
-    if (c->graph1q) hipGraphExecDestroy(c->graph1q);
-    if (c->graphMq) hipGraphExecDestroy(c->graphMq);
-    if (c->graphUq) hipGraphExecDestroy(c->graphUq);
-    c->graph1 = c->graphM = c->graphU = c->graph1q = c->graphMq = c->graphUq = nullptr;
-    c->graphs_valid = c->graphs_q_valid = false;
+    for (auto &gs : c->graphs) {
+        for (auto &g : gs.g) {
+            if (g) hipGraphExecDestroy(g);
+            g = nullptr;
+        }
+        gs.valid = false;
+    }
 }
 
 int read_status(dopf_ctx *c)
@@ -411,17 +405,6 @@ int enqueue_iteration(dopf_ctx *c, bool quiet = false, const hipEvent_t *ev = nu
     return DOPF_OK;
 }
 
-// several iterations in one launch (agents_persist.h): the single-GPU one-launch copper-plate chain only
-bool persist_on(const dopf_ctx *c) { return c->plan.persist && c->comm == nullptr; }
-
-void enqueue_persist(dopf_ctx *c, int iters)
-{
-    DevView v = c->v;
-    v.tail = v.tailDev;
-    v.persistIters = iters;
-    launch_agents_persist(v, c->plan, c->main);
-}
-
 int build_graph(dopf_ctx *c, int iters, hipGraphExec_t *out, bool quiet = false)
 {
     hipGraph_t g = nullptr;
@@ -429,14 +412,22 @@ int build_graph(dopf_ctx *c, int iters, hipGraphExec_t *out, bool quiet = false)
     // from tripping over what other host threads — other GPUs' drivers — do meanwhile)
     HIPCHK(c, hipStreamBeginCapture(c->main, c->comm ? hipStreamCaptureModeThreadLocal : hipStreamCaptureModeRelaxed));
     int rc = DOPF_OK;
-    if (persist_on(c)) enqueue_persist(c, iters);
-    else for (int i = 0; i < iters && rc == DOPF_OK; ++i) rc = enqueue_iteration(c, quiet);
+    for (int i = 0; i < iters && rc == DOPF_OK; ++i) rc = enqueue_iteration(c, quiet);
     const hipError_t ec = hipStreamEndCapture(c->main, &g);
     if (rc) { if (g) hipGraphDestroy(g); return rc; }
     if (ec != hipSuccess) return fail(c, DOPF_E_DEVICE, "hipStreamEndCapture: %s", hipGetErrorString(ec));
     hipError_t e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     if (e != hipSuccess) return fail(c, DOPF_E_DEVICE, "hipGraphInstantiate: %s", hipGetErrorString(e));
+    return DOPF_OK;
+}
+
+int build_graphs(dopf_ctx *c, bool quiet)
+{
+    dopf_ctx::Graphs &gs = c->graphs[quiet];
+    for (int k = 0; k < 3; ++k)
+        if (const int rc = build_graph(c, kGraphIters[k], &gs.g[k], quiet)) return rc;
+    gs.valid = true;
     return DOPF_OK;
 }
 
@@ -791,19 +782,14 @@ int dopf_iterate(dopf_ctx *c, int32_t n_iters, int32_t *iters_done, int32_t *con
     // the collective (DOPF_F_COMM_GRAPH): either way nothing synchronises with the host inside the loop, and the
     // host enqueues an iteration's four launches faster than the GPU retires them
     bool eager = (c->q.flags & DOPF_F_NO_GRAPH) != 0 || (!comm_capturable(c) && !(c->q.flags & DOPF_F_COMM_GRAPH));
-    if (!eager && !c->graphs_valid) {
-        int rc = build_graph(c, 1, &c->graph1);
-        if (rc == DOPF_OK) rc = build_graph(c, kMid, &c->graphM);
-        if (rc == DOPF_OK) rc = build_graph(c, kUnroll, &c->graphU);
-        if (rc) {
+    if (!eager && !c->graphs[0].valid) {
+        if (const int rc = build_graphs(c, false)) {
             if (!c->comm) return rc;
             // the collective refused to be captured: launch the same chain eagerly from now on (no host sync either way)
             drop_graphs(c);
             (void)hipGetLastError();
             c->q.flags |= DOPF_F_NO_GRAPH;
             eager = true;
-        } else {
-            c->graphs_valid = true;
         }
     }
     // Enqueue in slices and look at the device status word between slices, so that a converged (or capped)
@@ -823,22 +809,16 @@ int dopf_iterate(dopf_ctx *c, int32_t n_iters, int32_t *iters_done, int32_t *con
         // (on a peer exchange: the chain without k_reduce, see enqueue_iteration — every rank takes the same decision from the same
         // replicated status word at the same iteration)
         const bool quiet = c->quiet && quiet_allowed(c);
-        if (quiet && !eager && !c->graphs_q_valid) {
-            int rc = build_graph(c, 1, &c->graph1q, true);
-            if (rc == DOPF_OK) rc = build_graph(c, kMid, &c->graphMq, true);
-            if (rc == DOPF_OK) rc = build_graph(c, kUnroll, &c->graphUq, true);
-            if (rc) return rc;
-            c->graphs_q_valid = true;
+        if (quiet && !eager && !c->graphs[1].valid) {
+            if (const int rc = build_graphs(c, true)) return rc;
         }
         const int asked = slice, total_before = c->host_st.iters_total;
-        if (eager && persist_on(c)) {
-            for (; slice > 0; slice -= std::min(slice, kUnroll)) enqueue_persist(c, std::min(slice, kUnroll));
-        } else if (eager) {
+        if (eager) {
             for (int i = 0; i < slice; ++i) { const int rc = enqueue_iteration(c, quiet); if (rc) return rc; }
         } else {
-            for (; slice >= kUnroll; slice -= kUnroll) HIPCHK(c, hipGraphLaunch(quiet ? c->graphUq : c->graphU, c->main));
-            for (; slice >= kMid; slice -= kMid) HIPCHK(c, hipGraphLaunch(quiet ? c->graphMq : c->graphM, c->main));
-            for (; slice > 0; --slice) HIPCHK(c, hipGraphLaunch(quiet ? c->graph1q : c->graph1, c->main));
+            const dopf_ctx::Graphs &gs = c->graphs[quiet];
+            for (int k = 0; k < 3; ++k)
+                for (; slice >= kGraphIters[k]; slice -= kGraphIters[k]) HIPCHK(c, hipGraphLaunch(gs.g[k], c->main));
         }
         HIPCHK(c, hipGetLastError());
         if (timed && left == 0) HIPCHK(c, hipEventRecord(c->evT1, c->main));
@@ -908,7 +888,6 @@ int dopf_iterate_timed(dopf_ctx *c, int32_t n_iters, dopf_timing *out)
     out->slack_in_dual = (!v.tail && v.slackInDual) ? 1 : 0;
     out->quiet = v.quiet ? 1 : 0;
     out->sto_lean = (p.stoLean && v.S > 0 && v.use_warm) ? 1 : 0;
-    out->persist = persist_on(c) ? 1 : 0;
     out->sto_long = (p.stoLong && v.S > 0) ? 1 : 0;
     return DOPF_OK;
 }

@@ -497,7 +497,7 @@ int dopf_comm_info(const dopf_ctx *c, int32_t *world, int32_t *rank, int32_t *in
     if (!c) return DOPF_E_INVALID;
     if (world) *world = c->comm ? c->comm->world : 1;
     if (rank) *rank = c->comm ? c->comm->rank : 0;
-    if (in_graph) *in_graph = (c->comm && c->graphs_valid) ? 1 : 0;
+    if (in_graph) *in_graph = (c->comm && c->graphs[0].valid) ? 1 : 0;
     return DOPF_OK;
 }
 

@@ -18,12 +18,13 @@ struct dopf_ctx {
     hipEvent_t evFork = nullptr, evJoin = nullptr;
     hipEvent_t evT0 = nullptr, evT1 = nullptr;      // DOPF_F_TIME_CALLS: around the launches of the last dopf_iterate
     double last_call_ms = -1.0;
-    hipGraphExec_t graph1 = nullptr, graphM = nullptr, graphU = nullptr;   // 1, kMid, kUnroll iterations per launch
-    bool graphs_valid = false;
-    // Networks on the three-launch chain: while no line is flagged (Status::walk_last == 0 at the last look) the "quiet" chain runs —
-    // k_net_agents and the dual/price kernel, which forms the node sums itself; k_slack is not launched. Graphs of its own.
-    hipGraphExec_t graph1q = nullptr, graphMq = nullptr, graphUq = nullptr;
-    bool graphs_q_valid = false;
+    // The iteration graphs, kUnroll, kMid and 1 iterations per launch (dopf_api.hip: kGraphIters), built when first used; [1]: the
+    // quiet chain's. Networks on the three-launch chain: while no line is flagged (Status::walk_last == 0 at the last look) the "quiet"
+    // chain runs — k_net_agents and the dual/price kernel, which forms the node sums itself; k_slack is not launched.
+    struct Graphs {
+        hipGraphExec_t g[3] = {};
+        bool valid = false;
+    } graphs[2];
     bool quiet = false;             // no line flagged at the last look: the next launches may use the quiet chain (if quiet_allowed)
     unsigned long long quiet_parked = 0;    // times the quiet chain parked itself (a line got flagged) and the host went back
     std::vector<void *> allocs;

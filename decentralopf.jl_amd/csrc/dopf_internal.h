@@ -56,7 +56,6 @@ struct Status {
     int xchg_timeout;       // peer exchange: a peer's part of the consensus sum did not arrive in time (sticky)
     int tail_timeout;       // tail in the launch: the block sums of an iteration did not all arrive in time (sticky)
     int tail_par;           // tail in the launch: which of the two accumulator sets the next launch adds into
-    int pseq;               // persistent iterations (agents_persist.h): dual updates published inside launches so far (wraps; only differences count)
 };
 
 struct XchgView;
@@ -110,7 +109,6 @@ struct DevView {
                                     // kernel forms the node sums too
     int genTT256;                   // networks, fused launch: column tiling of a 256-thread generator block with the same R as genR
     int use_warm;                   // storage warm-start kernel runs first; the scan kernel serves its failures
-    int persistIters;               // per launch: iterations this launch runs
     int max_iters;
     int keepDeltas;                 // DOPF_F_KEEP_DELTAS: dltG / dltS are written for every timestep (diagnostic getters)
     int rootCap;                    // iteration cap of the scan kernel's root search (80; 2 with DOPF_F_DEBUG_ROOT_CAP)
@@ -223,7 +221,7 @@ struct Plan {
     bool sliceDual;                 // the one-block dual kernel may add k_reduce's slices itself (DevView::sliceDual)
     bool useWarm, stoLean;          // storage warm start (DevView::use_warm); the lean active-set body (sto_lean.h)
     bool fuseAgents, fuseNet;       // generators + storages in one launch: k_agents (copper plate, even T), k_net_agents (networks)
-    bool tail, persist;             // the tail of the iteration in the x-update launch (DevView::tailDev); DOPF_F_PERSIST (agents_persist.h)
+    bool tail;                      // the tail of the iteration in the x-update launch (DevView::tailDev)
     bool slackDual;                 // the one-launch dual/price kernel may form the slack sums: no k_reduce (DevView::slackInDual)
     bool quiet, commQuiet;          // the quiet chain may run: single GPU (DevView::quiet), on a peer exchange (DevView::slackGlobal)
     int genTT, genR, genTT2, genR2, genTT256, genSkip, genBlocks, tablesInDual;     // (DevView)
@@ -232,9 +230,9 @@ struct Plan {
 };
 
 // (lanes per storage, timesteps per lane) of the one-wave storage bodies. A launch family is instantiated for a prefix of the list:
-// k_agents_p for kPersistPairs, k_agents / k_net_agents for kFusedPairs, the storage launches for all.
+// k_agents / k_net_agents for kFusedPairs, the storage launches for all.
 constexpr int kStoPairs[][2] = {{8, 1}, {8, 2}, {8, 3}, {16, 3}, {32, 3}, {64, 3}, {64, 6}, {64, 8}};
-constexpr int kPersistPairs = 5, kFusedPairs = 6, kAllPairs = 8;
+constexpr int kFusedPairs = 6, kAllPairs = 8;
 
 // the central reference's view (kernels_central.hip): the context's arrays (P, D, C, E, items, partial sums, cons) plus the
 // multipliers, running sums and step sizes of the primal-dual iteration
@@ -261,7 +259,6 @@ void launch_gen_update(const DevView &v, hipStream_t s);
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s);
-void launch_agents_persist(const DevView &v, const Plan &p, hipStream_t s);        // v.persistIters iterations in one launch
 bool sto_config_supported(int T, Plan *p);
 int debug_timeline(unsigned long long *out, int n);     // DOPF_STATS builds: per-wave stamps of the storage body
 // kernels_consensus.hip

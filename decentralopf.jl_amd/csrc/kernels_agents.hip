@@ -15,12 +15,6 @@
 
 #include "dopf_internal.h"
 
-#ifdef DOPF_INLINE_CALLS
-#define DOPF_CALL_ATTR __forceinline__
-#else
-#define DOPF_CALL_ATTR __attribute__((noinline))
-#endif
-
 namespace dopf {
 
 #if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
@@ -51,13 +45,6 @@ __device__ __forceinline__ double rcp64(double x)
     return r;
 }
 
-// Loads / stores of words that ANOTHER block of the SAME launch wrote or will read (the persistent iterations of
-// agents_persist.h): agent scope — past the CU's vector L1 and the scalar cache, which are only refreshed between launches.
-__device__ __forceinline__ double p_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int p_ldi(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void p_st(double *p, double x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void p_sti(int *p, int x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // ------------------------------------------------------------------------------------------------
 // the tail of the iteration inside the x-update launch (DevView::tail; one node, no lines)
 // ------------------------------------------------------------------------------------------------
@@ -83,11 +70,6 @@ __device__ __forceinline__ void p_sti(int *p, int x) { __hip_atomic_store(p, x, 
 // (First version: every block waited for its adds, took a two-level ticket, the last one drained the accumulators with
 // atomic exchanges — four dependent device-scope round trips of ~2.5 us each next to the streaming blocks: as slow as the
 // two launches it replaced.)
-#ifdef DOPF_TAIL_NOINLINE
-#define DOPF_TAIL_INLINE __attribute__((noinline))
-#else
-#define DOPF_TAIL_INLINE __forceinline__
-#endif
 constexpr int kAccCntBits = 10;
 constexpr unsigned long long kAccCntMask = (1ull << kAccCntBits) - 1ull;
 
@@ -108,7 +90,7 @@ __device__ __forceinline__ void acc_add(const TailView &tv, int par, int slot, d
 // the set an iteration used is zeroed by the NEXT tail block while it waits, not between the last arrival and the dual step.
 // (`self`: the context's view in DEVICE memory — what this block needs is read there, inside its branch, instead of
 // widening the set of kernel arguments every block of the launch loads at its start)
-__device__ DOPF_TAIL_INLINE void tail_block(const DevView *self)
+__device__ __forceinline__ void tail_block(const DevView *self)
 {
     const DevView &v = *self;
     const TailView tv = *v.tailDev;
@@ -497,14 +479,14 @@ __global__ __launch_bounds__(512) void k_gen_update(DevView v)
 // LDS_ONLY: the barrier waits for this wave's LDS traffic only. __syncthreads() also drains every global load in
 // flight (s_waitcnt vmcnt(0)) — in the streaming blocks those are the NEXT item's rows, i.e. exactly the overlap the
 // streaming is for. Only LDS data crosses this barrier.
-template <int BS, bool TAIL, bool LDS_ONLY = false, bool PERSIST = false>
+template <int BS, bool TAIL, bool LDS_ONLY = false>
 __device__ __forceinline__ void gen_pair_sums(const DevView &v, const int blk, const int tid, const int r, const int tt,
-                                              double acc0, double acc1, double cost, double (*red)[BS], double *wc, const int ppar = 0)
+                                              double acc0, double acc1, double cost, double (*red)[BS], double *wc)
 {
     const int T = v.T, TT = v.genTT2, R = v.genR2;
     TailView tv{};                                           // TAIL: the launch chain carries the iteration's tail
     int par = 0;
-    if (TAIL) { tv = *v.tail; par = PERSIST ? ppar : v.st->tail_par; }        // (uniform scalar loads, in flight with the LDS traffic below)
+    if (TAIL) { tv = *v.tail; par = v.st->tail_par; }        // (uniform scalar loads, in flight with the LDS traffic below)
     for (int d = 32; d > 0; d >>= 1) cost += __shfl_xor(cost, d);
     red[0][tid] = acc0; red[1][tid] = acc1;
     if ((tid & 63) == 0) wc[tid >> 6] = cost;
@@ -1030,7 +1012,7 @@ __device__ __forceinline__ void eval_lines(const TabRef &tb, int &hint, double w
 // The same two as functions of their own, for the active-set body: there a (node, timestep) with a non-empty table is
 // the rare case (none in the settled state), and inlined their registers cost the common path a wave per SIMD.
 struct EvalOut { double dd, cc, s1, pc; int hint; };
-__device__ DOPF_CALL_ATTR EvalOut eval_lines_call(const DevView *self, int node, int t, int hint, double mc, double pm,
+__device__ __attribute__((noinline)) EvalOut eval_lines_call(const DevView *self, int node, int t, int hint, double mc, double pm,
                                                              double D0, double C0, double nu)
 {
     const DevView &v = *self;
@@ -1040,7 +1022,7 @@ __device__ DOPF_CALL_ATTR EvalOut eval_lines_call(const DevView *self, int node,
     eval_lines(tb, o.hint, v.w_prox, 1.0 / v.w_prox, mc, pm, D0, C0, nu, o.dd, o.cc, o.s1, o.pc);
     return o;
 }
-__device__ DOPF_CALL_ATTR double tab_psi_call(const DevView *self, int node, int t, double dl)
+__device__ __attribute__((noinline)) double tab_psi_call(const DevView *self, int node, int t, double dl)
 {
     return tab_psi_at(tab_ref(*self, node, t), dl);
 }
@@ -1052,8 +1034,8 @@ struct StoAgent {
 // `item_fail`: number of storages of this item the warm start left over (block-uniform); < 0 = read it
 // FULLT: the horizon fills the lane group exactly (T == LPS * NCH: 24 = 8 x 3, 48 = 16 x 3, 96 = 32 x 3): T is then a
 // compile-time constant and every "is this step inside the horizon" test folds away
-template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, bool PERSIST = false>
-__device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, int item_fail, const int ppar = 0)
+template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false>
+__device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, int item_fail)
 {
     constexpr int NG = 256 / LPS;
     __shared__ double red[NG * LPS * NCH];
@@ -1080,7 +1062,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
     for (int c = 0; c < NCH; ++c) {
         const int t = tbase + c;
         accQ[c] = 0.0;
-        th0[c] = (!LINES && t < T) ? (PERSIST ? p_ld(v.price + it.node + N * t) + gam * p_ld(v.s + t) : v.price[it.node + N * t] + gam * v.s[t]) : 0.0;
+        th0[c] = (!LINES && t < T) ? v.price[it.node + N * t] + gam * v.s[t] : 0.0;
     }
     // with lines: a (node, timestep) whose table is empty — no kink of Psi inside the node's window, the usual case —
     // is the copper-plate closed form with (Psi(0), slope) in place of (theta, gamma): cached here, no table reads
@@ -1364,7 +1346,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
                 double sum = 0.0;
                 for (int g2 = 0; g2 < NG; ++g2) sum += red[(g2 * LPS + li) * NCH + c];
                 // (tail in the launch: this thread wrote the active-set body's sum of slot t itself, a moment ago)
-                if (TAIL) { const TailView tv = *v.tail; acc_add(tv, PERSIST ? ppar : v.st->tail_par, t, sum + v.part_sinj_w[(size_t)blk * T + t], tv.scaleInj); }
+                if (TAIL) { const TailView tv = *v.tail; acc_add(tv, v.st->tail_par, t, sum + v.part_sinj_w[(size_t)blk * T + t], tv.scaleInj); }
                 else if (LINES) v.part_T[(size_t)t * v.rowsT + it.row] = sum;
                 else v.part_sinj[(size_t)blk * T + t] = sum;
             }
@@ -1375,7 +1357,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
         __syncthreads();
     }
     if (tid == 0) {
-        if (TAIL) { const TailView tv = *v.tail; acc_add(tv, PERSIST ? ppar : v.st->tail_par, T, redc[0] + v.part_scost_w[blk], tv.scaleCost); }
+        if (TAIL) { const TailView tv = *v.tail; acc_add(tv, v.st->tail_par, T, redc[0] + v.part_scost_w[blk], tv.scaleCost); }
         else v.part_scost[blk] = redc[0];
     }
     if (fails) atomicAdd(&v.st->solver_fail, fails);
@@ -2169,7 +2151,7 @@ namespace dopf {
 // something of. Inlined, its registers crowd the active-set body (255 VGPRs and spills, 40 % slower, measured); as a
 // separate launch it cost 4 us + a launch gap per iteration for finding nothing to do.
 template <int LPS, int NCH>
-__device__ DOPF_CALL_ATTR void sto_cold_lines_call(const DevView *self, const int blk, const int left)
+__device__ __attribute__((noinline)) void sto_cold_lines_call(const DevView *self, const int blk, const int left)
 {
     sto_cold_body<LPS, NCH, true>(*self, blk, left);
 }
@@ -2183,7 +2165,7 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_sto_warm(DevView v)
     // (networks, LEAN: the lean body where every table of the item's node is empty — the settled state — else the general one.
     // A template argument, not a branch on v.stoLean: with both bodies in one function the general one ran 6 % slower, measured)
     static_assert(LINES || !LEAN, "copper plates: k_sto_l");
-    const int left = LEAN ? sto_lean_body<LPS, NCH, false, false, true, false>(v, blockIdx.x, v.st->halt)
+    const int left = LEAN ? sto_lean_body<LPS, NCH, false, true, false>(v, blockIdx.x, v.st->halt)
                           : sto_warm_body<LPS, NCH, LINES>(v, blockIdx.x, v.st->halt);         // ends on a __syncthreads
     if (left < 0) return;                                                               // halted
     if (LINES) {                                 // the scan body for what the warm start left over: no k_sto_update launch
@@ -2218,7 +2200,7 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
         if (2 * v.genTT256 >= v.T) gen_lines_body2<256, DOPF_NET_GEN_FLIGHT>(v, gi, v.genTT256, v.genR);
         else gen_lines_body<256, DOPF_NET_GEN_FLIGHT>(v, gi, v.genTT256, v.genR);
     } else {
-        const int left = LEAN ? sto_lean_body<LPS, NCH, false, false, true, false>(v, si, v.st->halt)
+        const int left = LEAN ? sto_lean_body<LPS, NCH, false, true, false>(v, si, v.st->halt)
                               : sto_warm_body<LPS, NCH, true>(v, si, v.st->halt);                  // ends on a __syncthreads
         if (left < 0) return;                                                           // halted
         if (left == 0) {                     // (what the scan body writes when there is nothing for it)
@@ -2290,7 +2272,7 @@ template <int LPS, int NCH, bool TAIL, bool FULLT = true>
 __global__ __launch_bounds__(256, DOPF_LEAN_STO_WAVES) void k_sto_l(DevView v)
 {
     if (TAIL && (int)blockIdx.x == v.nStoItems) { tail_block(v.self); return; }
-    const int left = sto_lean_body<LPS, NCH, TAIL, false, false, FULLT>(v, blockIdx.x, v.st->halt);
+    const int left = sto_lean_body<LPS, NCH, TAIL, false, FULLT>(v, blockIdx.x, v.st->halt);
     if (left < 0) return;
     sto_cold_body<LPS, NCH, false, TAIL, FULLT>(v, blockIdx.x, left);
 }
@@ -2309,7 +2291,7 @@ __global__ __launch_bounds__(256, 3) void k_agents_l(DevView v)
         else gen_pair_body<256, TAIL, true>(v, blockIdx.x - nS);
     } else {
         if ((int)blockIdx.x < nS) {
-            const int left = sto_lean_body<LPS, NCH, TAIL, false, false, FULLT>(v, blockIdx.x, v.st->halt);
+            const int left = sto_lean_body<LPS, NCH, TAIL, false, FULLT>(v, blockIdx.x, v.st->halt);
             if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT>(v, blockIdx.x, left);
         } else {
             if (v.st->halt) return;
@@ -2321,10 +2303,6 @@ __global__ __launch_bounds__(256, 3) void k_agents_l(DevView v)
     if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
 #endif
 }
-
-}  // namespace dopf
-#include "agents_persist.h"
-namespace dopf {
 
 int debug_timeline(unsigned long long *out, int n)
 {
@@ -2407,12 +2385,6 @@ static void launch_agents_t(const DevView &v, const Plan &p, hipStream_t s)
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s)
 {
     with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) { launch_agents_t<decltype(lps)::value, decltype(nch)::value>(v, p, s); });
-}
-
-void launch_agents_persist(const DevView &v, const Plan &p, hipStream_t s)
-{
-    const dim3 grid(v.nStoItems + v.genBlocks + 1);
-    with_sto_pair<kPersistPairs>(p, [&](auto lps, auto nch) { hipLaunchKernelGGL((k_agents_p<decltype(lps)::value, decltype(nch)::value>), grid, dim3(256), 0, s, v); });
 }
 
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s)

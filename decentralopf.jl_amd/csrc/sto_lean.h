@@ -184,25 +184,7 @@ __device__ __forceinline__ void lz_seg_maxmin(double K, double &a, double &b)
     }
 }
 
-// persistent iterations (agents_persist.h): Status::pseq = number of dual updates published inside launches (low 30 bits) | the halt
-// word of the last of them (bit 31). One lane waits until the count has reached `want`; returns the word, or all ones on a time-out.
-constexpr unsigned kPersistHaltBit = 0x80000000u, kPersistSeqMask = 0x3fffffffu;
-__device__ __forceinline__ unsigned persist_wait_word(Status *st, const unsigned want)
-{
-    const unsigned long long t0 = wall_clock64();
-    for (unsigned round = 1;; ++round) {
-        const unsigned w = (unsigned)p_ldi(reinterpret_cast<const int *>(&st->pseq));
-        if (((w - want) & kPersistSeqMask) < 0x20000000u) return w;          // (count >= want, wrap-safe)
-        if ((round & 255u) == 0u && wall_clock64() - t0 > 200000000ull) return 0xffffffffu;      // 2 s of the 100 MHz wall clock
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-
 // returns the number of storages of the item left to the scan body (block-uniform); -1 = halted
-// PERSIST (agents_persist.h: several iterations in one launch): the prices another block of this launch has just published are
-// read past the caches, and the accumulator set is the caller's (`ppar`), not the status block's word.
-// (PERSIST, pwant != 0: the wait for the previous iteration's prices happens INSIDE, behind the first pass's row loads — those
-// do not depend on the prices; returns -1 when the wait found the halted state or timed out: nothing stored)
 // LINES: an item of storages at a node of a network whose tables are EMPTY for every timestep (no kink of Psi inside the node's
 // window: the settled state) — the copper plate's closed form with (Psi(0), slope) of the (node, timestep) in place of (theta, gamma);
 // an item that meets a non-empty table is handed to the general body (sto_warm_body) as a whole.
@@ -215,11 +197,11 @@ __device__ __attribute__((noinline)) int sto_warm_lines_call(const DevView *self
     return sto_warm_body<LPS, NCH, true>(*self, blk, halt);
 }
 
-template <int LPS, int NCH, bool TAIL, bool PERSIST = false, bool LINES = false, bool FULLT = true>
-__device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, const int halt, const int ppar = 0, const unsigned pwant = 0u)
+template <int LPS, int NCH, bool TAIL, bool LINES = false, bool FULLT = true>
+__device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, const int halt)
 {
     static_assert(LPS <= 64 && NCH <= 8, "4 pattern bits per step");
-    static_assert(!(PERSIST && (LINES || !FULLT)) && !(TAIL && LINES), "persistent iterations / the tail in the launch: full-horizon copper plates");
+    static_assert(!(TAIL && LINES), "the tail in the launch: copper plates");
     constexpr int NG = 256 / LPS, TP = LPS * NCH;
     const int T = FULLT ? TP : v.T;
     constexpr int MAXR = 16;                 // contact-set rounds per storage
@@ -275,8 +257,7 @@ __device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, co
     // step and pass) instead of registers (the kernel sits at its register limit) or two more loads per step and pass, whose
     // addresses cost a v_readlane each once the solve has taken the scalar registers.
     __shared__ double th0L[TP];
-    __shared__ int goL;
-    if (!PERSIST && !LINES) {
+    if (!LINES) {
         if (tid < LPS) {
 #pragma unroll
             for (int c = 0; c < NCH; ++c) th0L[tbase + c] = LZ_IN(c) ? v.price[it.node + N * (tbase + c)] + gam * v.s[tbase + c] : 0.0;
@@ -290,21 +271,14 @@ __device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, co
     for (int rep = 0; rep < nRep; ++rep) {
         const int s = it.a0 + rep * NG + grp;
         const bool live = s < it.a1;
-        // The arrays' addresses are read from the view's copy in device memory where they are needed (scalar loads, issued
-        // with the rows' loads) instead of being held in scalar registers across the solve: the solve keeps ~20 lane masks in
-        // scalar register pairs, and every address held beside them was a v_writelane / v_readlane pair per pass.
-#ifdef LZ_PV_LOAD
-        const DevView *pv = v.self;
-        asm volatile("" : "+s"(pv));
-#else
-        const DevView *pv = &v;
-#endif
         // A lane group without a storage of its own (the item's last pass) solves the item's FIRST storage again and stores nothing
         // (gdone from the start): every load below is unconditional, no exec-mask regions around them. Element offsets are 32-bit
         // (dopf_create offers this body only while S * T * 8 < 4 GB): base register + offset addressing, no 64-bit address arithmetic.
+        // The passes take the arrays' addresses from the kernel arguments (`v`); only the block's sums at the end read theirs from
+        // the view's copy in device memory (`pf`).
         const unsigned sl = live ? (unsigned)s : (unsigned)it.a0;
-        const double mc = pv->sto_mc[sl], pm = pv->sto_pmax[sl], em = pv->sto_emax[sl];
-        const bool havenu = live && pv->nu_valid[sl] != 0;
+        const double mc = v.sto_mc[sl], pm = v.sto_pmax[sl], em = v.sto_emax[sl];
+        const bool havenu = live && v.nu_valid[sl] != 0;
         double A0[NCH], B0[NCH], nuv[NCH], dq[NCH];      // rD = A0 - nu, rC = B0 + nu
         double run = 0.0;
         double d0r[NCH], c0r[NCH], nur[NCH];
@@ -312,30 +286,9 @@ __device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, co
         for (int c = 0; c < NCH; ++c) {
             const int t = tbase + c;
             const unsigned eb = (sl * (unsigned)T + (unsigned)(LZ_IN(c) ? t : 0)) * 8u;
-            d0r[c] = *lz_at(pv->D, eb); c0r[c] = *lz_at(pv->C, eb);
-            nur[c] = *lz_at(pv->nu_prev, eb);
+            d0r[c] = *lz_at(v.D, eb); c0r[c] = *lz_at(v.C, eb);
+            nur[c] = *lz_at(v.nu_prev, eb);
             if (!LZ_IN(c)) { d0r[c] = 0.0; c0r[c] = 0.0; nur[c] = 0.0; }
-        }
-        if (PERSIST && rep == 0) {
-            // the rows above are on their way; now the prices the launch's tail block publishes (agents_persist.h)
-            if (tid == 0) {
-                int go = 1;
-                if (pwant != 0u) {
-                    const unsigned w = persist_wait_word(v.st, pwant);
-                    go = w == 0xffffffffu ? -1 : ((w & kPersistHaltBit) ? 0 : 1);
-                }
-                goL = go;
-            }
-            __syncthreads();
-            if (goL <= 0) {
-                if (goL < 0 && tid == 0) v.st->tail_timeout = 1;
-                return -1;
-            }
-            if (tid < LPS) {
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) th0L[tbase + c] = p_ld(v.price + it.node + N * (tbase + c)) + gam * p_ld(v.s + tbase + c);
-            }
-            __syncthreads();
         }
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -446,11 +399,7 @@ __device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, co
                     npat |= (cD | (cC << 2)) << (4 * c);
                 }
                 // A plain Newton step that left every step of the wave on its piece: the sums moved by slope x step exactly
-#ifdef LZ_NO_SHORTCUT
-                const bool same = false;
-#else
                 const bool same = stepped && __all(npat == pat || gdone);
-#endif
                 pat = npat;
                 if (same) {
                     // px already holds the prediction (made where the prices were re-read). Rounding only: the step was exact;
@@ -685,12 +634,6 @@ __device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, co
                     __builtin_amdgcn_wave_barrier();
                 }
             }
-#ifdef LZ_DEBUG_PRINT
-            if (s == LZ_DEBUG_PRINT && v.st->iters_total == LZ_DEBUG_ITER) {
-                for (int c = 0; c < NCH; ++c)
-                    printf("r%d t%2d kind %d->%d en %d nuv %.6f D %.5f C %.5f px %.6f ps %.4f mlo %.6f mhi %.6f nuc %.6f okk %d nconv %d gdone %d A0 %.5f B0 %.5f\n", round, tbase + c, kind[c], nkind[c], (int)en[c], nuv[c], Dv[c], Cv[c], px[c], ps[c], mlo[c], mhi[c], nuc[c], (int)okk, (int)nconv, (int)gdone, A0[c], B0[c]);
-            }
-#endif
             const bool cert = nconv && group_bits<LPS>(!okk, gbase) == 0ull && !(v.debugLeave && s % 3 == 0);
             bool chg = false;
 #pragma unroll
@@ -701,21 +644,15 @@ __device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, co
             if (!gdone && cert) {
                 int s_ = s;
                 asm volatile("" : "+v"(s_));
-#ifdef LZ_PV_STORE
-                const DevView *pw = v.self;
-                asm volatile("" : "+s"(pw));
-#else
-                const DevView *pw = &v;
-#endif
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     if (!LZ_IN(c)) continue;
                     const unsigned eb = ((unsigned)s_ * (unsigned)T + (unsigned)(tbase + c)) * 8u;
-                    *lz_at(pw->D, eb) = Dv[c];
-                    *lz_at(pw->C, eb) = Cv[c];
+                    *lz_at(v.D, eb) = Dv[c];
+                    *lz_at(v.C, eb) = Cv[c];
                     // copper plate: nu + theta (theta back from the step's offsets); lines: nu
-                    *lz_at(pw->nu_prev, eb) = LINES ? nuc[c] : nuc[c] + 0.5 * (B0[c] - A0[c] - w * dq[c]);
-                    if (LINES && (pw->keepDeltas || pw->walk_any[tbase + c])) *lz_at(pw->dltS, eb) = (Dv[c] - Cv[c]) + dq[c];
+                    *lz_at(v.nu_prev, eb) = LINES ? nuc[c] : nuc[c] + 0.5 * (B0[c] - A0[c] - w * dq[c]);
+                    if (LINES && (v.keepDeltas || v.walk_any[tbase + c])) *lz_at(v.dltS, eb) = (Dv[c] - Cv[c]) + dq[c];
                     accQ[c] += Dv[c] - Cv[c];
                     accCost += mc * (Dv[c] + Cv[c]);
                 }
@@ -732,15 +669,7 @@ __device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, co
 #undef LZ_TGT
         }
 
-        {
-#ifdef LZ_PV_STORE
-            const DevView *pe = v.self;
-            asm volatile("" : "+s"(pe));
-#else
-            const DevView *pe = &v;
-#endif
-            if (live && first) { pe->sto_fail[s] = good ? 0 : 1; if (good) pe->nu_valid[s] = 1; }
-        }
+        if (live && first) { v.sto_fail[s] = good ? 0 : 1; if (good) v.nu_valid[s] = 1; }
         if (live && !good && first) anyFail += 1;
         __builtin_amdgcn_wave_barrier();
     }
@@ -776,15 +705,11 @@ __device__ __forceinline__ int sto_lean_body(const DevView &v, const int blk, co
             for (int c = 0; c < NCH; ++c) wsumS[tid >> 6][tbase + c] = accQ[c];
         }
     }
-#ifndef LZ_NO_PV_FINAL
-    const DevView *pf = v.self;                                  // (addresses from the view's copy in device memory: see the passes)
-    asm volatile("" : "+s"(pf));
-#else
-    const DevView *pf = &v;
-#endif
+    const DevView *pf = v.self;                                  // (addresses from the view's copy in device memory, not held in
+    asm volatile("" : "+s"(pf));                                 // scalar registers across the passes)
     TailView tv{};
     int tpar = 0;
-    if (TAIL) { tv = *pf->tailDev; tpar = PERSIST ? ppar : pf->st->tail_par; }   // (TAIL: this launch adds into the accumulators; uniform scalar loads,
+    if (TAIL) { tv = *pf->tailDev; tpar = pf->st->tail_par; }   // (TAIL: this launch adds into the accumulators; uniform scalar loads,
                                                                 // in flight across the barrier. The per-launch fields of the view live in the kernel arguments only.)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const int blockFail = wfailS[0] + wfailS[1] + wfailS[2] + wfailS[3];

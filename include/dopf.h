@@ -135,9 +135,7 @@ typedef struct dopf_params {
                                   * three-launch chain instead of inside the tail block of the one-launch iteration */
 #define DOPF_F_NET_SMALL_ITEMS 524288 /* networks, one launch for all agents: cut the generators into the ~1024 items the separate
                                   * launches use instead of ~512 larger ones (same partial-sum rows on both chains: bitwise comparisons) */
-#define DOPF_F_PERSIST 1048576 /* copper plates whose x-update is one launch with every block resident (config1, config2): run the
-                                  * iterations of a dopf_iterate call in launches of up to 16 ITERATIONS each — the grid stays, the tail block
-                                  * publishes the new prices to the other blocks (csrc/agents_persist.h; round 4 experiment) */
+#define DOPF_F_PERSIST 1048576 /* retired: accepted, has no effect; the bit is not reused */
 #define DOPF_F_LONG_HORIZON 2097152 /* storages on horizons beyond T = 512 (without it dopf_create refuses them): solved by the long-horizon
                                   * body (csrc/sto_long.h: one block per storage, the horizon in tiles of 2048 timesteps, no limit on T but
                                   * device memory) on the separate-launch chain. For T <= 512 the flag changes nothing. */
@@ -256,8 +254,7 @@ typedef struct dopf_timing {
     int32_t quiet;          /* 1 (networks): no line was flagged, k_slack was not launched (slack_ms is an empty event pair): the dual/price
                                kernel formed the node sums too */
     int32_t sto_lean;       /* 1: the storages of this problem are solved by the lean active-set body (csrc/sto_lean.h) */
-    int32_t persist;        /* 1: dopf_iterate runs several iterations per launch on this context (DOPF_F_PERSIST; this timed call itself
-                               launches iteration by iteration) */
+    int32_t persist;        /* always 0 (DOPF_F_PERSIST is retired; the field keeps the layout) */
     int32_t sto_long;       /* 1: the storages ran on the long-horizon body (csrc/sto_long.h: DOPF_F_LONG_HORIZON, DOPF_F_DEBUG_LONG_STO) */
 } dopf_timing;
 int dopf_iterate_timed(dopf_ctx *ctx, int32_t n_iters, dopf_timing *out);

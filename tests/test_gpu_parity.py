@@ -447,11 +447,11 @@ PERSIST = [
 
 
 @pytest.mark.parametrize("name,make", PERSIST, ids=[t[0] for t in PERSIST])
-def test_hip_persistent_iterations_match_the_launch_per_iteration_chain(hip_api, name, make):
-    """DOPF_F_PERSIST (csrc/agents_persist.h): up to 16 iterations per launch — the grid stays, the tail block publishes the new
-    prices to the other blocks — against one launch per iteration: the same kernels' arithmetic in the same order, so every
-    array is bit-identical, after calls of any length (1, 4 and 16 iterations per launch, mixed), through the cold start (storage
-    blocks that hand storages to the scan body), and the stop test fires at the same iteration and freezes the state."""
+def test_hip_retired_persist_flag_changes_nothing(hip_api, name, make):
+    """DOPF_F_PERSIST is retired: dopf_create still accepts the bit and the context runs the default one-launch copper-plate
+    chain (the tail in the launch, the lean storage body). Every array is bit-identical to a context without the flag, after
+    calls of any length (graphs of 1, 4 and 16 iterations, mixed), through the cold start (storage blocks that hand storages
+    to the scan body), and the stop test fires at the same iteration and freezes the state."""
     pp = make()
     if "mixed" in name:
         rng = np.random.default_rng(5)
@@ -460,7 +460,7 @@ def test_hip_persistent_iterations_match_the_launch_per_iteration_chain(hip_api,
     a = make_engine(hip_api, pp, eps=0.0, gamma=g, flags=_capi.F_PERSIST)
     b = make_engine(hip_api, pp, eps=0.0, gamma=g)
     ta, tb = a.iterate_timed(1), b.iterate_timed(1)
-    assert ta["persist"] == 1 and tb["persist"] == 0 and ta["tail_fused"] == 1 and ta["sto_lean"] == 1
+    assert ta["persist"] == 0 and tb["persist"] == 0 and ta["tail_fused"] == 1 and ta["sto_lean"] == 1
     for n in (1, 2, 5, 16, 37, 64, 3):
         a.iterate(n)
         b.iterate(n)
