@@ -80,6 +80,7 @@ F_LONG_HORIZON = 2097152
 F_DEBUG_LONG_STO = 4194304
 F_WIDE_NETWORK = 8388608
 F_DEBUG_WIDE_NET = 16777216
+F_STO_INITIAL_LEVEL = 33554432
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -169,6 +170,8 @@ class CApi:
             self._sig("multi_get_primal", C.c_int, [ctxp, c_double_p, c_double_p, c_double_p, c_double_p])
             self._sig("multi_size", C.c_int32, [ctxp])
             self._sig("multi_ctx", ctxp, [ctxp, C.c_int32])
+            self._sig("set_storage_initial_level", C.c_int, [ctxp, c_double_p])
+            self._sig("multi_set_storage_initial_level", C.c_int, [ctxp, c_double_p])
 
     def _sig(self, name, restype, argtypes):
         f = getattr(self.lib, self.prefix + name)
@@ -239,13 +242,32 @@ def default_params(**kw) -> DopfParams:
     return q
 
 
+def _initial_level_params(api: CApi, params: Optional[DopfParams], sto_e0, S: int):
+    """(params, e0) for an engine built with sto_e0: the params with F_STO_INITIAL_LEVEL added (a copy), e0 as float64 of
+    length S — or (params, None) when there is nothing to set (sto_e0 None, or all zeros on an API without initial levels)."""
+    if sto_e0 is None:
+        return params, None
+    e0 = _f64(sto_e0, S)
+    if not hasattr(api, "set_storage_initial_level"):
+        if np.any(e0 != 0.0):
+            raise DopfError(f"{api.prefix}*: this API has no storage initial levels (non-zero sto_e0; the reference starts "
+                            "every storage empty)")
+        return params, None
+    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
+    q.flags |= F_STO_INITIAL_LEVEL
+    return q, e0
+
+
 class Engine:
-    """A context of the C ABI with numpy in/out. Mirrors include/dopf.h one to one."""
+    """A context of the C ABI with numpy in/out. Mirrors include/dopf.h one to one.
+    sto_e0 (optional, S values): the storages' initial levels — sets F_STO_INITIAL_LEVEL and calls
+    dopf_set_storage_initial_level after create."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
-                 mode: Optional[int] = None):
+                 mode: Optional[int] = None, sto_e0=None):
         self.api = api
+        params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
         self.N, self.L, self.T = int(N), int(L), int(T)
         gen_mc = _f64(gen_mc)
         sto_mc = _f64(sto_mc)
@@ -268,6 +290,8 @@ class Engine:
         if rc != 0:
             msg = api.last_error(None)
             raise DopfError(f"{api.prefix}create failed ({rc}): {msg.decode() if msg else ''}")
+        if e0 is not None:
+            self.set_initial_levels(e0)
 
     # -- lifecycle -----------------------------------------------------------------------------
     def close(self):
@@ -338,6 +362,14 @@ class Engine:
         w = C.c_int32(0)
         self._chk(self.api.wide_net(self._ctx, C.byref(w)))
         return int(w.value)
+
+    def set_initial_levels(self, e0=None):
+        """dopf_set_storage_initial_level: the level of each storage before timestep 0 (S values, None = all 0); needs
+        F_STO_INITIAL_LEVEL. Takes effect at the next x-update."""
+        if not hasattr(self.api, "set_storage_initial_level"):
+            raise DopfError(f"{self.api.prefix}*: this API has no storage initial levels")
+        arr = None if e0 is None else _f64(e0, self.S)
+        self._chk(self.api.set_storage_initial_level(self._ctx, _dp(arr)))
 
     def warm_start_stats(self):
         """(storages the warm-start kernel solved, storages it left to the scan kernel) in the LAST iteration."""
@@ -485,8 +517,9 @@ class MultiEngine:
     thread per device). Replicated state (duals, consensus, prices, residuals) is read from shard 0."""
 
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
-                 sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None):
+                 sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None):
         self.api = api
+        params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
         self.N, self.L, self.T = int(N), int(L), int(T)
         gen_mc = _f64(gen_mc)
         sto_mc = _f64(sto_mc)
@@ -508,6 +541,13 @@ class MultiEngine:
             msg = api.multi_last_error(None)
             raise DopfError(f"dopf_multi_create failed ({rc}): {msg.decode() if msg else ''}")
         self.n = int(api.multi_size(self._m))
+        if e0 is not None:
+            self.set_initial_levels(e0)
+
+    def set_initial_levels(self, e0=None):
+        """dopf_multi_set_storage_initial_level: all storages' initial levels in the caller's order (None = all 0)."""
+        arr = None if e0 is None else _f64(e0, self.S)
+        self._chk(self.api.multi_set_storage_initial_level(self._m, _dp(arr)))
 
     def _chk(self, rc):
         if rc != 0:

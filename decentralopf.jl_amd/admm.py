@@ -138,6 +138,13 @@ class ADMM:
         self.engine = _capi.Engine(backend if backend is not None else _capi.hip_api(),
                                    params=self.params, mode=backend_mode, **p.engine_kwargs())
 
+    def set_initial_levels(self, e0=None) -> None:
+        """The level of each storage before the first timestep (S values in the order of `storages`; None = all 0), for a
+        horizon that continues where the last one ended. Not in the reference, which starts every storage empty
+        (src/optimization/subproblems.jl:154). Needs flags=F_STO_INITIAL_LEVEL (set for you when a Storage has a non-zero
+        initial_level); takes effect at the next iteration."""
+        self.engine.set_initial_levels(e0)
+
     # -- one iteration -------------------------------------------------------------------------
     def _fetch_result(self) -> Result:
         P, D, C, E = self.engine.get_primal()

@@ -10,6 +10,7 @@ same LP handed to HiGHS (the LP solver that ships with SciPy; no licence):
     EB[t]         sum_n I[n,t] = 0                                                               (:47)
     FlowUpper     ptdf I + U = f_max,   FlowLower   K - ptdf I = f_max                           (:49-51)
     StorageBalance  E[s,t] = E[s,t-1] - D + C, E[s,0] = 0                                        (:53)
+                  (here E[s,0] = initial_level[s] if given: DOPF_F_STO_INITIAL_LEVEL's target; 0 as in the reference by default)
     outputs       objective, P, D, C, line utilisation ptdf I, system price lambda = dual(EB),
                   nodal price = lambda + sum_l (dual(FlowUpper) + dual(FlowLower))[l,t] ptdf[l,:]  (:57-81)
 
@@ -43,9 +44,10 @@ class CentralResult:
     nodal_price: np.ndarray         # (N, T)
 
 
-def solve_central_packed(pp: PackedProblem, *, duals: bool = True) -> CentralResult:
+def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
-    tests/central_lp.aggregate_* first)."""
+    tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
+    side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference)."""
     from scipy import sparse
     from scipy.optimize import linprog
     N, L, T, G, S = pp.N, pp.L, pp.T, pp.G, pp.S
@@ -73,11 +75,16 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True) -> CentralRes
     rEB = r0                                                   # EB[t]: sum_n I[n,t] = 0
     rows.append(r0 + np.tile(tt, N)); cols.append(oI + np.arange(nI)); vals.append(np.ones(nI))
     beq.append(np.zeros(T)); r0 += T
-    k = np.arange(nS)                                          # E[t] - E[t-1] + D - C = 0
+    k = np.arange(nS)                                          # E[t] - E[t-1] + D - C = 0   (t = 0: E[0] + D - C = e0)
     rows += [r0 + k, r0 + k, r0 + k]; cols += [oE + k, oD + k, oC + k]; vals += [np.ones(nS), np.ones(nS), -np.ones(nS)]
     k1 = k[(k % T) > 0]
     rows.append(r0 + k1); cols.append(oE + k1 - 1); vals.append(-np.ones(k1.size))
-    beq.append(np.zeros(nS)); r0 += nS
+    if initial_level is None:
+        initial_level = pp.sto_e0
+    rhs = np.zeros(nS)
+    if initial_level is not None:
+        rhs[::T] = np.asarray(initial_level, dtype=np.float64).reshape(S)
+    beq.append(rhs); r0 += nS
     Aeq = sparse.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(r0, nv))
     rUp = rLo = r0
     if L > 0:
@@ -112,10 +119,10 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True) -> CentralRes
 
 
 def central_reference(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
-                      lines: Sequence[Line], *, verbose: bool = False) -> CentralResult:
+                      lines: Sequence[Line], *, verbose: bool = False, initial_level=None) -> CentralResult:
     """src/opf_central_reference.jl for a case given as the reference's element vectors; `verbose` prints what the
-    script prints (:60-81)."""
-    r = solve_central_packed(pack(nodes, generators, storages, lines))
+    script prints (:60-81). initial_level: (S,) storage levels before the first timestep (None: Storage.initial_level)."""
+    r = solve_central_packed(pack(nodes, generators, storages, lines), initial_level=initial_level)
     if verbose:
         print(f"Objective value: {r.objective}\n")
         print(f"Generator results:\n{r.generation}\n")

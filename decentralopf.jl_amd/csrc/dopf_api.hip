@@ -50,6 +50,20 @@ void keep_error(const dopf_ctx *c)
     if (c && c->err[0]) { strncpy(g_create_err, c->err, 511); g_create_err[511] = 0; }
 }
 
+
+// dopf_set_storage_initial_level's checks: the flag, and 0 <= e0[s] <= emax[s] for the caller's storage s (no NaN)
+int check_initial_levels(dopf_ctx *c, const double *e0)
+{
+    if (!(c->q.flags & DOPF_F_STO_INITIAL_LEVEL))
+        return fail(c, DOPF_E_UNSUPPORTED, "storage initial levels need DOPF_F_STO_INITIAL_LEVEL at dopf_create");
+    if (!e0) return DOPF_OK;
+    for (int i = 0; i < c->v.S; ++i) {
+        const int a = c->sto_perm[i];
+        if (!(e0[a] >= 0.0 && e0[a] <= c->sto_emax_h[i]))
+            return fail(c, DOPF_E_INVALID, "initial level of storage %d is %g, outside [0, max_level = %g]", a, e0[a], c->sto_emax_h[i]);
+    }
+    return DOPF_OK;
+}
 }  // namespace dopf
 
 namespace {
@@ -148,7 +162,9 @@ Plan plan_chain(const Shape &sh, unsigned flags, int cus)
     // The lean active-set body (sto_lean.h): 32-bit element offsets; on a network only where the storage blocks outnumber the
     // chip's resident slots several times — its gain is instruction count, and a grid of one resident round is bound by one
     // block's latency chain, which is no shorter (configs[3]: 114 us against 120 at 100 k agents; its 12.5 k share 43.3 against 41.1).
-    p.stoLean = !((flags & DOPF_F_STO_GENERAL) || (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
+    // DOPF_F_STO_INITIAL_LEVEL: the general bodies' E0 instantiations (a level before timestep 0); the lean body has none
+    p.stoE0 = S > 0 && (flags & DOPF_F_STO_INITIAL_LEVEL);
+    p.stoLean = !((flags & (DOPF_F_STO_GENERAL | DOPF_F_STO_INITIAL_LEVEL)) || (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
                   (L > 0 && (long long)S * p.stoLPS / 256 < 1024)) && !p.stoLong;
     p.genTT = std::min(T, 512);
     p.genR = 512 / p.genTT;
@@ -668,7 +684,15 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         TRY(dev_upload(c, &d, mp));
         v.gen_mp = reinterpret_cast<const double2 *>(d);
     }
-    TRY(dev_upload(c, &v.sto_mc, smc)); TRY(dev_upload(c, &v.sto_pmax, spm)); TRY(dev_upload(c, &v.sto_emax, sem));
+    TRY(dev_upload(c, &v.sto_mc, smc)); TRY(dev_upload(c, &v.sto_pmax, spm));
+    if (c->plan.stoE0) {                    // DOPF_F_STO_INITIAL_LEVEL: the initial levels behind the max levels (sto_e0), all 0 until the setter
+        c->sto_emax_h = sem;
+        std::vector<double> em2(sem);
+        em2.resize(2 * (size_t)S, 0.0);
+        TRY(dev_upload(c, &v.sto_emax, em2));
+    } else {
+        TRY(dev_upload(c, &v.sto_emax, sem));
+    }
     TRY(dev_upload(c, &v.gen_items, gitems)); TRY(dev_upload(c, &v.sto_items, sitems));
     TRY(dev_upload(c, &v.node_gen_beg, ngb)); TRY(dev_upload(c, &v.node_sto_beg, nsb));
     {
@@ -1006,7 +1030,7 @@ int dopf_get_primal(dopf_ctx *c, double *P, double *D, double *C, double *E)
     if ((rc = get_rows(c, D, c->v.D, c->sto_perm))) return rc;
     if ((rc = get_rows(c, C, c->v.C, c->sto_perm))) return rc;
     if (E && c->level_from_primal) {         // the level is rebuilt from D and C (the iteration's kernels do not store it)
-        launch_derive_level(c->v, c->main);
+        launch_derive_level(c->v, c->plan, c->main);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->main));
     }
@@ -1273,6 +1297,21 @@ int dopf_wide_net(const dopf_ctx *c, int32_t *out)
 {
     if (!c || !out) return DOPF_E_INVALID;
     *out = c->plan.wideNet ? 1 : 0;
+    return DOPF_OK;
+}
+
+int dopf_set_storage_initial_level(dopf_ctx *c, const double *e0)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_initial_levels(c, e0)) return rc;
+    if (c->v.S == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<double> h(c->v.S, 0.0);
+    if (e0)
+        for (int i = 0; i < c->v.S; ++i) h[i] = e0[c->sto_perm[i]] + 0.0;      // (+ 0.0: a -0.0 is stored as 0.0)
+    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again)
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_e0(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    HIPCHK(c, hipStreamSynchronize(c->main));
     return DOPF_OK;
 }
 

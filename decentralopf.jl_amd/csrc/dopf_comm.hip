@@ -686,6 +686,18 @@ int dopf_multi_iterate(dopf_multi *m, int32_t n_iters, int32_t *iters_done, int3
     return DOPF_OK;
 }
 
+int dopf_multi_set_storage_initial_level(dopf_multi *m, const double *e0)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all levels as they were
+        for (int i = 0; i < m->n; ++i) {
+            const double *ei = e0 ? e0 + m->s0[i] : nullptr;
+            const int rc = pass == 0 ? check_initial_levels(m->ctx[i], ei) : dopf_set_storage_initial_level(m->ctx[i], ei);
+            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
+        }
+    return DOPF_OK;
+}
+
 int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E)
 {
     if (!m) return DOPF_E_INVALID;

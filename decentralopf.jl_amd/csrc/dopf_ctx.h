@@ -31,6 +31,7 @@ struct dopf_ctx {
     void *own_cons = nullptr;
     double *getter_scratch = nullptr;      // 3 * N * T doubles, allocated at the first getter that needs them (freed with the context)
     std::vector<int> gen_perm, sto_perm;   // sorted position -> caller's index
+    std::vector<double> sto_emax_h;        // DOPF_F_STO_INITIAL_LEVEL: the storages' max_level in sorted order (the setter's bounds)
     dopf::Status host_st{};
     dopf::Status *host_pin = nullptr;       // page-locked landing area of the status read-back (a pageable target is staged: slower)
     unsigned long long solver_fail_seen = 0;   // failures already reported through DOPF_E_SOLVER
@@ -46,6 +47,7 @@ int fail(dopf_ctx *c, int code, const char *fmt, ...);
 void keep_error(const dopf_ctx *c);          // the context's message becomes what dopf_last_error(NULL) returns
 void drop_graphs(dopf_ctx *c);
 int read_status(dopf_ctx *c);
+int check_initial_levels(dopf_ctx *c, const double *e0);   // the checks of dopf_set_storage_initial_level (flag, 0 <= e0 <= emax)
 // dopf_comm.hip
 int check_one_runtime(dopf_ctx *c);           // DOPF_E_UNSUPPORTED when two HIP runtimes are mapped into the process
 int comm_enqueue_allreduce(dopf_ctx *c);      // sum of the consensus buffer over the ranks, on the context's stream

@@ -120,7 +120,8 @@ struct DevView {
     const double *ptdfT;                            // [n + N*l]: the transpose, for the price kernel's node-major threads
     const double *gen_mc, *gen_pmax;
     const double2 *gen_mp;                          // [g] {mc, pmax} side by side: one 16-byte load per row (streaming blocks)
-    const double *sto_mc, *sto_pmax, *sto_emax;
+    const double *sto_mc, *sto_pmax, *sto_emax;     // DOPF_F_STO_INITIAL_LEVEL: sto_emax has 2S entries, the initial levels behind the max levels
+                                                    // (sto_e0(v) below): the view, every kernel's argument, keeps its layout
     const Item *gen_items, *sto_items;
     const int *node_gen_beg, *node_sto_beg;         // N+1 each: agent ranges per node
     const double *node_win;                         // N: bound on |change of an agent's net injection| at the node
@@ -161,6 +162,9 @@ struct DevView {
     Status *st;
     const double *node_na;                          // wide chain: [n] agents at node n as a number (k_reduce's naL, read from memory)
 };
+
+// the storages' initial levels (DOPF_F_STO_INITIAL_LEVEL contexts only: zeros until dopf_set_storage_initial_level), sorted order
+__host__ __device__ inline const double *sto_e0(const DevView &v) { return v.sto_emax + v.S; }
 
 #ifndef DOPF_ACC_REP
 #define DOPF_ACC_REP 16
@@ -220,6 +224,7 @@ struct Plan {
     Consensus consensus;
     bool sliceDual;                 // the one-block dual kernel may add k_reduce's slices itself (DevView::sliceDual)
     bool useWarm, stoLean;          // storage warm start (DevView::use_warm); the lean active-set body (sto_lean.h)
+    bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: the storage bodies' E0 instantiations (initial levels: sto_e0(v))
     bool fuseAgents, fuseNet;       // generators + storages in one launch: k_agents (copper plate, even T), k_net_agents (networks)
     bool tail;                      // the tail of the iteration in the x-update launch (DevView::tailDev)
     bool slackDual;                 // the one-launch dual/price kernel may form the slack sums: no k_reduce (DevView::slackInDual)
@@ -286,7 +291,7 @@ void launch_xchg(const DevView &v, const XchgView &x, hipStream_t s, bool inj_on
 void launch_dual(const DevView &v, const Plan &p, hipStream_t s, const XchgView *xd = nullptr);   // xd: peer exchange inside the one-block kernel
 //      // consensus -> duals, residuals, prices, status
 void launch_derive(const DevView &v, const Plan &p, hipStream_t s, bool from_primal);
-void launch_derive_level(const DevView &v, hipStream_t s);            // E = cumsum(C - D) into v.E
+void launch_derive_level(const DevView &v, const Plan &p, hipStream_t s);   // E = e0 + cumsum(C - D) into v.E (e0 = 0 without p.stoE0)
 void launch_penalty_sums(const DevView &v, double *out /* [3][N][T], device */, hipStream_t s);   // Result.penalty_term, per node
 void launch_node_results(const DevView &v, double *gen, double *dis, double *chg, hipStream_t s);   // [n + N*t] each, device pointers   // consensus -> inj/s/flow/price (no dual step)
 

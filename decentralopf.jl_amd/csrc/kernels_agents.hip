@@ -782,7 +782,7 @@ void launch_gen_update(const DevView &v, hipStream_t s)
 //
 // A group of LPS lanes owns one storage; lane li owns the NCH CONSECUTIVE timesteps li*NCH .. li*NCH+NCH-1.
 // One "scan" evaluates, for a trial price nu, the whole forward recursion
-//     F_t = clamp(F_{t-1} + x_t(nu), 0, emax),  F_0 = 0
+//     F_t = clamp(F_{t-1} + x_t(nu), 0, emax),  F_0 = 0 (E0: F_0 = e0[s], DOPF_F_STO_INITIAL_LEVEL)
 // as an associative scan of clamp-add maps e -> clamp(e + A, LO, HI): NCH maps are composed inside the
 // lane, the lane composites are scanned across the group with DPP row shifts / row broadcasts (no LDS
 // traffic), and the prefix is applied back inside the lane.
@@ -1034,7 +1034,9 @@ struct StoAgent {
 // `item_fail`: number of storages of this item the warm start left over (block-uniform); < 0 = read it
 // FULLT: the horizon fills the lane group exactly (T == LPS * NCH: 24 = 8 x 3, 48 = 16 x 3, 96 = 32 x 3): T is then a
 // compile-time constant and every "is this step inside the horizon" test folds away
-template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false>
+// E0: the level before the first timestep is the storage's initial level sto_e0(v)[s] (DOPF_F_STO_INITIAL_LEVEL), not 0. A template
+// argument: without the flag the instantiations are the code of before, register for register
+template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, bool E0 = false>
 __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, int item_fail)
 {
     constexpr int NG = 256 / LPS;
@@ -1097,6 +1099,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
         ag.mc = live ? v.sto_mc[s] : 0.0;
         ag.pm = live ? v.sto_pmax[s] : 0.0;
         ag.em = live ? v.sto_emax[s] : 0.0;
+        const double e0 = (E0 && live) ? sto_e0(v)[s] : 0.0;       // level before timestep 0
         // rD0/rC0: the nu-independent part of the two gradient offsets (copper plate); D0/C0 otherwise
         double D0[NCH], C0[NCH], nuf[NCH];
 #pragma unroll
@@ -1167,7 +1170,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
             scan_maps<LPS>(inc, lane);
             Map3 ex;
             ex.A = prev_lane<LPS>(inc.A); ex.LO = prev_lane<LPS>(inc.LO); ex.HI = prev_lane<LPS>(inc.HI);
-            double e = li == 0 ? 0.0 : clampd(ex.A, ex.LO, ex.HI);
+            double e = li == 0 ? e0 : (E0 ? clampd(e0 + ex.A, ex.LO, ex.HI) : clampd(ex.A, ex.LO, ex.HI));
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 Sv[c] = e + x[c];
@@ -1302,7 +1305,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
             }
         }
 
-        // ---- final (D, C) at each timestep's price, level E = cumsum(C - D), outputs, partial sums ------
+        // ---- final (D, C) at each timestep's price, level E = e0 + cumsum(C - D), outputs, partial sums ------
         double Dn[NCH], Cn[NCH], run = 0.0;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -1368,11 +1371,11 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
 #endif
 }
 
-template <int LPS, int NCH, bool LINES>
+template <int LPS, int NCH, bool LINES, bool E0>
 __global__ __launch_bounds__(256, 2) void k_sto_update(DevView v)
 {
     if (v.st->halt) return;
-    sto_cold_body<LPS, NCH, LINES>(v, blockIdx.x, -1);
+    sto_cold_body<LPS, NCH, LINES, false, false, E0>(v, blockIdx.x, -1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1534,7 +1537,8 @@ __device__ __forceinline__ int next_lane_i(int x)
 }
 
 // returns the number of storages of the item left to the scan (block-uniform)
-template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false>
+// E0: the first segment starts at sto_e0(v)[s] instead of 0 (DOPF_F_STO_INITIAL_LEVEL; sto_cold_body)
+template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, bool E0 = false>
 __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, const int halt = 0)
 {
     constexpr int NG = 256 / LPS, TP = LPS * NCH;
@@ -1602,6 +1606,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
         const int s = it.a0 + rep * NG + grp;
         const bool live = s < it.a1;
         const double mc = live ? v.sto_mc[s] : 0.0, pm = live ? v.sto_pmax[s] : 0.0, em = live ? v.sto_emax[s] : 0.0;
+        const double e0 = (E0 && live) ? sto_e0(v)[s] : 0.0;     // level before timestep 0
         const bool havenu = live && v.nu_valid[s] != 0;
         // copper plate: the nu-independent parts of the two gradient offsets, rD = rD0 - nu, rC = rC0 + nu
         // (with lines Psi depends on the step itself: D0/C0 are kept and the offsets are built per evaluation)
@@ -1609,7 +1614,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
         int hint[NCH];
         double dq[NCH];                          // C0 - D0 per step: the level trajectory below needs only these
         const double iw = 1.0 / w;
-        double run = 0.0;
+        double run = li == 0 ? e0 : 0.0;         // (the group's prefix sums below then carry the initial level)
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const int t = tbase + c;
@@ -1662,13 +1667,13 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                 bD = w * A0[c] - mc - pc; bC = mc - w * B0[c] - pc;
             }
         };
-        // previous level trajectory -> contacts
+        // previous level trajectory (from this call's initial level: a guess like the rest) -> contacts
         const double inclE = scan_sum<LPS>(run, lane);
         const double prevE = prev_lane<LPS>(inclE);
         const double tolc = 1e-9 * (1.0 + em), tolE = 1e-11 * (1.0 + em), tolr = 1e-12 * (1.0 + em);
         int kind[NCH];                       // 0 free, 1 empty, 2 full
         {
-            double eo = li == 0 ? 0.0 : prevE;
+            double eo = li == 0 ? e0 : prevE;
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const int t = tbase + c;
@@ -1712,7 +1717,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                 for (int c = 0; c < NCH; ++c) {
                     const int t = tbase + c;
                     const bool stc = c == 0 ? st0 : (t < T && ISEND(c - 1));
-                    const double pinfo = c == 0 ? (li == 0 ? 0.0 : plInfo) : TGT(c - 1);
+                    const double pinfo = c == 0 ? (li == 0 ? e0 : plInfo) : TGT(c - 1);      // (the first segment: e0)
                     if (stc) base[send[c]] = pinfo;                  // level at which this segment starts
                     if (ISEND(c)) {
                         nuL[t] = kind[c] != 0 ? nuv[c] : 0.0;        // one price per segment; open last segment: 0
@@ -2150,23 +2155,24 @@ namespace dopf {
 // The scan body as a function of its own (networks): called by k_sto_warm for the rare item the active-set body leaves
 // something of. Inlined, its registers crowd the active-set body (255 VGPRs and spills, 40 % slower, measured); as a
 // separate launch it cost 4 us + a launch gap per iteration for finding nothing to do.
-template <int LPS, int NCH>
+template <int LPS, int NCH, bool E0>
 __device__ __attribute__((noinline)) void sto_cold_lines_call(const DevView *self, const int blk, const int left)
 {
-    sto_cold_body<LPS, NCH, true>(*self, blk, left);
+    sto_cold_body<LPS, NCH, true, false, false, E0>(*self, blk, left);
 }
 
 #ifndef DOPF_WARM_WAVES
 #define DOPF_WARM_WAVES 2
 #endif
-template <int LPS, int NCH, bool LINES, bool LEAN = false>
+template <int LPS, int NCH, bool LINES, bool LEAN = false, bool E0 = false>
 __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_sto_warm(DevView v)
 {
     // (networks, LEAN: the lean body where every table of the item's node is empty — the settled state — else the general one.
     // A template argument, not a branch on v.stoLean: with both bodies in one function the general one ran 6 % slower, measured)
     static_assert(LINES || !LEAN, "copper plates: k_sto_l");
+    static_assert(!(LEAN && E0), "the lean body has no initial level");
     const int left = LEAN ? sto_lean_body<LPS, NCH, false, true, false>(v, blockIdx.x, v.st->halt)
-                          : sto_warm_body<LPS, NCH, LINES>(v, blockIdx.x, v.st->halt);         // ends on a __syncthreads
+                          : sto_warm_body<LPS, NCH, LINES, false, false, E0>(v, blockIdx.x, v.st->halt);         // ends on a __syncthreads
     if (left < 0) return;                                                               // halted
     if (LINES) {                                 // the scan body for what the warm start left over: no k_sto_update launch
         if (left == 0) {                         // (what the scan body writes when there is nothing for it)
@@ -2174,7 +2180,7 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_sto_warm(DevView v)
             for (int t = threadIdx.x; t < v.T; t += 256) v.part_T[(size_t)t * v.rowsT + row] = 0.0;
             if (threadIdx.x == 0) v.part_scost[blockIdx.x] = 0.0;
         } else {
-            sto_cold_lines_call<LPS, NCH>(v.self, blockIdx.x, left);
+            sto_cold_lines_call<LPS, NCH, E0>(v.self, blockIdx.x, left);
         }
     }
 }
@@ -2186,9 +2192,10 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_sto_warm(DevView v)
 // launch: a chain of dependent round trips), the generator items behind them in 256-thread blocks that pass through the
 // wave slots the storages leave free. Alone, either launch is a few hundred short blocks bound by its own latency chain
 // (configs[3]'s share: 12 + 13 us and a kernel boundary); together they overlap.
-template <int LPS, int NCH, bool LEAN>
+template <int LPS, int NCH, bool LEAN, bool E0 = false>
 __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
 {
+    static_assert(!(LEAN && E0), "the lean body has no initial level");
     const int nS = v.nStoItems;
     const bool isGen = (int)blockIdx.x >= nS;
     const int gi = (int)blockIdx.x - nS, si = blockIdx.x;
@@ -2201,14 +2208,14 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
         else gen_lines_body<256, DOPF_NET_GEN_FLIGHT>(v, gi, v.genTT256, v.genR);
     } else {
         const int left = LEAN ? sto_lean_body<LPS, NCH, false, true, false>(v, si, v.st->halt)
-                              : sto_warm_body<LPS, NCH, true>(v, si, v.st->halt);                  // ends on a __syncthreads
+                              : sto_warm_body<LPS, NCH, true, false, false, E0>(v, si, v.st->halt); // ends on a __syncthreads
         if (left < 0) return;                                                           // halted
         if (left == 0) {                     // (what the scan body writes when there is nothing for it)
             const int row = v.sto_items[si].row;
             for (int t = threadIdx.x; t < v.T; t += 256) v.part_T[(size_t)t * v.rowsT + row] = 0.0;
             if (threadIdx.x == 0) v.part_scost[si] = 0.0;
         } else {
-            sto_cold_lines_call<LPS, NCH>(v.self, si, left);
+            sto_cold_lines_call<LPS, NCH, E0>(v.self, si, left);
         }
     }
 #if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
@@ -2219,14 +2226,14 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
 
 // Warm start and, in the same block, the cold scan for what it left over: one launch for the storages of the big
 // copper-plate grids (the separate k_sto_update launch mostly found nothing to do).
-template <int LPS, int NCH, bool LINES, bool TAIL, bool FULLT>
+template <int LPS, int NCH, bool LINES, bool TAIL, bool FULLT, bool E0 = false>
 __global__ __launch_bounds__(256, 3) void k_sto(DevView v)
 {
     // (TAIL: the generator launch in front of this one has added its sums; the grid's last block is the tail block)
     if (TAIL && (int)blockIdx.x == v.nStoItems) { tail_block(v.self); return; }
-    const int left = sto_warm_body<LPS, NCH, LINES, TAIL, FULLT>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
-    if (left < 0) return;                                                                       // __syncthreads: the sto_fail flags are visible)
-    sto_cold_body<LPS, NCH, LINES, TAIL, FULLT>(v, blockIdx.x, left);
+    const int left = sto_warm_body<LPS, NCH, LINES, TAIL, FULLT, E0>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
+    if (left < 0) return;                                                                           // __syncthreads: the sto_fail flags are visible)
+    sto_cold_body<LPS, NCH, LINES, TAIL, FULLT, E0>(v, blockIdx.x, left);
 }
 
 // All x-updates of one copper-plate iteration in ONE launch: blocks [0, nStoItems) solve storages (warm start,
@@ -2236,7 +2243,7 @@ __global__ __launch_bounds__(256, 3) void k_sto(DevView v)
 // ones (interleaving the two kinds in dispatch order starts the last storage blocks late and costs 50 %).
 // The launch runs at the storage code's 3 waves/SIMD, which starves the streaming generator blocks once the
 // grid is large, so dopf_create only fuses grids whose storage blocks are all resident from the start.
-template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT>
+template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT, bool E0 = false>
 __global__ __launch_bounds__(256, 3) void k_agents(DevView v)
 {
     const int nS = v.nStoItems;
@@ -2251,8 +2258,8 @@ __global__ __launch_bounds__(256, 3) void k_agents(DevView v)
         else gen_pair_body<256, TAIL, true>(v, blockIdx.x - nS);
     } else {
         if ((int)blockIdx.x < nS) {
-            const int left = sto_warm_body<LPS, NCH, false, TAIL, FULLT>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
-            if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT>(v, blockIdx.x, left);            // __syncthreads: the sto_fail flags are visible)
+            const int left = sto_warm_body<LPS, NCH, false, TAIL, FULLT, E0>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
+            if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT, E0>(v, blockIdx.x, left);            // __syncthreads: the sto_fail flags are visible)
         } else {
             if (v.st->halt) return;
             gen_pair_skip_body<256, TAIL>(v, blockIdx.x - nS);
@@ -2347,6 +2354,7 @@ static void with_bool(bool b, F &&f)
     else f(std::false_type{});
 }
 
+// (p.stoE0, DOPF_F_STO_INITIAL_LEVEL: the general bodies' E0 instantiations; plan_chain keeps such contexts off the lean body)
 template <int LPS, int NCH>
 static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
 {
@@ -2356,6 +2364,7 @@ static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
         with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NC, [&](auto full) {
             constexpr bool TL = decltype(tail)::value, FU = decltype(full)::value;
             if (p.stoLean) hipLaunchKernelGGL((k_sto_l<LPS, NC, TL, FU>), grid, dim3(256), 0, s, v);
+            else if (p.stoE0) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, true>), grid, dim3(256), 0, s, v);
             else hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU>), grid, dim3(256), 0, s, v);
         }); });
         return;
@@ -2364,11 +2373,15 @@ static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
     // body itself for what it leaves over
     if (v.use_warm) {
         if (p.stoLean) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        else if (p.stoE0) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false>), dim3(v.nStoItems), dim3(256), 0, s, v);
         return;
     }
-    if (v.L > 0) hipLaunchKernelGGL((k_sto_update<LPS, NCH, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
-    else hipLaunchKernelGGL((k_sto_update<LPS, NCH, false>), dim3(v.nStoItems), dim3(256), 0, s, v);
+    with_bool(p.stoE0, [&](auto e0) {
+        constexpr bool E0 = decltype(e0)::value;
+        if (v.L > 0) hipLaunchKernelGGL((k_sto_update<LPS, NCH, true, E0>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        else hipLaunchKernelGGL((k_sto_update<LPS, NCH, false, E0>), dim3(v.nStoItems), dim3(256), 0, s, v);
+    });
 }
 
 template <int LPS, int NCH>
@@ -2378,6 +2391,7 @@ static void launch_agents_t(const DevView &v, const Plan &p, hipStream_t s)
     with_bool(v.genSkip, [&](auto skip) { with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NCH, [&](auto full) {
         constexpr bool SK = decltype(skip)::value, TL = decltype(tail)::value, FU = decltype(full)::value;
         if (p.stoLean) hipLaunchKernelGGL((k_agents_l<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
+        else if (p.stoE0) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, true>), grid, dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
     }); }); });
 }
@@ -2392,6 +2406,7 @@ void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s)
     const dim3 grid(v.nStoItems + v.nGenItems);
     with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) {
         if (p.stoLean) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
+        else if (p.stoE0) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, true>), grid, dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false>), grid, dim3(256), 0, s, v);
     });
 }
@@ -2400,8 +2415,11 @@ void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s)
 {
     if (v.nStoItems == 0) return;
     if (p.stoLong) {                        // DOPF_F_LONG_HORIZON (sto_long.h): one block per item, any horizon
-        if (v.L > 0) hipLaunchKernelGGL((k_sto_long<true>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
-        else hipLaunchKernelGGL((k_sto_long<false>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
+        with_bool(p.stoE0, [&](auto e0) {
+            constexpr bool E0 = decltype(e0)::value;
+            if (v.L > 0) hipLaunchKernelGGL((k_sto_long<true, E0>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
+            else hipLaunchKernelGGL((k_sto_long<false, E0>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
+        });
         return;
     }
     with_sto_pair<kAllPairs>(p, [&](auto lps, auto nch) { launch_sto_t<decltype(lps)::value, decltype(nch)::value>(v, p, s); });

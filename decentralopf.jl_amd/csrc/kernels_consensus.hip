@@ -1820,12 +1820,12 @@ __global__ __launch_bounds__(256) void k_derive_cons(DevView v)
     if (v.L > 0) v.prev_node[i] = sum;        // what the next iteration's node changes refer to
 }
 
-__global__ __launch_bounds__(256) void k_derive_level(DevView v)
+__global__ __launch_bounds__(256) void k_derive_level(DevView v, const double *e0 /* S, or null: 0 */)
 {
     const int T = v.T;
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= v.S) return;
-    double e = 0.0;
+    double e = e0 ? e0[s] : 0.0;                      // DOPF_F_STO_INITIAL_LEVEL: the level before timestep 0
     for (int t = 0; t < T; ++t) {
         e += v.C[(size_t)s * T + t] - v.D[(size_t)s * T + t];
         v.E[(size_t)s * T + t] = e;
@@ -1854,10 +1854,11 @@ __global__ __launch_bounds__(256) void k_node_results(DevView v, double *gen, do
     }
 }
 
-// ResultStorage.level (results.jl:4): E = cumsum(C - D), on request (the solve kernels do not store it)
-void launch_derive_level(const DevView &v, hipStream_t s)
+// ResultStorage.level (results.jl:4): E = e0 + cumsum(C - D), on request (the solve kernels do not store it; e0 = 0 without
+// DOPF_F_STO_INITIAL_LEVEL)
+void launch_derive_level(const DevView &v, const Plan &p, hipStream_t s)
 {
-    if (v.S > 0) hipLaunchKernelGGL(k_derive_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v);
+    if (v.S > 0) hipLaunchKernelGGL(k_derive_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, p.stoE0 ? sto_e0(v) : nullptr);
 }
 
 // Result.penalty_term (reference src/structures/results.jl:66-70 with sum_up, src/helpers/penalty_terms.jl:1-6): the three
@@ -1911,7 +1912,7 @@ void launch_derive(const DevView &v, const Plan &p, hipStream_t s, bool from_pri
     const size_t NT = (size_t)v.N * v.T;
     if (from_primal) {        // serial over a node's agents: fine for tests / resume, not a hot path
         hipLaunchKernelGGL(k_derive_cons, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, s, v);
-        if (v.S > 0) hipLaunchKernelGGL(k_derive_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v);
+        launch_derive_level(v, p, s);
     }
     launch_consensus<false>(v, p, s, nullptr);
 }

@@ -34,7 +34,8 @@ struct LongCand {
     double Fp, Fm;      // distance to the nearest kink above / below nu over the run that ends at o (INFINITY: none)
 };
 
-template <bool LINES>
+// E0: the first tile is entered at the storage's initial level sto_e0(v)[s] (DOPF_F_STO_INITIAL_LEVEL), not at 0
+template <bool LINES, bool E0 = false>
 __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
 {
     if (v.st->halt) return;
@@ -58,6 +59,7 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
         const size_t row = (size_t)s * T;
         double *nuf = v.nu_prev + row;              // the price of each timestep, as the recursion assigns it
         const double tol = 1e-11 * (1.0 + em);
+        const double e0 = E0 ? sto_e0(v)[s] : 0.0;   // level before timestep 0
 
         // the lane's inputs of timesteps tbase .. tbase + NCH - 1 (those > lim: zeros, never evaluated)
         double D0[NCH], C0[NCH], P0[NCH], K0[NCH];
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
         // unclamped level leaves the band (classification, lim = k).
         auto scan = [&](double nu, int lim, bool root, int vv) -> LongCand {
             LongCand cd{-1, 0.0, 0.0, INFINITY, INFINITY};
-            double eT = 0.0;                                    // level entering the tile
+            double eT = e0;                                     // level entering the tile
             double cR = 0.0, cFp = INFINITY, cFm = INFINITY;    // slope / kinks since the last clamped step before the tile
             const int nt = lim / kLongTile + 1;
             for (int tb = 0; tb < nt; ++tb) {

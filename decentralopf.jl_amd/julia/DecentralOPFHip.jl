@@ -126,6 +126,7 @@ const DOPF_F_COMM_P2P = 1024      # include/dopf.h
 const DOPF_F_LONG_HORIZON = 2097152  # include/dopf.h
 const DOPF_F_WIDE_NETWORK = 8388608  # include/dopf.h
 const DOPF_F_DEBUG_WIDE_NET = 16777216  # include/dopf.h (tests)
+const DOPF_F_STO_INITIAL_LEVEL = 33554432  # include/dopf.h
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -139,7 +140,8 @@ library, a few microseconds instead of tens for the small vector of a copper pla
 reference's literals `w_flow = 10`, `w_prox = 1`, `eps = 1e-3`, `mask_thr = 1e-2`.
 Storages on horizons beyond 512 timesteps (an hourly year: T = 8 760) need `flags = DOPF_F_LONG_HORIZON`
 (the long-horizon storage body; without the flag the library refuses them). Networks of more than 2 048 lines
-need `flags = DOPF_F_WIDE_NETWORK` (the wide-network chain; without it the library refuses them). Flags combine with `|`.
+need `flags = DOPF_F_WIDE_NETWORK` (the wide-network chain; without it the library refuses them). Storages that start a
+horizon from a given level (see `set_initial_levels!`) need `flags = DOPF_F_STO_INITIAL_LEVEL`. Flags combine with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
@@ -217,6 +219,29 @@ function dopf_primal(admm::ADMM)
                          admm.ctx, P, D, C, E), admm.ctx)
     end
     return P, D, C, E
+end
+
+"""
+    set_initial_levels!(admm, e0)
+
+The level of each storage before the first timestep (`e0[s]`, in the order of `storages`, `0 <= e0[s] <= max_level`;
+`nothing` = all 0), for a horizon that continues where the last one ended. The reference starts every storage empty
+(src/optimization/subproblems.jl:154); the ADMM must have been created with `flags = DOPF_F_STO_INITIAL_LEVEL`. Takes
+effect at the next iteration.
+"""
+function set_initial_levels!(admm::ADMM, e0::Union{Nothing, Vector{Float64}})
+    S = length(admm.storages)
+    e0 === nothing || length(e0) == S || error("set_initial_levels!: expected $S levels, got $(length(e0))")
+    p = e0 === nothing ? Ptr{Cdouble}(C_NULL) : pointer(e0)
+    GC.@preserve e0 begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_storage_initial_level, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi, p),
+                             admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_storage_initial_level, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, p), admm.ctx)
+        end
+    end
+    return admm
 end
 
 """The fields of the reference's Result (src/structures/results.jl:37-48) for the last solved iteration."""

@@ -5,11 +5,13 @@ Mirrors, for the Python host (Julia is not in this image; the Julia shim is juli
   calculate_ptdf(nodes, lines)           src/helpers/ptdf.jl:1-41   (one-off O(N^3) set-up, stays on host)
   three_node_case()                      src/cases/three_node.jl:1-21
 Numeric struct fields are Int in the reference and are promoted to Float64 when packed.
+Storage.initial_level is not in the reference (which starts every storage empty, src/optimization/subproblems.jl:154): the
+level before the first timestep, for runs that continue a previous horizon (DOPF_F_STO_INITIAL_LEVEL).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -38,6 +40,7 @@ class Storage:
     max_level: int
     plot_color: str
     node: Node
+    initial_level: float = 0.0      # level before the first timestep, 0 <= initial_level <= max_level (not in the reference)
 
 
 @dataclass(eq=False)
@@ -106,6 +109,7 @@ class PackedProblem:
     sto_emax: np.ndarray
     sto_node: np.ndarray
     meta: dict = field(default_factory=dict)
+    sto_e0: Optional[np.ndarray] = None     # (S,) Storage.initial_level; None = all 0
 
     @property
     def G(self):
@@ -116,13 +120,17 @@ class PackedProblem:
         return int(self.sto_mc.size)
 
     def engine_kwargs(self):
-        """Arguments of _capi.Engine in the C ABI's memory order (column-major matrices)."""
-        return dict(
+        """Arguments of _capi.Engine in the C ABI's memory order (column-major matrices). sto_e0 only when some storage
+        starts above 0 (engines then run with F_STO_INITIAL_LEVEL; everything else sees the arguments of before)."""
+        kw = dict(
             N=self.N, L=self.L, T=self.T,
             demand=np.asarray(self.demand, dtype=np.float64).reshape(self.N, self.T).T.ravel(),
             ptdf=np.asarray(self.ptdf, dtype=np.float64).reshape(self.L, self.N).T.ravel(),
             f_max=self.f_max, gen_mc=self.gen_mc, gen_pmax=self.gen_pmax, gen_node=self.gen_node,
             sto_mc=self.sto_mc, sto_pmax=self.sto_pmax, sto_emax=self.sto_emax, sto_node=self.sto_node)
+        if self.sto_e0 is not None and np.any(np.asarray(self.sto_e0) != 0.0):
+            kw["sto_e0"] = np.asarray(self.sto_e0, dtype=np.float64)
+        return kw
 
     def shard(self, rank: int, world: int) -> "PackedProblem":
         """Contiguous slice of the agent lists for one rank (network data replicated)."""
@@ -138,7 +146,8 @@ class PackedProblem:
             sto_mc=self.sto_mc[s0:s1], sto_pmax=self.sto_pmax[s0:s1], sto_emax=self.sto_emax[s0:s1],
             sto_node=self.sto_node[s0:s1],
             meta=dict(self.meta, rank=rank, world=world, gen_range=(g0, g1), sto_range=(s0, s1),
-                      n_agents_global=self.G + self.S))
+                      n_agents_global=self.G + self.S),
+            sto_e0=None if self.sto_e0 is None else self.sto_e0[s0:s1])
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -162,4 +171,5 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         sto_mc=f64(s.marginal_costs for s in storages),
         sto_pmax=f64(s.max_power for s in storages),
         sto_emax=f64(s.max_level for s in storages),
-        sto_node=i32(idx[id(s.node)] for s in storages))
+        sto_node=i32(idx[id(s.node)] for s in storages),
+        sto_e0=f64(s.initial_level for s in storages))

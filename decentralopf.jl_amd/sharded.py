@@ -95,6 +95,15 @@ class ShardedADMM:
     def sync(self):
         return self.engine.sync()
 
+    def set_initial_levels(self, e0=None) -> None:
+        """All storages' levels before the first timestep (problem.S values, global order; None = all 0): this rank sets its
+        slice (dopf_set_storage_initial_level). Needs F_STO_INITIAL_LEVEL in the params; every rank calls it between steps."""
+        if e0 is None:
+            self.engine.set_initial_levels(None)
+            return
+        s0, s1 = self.shard.meta["sto_range"]
+        self.engine.set_initial_levels(np.asarray(e0, dtype=np.float64).reshape(self.problem.S)[s0:s1])
+
     def run(self, max_iters: int, check_every: int = 16):
         """Iterate until the stop test holds (checked every `check_every` iterations) or max_iters."""
         done = 0

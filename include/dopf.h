@@ -143,6 +143,12 @@ typedef struct dopf_params {
                                   * breakpoint tables, dual and price steps and line slack sums whose LDS does not grow with N or L). Limits:
                                   * L*N and L*T below 2^31, and the tables (N*T*(6L+1) doubles + 2 N*T*L doubles of slack partials) must fit
                                   * the device's free memory, else DOPF_E_NOMEM naming the bytes. For L <= 2048 the flag changes nothing. */
+#define DOPF_F_STO_INITIAL_LEVEL 33554432 /* storages start from a given level: the context keeps an initial level e0[s] per storage (all 0
+                                  * until dopf_set_storage_initial_level), and every storage body solves with E_t = e0 + sum_{tau<=t} (C - D) in
+                                  * [0, emax] instead of the reference's empty start (src/optimization/subproblems.jl:154: E[t] == (t == 1 ? 0 :
+                                  * E[t-1]) + C[t] - D[t]; src/opf_central_reference.jl:53: E[s,0] = 0). Runs on the general active-set body (as with
+                                  * DOPF_F_STO_GENERAL), the scan body and the long-horizon body; with every e0 = 0 the results are bit for bit those of
+                                  * DOPF_F_STO_GENERAL. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -267,6 +273,15 @@ double dopf_last_call_ms(const dopf_ctx *ctx);
 
 int64_t dopf_solver_failures(dopf_ctx *ctx);
 
+/* DOPF_F_STO_INITIAL_LEVEL: the level of each storage before the first timestep, e0[S] in the caller's order of this context's
+ * storages (NULL = all 0), 0 <= e0[s] <= max_level[s]. The reference pins it to 0 (src/optimization/subproblems.jl:154,
+ * src/opf_central_reference.jl:53); a receding-horizon caller hands the next window the level the last one reached. May be called
+ * between any two calls that iterate; takes effect at the next x-update. The values are copied before the call returns, in order
+ * on the context's stream (the captured iteration graphs read the same device array and stay valid). dopf_get_primal's E and
+ * dopf_set_state's levels start from it. DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID for a NaN, a negative value or one
+ * above max_level (the stored levels are then unchanged). */
+int dopf_set_storage_initial_level(dopf_ctx *ctx, const double *e0);
+
 /* ---- the central reference on the device ---------------------------------------------------------------
  * Replaces src/opf_central_reference.jl:16-81 (one JuMP model of the whole multi-period DC-OPF, solved by Gurobi): the same
  * LP — variables P, D, C, E in their boxes, energy balance per timestep, |ptdf * injection| <= f_max, storage balance —
@@ -330,6 +345,9 @@ int  dopf_multi_iterate(dopf_multi *m, int32_t n_iters, int32_t *iters_done, int
 /* Primal rows of all shards in the caller's agent order (layout of dopf_get_primal). */
 int  dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E);
 int32_t dopf_multi_size(const dopf_multi *m);
+/* dopf_set_storage_initial_level for all storages, e0[S] in the caller's order (NULL = all 0): each shard gets its slice. Every
+ * shard's values are checked before any is stored. */
+int  dopf_multi_set_storage_initial_level(dopf_multi *m, const double *e0);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);
