@@ -81,6 +81,7 @@ F_DEBUG_LONG_STO = 4194304
 F_WIDE_NETWORK = 8388608
 F_DEBUG_WIDE_NET = 16777216
 F_STO_INITIAL_LEVEL = 33554432
+F_STO_TERMINAL_LEVEL = 67108864
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -172,6 +173,8 @@ class CApi:
             self._sig("multi_ctx", ctxp, [ctxp, C.c_int32])
             self._sig("set_storage_initial_level", C.c_int, [ctxp, c_double_p])
             self._sig("multi_set_storage_initial_level", C.c_int, [ctxp, c_double_p])
+            self._sig("set_storage_terminal_level", C.c_int, [ctxp, c_double_p, c_double_p])
+            self._sig("multi_set_storage_terminal_level", C.c_int, [ctxp, c_double_p, c_double_p])
 
     def _sig(self, name, restype, argtypes):
         f = getattr(self.lib, self.prefix + name)
@@ -258,16 +261,37 @@ def _initial_level_params(api: CApi, params: Optional[DopfParams], sto_e0, S: in
     return q, e0
 
 
+def _terminal_level_params(api: CApi, params: Optional[DopfParams], sto_end_lo, sto_end_hi, sto_emax, S: int):
+    """(params, (lo, hi)) for an engine built with a terminal band: the params with F_STO_TERMINAL_LEVEL added (a copy), the band
+    as float64 arrays of length S (a None side: 0 resp. sto_emax) — or (params, None) when there is nothing to set (both None, or
+    the default band [0, max_level] on an API without terminal levels)."""
+    if sto_end_lo is None and sto_end_hi is None:
+        return params, None
+    em = _f64(sto_emax, S)
+    lo = np.zeros(S) if sto_end_lo is None else _f64(sto_end_lo, S)
+    hi = em.copy() if sto_end_hi is None else _f64(sto_end_hi, S)
+    if not hasattr(api, "set_storage_terminal_level"):
+        if np.any(lo != 0.0) or np.any(hi != em):
+            raise DopfError(f"{api.prefix}*: this API has no storage terminal levels (a band other than [0, max_level]; the "
+                            "reference leaves the last level free)")
+        return params, None
+    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
+    q.flags |= F_STO_TERMINAL_LEVEL
+    return q, (lo, hi)
+
+
 class Engine:
     """A context of the C ABI with numpy in/out. Mirrors include/dopf.h one to one.
     sto_e0 (optional, S values): the storages' initial levels — sets F_STO_INITIAL_LEVEL and calls
-    dopf_set_storage_initial_level after create."""
+    dopf_set_storage_initial_level after create. sto_end_lo / sto_end_hi (optional, S values each): the band of the level
+    after the last timestep — sets F_STO_TERMINAL_LEVEL and calls dopf_set_storage_terminal_level (after the initial levels)."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
-                 mode: Optional[int] = None, sto_e0=None):
+                 mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None):
         self.api = api
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
+        params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
         self.N, self.L, self.T = int(N), int(L), int(T)
         gen_mc = _f64(gen_mc)
         sto_mc = _f64(sto_mc)
@@ -292,6 +316,8 @@ class Engine:
             raise DopfError(f"{api.prefix}create failed ({rc}): {msg.decode() if msg else ''}")
         if e0 is not None:
             self.set_initial_levels(e0)
+        if band is not None:
+            self.set_terminal_levels(*band)
 
     # -- lifecycle -----------------------------------------------------------------------------
     def close(self):
@@ -370,6 +396,15 @@ class Engine:
             raise DopfError(f"{self.api.prefix}*: this API has no storage initial levels")
         arr = None if e0 is None else _f64(e0, self.S)
         self._chk(self.api.set_storage_initial_level(self._ctx, _dp(arr)))
+
+    def set_terminal_levels(self, lo=None, hi=None):
+        """dopf_set_storage_terminal_level: the band [lo, hi] of each storage's level after the last timestep (S values each;
+        both None = the default band [0, max_level]); needs F_STO_TERMINAL_LEVEL. Takes effect at the next x-update."""
+        if not hasattr(self.api, "set_storage_terminal_level"):
+            raise DopfError(f"{self.api.prefix}*: this API has no storage terminal levels")
+        a = None if lo is None else _f64(lo, self.S)
+        b = None if hi is None else _f64(hi, self.S)
+        self._chk(self.api.set_storage_terminal_level(self._ctx, _dp(a), _dp(b)))
 
     def warm_start_stats(self):
         """(storages the warm-start kernel solved, storages it left to the scan kernel) in the LAST iteration."""
@@ -517,9 +552,11 @@ class MultiEngine:
     thread per device). Replicated state (duals, consensus, prices, residuals) is read from shard 0."""
 
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
-                 sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None):
+                 sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
+                 sto_end_lo=None, sto_end_hi=None):
         self.api = api
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
+        params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
         self.N, self.L, self.T = int(N), int(L), int(T)
         gen_mc = _f64(gen_mc)
         sto_mc = _f64(sto_mc)
@@ -543,11 +580,19 @@ class MultiEngine:
         self.n = int(api.multi_size(self._m))
         if e0 is not None:
             self.set_initial_levels(e0)
+        if band is not None:
+            self.set_terminal_levels(*band)
 
     def set_initial_levels(self, e0=None):
         """dopf_multi_set_storage_initial_level: all storages' initial levels in the caller's order (None = all 0)."""
         arr = None if e0 is None else _f64(e0, self.S)
         self._chk(self.api.multi_set_storage_initial_level(self._m, _dp(arr)))
+
+    def set_terminal_levels(self, lo=None, hi=None):
+        """dopf_multi_set_storage_terminal_level: all storages' terminal bands in the caller's order (both None = [0, max_level])."""
+        a = None if lo is None else _f64(lo, self.S)
+        b = None if hi is None else _f64(hi, self.S)
+        self._chk(self.api.multi_set_storage_terminal_level(self._m, _dp(a), _dp(b)))
 
     def _chk(self, rc):
         if rc != 0:

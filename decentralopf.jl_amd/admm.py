@@ -145,6 +145,13 @@ class ADMM:
         initial_level); takes effect at the next iteration."""
         self.engine.set_initial_levels(e0)
 
+    def set_terminal_levels(self, lo=None, hi=None) -> None:
+        """The band [lo, hi] of each storage's level after the last timestep (S values each in the order of `storages`; both
+        None = [0, max_level]): "end at least at X" is [X, max_level], a cyclic horizon lo = hi = the initial level. Not in the
+        reference, which leaves that level free. Needs flags=F_STO_TERMINAL_LEVEL (set for you when a Storage has a band other
+        than the default); takes effect at the next iteration."""
+        self.engine.set_terminal_levels(lo, hi)
+
     # -- one iteration -------------------------------------------------------------------------
     def _fetch_result(self) -> Result:
         P, D, C, E = self.engine.get_primal()

@@ -10,7 +10,8 @@ same LP handed to HiGHS (the LP solver that ships with SciPy; no licence):
     EB[t]         sum_n I[n,t] = 0                                                               (:47)
     FlowUpper     ptdf I + U = f_max,   FlowLower   K - ptdf I = f_max                           (:49-51)
     StorageBalance  E[s,t] = E[s,t-1] - D + C, E[s,0] = 0                                        (:53)
-                  (here E[s,0] = initial_level[s] if given: DOPF_F_STO_INITIAL_LEVEL's target; 0 as in the reference by default)
+                  (here E[s,0] = initial_level[s] if given: DOPF_F_STO_INITIAL_LEVEL's target; 0 as in the reference by default;
+                  E[s,T] in [lo[s], hi[s]] if a terminal band is given: DOPF_F_STO_TERMINAL_LEVEL's; [0, max_level] by default)
     outputs       objective, P, D, C, line utilisation ptdf I, system price lambda = dual(EB),
                   nodal price = lambda + sum_l (dual(FlowUpper) + dual(FlowLower))[l,t] ptdf[l,:]  (:57-81)
 
@@ -44,10 +45,12 @@ class CentralResult:
     nodal_price: np.ndarray         # (N, T)
 
 
-def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None) -> CentralResult:
+def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
     tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
-    side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference)."""
+    side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference). terminal_level:
+    (lo, hi), (S,) each, the bounds of the level after the last timestep E[:, T-1] (None: the packed case's band, else
+    [0, max_level] as in the reference)."""
     from scipy import sparse
     from scipy.optimize import linprog
     N, L, T, G, S = pp.N, pp.L, pp.T, pp.G, pp.S
@@ -96,6 +99,13 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
         rUp, rLo = r0, r0 + nL
         Aeq = sparse.vstack([Aeq, up, lo], format="csr")
         beq += [np.repeat(pp.f_max, T), np.repeat(pp.f_max, T)]
+    if terminal_level is None and (pp.sto_end_lo is not None or pp.sto_end_hi is not None):
+        terminal_level = pp.terminal_band()
+    if terminal_level is not None and S > 0:
+        lb, ub = np.array(lb, dtype=np.float64), np.array(ub, dtype=np.float64)
+        last = oE + np.arange(S) * T + (T - 1)
+        lb[last] = np.asarray(terminal_level[0], dtype=np.float64).reshape(S)
+        ub[last] = np.asarray(terminal_level[1], dtype=np.float64).reshape(S)
     res = linprog(c, A_eq=Aeq, b_eq=np.concatenate(beq), bounds=np.stack([lb, ub], axis=1), method="highs")
     if res.status != 0:
         raise RuntimeError(f"central LP: {res.message}")
@@ -119,10 +129,13 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
 
 
 def central_reference(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
-                      lines: Sequence[Line], *, verbose: bool = False, initial_level=None) -> CentralResult:
+                      lines: Sequence[Line], *, verbose: bool = False, initial_level=None,
+                      terminal_level=None) -> CentralResult:
     """src/opf_central_reference.jl for a case given as the reference's element vectors; `verbose` prints what the
-    script prints (:60-81). initial_level: (S,) storage levels before the first timestep (None: Storage.initial_level)."""
-    r = solve_central_packed(pack(nodes, generators, storages, lines), initial_level=initial_level)
+    script prints (:60-81). initial_level: (S,) storage levels before the first timestep (None: Storage.initial_level).
+    terminal_level: (lo, hi) bounds of the level after the last timestep (None: Storage.terminal_level_min / _max)."""
+    r = solve_central_packed(pack(nodes, generators, storages, lines), initial_level=initial_level,
+                             terminal_level=terminal_level)
     if verbose:
         print(f"Objective value: {r.objective}\n")
         print(f"Generator results:\n{r.generation}\n")

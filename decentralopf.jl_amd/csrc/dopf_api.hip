@@ -51,16 +51,50 @@ void keep_error(const dopf_ctx *c)
 }
 
 
-// dopf_set_storage_initial_level's checks: the flag, and 0 <= e0[s] <= emax[s] for the caller's storage s (no NaN)
+// DOPF_F_STO_TERMINAL_LEVEL: the band [lo, hi] meets the end levels reachable from e0 in T steps of at most pm,
+// [max(0, e0 - T pm), min(em, e0 + T pm)]
+static bool band_reachable(double e0, double lo, double hi, double pm, double em, int T)
+{
+    const double span = (double)T * pm;
+    return lo <= std::min(em, e0 + span) && hi >= std::max(0.0, e0 - span);
+}
+
+// dopf_set_storage_initial_level's checks: the flag, and 0 <= e0[s] <= emax[s] for the caller's storage s (no NaN); with
+// DOPF_F_STO_TERMINAL_LEVEL also that the stored band stays reachable from e0 (NULL: from 0)
 int check_initial_levels(dopf_ctx *c, const double *e0)
 {
     if (!(c->q.flags & DOPF_F_STO_INITIAL_LEVEL))
         return fail(c, DOPF_E_UNSUPPORTED, "storage initial levels need DOPF_F_STO_INITIAL_LEVEL at dopf_create");
-    if (!e0) return DOPF_OK;
+    const bool band = (c->q.flags & DOPF_F_STO_TERMINAL_LEVEL) != 0;
+    if (!e0 && !band) return DOPF_OK;
     for (int i = 0; i < c->v.S; ++i) {
         const int a = c->sto_perm[i];
-        if (!(e0[a] >= 0.0 && e0[a] <= c->sto_emax_h[i]))
-            return fail(c, DOPF_E_INVALID, "initial level of storage %d is %g, outside [0, max_level = %g]", a, e0[a], c->sto_emax_h[i]);
+        const double x = e0 ? e0[a] : 0.0;
+        if (!(x >= 0.0 && x <= c->sto_emax_h[i]))
+            return fail(c, DOPF_E_INVALID, "initial level of storage %d is %g, outside [0, max_level = %g]", a, x, c->sto_emax_h[i]);
+        if (band && !band_reachable(x, c->sto_lo_h[i], c->sto_hi_h[i], c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T))
+            return fail(c, DOPF_E_INVALID, "initial level %g of storage %d leaves its terminal band [%g, %g] unreachable in %d steps of %g",
+                        x, a, c->sto_lo_h[i], c->sto_hi_h[i], c->v.T, c->sto_pmax_h[i]);
+    }
+    return DOPF_OK;
+}
+
+// dopf_set_storage_terminal_level's checks: the flag, both arrays or neither, 0 <= lo <= hi <= emax (no NaN), and the band reachable
+// from the stored initial level
+int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi)
+{
+    if (!(c->q.flags & DOPF_F_STO_TERMINAL_LEVEL))
+        return fail(c, DOPF_E_UNSUPPORTED, "storage terminal levels need DOPF_F_STO_TERMINAL_LEVEL at dopf_create");
+    if (!lo && !hi) return DOPF_OK;
+    if (!lo || !hi) return fail(c, DOPF_E_INVALID, "storage terminal levels: lo and hi must both be given or both be NULL");
+    for (int i = 0; i < c->v.S; ++i) {
+        const int a = c->sto_perm[i];
+        const double l = lo[a], h = hi[a], em = c->sto_emax_h[i];
+        if (!(l >= 0.0 && h <= em && l <= h))
+            return fail(c, DOPF_E_INVALID, "terminal band of storage %d is [%g, %g], not inside [0, max_level = %g] (or empty)", a, l, h, em);
+        if (!band_reachable(c->sto_e0_h[i], l, h, c->sto_pmax_h[i], em, c->v.T))
+            return fail(c, DOPF_E_INVALID, "terminal band [%g, %g] of storage %d is unreachable from its initial level %g in %d steps of %g",
+                        l, h, a, c->sto_e0_h[i], c->v.T, c->sto_pmax_h[i]);
     }
     return DOPF_OK;
 }
@@ -162,9 +196,12 @@ Plan plan_chain(const Shape &sh, unsigned flags, int cus)
     // The lean active-set body (sto_lean.h): 32-bit element offsets; on a network only where the storage blocks outnumber the
     // chip's resident slots several times — its gain is instruction count, and a grid of one resident round is bound by one
     // block's latency chain, which is no shorter (configs[3]: 114 us against 120 at 100 k agents; its 12.5 k share 43.3 against 41.1).
-    // DOPF_F_STO_INITIAL_LEVEL: the general bodies' E0 instantiations (a level before timestep 0); the lean body has none
+    // DOPF_F_STO_INITIAL_LEVEL / DOPF_F_STO_TERMINAL_LEVEL: the general bodies' level-mode instantiations (a level before timestep 0;
+    // and a band after the last one); the lean body has none
     p.stoE0 = S > 0 && (flags & DOPF_F_STO_INITIAL_LEVEL);
-    p.stoLean = !((flags & (DOPF_F_STO_GENERAL | DOPF_F_STO_INITIAL_LEVEL)) || (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
+    p.stoLV = S == 0 ? 0 : (flags & DOPF_F_STO_TERMINAL_LEVEL) ? 2 : (flags & DOPF_F_STO_INITIAL_LEVEL) ? 1 : 0;
+    p.stoLean = !((flags & (DOPF_F_STO_GENERAL | DOPF_F_STO_INITIAL_LEVEL | DOPF_F_STO_TERMINAL_LEVEL)) ||
+                  (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
                   (L > 0 && (long long)S * p.stoLPS / 256 < 1024)) && !p.stoLong;
     p.genTT = std::min(T, 512);
     p.genR = 512 / p.genTT;
@@ -685,10 +722,17 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         v.gen_mp = reinterpret_cast<const double2 *>(d);
     }
     TRY(dev_upload(c, &v.sto_mc, smc)); TRY(dev_upload(c, &v.sto_pmax, spm));
-    if (c->plan.stoE0) {                    // DOPF_F_STO_INITIAL_LEVEL: the initial levels behind the max levels (sto_e0), all 0 until the setter
+    if (c->plan.stoE0 || c->plan.stoLV == 2) {
+        // DOPF_F_STO_INITIAL_LEVEL: the initial levels behind the max levels (sto_e0), all 0 until the setter (and without that flag);
+        // DOPF_F_STO_TERMINAL_LEVEL: the terminal bands behind those (sto_end_lo, sto_end_hi), [0, emax] until the setter
         c->sto_emax_h = sem;
+        c->sto_pmax_h = spm;
+        c->sto_e0_h.assign(S, 0.0);
+        c->sto_lo_h.assign(S, 0.0);
+        c->sto_hi_h = sem;
         std::vector<double> em2(sem);
         em2.resize(2 * (size_t)S, 0.0);
+        if (c->plan.stoLV == 2) { em2.resize(3 * (size_t)S, 0.0); em2.insert(em2.end(), sem.begin(), sem.end()); }
         TRY(dev_upload(c, &v.sto_emax, em2));
     } else {
         TRY(dev_upload(c, &v.sto_emax, sem));
@@ -1312,6 +1356,28 @@ int dopf_set_storage_initial_level(dopf_ctx *c, const double *e0)
     // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again)
     HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_e0(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
     HIPCHK(c, hipStreamSynchronize(c->main));
+    c->sto_e0_h = h;                        // (what the terminal-level setter checks reachability from)
+    return DOPF_OK;
+}
+
+int dopf_set_storage_terminal_level(dopf_ctx *c, const double *lo, const double *hi)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_terminal_levels(c, lo, hi)) return rc;
+    const int S = c->v.S;
+    if (S == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<double> h(2 * (size_t)S);   // lo then hi: sto_end_hi(v) = sto_end_lo(v) + S
+    for (int i = 0; i < S; ++i) {
+        const int a = c->sto_perm[i];
+        h[i] = lo ? lo[a] + 0.0 : 0.0;                      // (+ 0.0: a -0.0 is stored as 0.0)
+        h[S + i] = hi ? hi[a] + 0.0 : c->sto_emax_h[i];
+    }
+    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again)
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_end_lo(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    c->sto_lo_h.assign(h.begin(), h.begin() + S);
+    c->sto_hi_h.assign(h.begin() + S, h.end());
     return DOPF_OK;
 }
 

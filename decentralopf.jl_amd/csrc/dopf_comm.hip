@@ -698,6 +698,18 @@ int dopf_multi_set_storage_initial_level(dopf_multi *m, const double *e0)
     return DOPF_OK;
 }
 
+int dopf_multi_set_storage_terminal_level(dopf_multi *m, const double *lo, const double *hi)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all bands as they were
+        for (int i = 0; i < m->n; ++i) {
+            const double *li = lo ? lo + m->s0[i] : nullptr, *hi_ = hi ? hi + m->s0[i] : nullptr;
+            const int rc = pass == 0 ? check_terminal_levels(m->ctx[i], li, hi_) : dopf_set_storage_terminal_level(m->ctx[i], li, hi_);
+            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
+        }
+    return DOPF_OK;
+}
+
 int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E)
 {
     if (!m) return DOPF_E_INVALID;

@@ -31,7 +31,10 @@ struct dopf_ctx {
     void *own_cons = nullptr;
     double *getter_scratch = nullptr;      // 3 * N * T doubles, allocated at the first getter that needs them (freed with the context)
     std::vector<int> gen_perm, sto_perm;   // sorted position -> caller's index
-    std::vector<double> sto_emax_h;        // DOPF_F_STO_INITIAL_LEVEL: the storages' max_level in sorted order (the setter's bounds)
+    std::vector<double> sto_emax_h;        // DOPF_F_STO_INITIAL_LEVEL / _TERMINAL_LEVEL: the storages' max_level in sorted order (the setters' bounds)
+    std::vector<double> sto_pmax_h;        // DOPF_F_STO_TERMINAL_LEVEL: max charge / discharge per step, sorted order (reachability)
+    std::vector<double> sto_e0_h, sto_lo_h, sto_hi_h;   // the values on the device: initial levels, terminal bands (sorted order; each
+                                                        // setter checks reachability against the other's)
     dopf::Status host_st{};
     dopf::Status *host_pin = nullptr;       // page-locked landing area of the status read-back (a pageable target is staged: slower)
     unsigned long long solver_fail_seen = 0;   // failures already reported through DOPF_E_SOLVER
@@ -48,6 +51,7 @@ void keep_error(const dopf_ctx *c);          // the context's message becomes wh
 void drop_graphs(dopf_ctx *c);
 int read_status(dopf_ctx *c);
 int check_initial_levels(dopf_ctx *c, const double *e0);   // the checks of dopf_set_storage_initial_level (flag, 0 <= e0 <= emax)
+int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi);   // those of dopf_set_storage_terminal_level
 // dopf_comm.hip
 int check_one_runtime(dopf_ctx *c);           // DOPF_E_UNSUPPORTED when two HIP runtimes are mapped into the process
 int comm_enqueue_allreduce(dopf_ctx *c);      // sum of the consensus buffer over the ranks, on the context's stream

@@ -121,7 +121,8 @@ struct DevView {
     const double *gen_mc, *gen_pmax;
     const double2 *gen_mp;                          // [g] {mc, pmax} side by side: one 16-byte load per row (streaming blocks)
     const double *sto_mc, *sto_pmax, *sto_emax;     // DOPF_F_STO_INITIAL_LEVEL: sto_emax has 2S entries, the initial levels behind the max levels
-                                                    // (sto_e0(v) below): the view, every kernel's argument, keeps its layout
+                                                    // (sto_e0(v) below): the view, every kernel's argument, keeps its layout;
+                                                    // DOPF_F_STO_TERMINAL_LEVEL: 4S, the terminal bands behind those (sto_end_lo/hi)
     const Item *gen_items, *sto_items;
     const int *node_gen_beg, *node_sto_beg;         // N+1 each: agent ranges per node
     const double *node_win;                         // N: bound on |change of an agent's net injection| at the node
@@ -165,6 +166,10 @@ struct DevView {
 
 // the storages' initial levels (DOPF_F_STO_INITIAL_LEVEL contexts only: zeros until dopf_set_storage_initial_level), sorted order
 __host__ __device__ inline const double *sto_e0(const DevView &v) { return v.sto_emax + v.S; }
+// the band of each storage's level after the last timestep (DOPF_F_STO_TERMINAL_LEVEL contexts only: [0, emax] until
+// dopf_set_storage_terminal_level), sorted order
+__host__ __device__ inline const double *sto_end_lo(const DevView &v) { return v.sto_emax + 2 * (size_t)v.S; }
+__host__ __device__ inline const double *sto_end_hi(const DevView &v) { return v.sto_emax + 3 * (size_t)v.S; }
 
 #ifndef DOPF_ACC_REP
 #define DOPF_ACC_REP 16
@@ -224,7 +229,9 @@ struct Plan {
     Consensus consensus;
     bool sliceDual;                 // the one-block dual kernel may add k_reduce's slices itself (DevView::sliceDual)
     bool useWarm, stoLean;          // storage warm start (DevView::use_warm); the lean active-set body (sto_lean.h)
-    bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: the storage bodies' E0 instantiations (initial levels: sto_e0(v))
+    bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
+    int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
+                                    // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag)
     bool fuseAgents, fuseNet;       // generators + storages in one launch: k_agents (copper plate, even T), k_net_agents (networks)
     bool tail;                      // the tail of the iteration in the x-update launch (DevView::tailDev)
     bool slackDual;                 // the one-launch dual/price kernel may form the slack sums: no k_reduce (DevView::slackInDual)

@@ -1034,11 +1034,15 @@ struct StoAgent {
 // `item_fail`: number of storages of this item the warm start left over (block-uniform); < 0 = read it
 // FULLT: the horizon fills the lane group exactly (T == LPS * NCH: 24 = 8 x 3, 48 = 16 x 3, 96 = 32 x 3): T is then a
 // compile-time constant and every "is this step inside the horizon" test folds away
-// E0: the level before the first timestep is the storage's initial level sto_e0(v)[s] (DOPF_F_STO_INITIAL_LEVEL), not 0. A template
-// argument: without the flag the instantiations are the code of before, register for register
-template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, bool E0 = false>
+// LV, the level mode (template arguments: without the flags the instantiations are the code of before, register for register):
+//   0: F_0 = 0, every level in [0, emax] (the reference);
+//   1 (E0): the level before the first timestep is the storage's initial level sto_e0(v)[s] (DOPF_F_STO_INITIAL_LEVEL), not 0;
+//   2: as 1, and the level after the last timestep lies in the storage's terminal band [sto_end_lo, sto_end_hi]
+//      (DOPF_F_STO_TERMINAL_LEVEL): the walk classifies step T-1 against that band and its root search targets lo or hi
+template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, int LV = 0>
 __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, int item_fail)
 {
+    constexpr bool E0 = LV >= 1;
     constexpr int NG = 256 / LPS;
     __shared__ double red[NG * LPS * NCH];
     __shared__ double redc[256];
@@ -1100,6 +1104,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
         ag.pm = live ? v.sto_pmax[s] : 0.0;
         ag.em = live ? v.sto_emax[s] : 0.0;
         const double e0 = (E0 && live) ? sto_e0(v)[s] : 0.0;       // level before timestep 0
+        const double elo = (LV == 2 && live) ? sto_end_lo(v)[s] : 0.0, ehi = (LV == 2 && live) ? sto_end_hi(v)[s] : ag.em;   // band of step T-1
         // rD0/rC0: the nu-independent part of the two gradient offsets (copper plate); D0/C0 otherwise
         double D0[NCH], C0[NCH], nuf[NCH];
 #pragma unroll
@@ -1266,12 +1271,13 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
                 }
             }
             if (classify) {
-                // largest open timestep whose unclamped level leaves [0, em] at this price
+                // largest open timestep whose unclamped level leaves [0, em] at this price ([elo, ehi] for step T-1 with LV 2)
                 int vnew = -1;
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     const int t = tbase + c;
-                    const unsigned long long bts = group_bits<LPS>(t <= k && t < T && (Sv[c] < -tol || Sv[c] > ag.em + tol), gbase);
+                    const unsigned long long bts = group_bits<LPS>(t <= k && t < T && (LV == 2 && t == T - 1 ? (Sv[c] < elo - tol || Sv[c] > ehi + tol)
+                                                                                                          : (Sv[c] < -tol || Sv[c] > ag.em + tol)), gbase);
                     if (bts) { const int j = (63 - __clzll(bts)) * NCH + c; vnew = j > vnew ? j : vnew; }
                 }
 #pragma unroll
@@ -1284,7 +1290,8 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
                 } else {
                     const double sv = level_at(vnew), sl = slope_at(vnew);
                     vv = vnew;
-                    target = sv < 0.0 ? 0.0 : ag.em;
+                    if (LV == 2 && vnew == T - 1) target = sv < elo ? elo : ehi;
+                    else target = sv < 0.0 ? 0.0 : ag.em;
                     const double res = sv - target;
                     lo = -INFINITY; hi = INFINITY;
                     if (res < 0.0) lo = nu; else hi = nu;
@@ -1371,11 +1378,11 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
 #endif
 }
 
-template <int LPS, int NCH, bool LINES, bool E0>
+template <int LPS, int NCH, bool LINES, int LV>
 __global__ __launch_bounds__(256, 2) void k_sto_update(DevView v)
 {
     if (v.st->halt) return;
-    sto_cold_body<LPS, NCH, LINES, false, false, E0>(v, blockIdx.x, -1);
+    sto_cold_body<LPS, NCH, LINES, false, false, LV>(v, blockIdx.x, -1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1537,10 +1544,14 @@ __device__ __forceinline__ int next_lane_i(int x)
 }
 
 // returns the number of storages of the item left to the scan (block-uniform)
-// E0: the first segment starts at sto_e0(v)[s] instead of 0 (DOPF_F_STO_INITIAL_LEVEL; sto_cold_body)
-template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, bool E0 = false>
+// LV (sto_cold_body): 1 (E0) the first segment starts at sto_e0(v)[s] instead of 0 (DOPF_F_STO_INITIAL_LEVEL); 2 also bounds the
+// level after step T-1 by [sto_end_lo, sto_end_hi] instead of [0, emax] (DOPF_F_STO_TERMINAL_LEVEL): a contact there targets lo
+// (kind 1) or hi (kind 2), its price obeys the sign rule of an empty / full contact against the 0 past the horizon, and with lo == hi
+// it may take any price (as every contact of a storage with emax = 0 could)
+template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, int LV = 0>
 __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, const int halt = 0)
 {
+    constexpr bool E0 = LV >= 1;
     constexpr int NG = 256 / LPS, TP = LPS * NCH;
     constexpr int MAXR = 16;                 // contact-set rounds per storage
     constexpr int MAXN = 40;                 // Newton iterations per round
@@ -1607,6 +1618,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
         const bool live = s < it.a1;
         const double mc = live ? v.sto_mc[s] : 0.0, pm = live ? v.sto_pmax[s] : 0.0, em = live ? v.sto_emax[s] : 0.0;
         const double e0 = (E0 && live) ? sto_e0(v)[s] : 0.0;     // level before timestep 0
+        const double elo = (LV == 2 && live) ? sto_end_lo(v)[s] : 0.0, ehi = (LV == 2 && live) ? sto_end_hi(v)[s] : em;   // band of step T-1
         const bool havenu = live && v.nu_valid[s] != 0;
         // copper plate: the nu-independent parts of the two gradient offsets, rD = rD0 - nu, rC = rC0 + nu
         // (with lines Psi depends on the step itself: D0/C0 are kept and the offsets are built per evaluation)
@@ -1678,7 +1690,8 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
             for (int c = 0; c < NCH; ++c) {
                 const int t = tbase + c;
                 eo += dq[c];
-                kind[c] = t < T ? (eo <= tolc ? 1 : (eo >= em - tolc ? 2 : 0)) : 0;
+                if (LV == 2 && t == T - 1) kind[c] = eo <= elo + tolc ? 1 : (eo >= ehi - tolc ? 2 : 0);
+                else kind[c] = t < T ? (eo <= tolc ? 1 : (eo >= em - tolc ? 2 : 0)) : 0;
             }
         }
 
@@ -1692,7 +1705,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
             DOPF_TIC();
             // end of a segment: a contact, or the last step; start: the step after an end (or step 0)
 #define ISEND(c) (tbase + (c) < T && (kind[c] != 0 || tbase + (c) == T - 1))
-#define TGT(c) (kind[c] == 2 ? em : 0.0)
+#define TGT(c) (LV == 2 && tbase + (c) == T - 1 ? (kind[c] == 2 ? ehi : elo) : (kind[c] == 2 ? em : 0.0))
             double bs[NCH];
             int send[NCH];
             bool st0;                                            // this lane's first step starts a segment
@@ -1917,7 +1930,10 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                 if (t < T) {
                     const double Ev = bs[c] + px[c];
                     if (!(ISEND(c) && kind[c] != 0)) {           // (a contact's level is its Newton target)
-                        if (Ev < -tolE) { okk = false; nkind[c] = 1; }
+                        if (LV == 2 && t == T - 1) {             // (the terminal band; PDAS: a contact at the bound it crossed)
+                            if (Ev < elo - tolE) { okk = false; nkind[c] = 1; }
+                            else if (Ev > ehi + tolE) { okk = false; nkind[c] = 2; }
+                        } else if (Ev < -tolE) { okk = false; nkind[c] = 1; }
                         else if (Ev > em + tolE) { okk = false; nkind[c] = 2; }
                     }
                     if (ISEND(c)) {
@@ -1935,8 +1951,10 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                             if (rD0 <= -rC0 && nuv[c] >= rD0 - 1e-9 && nuv[c] <= -rC0 + 1e-9) { mlo[c] = rD0; mhi[c] = -rC0; }
                         }
                         // lower-end chain: empty x -> max(mlo, x), full/open x -> mlo; upper-end chain: empty/open x -> mhi, full x -> min(mhi, x)
-                        const double a_lo = mlo[c], a_hi = kind[c] == 1 ? INFINITY : mlo[c];
-                        const double b_lo = kind[c] == 2 ? -INFINITY : mhi[c], b_hi = mhi[c];
+                        // (LV 2, a contact at T-1 with lo == hi: no sign condition, the maps of an open segment)
+                        const int sk = LV == 2 && t == T - 1 && elo == ehi ? 0 : kind[c];
+                        const double a_lo = mlo[c], a_hi = sk == 1 ? INFINITY : mlo[c];
+                        const double b_lo = sk == 2 ? -INFINITY : mhi[c], b_hi = mhi[c];
                         const double nal = lz_clamp(alo, a_lo, a_hi), nah = lz_clamp(ahi, a_lo, a_hi);
                         const double nbl = lz_clamp(blo2, b_lo, b_hi), nbh = lz_clamp(bhi2, b_lo, b_hi);
                         alo = nal; ahi = nah; blo2 = nbl; bhi2 = nbh;
@@ -1954,8 +1972,9 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                 const int t = tbase + c;
                 nuc[c] = nuv[c];
                 if (t < T && ISEND(c)) {
-                    flo = kind[c] == 1 ? lz_max(mlo[c], flo) : mlo[c];
-                    fhi = kind[c] == 2 ? lz_min(mhi[c], fhi) : mhi[c];
+                    const int sk = LV == 2 && t == T - 1 && elo == ehi ? 0 : kind[c];      // (as in the chains above)
+                    flo = sk == 1 ? lz_max(mlo[c], flo) : mlo[c];
+                    fhi = sk == 2 ? lz_min(mhi[c], fhi) : mhi[c];
                     if (kind[c] != 0) {
                         const double tn = 1e-10 * (1.0 + lz_minabs(flo, fhi));
                         if (flo > fhi + tn) { okk = false; nkind[c] = 0; }      // wrong sign: release the contact
@@ -2155,24 +2174,24 @@ namespace dopf {
 // The scan body as a function of its own (networks): called by k_sto_warm for the rare item the active-set body leaves
 // something of. Inlined, its registers crowd the active-set body (255 VGPRs and spills, 40 % slower, measured); as a
 // separate launch it cost 4 us + a launch gap per iteration for finding nothing to do.
-template <int LPS, int NCH, bool E0>
+template <int LPS, int NCH, int LV>
 __device__ __attribute__((noinline)) void sto_cold_lines_call(const DevView *self, const int blk, const int left)
 {
-    sto_cold_body<LPS, NCH, true, false, false, E0>(*self, blk, left);
+    sto_cold_body<LPS, NCH, true, false, false, LV>(*self, blk, left);
 }
 
 #ifndef DOPF_WARM_WAVES
 #define DOPF_WARM_WAVES 2
 #endif
-template <int LPS, int NCH, bool LINES, bool LEAN = false, bool E0 = false>
+template <int LPS, int NCH, bool LINES, bool LEAN = false, int LV = 0>
 __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_sto_warm(DevView v)
 {
     // (networks, LEAN: the lean body where every table of the item's node is empty — the settled state — else the general one.
     // A template argument, not a branch on v.stoLean: with both bodies in one function the general one ran 6 % slower, measured)
     static_assert(LINES || !LEAN, "copper plates: k_sto_l");
-    static_assert(!(LEAN && E0), "the lean body has no initial level");
+    static_assert(!(LEAN && LV), "the lean body has no initial or terminal level");
     const int left = LEAN ? sto_lean_body<LPS, NCH, false, true, false>(v, blockIdx.x, v.st->halt)
-                          : sto_warm_body<LPS, NCH, LINES, false, false, E0>(v, blockIdx.x, v.st->halt);         // ends on a __syncthreads
+                          : sto_warm_body<LPS, NCH, LINES, false, false, LV>(v, blockIdx.x, v.st->halt);         // ends on a __syncthreads
     if (left < 0) return;                                                               // halted
     if (LINES) {                                 // the scan body for what the warm start left over: no k_sto_update launch
         if (left == 0) {                         // (what the scan body writes when there is nothing for it)
@@ -2180,7 +2199,7 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_sto_warm(DevView v)
             for (int t = threadIdx.x; t < v.T; t += 256) v.part_T[(size_t)t * v.rowsT + row] = 0.0;
             if (threadIdx.x == 0) v.part_scost[blockIdx.x] = 0.0;
         } else {
-            sto_cold_lines_call<LPS, NCH, E0>(v.self, blockIdx.x, left);
+            sto_cold_lines_call<LPS, NCH, LV>(v.self, blockIdx.x, left);
         }
     }
 }
@@ -2192,10 +2211,10 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_sto_warm(DevView v)
 // launch: a chain of dependent round trips), the generator items behind them in 256-thread blocks that pass through the
 // wave slots the storages leave free. Alone, either launch is a few hundred short blocks bound by its own latency chain
 // (configs[3]'s share: 12 + 13 us and a kernel boundary); together they overlap.
-template <int LPS, int NCH, bool LEAN, bool E0 = false>
+template <int LPS, int NCH, bool LEAN, int LV = 0>
 __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
 {
-    static_assert(!(LEAN && E0), "the lean body has no initial level");
+    static_assert(!(LEAN && LV), "the lean body has no initial or terminal level");
     const int nS = v.nStoItems;
     const bool isGen = (int)blockIdx.x >= nS;
     const int gi = (int)blockIdx.x - nS, si = blockIdx.x;
@@ -2208,14 +2227,14 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
         else gen_lines_body<256, DOPF_NET_GEN_FLIGHT>(v, gi, v.genTT256, v.genR);
     } else {
         const int left = LEAN ? sto_lean_body<LPS, NCH, false, true, false>(v, si, v.st->halt)
-                              : sto_warm_body<LPS, NCH, true, false, false, E0>(v, si, v.st->halt); // ends on a __syncthreads
+                              : sto_warm_body<LPS, NCH, true, false, false, LV>(v, si, v.st->halt); // ends on a __syncthreads
         if (left < 0) return;                                                           // halted
         if (left == 0) {                     // (what the scan body writes when there is nothing for it)
             const int row = v.sto_items[si].row;
             for (int t = threadIdx.x; t < v.T; t += 256) v.part_T[(size_t)t * v.rowsT + row] = 0.0;
             if (threadIdx.x == 0) v.part_scost[si] = 0.0;
         } else {
-            sto_cold_lines_call<LPS, NCH, E0>(v.self, si, left);
+            sto_cold_lines_call<LPS, NCH, LV>(v.self, si, left);
         }
     }
 #if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
@@ -2226,14 +2245,14 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
 
 // Warm start and, in the same block, the cold scan for what it left over: one launch for the storages of the big
 // copper-plate grids (the separate k_sto_update launch mostly found nothing to do).
-template <int LPS, int NCH, bool LINES, bool TAIL, bool FULLT, bool E0 = false>
+template <int LPS, int NCH, bool LINES, bool TAIL, bool FULLT, int LV = 0>
 __global__ __launch_bounds__(256, 3) void k_sto(DevView v)
 {
     // (TAIL: the generator launch in front of this one has added its sums; the grid's last block is the tail block)
     if (TAIL && (int)blockIdx.x == v.nStoItems) { tail_block(v.self); return; }
-    const int left = sto_warm_body<LPS, NCH, LINES, TAIL, FULLT, E0>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
+    const int left = sto_warm_body<LPS, NCH, LINES, TAIL, FULLT, LV>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
     if (left < 0) return;                                                                           // __syncthreads: the sto_fail flags are visible)
-    sto_cold_body<LPS, NCH, LINES, TAIL, FULLT, E0>(v, blockIdx.x, left);
+    sto_cold_body<LPS, NCH, LINES, TAIL, FULLT, LV>(v, blockIdx.x, left);
 }
 
 // All x-updates of one copper-plate iteration in ONE launch: blocks [0, nStoItems) solve storages (warm start,
@@ -2243,7 +2262,7 @@ __global__ __launch_bounds__(256, 3) void k_sto(DevView v)
 // ones (interleaving the two kinds in dispatch order starts the last storage blocks late and costs 50 %).
 // The launch runs at the storage code's 3 waves/SIMD, which starves the streaming generator blocks once the
 // grid is large, so dopf_create only fuses grids whose storage blocks are all resident from the start.
-template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT, bool E0 = false>
+template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT, int LV = 0>
 __global__ __launch_bounds__(256, 3) void k_agents(DevView v)
 {
     const int nS = v.nStoItems;
@@ -2258,8 +2277,8 @@ __global__ __launch_bounds__(256, 3) void k_agents(DevView v)
         else gen_pair_body<256, TAIL, true>(v, blockIdx.x - nS);
     } else {
         if ((int)blockIdx.x < nS) {
-            const int left = sto_warm_body<LPS, NCH, false, TAIL, FULLT, E0>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
-            if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT, E0>(v, blockIdx.x, left);            // __syncthreads: the sto_fail flags are visible)
+            const int left = sto_warm_body<LPS, NCH, false, TAIL, FULLT, LV>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
+            if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT, LV>(v, blockIdx.x, left);            // __syncthreads: the sto_fail flags are visible)
         } else {
             if (v.st->halt) return;
             gen_pair_skip_body<256, TAIL>(v, blockIdx.x - nS);
@@ -2354,7 +2373,17 @@ static void with_bool(bool b, F &&f)
     else f(std::false_type{});
 }
 
-// (p.stoE0, DOPF_F_STO_INITIAL_LEVEL: the general bodies' E0 instantiations; plan_chain keeps such contexts off the lean body)
+// f(integral_constant<int, LV>) for the plan's level mode p.stoLV (0, 1, 2: all three instantiated)
+template <class F>
+static void with_lv(int lv, F &&f)
+{
+    if (lv == 2) f(std::integral_constant<int, 2>{});
+    else if (lv == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
+// (p.stoLV, DOPF_F_STO_INITIAL_LEVEL / DOPF_F_STO_TERMINAL_LEVEL: the general bodies' level-mode instantiations; plan_chain keeps such
+// contexts off the lean body)
 template <int LPS, int NCH>
 static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
 {
@@ -2364,7 +2393,8 @@ static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
         with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NC, [&](auto full) {
             constexpr bool TL = decltype(tail)::value, FU = decltype(full)::value;
             if (p.stoLean) hipLaunchKernelGGL((k_sto_l<LPS, NC, TL, FU>), grid, dim3(256), 0, s, v);
-            else if (p.stoE0) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, true>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 2) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, 2>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 1) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, 1>), grid, dim3(256), 0, s, v);
             else hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU>), grid, dim3(256), 0, s, v);
         }); });
         return;
@@ -2373,14 +2403,15 @@ static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
     // body itself for what it leaves over
     if (v.use_warm) {
         if (p.stoLean) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
-        else if (p.stoE0) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        else if (p.stoLV == 2) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, 2>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        else if (p.stoLV == 1) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, 1>), dim3(v.nStoItems), dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false>), dim3(v.nStoItems), dim3(256), 0, s, v);
         return;
     }
-    with_bool(p.stoE0, [&](auto e0) {
-        constexpr bool E0 = decltype(e0)::value;
-        if (v.L > 0) hipLaunchKernelGGL((k_sto_update<LPS, NCH, true, E0>), dim3(v.nStoItems), dim3(256), 0, s, v);
-        else hipLaunchKernelGGL((k_sto_update<LPS, NCH, false, E0>), dim3(v.nStoItems), dim3(256), 0, s, v);
+    with_lv(p.stoLV, [&](auto lv) {
+        constexpr int LV = decltype(lv)::value;
+        if (v.L > 0) hipLaunchKernelGGL((k_sto_update<LPS, NCH, true, LV>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        else hipLaunchKernelGGL((k_sto_update<LPS, NCH, false, LV>), dim3(v.nStoItems), dim3(256), 0, s, v);
     });
 }
 
@@ -2391,7 +2422,8 @@ static void launch_agents_t(const DevView &v, const Plan &p, hipStream_t s)
     with_bool(v.genSkip, [&](auto skip) { with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NCH, [&](auto full) {
         constexpr bool SK = decltype(skip)::value, TL = decltype(tail)::value, FU = decltype(full)::value;
         if (p.stoLean) hipLaunchKernelGGL((k_agents_l<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
-        else if (p.stoE0) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, true>), grid, dim3(256), 0, s, v);
+        else if (p.stoLV == 2) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 2>), grid, dim3(256), 0, s, v);
+        else if (p.stoLV == 1) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 1>), grid, dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
     }); }); });
 }
@@ -2406,7 +2438,8 @@ void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s)
     const dim3 grid(v.nStoItems + v.nGenItems);
     with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) {
         if (p.stoLean) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
-        else if (p.stoE0) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, true>), grid, dim3(256), 0, s, v);
+        else if (p.stoLV == 2) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 2>), grid, dim3(256), 0, s, v);
+        else if (p.stoLV == 1) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 1>), grid, dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false>), grid, dim3(256), 0, s, v);
     });
 }
@@ -2415,10 +2448,10 @@ void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s)
 {
     if (v.nStoItems == 0) return;
     if (p.stoLong) {                        // DOPF_F_LONG_HORIZON (sto_long.h): one block per item, any horizon
-        with_bool(p.stoE0, [&](auto e0) {
-            constexpr bool E0 = decltype(e0)::value;
-            if (v.L > 0) hipLaunchKernelGGL((k_sto_long<true, E0>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
-            else hipLaunchKernelGGL((k_sto_long<false, E0>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
+        with_lv(p.stoLV, [&](auto lv) {
+            constexpr int LV = decltype(lv)::value;
+            if (v.L > 0) hipLaunchKernelGGL((k_sto_long<true, LV>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
+            else hipLaunchKernelGGL((k_sto_long<false, LV>), dim3(v.nStoItems), dim3(kLongBS), 0, s, v);
         });
         return;
     }

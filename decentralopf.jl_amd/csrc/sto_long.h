@@ -34,10 +34,12 @@ struct LongCand {
     double Fp, Fm;      // distance to the nearest kink above / below nu over the run that ends at o (INFINITY: none)
 };
 
-// E0: the first tile is entered at the storage's initial level sto_e0(v)[s] (DOPF_F_STO_INITIAL_LEVEL), not at 0
-template <bool LINES, bool E0 = false>
+// LV (sto_cold_body): 1 (E0) the first tile is entered at the storage's initial level sto_e0(v)[s] (DOPF_F_STO_INITIAL_LEVEL), not at
+// 0; 2 also classifies timestep T-1 against the terminal band [sto_end_lo, sto_end_hi] and roots it on lo or hi (DOPF_F_STO_TERMINAL_LEVEL)
+template <bool LINES, int LV = 0>
 __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
 {
+    constexpr bool E0 = LV >= 1;
     if (v.st->halt) return;
     __shared__ double wmap[3][kLongWaves];          // each wave's composite map of the tile
     __shared__ int wint[3][kLongWaves];             // candidate, last clamped step before it, last clamped step
@@ -60,6 +62,7 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
         double *nuf = v.nu_prev + row;              // the price of each timestep, as the recursion assigns it
         const double tol = 1e-11 * (1.0 + em);
         const double e0 = E0 ? sto_e0(v)[s] : 0.0;   // level before timestep 0
+        const double elo = LV == 2 ? sto_end_lo(v)[s] : 0.0, ehi = LV == 2 ? sto_end_hi(v)[s] : em;    // band of timestep T-1
 
         // the lane's inputs of timesteps tbase .. tbase + NCH - 1 (those > lim: zeros, never evaluated)
         double D0[NCH], C0[NCH], P0[NCH], K0[NCH];
@@ -163,7 +166,8 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
                 } else {
 #pragma unroll
                     for (int c = 0; c < NCH; ++c) {
-                        const unsigned long long b = __ballot(tbase + c <= lim && (Sv[c] < -tol || Sv[c] > em + tol));
+                        const unsigned long long b = __ballot(tbase + c <= lim && (LV == 2 && tbase + c == T - 1 ? (Sv[c] < elo - tol || Sv[c] > ehi + tol)
+                                                                                                              : (Sv[c] < -tol || Sv[c] > em + tol)));
                         if (b) { const int j = (63 - __clzll(b)) * NCH + c; oW = j > oW ? j : oW; }
                     }
                 }
@@ -274,7 +278,8 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
                     k = -1;
                 } else {
                     vv = vnew;
-                    target = cd.sv < 0.0 ? 0.0 : em;
+                    if (LV == 2 && vnew == T - 1) target = cd.sv < elo ? elo : ehi;
+                    else target = cd.sv < 0.0 ? 0.0 : em;
                     const double res = cd.sv - target;
                     lo = -INFINITY; hi = INFINITY;
                     if (res < 0.0) lo = nu; else hi = nu;

@@ -127,6 +127,7 @@ const DOPF_F_LONG_HORIZON = 2097152  # include/dopf.h
 const DOPF_F_WIDE_NETWORK = 8388608  # include/dopf.h
 const DOPF_F_DEBUG_WIDE_NET = 16777216  # include/dopf.h (tests)
 const DOPF_F_STO_INITIAL_LEVEL = 33554432  # include/dopf.h
+const DOPF_F_STO_TERMINAL_LEVEL = 67108864  # include/dopf.h
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -141,7 +142,8 @@ reference's literals `w_flow = 10`, `w_prox = 1`, `eps = 1e-3`, `mask_thr = 1e-2
 Storages on horizons beyond 512 timesteps (an hourly year: T = 8 760) need `flags = DOPF_F_LONG_HORIZON`
 (the long-horizon storage body; without the flag the library refuses them). Networks of more than 2 048 lines
 need `flags = DOPF_F_WIDE_NETWORK` (the wide-network chain; without it the library refuses them). Storages that start a
-horizon from a given level (see `set_initial_levels!`) need `flags = DOPF_F_STO_INITIAL_LEVEL`. Flags combine with `|`.
+horizon from a given level (see `set_initial_levels!`) need `flags = DOPF_F_STO_INITIAL_LEVEL`; storages whose level after the
+last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_TERMINAL_LEVEL`. Flags combine with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
@@ -239,6 +241,32 @@ function set_initial_levels!(admm::ADMM, e0::Union{Nothing, Vector{Float64}})
                              admm.multi)
         else
             dopf_check(ccall((:dopf_set_storage_initial_level, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, p), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    set_terminal_levels!(admm, lo, hi)
+
+The band `[lo[s], hi[s]]` of each storage's level after the last timestep (in the order of `storages`,
+`0 <= lo[s] <= hi[s] <= max_level`, reachable from the initial level in T steps of at most `max_power`; `nothing` for both =
+`[0, max_level]`): "end at least at X" is `[X, max_level]`, a cyclic horizon `lo = hi =` the initial level. The reference leaves
+that level free; the ADMM must have been created with `flags = DOPF_F_STO_TERMINAL_LEVEL`. Takes effect at the next iteration.
+"""
+function set_terminal_levels!(admm::ADMM, lo::Union{Nothing, Vector{Float64}}, hi::Union{Nothing, Vector{Float64}})
+    S = length(admm.storages)
+    (lo === nothing) == (hi === nothing) || error("set_terminal_levels!: give both lo and hi, or neither")
+    lo === nothing || (length(lo) == S && length(hi) == S) || error("set_terminal_levels!: expected $S values each")
+    pl = lo === nothing ? Ptr{Cdouble}(C_NULL) : pointer(lo)
+    ph = hi === nothing ? Ptr{Cdouble}(C_NULL) : pointer(hi)
+    GC.@preserve lo hi begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_storage_terminal_level, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                                   admm.multi, pl, ph), admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_storage_terminal_level, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                             admm.ctx, pl, ph), admm.ctx)
         end
     end
     return admm

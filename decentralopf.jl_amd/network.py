@@ -7,6 +7,8 @@ Mirrors, for the Python host (Julia is not in this image; the Julia shim is juli
 Numeric struct fields are Int in the reference and are promoted to Float64 when packed.
 Storage.initial_level is not in the reference (which starts every storage empty, src/optimization/subproblems.jl:154): the
 level before the first timestep, for runs that continue a previous horizon (DOPF_F_STO_INITIAL_LEVEL).
+Storage.terminal_level_min / terminal_level_max are not in the reference either (which lets the level after the last timestep
+lie anywhere in [0, max_level]): a band for that level, e.g. "end at least at X" or a cyclic horizon (DOPF_F_STO_TERMINAL_LEVEL).
 """
 from __future__ import annotations
 
@@ -41,6 +43,8 @@ class Storage:
     plot_color: str
     node: Node
     initial_level: float = 0.0      # level before the first timestep, 0 <= initial_level <= max_level (not in the reference)
+    terminal_level_min: float = 0.0                 # band of the level after the last timestep (not in the reference)
+    terminal_level_max: Optional[float] = None      # (None: max_level)
 
 
 @dataclass(eq=False)
@@ -110,6 +114,8 @@ class PackedProblem:
     sto_node: np.ndarray
     meta: dict = field(default_factory=dict)
     sto_e0: Optional[np.ndarray] = None     # (S,) Storage.initial_level; None = all 0
+    sto_end_lo: Optional[np.ndarray] = None     # (S,) Storage.terminal_level_min; None = all 0
+    sto_end_hi: Optional[np.ndarray] = None     # (S,) Storage.terminal_level_max; None = sto_emax
 
     @property
     def G(self):
@@ -130,7 +136,20 @@ class PackedProblem:
             sto_mc=self.sto_mc, sto_pmax=self.sto_pmax, sto_emax=self.sto_emax, sto_node=self.sto_node)
         if self.sto_e0 is not None and np.any(np.asarray(self.sto_e0) != 0.0):
             kw["sto_e0"] = np.asarray(self.sto_e0, dtype=np.float64)
+        if self.has_terminal_band():      # (engines then run with F_STO_TERMINAL_LEVEL)
+            kw["sto_end_lo"], kw["sto_end_hi"] = self.terminal_band()
         return kw
+
+    def terminal_band(self):
+        """(lo, hi) of the level after the last timestep, float64 (S,) each, the defaults filled in: [0, sto_emax]."""
+        lo = np.zeros(self.S) if self.sto_end_lo is None else np.asarray(self.sto_end_lo, dtype=np.float64)
+        hi = np.asarray(self.sto_emax if self.sto_end_hi is None else self.sto_end_hi, dtype=np.float64)
+        return lo, hi
+
+    def has_terminal_band(self) -> bool:
+        """Some storage's band differs from the default [0, max_level]."""
+        lo, hi = self.terminal_band()
+        return bool(np.any(lo != 0.0) or np.any(hi != np.asarray(self.sto_emax, dtype=np.float64)))
 
     def shard(self, rank: int, world: int) -> "PackedProblem":
         """Contiguous slice of the agent lists for one rank (network data replicated)."""
@@ -147,7 +166,9 @@ class PackedProblem:
             sto_node=self.sto_node[s0:s1],
             meta=dict(self.meta, rank=rank, world=world, gen_range=(g0, g1), sto_range=(s0, s1),
                       n_agents_global=self.G + self.S),
-            sto_e0=None if self.sto_e0 is None else self.sto_e0[s0:s1])
+            sto_e0=None if self.sto_e0 is None else self.sto_e0[s0:s1],
+            sto_end_lo=None if self.sto_end_lo is None else self.sto_end_lo[s0:s1],
+            sto_end_hi=None if self.sto_end_hi is None else self.sto_end_hi[s0:s1])
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -172,4 +193,6 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         sto_pmax=f64(s.max_power for s in storages),
         sto_emax=f64(s.max_level for s in storages),
         sto_node=i32(idx[id(s.node)] for s in storages),
-        sto_e0=f64(s.initial_level for s in storages))
+        sto_e0=f64(s.initial_level for s in storages),
+        sto_end_lo=f64(s.terminal_level_min for s in storages),
+        sto_end_hi=f64(s.max_level if s.terminal_level_max is None else s.terminal_level_max for s in storages))

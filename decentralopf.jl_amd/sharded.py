@@ -104,6 +104,16 @@ class ShardedADMM:
         s0, s1 = self.shard.meta["sto_range"]
         self.engine.set_initial_levels(np.asarray(e0, dtype=np.float64).reshape(self.problem.S)[s0:s1])
 
+    def set_terminal_levels(self, lo=None, hi=None) -> None:
+        """All storages' terminal bands (problem.S values each, global order; both None = [0, max_level]): this rank sets its
+        slice (dopf_set_storage_terminal_level). Needs F_STO_TERMINAL_LEVEL in the params; every rank calls it between steps."""
+        if lo is None and hi is None:
+            self.engine.set_terminal_levels(None, None)
+            return
+        s0, s1 = self.shard.meta["sto_range"]
+        cut = lambda x: None if x is None else np.asarray(x, dtype=np.float64).reshape(self.problem.S)[s0:s1]
+        self.engine.set_terminal_levels(cut(lo), cut(hi))
+
     def run(self, max_iters: int, check_every: int = 16):
         """Iterate until the stop test holds (checked every `check_every` iterations) or max_iters."""
         done = 0

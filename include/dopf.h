@@ -149,6 +149,13 @@ typedef struct dopf_params {
                                   * E[t-1]) + C[t] - D[t]; src/opf_central_reference.jl:53: E[s,0] = 0). Runs on the general active-set body (as with
                                   * DOPF_F_STO_GENERAL), the scan body and the long-horizon body; with every e0 = 0 the results are bit for bit those of
                                   * DOPF_F_STO_GENERAL. */
+#define DOPF_F_STO_TERMINAL_LEVEL 67108864 /* storages end inside a given band: the context keeps a band [lo[s], hi[s]] per storage
+                                  * ([0, max_level] until dopf_set_storage_terminal_level), and every storage body solves with the level after
+                                  * the last timestep, E_{T-1}, in [lo, hi] instead of [0, emax] (lo == hi: an equality target; lo = hi = e0: a
+                                  * cyclic horizon). Nothing else changes. Works alone (from the empty start) and with DOPF_F_STO_INITIAL_LEVEL.
+                                  * Runs on the general active-set body, the scan body and the long-horizon body; with the default band the
+                                  * results are those of DOPF_F_STO_GENERAL (with DOPF_F_STO_INITIAL_LEVEL: of that flag alone), bit for bit
+                                  * where no storage has max_level 0 (there the last contact takes any price, so the path may differ). */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -282,6 +289,14 @@ int64_t dopf_solver_failures(dopf_ctx *ctx);
  * above max_level (the stored levels are then unchanged). */
 int dopf_set_storage_initial_level(dopf_ctx *ctx, const double *e0);
 
+/* DOPF_F_STO_TERMINAL_LEVEL: the band of each storage's level after the last timestep, lo[S] and hi[S] in the caller's order of this
+ * context's storages (both NULL = the default band [0, max_level], the reference's). Timing and copies as for
+ * dopf_set_storage_initial_level. DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID, and nothing stored, for a NaN, lo < 0,
+ * hi > max_level, lo > hi, only one of the arrays NULL, or a band that the storage cannot reach from its initial level e0 in T steps of
+ * at most pmax: the reachable end levels are [max(0, e0 - T pmax), min(max_level, e0 + T pmax)]. In contexts with both flags
+ * dopf_set_storage_initial_level refuses (DOPF_E_INVALID) an e0 from which the stored band is unreachable. */
+int dopf_set_storage_terminal_level(dopf_ctx *ctx, const double *lo, const double *hi);
+
 /* ---- the central reference on the device ---------------------------------------------------------------
  * Replaces src/opf_central_reference.jl:16-81 (one JuMP model of the whole multi-period DC-OPF, solved by Gurobi): the same
  * LP — variables P, D, C, E in their boxes, energy balance per timestep, |ptdf * injection| <= f_max, storage balance —
@@ -348,6 +363,9 @@ int32_t dopf_multi_size(const dopf_multi *m);
 /* dopf_set_storage_initial_level for all storages, e0[S] in the caller's order (NULL = all 0): each shard gets its slice. Every
  * shard's values are checked before any is stored. */
 int  dopf_multi_set_storage_initial_level(dopf_multi *m, const double *e0);
+/* dopf_set_storage_terminal_level for all storages, lo[S] and hi[S] in the caller's order (both NULL = the default band): each shard
+ * gets its slice. Every shard's values are checked before any is stored. */
+int  dopf_multi_set_storage_terminal_level(dopf_multi *m, const double *lo, const double *hi);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);
