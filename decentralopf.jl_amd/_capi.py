@@ -82,6 +82,7 @@ F_WIDE_NETWORK = 8388608
 F_DEBUG_WIDE_NET = 16777216
 F_STO_INITIAL_LEVEL = 33554432
 F_STO_TERMINAL_LEVEL = 67108864
+F_GEN_AVAILABILITY = 134217728
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -175,6 +176,8 @@ class CApi:
             self._sig("multi_set_storage_initial_level", C.c_int, [ctxp, c_double_p])
             self._sig("set_storage_terminal_level", C.c_int, [ctxp, c_double_p, c_double_p])
             self._sig("multi_set_storage_terminal_level", C.c_int, [ctxp, c_double_p, c_double_p])
+            self._sig("set_generator_availability", C.c_int, [ctxp, C.c_int32, c_double_p, c_int32_p])
+            self._sig("multi_set_generator_availability", C.c_int, [ctxp, C.c_int32, c_double_p, c_int32_p])
 
     def _sig(self, name, restype, argtypes):
         f = getattr(self.lib, self.prefix + name)
@@ -280,18 +283,48 @@ def _terminal_level_params(api: CApi, params: Optional[DopfParams], sto_end_lo, 
     return q, (lo, hi)
 
 
+def _availability_arrays(profiles, profile_of, T: int, G: int):
+    """(K, profiles as float64 [t + T*k], profile_of as int32 (G,)) from a (K, T) array (or None) and G indices (or None)."""
+    if profiles is None and profile_of is None:
+        return 0, None, None
+    prof = np.zeros((0, T)) if profiles is None else np.asarray(profiles, dtype=np.float64).reshape(-1, T)
+    of = None if profile_of is None else _i32(profile_of, G)
+    return int(prof.shape[0]), np.ascontiguousarray(prof).ravel(), of
+
+
+def _availability_params(api: CApi, params: Optional[DopfParams], gen_avail, gen_avail_of, T: int, G: int):
+    """(params, (profiles, profile_of)) for an engine built with availability profiles: the params with F_GEN_AVAILABILITY added
+    (a copy) — or (params, None) when there is nothing to set (both None, or every generator on -1 / an all-ones profile on an API
+    without availability)."""
+    if gen_avail is None and gen_avail_of is None:
+        return params, None
+    K, prof, of = _availability_arrays(gen_avail, gen_avail_of, T, G)
+    if not hasattr(api, "set_generator_availability"):
+        used = [] if of is None else sorted({int(k) for k in of if k >= 0})
+        if any(k >= K or np.any(prof.reshape(K, T)[k] != 1.0) for k in used):
+            raise DopfError(f"{api.prefix}*: this API has no generator availability (a profile other than all ones; the "
+                            "reference keeps every generator at max_generation)")
+        return params, None
+    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
+    q.flags |= F_GEN_AVAILABILITY
+    return q, (prof.reshape(K, T), of)
+
+
 class Engine:
     """A context of the C ABI with numpy in/out. Mirrors include/dopf.h one to one.
     sto_e0 (optional, S values): the storages' initial levels — sets F_STO_INITIAL_LEVEL and calls
     dopf_set_storage_initial_level after create. sto_end_lo / sto_end_hi (optional, S values each): the band of the level
-    after the last timestep — sets F_STO_TERMINAL_LEVEL and calls dopf_set_storage_terminal_level (after the initial levels)."""
+    after the last timestep — sets F_STO_TERMINAL_LEVEL and calls dopf_set_storage_terminal_level (after the initial levels).
+    gen_avail (optional, K x T) / gen_avail_of (optional, G indices in [-1, K)): the generators' availability profiles — sets
+    F_GEN_AVAILABILITY and calls dopf_set_generator_availability."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
-                 mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None):
+                 mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None):
         self.api = api
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
         params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
+        params, avail = _availability_params(api, params, gen_avail, gen_avail_of, int(T), _f64(gen_mc).size)
         self.N, self.L, self.T = int(N), int(L), int(T)
         gen_mc = _f64(gen_mc)
         sto_mc = _f64(sto_mc)
@@ -318,6 +351,8 @@ class Engine:
             self.set_initial_levels(e0)
         if band is not None:
             self.set_terminal_levels(*band)
+        if avail is not None:
+            self.set_availability(*avail)
 
     # -- lifecycle -----------------------------------------------------------------------------
     def close(self):
@@ -405,6 +440,14 @@ class Engine:
         a = None if lo is None else _f64(lo, self.S)
         b = None if hi is None else _f64(hi, self.S)
         self._chk(self.api.set_storage_terminal_level(self._ctx, _dp(a), _dp(b)))
+
+    def set_availability(self, profiles=None, profile_of=None):
+        """dopf_set_generator_availability: K profiles (K x T, values in [0, 1]) and each generator's profile (G indices, -1 =
+        max_generation); both None resets every generator to -1. Needs F_GEN_AVAILABILITY. Takes effect at the next x-update."""
+        if not hasattr(self.api, "set_generator_availability"):
+            raise DopfError(f"{self.api.prefix}*: this API has no generator availability")
+        K, prof, of = _availability_arrays(profiles, profile_of, self.T, self.G)
+        self._chk(self.api.set_generator_availability(self._ctx, K, _dp(prof), None if of is None else of.ctypes.data_as(c_int32_p)))
 
     def warm_start_stats(self):
         """(storages the warm-start kernel solved, storages it left to the scan kernel) in the LAST iteration."""
@@ -553,10 +596,11 @@ class MultiEngine:
 
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
-                 sto_end_lo=None, sto_end_hi=None):
+                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None):
         self.api = api
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
         params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
+        params, avail = _availability_params(api, params, gen_avail, gen_avail_of, int(T), _f64(gen_mc).size)
         self.N, self.L, self.T = int(N), int(L), int(T)
         gen_mc = _f64(gen_mc)
         sto_mc = _f64(sto_mc)
@@ -582,6 +626,14 @@ class MultiEngine:
             self.set_initial_levels(e0)
         if band is not None:
             self.set_terminal_levels(*band)
+        if avail is not None:
+            self.set_availability(*avail)
+
+    def set_availability(self, profiles=None, profile_of=None):
+        """dopf_multi_set_generator_availability: K profiles (K x T) and all G generators' indices in the caller's order (every
+        shard gets the whole table and its slice); both None resets every generator to -1."""
+        K, prof, of = _availability_arrays(profiles, profile_of, self.T, self.G)
+        self._chk(self.api.multi_set_generator_availability(self._m, K, _dp(prof), None if of is None else of.ctypes.data_as(c_int32_p)))
 
     def set_initial_levels(self, e0=None):
         """dopf_multi_set_storage_initial_level: all storages' initial levels in the caller's order (None = all 0)."""

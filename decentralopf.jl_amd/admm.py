@@ -152,6 +152,13 @@ class ADMM:
         than the default); takes effect at the next iteration."""
         self.engine.set_terminal_levels(lo, hi)
 
+    def set_availability(self, profiles=None, profile_of=None) -> None:
+        """The generators' availability: K profiles (K x T, values in [0, 1]) and each generator's profile (G indices in the order
+        of `generators`, -1 = always max_generation); both None = every generator at max_generation. The box of P[g,t] becomes
+        [0, max_generation * profiles[k][t]]. Not in the reference (one nameplate value per generator). Needs
+        flags=F_GEN_AVAILABILITY (set for you when a Generator has an availability series); takes effect at the next iteration."""
+        self.engine.set_availability(profiles, profile_of)
+
     # -- one iteration -------------------------------------------------------------------------
     def _fetch_result(self) -> Result:
         P, D, C, E = self.engine.get_primal()

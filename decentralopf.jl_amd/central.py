@@ -45,12 +45,14 @@ class CentralResult:
     nodal_price: np.ndarray         # (N, T)
 
 
-def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None) -> CentralResult:
+def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None,
+                         availability=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
     tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
     side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference). terminal_level:
     (lo, hi), (S,) each, the bounds of the level after the last timestep E[:, T-1] (None: the packed case's band, else
-    [0, max_level] as in the reference)."""
+    [0, max_level] as in the reference). availability: (profiles (K, T), profile_of (G,)), the upper bound of P[g,t] becomes
+    gen_pmax[g] * profiles[profile_of[g], t] (gen_pmax for -1; None: the packed case's profiles, else gen_pmax as in the reference)."""
     from scipy import sparse
     from scipy.optimize import linprog
     N, L, T, G, S = pp.N, pp.L, pp.T, pp.G, pp.S
@@ -65,6 +67,15 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
     ub = np.concatenate([np.repeat(pp.gen_pmax, T), np.repeat(pp.sto_pmax, T), np.repeat(pp.sto_pmax, T),
                          np.repeat(pp.sto_emax, T), np.full(nI, np.inf), np.full(2 * nL, np.inf)])
     lb[oI:oI + nI] = -np.inf
+    if availability is None and pp.has_availability():
+        availability = pp.availability()
+    if availability is not None and G > 0:
+        prof = np.asarray(availability[0], dtype=np.float64).reshape(-1, T)
+        of = np.asarray(availability[1], dtype=np.int64).reshape(G)
+        pm = np.asarray(pp.gen_pmax, dtype=np.float64)
+        f = np.ones((G, T))
+        f[of >= 0] = prof[of[of >= 0]]
+        ub[:nP] = np.where((of >= 0)[:, None], pm[:, None] * f, pm[:, None]).reshape(-1)      # one multiply, as the kernels
     tt = np.arange(T)
     rows, cols, vals, beq = [], [], [], []
     # I[n,t] - sum of the node's units = -demand[n,t]          rows n*T + t

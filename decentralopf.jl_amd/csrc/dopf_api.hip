@@ -81,6 +81,28 @@ int check_initial_levels(dopf_ctx *c, const double *e0)
 
 // dopf_set_storage_terminal_level's checks: the flag, both arrays or neither, 0 <= lo <= hi <= emax (no NaN), and the band reachable
 // from the stored initial level
+int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of)
+{
+    if (!(c->q.flags & DOPF_F_GEN_AVAILABILITY))
+        return fail(c, DOPF_E_UNSUPPORTED, "generator availability needs DOPF_F_GEN_AVAILABILITY at dopf_create");
+    if (K < 0) return fail(c, DOPF_E_INVALID, "n_profiles = %d < 0", K);
+    if (K > 0 && !profiles) return fail(c, DOPF_E_INVALID, "profiles is NULL with n_profiles = %d", K);
+    if (K > 0 && !profile_of) return fail(c, DOPF_E_INVALID, "profile_of is NULL with n_profiles = %d", K);
+    const int T = c->v.T, G = c->v.G;
+    if ((int64_t)K * T > ((int64_t)1 << 40)) return fail(c, DOPF_E_INVALID, "n_profiles = %d: table too large", K);
+    for (int64_t i = 0; i < (int64_t)K * T; ++i) {
+        const double f = profiles[i];
+        if (std::isnan(f)) return fail(c, DOPF_E_INVALID, "profiles[%lld] (profile %lld, t = %lld) is NaN", (long long)i, (long long)(i / T), (long long)(i % T));
+        if (!(f >= 0.0 && f <= 1.0))
+            return fail(c, DOPF_E_INVALID, "profiles[%lld] (profile %lld, t = %lld) = %g outside [0, 1]", (long long)i, (long long)(i / T), (long long)(i % T), f);
+    }
+    if (profile_of)
+        for (int g = 0; g < G; ++g)
+            if (profile_of[g] < -1 || profile_of[g] >= K)
+                return fail(c, DOPF_E_INVALID, "profile_of[%d] = %d outside [-1, %d)", g, profile_of[g], K);
+    return DOPF_OK;
+}
+
 int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi)
 {
     if (!(c->q.flags & DOPF_F_STO_TERMINAL_LEVEL))
@@ -199,6 +221,9 @@ Plan plan_chain(const Shape &sh, unsigned flags, int cus)
     // DOPF_F_STO_INITIAL_LEVEL / DOPF_F_STO_TERMINAL_LEVEL: the general bodies' level-mode instantiations (a level before timestep 0;
     // and a band after the last one); the lean body has none
     p.stoE0 = S > 0 && (flags & DOPF_F_STO_INITIAL_LEVEL);
+    // DOPF_F_GEN_AVAILABILITY: the same chain, with the generator bodies' AV instantiations (cap <= gen_pmax: every bound derived
+    // from gen_pmax below and in dopf_create stays valid)
+    p.genAvail = G > 0 && (flags & DOPF_F_GEN_AVAILABILITY);
     p.stoLV = S == 0 ? 0 : (flags & DOPF_F_STO_TERMINAL_LEVEL) ? 2 : (flags & DOPF_F_STO_INITIAL_LEVEL) ? 1 : 0;
     p.stoLean = !((flags & (DOPF_F_STO_GENERAL | DOPF_F_STO_INITIAL_LEVEL | DOPF_F_STO_TERMINAL_LEVEL)) ||
                   (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
@@ -318,6 +343,18 @@ Plan plan_chain(const Shape &sh, unsigned flags, int cus)
 
 namespace dopf {
 
+// DOPF_F_GEN_AVAILABILITY: the caps changed — a row summarised as "all at the cap" (gen_state 1) becomes "mixed" (2)
+__global__ void k_demote_full_rows(int *state, int G)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < G && state[g] == 1) state[g] = 2;
+}
+
+void launch_demote_full_rows(const DevView &v, hipStream_t s)
+{
+    if (v.G > 0) hipLaunchKernelGGL(k_demote_full_rows, dim3((v.G + 255) / 256), dim3(256), 0, s, v.gen_state, v.G);
+}
+
 void drop_graphs(dopf_ctx *c)
 {
     for (auto &gs : c->graphs) {
@@ -424,7 +461,7 @@ void enqueue_local(dopf_ctx *c, const Step &st, const hipEvent_t *ev = nullptr)
     mark(E_G0, c->main);
     if (p.fuseAgents) launch_agents_fused(v, p, c->main);
     else if (p.fuseNet) launch_net_agents(v, p, c->main);
-    else launch_gen_update(v, c->main);
+    else launch_gen_update(v, p, c->main);
     mark(E_G1, c->main);
     if (fork) {
         hipStreamWaitEvent(c->main, c->evJoin, 0);
@@ -757,7 +794,13 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     }
     TRY(dev_upload(c, &v.node_gitem_beg, ngib)); TRY(dev_upload(c, &v.node_sitem_beg, nsib));
     TRY(dev_alloc(c, &v.P, (size_t)G * T));
-    TRY(dev_alloc(c, &v.gen_state, G));            // zero = "all zero", which is what P is now
+    TRY(dev_alloc(c, &v.gen_state, gen_state_ints(G, pl.genAvail)));            // zero = "all zero", which is what P is now
+    if (pl.genAvail) {
+        // DOPF_F_GEN_AVAILABILITY: every generator on gen_pmax until the setter (gen_prof(v), behind the row states); no table yet
+        // (its address, behind those, is null)
+        c->gen_prof_h.assign(G, -1);
+        HIPTRY(hipMemcpyAsync(gen_prof(v), c->gen_prof_h.data(), sizeof(int) * G, hipMemcpyHostToDevice, c->main));
+    }
     TRY(dev_alloc(c, &v.D, (size_t)S * T)); TRY(dev_alloc(c, &v.C, (size_t)S * T)); TRY(dev_alloc(c, &v.E, (size_t)S * T));
     if (L > 0) { TRY(dev_alloc(c, &v.dltG, (size_t)G * T)); TRY(dev_alloc(c, &v.dltS, (size_t)S * T)); }
     TRY(dev_alloc(c, &v.lam, T)); TRY(dev_alloc(c, &v.mu, LT)); TRY(dev_alloc(c, &v.rho, LT));
@@ -1378,6 +1421,42 @@ int dopf_set_storage_terminal_level(dopf_ctx *c, const double *lo, const double 
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->sto_lo_h.assign(h.begin(), h.begin() + S);
     c->sto_hi_h.assign(h.begin() + S, h.end());
+    return DOPF_OK;
+}
+
+int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const double *profiles, const int32_t *profile_of)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_generator_availability(c, n_profiles, profiles, profile_of)) return rc;
+    DevView &v = c->v;
+    const int G = v.G, T = v.T;
+    if (G == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<int> pr(G, -1);
+    if (profile_of)
+        for (int i = 0; i < G; ++i) pr[i] = profile_of[c->gen_perm[i]];
+    const size_t need = (size_t)n_profiles * T;
+    if (n_profiles > c->gen_avail_cap) {
+        // the table grows: a new allocation, whose address goes into gen_avail_slot(v) behind everything queued (the kernels read it
+        // there, once per block). The iteration graphs are captured again at the next dopf_iterate. (The old table stays allocated
+        // until the context goes.)
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        const int cap = std::max(n_profiles, 2 * c->gen_avail_cap);
+        double *tab = nullptr;
+        if (int rc = dev_alloc(c, &tab, (size_t)cap * T, false)) return rc;
+        c->gen_avail = tab;
+        c->gen_avail_cap = cap;
+        HIPCHK(c, hipMemcpyAsync(gen_avail_slot(v), &c->gen_avail, sizeof(double *), hipMemcpyHostToDevice, c->main));
+        drop_graphs(c);
+    }
+    // ordered on the context's stream behind what is queued there: the table, the indices, and the rows that sat at their old caps
+    // (state 1) demoted to "mixed" — at the new caps they are not (state 0 stays: a row at 0 is at 0 under any cap >= 0)
+    if (need) HIPCHK(c, hipMemcpyAsync(c->gen_avail, profiles, need * sizeof(double), hipMemcpyHostToDevice, c->main));
+    HIPCHK(c, hipMemcpyAsync(gen_prof(v), pr.data(), sizeof(int) * G, hipMemcpyHostToDevice, c->main));
+    launch_demote_full_rows(v, c->main);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    c->gen_prof_h = pr;
     return DOPF_OK;
 }
 

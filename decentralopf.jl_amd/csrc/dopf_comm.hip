@@ -710,6 +710,19 @@ int dopf_multi_set_storage_terminal_level(dopf_multi *m, const double *lo, const
     return DOPF_OK;
 }
 
+int dopf_multi_set_generator_availability(dopf_multi *m, int32_t n_profiles, const double *profiles, const int32_t *profile_of)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all profiles as they were
+        for (int i = 0; i < m->n; ++i) {           // (every shard gets the whole table and its slice of the indices)
+            const int32_t *pi = profile_of ? profile_of + m->g0[i] : nullptr;
+            const int rc = pass == 0 ? check_generator_availability(m->ctx[i], n_profiles, profiles, pi)
+                                     : dopf_set_generator_availability(m->ctx[i], n_profiles, profiles, pi);
+            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
+        }
+    return DOPF_OK;
+}
+
 int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E)
 {
     if (!m) return DOPF_E_INVALID;

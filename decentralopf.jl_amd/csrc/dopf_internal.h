@@ -171,6 +171,18 @@ __host__ __device__ inline const double *sto_e0(const DevView &v) { return v.sto
 __host__ __device__ inline const double *sto_end_lo(const DevView &v) { return v.sto_emax + 2 * (size_t)v.S; }
 __host__ __device__ inline const double *sto_end_hi(const DevView &v) { return v.sto_emax + 3 * (size_t)v.S; }
 
+// DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
+// gen_pmax[g] for k = -1. gen_state has room for both behind its G row states: the G profile indices (sorted order, -1 until
+// dopf_set_generator_availability), then, on the next 8-byte boundary, the device address of the profile table f (grown by the
+// setter). The view, every kernel's argument, keeps its layout: a longer DevView moved the register allocation of the fused
+// storage kernels.
+__host__ __device__ inline int *gen_prof(const DevView &v) { return v.gen_state + v.G; }
+__host__ __device__ inline const double **gen_avail_slot(const DevView &v)
+{
+    return reinterpret_cast<const double **>(v.gen_state + ((2 * (size_t)v.G + 1) & ~(size_t)1));
+}
+inline size_t gen_state_ints(int G, bool avail) { return avail ? ((2 * (size_t)G + 1) & ~(size_t)1) + 2 : (size_t)G; }
+
 #ifndef DOPF_ACC_REP
 #define DOPF_ACC_REP 16
 #endif
@@ -229,6 +241,7 @@ struct Plan {
     Consensus consensus;
     bool sliceDual;                 // the one-block dual kernel may add k_reduce's slices itself (DevView::sliceDual)
     bool useWarm, stoLean;          // storage warm start (DevView::use_warm); the lean active-set body (sto_lean.h)
+    bool genAvail;                  // DOPF_F_GEN_AVAILABILITY: the generator bodies that read the rows' profiles (nothing else of the plan changes)
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag)
@@ -267,7 +280,7 @@ void central_launch_metrics(const CentralView &c, const DevView &vreduce, const 
 void central_launch_scale_copy(double *dst, const double *src, double scale, size_t n, hipStream_t s);
 
 // kernels_agents.hip
-void launch_gen_update(const DevView &v, hipStream_t s);
+void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s);

@@ -36,6 +36,32 @@ __device__ __forceinline__ double clampd(double v, double lo, double hi)
     return fmin(fmax(v, lo), hi);
 }
 
+// DOPF_F_GEN_AVAILABILITY (the AV instantiations of the generator bodies): the row's upper bound at a timestep, cap = pmax * f with f
+// the row's profile value — one fp64 multiply, never contracted into the sums that add it (a kept row adds cap itself, and the full
+// sweep adds the clamped value: both must be the same bits). prof < 0: pmax, no shape is read.
+__device__ __forceinline__ double avail_mul(double pm, double f)
+{
+#pragma clang fp contract(off)
+    return pm * f;
+}
+
+// (f: the profile table, *gen_avail_slot(v), loaded once per block)
+__device__ __forceinline__ double avail_cap(const double *f, int T, int prof, double pm, int t)
+{
+    return prof >= 0 ? avail_mul(pm, f[(size_t)prof * T + t]) : pm;
+}
+
+// the pair columns 2 tt, 2 tt + 1 of the row (T even: [t + T*k] is 16-byte aligned)
+__device__ __forceinline__ double2 avail_cap2(const double *tab, int prof, double pm, size_t half, int tt)
+{
+    double2 c{pm, pm};
+    if (prof >= 0) {
+        const double2 f = reinterpret_cast<const double2 *>(tab)[(size_t)prof * half + tt];
+        c.x = avail_mul(pm, f.x); c.y = avail_mul(pm, f.y);
+    }
+    return c;
+}
+
 // 1/x to fp64 rounding without the ~30-instruction division sequence: hardware estimate + two Newton steps
 __device__ __forceinline__ double rcp64(double x)
 {
@@ -242,7 +268,8 @@ __device__ __forceinline__ void lin_coef(double w, double iw, double kap, double
 // One item of generators at a node of a network (tables of the node's Psi): a block of BS threads, thread (r, tt) of an R x TT
 // tiling, ceil(T / TT) column passes. k_gen_update<true> runs it with 512 threads, k_net_agents (generators and storages of a
 // network in ONE launch) with 256 and the same R — the same rows meet in the same order, the sums carry the same bits.
-template <int BS, int FL = 4>
+// AV (DOPF_F_GEN_AVAILABILITY): the upper bound is the row's cap (avail_cap) instead of pmax; nothing else changes
+template <int BS, int FL = 4, bool AV = false>
 __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item, const int TT, const int R)
 {
     __shared__ double red[BS];
@@ -252,6 +279,9 @@ __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item,
     const int r = tid / TT, tt = tid - r * TT;
     const double w = v.w_prox;
     double cost = 0.0;
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
 
     for (int tc = 0; tc < T; tc += TT) {
         const int t = tc + tt;
@@ -267,10 +297,16 @@ __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item,
             const bool keepd = v.keepDeltas || v.walk_any[t];      // the change is needed agent by agent only for walked slack sums
             for (int g0 = it.a0 + r; g0 < it.a1; g0 += FL * R) {         // FL agents' rows in flight per lane (added in row order)
                 double mc[FL], pm[FL], p0[FL];
+                int pr[FL];
 #pragma unroll
                 for (int u = 0; u < FL; ++u) {
                     const int g = g0 + u * R < it.a1 ? g0 + u * R : g0;
                     mc[u] = v.gen_mc[g]; pm[u] = v.gen_pmax[g]; p0[u] = v.P[(size_t)g * T + t];
+                    if constexpr (AV) pr[u] = prof[g];
+                }
+                if constexpr (AV) {
+#pragma unroll
+                    for (int u = 0; u < FL; ++u) pm[u] = avail_cap(ftab, T, pr[u], pm[u], t);
                 }
 #pragma unroll
                 for (int u = 0; u < FL; ++u) {
@@ -325,7 +361,7 @@ __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item,
 // rows' costs are loaded once. A block of that launch is one of a few hundred that pass through the wave slots the storage
 // blocks leave free, each a chain of dependent round trips: two chains in parallel instead of one behind the other. Per
 // timestep the same rows meet in the same order as in gen_lines_body: the injection sums carry the same bits.
-template <int BS, int FL>
+template <int BS, int FL, bool AV = false>
 __device__ __forceinline__ void gen_lines_body2(const DevView &v, const int item, const int TT, const int R)
 {
     __shared__ double red[2][BS];
@@ -336,6 +372,9 @@ __device__ __forceinline__ void gen_lines_body2(const DevView &v, const int item
     const double w = v.w_prox;
     double cost = 0.0, acc[2] = {0.0, 0.0};
     const bool on[2] = {r < R && tt < T, r < R && tt + TT < T};
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
     if (on[0]) {
         int m[2];
         const double *beta[2], *psi[2], *slope[2];
@@ -355,13 +394,22 @@ __device__ __forceinline__ void gen_lines_body2(const DevView &v, const int item
 #pragma unroll
         for (int c = 0; c < 2; ++c) inv0[c] = rcp64(inv0[c] + w);          // (empty table: one piece for every agent of the node)
         for (int g0 = it.a0 + r; g0 < it.a1; g0 += FL * R) {              // FL agents' rows in flight per lane and column
-            double mc[FL], pm[FL], p0[2][FL];
+            double mc[FL], pm[FL], p0[2][FL], cp[2][FL];
+            int pr[FL];
 #pragma unroll
             for (int u = 0; u < FL; ++u) {
                 const int g = g0 + u * R < it.a1 ? g0 + u * R : g0;
                 mc[u] = v.gen_mc[g]; pm[u] = v.gen_pmax[g];
                 p0[0][u] = v.P[(size_t)g * T + tt];
                 p0[1][u] = v.P[(size_t)g * T + (on[1] ? tt + TT : tt)];
+                if constexpr (AV) pr[u] = prof[g];
+            }
+            if constexpr (AV) {
+#pragma unroll
+                for (int u = 0; u < FL; ++u) {
+                    cp[0][u] = avail_cap(ftab, T, pr[u], pm[u], tt);
+                    cp[1][u] = avail_cap(ftab, T, pr[u], pm[u], on[1] ? tt + TT : tt);
+                }
             }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
@@ -383,7 +431,7 @@ __device__ __forceinline__ void gen_lines_body2(const DevView &v, const int item
                         const int a = lo < m[c] ? lo : m[c] - 1;
                         dl = beta[c][a] - (mc[u] + psi[c][a] + w * beta[c][a]) * rcp64(slope[c][lo] + w);
                     }
-                    const double pn = clampd(p0[c][u] + dl, 0.0, pm[u]);
+                    const double pn = clampd(p0[c][u] + dl, 0.0, AV ? cp[c][u] : pm[u]);
                     v.P[e] = pn;
                     if (keepd[c]) v.dltG[e] = pn - p0[c][u];
                     acc[c] += pn;
@@ -416,12 +464,12 @@ __device__ __forceinline__ void gen_lines_body2(const DevView &v, const int item
     }
 }
 
-template <bool LINES>
-__global__ __launch_bounds__(512) void k_gen_update(DevView v)
+template <bool LINES, bool AV>
+__device__ __forceinline__ void gen_update_body(const DevView &v)
 {
     if (v.st->halt) return;
     if (LINES) {
-        gen_lines_body<512>(v, blockIdx.x, v.genTT, v.genR);
+        gen_lines_body<512, 4, AV>(v, blockIdx.x, v.genTT, v.genR);
         return;
     }
     __shared__ double red[512];
@@ -432,6 +480,9 @@ __global__ __launch_bounds__(512) void k_gen_update(DevView v)
     const double w = v.w_prox, gam = v.gamma;
     const double inv = 1.0 / (w + gam);
     double cost = 0.0;
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
 
     for (int tc = 0; tc < T; tc += TT) {
         const int t = tc + tt;
@@ -444,7 +495,7 @@ __global__ __launch_bounds__(512) void k_gen_update(DevView v)
                 const size_t e = (size_t)g * T + t;
                 const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
                 const double p0 = v.P[e];
-                const double pn = clampd(p0 - (mc * inv + shift), 0.0, pm);
+                const double pn = clampd(p0 - (mc * inv + shift), 0.0, AV ? avail_cap(ftab, T, prof[g], pm, t) : pm);
                 v.P[e] = pn;
                 acc += pn;
                 cost += mc * pn;
@@ -471,6 +522,19 @@ __global__ __launch_bounds__(512) void k_gen_update(DevView v)
         for (int q = 0; q < 8; ++q) c += wcost[q];
         v.part_gcost[blockIdx.x] = c;
     }
+}
+
+template <bool LINES>
+__global__ __launch_bounds__(512) void k_gen_update(DevView v)
+{
+    gen_update_body<LINES, false>(v);
+}
+
+// DOPF_F_GEN_AVAILABILITY: the same with the rows' caps (kernels of their own: the flagless ones keep their code)
+template <bool LINES>
+__global__ __launch_bounds__(512) void k_gen_update_av(DevView v)
+{
+    gen_update_body<LINES, true>(v);
 }
 
 // End of a generator block of the pair kernels: per-column sums of the R agent lanes and the block's cost, every sum in
@@ -514,7 +578,8 @@ __device__ __forceinline__ void gen_pair_sums(const DevView &v, const int blk, c
 // Copper plate, even T: each thread owns TWO consecutive timesteps of an agent, so every P access is a
 // 16-byte-per-lane double2 (the widest coalesced form), half as many load/store instructions per byte.
 // returns false when the block found the halted state (nothing stored, nothing added)
-template <int BS, bool TAIL, bool CHECK_HALT = false>
+// AV: the rows' caps (DOPF_F_GEN_AVAILABILITY), the profile index loaded with mc / pmax
+template <int BS, bool TAIL, bool CHECK_HALT = false, bool AV = false>
 __device__ __forceinline__ bool gen_pair_body(const DevView &v, const int blk)
 {
     const int halt = CHECK_HALT ? v.st->halt : 0;        // (the load is in flight with the ones below)
@@ -531,6 +596,9 @@ __device__ __forceinline__ bool gen_pair_body(const DevView &v, const int blk)
     const double w = v.w_prox, gam = v.gamma;
     const double inv = 1.0 / (w + gam);
     double cost = 0.0, acc0 = 0.0, acc1 = 0.0;
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
     if (r < R) {
         const int t = 2 * tt;
         const double sh0 = fma(gam, v.s[t], v.price[it.node + N * t]) * inv;
@@ -543,13 +611,19 @@ __device__ __forceinline__ bool gen_pair_body(const DevView &v, const int blk)
         // (the fused launch cuts config2's generators into items of 6 rows per lane: one batch)
         constexpr int GU = BS == 256 ? 6 : 4;
         for (int g0 = it.a0 + r; g0 < it.a1; g0 += GU * R) {
-            double2 p0[GU];
+            double2 p0[GU], cp[GU];
             double mc[GU], pm[GU];
+            int pr[GU];
 #pragma unroll
             for (int u = 0; u < GU; ++u) {
                 const int g = g0 + u * R < it.a1 ? g0 + u * R : g0;          // (a valid row; result dropped below)
                 mc[u] = v.gen_mc[g]; pm[u] = v.gen_pmax[g];
                 p0[u] = P2[(size_t)g * half + tt];
+                if constexpr (AV) pr[u] = prof[g];
+            }
+            if constexpr (AV) {
+#pragma unroll
+                for (int u = 0; u < GU; ++u) cp[u] = avail_cap2(ftab, pr[u], pm[u], half, tt);
             }
 #pragma unroll
             for (int u = 0; u < GU; ++u) {
@@ -557,8 +631,8 @@ __device__ __forceinline__ bool gen_pair_body(const DevView &v, const int blk)
                 if (g >= it.a1) break;
                 double2 pn;
                 // explicit fma: the row-skipping variant below must round exactly like this sweep
-                pn.x = clampd(p0[u].x - fma(mc[u], inv, sh0), 0.0, pm[u]);
-                pn.y = clampd(p0[u].y - fma(mc[u], inv, sh1), 0.0, pm[u]);
+                pn.x = clampd(p0[u].x - fma(mc[u], inv, sh0), 0.0, AV ? cp[u].x : pm[u]);
+                pn.y = clampd(p0[u].y - fma(mc[u], inv, sh1), 0.0, AV ? cp[u].y : pm[u]);
                 P2[(size_t)g * half + tt] = pn;
                 acc0 += pn.x; acc1 += pn.y;
                 cost = fma(mc[u], pn.x + pn.y, cost);
@@ -581,7 +655,9 @@ __device__ __forceinline__ bool gen_pair_body(const DevView &v, const int blk)
 // order, bitwise reproducible; no LDS traffic or barrier inside the loop). (Tried: items drawn from a counter so that blocks starting late can help
 // — a same-address device-scope atomic per item costs more than it balances on eight L2s: 26 vs 21 us.)
 // returns false when the block found the halted state (nothing stored, nothing added)
-template <int BS, bool TAIL>
+// AV: the rows' caps (DOPF_F_GEN_AVAILABILITY); the profile index travels with the next batch's loads, the shape values are read
+// (L2) in front of the batch's work
+template <int BS, bool TAIL, bool AV = false>
 __device__ __forceinline__ bool gen_pair_stream(const DevView &v, const int first, const int stride)
 {
     constexpr int GU = kGenStreamRows;
@@ -601,12 +677,16 @@ __device__ __forceinline__ bool gen_pair_stream(const DevView &v, const int firs
     const size_t half = (size_t)(T >> 1);
     double2 pa[GU], pb[GU];
     double mca[GU], pma[GU], mcb[GU], pmb[GU];
+    int pra[GU], prb[GU];
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
     // Straight-line on purpose. The wait before a use is a count of NEWER operations the in-order counter may leave
     // outstanding, fixed per program point: any path on which the next batch's loads are skipped (no next item, a lane
     // without a row, an early exit from the row loop) makes the compiler assume that path everywhere — the use then
     // waits for the next batch as well and the overlap is gone. So: every lane loads every time (a valid row, dropped
     // if it is not its own), the last item is loaded once more instead of nothing, rows are masked, not skipped.
-#define DOPF_GEN_LOAD(item, p, mc, pm)                                                      \
+#define DOPF_GEN_LOAD(item, p, mc, pm, pr)                                                  \
     {                                                                                       \
         const int a0_ = (item) * chunk, a1_ = min(G, a0_ + chunk);                          \
         _Pragma("unroll") for (int u = 0; u < GU; ++u) {                                    \
@@ -614,17 +694,23 @@ __device__ __forceinline__ bool gen_pair_stream(const DevView &v, const int firs
             const double2 mp_ = v.gen_mp[g_];                                               \
             mc[u] = mp_.x; pm[u] = mp_.y;                                                   \
             p[u] = P2[(size_t)g_ * half + tt];                                              \
+            if constexpr (AV) pr[u] = prof[g_];                                             \
         }                                                                                   \
     }
-#define DOPF_GEN_WORK(item, p, mc, pm)                                                      \
+#define DOPF_GEN_WORK(item, p, mc, pm, pr)                                                  \
     {                                                                                       \
         const int a0_ = (item) * chunk, a1_ = min(G, a0_ + chunk);                          \
+        double2 cp_[GU];                                                                    \
+        if constexpr (AV) {                                                                 \
+            _Pragma("unroll") for (int u = 0; u < GU; ++u)                                  \
+                cp_[u] = avail_cap2(ftab, pr[u], pm[u], half, tt);                          \
+        }                                                                                   \
         _Pragma("unroll") for (int u = 0; u < GU; ++u) {                                    \
             const int g_ = a0_ + r + u * R;                                                 \
             const bool mine = rowlane && g_ < a1_;                                          \
             double2 pn;            /* explicit fma: rounds exactly like gen_pair_body */     \
-            pn.x = clampd(p[u].x - fma(mc[u], inv, sh0), 0.0, pm[u]);                       \
-            pn.y = clampd(p[u].y - fma(mc[u], inv, sh1), 0.0, pm[u]);                       \
+            pn.x = clampd(p[u].x - fma(mc[u], inv, sh0), 0.0, AV ? cp_[u].x : pm[u]);       \
+            pn.y = clampd(p[u].y - fma(mc[u], inv, sh1), 0.0, AV ? cp_[u].y : pm[u]);       \
             if (mine) {                                                                     \
                 P2[(size_t)g_ * half + tt] = pn;                                            \
                 acc0 += pn.x; acc1 += pn.y;                                                 \
@@ -634,16 +720,16 @@ __device__ __forceinline__ bool gen_pair_stream(const DevView &v, const int firs
     }
     double acc0 = 0.0, acc1 = 0.0, cost = 0.0;
     int i = first;
-    DOPF_GEN_LOAD(i, pa, mca, pma)
+    DOPF_GEN_LOAD(i, pa, mca, pma, pra)
     for (;;) {
         const int j = i + stride;
-        DOPF_GEN_LOAD(min(j, nI - 1), pb, mcb, pmb)
+        DOPF_GEN_LOAD(min(j, nI - 1), pb, mcb, pmb, prb)
         if (halt) return false;                              // (uniform) nothing is stored in a halted state
-        DOPF_GEN_WORK(i, pa, mca, pma)
+        DOPF_GEN_WORK(i, pa, mca, pma, pra)
         if (j >= nI) break;
         const int k = j + stride;
-        DOPF_GEN_LOAD(min(k, nI - 1), pa, mca, pma)
-        DOPF_GEN_WORK(j, pb, mcb, pmb)
+        DOPF_GEN_LOAD(min(k, nI - 1), pa, mca, pma, pra)
+        DOPF_GEN_WORK(j, pb, mcb, pmb, prb)
         if (k >= nI) break;
         i = k;
     }
@@ -664,13 +750,23 @@ __global__ __launch_bounds__(512) void k_gen_update_pair(DevView v)
     gen_pair_body<512, MODE != 0>(v, blockIdx.x);
 }
 
+template <int MODE>
+__global__ __launch_bounds__(512) void k_gen_update_pair_av(DevView v)
+{
+    if (MODE == 2 && (int)blockIdx.x == v.nGenItems) { tail_block(v.self); return; }
+    if (v.st->halt) return;
+    gen_pair_body<512, MODE != 0, false, true>(v, blockIdx.x);
+}
+
 // Row skipping variant (used when a block sweeps many agents, so that its fixed cost is amortised): in a
 // settled dispatch two thirds of the generators sit at 0 or at pmax for ALL timesteps and stay there. A word
 // per generator remembers "all zero" / "all at pmax" / "mixed"; an all-zero row stays all zero iff
 // mc/(w+gamma) + min_t shift_t >= 0, an all-pmax row stays iff mc/(w+gamma) + max_t shift_t <= 0 (the update
 // then clamps every element back onto the same bound), so such a row is neither read nor written — its
 // contribution to the sums is 0 or pmax. Results are identical to the full sweep, bit for bit.
-template <int BS, bool TAIL>
+// AV (DOPF_F_GEN_AVAILABILITY): state 1 is "all at cap" (per column: pmax * f); a kept row adds its caps. The setter of the profiles
+// demotes every state-1 row to 2 (a row at its old caps is not at its new ones); state 0 stays valid under any cap >= 0.
+template <int BS, bool TAIL, bool AV = false>
 __device__ __forceinline__ void gen_pair_skip_body(const DevView &v, const int blk)
 {
     __shared__ double red[2][BS];
@@ -705,10 +801,14 @@ __device__ __forceinline__ void gen_pair_skip_body(const DevView &v, const int b
     // the row's state word and parameters are fetched one pass ahead: the decision "sweep or skip" then costs no round
     // trip of its own in front of the row load (a valid row is read when the lane has none: straight-line, dropped)
     double mcN, pmN;
-    int sttN;
+    int sttN, prN = -1;
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
     {
         const int g0_ = it.a0 + r < it.a1 && r < R ? it.a0 + r : it.a0;
         mcN = v.gen_mc[g0_]; pmN = v.gen_pmax[g0_]; sttN = v.gen_state[g0_];
+        if constexpr (AV) prN = prof[g0_];
     }
     for (int p = 0; p < nPass; ++p) {
         const int g = it.a0 + p * R + r;
@@ -716,27 +816,36 @@ __device__ __forceinline__ void gen_pair_skip_body(const DevView &v, const int b
         bool full = false;
         const double mc = mcN, pm = pmN;
         const int stt = sttN;                               // 0 all zero, 1 all at pmax, 2 mixed
+        const int pr = prN;
         {
             const int gn_ = g + R < it.a1 && r < R ? g + R : it.a0;
             mcN = v.gen_mc[gn_]; pmN = v.gen_pmax[gn_]; sttN = v.gen_state[gn_];
+            if constexpr (AV) prN = prof[gn_];
         }
         if (on) {
             // fma(mc, inv, .) is monotone in its addend, so its extremes over t are at smin / smax
             if (stt == 0 && fma(mc, inv, smin) >= 0.0) {
                 // stays all zero: nothing to read, write or add
             } else if (stt == 1 && fma(mc, inv, smax) <= 0.0) {
-                acc0 += pm; acc1 += pm; cost = fma(mc, pm + pm, cost);      // stays all at pmax
+                if constexpr (AV) {                         // stays all at cap
+                    const double2 cp = avail_cap2(ftab, pr, pm, half, tt);
+                    acc0 += cp.x; acc1 += cp.y; cost = fma(mc, cp.x + cp.y, cost);
+                } else {
+                    acc0 += pm; acc1 += pm; cost = fma(mc, pm + pm, cost);      // stays all at pmax
+                }
             } else {
                 full = true;
                 const size_t e = (size_t)g * half + tt;
                 const double2 p0 = P2[e];
+                double2 cp{pm, pm};
+                if constexpr (AV) cp = avail_cap2(ftab, pr, pm, half, tt);
                 double2 pn;
-                pn.x = clampd(p0.x - fma(mc, inv, sh0), 0.0, pm);
-                pn.y = clampd(p0.y - fma(mc, inv, sh1), 0.0, pm);
+                pn.x = clampd(p0.x - fma(mc, inv, sh0), 0.0, cp.x);
+                pn.y = clampd(p0.y - fma(mc, inv, sh1), 0.0, cp.y);
                 P2[e] = pn;
                 acc0 += pn.x; acc1 += pn.y;
                 cost = fma(mc, pn.x + pn.y, cost);
-                const int bits = ((pn.x == 0.0 && pn.y == 0.0) ? 1 : 0) | ((pn.x == pm && pn.y == pm) ? 2 : 0);
+                const int bits = ((pn.x == 0.0 && pn.y == 0.0) ? 1 : 0) | ((pn.x == cp.x && pn.y == cp.y) ? 2 : 0);
                 if (bits != 3) atomicAnd(&flg[p & 1][r], bits);
             }
         }
@@ -760,9 +869,34 @@ __global__ __launch_bounds__(512) void k_gen_update_pair_skip(DevView v)
     gen_pair_skip_body<512, MODE != 0>(v, blockIdx.x);
 }
 
-void launch_gen_update(const DevView &v, hipStream_t s)
+template <int MODE>
+__global__ __launch_bounds__(512) void k_gen_update_pair_skip_av(DevView v)
+{
+    if (MODE == 2 && (int)blockIdx.x == v.nGenItems) { tail_block(v.self); return; }
+    if (v.st->halt) return;
+    gen_pair_skip_body<512, MODE != 0, true>(v, blockIdx.x);
+}
+
+// DOPF_F_GEN_AVAILABILITY (p.genAvail): the same choice among the kernels with the rows' caps
+static void launch_gen_update_av(const DevView &v, hipStream_t s)
+{
+    if (v.L > 0) hipLaunchKernelGGL(k_gen_update_av<true>, dim3(v.nGenItems), dim3(512), 0, s, v);
+    else if (v.genTT2 > 0 && v.tail && v.nStoItems == 0) {
+        if (v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip_av<2>, dim3(v.nGenItems + 1), dim3(512), 0, s, v);
+        else hipLaunchKernelGGL(k_gen_update_pair_av<2>, dim3(v.nGenItems + 1), dim3(512), 0, s, v);
+    } else if (v.genTT2 > 0 && v.tail) {
+        if (v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip_av<1>, dim3(v.nGenItems), dim3(512), 0, s, v);
+        else hipLaunchKernelGGL(k_gen_update_pair_av<1>, dim3(v.nGenItems), dim3(512), 0, s, v);
+    }
+    else if (v.genTT2 > 0 && v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip_av<0>, dim3(v.nGenItems), dim3(512), 0, s, v);
+    else if (v.genTT2 > 0) hipLaunchKernelGGL(k_gen_update_pair_av<0>, dim3(v.nGenItems), dim3(512), 0, s, v);
+    else hipLaunchKernelGGL(k_gen_update_av<false>, dim3(v.nGenItems), dim3(512), 0, s, v);
+}
+
+void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s)
 {
     if (v.nGenItems == 0) return;
+    if (p.genAvail) { launch_gen_update_av(v, s); return; }
     if (v.L > 0) hipLaunchKernelGGL(k_gen_update<true>, dim3(v.nGenItems), dim3(512), 0, s, v);
     else if (v.genTT2 > 0 && v.tail && v.nStoItems == 0) {
         if (v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip<2>, dim3(v.nGenItems + 1), dim3(512), 0, s, v);
@@ -2243,6 +2377,40 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
 #endif
 }
 
+// DOPF_F_GEN_AVAILABILITY: the same kernel with the generator bodies' AV instantiations (a copy, not a shared body: as one
+// __forceinline__ body behind both, the flagless kernel's scalar spills moved — DESIGN.md 5j)
+template <int LPS, int NCH, bool LEAN, int LV = 0>
+__global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents_av(DevView v)
+{
+    static_assert(!(LEAN && LV), "the lean body has no initial or terminal level");
+    const int nS = v.nStoItems;
+    const bool isGen = (int)blockIdx.x >= nS;
+    const int gi = (int)blockIdx.x - nS, si = blockIdx.x;
+#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
+    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
+#endif
+    if (isGen) {
+        if (v.st->halt) return;
+        if (2 * v.genTT256 >= v.T) gen_lines_body2<256, DOPF_NET_GEN_FLIGHT, true>(v, gi, v.genTT256, v.genR);
+        else gen_lines_body<256, DOPF_NET_GEN_FLIGHT, true>(v, gi, v.genTT256, v.genR);
+    } else {
+        const int left = LEAN ? sto_lean_body<LPS, NCH, false, true, false>(v, si, v.st->halt)
+                              : sto_warm_body<LPS, NCH, true, false, false, LV>(v, si, v.st->halt); // ends on a __syncthreads
+        if (left < 0) return;                                                           // halted
+        if (left == 0) {                     // (what the scan body writes when there is nothing for it)
+            const int row = v.sto_items[si].row;
+            for (int t = threadIdx.x; t < v.T; t += 256) v.part_T[(size_t)t * v.rowsT + row] = 0.0;
+            if (threadIdx.x == 0) v.part_scost[si] = 0.0;
+        } else {
+            sto_cold_lines_call<LPS, NCH, LV>(v.self, si, left);
+        }
+    }
+#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
+    __syncthreads();
+    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
+#endif
+}
+
 // Warm start and, in the same block, the cold scan for what it left over: one launch for the storages of the big
 // copper-plate grids (the separate k_sto_update launch mostly found nothing to do).
 template <int LPS, int NCH, bool LINES, bool TAIL, bool FULLT, int LV = 0>
@@ -2290,6 +2458,36 @@ __global__ __launch_bounds__(256, 3) void k_agents(DevView v)
 #endif
 }
 
+// DOPF_F_GEN_AVAILABILITY: the same kernel with the generator bodies' AV instantiations (a copy, not a shared body: as one
+// __forceinline__ body behind both, the flagless kernel's scalar spills moved — DESIGN.md 5j)
+template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT, int LV = 0>
+__global__ __launch_bounds__(256, 3) void k_agents_av(DevView v)
+{
+    const int nS = v.nStoItems;
+#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
+    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
+#endif
+    if (TAIL && blockIdx.x == gridDim.x - 1) {
+        tail_block(v.self);
+    } else if (!SKIP && (int)blockIdx.x >= nS) {
+        // generator block: its loads do not wait for the halt word
+        if (v.genBlocks > 0) gen_pair_stream<256, TAIL, true>(v, blockIdx.x - nS, v.genBlocks);
+        else gen_pair_body<256, TAIL, true, true>(v, blockIdx.x - nS);
+    } else {
+        if ((int)blockIdx.x < nS) {
+            const int left = sto_warm_body<LPS, NCH, false, TAIL, FULLT, LV>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
+            if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT, LV>(v, blockIdx.x, left);            // __syncthreads: the sto_fail flags are visible)
+        } else {
+            if (v.st->halt) return;
+            gen_pair_skip_body<256, TAIL, true>(v, blockIdx.x - nS);
+        }
+    }
+#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
+    __syncthreads();
+    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
+#endif
+}
+
 // The same two launches with the lean copper-plate storage body (sto_lean.h): horizon == LPS * NCH, at most 32 lanes per storage.
 #ifndef DOPF_LEAN_STO_WAVES
 #define DOPF_LEAN_STO_WAVES 3
@@ -2322,6 +2520,35 @@ __global__ __launch_bounds__(256, 3) void k_agents_l(DevView v)
         } else {
             if (v.st->halt) return;
             gen_pair_skip_body<256, TAIL>(v, blockIdx.x - nS);
+        }
+    }
+#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
+    __syncthreads();
+    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
+#endif
+}
+
+// DOPF_F_GEN_AVAILABILITY: the same kernel with the generator bodies' AV instantiations (a copy, not a shared body: as one
+// __forceinline__ body behind both, the flagless kernel's scalar spills moved — DESIGN.md 5j)
+template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT = true>
+__global__ __launch_bounds__(256, 3) void k_agents_l_av(DevView v)
+{
+    const int nS = v.nStoItems;
+#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
+    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
+#endif
+    if (TAIL && blockIdx.x == gridDim.x - 1) {
+        tail_block(v.self);
+    } else if (!SKIP && (int)blockIdx.x >= nS) {
+        if (v.genBlocks > 0) gen_pair_stream<256, TAIL, true>(v, blockIdx.x - nS, v.genBlocks);
+        else gen_pair_body<256, TAIL, true, true>(v, blockIdx.x - nS);
+    } else {
+        if ((int)blockIdx.x < nS) {
+            const int left = sto_lean_body<LPS, NCH, TAIL, false, FULLT>(v, blockIdx.x, v.st->halt);
+            if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT>(v, blockIdx.x, left);
+        } else {
+            if (v.st->halt) return;
+            gen_pair_skip_body<256, TAIL, true>(v, blockIdx.x - nS);
         }
     }
 #if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
@@ -2421,6 +2648,13 @@ static void launch_agents_t(const DevView &v, const Plan &p, hipStream_t s)
     const dim3 grid(v.nStoItems + (v.genBlocks > 0 && !v.genSkip ? v.genBlocks : v.nGenItems) + (v.tail ? 1 : 0));
     with_bool(v.genSkip, [&](auto skip) { with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NCH, [&](auto full) {
         constexpr bool SK = decltype(skip)::value, TL = decltype(tail)::value, FU = decltype(full)::value;
+        if (p.genAvail) {           // DOPF_F_GEN_AVAILABILITY: the generator blocks with the rows' caps, the same storage bodies
+            if (p.stoLean) hipLaunchKernelGGL((k_agents_l_av<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 2) hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU, 2>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 1) hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU, 1>), grid, dim3(256), 0, s, v);
+            else hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
+            return;
+        }
         if (p.stoLean) hipLaunchKernelGGL((k_agents_l<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
         else if (p.stoLV == 2) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 2>), grid, dim3(256), 0, s, v);
         else if (p.stoLV == 1) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 1>), grid, dim3(256), 0, s, v);
@@ -2437,6 +2671,13 @@ void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s)
 {
     const dim3 grid(v.nStoItems + v.nGenItems);
     with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) {
+        if (p.genAvail) {           // DOPF_F_GEN_AVAILABILITY: the generator blocks with the rows' caps, the same storage bodies
+            if (p.stoLean) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 2) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false, 2>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 1) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false, 1>), grid, dim3(256), 0, s, v);
+            else hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false>), grid, dim3(256), 0, s, v);
+            return;
+        }
         if (p.stoLean) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
         else if (p.stoLV == 2) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 2>), grid, dim3(256), 0, s, v);
         else if (p.stoLV == 1) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 1>), grid, dim3(256), 0, s, v);

@@ -128,6 +128,7 @@ const DOPF_F_WIDE_NETWORK = 8388608  # include/dopf.h
 const DOPF_F_DEBUG_WIDE_NET = 16777216  # include/dopf.h (tests)
 const DOPF_F_STO_INITIAL_LEVEL = 33554432  # include/dopf.h
 const DOPF_F_STO_TERMINAL_LEVEL = 67108864  # include/dopf.h
+const DOPF_F_GEN_AVAILABILITY = 134217728  # include/dopf.h
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -143,7 +144,8 @@ Storages on horizons beyond 512 timesteps (an hourly year: T = 8 760) need `flag
 (the long-horizon storage body; without the flag the library refuses them). Networks of more than 2 048 lines
 need `flags = DOPF_F_WIDE_NETWORK` (the wide-network chain; without it the library refuses them). Storages that start a
 horizon from a given level (see `set_initial_levels!`) need `flags = DOPF_F_STO_INITIAL_LEVEL`; storages whose level after the
-last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_TERMINAL_LEVEL`. Flags combine with `|`.
+last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_TERMINAL_LEVEL`; generators that follow an
+availability profile (see `set_availability!`) need `flags = DOPF_F_GEN_AVAILABILITY`. Flags combine with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
@@ -267,6 +269,35 @@ function set_terminal_levels!(admm::ADMM, lo::Union{Nothing, Vector{Float64}}, h
         else
             dopf_check(ccall((:dopf_set_storage_terminal_level, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
                              admm.ctx, pl, ph), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    set_availability!(admm, profiles, profile_of)
+
+The generators' availability: `profiles` is T x K (column k = one per-unit profile, values in [0, 1]), `profile_of[g]` the
+profile of generator g (in the order of `generators`, 0-based, -1 = always `max_generation`); `nothing` for both = every
+generator at `max_generation`. The box of generator g at t becomes `[0, max_generation * profiles[t, profile_of[g] + 1]]`. The
+reference keeps one nameplate value per generator; the ADMM must have been created with `flags = DOPF_F_GEN_AVAILABILITY`.
+Takes effect at the next iteration.
+"""
+function set_availability!(admm::ADMM, profiles::Union{Nothing, Matrix{Float64}}, profile_of::Union{Nothing, Vector{Cint}})
+    T, G = length(admm.T), length(admm.generators)
+    (profiles === nothing) == (profile_of === nothing) || error("set_availability!: give both profiles and profile_of, or neither")
+    profiles === nothing || size(profiles, 1) == T || error("set_availability!: expected $T rows of profiles, got $(size(profiles, 1))")
+    profile_of === nothing || length(profile_of) == G || error("set_availability!: expected $G profile indices")
+    K = profiles === nothing ? 0 : size(profiles, 2)
+    pp = profiles === nothing ? Ptr{Cdouble}(C_NULL) : pointer(profiles)        # T x K column-major = [t + T*k]
+    po = profile_of === nothing ? Ptr{Cint}(C_NULL) : pointer(profile_of)
+    GC.@preserve profiles profile_of begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_generator_availability, DOPF_LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cint}),
+                                   admm.multi, K, pp, po), admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_generator_availability, DOPF_LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cint}),
+                             admm.ctx, K, pp, po), admm.ctx)
         end
     end
     return admm

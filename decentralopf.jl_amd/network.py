@@ -9,6 +9,9 @@ Storage.initial_level is not in the reference (which starts every storage empty,
 level before the first timestep, for runs that continue a previous horizon (DOPF_F_STO_INITIAL_LEVEL).
 Storage.terminal_level_min / terminal_level_max are not in the reference either (which lets the level after the last timestep
 lie anywhere in [0, max_level]): a band for that level, e.g. "end at least at X" or a cyclic horizon (DOPF_F_STO_TERMINAL_LEVEL).
+Generator.availability is not in the reference either (one nameplate max_generation for the whole horizon,
+src/optimization/subproblems.jl:26): T per-unit values in [0, 1], the box of P[t] becomes [0, max_generation * availability[t]] —
+a solar or wind profile, or a rolling horizon's renewable forecast (DOPF_F_GEN_AVAILABILITY).
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ class Generator:
     max_generation: int
     plot_color: str
     node: Node
+    availability: Optional[Sequence[float]] = None      # T per-unit values in [0, 1]; None = always max_generation (not in the reference)
 
 
 @dataclass(eq=False)
@@ -116,6 +120,8 @@ class PackedProblem:
     sto_e0: Optional[np.ndarray] = None     # (S,) Storage.initial_level; None = all 0
     sto_end_lo: Optional[np.ndarray] = None     # (S,) Storage.terminal_level_min; None = all 0
     sto_end_hi: Optional[np.ndarray] = None     # (S,) Storage.terminal_level_max; None = sto_emax
+    gen_avail: Optional[np.ndarray] = None      # (K, T) the distinct Generator.availability series; None = no generator has one
+    gen_avail_of: Optional[np.ndarray] = None   # (G,) int32 row of gen_avail per generator, -1 = always gen_pmax
 
     @property
     def G(self):
@@ -138,7 +144,20 @@ class PackedProblem:
             kw["sto_e0"] = np.asarray(self.sto_e0, dtype=np.float64)
         if self.has_terminal_band():      # (engines then run with F_STO_TERMINAL_LEVEL)
             kw["sto_end_lo"], kw["sto_end_hi"] = self.terminal_band()
+        if self.has_availability():      # (engines then run with F_GEN_AVAILABILITY)
+            kw["gen_avail"], kw["gen_avail_of"] = self.availability()
         return kw
+
+    def availability(self):
+        """(profiles (K, T) float64, profile_of (G,) int32): the generators' availability, K = 0 and all -1 when none has one."""
+        prof = np.zeros((0, self.T)) if self.gen_avail is None else np.asarray(self.gen_avail, dtype=np.float64).reshape(-1, self.T)
+        of = (np.full(self.G, -1, dtype=np.int32) if self.gen_avail_of is None
+              else np.asarray(self.gen_avail_of, dtype=np.int32))
+        return prof, of
+
+    def has_availability(self) -> bool:
+        """Some generator has an availability profile."""
+        return self.gen_avail_of is not None and bool(np.any(np.asarray(self.gen_avail_of) >= 0))
 
     def terminal_band(self):
         """(lo, hi) of the level after the last timestep, float64 (S,) each, the defaults filled in: [0, sto_emax]."""
@@ -168,7 +187,9 @@ class PackedProblem:
                       n_agents_global=self.G + self.S),
             sto_e0=None if self.sto_e0 is None else self.sto_e0[s0:s1],
             sto_end_lo=None if self.sto_end_lo is None else self.sto_end_lo[s0:s1],
-            sto_end_hi=None if self.sto_end_hi is None else self.sto_end_hi[s0:s1])
+            sto_end_hi=None if self.sto_end_hi is None else self.sto_end_hi[s0:s1],
+            gen_avail=self.gen_avail,
+            gen_avail_of=None if self.gen_avail_of is None else self.gen_avail_of[g0:g1])
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -181,6 +202,23 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
             raise ValueError("all nodes need a demand series of the same length")
     f64 = lambda xs: np.asarray(list(xs), dtype=np.float64)
     i32 = lambda xs: np.asarray(list(xs), dtype=np.int32)
+    # availability: identical series share one row of the table (one solar shape for many units)
+    rows, of, seen = [], [], {}
+    for g in generators:
+        if g.availability is None:
+            of.append(-1)
+            continue
+        a = f64(g.availability)
+        if a.shape != (T,):
+            raise ValueError(f"generator {g.name}: availability needs {T} values, got {a.size}")
+        if np.any(np.isnan(a)) or np.any(a < 0.0) or np.any(a > 1.0):
+            raise ValueError(f"generator {g.name}: availability values must lie in [0, 1]")
+        key = a.tobytes()
+        if key not in seen:
+            seen[key] = len(rows)
+            rows.append(a)
+        of.append(seen[key])
+    has_avail = bool(rows)
     return PackedProblem(
         N=len(nodes), L=len(lines), T=T,
         demand=np.asarray([n.demand for n in nodes], dtype=np.float64).reshape(len(nodes), T),
@@ -195,4 +233,6 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         sto_node=i32(idx[id(s.node)] for s in storages),
         sto_e0=f64(s.initial_level for s in storages),
         sto_end_lo=f64(s.terminal_level_min for s in storages),
-        sto_end_hi=f64(s.max_level if s.terminal_level_max is None else s.terminal_level_max for s in storages))
+        sto_end_hi=f64(s.max_level if s.terminal_level_max is None else s.terminal_level_max for s in storages),
+        gen_avail=np.asarray(rows, dtype=np.float64).reshape(len(rows), T) if has_avail else None,
+        gen_avail_of=i32(of) if has_avail else None)

@@ -114,6 +114,17 @@ class ShardedADMM:
         cut = lambda x: None if x is None else np.asarray(x, dtype=np.float64).reshape(self.problem.S)[s0:s1]
         self.engine.set_terminal_levels(cut(lo), cut(hi))
 
+    def set_availability(self, profiles=None, profile_of=None) -> None:
+        """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
+        max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs
+        F_GEN_AVAILABILITY in the params; every rank calls it between steps."""
+        if profiles is None and profile_of is None:
+            self.engine.set_availability(None, None)
+            return
+        g0, g1 = self.shard.meta["gen_range"]
+        of = None if profile_of is None else np.asarray(profile_of, dtype=np.int32).reshape(self.problem.G)[g0:g1]
+        self.engine.set_availability(profiles, of)
+
     def run(self, max_iters: int, check_every: int = 16):
         """Iterate until the stop test holds (checked every `check_every` iterations) or max_iters."""
         done = 0

@@ -156,6 +156,12 @@ typedef struct dopf_params {
                                   * Runs on the general active-set body, the scan body and the long-horizon body; with the default band the
                                   * results are those of DOPF_F_STO_GENERAL (with DOPF_F_STO_INITIAL_LEVEL: of that flag alone), bit for bit
                                   * where no storage has max_level 0 (there the last contact takes any price, so the path may differ). */
+#define DOPF_F_GEN_AVAILABILITY 134217728 /* generators follow availability profiles: the context keeps K profiles f[k][t] in [0, 1] and a
+                                  * profile index per generator (-1 until dopf_set_generator_availability), and every generator's box becomes
+                                  * 0 <= P[g,t] <= cap[g,t] = gen_pmax[g] * f[prof[g]][t] (one fp64 multiply; gen_pmax[g] for index -1) instead of
+                                  * the reference's 0 <= P <= max_generation (src/optimization/subproblems.jl:26). Nothing else changes: the same
+                                  * chain runs, with generator kernels that read the profiles; with every index -1, or every profile all ones, the
+                                  * results are those of the context without the flag, bit for bit. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -297,6 +303,16 @@ int dopf_set_storage_initial_level(dopf_ctx *ctx, const double *e0);
  * dopf_set_storage_initial_level refuses (DOPF_E_INVALID) an e0 from which the stored band is unreachable. */
 int dopf_set_storage_terminal_level(dopf_ctx *ctx, const double *lo, const double *hi);
 
+/* DOPF_F_GEN_AVAILABILITY: the generators' availability. profiles: T x n_profiles, [t + T*k] (agent-major like P), every value in
+ * [0, 1]; profile_of: G in the caller's order of this context's generators, -1 = always gen_pmax, else a profile in [0, n_profiles).
+ * n_profiles == 0 with both NULL resets every generator to -1. Many generators may share a profile (one solar shape per region): the
+ * kernels read the table per (row, timestep), and a small one stays in L2. Timing and copies as for dopf_set_storage_initial_level;
+ * a table larger than any before is allocated anew, and the iteration graphs are then captured again at the next dopf_iterate.
+ * dopf_set_state may hand in P above a cap: the next x-update clamps it. DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID, naming
+ * the entry and storing nothing, for a NaN, a value outside [0, 1], an index outside [-1, n_profiles), n_profiles < 0, or a NULL
+ * array with n_profiles > 0. */
+int dopf_set_generator_availability(dopf_ctx *ctx, int32_t n_profiles, const double *profiles, const int32_t *profile_of);
+
 /* ---- the central reference on the device ---------------------------------------------------------------
  * Replaces src/opf_central_reference.jl:16-81 (one JuMP model of the whole multi-period DC-OPF, solved by Gurobi): the same
  * LP — variables P, D, C, E in their boxes, energy balance per timestep, |ptdf * injection| <= f_max, storage balance —
@@ -366,6 +382,9 @@ int  dopf_multi_set_storage_initial_level(dopf_multi *m, const double *e0);
 /* dopf_set_storage_terminal_level for all storages, lo[S] and hi[S] in the caller's order (both NULL = the default band): each shard
  * gets its slice. Every shard's values are checked before any is stored. */
 int  dopf_multi_set_storage_terminal_level(dopf_multi *m, const double *lo, const double *hi);
+/* all G generators in the caller's order; every shard gets the whole table and its slice of profile_of (checked for every shard
+ * before any is stored) */
+int dopf_multi_set_generator_availability(dopf_multi *m, int32_t n_profiles, const double *profiles, const int32_t *profile_of);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);
