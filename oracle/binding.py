@@ -22,13 +22,21 @@ MODE_LITERAL, MODE_EXACT = 0, 1
 
 
 class OracleApi(_capi.CApi):
-    def __init__(self, path: str = ORACLE_LIB):
+    """features=True also binds the setters of the three problem extensions (storage initial and terminal levels, generator
+    availability), so that Engine(sto_e0=..., sto_end_lo=..., gen_avail=...) and its set_* methods drive them. Without it the API
+    has none of them, as the reference has none, and _capi refuses any non-default value (tests/test_*_abi.py pin that guard)."""
+
+    def __init__(self, path: str = ORACLE_LIB, features: bool = False):
         super().__init__(path, "oracle_", create_extra=(C.c_int32,))
         ctxp, dp, ip = C.c_void_p, _capi.c_double_p, _capi.c_int32_p
         self._sig("set_threads", None, [ctxp, C.c_int32])
         self._sig("get_agent_slacks", C.c_int, [ctxp, C.c_int32, dp, dp])
         self._sig("calculate_ptdf", C.c_int, [C.c_int32, C.c_int32, ip, ip, dp, C.c_int32, dp])
         self._sig("qp_solve", C.c_int, [C.c_int32, C.c_int32] + [dp] * 8 + [ip])
+        if features:
+            self._sig("set_storage_initial_level", C.c_int, [ctxp, dp])
+            self._sig("set_storage_terminal_level", C.c_int, [ctxp, dp, dp])
+            self._sig("set_generator_availability", C.c_int, [ctxp, C.c_int32, dp, ip])
 
 
 def set_threads(engine: _capi.Engine, n: int) -> None:

@@ -275,12 +275,74 @@ done:
 
 /* Mehrotra from the plain starting point; if that does not get close (seen on random network cases whose line
  * slacks sit thousands away from the start), once more from a starting point scaled to the problem. */
+static int qp_solve_twice(int32_t n, int32_t m, const double *Q, const double *c0, const double *A, const double *b0,
+                          const double *lb, const double *ub, double *xout, double *yout, int32_t *iters_out)
+{
+    int rc = qp_solve_from(n, m, Q, c0, A, b0, lb, ub, xout, yout, iters_out, 0);
+    if (rc != 0) rc = qp_solve_from(n, m, Q, c0, A, b0, lb, ub, xout, yout, iters_out, 1);
+    return rc;
+}
+
+/* A fixed variable has no interior, and the sliver qp_solve_from gives a box of one point leaves an error of its width (1e-9)
+ * in the answer. Fixed are: a variable whose box is one point (ub <= lb: a generator capped at 0, a storage with emax = 0 or
+ * pmax = 0, a terminal band lo == hi), and, repeatedly, the one unknown left in an equality row (the levels of a storage that
+ * cannot move). They are substituted and the QP over the others is solved; an equality row left without unknowns is dropped
+ * (multiplier 0). Without a box of one point this is qp_solve_twice as it stands. */
 int oracle_qp_solve(int32_t n, int32_t m, const double *Q, const double *c0, const double *A,
                     const double *b0, const double *lb, const double *ub, double *xout,
                     double *yout, int32_t *iters_out)
 {
-    int rc = qp_solve_from(n, m, Q, c0, A, b0, lb, ub, xout, yout, iters_out, 0);
-    if (rc != 0) rc = qp_solve_from(n, m, Q, c0, A, b0, lb, ub, xout, yout, iters_out, 1);
+    int any_fixed = 0;
+    for (int i = 0; i < n; ++i) any_fixed |= ub[i] <= lb[i];
+    if (!any_fixed) return qp_solve_twice(n, m, Q, c0, A, b0, lb, ub, xout, yout, iters_out);
+    char *fx = (char *)calloc(n ? n : 1, 1);
+    int *fi = (int *)calloc(n ? n : 1, sizeof(int)), *ri = (int *)calloc(m ? m : 1, sizeof(int));
+    double *val = dalloc(n), *Qr = dalloc((size_t)n * n), *cr = dalloc(n), *Ar = dalloc((size_t)m * n), *br = dalloc(m);
+    double *lr = dalloc(n), *ur = dalloc(n), *xr = dalloc(n), *yr = dalloc(m);
+    int rc = -1, nf = 0, mr = 0;
+    if (!fx || !fi || !ri || !val || !Qr || !cr || !Ar || !br || !lr || !ur || !xr || !yr) goto done;
+    for (int i = 0; i < n; ++i) if (ub[i] <= lb[i]) { fx[i] = 1; val[i] = lb[i]; }
+    for (int changed = 1; changed;) {
+        changed = 0;
+        for (int r = 0; r < m; ++r) {
+            int unk = -1, cnt = 0;
+            double v = b0[r];
+            for (int i = 0; i < n; ++i) {
+                const double a = A[(size_t)r * n + i];
+                if (a == 0.0) continue;
+                if (fx[i]) v -= a * val[i];
+                else { unk = i; ++cnt; }
+            }
+            if (cnt == 1) { fx[unk] = 1; val[unk] = v / A[(size_t)r * n + unk]; changed = 1; }
+        }
+    }
+    for (int i = 0; i < n; ++i) if (!fx[i]) fi[nf++] = i;
+    for (int j = 0; j < nf; ++j) {
+        double v = c0[fi[j]];
+        for (int i = 0; i < n; ++i) if (fx[i]) v += Q[(size_t)fi[j] * n + i] * val[i];
+        cr[j] = v; lr[j] = lb[fi[j]]; ur[j] = ub[fi[j]];
+        for (int k = 0; k < nf; ++k) Qr[(size_t)j * nf + k] = Q[(size_t)fi[j] * n + fi[k]];
+    }
+    for (int r = 0; r < m; ++r) {
+        int any = 0;
+        for (int j = 0; j < nf; ++j) any |= A[(size_t)r * n + fi[j]] != 0.0;
+        if (!any) continue;
+        double v = b0[r];
+        for (int i = 0; i < n; ++i) if (fx[i]) v -= A[(size_t)r * n + i] * val[i];
+        for (int j = 0; j < nf; ++j) Ar[(size_t)mr * nf + j] = A[(size_t)r * n + fi[j]];
+        br[mr] = v; ri[mr++] = r;
+    }
+    rc = nf ? qp_solve_twice(nf, mr, Qr, cr, Ar, br, lr, ur, xr, yr, iters_out) : 0;
+    if (rc == 0) {
+        for (int i = 0; i < n; ++i) xout[i] = val[i];
+        for (int j = 0; j < nf; ++j) xout[fi[j]] = xr[j];
+        if (yout) {
+            for (int r = 0; r < m; ++r) yout[r] = 0.0;
+            for (int q = 0; q < mr; ++q) yout[ri[q]] = yr[q];
+        }
+    }
+done:
+    free(fx); free(fi); free(ri); free(val); free(Qr); free(cr); free(Ar); free(br); free(lr); free(ur); free(xr); free(yr);
     return rc;
 }
 
@@ -306,6 +368,11 @@ struct oracle_ctx {
     int bisect_only;        /* ORACLE_BISECT=1: plain bisection in the exact storage solve (cross-check of the regula falsi) */
     double *demand, *ptdf, *fmax, *gen_mc, *gen_pmax, *sto_mc, *sto_pmax, *sto_emax;
     int *gen_node, *sto_node;
+    /* DOPF_F_STO_INITIAL_LEVEL / DOPF_F_STO_TERMINAL_LEVEL / DOPF_F_GEN_AVAILABILITY (the defaults until a setter is called:
+     * e0 = 0, the band [0, emax], every generator on profile -1 = gen_pmax) */
+    double *sto_e0, *sto_lo, *sto_hi;
+    double *avail;          /* n_prof x T, [t + T*k] */
+    int n_prof, *gen_prof;
     dopf_params q;
     int A_global;
     /* admm.iteration (admm.jl:29), Convergence.all */
@@ -370,6 +437,9 @@ int oracle_create(oracle_ctx **out, const dopf_problem *p, const dopf_params *q,
     c->sto_node = (int *)calloc(p->S ? p->S : 1, sizeof(int));
     for (int g = 0; g < p->G; ++g) c->gen_node[g] = p->gen_node[g];
     for (int s = 0; s < p->S; ++s) c->sto_node[s] = p->sto_node[s];
+    c->sto_e0 = dalloc(p->S); c->sto_lo = dalloc(p->S); c->sto_hi = dupd(p->sto_emax, p->S);
+    c->gen_prof = (int *)calloc(p->G ? p->G : 1, sizeof(int));
+    for (int g = 0; g < p->G; ++g) c->gen_prof[g] = -1;
     c->iteration = 1;                                   /* admm.jl:29 */
     c->lam = dalloc(p->T); c->mu = dalloc(LT); c->rho = dalloc(LT);   /* zeros, admm.jl:34-36 */
     c->lam_used = dalloc(p->T); c->mu_used = dalloc(LT); c->rho_used = dalloc(LT);
@@ -396,6 +466,7 @@ void oracle_destroy(oracle_ctx *c)
     if (!c) return;
     free(c->demand); free(c->ptdf); free(c->fmax); free(c->gen_mc); free(c->gen_pmax);
     free(c->sto_mc); free(c->sto_pmax); free(c->sto_emax); free(c->gen_node); free(c->sto_node);
+    free(c->sto_e0); free(c->sto_lo); free(c->sto_hi); free(c->avail); free(c->gen_prof);
     free(c->lam); free(c->mu); free(c->rho); free(c->lam_used); free(c->mu_used); free(c->rho_used);
     free(c->P); free(c->D); free(c->C); free(c->E); free(c->agentU); free(c->agentK);
     free(c->ngen); free(c->ndis); free(c->nchg); free(c->inj); free(c->avgU); free(c->avgK);
@@ -461,6 +532,14 @@ static double node_price(const oracle_ctx *c, const double *lam, const double *m
     return v;
 }
 
+/* the generator's upper bound at t: gen_pmax, or gen_pmax * f[prof][t] under DOPF_F_GEN_AVAILABILITY (the same one multiply as
+ * the kernels) */
+static double gen_cap(const oracle_ctx *c, int g, int t)
+{
+    const int k = c->gen_prof[g];
+    return k < 0 ? c->gen_pmax[g] : c->gen_pmax[g] * c->avail[t + (size_t)c->T * k];
+}
+
 /* optimize_subproblem(generator), subproblems.jl:19-105 */
 static int literal_generator(oracle_ctx *c, int g, double *Pnew, double *U, double *K)
 {
@@ -473,7 +552,7 @@ static int literal_generator(oracle_ctx *c, int g, double *Pnew, double *U, doub
     for (int i = 0; i < n; ++i) { lb[i] = 0; ub[i] = INFINITY; }
     for (int t = 0; t < T; ++t) {
         const int iP = t, iU = T + L * t, iK = T + L * T + L * t;
-        ub[iP] = c->gen_pmax[g];                                    /* :26 */
+        ub[iP] = gen_cap(c, g, t);                                  /* :26 */
         o.c[iP] += c->gen_mc[g] + node_price(c, c->lam, c->mu, c->rho, own, t);     /* :66-75 */
         double one = 1.0;
         literal_penalties(c, &o, t, own, 1, &iP, &one, prevP[t], 0, 0, iU, iK);
@@ -511,10 +590,12 @@ static int literal_storage(oracle_ctx *c, int s, double *Dn, double *Cn, double 
         double one = 1.0;
         qp_add_sq(&o, c->q.w_prox / 2, 1, &iD, &one, -pD[t]);       /* :180 */
         qp_add_sq(&o, c->q.w_prox / 2, 1, &iC, &one, -pC[t]);       /* :181 */
-        /* StorageBalance: E[t] == (t == 1 ? 0 : E[t-1]) + C[t] - D[t]   :150-156 */
+        /* StorageBalance: E[t] == (t == 1 ? e0 : E[t-1]) + C[t] - D[t]   :150-156 (e0 = 0 there) */
         A[t * n + iE] = 1.0; A[t * n + iC] = -1.0; A[t * n + iD] = 1.0;
         if (t > 0) A[t * n + iE - 1] = -1.0;
+        else b[t] = c->sto_e0[s];
     }
+    lb[3 * T - 1] = c->sto_lo[s]; ub[3 * T - 1] = c->sto_hi[s];     /* E[T-1] in the terminal band ([0, emax] there) */
     rc = oracle_qp_solve(n, T, o.Q, o.c, A, b, lb, ub, x, NULL, NULL);
     if (rc == 0) {
         for (int t = 0; t < T; ++t) {
@@ -614,8 +695,8 @@ static void build_table(oracle_ctx *c, int n, int t)
     c->tb_psi0[at] = psi_eval(c, n, t, 0.0);
 }
 
-/* exact generator step: P* = clamp(root of mc + Psi(P - P0) + w_prox (P - P0), 0, pmax) */
-static double exact_gen_step(const oracle_ctx *c, int n, int t, double mc, double pmax, double P0)
+/* exact generator step: P* = clamp(root of mc + Psi(P - P0) + w_prox (P - P0), 0, cap) */
+static double exact_gen_step(const oracle_ctx *c, int n, int t, double mc, double cap, double P0)
 {
     const size_t M2 = 2 * (size_t)c->L, at = (size_t)n + (size_t)c->N * t;
     const double *beta = c->tb_beta + at * (M2 ? M2 : 1), *psi = c->tb_psi + at * (M2 ? M2 : 1);
@@ -630,7 +711,7 @@ static double exact_gen_step(const oracle_ctx *c, int n, int t, double mc, doubl
         const int j = lo, a = j < m ? j : m - 1;
         dlt = beta[a] - (mc + psi[a] + w * beta[a]) / (slope[j] + w);
     }
-    return clampd(P0 + dlt, 0.0, pmax);
+    return clampd(P0 + dlt, 0.0, cap);
 }
 
 /* min over the box [0,pm]^2 of the strictly convex 2x2 quadratic with gradient
@@ -646,7 +727,7 @@ static void box2(double a, double b, double rD, double rC, double pm, double *D,
     else { *C = Cf; *D = Df; }
 }
 
-typedef struct { int n, t; double mc, pm, D0, C0; } sto_step;
+typedef struct { int n, t; double mc, pm, D0, C0, elo, ehi; } sto_step;   /* elo, ehi: the bounds of the level after step t */
 
 /* (D,C)(nu) = argmin over the box of the step-t objective minus nu * (C - D); net charge
  * x = C - D is continuous and nondecreasing in nu. */
@@ -676,51 +757,55 @@ static void sto_eval(const oracle_ctx *c, const sto_step *st, double nu, double 
     box2(w + sg, sg, w * st->D0 - st->mc - theta - nu, w * st->C0 - st->mc + theta + nu, st->pm, D, C);
 }
 
-/* S_k(nu) of the forward recursion F_t = clamp(F_{t-1} + x_t(nu), 0, emax), F_0 = 0, and the
- * trajectory; returns the largest index <= k whose unclamped level leaves [0, emax] (or -1). */
-static int sto_scan(const oracle_ctx *c, const sto_step *st, int k, double emax, double nu,
+/* S_k(nu) of the forward recursion F_t = clamp(F_{t-1} + x_t(nu), elo_t, ehi_t), F_{-1} = e0, and the
+ * trajectory; returns the largest index <= k whose unclamped level leaves [elo_t, ehi_t] (or -1). */
+static int sto_scan(const oracle_ctx *c, const sto_step *st, int k, double e0, double nu,
                     double *Dv, double *Cv, double *Fv, double *Sv, double tol)
 {
-    double e = 0.0;
+    double e = e0;
     int last = -1;
     for (int t = 0; t <= k; ++t) {
         sto_eval(c, &st[t], nu, &Dv[t], &Cv[t]);
         double sv = e + (Cv[t] - Dv[t]);
         Sv[t] = sv;
-        if (sv < -tol || sv > emax + tol) last = t;
-        e = clampd(sv, 0.0, emax);
+        if (sv < st[t].elo - tol || sv > st[t].ehi + tol) last = t;
+        e = clampd(sv, st[t].elo, st[t].ehi);
         Fv[t] = e;
     }
     return last;
 }
 
 /* exact storage step. Optimality: E_t = F_t(nu_{t+1}) and nu_t = nu_{t+1} unless the unclamped
- * level S_t(nu_{t+1}) leaves [0, emax]; then E_t sits on that bound and nu_t is the root of
- * S_t(nu) = bound. nu_{T+1} = 0 (no terminal value of stored energy). See DESIGN.md. */
+ * level S_t(nu_{t+1}) leaves [elo_t, ehi_t]; then E_t sits on that bound and nu_t is the root of
+ * S_t(nu) = bound. nu_{T+1} = 0 (no terminal value of stored energy). The level before step 0 is e0;
+ * every step has [0, emax] but the last, which has the terminal band [lo, hi] ([0, emax] by default).
+ * See DESIGN.md sections 3, 5h, 5i. */
 static int exact_storage(const oracle_ctx *c, int s, double *Dn, double *Cn, double *En)
 {
     const int T = c->T;
-    const double emax = c->sto_emax[s], pm = c->sto_pmax[s];
+    const double emax = c->sto_emax[s], pm = c->sto_pmax[s], e0 = c->sto_e0[s];
     const double tol = 1e-11 * (1.0 + emax);
     sto_step *st = (sto_step *)calloc(T, sizeof *st);
     double *Dv = dalloc(T), *Cv = dalloc(T), *Fv = dalloc(T), *Sv = dalloc(T);
     for (int t = 0; t < T; ++t) {
         st[t].n = c->sto_node[s]; st[t].t = t; st[t].mc = c->sto_mc[s]; st[t].pm = pm;
         st[t].D0 = c->D[(size_t)T * s + t]; st[t].C0 = c->C[(size_t)T * s + t];
+        st[t].elo = t == T - 1 ? c->sto_lo[s] : 0.0;
+        st[t].ehi = t == T - 1 ? c->sto_hi[s] : emax;
     }
     double nu = 0.0;
     int k = T - 1, rc = 0;
     while (k >= 0) {
-        int v = sto_scan(c, st, k, emax, nu, Dv, Cv, Fv, Sv, tol);
+        int v = sto_scan(c, st, k, e0, nu, Dv, Cv, Fv, Sv, tol);
         for (int t = v + 1; t <= k; ++t) { Dn[t] = Dv[t]; Cn[t] = Cv[t]; }
         if (v < 0) break;
-        const int low = Sv[v] < 0.0;
-        const double target = low ? 0.0 : emax;
+        const int low = Sv[v] < st[v].elo;
+        const double target = low ? st[v].elo : st[v].ehi;
         /* bracket the root of S_v(nu) = target: S_v is nondecreasing in nu */
         double a = nu, b = nu, step = 1.0;
         int guard = 0;
-        if (low) { do { b = nu + step; step *= 2; sto_scan(c, st, v, emax, b, Dv, Cv, Fv, Sv, tol); } while (Sv[v] < target && ++guard < 1100); }
-        else     { do { a = nu - step; step *= 2; sto_scan(c, st, v, emax, a, Dv, Cv, Fv, Sv, tol); } while (Sv[v] > target && ++guard < 1100); }
+        if (low) { do { b = nu + step; step *= 2; sto_scan(c, st, v, e0, b, Dv, Cv, Fv, Sv, tol); } while (Sv[v] < target && ++guard < 1100); }
+        else     { do { a = nu - step; step *= 2; sto_scan(c, st, v, e0, a, Dv, Cv, Fv, Sv, tol); } while (Sv[v] > target && ++guard < 1100); }
         if (guard >= 1100) { rc = -1; break; }
         /* S_v(a) <= target <= S_v(b). Bracketed regula falsi (Illinois): S_v is piecewise linear, so the secant lands on
          * the root's piece after a few steps; every third step, and whenever the secant point is not strictly inside, the
@@ -728,8 +813,8 @@ static int exact_storage(const oracle_ctx *c, int s, double *Dn, double *Cn, dou
         int found = 0;
         if (!c->bisect_only) {
             double fa, fb;
-            sto_scan(c, st, v, emax, a, Dv, Cv, Fv, Sv, tol); fa = Sv[v] - target;
-            sto_scan(c, st, v, emax, b, Dv, Cv, Fv, Sv, tol); fb = Sv[v] - target;
+            sto_scan(c, st, v, e0, a, Dv, Cv, Fv, Sv, tol); fa = Sv[v] - target;
+            sto_scan(c, st, v, e0, b, Dv, Cv, Fv, Sv, tol); fb = Sv[v] - target;
             const double rtol = 1e-12 * (1.0 + emax);      /* the tolerance of the HIP kernels' root searches */
             if (fabs(fa) <= rtol) { nu = a; found = 1; }
             else if (fabs(fb) <= rtol) { nu = b; found = 1; }
@@ -738,7 +823,7 @@ static int exact_storage(const oracle_ctx *c, int s, double *Dn, double *Cn, dou
                 double x = (fb != fa) ? b - fb * (b - a) / (fb - fa) : 0.5 * (a + b);
                 if (it % 3 == 2 || !(x > a && x < b)) x = 0.5 * (a + b);
                 if (!(x > a && x < b)) break;                       /* adjacent doubles */
-                sto_scan(c, st, v, emax, x, Dv, Cv, Fv, Sv, tol);
+                sto_scan(c, st, v, e0, x, Dv, Cv, Fv, Sv, tol);
                 const double fx = Sv[v] - target;
                 if (fabs(fx) <= rtol) { nu = x; found = 1; break; }
                 if (fx < 0.0) { a = x; fa = fx; if (side == -1) fb *= 0.5; side = -1; }
@@ -749,16 +834,16 @@ static int exact_storage(const oracle_ctx *c, int s, double *Dn, double *Cn, dou
             for (int it = 0; it < 300; ++it) {
                 double mid = 0.5 * (a + b);
                 if (!(mid > a && mid < b)) break;
-                sto_scan(c, st, v, emax, mid, Dv, Cv, Fv, Sv, tol);
+                sto_scan(c, st, v, e0, mid, Dv, Cv, Fv, Sv, tol);
                 if (Sv[v] < target) a = mid; else b = mid;
             }
             nu = low ? b : a;
         }
-        sto_scan(c, st, v, emax, nu, Dv, Cv, Fv, Sv, tol);
+        sto_scan(c, st, v, e0, nu, Dv, Cv, Fv, Sv, tol);
         Dn[v] = Dv[v]; Cn[v] = Cv[v];
         k = v - 1;
     }
-    double e = 0.0;
+    double e = e0;
     for (int t = 0; t < T; ++t) { e += Cn[t] - Dn[t]; En[t] = e; }
     free(st); free(Dv); free(Cv); free(Fv); free(Sv);
     return rc;
@@ -815,7 +900,7 @@ int oracle_local_update(oracle_ctx *c)
             if (c->mode == ORACLE_MODE_LITERAL) fail |= literal_generator(c, g, Pn + (size_t)T * g, U, K) != 0;
             else for (int t = 0; t < T; ++t) {
                 double P0 = c->P[(size_t)T * g + t];
-                double Pv = exact_gen_step(c, n, t, c->gen_mc[g], c->gen_pmax[g], P0);
+                double Pv = exact_gen_step(c, n, t, c->gen_mc[g], gen_cap(c, g, t), P0);
                 Pn[(size_t)T * g + t] = Pv;
                 for (int l = 0; l < L; ++l) {
                     const double h = c->ptdf[l + L * n];
@@ -961,8 +1046,22 @@ int oracle_get_duals_used(oracle_ctx *c, double *lambda, double *mu, double *rho
     cpy(lambda, c->lam_used, c->T); cpy(mu, c->mu_used, (size_t)c->L * c->T); cpy(rho, c->rho_used, (size_t)c->L * c->T);
     return DOPF_OK;
 }
+/* ResultStorage.level: E = e0 + cumsum(C - D) from the current e0, in k_derive_level's order */
+static void derive_levels(oracle_ctx *c)
+{
+    const int T = c->T;
+    for (int s = 0; s < c->S; ++s) {
+        double e = c->sto_e0[s];
+        for (int t = 0; t < T; ++t) {
+            e += c->C[(size_t)T * s + t] - c->D[(size_t)T * s + t];
+            c->E[(size_t)T * s + t] = e;
+        }
+    }
+}
+
 int oracle_get_primal(oracle_ctx *c, double *P, double *D, double *C, double *E)
 {
+    if (E) derive_levels(c);
     cpy(P, c->P, (size_t)c->G * c->T); cpy(D, c->D, (size_t)c->S * c->T);
     cpy(C, c->C, (size_t)c->S * c->T); cpy(E, c->E, (size_t)c->S * c->T);
     return DOPF_OK;
@@ -1020,18 +1119,109 @@ int oracle_set_state(oracle_ctx *c, const double *P, const double *D, const doub
     /* re-derive the per-node totals and E from the primal state (single-shard view) */
     memset(c->ngen, 0, sizeof(double) * NT); memset(c->ndis, 0, sizeof(double) * NT); memset(c->nchg, 0, sizeof(double) * NT);
     for (int g = 0; g < c->G; ++g) for (int t = 0; t < T; ++t) c->ngen[c->gen_node[g] + N * t] += c->P[(size_t)T * g + t];
-    for (int s = 0; s < c->S; ++s) {
-        double e = 0;
+    for (int s = 0; s < c->S; ++s)
         for (int t = 0; t < T; ++t) {
             c->ndis[c->sto_node[s] + N * t] += c->D[(size_t)T * s + t];
             c->nchg[c->sto_node[s] + N * t] += c->C[(size_t)T * s + t];
-            e += c->C[(size_t)T * s + t] - c->D[(size_t)T * s + t];
-            c->E[(size_t)T * s + t] = e;
         }
-    }
+    derive_levels(c);
     for (size_t i = 0; i < NT; ++i) c->inj[i] = -c->demand[i] + c->ngen[i] + c->ndis[i] - c->nchg[i];
     c->iteration = iteration;
     c->converged = 0;
+    return DOPF_OK;
+}
+
+/* ------------------------------------------------------------------------------------------ */
+/* the three setters of include/dopf.h: same checks, same refusals, nothing stored on a refusal */
+/* ------------------------------------------------------------------------------------------ */
+
+/* the band [lo, hi] meets the end levels reachable from e0 in T steps of at most pm, [max(0, e0 - T pm), min(em, e0 + T pm)] */
+static int band_reachable(double e0, double lo, double hi, double pm, double em, int T)
+{
+    const double span = (double)T * pm;
+    return lo <= fmin(em, e0 + span) && hi >= dmax(0.0, e0 - span);
+}
+
+int oracle_set_storage_initial_level(oracle_ctx *c, const double *e0)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (!(c->q.flags & DOPF_F_STO_INITIAL_LEVEL)) {
+        snprintf(c->err, sizeof c->err, "storage initial levels need DOPF_F_STO_INITIAL_LEVEL at create");
+        return DOPF_E_UNSUPPORTED;
+    }
+    const int band = (c->q.flags & DOPF_F_STO_TERMINAL_LEVEL) != 0;
+    for (int s = 0; s < c->S; ++s) {
+        const double x = e0 ? e0[s] : 0.0;
+        if (!(x >= 0.0 && x <= c->sto_emax[s])) {
+            snprintf(c->err, sizeof c->err, "initial level of storage %d is %g, outside [0, max_level = %g]", s, x, c->sto_emax[s]);
+            return DOPF_E_INVALID;
+        }
+        if (band && !band_reachable(x, c->sto_lo[s], c->sto_hi[s], c->sto_pmax[s], c->sto_emax[s], c->T)) {
+            snprintf(c->err, sizeof c->err, "initial level %g of storage %d leaves its terminal band unreachable", x, s);
+            return DOPF_E_INVALID;
+        }
+    }
+    for (int s = 0; s < c->S; ++s) c->sto_e0[s] = e0 ? e0[s] + 0.0 : 0.0;
+    return DOPF_OK;
+}
+
+int oracle_set_storage_terminal_level(oracle_ctx *c, const double *lo, const double *hi)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (!(c->q.flags & DOPF_F_STO_TERMINAL_LEVEL)) {
+        snprintf(c->err, sizeof c->err, "storage terminal levels need DOPF_F_STO_TERMINAL_LEVEL at create");
+        return DOPF_E_UNSUPPORTED;
+    }
+    if (!lo != !hi) {
+        snprintf(c->err, sizeof c->err, "storage terminal levels: lo and hi must both be given or both be NULL");
+        return DOPF_E_INVALID;
+    }
+    for (int s = 0; lo && s < c->S; ++s) {
+        const double l = lo[s], h = hi[s], em = c->sto_emax[s];
+        if (!(l >= 0.0 && h <= em && l <= h)) {
+            snprintf(c->err, sizeof c->err, "terminal band of storage %d is [%g, %g], not inside [0, max_level = %g] (or empty)", s, l, h, em);
+            return DOPF_E_INVALID;
+        }
+        if (!band_reachable(c->sto_e0[s], l, h, c->sto_pmax[s], em, c->T)) {
+            snprintf(c->err, sizeof c->err, "terminal band [%g, %g] of storage %d is unreachable from its initial level %g", l, h, s, c->sto_e0[s]);
+            return DOPF_E_INVALID;
+        }
+    }
+    for (int s = 0; s < c->S; ++s) {
+        c->sto_lo[s] = lo ? lo[s] + 0.0 : 0.0;
+        c->sto_hi[s] = hi ? hi[s] + 0.0 : c->sto_emax[s];
+    }
+    return DOPF_OK;
+}
+
+int oracle_set_generator_availability(oracle_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of)
+{
+    if (!c) return DOPF_E_INVALID;
+    const int T = c->T, G = c->G;
+    if (!(c->q.flags & DOPF_F_GEN_AVAILABILITY)) {
+        snprintf(c->err, sizeof c->err, "generator availability needs DOPF_F_GEN_AVAILABILITY at create");
+        return DOPF_E_UNSUPPORTED;
+    }
+    if (K < 0 || (K > 0 && (!profiles || !profile_of)) || (int64_t)K * T > ((int64_t)1 << 40)) {
+        snprintf(c->err, sizeof c->err, "n_profiles = %d with profiles %s, profile_of %s", K, profiles ? "set" : "NULL", profile_of ? "set" : "NULL");
+        return DOPF_E_INVALID;
+    }
+    for (int64_t i = 0; i < (int64_t)K * T; ++i)
+        if (!(profiles[i] >= 0.0 && profiles[i] <= 1.0)) {
+            snprintf(c->err, sizeof c->err, "profiles[%lld] (profile %lld, t = %lld) = %g outside [0, 1]", (long long)i, (long long)(i / T), (long long)(i % T), profiles[i]);
+            return DOPF_E_INVALID;
+        }
+    for (int g = 0; profile_of && g < G; ++g)
+        if (profile_of[g] < -1 || profile_of[g] >= K) {
+            snprintf(c->err, sizeof c->err, "profile_of[%d] = %d outside [-1, %d)", g, profile_of[g], K);
+            return DOPF_E_INVALID;
+        }
+    double *tab = dupd(profiles, (size_t)K * T);
+    if (!tab) return DOPF_E_NOMEM;
+    free(c->avail);
+    c->avail = tab;
+    c->n_prof = K;
+    for (int g = 0; g < G; ++g) c->gen_prof[g] = profile_of ? profile_of[g] : -1;
     return DOPF_OK;
 }
 

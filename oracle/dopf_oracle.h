@@ -61,6 +61,14 @@ int oracle_get_nodal_price(oracle_ctx *ctx, int32_t which, double *out);
 int oracle_set_state(oracle_ctx *ctx, const double *P, const double *D, const double *C,
                      const double *avg_U, const double *avg_K,
                      const double *lambda, const double *mu, const double *rho, int32_t iteration);
+/* DOPF_F_STO_INITIAL_LEVEL, DOPF_F_STO_TERMINAL_LEVEL, DOPF_F_GEN_AVAILABILITY: the setters of include/dopf.h with the same
+ * signatures, checks and refusals (DOPF_E_UNSUPPORTED without the flag in params.flags; DOPF_E_INVALID, nothing stored). May be
+ * called between any two iterations. Literal mode: the right-hand side of the storage-balance row at t = 0 is e0, E[T-1] has the
+ * bounds [lo, hi], P[g,t] the upper bound cap[g,t]; exact mode: the same in the level recursion and the generator clamp. */
+int oracle_set_storage_initial_level(oracle_ctx *ctx, const double *e0);
+int oracle_set_storage_terminal_level(oracle_ctx *ctx, const double *lo, const double *hi);
+int oracle_set_generator_availability(oracle_ctx *ctx, int32_t n_profiles, const double *profiles, const int32_t *profile_of);
+
 /* Per-agent slack matrices of the last solve (ResultGenerator.U/K, ResultStorage.U/K,
  * src/structures/results.jl:1-17); agent index: generators 0..G-1 then storages G..G+S-1. */
 int oracle_get_agent_slacks(oracle_ctx *ctx, int32_t agent, double *U /*L*T*/, double *K /*L*T*/);

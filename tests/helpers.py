@@ -101,3 +101,129 @@ def storage_kkt_violation(pp, s_idx, D0, C0, D, C, E, theta, gamma, w=1.0, tol=1
         flo = np.where(bad, mid, flo)
         fhi = np.where(bad, mid, fhi)
     return max(worst, 0.0)
+
+
+def storage_kkt_violation_band(pp, D0, C0, D, C, E, theta, gamma, lo_end, hi_end, w=1.0, tol=1e-7):
+    """helpers.storage_kkt_violation with the terminal band: the level after the last timestep lies in [lo_end, hi_end] instead
+    of [0, emax]. The price past the horizon is 0, so the last segment's price is 0 with E_{T-1} strictly inside the band, >= 0 at
+    lo_end, <= 0 at hi_end and free with lo_end == hi_end. Returns the largest amount by which an interval of feasible prices is
+    empty (0 = optimal within tol)."""
+    mc = pp.sto_mc[:, None]
+    pm = pp.sto_pmax[:, None]
+    em = pp.sto_emax
+    q = D - C
+    gD = mc + theta + gamma * q + w * (D - D0)
+    gC = mc - theta - gamma * q + w * (C - C0)
+    inf = np.inf
+    lo = np.where(D <= tol, -gD, np.where(D >= pm - tol, -inf, -gD))
+    hi = np.where(D <= tol, inf, np.where(D >= pm - tol, -gD, -gD))
+    lo = np.maximum(lo, np.where(C <= tol, -inf, np.where(C >= pm - tol, gC, gC)))
+    hi = np.minimum(hi, np.where(C <= tol, gC, np.where(C >= pm - tol, inf, gC)))
+    degenerate = pm <= tol
+    lo = np.where(degenerate, -inf, lo)
+    hi = np.where(degenerate, inf, hi)
+    T = D.shape[1]
+    flo = np.zeros(D.shape[0])
+    fhi = np.zeros(D.shape[0])
+    worst = 0.0
+    for t in range(T - 1, -1, -1):
+        blo, bhi = (lo_end, hi_end) if t == T - 1 else (np.zeros_like(em), em)
+        at_hi = E[:, t] >= bhi - tol
+        at_lo = E[:, t] <= blo + tol
+        both = at_hi & at_lo          # a band of one point: any jump allowed
+        nlo = np.where(both, -inf, np.where(at_hi, -inf, flo))      # E on its upper bound: nu_t <= nu_{t+1}
+        nhi = np.where(both, inf, np.where(at_lo, inf, fhi))        # E on its lower bound: nu_t >= nu_{t+1}
+        nlo = np.where(at_lo & ~both, flo, nlo)
+        nhi = np.where(at_hi & ~both, fhi, nhi)
+        flo = np.maximum(nlo, lo[:, t])
+        fhi = np.minimum(nhi, hi[:, t])
+        worst = max(worst, float(np.max(flo - fhi)))
+        mid = 0.5 * (flo + fhi)
+        bad = flo > fhi
+        flo = np.where(bad, mid, flo)
+        fhi = np.where(bad, mid, fhi)
+    return max(worst, 0.0)
+
+
+# ---- inputs of the three problem extensions (storage initial levels, terminal bands, generator availability) ----------------
+
+def engine(api, pp, mode, flags=0, **params):
+    return _capi.Engine(api, params=_capi.default_params(flags=flags, **params), mode=mode, **pp.engine_kwargs())
+
+
+def set_from(e, st, iteration):
+    e.set_state(P=st["P"], D=st["D"], C_=st["C"], avg_U=st["avg_U"], avg_K=st["avg_K"], lam=st["lam"], mu=st["mu"],
+                rho=st["rho"], iteration=iteration)
+
+
+def reachable(pp, e0):
+    span = pp.T * pp.sto_pmax
+    return np.maximum(0.0, e0 - span), np.minimum(pp.sto_emax, e0 + span)
+
+
+def draw_e0(pp, kind, rng):
+    em = pp.sto_emax
+    return {"0": np.zeros(pp.S), "full": em.copy(), "inside": rng.uniform(0.1, 0.9, pp.S) * em,
+            "mix": np.where(np.arange(pp.S) % 3 == 0, 0.0, np.where(np.arange(pp.S) % 3 == 1, em, 0.5 * em))}[kind]
+
+
+def draw_band(pp, e0, kind, rng):
+    """default [0, emax]; eq: an equality target inside the reachable levels; cyclic: lo = hi = e0; edge: the highest
+    reachable level e0 + T pmax (capped at emax) as an equality; edge-lo: the lowest; mix: a bit of everything."""
+    rlo, rhi = reachable(pp, e0)
+    em = pp.sto_emax
+    x = rlo + rng.uniform(0.0, 1.0, pp.S) * (rhi - rlo)
+    if kind == "mix":
+        k = np.arange(pp.S) % 5
+        lo = np.select([k == 0, k == 1, k == 2, k == 3], [x, e0, rhi, np.minimum(x, 0.5 * (rlo + rhi))], 0.0)
+        hi = np.select([k == 0, k == 1, k == 2, k == 3], [x, e0, rhi, np.maximum(x, 0.5 * (rlo + rhi))], em)
+        return lo, hi
+    return {"default": (np.zeros(pp.S), em.copy()), "eq": (x, x.copy()), "cyclic": (e0.copy(), e0.copy()),
+            "edge": (rhi, rhi.copy()), "edge-lo": (rlo, rlo.copy())}[kind]
+
+
+def draw_profiles(pp, kind, rng):
+    """K profiles with zeros (night hours and a few random ones) and every third generator on -1."""
+    K = {"K1": 1, "K3": 3, "KG": pp.G}[kind]
+    prof = rng.uniform(0.0, 1.0, (K, pp.T))
+    prof[rng.random((K, pp.T)) < 0.2] = 0.0
+    prof[:, ::4] = 0.0
+    of = rng.integers(0, K, pp.G).astype(np.int32)
+    of[::3] = -1
+    return prof, of
+
+
+def degenerate(pp, kind):
+    """Storages that cannot store (emax = 0) or cannot move (pmax = 0)."""
+    if "emax0" in kind:
+        pp.sto_emax = pp.sto_emax.copy()
+        pp.sto_emax[::4] = 0.0
+    if "pmax0" in kind:
+        pp.sto_pmax = pp.sto_pmax.copy()
+        pp.sto_pmax[1::4] = 0.0
+    return pp
+
+
+class Features:
+    """One draw of the three inputs for a case; applied to any number of engines."""
+
+    def __init__(self, pp, e0kind, bandkind, profkind, seed):
+        rng = np.random.default_rng(seed)
+        self.e0 = draw_e0(pp, e0kind, rng) if e0kind else None
+        self.band = draw_band(pp, self.e0 if self.e0 is not None else np.zeros(pp.S), bandkind, rng) if bandkind else None
+        self.prof = draw_profiles(pp, profkind, rng) if profkind else None
+
+    @property
+    def flags(self):
+        return ((_capi.F_STO_INITIAL_LEVEL if self.e0 is not None else 0) | (_capi.F_STO_TERMINAL_LEVEL if self.band is not None else 0)
+                | (_capi.F_GEN_AVAILABILITY if self.prof is not None else 0))
+
+    def apply(self, e):
+        if self.band is not None:
+            e.set_terminal_levels()             # the default band first: the new e0 is then checked against it, not the old band
+        if self.e0 is not None:
+            e.set_initial_levels(self.e0)
+        if self.band is not None:
+            e.set_terminal_levels(*self.band)
+        if self.prof is not None:
+            e.set_availability(*self.prof)

@@ -24,6 +24,7 @@ SLICES = [
     ("fuzz_quiet", 45, 415, {}, "the quiet network chain (no k_slack launch) bit for bit against the chain it replaces"),
     ("fuzz_net_wide", 10, 416, {}, "wide networks: 12-300 nodes, up to 400 lines, 24-192 steps"),
     ("fuzz_oracle", 40, 417, {"ORACLE_MODE": "0"}, "HIP vs the LITERAL mode of the oracle (term-by-term QP, interior point)"),
+    ("fuzz_levels", 80, 419, {}, "initial levels, terminal bands and availability profiles on every chain vs the oracle"),
 ]
 
 

@@ -9,7 +9,7 @@ import pytest
 import decentralopf_jl_amd as pkg
 from decentralopf_jl_amd import _capi, synth
 from decentralopf_jl_amd.central import solve_central_packed
-from helpers import make_engine, max_diff, state_of
+from helpers import make_engine, max_diff, state_of, storage_kkt_violation_band
 
 pytestmark = pytest.mark.gpu
 
@@ -24,48 +24,6 @@ def bitwise_equal(a, b):
 def set_from(e, st, iteration):
     e.set_state(P=st["P"], D=st["D"], C_=st["C"], avg_U=st["avg_U"], avg_K=st["avg_K"], lam=st["lam"], mu=st["mu"],
                 rho=st["rho"], iteration=iteration)
-
-
-def storage_kkt_violation_band(pp, D0, C0, D, C, E, theta, gamma, lo_end, hi_end, w=1.0, tol=1e-7):
-    """helpers.storage_kkt_violation with the terminal band: the level after the last timestep lies in [lo_end, hi_end] instead
-    of [0, emax]. The price past the horizon is 0, so the last segment's price is 0 with E_{T-1} strictly inside the band, >= 0 at
-    lo_end, <= 0 at hi_end and free with lo_end == hi_end. Returns the largest amount by which an interval of feasible prices is
-    empty (0 = optimal within tol)."""
-    mc = pp.sto_mc[:, None]
-    pm = pp.sto_pmax[:, None]
-    em = pp.sto_emax
-    q = D - C
-    gD = mc + theta + gamma * q + w * (D - D0)
-    gC = mc - theta - gamma * q + w * (C - C0)
-    inf = np.inf
-    lo = np.where(D <= tol, -gD, np.where(D >= pm - tol, -inf, -gD))
-    hi = np.where(D <= tol, inf, np.where(D >= pm - tol, -gD, -gD))
-    lo = np.maximum(lo, np.where(C <= tol, -inf, np.where(C >= pm - tol, gC, gC)))
-    hi = np.minimum(hi, np.where(C <= tol, gC, np.where(C >= pm - tol, inf, gC)))
-    degenerate = pm <= tol
-    lo = np.where(degenerate, -inf, lo)
-    hi = np.where(degenerate, inf, hi)
-    T = D.shape[1]
-    flo = np.zeros(D.shape[0])
-    fhi = np.zeros(D.shape[0])
-    worst = 0.0
-    for t in range(T - 1, -1, -1):
-        blo, bhi = (lo_end, hi_end) if t == T - 1 else (np.zeros_like(em), em)
-        at_hi = E[:, t] >= bhi - tol
-        at_lo = E[:, t] <= blo + tol
-        both = at_hi & at_lo          # a band of one point: any jump allowed
-        nlo = np.where(both, -inf, np.where(at_hi, -inf, flo))      # E on its upper bound: nu_t <= nu_{t+1}
-        nhi = np.where(both, inf, np.where(at_lo, inf, fhi))        # E on its lower bound: nu_t >= nu_{t+1}
-        nlo = np.where(at_lo & ~both, flo, nlo)
-        nhi = np.where(at_hi & ~both, fhi, nhi)
-        flo = np.maximum(nlo, lo[:, t])
-        fhi = np.minimum(nhi, hi[:, t])
-        worst = max(worst, float(np.max(flo - fhi)))
-        mid = 0.5 * (flo + fhi)
-        bad = flo > fhi
-        flo = np.where(bad, mid, flo)
-        fhi = np.where(bad, mid, fhi)
-    return max(worst, 0.0)
 
 
 def reachable(pp, e0):

@@ -74,18 +74,57 @@ SYNTH = [
 ]
 
 
-@pytest.mark.parametrize("name,case,params,iters,tol", SYNTH, ids=[s[0] for s in SYNTH])
-def test_exact_mode_equals_literal_qp(oracle_api, name, case, params, iters, tol):
-    """Slack elimination + price-threshold recursion (mode 1) against the literally assembled QPs."""
+# Copper plates beyond T = 12: 8 storages with the storage shapes of scripts/fuzz_lean.py (emax = pmax x {0.7, 1, 2, 3.3, 5},
+# pmax x U(0.6, 1.4)), plain and with the three problem extensions (features: e0, band, profiles of helpers.Features). Tolerances
+# from a measurement over 4 steps (worst difference of the arrays, the cost excluded: it is a sum over all agents, compared
+# relatively): plain 1.3e-10 / 1.7e-8 / 2.1e-8, with the features 3.0e-9 / 3.5e-8 / 1.3e-7 at T = 24 / 96 / 168. Where it exceeds
+# 1e-9 a storage sits on a degenerate vertex, where the interior-point QP stops short of it (tests/test_oracle_features.py).
+LONG = [
+    ("copper-T24-shapes", dict(n_gen=12, n_sto=8, T=24, seed=84, shapes=True), dict(gamma=0.05), 4, 1e-9, None),
+    ("copper-T96-shapes", dict(n_gen=12, n_sto=8, T=96, seed=156, shapes=True), dict(gamma=0.05), 4, 1e-7, None),
+    ("copper-T168-shapes", dict(n_gen=12, n_sto=8, T=168, seed=228, shapes=True), dict(gamma=0.05), 4, 1e-7, None),
+    ("copper-T24-shapes-features", dict(n_gen=12, n_sto=8, T=24, seed=84, shapes=True), dict(gamma=0.05), 4, 2e-8, ("mix", "mix", "K3")),
+    ("copper-T96-shapes-features", dict(n_gen=12, n_sto=8, T=96, seed=156, shapes=True), dict(gamma=0.05), 4, 2e-7, ("mix", "mix", "K3")),
+    ("copper-T168-shapes-features", dict(n_gen=12, n_sto=8, T=168, seed=228, shapes=True), dict(gamma=0.05), 4, 1e-6, ("mix", "mix", "K3")),
+]
+
+
+def _lean_shapes(case):
+    case = dict(case)
+    shapes = case.pop("shapes", False)
     pp = synth.synthetic_case(**case)
-    a = make_engine(oracle_api, pp, mode=0, eps=0.0, **params)
-    b = make_engine(oracle_api, pp, mode=1, eps=0.0, **params)
+    if shapes:
+        rng = np.random.default_rng(case["seed"])
+        pp.sto_emax = pp.sto_pmax * rng.choice([0.7, 1.0, 2.0, 3.3, 5.0], size=pp.S)
+        pp.sto_pmax = pp.sto_pmax * rng.uniform(0.6, 1.4, size=pp.S)
+    return pp
+
+
+@pytest.mark.parametrize("name,case,params,iters,tol,features", [r + (None,) for r in SYNTH] + LONG,
+                         ids=[s[0] for s in SYNTH + LONG])
+def test_exact_mode_equals_literal_qp(oracle_api, name, case, params, iters, tol, features):
+    """Slack elimination + price-threshold recursion (mode 1) against the literally assembled QPs."""
+    pp = _lean_shapes(case)
+    if features is None:
+        a = make_engine(oracle_api, pp, mode=0, eps=0.0, **params)
+        b = make_engine(oracle_api, pp, mode=1, eps=0.0, **params)
+    else:
+        from oracle.binding import OracleApi
+        from helpers import Features, engine
+        api = OracleApi(oracle_api.path, features=True)
+        f = Features(pp, *features, seed=case["seed"])
+        a, b = engine(api, pp, 0, flags=f.flags, eps=0.0, **params), engine(api, pp, 1, flags=f.flags, eps=0.0, **params)
+        f.apply(a)
+        f.apply(b)
+    if pp.T > 12:
+        from oracle.binding import set_threads
+        set_threads(a, 4)
     for k in range(iters):
         a.iterate(1)
         # one-step comparison: start b from a's previous state so that differences do not compound
         b.iterate(1)
         sa, sb = state_of(a), state_of(b)
-        worst, where = max_diff(sa, sb)
+        worst, where = max_diff(sa, sb, keys=None if name in dict((r[0], 0) for r in SYNTH) else [x for x in sa if x != "cost"])
         assert worst < tol, (k, where, worst)
         b.set_state(P=sa["P"], D=sa["D"], C_=sa["C"], avg_U=sa["avg_U"], avg_K=sa["avg_K"], lam=sa["lam"],
                     mu=sa["mu"], rho=sa["rho"], iteration=a.get_residuals()[3])
