@@ -159,13 +159,21 @@ def central_reference(nodes: Sequence[Node], generators: Sequence[Generator], st
 
 
 def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
-                                lines: Sequence[Line], *, tol: float = 1e-9, max_iters: int = 200000, device: int = -1) -> CentralResult:
-    """The same LP solved on the GPU by libdopf_hip (dopf_central_solve: first-order primal-dual method, csrc/kernels_central.hip)
-    — for cases beyond a host LP solver, and as a cross-check that shares no code with HiGHS."""
+                                lines: Sequence[Line], *, tol: float = 1e-9, max_iters: int = 200000, device: int = -1,
+                                initial_level=None, terminal_level=None) -> CentralResult:
+    """The same LP solved on the GPU by libdopf_hip (dopf_central_solve / dopf_central_solve_ex: first-order primal-dual method,
+    csrc/kernels_central.hip) — for cases beyond a host LP solver, and as a cross-check that shares no code with HiGHS. The
+    elements' initial levels, terminal bands and availability series are part of the LP, as in central_reference;
+    initial_level / terminal_level override the storages' own, as there."""
     from . import _capi
     pp = pack(nodes, generators, storages, lines)
-    r = _capi.central_solve(_capi.hip_api(), tol=tol, max_iters=max_iters, params=_capi.default_params(device=device),
-                            **pp.engine_kwargs())
+    kw = pp.engine_kwargs()
+    if initial_level is not None:
+        kw["sto_e0"] = np.asarray(initial_level, dtype=np.float64).reshape(pp.S)
+    if terminal_level is not None:
+        kw["sto_end_lo"] = np.asarray(terminal_level[0], dtype=np.float64).reshape(pp.S)
+        kw["sto_end_hi"] = np.asarray(terminal_level[1], dtype=np.float64).reshape(pp.S)
+    r = _capi.central_solve(_capi.hip_api(), tol=tol, max_iters=max_iters, params=_capi.default_params(device=device), **kw)
     if not r["converged"]:
         raise RuntimeError(f"central LP on the device: gap {r['gap']:.2e} after {r['iterations']} iterations (infeasible case?)")
     inj = -np.asarray(pp.demand, dtype=np.float64).copy()

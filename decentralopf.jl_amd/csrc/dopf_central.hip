@@ -4,6 +4,10 @@
 // primal-dual iteration of kernels_central.hip in batches, looks at the primal / dual objectives and the worst constraint
 // violation of the last iterate and of the running average between batches, restarts from the better one when its
 // normalised gap has halved, stops at the requested tolerance.
+//
+// dopf_central_solve_ex: the LP with initial levels, terminal bands and availability profiles. Only boxes and right-hand sides change,
+// so the step sizes, the averaging and the restarts below are untouched. The inputs go through the ADMM path's own setters on the
+// temporary context (their checks, their codes, their device arrays); Plan::genAvail / stoLV then select the sweeps' instantiations.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -41,17 +45,46 @@ extern "C" int dopf_central_solve(const dopf_problem *p, const dopf_params *q, d
                                   double *system_price, double *nodal_price, double *line_utilization,
                                   double *flow_upper_dual, double *flow_lower_dual)
 {
+    return dopf_central_solve_ex(p, q, nullptr, nullptr, nullptr, 0, nullptr, nullptr, tol, max_iters, res, P, D, C, E,
+                                 system_price, nodal_price, line_utilization, flow_upper_dual, flow_lower_dual);
+}
+
+extern "C" int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q, const double *sto_e0_in,
+                                     const double *sto_end_lo_in, const double *sto_end_hi_in,
+                                     int32_t n_profiles, const double *profiles, const int32_t *profile_of,
+                                     double tol, int32_t max_iters,
+                                     dopf_central_result *res, double *P, double *D, double *C, double *E,
+                                     double *system_price, double *nodal_price, double *line_utilization,
+                                     double *flow_upper_dual, double *flow_lower_dual)
+{
     if (!p || !q || !res || !(tol > 0) || max_iters < 1) return fail(nullptr, DOPF_E_INVALID, "bad argument");
     memset(res, 0, sizeof *res);
     dopf_ctx *c = nullptr;
     dopf_params qq = *q;
     qq.stream = nullptr;
     qq.flags &= ~(DOPF_F_OVERLAP_AGENTS);
+    // every input that is given sets its flag (the caller's own flags stay: a flag without its input is that feature's default)
+    const bool has_e0 = sto_e0_in != nullptr, has_band = sto_end_lo_in || sto_end_hi_in;
+    const bool has_avail = n_profiles != 0 || profiles || profile_of;
+    if (has_e0) qq.flags |= DOPF_F_STO_INITIAL_LEVEL;
+    if (has_band) qq.flags |= DOPF_F_STO_TERMINAL_LEVEL;
+    if (has_avail) qq.flags |= DOPF_F_GEN_AVAILABILITY;
     int rc = dopf_create(&c, p, &qq);       // sorted agents, items, node maps, partial-sum arrays, P/D/C/E (zero)
     if (rc) return rc;
     // (callers read dopf_last_error(NULL): the temporary context's message has to outlive it)
     struct Guard { dopf_ctx *c; ~Guard() { keep_error(c); dopf_destroy(c); } } guard{c};
     DeviceGuard dev(c->device);
+    {   // e0 first (the band's reachability is checked from it), then the band, then the profiles; a refusal is the setter's
+        // code, and its message names this entry
+        rc = DOPF_OK;
+        if (has_e0) rc = dopf_set_storage_initial_level(c, sto_e0_in);
+        if (!rc && has_band) rc = dopf_set_storage_terminal_level(c, sto_end_lo_in, sto_end_hi_in);
+        if (!rc && has_avail) rc = dopf_set_generator_availability(c, n_profiles, profiles, profile_of);
+        if (rc) {
+            const std::string why = c->err;
+            return fail(c, rc, "dopf_central_solve_ex: %s", why.c_str());
+        }
+    }
     const DevView &v = c->v;
     const int N = v.N, L = v.L, T = v.T, G = v.G, S = v.S;
     const size_t NT = (size_t)N * T, LT = (size_t)L * T, GT = (size_t)G * T, ST = (size_t)S * T;
@@ -98,7 +131,7 @@ extern "C" int dopf_central_solve(const dopf_problem *p, const dopf_params *q, d
     for (size_t i = 0; i < NT; ++i) dmax = std::max(dmax, std::fabs(p->demand[i]));
     auto metrics = [&](const double *XP, const double *XD, const double *XC, const double *XE, const double *yb, const double *yf,
                        double scale, Metrics &m) -> int {
-        central_launch_metrics(cv, vred, XP, XD, XC, XE, yb, yf, scale, c->main);
+        central_launch_metrics(cv, c->plan, vred, XP, XD, XC, XE, yb, yf, scale, c->main);
         double cost = 0.0;
         HIPCHK(c, hipMemcpyAsync(&cost, v.cons + NT, sizeof(double), hipMemcpyDeviceToHost, c->main));
         if (!mg.empty()) HIPCHK(c, hipMemcpyAsync(mg.data(), cv.m_gen, mg.size() * sizeof(double), hipMemcpyDeviceToHost, c->main));
@@ -121,7 +154,7 @@ extern "C" int dopf_central_solve(const dopf_problem *p, const dopf_params *q, d
     bool use_avg = false, done = false;
     while (it < max_iters && !done) {
         const int nb = std::min(batch, max_iters - it);
-        for (int k = 0; k < nb; ++k) central_launch_iteration(cv, vred, c->main);
+        for (int k = 0; k < nb; ++k) central_launch_iteration(cv, c->plan, vred, c->main);
         HIPCHK(c, hipGetLastError());
         it += nb; navg += nb;
         if ((rc = metrics(v.P, v.D, v.C, cv.yE, cv.yb, cv.yf, 1.0, mc))) return rc;

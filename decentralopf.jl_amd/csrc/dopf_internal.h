@@ -183,6 +183,21 @@ __host__ __device__ inline const double **gen_avail_slot(const DevView &v)
 }
 inline size_t gen_state_ints(int G, bool avail) { return avail ? ((2 * (size_t)G + 1) & ~(size_t)1) + 2 : (size_t)G; }
 
+// DOPF_F_GEN_AVAILABILITY (the AV instantiations of the generator bodies, kernels_agents.hip and kernels_central.hip): the row's upper bound at a timestep, cap = pmax * f with f
+// the row's profile value — one fp64 multiply, never contracted into the sums that add it (a kept row adds cap itself, and the full
+// sweep adds the clamped value: both must be the same bits). prof < 0: pmax, no shape is read.
+__device__ __forceinline__ double avail_mul(double pm, double f)
+{
+#pragma clang fp contract(off)
+    return pm * f;
+}
+
+// (f: the profile table, *gen_avail_slot(v), loaded once per block)
+__device__ __forceinline__ double avail_cap(const double *f, int T, int prof, double pm, int t)
+{
+    return prof >= 0 ? avail_mul(pm, f[(size_t)prof * T + t]) : pm;
+}
+
 #ifndef DOPF_ACC_REP
 #define DOPF_ACC_REP 16
 #endif
@@ -274,8 +289,9 @@ struct CentralView {
 };
 
 // kernels_central.hip
-void central_launch_iteration(const CentralView &c, const DevView &vreduce, hipStream_t s);
-void central_launch_metrics(const CentralView &c, const DevView &vreduce, const double *XP, const double *XD, const double *XC,
+// (p: the context's plan — genAvail and stoLV select the sweeps' feature instantiations)
+void central_launch_iteration(const CentralView &c, const Plan &p, const DevView &vreduce, hipStream_t s);
+void central_launch_metrics(const CentralView &c, const Plan &p, const DevView &vreduce, const double *XP, const double *XD, const double *XC,
                             const double *XE, const double *yb, const double *yf, double scale, hipStream_t s);
 void central_launch_scale_copy(double *dst, const double *src, double scale, size_t n, hipStream_t s);
 

@@ -36,20 +36,7 @@ __device__ __forceinline__ double clampd(double v, double lo, double hi)
     return fmin(fmax(v, lo), hi);
 }
 
-// DOPF_F_GEN_AVAILABILITY (the AV instantiations of the generator bodies): the row's upper bound at a timestep, cap = pmax * f with f
-// the row's profile value — one fp64 multiply, never contracted into the sums that add it (a kept row adds cap itself, and the full
-// sweep adds the clamped value: both must be the same bits). prof < 0: pmax, no shape is read.
-__device__ __forceinline__ double avail_mul(double pm, double f)
-{
-#pragma clang fp contract(off)
-    return pm * f;
-}
-
-// (f: the profile table, *gen_avail_slot(v), loaded once per block)
-__device__ __forceinline__ double avail_cap(const double *f, int T, int prof, double pm, int t)
-{
-    return prof >= 0 ? avail_mul(pm, f[(size_t)prof * T + t]) : pm;
-}
+// (avail_mul, avail_cap: dopf_internal.h — the central reference's generator sweep forms the same product)
 
 // the pair columns 2 tt, 2 tt + 1 of the row (T even: [t + T*k] is 16-byte aligned)
 __device__ __forceinline__ double2 avail_cap2(const double *tab, int prof, double pm, size_t half, int tt)

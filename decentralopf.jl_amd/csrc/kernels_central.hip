@@ -15,6 +15,10 @@
 //               of (last iterate, average) whenever its normalised gap has halved (the scheme of PDLP, without its line
 //               search). Prototype and convergence record: scripts/proto_pdlp.py (machine precision in 4k-12k iterations on
 //               config1, config2/10 and a 118-node case).
+//   inputs      dopf_central_solve_ex (DOPF_F_STO_INITIAL_LEVEL, _TERMINAL_LEVEL, DOPF_F_GEN_AVAILABILITY): boxes and right-hand sides only,
+//               K stays — box 0 <= P[g,t] <= cap[g,t] = gen_pmax[g] * f[prof[g]][t] (kc_gen<., AV>); level rows
+//               lb_t - e0 <= sum_{tau <= t} (C - D) <= ub_t - e0 with [lb_t, ub_t] = [0, e_max], [lo, hi] at t = T-1 (kc_sto<., LV>).
+//               Read from the arrays the ADMM kernels read: gen_prof(v), gen_avail_slot(v), sto_e0(v), sto_end_lo/hi(v).
 //   outputs     objective, P, D, C, E; system price = -yb (dual(EB) of the reference), nodal price = -(yb + ptdf' yf)
 //               (src/opf_central_reference.jl:66-79).
 #include "dopf_internal.h"
@@ -57,7 +61,9 @@ __global__ __launch_bounds__(256) void kc_price(CentralView c, const double *yb,
 
 // generators. ITER: one PDHG step of every (g,t) of the item; per-item sums of the extrapolated point 2x+ - x.
 // !ITER: metrics of the candidate scale * X: per-item sums of x, cost, and sum min(reduced cost, 0) * pmax.
-template <bool ITER>
+// AV (DOPF_F_GEN_AVAILABILITY contexts): the box's upper end is cap[g,t] = avail_cap(...), the ADMM kernels' product, in the clamp
+// and in the reduced-cost term; the row's index is read with mc / pmax, its shape through L2.
+template <bool ITER, bool AV = false>
 __global__ __launch_bounds__(512) void kc_gen(CentralView c, const double *X, double scale)
 {
     __shared__ double red[512];
@@ -67,6 +73,9 @@ __global__ __launch_bounds__(512) void kc_gen(CentralView c, const double *X, do
     const int tid = threadIdx.x, r = tid / TT, tt = tid - r * TT;
     const double tau = c.tauN[it.node] / c.w;
     double cost = 0.0, dpart = 0.0;
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
     for (int tc = 0; tc < T; tc += TT) {
         const int t = tc + tt;
         double acc = 0.0;
@@ -74,7 +83,9 @@ __global__ __launch_bounds__(512) void kc_gen(CentralView c, const double *X, do
             const double pi = c.pi[it.node + (size_t)N * t];
             for (int g = it.a0 + r; g < it.a1; g += R) {
                 const size_t e = (size_t)g * T + t;
-                const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
+                const double mc = v.gen_mc[g];
+                double pm = v.gen_pmax[g];
+                if constexpr (AV) pm = avail_cap(ftab, T, prof[g], pm, t);
                 if (ITER) {
                     const double x0 = v.P[e];
                     const double xn = cclamp(x0 - tau * (mc + pi), 0.0, pm);
@@ -115,7 +126,13 @@ __global__ __launch_bounds__(512) void kc_gen(CentralView c, const double *X, do
 // ITER: D+, C+ from the gradient c -+ (pi - sum_{tau >= t} yE), levels of the extrapolated point by a prefix sum, the level
 // multipliers' proximal step, running sums. !ITER: metrics of the candidate (scale * XD, XC, XE): cost, reduced-cost term,
 // worst level violation, -sum max(yE, 0) e_max; the levels themselves are written to v.E.
-template <bool ITER>
+// LV (Plan::stoLV; 1: DOPF_F_STO_INITIAL_LEVEL, 2: DOPF_F_STO_TERMINAL_LEVEL, sto_e0(v) zeros without the first flag): the level
+// prefix sums start from e0 (so v.E holds levels that include it), and the row of timestep t lies in [lb_t, ub_t] = [0, e_max],
+// with LV 2 [lo, hi] at t = T-1 — that one slot, k = (T-1) % K of lane (T-1) / K. The multiplier's proximal step projects onto
+// [lb_t, ub_t] (the row cumsum(C - D) onto [lb_t - e0, ub_t - e0]: the same step, e0 moved to the other side), the violation is
+// measured against it, and the dual objective gets the interval's support function sum max(yE, 0) (ub_t - e0) + min(yE, 0) (lb_t - e0):
+// with lb_t - e0 != 0 both signs of the multiplier count.
+template <bool ITER, int LV = 0>
 __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, const double *XC, const double *XE, double scale)
 {
     constexpr int KMAX = 8;
@@ -133,6 +150,9 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
     const double absH = c.absHn[it.node];
     for (int s = it.a0 + wv; s < it.a1; s += 4) {           // (wave-uniform trip count per wave)
         const double mc = v.sto_mc[s], pm = v.sto_pmax[s], em = v.sto_emax[s];
+        double e0 = 0.0, elo = 0.0, ehi = em;                 // LV: the level before timestep 0, the band of the last one
+        if constexpr (LV >= 1) e0 = sto_e0(v)[s];
+        if constexpr (LV == 2) { elo = sto_end_lo(v)[s]; ehi = sto_end_hi(v)[s]; }
         double yE[KMAX], d0[KMAX], c0[KMAX];
         double ysum = 0.0;
 #pragma unroll
@@ -171,12 +191,19 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
                     net += c0[k] - d0[k];
                     cost += mc * (d0[k] + c0[k]);
                     dpart += (fmin(rD, 0.0) + fmin(rC, 0.0)) * pm;
-                    yterm += fmax(yE[k], 0.0) * em;
+                    if constexpr (LV == 0) yterm += fmax(yE[k], 0.0) * em;
+                    else {
+                        const bool last = LV == 2 && t == T - 1;
+                        // (two fused steps, the first the one of LV 0: with e0 = 0 and the default band the same bits)
+                        yterm = fma(fmax(yE[k], 0.0), (last ? ehi : em) - e0, yterm);
+                        yterm = fma(fmin(yE[k], 0.0), (last ? elo : 0.0) - e0, yterm);
+                    }
                 }
             }
         }
         const double inclE = wave_prefix(net, lane);
         double lev = inclE - net;                             // level before this lane's first step
+        if constexpr (LV >= 1) lev += e0;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             const int t = t0 + k;
@@ -186,14 +213,17 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
                     lev += (2.0 * cn[k] - c0[k]) - (2.0 * dn[k] - d0[k]);
                     const double sg = c.w / (2.0 * (double)(t + 1));
                     const double z = yE[k] + sg * lev;
-                    const double yn = z - sg * cclamp(z / sg, 0.0, em);
+                    double yn;
+                    if constexpr (LV == 2) { const bool last = t == T - 1; yn = z - sg * cclamp(z / sg, last ? elo : 0.0, last ? ehi : em); }
+                    else yn = z - sg * cclamp(z / sg, 0.0, em);
                     v.D[e] = dn[k]; v.C[e] = cn[k];
                     c.yE[e] = yn;
                     c.aD[e] += dn[k]; c.aC[e] += cn[k]; c.aE[e] += yn;
                 } else {
                     lev += c0[k] - d0[k];
                     v.E[e] = lev;
-                    viol = fmax(viol, fmax(-lev, lev - em));
+                    if constexpr (LV == 2) { const bool last = t == T - 1; viol = fmax(viol, fmax((last ? elo : 0.0) - lev, lev - (last ? ehi : em))); }
+                    else viol = fmax(viol, fmax(-lev, lev - em));
                 }
             }
         }
@@ -315,23 +345,41 @@ void central_launch_price(const CentralView &c, const double *yb, const double *
     hipLaunchKernelGGL(kc_price, dim3(c.v.T), dim3(256), (size_t)c.v.L * sizeof(double), s, c, yb, yf, scale);
 }
 
-void central_launch_iteration(const CentralView &c, const DevView &vreduce, hipStream_t s)
+// the generator / storage sweep of a context: the plan's feature instantiation (genAvail, stoLV), today's without the flags
+template <bool ITER>
+static void launch_gen(const CentralView &c, const Plan &p, const double *X, double scale, hipStream_t s)
+{
+    if (!c.v.nGenItems) return;
+    if (p.genAvail) hipLaunchKernelGGL((kc_gen<ITER, true>), dim3(c.v.nGenItems), dim3(512), 0, s, c, X, scale);
+    else hipLaunchKernelGGL((kc_gen<ITER>), dim3(c.v.nGenItems), dim3(512), 0, s, c, X, scale);
+}
+
+template <bool ITER>
+static void launch_sto(const CentralView &c, const Plan &p, const double *XD, const double *XC, const double *XE, double scale, hipStream_t s)
+{
+    if (!c.v.nStoItems) return;
+    if (p.stoLV == 2) hipLaunchKernelGGL((kc_sto<ITER, 2>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
+    else if (p.stoLV == 1) hipLaunchKernelGGL((kc_sto<ITER, 1>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
+    else hipLaunchKernelGGL((kc_sto<ITER>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
+}
+
+void central_launch_iteration(const CentralView &c, const Plan &p, const DevView &vreduce, hipStream_t s)
 {
     const DevView &v = c.v;
     central_launch_price(c, c.yb, c.yf, 1.0, s);
-    if (v.nGenItems) hipLaunchKernelGGL(kc_gen<true>, dim3(v.nGenItems), dim3(512), 0, s, c, (const double *)nullptr, 1.0);
-    if (v.nStoItems) hipLaunchKernelGGL(kc_sto<true>, dim3(v.nStoItems), dim3(256), 0, s, c, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 1.0);
+    launch_gen<true>(c, p, nullptr, 1.0, s);
+    launch_sto<true>(c, p, nullptr, nullptr, nullptr, 1.0, s);
     launch_reduce(vreduce, Plan{}, s);            // (nodal sums and cost: k_reduce, whatever chain the context runs)
     hipLaunchKernelGGL(kc_dual<true>, dim3(v.T), dim3(256), 2 * (size_t)v.N * sizeof(double), s, c, (const double *)nullptr, (const double *)nullptr, 1.0);
 }
 
-void central_launch_metrics(const CentralView &c, const DevView &vreduce, const double *XP, const double *XD, const double *XC, const double *XE,
+void central_launch_metrics(const CentralView &c, const Plan &p, const DevView &vreduce, const double *XP, const double *XD, const double *XC, const double *XE,
                             const double *yb, const double *yf, double scale, hipStream_t s)
 {
     const DevView &v = c.v;
     central_launch_price(c, yb, yf, scale, s);
-    if (v.nGenItems) hipLaunchKernelGGL(kc_gen<false>, dim3(v.nGenItems), dim3(512), 0, s, c, XP, scale);
-    if (v.nStoItems) hipLaunchKernelGGL(kc_sto<false>, dim3(v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
+    launch_gen<false>(c, p, XP, scale, s);
+    launch_sto<false>(c, p, XD, XC, XE, scale, s);
     launch_reduce(vreduce, Plan{}, s);            // (nodal sums and cost: k_reduce, whatever chain the context runs)
     hipLaunchKernelGGL(kc_dual<false>, dim3(v.T), dim3(256), 2 * (size_t)v.N * sizeof(double), s, c, yb, yf, scale);
 }

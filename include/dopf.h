@@ -332,6 +332,25 @@ int dopf_central_solve(const dopf_problem *p, const dopf_params *q, double tol, 
                        double *system_price, double *nodal_price, double *line_utilization,
                        double *flow_upper_dual, double *flow_lower_dual);
 
+/* The same LP with the inputs of DOPF_F_STO_INITIAL_LEVEL, DOPF_F_STO_TERMINAL_LEVEL and DOPF_F_GEN_AVAILABILITY: the parity target
+ * of a decentral run that uses them. sto_e0[S] (NULL = all 0): the level rows become e0 + sum_{tau<=t} (C - D) in [0, max_level];
+ * sto_end_lo[S], sto_end_hi[S] (both or neither; NULL = [0, max_level]): the row of the last timestep lies in [lo, hi] instead;
+ * profiles (T x n_profiles, [t + T*k]) and profile_of[G] (-1 = always gen_pmax): the box of P[g,t] is [0, gen_pmax[g] *
+ * profiles[t + T*profile_of[g]]]. All in the caller's agent order, like p. Meaning, checks and error codes are those of
+ * dopf_set_storage_initial_level, dopf_set_storage_terminal_level (incl. the band's reachability from e0) and
+ * dopf_set_generator_availability: the entry sets the matching flag for every input given and calls them on its own context; a
+ * refusal returns that setter's code, its message (dopf_last_error(NULL)) names this entry, and no output is written. The E output
+ * holds levels that include e0, as dopf_get_primal returns them. With every input NULL / 0 this is dopf_central_solve. */
+int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q,
+                          const double *sto_e0,
+                          const double *sto_end_lo, const double *sto_end_hi,
+                          int32_t n_profiles, const double *profiles,
+                          const int32_t *profile_of,
+                          double tol, int32_t max_iters, dopf_central_result *res,
+                          double *P, double *D, double *C, double *E,
+                          double *system_price, double *nodal_price, double *line_utilization,
+                          double *flow_upper_dual, double *flow_lower_dual);
+
 /* ---- consensus sum across GPUs inside the library (RCCL over xGMI, loaded at run time) -------------
  * Replaces nothing in the reference (it has no parallelism); what is distributed is the agent loop of
  * optimize_all_subproblems! (src/optimization/subproblems.jl:1-17) and the agent sums of Result(...)
