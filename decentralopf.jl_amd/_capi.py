@@ -143,6 +143,9 @@ class CApi:
         self._sig("get_residuals", C.c_int, [ctxp, c_double_p, c_double_p, c_double_p, c_int32_p])
         self._sig("get_nodal_price", C.c_int, [ctxp, C.c_int32, c_double_p])
         self._sig("set_state", C.c_int, [ctxp] + [c_double_p] * 8 + [C.c_int32])
+        # the receding-horizon entries: optional — a library of the same ABI may lack them (Engine.roll then goes the host route)
+        self._opt("set_demand", C.c_int, [ctxp, c_double_p])
+        self._opt("roll_horizon", C.c_int, [ctxp, C.c_int32, c_double_p])
         if prefix == "dopf_":
             self._sig("bind_consensus", C.c_int, [ctxp, C.c_void_p])
             self._sig("solver_failures", C.c_int64, [ctxp])
@@ -181,6 +184,10 @@ class CApi:
             self._sig("multi_set_storage_terminal_level", C.c_int, [ctxp, c_double_p, c_double_p])
             self._sig("set_generator_availability", C.c_int, [ctxp, C.c_int32, c_double_p, c_int32_p])
             self._sig("multi_set_generator_availability", C.c_int, [ctxp, C.c_int32, c_double_p, c_int32_p])
+
+    def _opt(self, name, restype, argtypes):
+        if hasattr(self.lib, self.prefix + name):
+            self._sig(name, restype, argtypes)
 
     def _sig(self, name, restype, argtypes):
         f = getattr(self.lib, self.prefix + name)
@@ -342,6 +349,10 @@ class Engine:
             ptr = v.ctypes.data_as(c_int32_p if v.dtype == np.int32 else c_double_p)
             setattr(prob, k, ptr)
         self.params = params if params is not None else default_params()
+        # what a window change needs of the problem: the arrays as handed to create, and the inputs of the setters as they stand
+        self._keep, self._mode = keep, mode
+        self._e0 = None if e0 is None else e0.copy()
+        self._band, self._avail = band, avail
         self._ctx = C.c_void_p()
         args = [C.byref(self._ctx), C.byref(prob), C.byref(self.params)]
         if api.has_mode:
@@ -434,6 +445,7 @@ class Engine:
             raise DopfError(f"{self.api.prefix}*: this API has no storage initial levels")
         arr = None if e0 is None else _f64(e0, self.S)
         self._chk(self.api.set_storage_initial_level(self._ctx, _dp(arr)))
+        self._e0 = None if arr is None else arr.copy()
 
     def set_terminal_levels(self, lo=None, hi=None):
         """dopf_set_storage_terminal_level: the band [lo, hi] of each storage's level after the last timestep (S values each;
@@ -443,6 +455,7 @@ class Engine:
         a = None if lo is None else _f64(lo, self.S)
         b = None if hi is None else _f64(hi, self.S)
         self._chk(self.api.set_storage_terminal_level(self._ctx, _dp(a), _dp(b)))
+        self._band = None if a is None and b is None else (a, b)
 
     def set_availability(self, profiles=None, profile_of=None):
         """dopf_set_generator_availability: K profiles (K x T, values in [0, 1]) and each generator's profile (G indices, -1 =
@@ -451,6 +464,67 @@ class Engine:
             raise DopfError(f"{self.api.prefix}*: this API has no generator availability")
         K, prof, of = _availability_arrays(profiles, profile_of, self.T, self.G)
         self._chk(self.api.set_generator_availability(self._ctx, K, _dp(prof), None if of is None else of.ctypes.data_as(c_int32_p)))
+        self._avail = None if prof is None and of is None else (None if prof is None else prof.reshape(K, self.T), of)
+
+    # -- a receding horizon --------------------------------------------------------------------
+    def demand(self) -> np.ndarray:
+        """The context's demand as it stands, (N, T)."""
+        return self._keep["demand"].reshape(self.T, self.N).T.copy()
+
+    def set_demand(self, demand):
+        """dopf_set_demand: the demand (N, T) replaced in place; P, D, C, the duals and the iteration counter stay, injection,
+        flows and prices are derived again, converged becomes False. A backend without the entry: DopfError."""
+        if not hasattr(self.api, "set_demand"):
+            raise DopfError(f"{self.api.prefix}*: this API has no set_demand")
+        arr = _f64(np.asarray(demand, dtype=np.float64).reshape(self.N, self.T).T, self.N * self.T)
+        self._chk(self.api.set_demand(self._ctx, _dp(arr)))
+        self._keep["demand"] = arr
+
+    def roll(self, k: int, demand_tail):
+        """dopf_roll_horizon: the window advances by k steps (1 <= k <= T - 1); demand_tail (N, k) is the demand of the k new
+        steps. The rule is horizon.shift_window's. A backend without the entry goes the host route: getters -> shift_window -> a
+        new context with the setters and set_state(iteration = 2), which replaces this engine's context; like the entry it refuses
+        storages in a context without F_STO_INITIAL_LEVEL (DopfError). The availability profiles are not moved: set the new
+        window's with set_availability."""
+        from .horizon import shift_window
+        k = int(k)
+        native = hasattr(self.api, "roll_horizon")
+        if not 1 <= k <= self.T - 1:
+            if native:
+                self._chk(self.api.roll_horizon(self._ctx, k, None))       # (the library's refusal and message)
+            raise ValueError(f"roll: k = {k} outside [1, T - 1 = {self.T - 1}]")
+        tail = np.asarray(demand_tail, dtype=np.float64).reshape(self.N, k)
+        if native:
+            # (the initial levels now live on the device only; the host route, which reads self._e0, is never taken with this API)
+            self._chk(self.api.roll_horizon(self._ctx, k, _dp(_f64(tail.T, self.N * k))))
+            self._keep["demand"] = _f64(np.concatenate([self.demand()[:, k:], tail], axis=1).T)
+            return
+        if self.S and not self.params.flags & F_STO_INITIAL_LEVEL:          # (the native entry's refusal, DOPF_E_UNSUPPORTED)
+            raise DopfError(f"roll: the storages' levels after {k} steps become the next window's initial levels, which need "
+                            "DOPF_F_STO_INITIAL_LEVEL at create")
+        P, D, Cc, E = self.get_primal()
+        lam, mu, rho = self.get_duals()
+        _, aU, aK, _, _ = self.get_consensus()
+        w = shift_window(k, tail, demand=self.demand(), P=P, D=D, C=Cc, E=E, lam=lam, mu=mu, rho=rho, avg_U=aU, avg_K=aK,
+                         sto_emax=self._keep["sto_emax"])
+        kw = dict(self._keep, demand=_f64(w["demand"].T))
+        if self.S:
+            kw["sto_e0"] = w["e0"]
+        if self._band is not None:
+            kw["sto_end_lo"], kw["sto_end_hi"] = self._band
+        if self._avail is not None:
+            kw["gen_avail"], kw["gen_avail_of"] = self._avail
+        new = Engine(self.api, N=self.N, L=self.L, T=self.T, params=self.params, mode=self._mode, **kw)
+        new.set_state(P=w["P"], D=w["D"], C_=w["C"], avg_U=w["avg_U"], avg_K=w["avg_K"], lam=w["lam"], mu=w["mu"], rho=w["rho"],
+                      iteration=2)
+        self._adopt(new)
+
+    def _adopt(self, new: "Engine"):
+        """This engine goes on as `new`: its own context is destroyed, new's context and host mirrors move here, and `new` is left
+        without a context (so that nothing is destroyed twice)."""
+        self.close()
+        self.__dict__.update(new.__dict__)
+        new._ctx = C.c_void_p()
 
     def warm_start_stats(self):
         """(storages the warm-start kernel solved, storages it left to the scan kernel) in the LAST iteration."""

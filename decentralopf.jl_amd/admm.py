@@ -159,6 +159,34 @@ class ADMM:
         flags=F_GEN_AVAILABILITY (set for you when a Generator has an availability series); takes effect at the next iteration."""
         self.engine.set_availability(profiles, profile_of)
 
+    # -- a receding horizon ----------------------------------------------------------------------
+    def _new_window(self, demand: np.ndarray) -> None:
+        """the host's mirrors of the demand follow the engine's, and the recorded history starts anew for the new window"""
+        for i, n in enumerate(self.nodes):
+            n.demand = [float(x) for x in demand[i]]
+        self.packed.demand = demand.copy()
+        self.total_demand = demand.sum(axis=0)
+        self.node_id_to_demand = {i + 1: list(n.demand) for i, n in enumerate(self.nodes)}
+        lam, mu, rho = self.engine.get_duals()
+        self.lambdas, self.mues, self.rhos = [lam], [mu], [rho]
+        self.results = []
+        self.convergence = Convergence()
+        self.iteration = self.engine.get_residuals()[3]
+
+    def set_demand(self, demand) -> None:
+        """A new demand (N, T) for the same window, in place (dopf_set_demand): the primal state, the duals and the iteration
+        counter stay, the run is no longer converged. Not in the reference, which builds a new ADMM(...) per window."""
+        self.engine.set_demand(demand)
+        self._new_window(self.engine.demand())
+
+    def roll(self, k: int, demand_tail) -> None:
+        """The window advances by k steps (dopf_roll_horizon; the rule is horizon.shift_window's): demand_tail (N, k) is the demand
+        of the k new steps, every storage starts from the level it had after step k, the state of the kept steps warm-starts
+        the new window and the iteration counter becomes 2. The availability profiles are not moved: set the new window's with
+        set_availability. Not in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62)."""
+        self.engine.roll(k, demand_tail)
+        self._new_window(self.engine.demand())
+
     # -- one iteration -------------------------------------------------------------------------
     def _fetch_result(self) -> Result:
         P, D, C, E = self.engine.get_primal()

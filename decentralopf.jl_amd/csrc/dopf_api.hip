@@ -1460,6 +1460,99 @@ int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const doubl
     return DOPF_OK;
 }
 
+// scratch of dopf_set_demand / dopf_roll_horizon, allocated at the first call (freed with the context's other arrays): the moved
+// per-timestep vectors (demand, 2 x lambda, 8 line vectors) | the caller's demand tail (up to N*(T-1)) | the new initial levels (S)
+static int roll_scratch(dopf_ctx *c, double **out)
+{
+    if (!c->roll_scratch) {
+        const size_t NT = (size_t)c->v.N * c->v.T, LT = (size_t)c->v.L * c->v.T;
+        int rc = dev_alloc(c, &c->roll_scratch, 2 * NT + 2 * (size_t)c->v.T + 8 * LT + (size_t)c->v.S, false);
+        if (rc) return rc;
+    }
+    *out = c->roll_scratch;
+    return DOPF_OK;
+}
+
+// the checks both entries share: a context of its own (no communicator), and n finite values behind p
+static int roll_checks(dopf_ctx *c, const char *entry, const char *what, const double *p, size_t n, int N, int t0)
+{
+    if (c->comm)
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: not on a context joined to a communicator or a peer exchange (the shards' node sums "
+                                           "would need an exchange)", entry);
+    if (!p) return fail(c, DOPF_E_INVALID, "%s: %s is NULL", entry, what);
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(p[i]))
+            return fail(c, DOPF_E_INVALID, "%s: %s[%zu] (node %zu, t = %zu) is %g", entry, what, i, i % (size_t)N, i / (size_t)N + (size_t)t0, p[i]);
+    return DOPF_OK;
+}
+
+int dopf_set_demand(dopf_ctx *c, const double *demand)
+{
+    if (!c) return DOPF_E_INVALID;
+    DevView &v = c->v;
+    const size_t NT = (size_t)v.N * v.T;
+    if (int rc = roll_checks(c, "dopf_set_demand", "demand", demand, NT, v.N, 0)) return rc;
+    DeviceGuard guard(c->device);
+    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again). The
+    // node sums are formed again from P, D and C (item by item, in parallel): every chain leaves its last sums in cons, but a
+    // buffer bound by the caller (dopf_bind_consensus) holds whatever the caller left in it; as dopf_set_state does — DESIGN.md 5l
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(v.demand), demand, NT * sizeof(double), hipMemcpyHostToDevice, c->main));
+    launch_roll_state(v, c->plan, 0, 0, c->main);
+    HIPCHK(c, hipGetLastError());
+    c->quiet = false;                      // (flags are formed anew from the new flows)
+    return read_status(c);
+}
+
+int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
+{
+    if (!c) return DOPF_E_INVALID;
+    DevView &v = c->v;
+    const int N = v.N, L = v.L, T = v.T, S = v.S;
+    if (c->comm) return roll_checks(c, "dopf_roll_horizon", "demand_tail", demand_tail, 0, N, 0);
+    if (k < 1 || k >= T) return fail(c, DOPF_E_INVALID, "dopf_roll_horizon: k = %d outside [1, T - 1 = %d]", k, T - 1);
+    if (int rc = roll_checks(c, "dopf_roll_horizon", "demand_tail", demand_tail, (size_t)N * k, N, T - k)) return rc;
+    if (S > 0 && !(c->q.flags & DOPF_F_STO_INITIAL_LEVEL))
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: the storages' levels after %d steps become the next window's initial levels, "
+                                           "which need DOPF_F_STO_INITIAL_LEVEL at dopf_create", k);
+    DeviceGuard guard(c->device);
+    const size_t NT = (size_t)N * T, LT = (size_t)L * T;
+    double *scr = nullptr;
+    if (int rc = roll_scratch(c, &scr)) return rc;
+    double *tail_d = scr + NT + 2 * (size_t)T + 8 * LT, *e0_d = tail_d + NT;
+    std::vector<double> e0s(S), e0c(S);
+    if (S > 0) {
+        // the new initial levels first, into scratch; checked as the setters check theirs before anything is overwritten
+        launch_roll_level(v, c->plan, k, !c->level_from_primal, e0_d, c->main);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(e0s.data(), e0_d, sizeof(double) * S, hipMemcpyDeviceToHost, c->main));
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        for (int i = 0; i < S; ++i) e0c[c->sto_perm[i]] = e0s[i];          // (check_initial_levels reads the caller's order)
+        if (int rc = check_initial_levels(c, e0c.data())) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(tail_d, demand_tail, sizeof(double) * N * k, hipMemcpyHostToDevice, c->main));
+    RollVecs rv{};
+    rv.scratch = scr;
+    size_t off = 0;
+    auto add = [&](double *p, int stride, const double *tail) {
+        if (stride > 0) { rv.a[rv.n++] = RollVec{p, tail, off, stride}; off += (size_t)stride * T; }
+    };
+    add(const_cast<double *>(v.demand), N, tail_d);
+    add(v.lam, 1, nullptr); add(v.lam_used, 1, nullptr);
+    for (double *p : {v.mu, v.mu_used, v.rho, v.rho_used, v.avgU, v.avgU_used, v.avgK, v.avgK_used}) add(p, L, nullptr);
+    launch_roll_vecs(rv, T, k, c->main);
+    if (S > 0) {
+        HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_e0(v)), e0_d, sizeof(double) * S, hipMemcpyDeviceToDevice, c->main));
+        HIPCHK(c, hipMemsetAsync(v.nu_valid, 0, sizeof(int) * S, c->main));   // stored prices no longer match the state
+    }
+    if (v.G > 0) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v.gen_state), 2, (size_t)v.G, c->main));   // nor do the row summaries of P
+    launch_roll_state(v, c->plan, k, 2, c->main);
+    HIPCHK(c, hipGetLastError());
+    c->quiet = false;                      // (flags are formed anew from the moved state)
+    c->level_from_primal = true;           // (a central solve's levels belonged to the old window)
+    if (S > 0) c->sto_e0_h = e0s;
+    return read_status(c);
+}
+
 int dopf_debug_stats(dopf_ctx *c, uint64_t *out3 /* 15 values */)
 {
     if (!c || !out3) return DOPF_E_INVALID;

@@ -30,6 +30,7 @@ struct dopf_ctx {
     std::vector<void *> allocs;
     void *own_cons = nullptr;
     double *getter_scratch = nullptr;      // 3 * N * T doubles, allocated at the first getter that needs them (freed with the context)
+    double *roll_scratch = nullptr;        // dopf_set_demand / dopf_roll_horizon: the moved vectors, the demand tail, the new initial levels
     std::vector<int> gen_perm, sto_perm;   // sorted position -> caller's index
     std::vector<double> sto_emax_h;        // DOPF_F_STO_INITIAL_LEVEL / _TERMINAL_LEVEL: the storages' max_level in sorted order (the setters' bounds)
     std::vector<double> sto_pmax_h;        // DOPF_F_STO_TERMINAL_LEVEL: max charge / discharge per step, sorted order (reachability)

@@ -328,6 +328,15 @@ void launch_dual(const DevView &v, const Plan &p, hipStream_t s, const XchgView 
 //      // consensus -> duals, residuals, prices, status
 void launch_derive(const DevView &v, const Plan &p, hipStream_t s, bool from_primal);
 void launch_derive_level(const DevView &v, const Plan &p, hipStream_t s);   // E = e0 + cumsum(C - D) into v.E (e0 = 0 without p.stoE0)
+// dopf_set_demand / dopf_roll_horizon (kernels_consensus.hip). A per-timestep vector [j + stride*t] that moves by k
+// timesteps through the scratch (at off); tail: what follows the kept part (stride*k values), null: the old last timestep
+struct RollVec { double *p; const double *tail; size_t off; int stride; };
+struct RollVecs { RollVec a[11]; double *scratch; int n; };
+void launch_roll_level(const DevView &v, const Plan &p, int k, bool from_E, double *out /* S, device */, hipStream_t s);   // clamped level after timestep k - 1
+void launch_roll_vecs(const RollVecs &rv, int T, int k, hipStream_t s);
+// P, D, C moved by k in place (k = 0: left alone), the node sums formed from the rows item by item, status (iteration <= 0: kept)
+// and the derived consensus state as dopf_set_state leaves them
+void launch_roll_state(const DevView &v, const Plan &p, int k, int iteration, hipStream_t s);
 void launch_penalty_sums(const DevView &v, double *out /* [3][N][T], device */, hipStream_t s);   // Result.penalty_term, per node
 void launch_node_results(const DevView &v, double *gen, double *dis, double *chg, hipStream_t s);   // [n + N*t] each, device pointers   // consensus -> inj/s/flow/price (no dual step)
 

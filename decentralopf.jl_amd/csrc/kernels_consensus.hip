@@ -1917,4 +1917,159 @@ void launch_derive(const DevView &v, const Plan &p, hipStream_t s, bool from_pri
     launch_consensus<false>(v, p, s, nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------
+// dopf_set_demand / dopf_roll_horizon: the window moves by k timesteps on the device
+// ------------------------------------------------------------------------------------------------
+// The level every storage has after timestep k - 1 — bit for bit k_derive_level's recursion, or (from_E: a central solve's own
+// levels are in v.E) what is stored there — clamped into [0, max_level]: the next window's initial levels. A NaN level (a diverged
+// state) stays NaN, as in horizon.shift_window, so that check_initial_levels refuses the roll (fmin / fmax alone would make it 0)
+__global__ __launch_bounds__(256) void k_roll_level(DevView v, const double *e0 /* S, or null: 0 */, int k, int from_E, double *out /* S */)
+{
+    const int T = v.T;
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= v.S) return;
+    double e;
+    if (from_E) {
+        e = v.E[(size_t)s * T + (k - 1)];
+    } else {
+        e = e0 ? e0[s] : 0.0;
+        for (int t = 0; t < k; ++t) e += v.C[(size_t)s * T + t] - v.D[(size_t)s * T + t];
+    }
+    out[s] = e != e ? e : fmin(fmax(e, 0.0), v.sto_emax[s]) + 0.0;
+}
+
+// One block per work item (the x-update's own items: rows [a0, a1) of one node), STO: a storage item (rows of D and C) instead of
+// a generator item (rows of P). Thread = (row lane r, column tt): W = min(T, 256) columns x R = 256 / W rows at a time.
+// k > 0: every row moves left by k IN PLACE — new[t] = old[t + k] for t < T - k, behind it old[T - 1] (P: persistence) or 0 (D, C).
+// The hazard of the in-place move: new[t] is old[t + k], so a column chunk [c, c + W) is written from [c + k, c + W + k). The
+// chunks are walked in ascending order, and a chunk of a row is read by all its threads BEFORE the block's barrier and written
+// behind it: every write lands below everything still to be read (reads of later chunks start at c + W + k), and old[T - 1], the
+// tail's source, is only ever overwritten with itself. k == 0 (dopf_set_demand): nothing moves, the rows are only summed.
+// Either way the item's column sums (P resp. D - C, rows in order, the R row lanes added in lane order: a fixed order) go to
+// part[item*T + t] — part_ginj / part_sinj, the rows the copper chains' x-updates write; k_roll_node_sums adds them per node.
+template <bool STO>
+__global__ __launch_bounds__(256) void k_roll_rows(DevView v, int k)
+{
+    __shared__ double red[256];
+    const int T = v.T, W = T < 256 ? T : 256, R = 256 / W;
+    const int tid = threadIdx.x, r = tid / W, tt = tid - r * W;
+    const Item it = (STO ? v.sto_items : v.gen_items)[blockIdx.x];
+    double *part = (STO ? v.part_sinj : v.part_ginj) + (size_t)blockIdx.x * T;
+    const int keep = T - k;
+    for (int c0 = 0; c0 < T; c0 += W) {
+        const int t = c0 + tt;
+        const bool col = r < R && t < T;
+        double sum = 0.0;
+        for (int a0 = it.a0; a0 < it.a1; a0 += R) {           // (uniform trip count: the barrier below is reached by all)
+            const int a = a0 + r;
+            const bool on = col && a < it.a1;
+            double x = 0.0, y = 0.0;
+            if (on) {
+                const size_t row = (size_t)a * T;
+                if (STO) {
+                    if (t < keep) { x = v.D[row + t + k]; y = v.C[row + t + k]; }
+                } else {
+                    x = v.P[row + (t < keep ? t + k : T - 1)];
+                }
+            }
+            if (k > 0) {
+                __syncthreads();
+                if (on) {
+                    const size_t row = (size_t)a * T;
+                    if (STO) { v.D[row + t] = x; v.C[row + t] = y; }
+                    else v.P[row + t] = x;
+                }
+            }
+            sum += STO ? x - y : x;
+        }
+        if (R > 1) {
+            __syncthreads();
+            red[tid] = sum;
+            __syncthreads();
+            if (r == 0 && t < T) {
+                double tot = 0.0;
+                for (int q = 0; q < R; ++q) tot += red[q * W + tt];
+                part[t] = tot;
+            }
+        } else if (col) {
+            part[t] = sum;
+        }
+    }
+}
+
+// cons[n + N*t] (and, with lines, prev_node: what the next iteration's node changes refer to) = the node's generator items' rows
+// of part_ginj, then its storage items' rows of part_sinj. Block = (node, 32 timesteps), 8 row lanes, fixed order — what
+// k_derive_cons forms agent by agent, from the items' sums.
+__global__ __launch_bounds__(256) void k_roll_node_sums(DevView v)
+{
+    __shared__ double red[256];
+    const int N = v.N, T = v.T, TC = (T + 31) / 32;
+    const int n = blockIdx.x / TC, t = (blockIdx.x % TC) * 32 + (threadIdx.x & 31), r = threadIdx.x >> 5;
+    double sum = 0.0;
+    if (t < T) {
+        for (int i = v.node_gitem_beg[n] + r; i < v.node_gitem_beg[n + 1]; i += 8) sum += v.part_ginj[(size_t)i * T + t];
+        for (int i = v.node_sitem_beg[n] + r; i < v.node_sitem_beg[n + 1]; i += 8) sum += v.part_sinj[(size_t)i * T + t];
+    }
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    if (r == 0 && t < T) {
+        double tot = 0.0;
+        for (int q = 0; q < 8; ++q) tot += red[q * 32 + threadIdx.x];
+        const size_t i = (size_t)n + (size_t)N * t;
+        v.cons[i] = tot;
+        if (v.L > 0) v.prev_node[i] = tot;
+    }
+}
+
+// The per-timestep vectors ([j + stride*t]: demand, the duals, avg_U / avg_K and what the last solve read of them) move through a
+// second buffer: k_roll_vecs<0> writes the moved vector into the scratch, k_roll_vecs<1> copies it back. Behind the kept part: the
+// caller's tail (demand) or the old last timestep (persistence).
+template <int BACK>
+__global__ __launch_bounds__(256) void k_roll_vecs(RollVecs rv, int T, int k)
+{
+    const RollVec a = rv.a[blockIdx.y];
+    const size_t n = (size_t)a.stride * T, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (BACK) { a.p[i] = rv.scratch[a.off + i]; return; }
+    const size_t keep = (size_t)a.stride * (T - k);
+    rv.scratch[a.off + i] = i < keep ? a.p[i + (size_t)a.stride * k] : a.tail ? a.tail[i - keep] : a.p[(size_t)a.stride * (T - 1) + i % a.stride];
+}
+
+// status as dopf_set_state leaves it: iteration (<= 0: kept), not converged, halt from max_iters, residual bits cleared
+__global__ void k_roll_status(DevView v, int iteration)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Status *st = v.st;
+    const int it = iteration > 0 ? iteration : st->iteration;
+    st->iteration = it;
+    st->converged = 0;
+    st->halt = (v.max_iters > 0 && it > v.max_iters) ? 1 : 0;
+    for (int i = 0; i < 3; ++i) { st->resbits[i] = 0ull; st->resbits2[0][i] = 0ull; st->resbits2[1][i] = 0ull; }
+}
+
+void launch_roll_level(const DevView &v, const Plan &p, int k, bool from_E, double *out, hipStream_t s)
+{
+    if (v.S > 0) hipLaunchKernelGGL(k_roll_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, p.stoE0 ? sto_e0(v) : nullptr, k, from_E ? 1 : 0, out);
+}
+
+void launch_roll_vecs(const RollVecs &rv, int T, int k, hipStream_t s)
+{
+    size_t most = 0;
+    for (int i = 0; i < rv.n; ++i) most = most > (size_t)rv.a[i].stride * T ? most : (size_t)rv.a[i].stride * T;
+    if (most == 0) return;
+    const dim3 grid((unsigned)((most + 255) / 256), (unsigned)rv.n);
+    hipLaunchKernelGGL(k_roll_vecs<0>, grid, dim3(256), 0, s, rv, T, k);
+    hipLaunchKernelGGL(k_roll_vecs<1>, grid, dim3(256), 0, s, rv, T, k);
+}
+
+// rows moved by k (0: not at all), node sums from them, then the consensus step's derived state (launch_derive without k_derive_cons)
+void launch_roll_state(const DevView &v, const Plan &p, int k, int iteration, hipStream_t s)
+{
+    if (v.nGenItems > 0) hipLaunchKernelGGL(k_roll_rows<false>, dim3(v.nGenItems), dim3(256), 0, s, v, k);
+    if (v.nStoItems > 0) hipLaunchKernelGGL(k_roll_rows<true>, dim3(v.nStoItems), dim3(256), 0, s, v, k);
+    hipLaunchKernelGGL(k_roll_node_sums, dim3(v.N * ((v.T + 31) / 32)), dim3(256), 0, s, v);
+    hipLaunchKernelGGL(k_roll_status, dim3(1), dim3(64), 0, s, v, iteration);
+    launch_derive(v, p, s, false);
+}
+
 }  // namespace dopf

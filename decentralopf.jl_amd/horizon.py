@@ -1,0 +1,63 @@
+"""Moving a window of the decentral OPF by k timesteps: the rule of dopf_roll_horizon (include/dopf.h) in NumPy.
+
+``shift_window`` is the specification in executable form: the library's device path is tested against it, and ``Engine.roll``
+uses it on a backend that has no dopf_roll_horizon of its own (getters -> shift_window -> a new context with the setters and
+dopf_set_state). Not in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62).
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import numpy as np
+
+
+def _mat(a, rows: int, T: int) -> np.ndarray:
+    return np.asarray(a, dtype=np.float64).reshape(rows, T)
+
+
+def _persist(a: np.ndarray, k: int) -> np.ndarray:
+    """new[:, t] = old[:, t + k] for t < T - k, behind it the old last column"""
+    T = a.shape[-1]
+    return np.concatenate([a[..., k:], np.repeat(a[..., T - 1:T], k, axis=-1)], axis=-1)
+
+
+def _zeros(a: np.ndarray, k: int) -> np.ndarray:
+    """new[:, t] = old[:, t + k] for t < T - k, behind it zeros"""
+    return np.concatenate([a[..., k:], np.zeros(a.shape[:-1] + (k,))], axis=-1)
+
+
+def shift_window(k: int, demand_tail, *, demand, P, D, C, E, lam, mu, rho, avg_U, avg_K, sto_emax,
+                 used: Optional[dict] = None) -> Dict[str, np.ndarray]:
+    """The state of the window that starts k steps later, 1 <= k <= T - 1. Matrices in Julia shape (rows, T): demand (N, T),
+    P (G, T), D / C / E (S, T), mu / rho / avg_U / avg_K (L, T); lam (T,); demand_tail (N, k); sto_emax (S,). E is what
+    get_primal returned for the old window (it includes that window's initial levels).
+
+    "Kept": the new value at t is the old one at t + k, for t < T - k. Behind it: demand = demand_tail; P = the old last column
+    (persistence; the next x-update clamps it to the cap); D = C = 0; the duals and avg_U / avg_K = their old last column.
+    e0[s] = min(max(E[s, k - 1], 0), max_level[s]): the level the old window reached where the new one starts.
+
+    Returns demand, P, D, C, lam, mu, rho, avg_U, avg_K, e0; with `used` (a dict with any of lam, mu, rho, avg_U, avg_K: what the
+    last solve read) also a dict `used`, moved like the duals."""
+    lam = np.asarray(lam, dtype=np.float64).reshape(-1)
+    T = lam.size
+    k = int(k)
+    if not 1 <= k <= T - 1:
+        raise ValueError(f"k = {k} outside [1, T - 1 = {T - 1}]")
+    em = np.asarray(sto_emax, dtype=np.float64).reshape(-1)
+    S = em.size
+    demand = np.asarray(demand, dtype=np.float64)
+    N = demand.size // T
+    tail = np.asarray(demand_tail, dtype=np.float64).reshape(N, k)
+    if not np.all(np.isfinite(tail)):
+        raise ValueError("demand_tail holds a NaN or Inf")
+    rows = lambda a: _mat(a, np.asarray(a).size // T, T)
+    out = dict(
+        demand=np.concatenate([_mat(demand, N, T)[:, k:], tail], axis=1),
+        P=_persist(rows(P), k), D=_zeros(rows(D), k), C=_zeros(rows(C), k),
+        lam=_persist(lam, k), mu=_persist(rows(mu), k), rho=_persist(rows(rho), k),
+        avg_U=_persist(rows(avg_U), k), avg_K=_persist(rows(avg_K), k),
+        e0=np.minimum(np.maximum(_mat(E, S, T)[:, k - 1], 0.0), em) + 0.0)
+    if used is not None:
+        out["used"] = {name: _persist(np.asarray(a, dtype=np.float64).reshape(-1) if name == "lam" else rows(a), k)
+                       for name, a in used.items()}
+    return out

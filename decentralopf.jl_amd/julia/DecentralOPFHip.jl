@@ -303,6 +303,54 @@ function set_availability!(admm::ADMM, profiles::Union{Nothing, Matrix{Float64}}
     return admm
 end
 
+# a new window: the recorded history starts anew from the duals the context holds now. (The nodes' own demand vectors stay as
+# they were built: the reference's Node.demand is a Vector{Int}, a forecast need not be.)
+function dopf_new_window!(admm::ADMM, total_demand::Vector{Float64})
+    admm.total_demand = total_demand
+    L, T = length(admm.L), length(admm.T)
+    lam = zeros(T); mu = zeros(L, T); rho = zeros(L, T)
+    dopf_check(ccall((:dopf_get_duals, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}), admm.ctx, lam, mu, rho), admm.ctx)
+    admm.lambdas = [lam]; admm.mues = [mu]; admm.rhos = [rho]
+    admm.results = []
+    admm.convergence = Convergence()
+    it = Ref{Cint}(0); conv = Ref{Cint}(0)
+    dopf_check(ccall((:dopf_sync, DOPF_LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}), admm.ctx, it, conv), admm.ctx)
+    admm.iteration = Int(it[])
+    return admm
+end
+
+"""
+    set_demand!(admm, demand)
+
+A new demand (`N x T`, row n = `admm.nodes[n]`) for the same window, replaced in place on the device: the primal state, the duals
+and the iteration counter stay, injection, flows and prices are derived again, and the run is no longer converged. The reference
+builds a new `ADMM(...)` per window (src/structures/admm.jl:23-62). One GPU only (`n_gpus == 1`).
+"""
+function set_demand!(admm::ADMM, demand::Matrix{Float64})
+    N, T = length(admm.N), length(admm.T)
+    size(demand) == (N, T) || error("set_demand!: expected a $N x $T demand, got $(size(demand))")
+    admm.multi == C_NULL || error("set_demand!: one GPU only (no dopf_multi_* wrapper)")
+    dopf_check(ccall((:dopf_set_demand, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, demand), admm.ctx)   # N x T column-major = [n + N*t]
+    return dopf_new_window!(admm, vec(sum(demand, dims=1)))
+end
+
+"""
+    roll_horizon!(admm, k, demand_tail)
+
+The window advances by `k` steps, `1 <= k <= T - 1`, on the device: the state of the kept steps moves to the front and
+warm-starts the new window, `demand_tail` (`N x k`) is the demand of the `k` new steps, every storage starts from the level it
+had after step `k` (storages need `flags = DOPF_F_STO_INITIAL_LEVEL`), the iteration counter becomes 2. The terminal band now
+applies to the new window's end; the availability profiles are not moved (`set_availability!`). The reference builds a new
+`ADMM(...)` per window (src/structures/admm.jl:23-62). One GPU only (`n_gpus == 1`).
+"""
+function roll_horizon!(admm::ADMM, k::Int, demand_tail::Matrix{Float64})
+    N, T = length(admm.N), length(admm.T)
+    size(demand_tail) == (N, k) || error("roll_horizon!: expected a $N x $k demand tail, got $(size(demand_tail))")
+    admm.multi == C_NULL || error("roll_horizon!: one GPU only (no dopf_multi_* wrapper)")
+    dopf_check(ccall((:dopf_roll_horizon, DOPF_LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}), admm.ctx, k, demand_tail), admm.ctx)
+    return dopf_new_window!(admm, vcat(admm.total_demand[k+1:end], vec(sum(demand_tail, dims=1))))
+end
+
 """The fields of the reference's Result (src/structures/results.jl:37-48) for the last solved iteration."""
 function dopf_result(admm::ADMM)
     N, L, T = length(admm.N), length(admm.L), length(admm.T)

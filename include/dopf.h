@@ -313,6 +313,31 @@ int dopf_set_storage_terminal_level(dopf_ctx *ctx, const double *lo, const doubl
  * array with n_profiles > 0. */
 int dopf_set_generator_availability(dopf_ctx *ctx, int32_t n_profiles, const double *profiles, const int32_t *profile_of);
 
+/* ---- a receding horizon: the window's demand and the window itself change in place -------------------------------
+ * Replace nothing in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62). Both need no flag, work
+ * on every single-GPU chain, keep the captured iteration graphs valid (they write the arrays the graphs read) and return after
+ * their work on the context's stream is done. Both are DOPF_E_UNSUPPORTED on a context joined to a communicator or a peer exchange
+ * (the shards' node sums would need an exchange); there are no dopf_multi_* wrappers.
+ *
+ * dopf_set_demand: the context's demand, N x T, [n + N*t], replaced in the same device array. P, D, C, the duals, avg_U / avg_K and
+ * the inputs of the setters above are unchanged; injection, imbalance, flows, prices and the consensus buffer are derived again
+ * from the agents' node sums (formed from P, D, C in parallel) and the new demand. converged becomes 0, halt is formed again from
+ * max_iters, the residual maxima are cleared as dopf_set_state clears them; the iteration counter is kept. DOPF_E_INVALID, with
+ * nothing stored, for a NULL pointer or a NaN / Inf entry (the message names it). */
+int dopf_set_demand(dopf_ctx *ctx, const double *demand /* N x T, [n + N*t] */);
+/* dopf_roll_horizon: the window advances by k steps, 1 <= k <= T - 1, on the device: the new value at t is the old one at t + k for
+ * t < T - k ("kept"); behind it ("tail"): demand = demand_tail, N x k, [n + N*j]; P = the old P[g, T-1] (persistence; the next
+ * x-update clamps it to the cap, as for dopf_set_state); D = C = 0; lambda, mu, rho, avg_U, avg_K (and what the last solve read of
+ * them) = their old values at T - 1. Each storage's initial level becomes min(max(E[s, k-1], 0), max_level[s]) with E what
+ * dopf_get_primal returns just before the call. The terminal band and the availability table stay as they are: the band now
+ * applies to the new window's end, and the caller sets the new window's profiles with dopf_set_generator_availability. Status:
+ * iteration = 2, converged = 0, halt from max_iters, residual maxima cleared; the warm-start summaries are reset. By definition the
+ * context is then in the state of a fresh context of the shifted problem after the same setters and dopf_set_state(shifted arrays,
+ * iteration = 2). The new initial levels are computed and checked first: a refusal leaves the context as it was.
+ * DOPF_E_INVALID for k < 1, k >= T, a NULL demand_tail, a NaN / Inf in it, or a stored terminal band that is unreachable from the
+ * new initial levels; DOPF_E_UNSUPPORTED with storages in a context without DOPF_F_STO_INITIAL_LEVEL. */
+int dopf_roll_horizon(dopf_ctx *ctx, int32_t k, const double *demand_tail /* N x k, [n + N*j] */);
+
 /* ---- the central reference on the device ---------------------------------------------------------------
  * Replaces src/opf_central_reference.jl:16-81 (one JuMP model of the whole multi-period DC-OPF, solved by Gurobi): the same
  * LP — variables P, D, C, E in their boxes, energy balance per timestep, |ptdf * injection| <= f_max, storage balance —
