@@ -83,6 +83,7 @@ F_DEBUG_WIDE_NET = 16777216
 F_STO_INITIAL_LEVEL = 33554432
 F_STO_TERMINAL_LEVEL = 67108864
 F_GEN_AVAILABILITY = 134217728
+F_STO_EFFICIENCY = 268435456
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -184,6 +185,9 @@ class CApi:
             self._sig("multi_set_storage_terminal_level", C.c_int, [ctxp, c_double_p, c_double_p])
             self._sig("set_generator_availability", C.c_int, [ctxp, C.c_int32, c_double_p, c_int32_p])
             self._sig("multi_set_generator_availability", C.c_int, [ctxp, C.c_int32, c_double_p, c_int32_p])
+        # storage efficiencies: optional — the oracle backend loads without them (Engine.set_efficiency then refuses)
+        self._opt("set_storage_efficiency", C.c_int, [ctxp, c_double_p, c_double_p])
+        self._opt("multi_set_storage_efficiency", C.c_int, [ctxp, c_double_p, c_double_p])
 
     def _opt(self, name, restype, argtypes):
         if hasattr(self.lib, self.prefix + name):
@@ -293,6 +297,23 @@ def _terminal_level_params(api: CApi, params: Optional[DopfParams], sto_end_lo, 
     return q, (lo, hi)
 
 
+def _efficiency_params(api: CApi, params: Optional[DopfParams], sto_eta, S: int):
+    """(params, (eta_c, eta_d)) for an engine built with sto_eta = (eta_c, eta_d): the params with F_STO_EFFICIENCY added (a copy),
+    both as float64 of length S — or (params, None) when there is nothing to set (sto_eta None, or all ones on an API without
+    efficiencies)."""
+    if sto_eta is None:
+        return params, None
+    ec, ed = _f64(sto_eta[0], S), _f64(sto_eta[1], S)
+    if not hasattr(api, "set_storage_efficiency"):
+        if np.any(ec != 1.0) or np.any(ed != 1.0):
+            raise DopfError(f"{api.prefix}*: this API has no storage efficiencies (a value other than 1; the reference's storages "
+                            "are lossless)")
+        return params, None
+    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
+    q.flags |= F_STO_EFFICIENCY
+    return q, (ec, ed)
+
+
 def _availability_arrays(profiles, profile_of, T: int, G: int):
     """(K, profiles as float64 [t + T*k], profile_of as int32 (G,)) from a (K, T) array (or None) and G indices (or None)."""
     if profiles is None and profile_of is None:
@@ -326,12 +347,16 @@ class Engine:
     dopf_set_storage_initial_level after create. sto_end_lo / sto_end_hi (optional, S values each): the band of the level
     after the last timestep — sets F_STO_TERMINAL_LEVEL and calls dopf_set_storage_terminal_level (after the initial levels).
     gen_avail (optional, K x T) / gen_avail_of (optional, G indices in [-1, K)): the generators' availability profiles — sets
-    F_GEN_AVAILABILITY and calls dopf_set_generator_availability."""
+    F_GEN_AVAILABILITY and calls dopf_set_generator_availability. sto_eta = (eta_c, eta_d) (optional, S values each): the storages'
+    charge and discharge efficiencies — sets F_STO_EFFICIENCY and calls dopf_set_storage_efficiency (before the levels: their
+    reachability checks then see the efficiencies)."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
-                 mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None):
+                 mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
+                 sto_eta=None):
         self.api = api
+        params, eta = _efficiency_params(api, params, sto_eta, _f64(sto_mc).size)
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
         params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
         params, avail = _availability_params(api, params, gen_avail, gen_avail_of, int(T), _f64(gen_mc).size)
@@ -353,6 +378,7 @@ class Engine:
         self._keep, self._mode = keep, mode
         self._e0 = None if e0 is None else e0.copy()
         self._band, self._avail = band, avail
+        self._eta = eta
         self._ctx = C.c_void_p()
         args = [C.byref(self._ctx), C.byref(prob), C.byref(self.params)]
         if api.has_mode:
@@ -361,6 +387,8 @@ class Engine:
         if rc != 0:
             msg = api.last_error(None)
             raise DopfError(f"{api.prefix}create failed ({rc}): {msg.decode() if msg else ''}")
+        if eta is not None:
+            self.set_efficiency(*eta)
         if e0 is not None:
             self.set_initial_levels(e0)
         if band is not None:
@@ -457,6 +485,17 @@ class Engine:
         self._chk(self.api.set_storage_terminal_level(self._ctx, _dp(a), _dp(b)))
         self._band = None if a is None and b is None else (a, b)
 
+    def set_efficiency(self, eta_c=None, eta_d=None):
+        """dopf_set_storage_efficiency: each storage's charge and discharge efficiency in (0, 1] (S values each; both None = all
+        1); needs F_STO_EFFICIENCY. The level then follows E_t = E_{t-1} + eta_c C_t - D_t / eta_d. Takes effect at the next
+        x-update. A backend without the entry: DopfError (unsupported)."""
+        if not hasattr(self.api, "set_storage_efficiency"):
+            raise DopfError(f"{self.api.prefix}*: this API has no storage efficiencies (unsupported)")
+        a = None if eta_c is None else _f64(eta_c, self.S)
+        b = None if eta_d is None else _f64(eta_d, self.S)
+        self._chk(self.api.set_storage_efficiency(self._ctx, _dp(a), _dp(b)))
+        self._eta = None if a is None and b is None else (a, b)
+
     def set_availability(self, profiles=None, profile_of=None):
         """dopf_set_generator_availability: K profiles (K x T, values in [0, 1]) and each generator's profile (G indices, -1 =
         max_generation); both None resets every generator to -1. Needs F_GEN_AVAILABILITY. Takes effect at the next x-update."""
@@ -514,6 +553,8 @@ class Engine:
             kw["sto_end_lo"], kw["sto_end_hi"] = self._band
         if self._avail is not None:
             kw["gen_avail"], kw["gen_avail_of"] = self._avail
+        if self._eta is not None:
+            kw["sto_eta"] = self._eta
         new = Engine(self.api, N=self.N, L=self.L, T=self.T, params=self.params, mode=self._mode, **kw)
         new.set_state(P=w["P"], D=w["D"], C_=w["C"], avg_U=w["avg_U"], avg_K=w["avg_K"], lam=w["lam"], mu=w["mu"], rho=w["rho"],
                       iteration=2)
@@ -673,8 +714,9 @@ class MultiEngine:
 
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
-                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None):
+                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None):
         self.api = api
+        params, eta = _efficiency_params(api, params, sto_eta, _f64(sto_mc).size)
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
         params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
         params, avail = _availability_params(api, params, gen_avail, gen_avail_of, int(T), _f64(gen_mc).size)
@@ -699,6 +741,9 @@ class MultiEngine:
             msg = api.multi_last_error(None)
             raise DopfError(f"dopf_multi_create failed ({rc}): {msg.decode() if msg else ''}")
         self.n = int(api.multi_size(self._m))
+        self._eta = None
+        if eta is not None:
+            self.set_efficiency(*eta)
         if e0 is not None:
             self.set_initial_levels(e0)
         if band is not None:
@@ -711,6 +756,15 @@ class MultiEngine:
         shard gets the whole table and its slice); both None resets every generator to -1."""
         K, prof, of = _availability_arrays(profiles, profile_of, self.T, self.G)
         self._chk(self.api.multi_set_generator_availability(self._m, K, _dp(prof), None if of is None else of.ctypes.data_as(c_int32_p)))
+
+    def set_efficiency(self, eta_c=None, eta_d=None):
+        """dopf_multi_set_storage_efficiency: all storages' efficiencies in the caller's order (both None = all 1)."""
+        if not hasattr(self.api, "multi_set_storage_efficiency"):
+            raise DopfError(f"{self.api.prefix}*: this API has no storage efficiencies (unsupported)")
+        a = None if eta_c is None else _f64(eta_c, self.S)
+        b = None if eta_d is None else _f64(eta_d, self.S)
+        self._chk(self.api.multi_set_storage_efficiency(self._m, _dp(a), _dp(b)))
+        self._eta = None if a is None and b is None else (a, b)
 
     def set_initial_levels(self, e0=None):
         """dopf_multi_set_storage_initial_level: all storages' initial levels in the caller's order (None = all 0)."""

@@ -152,6 +152,13 @@ class ADMM:
         than the default); takes effect at the next iteration."""
         self.engine.set_terminal_levels(lo, hi)
 
+    def set_efficiency(self, eta_c=None, eta_d=None) -> None:
+        """Each storage's charge and discharge efficiency in (0, 1] (S values each in the order of `storages`; both None = all 1):
+        the level follows E_t = E_{t-1} + eta_c C_t - D_t / eta_d. Not in the reference, whose storages are lossless
+        (src/optimization/subproblems.jl:150-156). Needs flags=F_STO_EFFICIENCY (set for you when a Storage has an efficiency
+        other than 1); takes effect at the next iteration."""
+        self.engine.set_efficiency(eta_c, eta_d)
+
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability: K profiles (K x T, values in [0, 1]) and each generator's profile (G indices in the order
         of `generators`, -1 = always max_generation); both None = every generator at max_generation. The box of P[g,t] becomes

@@ -11,7 +11,8 @@ same LP handed to HiGHS (the LP solver that ships with SciPy; no licence):
     FlowUpper     ptdf I + U = f_max,   FlowLower   K - ptdf I = f_max                           (:49-51)
     StorageBalance  E[s,t] = E[s,t-1] - D + C, E[s,0] = 0                                        (:53)
                   (here E[s,0] = initial_level[s] if given: DOPF_F_STO_INITIAL_LEVEL's target; 0 as in the reference by default;
-                  E[s,T] in [lo[s], hi[s]] if a terminal band is given: DOPF_F_STO_TERMINAL_LEVEL's; [0, max_level] by default)
+                  E[s,T] in [lo[s], hi[s]] if a terminal band is given: DOPF_F_STO_TERMINAL_LEVEL's; [0, max_level] by default;
+                  E[s,t] = E[s,t-1] - D / eta_d + eta_c C if efficiencies are given: DOPF_F_STO_EFFICIENCY's; lossless by default)
     outputs       objective, P, D, C, line utilisation ptdf I, system price lambda = dual(EB),
                   nodal price = lambda + sum_l (dual(FlowUpper) + dual(FlowLower))[l,t] ptdf[l,:]  (:57-81)
 
@@ -45,14 +46,25 @@ class CentralResult:
     nodal_price: np.ndarray         # (N, T)
 
 
+def _efficiencies(pp: PackedProblem, efficiency):
+    """(eta_c, eta_d) as float64 (S,): the argument, else the packed case's, else all 1."""
+    ec, ed = pp.efficiency() if efficiency is None else efficiency
+    ec, ed = np.asarray(ec, dtype=np.float64).reshape(pp.S), np.asarray(ed, dtype=np.float64).reshape(pp.S)
+    if np.any(~(ec > 0.0)) or np.any(ec > 1.0) or np.any(~(ed > 0.0)) or np.any(ed > 1.0):
+        raise ValueError("storage efficiencies must lie in (0, 1]")
+    return ec, ed
+
+
 def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None,
-                         availability=None) -> CentralResult:
+                         availability=None, efficiency=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
     tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
     side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference). terminal_level:
     (lo, hi), (S,) each, the bounds of the level after the last timestep E[:, T-1] (None: the packed case's band, else
     [0, max_level] as in the reference). availability: (profiles (K, T), profile_of (G,)), the upper bound of P[g,t] becomes
-    gen_pmax[g] * profiles[profile_of[g], t] (gen_pmax for -1; None: the packed case's profiles, else gen_pmax as in the reference)."""
+    gen_pmax[g] * profiles[profile_of[g], t] (gen_pmax for -1; None: the packed case's profiles, else gen_pmax as in the reference).
+    efficiency: (eta_c, eta_d), (S,) each in (0, 1]: the storage-balance rows read E[t] - E[t-1] + D / eta_d - eta_c C = 0 (None:
+    the packed case's efficiencies, else all 1 as in the reference)."""
     from scipy import sparse
     from scipy.optimize import linprog
     N, L, T, G, S = pp.N, pp.L, pp.T, pp.G, pp.S
@@ -89,8 +101,10 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
     rEB = r0                                                   # EB[t]: sum_n I[n,t] = 0
     rows.append(r0 + np.tile(tt, N)); cols.append(oI + np.arange(nI)); vals.append(np.ones(nI))
     beq.append(np.zeros(T)); r0 += T
-    k = np.arange(nS)                                          # E[t] - E[t-1] + D - C = 0   (t = 0: E[0] + D - C = e0)
-    rows += [r0 + k, r0 + k, r0 + k]; cols += [oE + k, oD + k, oC + k]; vals += [np.ones(nS), np.ones(nS), -np.ones(nS)]
+    k = np.arange(nS)                                          # E[t] - E[t-1] + al D - be C = 0   (t = 0: E[0] + al D - be C = e0)
+    eta_c, eta_d = _efficiencies(pp, efficiency)               # (al = 1 / eta_d, be = eta_c; all 1: the reference's rows, bit for bit)
+    rows += [r0 + k, r0 + k, r0 + k]; cols += [oE + k, oD + k, oC + k]
+    vals += [np.ones(nS), np.repeat(1.0 / eta_d, T), -np.repeat(eta_c, T)]
     k1 = k[(k % T) > 0]
     rows.append(r0 + k1); cols.append(oE + k1 - 1); vals.append(-np.ones(k1.size))
     if initial_level is None:
@@ -141,12 +155,13 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
 
 def central_reference(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
                       lines: Sequence[Line], *, verbose: bool = False, initial_level=None,
-                      terminal_level=None) -> CentralResult:
+                      terminal_level=None, efficiency=None) -> CentralResult:
     """src/opf_central_reference.jl for a case given as the reference's element vectors; `verbose` prints what the
     script prints (:60-81). initial_level: (S,) storage levels before the first timestep (None: Storage.initial_level).
-    terminal_level: (lo, hi) bounds of the level after the last timestep (None: Storage.terminal_level_min / _max)."""
+    terminal_level: (lo, hi) bounds of the level after the last timestep (None: Storage.terminal_level_min / _max).
+    efficiency: (eta_c, eta_d) (None: Storage.charge_efficiency / discharge_efficiency)."""
     r = solve_central_packed(pack(nodes, generators, storages, lines), initial_level=initial_level,
-                             terminal_level=terminal_level)
+                             terminal_level=terminal_level, efficiency=efficiency)
     if verbose:
         print(f"Objective value: {r.objective}\n")
         print(f"Generator results:\n{r.generation}\n")
@@ -160,14 +175,20 @@ def central_reference(nodes: Sequence[Node], generators: Sequence[Generator], st
 
 def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
                                 lines: Sequence[Line], *, tol: float = 1e-9, max_iters: int = 200000, device: int = -1,
-                                initial_level=None, terminal_level=None) -> CentralResult:
+                                initial_level=None, terminal_level=None, efficiency=None) -> CentralResult:
     """The same LP solved on the GPU by libdopf_hip (dopf_central_solve / dopf_central_solve_ex: first-order primal-dual method,
     csrc/kernels_central.hip) — for cases beyond a host LP solver, and as a cross-check that shares no code with HiGHS. The
     elements' initial levels, terminal bands and availability series are part of the LP, as in central_reference;
-    initial_level / terminal_level override the storages' own, as there."""
+    initial_level / terminal_level override the storages' own, as there. The device LP is lossless: efficiencies other than 1
+    (the argument's, or the storages' own) raise ValueError — use central_reference (HiGHS) for those."""
     from . import _capi
     pp = pack(nodes, generators, storages, lines)
+    ec, ed = _efficiencies(pp, efficiency)
+    if np.any(ec != 1.0) or np.any(ed != 1.0):
+        raise ValueError("central_reference_on_device: the device LP (dopf_central_solve_ex) has no storage efficiencies; "
+                         "use central_reference for a case with charge / discharge efficiencies other than 1")
     kw = pp.engine_kwargs()
+    kw.pop("sto_eta", None)
     if initial_level is not None:
         kw["sto_e0"] = np.asarray(initial_level, dtype=np.float64).reshape(pp.S)
     if terminal_level is not None:

@@ -59,6 +59,21 @@ static bool band_reachable(double e0, double lo, double hi, double pm, double em
     return lo <= std::min(em, e0 + span) && hi >= std::max(0.0, e0 - span);
 }
 
+// DOPF_F_STO_EFFICIENCY: a step moves the level by at most be pm up and al pm down (al = 1 / eta_d, be = eta_c):
+// [max(0, e0 - T al pm), min(em, e0 + T be pm)]
+static bool band_reachable(double e0, double lo, double hi, double pm, double em, int T, double al, double be)
+{
+    return lo <= std::min(em, e0 + (double)T * be * pm) && hi >= std::max(0.0, e0 - (double)T * al * pm);
+}
+
+// sorted storage i of the context: the stored band is reachable from e0 (contexts with DOPF_F_STO_EFFICIENCY: under the stored efficiencies)
+static bool band_reachable_ctx(const dopf_ctx *c, int i, double e0, double lo, double hi)
+{
+    if (c->q.flags & DOPF_F_STO_EFFICIENCY)
+        return band_reachable(e0, lo, hi, c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T, c->sto_al_h[i], c->sto_be_h[i]);
+    return band_reachable(e0, lo, hi, c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T);
+}
+
 // dopf_set_storage_initial_level's checks: the flag, and 0 <= e0[s] <= emax[s] for the caller's storage s (no NaN); with
 // DOPF_F_STO_TERMINAL_LEVEL also that the stored band stays reachable from e0 (NULL: from 0)
 int check_initial_levels(dopf_ctx *c, const double *e0)
@@ -72,7 +87,7 @@ int check_initial_levels(dopf_ctx *c, const double *e0)
         const double x = e0 ? e0[a] : 0.0;
         if (!(x >= 0.0 && x <= c->sto_emax_h[i]))
             return fail(c, DOPF_E_INVALID, "initial level of storage %d is %g, outside [0, max_level = %g]", a, x, c->sto_emax_h[i]);
-        if (band && !band_reachable(x, c->sto_lo_h[i], c->sto_hi_h[i], c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T))
+        if (band && !band_reachable_ctx(c, i, x, c->sto_lo_h[i], c->sto_hi_h[i]))
             return fail(c, DOPF_E_INVALID, "initial level %g of storage %d leaves its terminal band [%g, %g] unreachable in %d steps of %g",
                         x, a, c->sto_lo_h[i], c->sto_hi_h[i], c->v.T, c->sto_pmax_h[i]);
     }
@@ -114,9 +129,32 @@ int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi)
         const double l = lo[a], h = hi[a], em = c->sto_emax_h[i];
         if (!(l >= 0.0 && h <= em && l <= h))
             return fail(c, DOPF_E_INVALID, "terminal band of storage %d is [%g, %g], not inside [0, max_level = %g] (or empty)", a, l, h, em);
-        if (!band_reachable(c->sto_e0_h[i], l, h, c->sto_pmax_h[i], em, c->v.T))
+        if (!band_reachable_ctx(c, i, c->sto_e0_h[i], l, h))
             return fail(c, DOPF_E_INVALID, "terminal band [%g, %g] of storage %d is unreachable from its initial level %g in %d steps of %g",
                         l, h, a, c->sto_e0_h[i], c->v.T, c->sto_pmax_h[i]);
+    }
+    return DOPF_OK;
+}
+
+// dopf_set_storage_efficiency's checks: the flag, both arrays or neither, every value in (0, 1] (no NaN); with
+// DOPF_F_STO_TERMINAL_LEVEL also that the stored band stays reachable from the stored e0
+int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta_d)
+{
+    if (!(c->q.flags & DOPF_F_STO_EFFICIENCY))
+        return fail(c, DOPF_E_UNSUPPORTED, "storage efficiencies need DOPF_F_STO_EFFICIENCY at dopf_create");
+    if (!eta_c && !eta_d) return DOPF_OK;          // (all 1: the widest reachable range, and the stored pair passed under a narrower one or this)
+    if (!eta_c || !eta_d) return fail(c, DOPF_E_INVALID, "storage efficiencies: eta_c and eta_d must both be given or both be NULL");
+    const bool band = (c->q.flags & DOPF_F_STO_TERMINAL_LEVEL) != 0;
+    for (int i = 0; i < c->v.S; ++i) {
+        const int a = c->sto_perm[i];
+        const double ec = eta_c[a], ed = eta_d[a];
+        if (std::isnan(ec) || std::isnan(ed)) return fail(c, DOPF_E_INVALID, "%s[%d] is NaN", std::isnan(ec) ? "eta_c" : "eta_d", a);
+        if (!(ec > 0.0 && ec <= 1.0)) return fail(c, DOPF_E_INVALID, "eta_c[%d] = %g outside (0, 1]", a, ec);
+        if (!(ed > 0.0 && ed <= 1.0)) return fail(c, DOPF_E_INVALID, "eta_d[%d] = %g outside (0, 1]", a, ed);
+        if (band && !band_reachable(c->sto_e0_h[i], c->sto_lo_h[i], c->sto_hi_h[i], c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T, 1.0 / ed, ec))
+            return fail(c, DOPF_E_INVALID, "efficiencies eta_c[%d] = %g, eta_d[%d] = %g leave the terminal band [%g, %g] of storage %d unreachable "
+                        "from its initial level %g in %d steps of %g", a, ec, a, ed, c->sto_lo_h[i], c->sto_hi_h[i], a, c->sto_e0_h[i], c->v.T,
+                        c->sto_pmax_h[i]);
     }
     return DOPF_OK;
 }
@@ -224,8 +262,11 @@ Plan plan_chain(const Shape &sh, unsigned flags, int cus)
     // DOPF_F_GEN_AVAILABILITY: the same chain, with the generator bodies' AV instantiations (cap <= gen_pmax: every bound derived
     // from gen_pmax below and in dopf_create stays valid)
     p.genAvail = G > 0 && (flags & DOPF_F_GEN_AVAILABILITY);
-    p.stoLV = S == 0 ? 0 : (flags & DOPF_F_STO_TERMINAL_LEVEL) ? 2 : (flags & DOPF_F_STO_INITIAL_LEVEL) ? 1 : 0;
-    p.stoLean = !((flags & (DOPF_F_STO_GENERAL | DOPF_F_STO_INITIAL_LEVEL | DOPF_F_STO_TERMINAL_LEVEL)) ||
+    // DOPF_F_STO_EFFICIENCY: level mode 3 whatever the other two flags say (e0 and the band at their defaults without them) — one more
+    // instantiation per storage launch family; the chain is the one the same problem runs with the other two flags
+    p.stoEff = S > 0 && (flags & DOPF_F_STO_EFFICIENCY);
+    p.stoLV = S == 0 ? 0 : p.stoEff ? 3 : (flags & DOPF_F_STO_TERMINAL_LEVEL) ? 2 : (flags & DOPF_F_STO_INITIAL_LEVEL) ? 1 : 0;
+    p.stoLean = !((flags & (DOPF_F_STO_GENERAL | DOPF_F_STO_INITIAL_LEVEL | DOPF_F_STO_TERMINAL_LEVEL | DOPF_F_STO_EFFICIENCY)) ||
                   (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
                   (L > 0 && (long long)S * p.stoLPS / 256 < 1024)) && !p.stoLong;
     p.genTT = std::min(T, 512);
@@ -759,7 +800,7 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         v.gen_mp = reinterpret_cast<const double2 *>(d);
     }
     TRY(dev_upload(c, &v.sto_mc, smc)); TRY(dev_upload(c, &v.sto_pmax, spm));
-    if (c->plan.stoE0 || c->plan.stoLV == 2) {
+    if (c->plan.stoE0 || c->plan.stoLV >= 2) {
         // DOPF_F_STO_INITIAL_LEVEL: the initial levels behind the max levels (sto_e0), all 0 until the setter (and without that flag);
         // DOPF_F_STO_TERMINAL_LEVEL: the terminal bands behind those (sto_end_lo, sto_end_hi), [0, emax] until the setter
         c->sto_emax_h = sem;
@@ -769,7 +810,12 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
         c->sto_hi_h = sem;
         std::vector<double> em2(sem);
         em2.resize(2 * (size_t)S, 0.0);
-        if (c->plan.stoLV == 2) { em2.resize(3 * (size_t)S, 0.0); em2.insert(em2.end(), sem.begin(), sem.end()); }
+        if (c->plan.stoLV >= 2) { em2.resize(3 * (size_t)S, 0.0); em2.insert(em2.end(), sem.begin(), sem.end()); }
+        if (c->plan.stoEff) {       // DOPF_F_STO_EFFICIENCY: al = 1 / eta_d and be = eta_c behind the bands (sto_eff_alpha, sto_eff_beta), ones until the setter
+            c->sto_al_h.assign(S, 1.0);
+            c->sto_be_h.assign(S, 1.0);
+            em2.resize(6 * (size_t)S, 1.0);
+        }
         TRY(dev_upload(c, &v.sto_emax, em2));
     } else {
         TRY(dev_upload(c, &v.sto_emax, sem));
@@ -1421,6 +1467,28 @@ int dopf_set_storage_terminal_level(dopf_ctx *c, const double *lo, const double 
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->sto_lo_h.assign(h.begin(), h.begin() + S);
     c->sto_hi_h.assign(h.begin() + S, h.end());
+    return DOPF_OK;
+}
+
+int dopf_set_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta_d)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_storage_efficiency(c, eta_c, eta_d)) return rc;
+    const int S = c->v.S;
+    if (S == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<double> h(2 * (size_t)S, 1.0);   // al then be: sto_eff_beta(v) = sto_eff_alpha(v) + S
+    if (eta_c)
+        for (int i = 0; i < S; ++i) {
+            const int a = c->sto_perm[i];
+            h[i] = 1.0 / eta_d[a];
+            h[S + i] = eta_c[a];
+        }
+    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again)
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_eff_alpha(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    c->sto_al_h.assign(h.begin(), h.begin() + S);
+    c->sto_be_h.assign(h.begin() + S, h.end());
     return DOPF_OK;
 }
 

@@ -62,7 +62,7 @@ extern "C" int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q
     dopf_ctx *c = nullptr;
     dopf_params qq = *q;
     qq.stream = nullptr;
-    qq.flags &= ~(DOPF_F_OVERLAP_AGENTS);
+    qq.flags &= ~(DOPF_F_OVERLAP_AGENTS | DOPF_F_STO_EFFICIENCY);     // (the device LP is lossless: no efficiency input, the flag's default)
     // every input that is given sets its flag (the caller's own flags stay: a flag without its input is that feature's default)
     const bool has_e0 = sto_e0_in != nullptr, has_band = sto_end_lo_in || sto_end_hi_in;
     const bool has_avail = n_profiles != 0 || profiles || profile_of;

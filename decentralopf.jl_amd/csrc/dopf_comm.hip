@@ -710,6 +710,18 @@ int dopf_multi_set_storage_terminal_level(dopf_multi *m, const double *lo, const
     return DOPF_OK;
 }
 
+int dopf_multi_set_storage_efficiency(dopf_multi *m, const double *eta_c, const double *eta_d)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all efficiencies as they were
+        for (int i = 0; i < m->n; ++i) {
+            const double *ci = eta_c ? eta_c + m->s0[i] : nullptr, *di = eta_d ? eta_d + m->s0[i] : nullptr;
+            const int rc = pass == 0 ? check_storage_efficiency(m->ctx[i], ci, di) : dopf_set_storage_efficiency(m->ctx[i], ci, di);
+            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
+        }
+    return DOPF_OK;
+}
+
 int dopf_multi_set_generator_availability(dopf_multi *m, int32_t n_profiles, const double *profiles, const int32_t *profile_of)
 {
     if (!m) return DOPF_E_INVALID;

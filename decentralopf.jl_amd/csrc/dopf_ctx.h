@@ -36,6 +36,7 @@ struct dopf_ctx {
     std::vector<double> sto_pmax_h;        // DOPF_F_STO_TERMINAL_LEVEL: max charge / discharge per step, sorted order (reachability)
     std::vector<double> sto_e0_h, sto_lo_h, sto_hi_h;   // the values on the device: initial levels, terminal bands (sorted order; each
                                                         // setter checks reachability against the other's)
+    std::vector<double> sto_al_h, sto_be_h;   // DOPF_F_STO_EFFICIENCY: 1 / eta_d and eta_c on the device (sorted order; empty without the flag)
     std::vector<int> gen_prof_h;           // DOPF_F_GEN_AVAILABILITY: the generators' profile indices on the device (sorted order)
     double *gen_avail = nullptr;           // ... the profile table on the device (its address is in gen_avail_slot(v)) and the
     int gen_avail_cap = 0;                 //     profiles it has room for
@@ -56,6 +57,7 @@ void drop_graphs(dopf_ctx *c);
 int read_status(dopf_ctx *c);
 int check_initial_levels(dopf_ctx *c, const double *e0);   // the checks of dopf_set_storage_initial_level (flag, 0 <= e0 <= emax)
 int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi);   // those of dopf_set_storage_terminal_level
+int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta_d);   // those of dopf_set_storage_efficiency
 int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of);   // dopf_set_generator_availability's
 void launch_demote_full_rows(const DevView &v, hipStream_t s);   // gen_state 1 -> 2 (the caps changed)
 // dopf_comm.hip

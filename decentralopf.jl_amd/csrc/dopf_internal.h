@@ -170,6 +170,10 @@ __host__ __device__ inline const double *sto_e0(const DevView &v) { return v.sto
 // dopf_set_storage_terminal_level), sorted order
 __host__ __device__ inline const double *sto_end_lo(const DevView &v) { return v.sto_emax + 2 * (size_t)v.S; }
 __host__ __device__ inline const double *sto_end_hi(const DevView &v) { return v.sto_emax + 3 * (size_t)v.S; }
+// DOPF_F_STO_EFFICIENCY contexts only (sto_emax then has 6S entries; e0 and the band at their defaults without the other two flags):
+// al = 1 / eta_d and be = eta_c of each storage, sorted order, ones until dopf_set_storage_efficiency. The level moves by be C - al D.
+__host__ __device__ inline const double *sto_eff_alpha(const DevView &v) { return v.sto_emax + 4 * (size_t)v.S; }
+__host__ __device__ inline const double *sto_eff_beta(const DevView &v) { return v.sto_emax + 5 * (size_t)v.S; }
 
 // DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
 // gen_pmax[g] for k = -1. gen_state has room for both behind its G row states: the G profile indices (sorted order, -1 until
@@ -259,7 +263,9 @@ struct Plan {
     bool genAvail;                  // DOPF_F_GEN_AVAILABILITY: the generator bodies that read the rows' profiles (nothing else of the plan changes)
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
-                                    // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag)
+                                    // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those
+                                    // and efficiencies (DOPF_F_STO_EFFICIENCY; defaults for what the other two flags do not set)
+    bool stoEff;                    // DOPF_F_STO_EFFICIENCY: levels are e0 + cumsum(be C - al D) (k_derive_level_eff, k_roll_level_eff)
     bool fuseAgents, fuseNet;       // generators + storages in one launch: k_agents (copper plate, even T), k_net_agents (networks)
     bool tail;                      // the tail of the iteration in the x-update launch (DevView::tailDev)
     bool slackDual;                 // the one-launch dual/price kernel may form the slack sums: no k_reduce (DevView::slackInDual)
@@ -327,7 +333,7 @@ void launch_xchg(const DevView &v, const XchgView &x, hipStream_t s, bool inj_on
 void launch_dual(const DevView &v, const Plan &p, hipStream_t s, const XchgView *xd = nullptr);   // xd: peer exchange inside the one-block kernel
 //      // consensus -> duals, residuals, prices, status
 void launch_derive(const DevView &v, const Plan &p, hipStream_t s, bool from_primal);
-void launch_derive_level(const DevView &v, const Plan &p, hipStream_t s);   // E = e0 + cumsum(C - D) into v.E (e0 = 0 without p.stoE0)
+void launch_derive_level(const DevView &v, const Plan &p, hipStream_t s);   // E = e0 + cumsum(C - D) into v.E (e0 = 0 without p.stoE0; p.stoEff: be C - al D)
 // dopf_set_demand / dopf_roll_horizon (kernels_consensus.hip). A per-timestep vector [j + stride*t] that moves by k
 // timesteps through the scratch (at off); tail: what follows the kept part (stride*k values), null: the old last timestep
 struct RollVec { double *p; const double *tail; size_t off; int stride; };

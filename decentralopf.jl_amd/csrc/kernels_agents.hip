@@ -1058,6 +1058,16 @@ __device__ __forceinline__ void box2(double a, double b, double ia, double idet,
     sg = (fD && fC) ? s2 : ((fD || fC) ? ia : 0.0);
 }
 
+// DOPF_F_STO_EFFICIENCY (level mode 3): the level moves by x = be C - al D (be = eta_c, al = 1 / eta_d), the price nu enters the two
+// gradient offsets as rD = rD0 - al nu, rC = rC0 + be nu, and box2 itself is unchanged. dx/dnu on the active piece of box2's solution
+// (D, C): (a (al^2 + be^2) - 2 b al be) / (a^2 - b^2) with both free, al^2 / a with D free, be^2 / a with C free, 0 with none
+// (al = be = 1: box2's own sg).
+__device__ __forceinline__ double eff_slope(double a, double b, double ia, double idet, double al, double be, double pm, double D, double C)
+{
+    const bool fD = D > 0.0 && D < pm, fC = C > 0.0 && C < pm;
+    return (fD && fC) ? (a * (al * al + be * be) - 2.0 * b * al * be) * idet : (fD ? al * al * ia : (fC ? be * be * ia : 0.0));
+}
+
 // breakpoint table of Psi_{n,t} as one lane-timestep sees it
 struct TabRef {
     const double *beta, *psi, *slope;
@@ -1130,6 +1140,45 @@ __device__ __forceinline__ void eval_lines(const TabRef &tb, int &hint, double w
     psi_cur = theta + kap * (dd - cc);       // Psi at the step's current net injection
 }
 
+// DOPF_F_STO_EFFICIENCY: the same search with the price as the two sides see it — the probe's D at Psi + al nu, its C at Psi + be nu —
+// and s1 = d(be C - al D)/dnu (an overload of its own: the level modes of before call the one above, unchanged)
+__device__ __forceinline__ void eval_lines(const TabRef &tb, int &hint, double w, double iw, double mc, double pm,
+                                           double D0, double C0, double nu, double al, double be, double &dd, double &cc, double &s1,
+                                           double &psi_cur)
+{
+    const double q0 = D0 - C0, nD = al * nu, nC = be * nu;
+    double ab = 0.0, ap = tb.psi0, kap = tb.slope[0];
+    const int m = tb.m;
+    if (m > 0) {
+        auto rneg = [&](int idx) -> bool {
+            const double z = tb.psi[idx];
+            const double Dz = clampd(D0 - (mc + z + nD) * iw, 0.0, pm), Cz = clampd(C0 - (mc - z - nC) * iw, 0.0, pm);
+            return tb.beta[idx] - (Dz - Cz - q0) < 0.0;
+        };
+        int l2 = hint < 0 ? 0 : (hint > m ? m : hint);
+        const bool okLo = l2 == 0 || rneg(l2 - 1);
+        const bool okHi = l2 == m || !rneg(l2);
+        if (!(okLo && okHi)) {
+            int lo = okLo ? l2 + 1 : 0, hi = okLo ? m : l2 - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (!rneg(mid)) hi = mid; else lo = mid + 1;
+            }
+            l2 = lo;
+        }
+        hint = l2;
+        const int a = l2 < m ? l2 : m - 1;
+        ab = tb.beta[a]; ap = tb.psi[a]; kap = tb.slope[l2];
+    }
+    const double theta = ap - kap * (ab + q0);
+    const double a = w + kap;
+    double ia, idet, s2;
+    lin_coef(w, iw, kap, ia, idet, s2);
+    box2(a, kap, ia, idet, s2, w * D0 - mc - theta - nD, w * C0 - mc + theta + nC, pm, dd, cc, s1);
+    s1 = eff_slope(a, kap, ia, idet, al, be, pm, dd, cc);
+    psi_cur = theta + kap * (dd - cc);       // Psi at the step's current net injection
+}
+
 // The same two as functions of their own, for the active-set body: there a (node, timestep) with a non-empty table is
 // the rare case (none in the settled state), and inlined their registers cost the common path a wave per SIMD.
 struct EvalOut { double dd, cc, s1, pc; int hint; };
@@ -1141,6 +1190,17 @@ __device__ __attribute__((noinline)) EvalOut eval_lines_call(const DevView *self
     EvalOut o;
     o.hint = hint;
     eval_lines(tb, o.hint, v.w_prox, 1.0 / v.w_prox, mc, pm, D0, C0, nu, o.dd, o.cc, o.s1, o.pc);
+    return o;
+}
+// (DOPF_F_STO_EFFICIENCY: the overload with al, be)
+__device__ __attribute__((noinline)) EvalOut eval_lines_call(const DevView *self, int node, int t, int hint, double mc, double pm,
+                                                             double D0, double C0, double nu, double al, double be)
+{
+    const DevView &v = *self;
+    const TabRef tb = tab_ref(v, node, t);
+    EvalOut o;
+    o.hint = hint;
+    eval_lines(tb, o.hint, v.w_prox, 1.0 / v.w_prox, mc, pm, D0, C0, nu, al, be, o.dd, o.cc, o.s1, o.pc);
     return o;
 }
 __device__ __attribute__((noinline)) double tab_psi_call(const DevView *self, int node, int t, double dl)
@@ -1160,10 +1220,13 @@ struct StoAgent {
 //   1 (E0): the level before the first timestep is the storage's initial level sto_e0(v)[s] (DOPF_F_STO_INITIAL_LEVEL), not 0;
 //   2: as 1, and the level after the last timestep lies in the storage's terminal band [sto_end_lo, sto_end_hi]
 //      (DOPF_F_STO_TERMINAL_LEVEL): the walk classifies step T-1 against that band and its root search targets lo or hi
+//   3 (EF): as 2, and the level moves by be C - al D with the storage's be = eta_c = sto_eff_beta(v)[s], al = 1 / eta_d =
+//      sto_eff_alpha(v)[s] (DOPF_F_STO_EFFICIENCY; e0 and the band at their defaults without the other two flags): x_t, its slope
+//      and the four kink prices change (eff_slope above), nothing else
 template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, int LV = 0>
 __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, int item_fail)
 {
-    constexpr bool E0 = LV >= 1;
+    constexpr bool E0 = LV >= 1, EF = LV == 3;
     constexpr int NG = 256 / LPS;
     __shared__ double red[NG * LPS * NCH];
     __shared__ double redc[256];
@@ -1225,7 +1288,10 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
         ag.pm = live ? v.sto_pmax[s] : 0.0;
         ag.em = live ? v.sto_emax[s] : 0.0;
         const double e0 = (E0 && live) ? sto_e0(v)[s] : 0.0;       // level before timestep 0
-        const double elo = (LV == 2 && live) ? sto_end_lo(v)[s] : 0.0, ehi = (LV == 2 && live) ? sto_end_hi(v)[s] : ag.em;   // band of step T-1
+        const double elo = (LV >= 2 && live) ? sto_end_lo(v)[s] : 0.0, ehi = (LV >= 2 && live) ? sto_end_hi(v)[s] : ag.em;   // band of step T-1
+        // (EF: a lane group without a storage reads 1, 1)
+        const double al = (EF && live) ? sto_eff_alpha(v)[s] : 1.0, be = (EF && live) ? sto_eff_beta(v)[s] : 1.0;
+        const double ial = EF ? 1.0 / al : 1.0, ibe = EF ? 1.0 / be : 1.0;
         // rD0/rC0: the nu-independent part of the two gradient offsets (copper plate); D0/C0 otherwise
         double D0[NCH], C0[NCH], nuf[NCH];
 #pragma unroll
@@ -1245,21 +1311,25 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
         for (int c = 0; c < NCH; ++c) hint[c] = 0;
         const double iw = 1.0 / w;
         auto eval = [&](int c, double nu, double &dd, double &cc, double &s1, double &pc) {
+            const double nD = EF ? al * nu : nu, nC = EF ? be * nu : nu;      // the price as D's and as C's gradient see it
             if (!LINES) {
                 const double q0 = D0[c] - C0[c], theta = th0[c] - gam * q0;
-                box2(a0, gam, ia0, idet0, s20, w * D0[c] - ag.mc - theta - nu, w * C0[c] - ag.mc + theta + nu,
+                box2(a0, gam, ia0, idet0, s20, w * D0[c] - ag.mc - theta - nD, w * C0[c] - ag.mc + theta + nC,
                      ag.pm, dd, cc, s1);
+                if (EF) s1 = eff_slope(a0, gam, ia0, idet0, al, be, ag.pm, dd, cc);
                 pc = theta + gam * (dd - cc);
             } else if (lin[c]) {
                 const double q0 = D0[c] - C0[c], theta = lp0[c] - lkap[c] * q0;
                 double lia, lidet, ls2;
                 lin_coef(w, iw, lkap[c], lia, lidet, ls2);
-                box2(w + lkap[c], lkap[c], lia, lidet, ls2, w * D0[c] - ag.mc - theta - nu, w * C0[c] - ag.mc + theta + nu,
+                box2(w + lkap[c], lkap[c], lia, lidet, ls2, w * D0[c] - ag.mc - theta - nD, w * C0[c] - ag.mc + theta + nC,
                      ag.pm, dd, cc, s1);
+                if (EF) s1 = eff_slope(w + lkap[c], lkap[c], lia, lidet, al, be, ag.pm, dd, cc);
                 pc = theta + lkap[c] * (dd - cc);
             } else {
                 const TabRef tb = tab_ref(v, it.node, tbase + c);
-                eval_lines(tb, hint[c], w, iw, ag.mc, ag.pm, D0[c], C0[c], nu, dd, cc, s1, pc);
+                if constexpr (EF) eval_lines(tb, hint[c], w, iw, ag.mc, ag.pm, D0[c], C0[c], nu, al, be, dd, cc, s1, pc);
+                else eval_lines(tb, hint[c], w, iw, ag.mc, ag.pm, D0[c], C0[c], nu, dd, cc, s1, pc);
             }
         };
 
@@ -1285,7 +1355,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
                 const int t = tbase + c;
                 double dd = 0.0, cc = 0.0, s1 = 0.0, pc = 0.0;
                 if (t <= k && t < T) eval(c, nu, dd, cc, s1, pc);
-                x[c] = cc - dd;
+                x[c] = EF ? be * cc - al * dd : cc - dd;
                 sg[c] = s1;
                 psc[c] = pc;
                 loc.A += x[c];
@@ -1341,7 +1411,8 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
                 for (int c = 0; c < NCH; ++c) {
                     if (tbase + c > idx || tbase + c <= jlast) continue;
                     const double bD = w * D0[c] - ag.mc - psc[c], bC = ag.mc - w * C0[c] - psc[c], wp = w * ag.pm;
-                    const double cand[4] = {bD, bD - wp, bC, bC + wp};
+                    // (EF: D's two at b / al, C's two at b / be)
+                    const double cand[4] = {EF ? bD * ial : bD, EF ? (bD - wp) * ial : bD - wp, EF ? bC * ibe : bC, EF ? (bC + wp) * ibe : bC + wp};
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const double d = (cand[q] - nu) * dir;
@@ -1397,7 +1468,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     const int t = tbase + c;
-                    const unsigned long long bts = group_bits<LPS>(t <= k && t < T && (LV == 2 && t == T - 1 ? (Sv[c] < elo - tol || Sv[c] > ehi + tol)
+                    const unsigned long long bts = group_bits<LPS>(t <= k && t < T && (LV >= 2 && t == T - 1 ? (Sv[c] < elo - tol || Sv[c] > ehi + tol)
                                                                                                           : (Sv[c] < -tol || Sv[c] > ag.em + tol)), gbase);
                     if (bts) { const int j = (63 - __clzll(bts)) * NCH + c; vnew = j > vnew ? j : vnew; }
                 }
@@ -1411,7 +1482,7 @@ __device__ __forceinline__ void sto_cold_body(const DevView &v, const int blk, i
                 } else {
                     const double sv = level_at(vnew), sl = slope_at(vnew);
                     vv = vnew;
-                    if (LV == 2 && vnew == T - 1) target = sv < elo ? elo : ehi;
+                    if (LV >= 2 && vnew == T - 1) target = sv < elo ? elo : ehi;
                     else target = sv < 0.0 ? 0.0 : ag.em;
                     const double res = sv - target;
                     lo = -INFINITY; hi = INFINITY;
@@ -1672,7 +1743,7 @@ __device__ __forceinline__ int next_lane_i(int x)
 template <int LPS, int NCH, bool LINES, bool TAIL = false, bool FULLT = false, int LV = 0>
 __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, const int halt = 0)
 {
-    constexpr bool E0 = LV >= 1;
+    constexpr bool E0 = LV >= 1, EF = LV == 3;
     constexpr int NG = 256 / LPS, TP = LPS * NCH;
     constexpr int MAXR = 16;                 // contact-set rounds per storage
     constexpr int MAXN = 40;                 // Newton iterations per round
@@ -1739,7 +1810,10 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
         const bool live = s < it.a1;
         const double mc = live ? v.sto_mc[s] : 0.0, pm = live ? v.sto_pmax[s] : 0.0, em = live ? v.sto_emax[s] : 0.0;
         const double e0 = (E0 && live) ? sto_e0(v)[s] : 0.0;     // level before timestep 0
-        const double elo = (LV == 2 && live) ? sto_end_lo(v)[s] : 0.0, ehi = (LV == 2 && live) ? sto_end_hi(v)[s] : em;   // band of step T-1
+        const double elo = (LV >= 2 && live) ? sto_end_lo(v)[s] : 0.0, ehi = (LV >= 2 && live) ? sto_end_hi(v)[s] : em;   // band of step T-1
+        // (EF, once per storage pass: a lane group without a storage reads 1, 1)
+        const double al = (EF && live) ? sto_eff_alpha(v)[s] : 1.0, be = (EF && live) ? sto_eff_beta(v)[s] : 1.0;
+        const double ial = EF ? 1.0 / al : 1.0, ibe = EF ? 1.0 / be : 1.0;
         const bool havenu = live && v.nu_valid[s] != 0;
         // copper plate: the nu-independent parts of the two gradient offsets, rD = rD0 - nu, rC = rC0 + nu
         // (with lines Psi depends on the step itself: D0/C0 are kept and the offsets are built per evaluation)
@@ -1758,8 +1832,8 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                                                                // has s past the end — a load behind the nu_valid word would be a second round trip)
             nuv[c] = (ok && havenu) ? nu_st : 0.0;             // no stored prices (zero state, set_state): start from 0
             hint[c] = 0;
-            dq[c] = c0 - d0;
-            run += c0 - d0;
+            dq[c] = EF ? be * c0 - al * d0 : c0 - d0;
+            run += EF ? be * c0 - al * d0 : c0 - d0;
             if (LINES) { A0[c] = d0; B0[c] = c0; }
             else {
                 const double th0 = t < T ? v.price[it.node + N * t] + gam * v.s[t] : 0.0;
@@ -1775,16 +1849,21 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
         if (rep == 0 && halt) return -1;         // (uniform; the loads above are on their way, nothing has been stored)
         // (D, C)(nu) of step c, d(C - D)/dnu; shift = Psi at the step's net injection minus its nu-independent anchor
         auto eval = [&](int c, double nu, double &dd, double &cc, double &s1) {
+            const double nD = EF ? al * nu : nu, nC = EF ? be * nu : nu;      // the price as D's and as C's gradient see it
             if (!LINES) {
-                box2(a0, gam, ia0, idet0, s20, A0[c] - nu, B0[c] + nu, pm, dd, cc, s1);
+                box2(a0, gam, ia0, idet0, s20, A0[c] - nD, B0[c] + nC, pm, dd, cc, s1);
+                if (EF) s1 = eff_slope(a0, gam, ia0, idet0, al, be, pm, dd, cc);
             } else if (lin[c]) {
                 const double q0 = A0[c] - B0[c], theta = lp0[c] - lkap[c] * q0;
                 double lia, lidet, ls2;
                 lin_coef(w, iw, lkap[c], lia, lidet, ls2);
-                box2(w + lkap[c], lkap[c], lia, lidet, ls2, w * A0[c] - mc - theta - nu, w * B0[c] - mc + theta + nu,
+                box2(w + lkap[c], lkap[c], lia, lidet, ls2, w * A0[c] - mc - theta - nD, w * B0[c] - mc + theta + nC,
                      pm, dd, cc, s1);
+                if (EF) s1 = eff_slope(w + lkap[c], lkap[c], lia, lidet, al, be, pm, dd, cc);
             } else {
-                const EvalOut o = eval_lines_call(v.self, it.node, tbase + c, hint[c], mc, pm, A0[c], B0[c], nu);
+                EvalOut o;
+                if constexpr (EF) o = eval_lines_call(v.self, it.node, tbase + c, hint[c], mc, pm, A0[c], B0[c], nu, al, be);
+                else o = eval_lines_call(v.self, it.node, tbase + c, hint[c], mc, pm, A0[c], B0[c], nu);
                 dd = o.dd; cc = o.cc; s1 = o.s1; hint[c] = o.hint;
             }
         };
@@ -1811,7 +1890,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
             for (int c = 0; c < NCH; ++c) {
                 const int t = tbase + c;
                 eo += dq[c];
-                if (LV == 2 && t == T - 1) kind[c] = eo <= elo + tolc ? 1 : (eo >= ehi - tolc ? 2 : 0);
+                if (LV >= 2 && t == T - 1) kind[c] = eo <= elo + tolc ? 1 : (eo >= ehi - tolc ? 2 : 0);
                 else kind[c] = t < T ? (eo <= tolc ? 1 : (eo >= em - tolc ? 2 : 0)) : 0;
             }
         }
@@ -1826,7 +1905,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
             DOPF_TIC();
             // end of a segment: a contact, or the last step; start: the step after an end (or step 0)
 #define ISEND(c) (tbase + (c) < T && (kind[c] != 0 || tbase + (c) == T - 1))
-#define TGT(c) (LV == 2 && tbase + (c) == T - 1 ? (kind[c] == 2 ? ehi : elo) : (kind[c] == 2 ? em : 0.0))
+#define TGT(c) (LV >= 2 && tbase + (c) == T - 1 ? (kind[c] == 2 ? ehi : elo) : (kind[c] == 2 ? em : 0.0))
             double bs[NCH];
             int send[NCH];
             bool st0;                                            // this lane's first step starts a segment
@@ -1887,7 +1966,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                         if (tbase + c < T) eval(c, nuv[c], dd, cc, s1);
                         Dv[c] = dd; Cv[c] = cc;            // (of the last evaluation: the certified values when the round passes)
                         if (STARTS(c)) { rx = 0.0; rs = 0.0; f = 1; }
-                        rx += cc - dd; rs += s1;
+                        rx += EF ? be * cc - al * dd : cc - dd; rs += s1;
                         px[c] = rx; ps[c] = rs;
                     }
                     int fl = f;
@@ -1920,7 +1999,8 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                             double bD, bC;
                             kinks(c, Dv[c], Cv[c], bD, bC);          // (D, C) of this Newton iteration's evaluation at nuv[c]
                             const double wp = w * pm;
-                            const double cand[4] = {bD, bD - wp, bC, bC + wp};
+                            // (EF: D's two at b / al, C's two at b / be)
+                            const double cand[4] = {EF ? bD * ial : bD, EF ? (bD - wp) * ial : bD - wp, EF ? bC * ibe : bC, EF ? (bC + wp) * ibe : bC + wp};
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
                                 const double d = cand[q] - nuv[c];
@@ -2017,8 +2097,13 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                     if (t < T) {
                         const double rD0 = A0[c], rC0 = B0[c];
                         const double dd = Dv[c], cc = Cv[c];
+                        if constexpr (EF) {     // (the price enters grad_D as al nu, grad_C as be nu: D's bounds / al, C's / be)
+                            if (dd <= 0.0) lo = (rD0 + gam * cc) * ial; else if (dd >= pm) hi = (rD0 - a0 * pm + gam * cc) * ial;
+                            if (cc <= 0.0) hi = lz_min(hi, (-rC0 - gam * dd) * ibe); else if (cc >= pm) lo = lz_max(lo, (a0 * pm - gam * dd - rC0) * ibe);
+                        } else {
                         if (dd <= 0.0) lo = rD0 + gam * cc; else if (dd >= pm) hi = rD0 - a0 * pm + gam * cc;
                         if (cc <= 0.0) hi = lz_min(hi, -rC0 - gam * dd); else if (cc >= pm) lo = lz_max(lo, a0 * pm - gam * dd - rC0);
+                        }
                     }
                     if (STARTS(c)) { rl = -INFINITY; rh = INFINITY; f = 1; }
                     rl = lz_max(rl, lo); rh = lz_min(rh, hi);
@@ -2051,7 +2136,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                 if (t < T) {
                     const double Ev = bs[c] + px[c];
                     if (!(ISEND(c) && kind[c] != 0)) {           // (a contact's level is its Newton target)
-                        if (LV == 2 && t == T - 1) {             // (the terminal band; PDAS: a contact at the bound it crossed)
+                        if (LV >= 2 && t == T - 1) {             // (the terminal band; PDAS: a contact at the bound it crossed)
                             if (Ev < elo - tolE) { okk = false; nkind[c] = 1; }
                             else if (Ev > ehi + tolE) { okk = false; nkind[c] = 2; }
                         } else if (Ev < -tolE) { okk = false; nkind[c] = 1; }
@@ -2068,12 +2153,14 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                             // idle on a bound: with D = C = 0 the step's net injection is unchanged at q = 0: dlt = -q0
                             const double q0 = A0[c] - B0[c];
                             const double theta = lin[c] ? lp0[c] - lkap[c] * q0 : tab_psi_call(v.self, it.node, t, -q0);
-                            const double rD0 = w * A0[c] - mc - theta, rC0 = w * B0[c] - mc + theta;
+                            // (EF: the dead band in nu is [rD0 / al, -rC0 / be])
+                            const double rD0 = EF ? (w * A0[c] - mc - theta) * ial : w * A0[c] - mc - theta;
+                            const double rC0 = EF ? (w * B0[c] - mc + theta) * ibe : w * B0[c] - mc + theta;
                             if (rD0 <= -rC0 && nuv[c] >= rD0 - 1e-9 && nuv[c] <= -rC0 + 1e-9) { mlo[c] = rD0; mhi[c] = -rC0; }
                         }
                         // lower-end chain: empty x -> max(mlo, x), full/open x -> mlo; upper-end chain: empty/open x -> mhi, full x -> min(mhi, x)
                         // (LV 2, a contact at T-1 with lo == hi: no sign condition, the maps of an open segment)
-                        const int sk = LV == 2 && t == T - 1 && elo == ehi ? 0 : kind[c];
+                        const int sk = LV >= 2 && t == T - 1 && elo == ehi ? 0 : kind[c];
                         const double a_lo = mlo[c], a_hi = sk == 1 ? INFINITY : mlo[c];
                         const double b_lo = sk == 2 ? -INFINITY : mhi[c], b_hi = mhi[c];
                         const double nal = lz_clamp(alo, a_lo, a_hi), nah = lz_clamp(ahi, a_lo, a_hi);
@@ -2093,7 +2180,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                 const int t = tbase + c;
                 nuc[c] = nuv[c];
                 if (t < T && ISEND(c)) {
-                    const int sk = LV == 2 && t == T - 1 && elo == ehi ? 0 : kind[c];      // (as in the chains above)
+                    const int sk = LV >= 2 && t == T - 1 && elo == ehi ? 0 : kind[c];      // (as in the chains above)
                     flo = sk == 1 ? lz_max(mlo[c], flo) : mlo[c];
                     fhi = sk == 2 ? lz_min(mhi[c], fhi) : mhi[c];
                     if (kind[c] != 0) {
@@ -2198,6 +2285,11 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
                         v.C[e] = Cv[c];
                         // (nu + theta, see the loads; theta back from the step's offsets: B0 - A0 = w (c0 - d0) + 2 theta. Kept in
                         // registers: a second array of solver state in memory cost 1.2 us per iteration, the registers nothing)
+                        if constexpr (EF && !LINES) {
+                            // (dq is be c0 - al d0 here; c0 - d0 back from it and A0 + B0 = w (d0 + c0) - 2 mc. A guess, as before)
+                            const double sum = (A0[c] + B0[c] + 2.0 * mc) * iw, c0 = (dq[c] + al * sum) / (al + be);
+                            v.nu_prev[e] = nuc[c] + 0.5 * (B0[c] - A0[c] - w * (2.0 * c0 - sum));
+                        } else
                         v.nu_prev[e] = LINES ? nuc[c] : nuc[c] + 0.5 * (B0[c] - A0[c] - w * dq[c]);
                         if (LINES && (v.keepDeltas || v.walk_any[t])) v.dltS[e] = (Dv[c] - Cv[c]) - (A0[c] - B0[c]);
                         accQ[c] += Dv[c] - Cv[c];
@@ -2587,11 +2679,12 @@ static void with_bool(bool b, F &&f)
     else f(std::false_type{});
 }
 
-// f(integral_constant<int, LV>) for the plan's level mode p.stoLV (0, 1, 2: all three instantiated)
+// f(integral_constant<int, LV>) for the plan's level mode p.stoLV (0 .. 3: all four instantiated)
 template <class F>
 static void with_lv(int lv, F &&f)
 {
-    if (lv == 2) f(std::integral_constant<int, 2>{});
+    if (lv == 3) f(std::integral_constant<int, 3>{});
+    else if (lv == 2) f(std::integral_constant<int, 2>{});
     else if (lv == 1) f(std::integral_constant<int, 1>{});
     else f(std::integral_constant<int, 0>{});
 }
@@ -2607,6 +2700,7 @@ static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
         with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NC, [&](auto full) {
             constexpr bool TL = decltype(tail)::value, FU = decltype(full)::value;
             if (p.stoLean) hipLaunchKernelGGL((k_sto_l<LPS, NC, TL, FU>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 3) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, 3>), grid, dim3(256), 0, s, v);
             else if (p.stoLV == 2) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, 2>), grid, dim3(256), 0, s, v);
             else if (p.stoLV == 1) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, 1>), grid, dim3(256), 0, s, v);
             else hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU>), grid, dim3(256), 0, s, v);
@@ -2617,6 +2711,7 @@ static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
     // body itself for what it leaves over
     if (v.use_warm) {
         if (p.stoLean) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        else if (p.stoLV == 3) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, 3>), dim3(v.nStoItems), dim3(256), 0, s, v);
         else if (p.stoLV == 2) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, 2>), dim3(v.nStoItems), dim3(256), 0, s, v);
         else if (p.stoLV == 1) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, 1>), dim3(v.nStoItems), dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false>), dim3(v.nStoItems), dim3(256), 0, s, v);
@@ -2637,12 +2732,14 @@ static void launch_agents_t(const DevView &v, const Plan &p, hipStream_t s)
         constexpr bool SK = decltype(skip)::value, TL = decltype(tail)::value, FU = decltype(full)::value;
         if (p.genAvail) {           // DOPF_F_GEN_AVAILABILITY: the generator blocks with the rows' caps, the same storage bodies
             if (p.stoLean) hipLaunchKernelGGL((k_agents_l_av<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 3) hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU, 3>), grid, dim3(256), 0, s, v);
             else if (p.stoLV == 2) hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU, 2>), grid, dim3(256), 0, s, v);
             else if (p.stoLV == 1) hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU, 1>), grid, dim3(256), 0, s, v);
             else hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
             return;
         }
         if (p.stoLean) hipLaunchKernelGGL((k_agents_l<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
+        else if (p.stoLV == 3) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 3>), grid, dim3(256), 0, s, v);
         else if (p.stoLV == 2) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 2>), grid, dim3(256), 0, s, v);
         else if (p.stoLV == 1) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 1>), grid, dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
@@ -2660,12 +2757,14 @@ void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s)
     with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) {
         if (p.genAvail) {           // DOPF_F_GEN_AVAILABILITY: the generator blocks with the rows' caps, the same storage bodies
             if (p.stoLean) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
+            else if (p.stoLV == 3) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false, 3>), grid, dim3(256), 0, s, v);
             else if (p.stoLV == 2) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false, 2>), grid, dim3(256), 0, s, v);
             else if (p.stoLV == 1) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false, 1>), grid, dim3(256), 0, s, v);
             else hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false>), grid, dim3(256), 0, s, v);
             return;
         }
         if (p.stoLean) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
+        else if (p.stoLV == 3) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 3>), grid, dim3(256), 0, s, v);
         else if (p.stoLV == 2) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 2>), grid, dim3(256), 0, s, v);
         else if (p.stoLV == 1) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 1>), grid, dim3(256), 0, s, v);
         else hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false>), grid, dim3(256), 0, s, v);

@@ -1832,6 +1832,20 @@ __global__ __launch_bounds__(256) void k_derive_level(DevView v, const double *e
     }
 }
 
+// DOPF_F_STO_EFFICIENCY: E = e0 + cumsum(be C - al D) (a kernel of its own: k_derive_level stays as it is)
+__global__ __launch_bounds__(256) void k_derive_level_eff(DevView v)
+{
+    const int T = v.T;
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= v.S) return;
+    const double al = sto_eff_alpha(v)[s], be = sto_eff_beta(v)[s];
+    double e = sto_e0(v)[s];
+    for (int t = 0; t < T; ++t) {
+        e += be * v.C[(size_t)s * T + t] - al * v.D[(size_t)s * T + t];
+        v.E[(size_t)s * T + t] = e;
+    }
+}
+
 // ResultNode.{generation, discharge, charge} (results.jl:19-35): per node and timestep the sums over the node's units,
 // on request. Block = (node, chunk of 32 timesteps), 8 agent lanes per timestep, fixed-order sums.
 __global__ __launch_bounds__(256) void k_node_results(DevView v, double *gen, double *dis, double *chg)
@@ -1858,7 +1872,8 @@ __global__ __launch_bounds__(256) void k_node_results(DevView v, double *gen, do
 // DOPF_F_STO_INITIAL_LEVEL)
 void launch_derive_level(const DevView &v, const Plan &p, hipStream_t s)
 {
-    if (v.S > 0) hipLaunchKernelGGL(k_derive_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, p.stoE0 ? sto_e0(v) : nullptr);
+    if (v.S > 0 && p.stoEff) hipLaunchKernelGGL(k_derive_level_eff, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v);
+    else if (v.S > 0) hipLaunchKernelGGL(k_derive_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, p.stoE0 ? sto_e0(v) : nullptr);
 }
 
 // Result.penalty_term (reference src/structures/results.jl:66-70 with sum_up, src/helpers/penalty_terms.jl:1-6): the three
@@ -1934,6 +1949,23 @@ __global__ __launch_bounds__(256) void k_roll_level(DevView v, const double *e0 
     } else {
         e = e0 ? e0[s] : 0.0;
         for (int t = 0; t < k; ++t) e += v.C[(size_t)s * T + t] - v.D[(size_t)s * T + t];
+    }
+    out[s] = e != e ? e : fmin(fmax(e, 0.0), v.sto_emax[s]) + 0.0;
+}
+
+// DOPF_F_STO_EFFICIENCY: the same with k_derive_level_eff's recursion, e0 + cumsum(be C - al D)
+__global__ __launch_bounds__(256) void k_roll_level_eff(DevView v, int k, int from_E, double *out /* S */)
+{
+    const int T = v.T;
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= v.S) return;
+    double e;
+    if (from_E) {
+        e = v.E[(size_t)s * T + (k - 1)];
+    } else {
+        const double al = sto_eff_alpha(v)[s], be = sto_eff_beta(v)[s];
+        e = sto_e0(v)[s];
+        for (int t = 0; t < k; ++t) e += be * v.C[(size_t)s * T + t] - al * v.D[(size_t)s * T + t];
     }
     out[s] = e != e ? e : fmin(fmax(e, 0.0), v.sto_emax[s]) + 0.0;
 }
@@ -2049,7 +2081,8 @@ __global__ void k_roll_status(DevView v, int iteration)
 
 void launch_roll_level(const DevView &v, const Plan &p, int k, bool from_E, double *out, hipStream_t s)
 {
-    if (v.S > 0) hipLaunchKernelGGL(k_roll_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, p.stoE0 ? sto_e0(v) : nullptr, k, from_E ? 1 : 0, out);
+    if (v.S > 0 && p.stoEff) hipLaunchKernelGGL(k_roll_level_eff, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, k, from_E ? 1 : 0, out);
+    else if (v.S > 0) hipLaunchKernelGGL(k_roll_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, p.stoE0 ? sto_e0(v) : nullptr, k, from_E ? 1 : 0, out);
 }
 
 void launch_roll_vecs(const RollVecs &rv, int T, int k, hipStream_t s)

@@ -35,11 +35,12 @@ struct LongCand {
 };
 
 // LV (sto_cold_body): 1 (E0) the first tile is entered at the storage's initial level sto_e0(v)[s] (DOPF_F_STO_INITIAL_LEVEL), not at
-// 0; 2 also classifies timestep T-1 against the terminal band [sto_end_lo, sto_end_hi] and roots it on lo or hi (DOPF_F_STO_TERMINAL_LEVEL)
+// 0; 2 also classifies timestep T-1 against the terminal band [sto_end_lo, sto_end_hi] and roots it on lo or hi (DOPF_F_STO_TERMINAL_LEVEL);
+// 3 (EF) as 2 with the level moving by be C - al D (DOPF_F_STO_EFFICIENCY): x_t, its slope and the kink distances dp / dm change
 template <bool LINES, int LV = 0>
 __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
 {
-    constexpr bool E0 = LV >= 1;
+    constexpr bool E0 = LV >= 1, EF = LV == 3;
     if (v.st->halt) return;
     __shared__ double wmap[3][kLongWaves];          // each wave's composite map of the tile
     __shared__ int wint[3][kLongWaves];             // candidate, last clamped step before it, last clamped step
@@ -62,7 +63,8 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
         double *nuf = v.nu_prev + row;              // the price of each timestep, as the recursion assigns it
         const double tol = 1e-11 * (1.0 + em);
         const double e0 = E0 ? sto_e0(v)[s] : 0.0;   // level before timestep 0
-        const double elo = LV == 2 ? sto_end_lo(v)[s] : 0.0, ehi = LV == 2 ? sto_end_hi(v)[s] : em;    // band of timestep T-1
+        const double al = EF ? sto_eff_alpha(v)[s] : 1.0, be = EF ? sto_eff_beta(v)[s] : 1.0, ial = EF ? 1.0 / al : 1.0, ibe = EF ? 1.0 / be : 1.0;
+        const double elo = LV >= 2 ? sto_end_lo(v)[s] : 0.0, ehi = LV >= 2 ? sto_end_hi(v)[s] : em;    // band of timestep T-1
 
         // the lane's inputs of timesteps tbase .. tbase + NCH - 1 (those > lim: zeros, never evaluated)
         double D0[NCH], C0[NCH], P0[NCH], K0[NCH];
@@ -87,20 +89,24 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
         };
         // x_t(nu) of lane step c = timestep t, as in sto_cold_body (the piece hint of a table starts at 0: it only saves probes)
         auto eval = [&](int c, int t, double nu, double &dd, double &cc, double &s1, double &pc) {
+            const double nD = EF ? al * nu : nu, nC = EF ? be * nu : nu;      // the price as D's and as C's gradient see it
             if (!LINES) {
                 const double q0 = D0[c] - C0[c], theta = P0[c] - gam * q0;
-                box2(a0, gam, ia0, idet0, s20, w * D0[c] - mc - theta - nu, w * C0[c] - mc + theta + nu, pm, dd, cc, s1);
+                box2(a0, gam, ia0, idet0, s20, w * D0[c] - mc - theta - nD, w * C0[c] - mc + theta + nC, pm, dd, cc, s1);
+                if (EF) s1 = eff_slope(a0, gam, ia0, idet0, al, be, pm, dd, cc);
                 pc = theta + gam * (dd - cc);
             } else if (lin[c]) {
                 const double q0 = D0[c] - C0[c], theta = P0[c] - K0[c] * q0;
                 double lia, lidet, ls2;
                 lin_coef(w, iw, K0[c], lia, lidet, ls2);
-                box2(w + K0[c], K0[c], lia, lidet, ls2, w * D0[c] - mc - theta - nu, w * C0[c] - mc + theta + nu, pm, dd, cc, s1);
+                box2(w + K0[c], K0[c], lia, lidet, ls2, w * D0[c] - mc - theta - nD, w * C0[c] - mc + theta + nC, pm, dd, cc, s1);
+                if (EF) s1 = eff_slope(w + K0[c], K0[c], lia, lidet, al, be, pm, dd, cc);
                 pc = theta + K0[c] * (dd - cc);
             } else {
                 const TabRef tb = tab_ref(v, it.node, t);
                 int hint = 0;
-                eval_lines(tb, hint, w, iw, mc, pm, D0[c], C0[c], nu, dd, cc, s1, pc);
+                if constexpr (EF) eval_lines(tb, hint, w, iw, mc, pm, D0[c], C0[c], nu, al, be, dd, cc, s1, pc);
+                else eval_lines(tb, hint, w, iw, mc, pm, D0[c], C0[c], nu, dd, cc, s1, pc);
             }
         };
 
@@ -127,7 +133,8 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
                         eval(c, t, nu, dd, cc, s1, pc);
                         // the four prices at which D or C would leave a bound (flat pieces: sto_cold_body's flat_jump)
                         const double bD = w * D0[c] - mc - pc, bC = mc - w * C0[c] - pc, wp = w * pm;
-                        const double cand[4] = {bD, bD - wp, bC, bC + wp};
+                        // (EF: D's two at b / al, C's two at b / be)
+                        const double cand[4] = {EF ? bD * ial : bD, EF ? (bD - wp) * ial : bD - wp, EF ? bC * ibe : bC, EF ? (bC + wp) * ibe : bC + wp};
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const double d = cand[q] - nu;
@@ -135,7 +142,7 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
                             if (-d > 0.0) dm[c] = fmin(dm[c], -d);
                         }
                     }
-                    Sv[c] = cc - dd;
+                    Sv[c] = EF ? be * cc - al * dd : cc - dd;
                     sg[c] = s1;
                     loc.A += Sv[c];
                     loc.LO = clampd(loc.LO + Sv[c], 0.0, em);
@@ -166,7 +173,7 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
                 } else {
 #pragma unroll
                     for (int c = 0; c < NCH; ++c) {
-                        const unsigned long long b = __ballot(tbase + c <= lim && (LV == 2 && tbase + c == T - 1 ? (Sv[c] < elo - tol || Sv[c] > ehi + tol)
+                        const unsigned long long b = __ballot(tbase + c <= lim && (LV >= 2 && tbase + c == T - 1 ? (Sv[c] < elo - tol || Sv[c] > ehi + tol)
                                                                                                               : (Sv[c] < -tol || Sv[c] > em + tol)));
                         if (b) { const int j = (63 - __clzll(b)) * NCH + c; oW = j > oW ? j : oW; }
                     }
@@ -278,7 +285,7 @@ __global__ __launch_bounds__(kLongBS) void k_sto_long(DevView v)
                     k = -1;
                 } else {
                     vv = vnew;
-                    if (LV == 2 && vnew == T - 1) target = cd.sv < elo ? elo : ehi;
+                    if (LV >= 2 && vnew == T - 1) target = cd.sv < elo ? elo : ehi;
                     else target = cd.sv < 0.0 ? 0.0 : em;
                     const double res = cd.sv - target;
                     lo = -INFINITY; hi = INFINITY;

@@ -129,6 +129,7 @@ const DOPF_F_DEBUG_WIDE_NET = 16777216  # include/dopf.h (tests)
 const DOPF_F_STO_INITIAL_LEVEL = 33554432  # include/dopf.h
 const DOPF_F_STO_TERMINAL_LEVEL = 67108864  # include/dopf.h
 const DOPF_F_GEN_AVAILABILITY = 134217728  # include/dopf.h
+const DOPF_F_STO_EFFICIENCY = 268435456  # include/dopf.h
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -145,7 +146,9 @@ Storages on horizons beyond 512 timesteps (an hourly year: T = 8 760) need `flag
 need `flags = DOPF_F_WIDE_NETWORK` (the wide-network chain; without it the library refuses them). Storages that start a
 horizon from a given level (see `set_initial_levels!`) need `flags = DOPF_F_STO_INITIAL_LEVEL`; storages whose level after the
 last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_TERMINAL_LEVEL`; generators that follow an
-availability profile (see `set_availability!`) need `flags = DOPF_F_GEN_AVAILABILITY`. Flags combine with `|`.
+availability profile (see `set_availability!`) need `flags = DOPF_F_GEN_AVAILABILITY`; storages with charge / discharge
+efficiencies below 1 (see `set_efficiency!`; the reference's `Storage` type, used verbatim, has no such fields) need
+`flags = DOPF_F_STO_EFFICIENCY`. Flags combine with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
@@ -269,6 +272,32 @@ function set_terminal_levels!(admm::ADMM, lo::Union{Nothing, Vector{Float64}}, h
         else
             dopf_check(ccall((:dopf_set_storage_terminal_level, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
                              admm.ctx, pl, ph), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    set_efficiency!(admm, eta_c, eta_d)
+
+The charge and discharge efficiency of each storage (`eta_c[s]`, `eta_d[s]` in `(0, 1]`, in the order of `storages`; `nothing`
+for both = all 1): the level follows `E[t] = E[t-1] + eta_c * C[t] - D[t] / eta_d`. The reference's storages are lossless
+(src/optimization/subproblems.jl:150-156); the ADMM must have been created with `flags = DOPF_F_STO_EFFICIENCY`. Takes effect at
+the next iteration.
+"""
+function set_efficiency!(admm::ADMM, eta_c::Union{Nothing, Vector{Float64}}, eta_d::Union{Nothing, Vector{Float64}})
+    S = length(admm.storages)
+    (eta_c === nothing) == (eta_d === nothing) || error("set_efficiency!: give both eta_c and eta_d, or neither")
+    eta_c === nothing || (length(eta_c) == S && length(eta_d) == S) || error("set_efficiency!: expected $S values each")
+    pc = eta_c === nothing ? Ptr{Cdouble}(C_NULL) : pointer(eta_c)
+    pd = eta_d === nothing ? Ptr{Cdouble}(C_NULL) : pointer(eta_d)
+    GC.@preserve eta_c eta_d begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_storage_efficiency, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                                   admm.multi, pc, pd), admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_storage_efficiency, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                             admm.ctx, pc, pd), admm.ctx)
         end
     end
     return admm

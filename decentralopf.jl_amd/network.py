@@ -12,6 +12,9 @@ lie anywhere in [0, max_level]): a band for that level, e.g. "end at least at X"
 Generator.availability is not in the reference either (one nameplate max_generation for the whole horizon,
 src/optimization/subproblems.jl:26): T per-unit values in [0, 1], the box of P[t] becomes [0, max_generation * availability[t]] —
 a solar or wind profile, or a rolling horizon's renewable forecast (DOPF_F_GEN_AVAILABILITY).
+Storage.charge_efficiency / discharge_efficiency are not in the reference either (whose storages are lossless,
+src/optimization/subproblems.jl:150-156): eta_c, eta_d in (0, 1], the level follows E_t = E_{t-1} + eta_c C_t - D_t / eta_d
+(DOPF_F_STO_EFFICIENCY).
 """
 from __future__ import annotations
 
@@ -49,6 +52,8 @@ class Storage:
     initial_level: float = 0.0      # level before the first timestep, 0 <= initial_level <= max_level (not in the reference)
     terminal_level_min: float = 0.0                 # band of the level after the last timestep (not in the reference)
     terminal_level_max: Optional[float] = None      # (None: max_level)
+    charge_efficiency: float = 1.0                  # eta_c in (0, 1]: the level gains eta_c * C (not in the reference)
+    discharge_efficiency: float = 1.0               # eta_d in (0, 1]: the level loses D / eta_d (not in the reference)
 
 
 @dataclass(eq=False)
@@ -122,6 +127,8 @@ class PackedProblem:
     sto_end_hi: Optional[np.ndarray] = None     # (S,) Storage.terminal_level_max; None = sto_emax
     gen_avail: Optional[np.ndarray] = None      # (K, T) the distinct Generator.availability series; None = no generator has one
     gen_avail_of: Optional[np.ndarray] = None   # (G,) int32 row of gen_avail per generator, -1 = always gen_pmax
+    sto_eta_c: Optional[np.ndarray] = None      # (S,) Storage.charge_efficiency; None = all 1
+    sto_eta_d: Optional[np.ndarray] = None      # (S,) Storage.discharge_efficiency; None = all 1
 
     @property
     def G(self):
@@ -146,7 +153,20 @@ class PackedProblem:
             kw["sto_end_lo"], kw["sto_end_hi"] = self.terminal_band()
         if self.has_availability():      # (engines then run with F_GEN_AVAILABILITY)
             kw["gen_avail"], kw["gen_avail_of"] = self.availability()
+        if self.has_efficiency():      # (engines then run with F_STO_EFFICIENCY)
+            kw["sto_eta"] = self.efficiency()
         return kw
+
+    def efficiency(self):
+        """(eta_c, eta_d), float64 (S,) each, the defaults filled in: all 1."""
+        ec = np.ones(self.S) if self.sto_eta_c is None else np.asarray(self.sto_eta_c, dtype=np.float64)
+        ed = np.ones(self.S) if self.sto_eta_d is None else np.asarray(self.sto_eta_d, dtype=np.float64)
+        return ec, ed
+
+    def has_efficiency(self) -> bool:
+        """Some storage's charge or discharge efficiency differs from 1."""
+        ec, ed = self.efficiency()
+        return bool(np.any(ec != 1.0) or np.any(ed != 1.0))
 
     def availability(self):
         """(profiles (K, T) float64, profile_of (G,) int32): the generators' availability, K = 0 and all -1 when none has one."""
@@ -189,7 +209,9 @@ class PackedProblem:
             sto_end_lo=None if self.sto_end_lo is None else self.sto_end_lo[s0:s1],
             sto_end_hi=None if self.sto_end_hi is None else self.sto_end_hi[s0:s1],
             gen_avail=self.gen_avail,
-            gen_avail_of=None if self.gen_avail_of is None else self.gen_avail_of[g0:g1])
+            gen_avail_of=None if self.gen_avail_of is None else self.gen_avail_of[g0:g1],
+            sto_eta_c=None if self.sto_eta_c is None else self.sto_eta_c[s0:s1],
+            sto_eta_d=None if self.sto_eta_d is None else self.sto_eta_d[s0:s1])
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -235,4 +257,6 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         sto_end_lo=f64(s.terminal_level_min for s in storages),
         sto_end_hi=f64(s.max_level if s.terminal_level_max is None else s.terminal_level_max for s in storages),
         gen_avail=np.asarray(rows, dtype=np.float64).reshape(len(rows), T) if has_avail else None,
-        gen_avail_of=i32(of) if has_avail else None)
+        gen_avail_of=i32(of) if has_avail else None,
+        sto_eta_c=f64(s.charge_efficiency for s in storages),
+        sto_eta_d=f64(s.discharge_efficiency for s in storages))

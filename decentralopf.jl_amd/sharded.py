@@ -114,6 +114,16 @@ class ShardedADMM:
         cut = lambda x: None if x is None else np.asarray(x, dtype=np.float64).reshape(self.problem.S)[s0:s1]
         self.engine.set_terminal_levels(cut(lo), cut(hi))
 
+    def set_efficiency(self, eta_c=None, eta_d=None) -> None:
+        """All storages' charge and discharge efficiencies (problem.S values each, global order; both None = all 1): this rank sets
+        its slice (dopf_set_storage_efficiency). Needs F_STO_EFFICIENCY in the params; every rank calls it between steps."""
+        if eta_c is None and eta_d is None:
+            self.engine.set_efficiency(None, None)
+            return
+        s0, s1 = self.shard.meta["sto_range"]
+        cut = lambda x: None if x is None else np.asarray(x, dtype=np.float64).reshape(self.problem.S)[s0:s1]
+        self.engine.set_efficiency(cut(eta_c), cut(eta_d))
+
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
         max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs

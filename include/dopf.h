@@ -162,6 +162,16 @@ typedef struct dopf_params {
                                   * the reference's 0 <= P <= max_generation (src/optimization/subproblems.jl:26). Nothing else changes: the same
                                   * chain runs, with generator kernels that read the profiles; with every index -1, or every profile all ones, the
                                   * results are those of the context without the flag, bit for bit. */
+#define DOPF_F_STO_EFFICIENCY 268435456 /* storages lose energy on the way in and out: the context keeps a charge efficiency eta_c[s] and a
+                                  * discharge efficiency eta_d[s] per storage, both in (0, 1] (all 1 until dopf_set_storage_efficiency), and every
+                                  * storage body solves with E_t = E_{t-1} + eta_c C_t - D_t / eta_d instead of the reference's lossless balance
+                                  * (src/optimization/subproblems.jl:150-156, src/opf_central_reference.jl:53). The objective, the boxes
+                                  * 0 <= D, C <= pmax, the injection D - C and the proximal terms stay. Works alone and with
+                                  * DOPF_F_STO_INITIAL_LEVEL, DOPF_F_STO_TERMINAL_LEVEL, DOPF_F_GEN_AVAILABILITY, DOPF_F_LONG_HORIZON and
+                                  * DOPF_F_WIDE_NETWORK, on every chain. Runs on the general active-set body with the scan body behind it
+                                  * (as with DOPF_F_STO_GENERAL) and on the long-horizon body; the lean body has no efficiencies. Wherever a level is formed from D and C — dopf_get_primal's E, dopf_set_state,
+                                  * dopf_roll_horizon's new initial level — it is e0 + sum (eta_c C - D / eta_d). dopf_central_solve(_ex) ignores
+                                  * the flag: the device LP is lossless. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -303,6 +313,16 @@ int dopf_set_storage_initial_level(dopf_ctx *ctx, const double *e0);
  * dopf_set_storage_initial_level refuses (DOPF_E_INVALID) an e0 from which the stored band is unreachable. */
 int dopf_set_storage_terminal_level(dopf_ctx *ctx, const double *lo, const double *hi);
 
+/* DOPF_F_STO_EFFICIENCY: the storages' charge and discharge efficiencies, eta_c[S] and eta_d[S] in the caller's order of this
+ * context's storages, every value in (0, 1] (both NULL = all 1, the reference's lossless storage; all 1 until the first call). The
+ * level then follows E_t = E_{t-1} + eta_c C_t - D_t / eta_d, E_{-1} = e0, 0 <= E_t <= max_level (E_{T-1} in the terminal band). Timing
+ * and copies as for dopf_set_storage_initial_level. DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID, naming the entry and storing
+ * nothing, for a NaN, a value <= 0 or > 1, only one of the arrays NULL, or (contexts with DOPF_F_STO_TERMINAL_LEVEL) efficiencies
+ * under which the stored band is unreachable from the stored e0: the reachable end levels are
+ * [max(0, e0 - T pmax / eta_d), min(max_level, e0 + T eta_c pmax)]. In contexts with this flag dopf_set_storage_initial_level and
+ * dopf_set_storage_terminal_level check reachability over that range. */
+int dopf_set_storage_efficiency(dopf_ctx *ctx, const double *eta_c, const double *eta_d);
+
 /* DOPF_F_GEN_AVAILABILITY: the generators' availability. profiles: T x n_profiles, [t + T*k] (agent-major like P), every value in
  * [0, 1]; profile_of: G in the caller's order of this context's generators, -1 = always gen_pmax, else a profile in [0, n_profiles).
  * n_profiles == 0 with both NULL resets every generator to -1. Many generators may share a profile (one solar shape per region): the
@@ -426,6 +446,9 @@ int  dopf_multi_set_storage_initial_level(dopf_multi *m, const double *e0);
 /* dopf_set_storage_terminal_level for all storages, lo[S] and hi[S] in the caller's order (both NULL = the default band): each shard
  * gets its slice. Every shard's values are checked before any is stored. */
 int  dopf_multi_set_storage_terminal_level(dopf_multi *m, const double *lo, const double *hi);
+/* dopf_set_storage_efficiency for all storages, eta_c[S] and eta_d[S] in the caller's order (both NULL = all 1): each shard gets its
+ * slice; every shard is checked before any is stored */
+int  dopf_multi_set_storage_efficiency(dopf_multi *m, const double *eta_c, const double *eta_d);
 /* all G generators in the caller's order; every shard gets the whole table and its slice of profile_of (checked for every shard
  * before any is stored) */
 int dopf_multi_set_generator_availability(dopf_multi *m, int32_t n_profiles, const double *profiles, const int32_t *profile_of);
