@@ -164,6 +164,9 @@ class CApi:
             self._sig("central_solve_ex", C.c_int, [C.POINTER(DopfProblem), C.POINTER(DopfParams), c_double_p, c_double_p, c_double_p,
                                                     C.c_int32, c_double_p, c_int32_p, C.c_double, C.c_int32,
                                                     C.POINTER(DopfCentralResult)] + [c_double_p] * 9)
+            self._sig("central_solve_lossy", C.c_int, [C.POINTER(DopfProblem), C.POINTER(DopfParams)] + [c_double_p] * 5 +
+                                                      [C.c_int32, c_double_p, c_int32_p, C.c_double, C.c_int32,
+                                                       C.POINTER(DopfCentralResult)] + [c_double_p] * 9)
             self._sig("get_node_results", C.c_int, [ctxp, c_double_p, c_double_p, c_double_p])
             self._sig("last_call_ms", C.c_double, [ctxp])
             # consensus sum across GPUs inside the library (RCCL, loaded on first use)
@@ -819,14 +822,16 @@ class MultiEngine:
 
 def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                   sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
-                  sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None) -> dict:
+                  sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None) -> dict:
     """dopf_central_solve: the central reference (src/opf_central_reference.jl) as one LP solved on the GPU by a first-order
     primal-dual method. Arguments as Engine (PackedProblem.engine_kwargs()). Returns objective, gap, iterations and the
     reference script's outputs in Julia shapes: P (G,T), D/C/E (S,T), system_price (T), nodal_price (N,T),
     line_utilization (L,T).
     sto_e0 (S), sto_end_lo / sto_end_hi (S each, both or neither), gen_avail (K x T) / gen_avail_of (G indices in [-1, K)): the
     inputs of the three problem extensions, as Engine takes them; with any of them given the call is dopf_central_solve_ex, which
-    checks them as the setters do (DopfError with the setter's message), and E holds levels that include sto_e0."""
+    checks them as the setters do (DopfError with the setter's message), and E holds levels that include sto_e0.
+    sto_eta = (eta_c, eta_d) (S each, in (0, 1]): the storages' charge and discharge efficiencies, as Engine takes them; whenever it is
+    given (all ones too) the call is dopf_central_solve_lossy, and E = sto_e0 + cumsum(eta_c C - D / eta_d)."""
     N, L, T = int(N), int(L), int(T)
     gen_mc = _f64(gen_mc)
     sto_mc = _f64(sto_mc)
@@ -843,17 +848,22 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     lam, nodal, flow = np.zeros(T), np.zeros(N * T), np.zeros(L * T)
     fu, fl = np.zeros(L * T), np.zeros(L * T)
     outs = (_dp(P), _dp(D), _dp(Cc), _dp(E), _dp(lam), _dp(nodal), _dp(flow), _dp(fu), _dp(fl))
-    if all(a is None for a in (sto_e0, sto_end_lo, sto_end_hi, gen_avail, gen_avail_of)):
+    if all(a is None for a in (sto_e0, sto_end_lo, sto_end_hi, gen_avail, gen_avail_of, sto_eta)):
         entry = "dopf_central_solve"
         rc = api.central_solve(C.byref(prob), C.byref(q), float(tol), int(max_iters), C.byref(res), *outs)
     else:
-        entry = "dopf_central_solve_ex"
         e0 = None if sto_e0 is None else _f64(sto_e0, S)
         lo = None if sto_end_lo is None else _f64(sto_end_lo, S)
         hi = None if sto_end_hi is None else _f64(sto_end_hi, S)
         K, prof, of = _availability_arrays(gen_avail, gen_avail_of, T, G)
-        rc = api.central_solve_ex(C.byref(prob), C.byref(q), _dp(e0), _dp(lo), _dp(hi), K, _dp(prof),
-                                  None if of is None else of.ctypes.data_as(c_int32_p), float(tol), int(max_iters), C.byref(res), *outs)
+        tail = (K, _dp(prof), None if of is None else of.ctypes.data_as(c_int32_p), float(tol), int(max_iters), C.byref(res)) + outs
+        if sto_eta is None:
+            entry = "dopf_central_solve_ex"
+            rc = api.central_solve_ex(C.byref(prob), C.byref(q), _dp(e0), _dp(lo), _dp(hi), *tail)
+        else:
+            entry = "dopf_central_solve_lossy"
+            ec, ed = _f64(sto_eta[0], S), _f64(sto_eta[1], S)
+            rc = api.central_solve_lossy(C.byref(prob), C.byref(q), _dp(e0), _dp(lo), _dp(hi), _dp(ec), _dp(ed), *tail)
     if rc != 0:
         msg = api.last_error(None)
         raise DopfError(f"{entry} failed ({rc}): {msg.decode() if msg else ''}")

@@ -175,20 +175,24 @@ def central_reference(nodes: Sequence[Node], generators: Sequence[Generator], st
 
 def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
                                 lines: Sequence[Line], *, tol: float = 1e-9, max_iters: int = 200000, device: int = -1,
-                                initial_level=None, terminal_level=None, efficiency=None) -> CentralResult:
-    """The same LP solved on the GPU by libdopf_hip (dopf_central_solve / dopf_central_solve_ex: first-order primal-dual method,
-    csrc/kernels_central.hip) — for cases beyond a host LP solver, and as a cross-check that shares no code with HiGHS. The
-    elements' initial levels, terminal bands and availability series are part of the LP, as in central_reference;
-    initial_level / terminal_level override the storages' own, as there. The device LP is lossless: efficiencies other than 1
-    (the argument's, or the storages' own) raise ValueError — use central_reference (HiGHS) for those."""
+                                initial_level=None, terminal_level=None, efficiency=None, lossy: bool = False) -> CentralResult:
+    """The same LP solved on the GPU by libdopf_hip (dopf_central_solve / dopf_central_solve_ex / dopf_central_solve_lossy:
+    first-order primal-dual method, csrc/kernels_central.hip) — for cases beyond a host LP solver, and as a cross-check that shares
+    no code with HiGHS. The elements' initial levels, terminal bands and availability series are part of the LP, as in
+    central_reference; initial_level / terminal_level override the storages' own, as there. Without lossy=True the device LP is
+    lossless: efficiencies other than 1 (the argument's, or the storages' own) raise ValueError. With lossy=True they (the
+    argument's, else the storages' own) are part of the LP (dopf_central_solve_lossy), as in central_reference."""
     from . import _capi
     pp = pack(nodes, generators, storages, lines)
     ec, ed = _efficiencies(pp, efficiency)
-    if np.any(ec != 1.0) or np.any(ed != 1.0):
+    if not lossy and (np.any(ec != 1.0) or np.any(ed != 1.0)):
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve_ex) has no storage efficiencies; "
-                         "use central_reference for a case with charge / discharge efficiencies other than 1")
+                         "pass lossy=True (dopf_central_solve_lossy) or use central_reference for a case with charge / discharge "
+                         "efficiencies other than 1")
     kw = pp.engine_kwargs()
     kw.pop("sto_eta", None)
+    if lossy:
+        kw["sto_eta"] = (ec, ed)
     if initial_level is not None:
         kw["sto_e0"] = np.asarray(initial_level, dtype=np.float64).reshape(pp.S)
     if terminal_level is not None:

@@ -8,6 +8,11 @@
 // dopf_central_solve_ex: the LP with initial levels, terminal bands and availability profiles. Only boxes and right-hand sides change,
 // so the step sizes, the averaging and the restarts below are untouched. The inputs go through the ADMM path's own setters on the
 // temporary context (their checks, their codes, their device arrays); Plan::genAvail / stoLV then select the sweeps' instantiations.
+//
+// dopf_central_solve_lossy: the same with storage efficiencies (DOPF_F_STO_EFFICIENCY on the temporary context, stoLV 3). The level
+// rows' coefficients change, and with them the storages' gradient, step sizes and levels — all inside kc_sto<., 3>, which reads
+// sto_eff_alpha(v) / sto_eff_beta(v). The balance and flow rows act on the injection D - C, whose coefficients stay, so the step-size
+// block below (tauN, sigB, sigF) is that of the lossless LP. dopf_central_solve_ex is this entry without efficiencies.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -49,6 +54,19 @@ extern "C" int dopf_central_solve(const dopf_problem *p, const dopf_params *q, d
                                  system_price, nodal_price, line_utilization, flow_upper_dual, flow_lower_dual);
 }
 
+namespace {
+
+// the body of dopf_central_solve_ex / dopf_central_solve_lossy; entry: the name a refusal's message carries
+int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_params *q, const double *sto_e0_in,
+                       const double *sto_end_lo_in, const double *sto_end_hi_in, const double *sto_eta_c_in, const double *sto_eta_d_in,
+                       int32_t n_profiles, const double *profiles, const int32_t *profile_of,
+                       double tol, int32_t max_iters,
+                       dopf_central_result *res, double *P, double *D, double *C, double *E,
+                       double *system_price, double *nodal_price, double *line_utilization,
+                       double *flow_upper_dual, double *flow_lower_dual);
+
+}  // namespace
+
 extern "C" int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q, const double *sto_e0_in,
                                      const double *sto_end_lo_in, const double *sto_end_hi_in,
                                      int32_t n_profiles, const double *profiles, const int32_t *profile_of,
@@ -57,15 +75,46 @@ extern "C" int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q
                                      double *system_price, double *nodal_price, double *line_utilization,
                                      double *flow_upper_dual, double *flow_lower_dual)
 {
+    return central_solve_impl("dopf_central_solve_ex", p, q, sto_e0_in, sto_end_lo_in, sto_end_hi_in, nullptr, nullptr, n_profiles, profiles,
+                              profile_of, tol, max_iters, res, P, D, C, E, system_price, nodal_price, line_utilization, flow_upper_dual,
+                              flow_lower_dual);
+}
+
+extern "C" int dopf_central_solve_lossy(const dopf_problem *p, const dopf_params *q, const double *sto_e0_in,
+                                        const double *sto_end_lo_in, const double *sto_end_hi_in,
+                                        const double *sto_eta_c_in, const double *sto_eta_d_in,
+                                        int32_t n_profiles, const double *profiles, const int32_t *profile_of,
+                                        double tol, int32_t max_iters,
+                                        dopf_central_result *res, double *P, double *D, double *C, double *E,
+                                        double *system_price, double *nodal_price, double *line_utilization,
+                                        double *flow_upper_dual, double *flow_lower_dual)
+{
+    return central_solve_impl("dopf_central_solve_lossy", p, q, sto_e0_in, sto_end_lo_in, sto_end_hi_in, sto_eta_c_in, sto_eta_d_in, n_profiles,
+                              profiles, profile_of, tol, max_iters, res, P, D, C, E, system_price, nodal_price, line_utilization,
+                              flow_upper_dual, flow_lower_dual);
+}
+
+namespace {
+
+int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_params *q, const double *sto_e0_in,
+                       const double *sto_end_lo_in, const double *sto_end_hi_in, const double *sto_eta_c_in, const double *sto_eta_d_in,
+                       int32_t n_profiles, const double *profiles, const int32_t *profile_of,
+                       double tol, int32_t max_iters,
+                       dopf_central_result *res, double *P, double *D, double *C, double *E,
+                       double *system_price, double *nodal_price, double *line_utilization,
+                       double *flow_upper_dual, double *flow_lower_dual)
+{
     if (!p || !q || !res || !(tol > 0) || max_iters < 1) return fail(nullptr, DOPF_E_INVALID, "bad argument");
     memset(res, 0, sizeof *res);
     dopf_ctx *c = nullptr;
     dopf_params qq = *q;
     qq.stream = nullptr;
-    qq.flags &= ~(DOPF_F_OVERLAP_AGENTS | DOPF_F_STO_EFFICIENCY);     // (the device LP is lossless: no efficiency input, the flag's default)
+    qq.flags &= ~(DOPF_F_OVERLAP_AGENTS | DOPF_F_STO_EFFICIENCY);     // (the caller's efficiency flag is ignored: lossless unless the arrays are given)
     // every input that is given sets its flag (the caller's own flags stay: a flag without its input is that feature's default)
     const bool has_e0 = sto_e0_in != nullptr, has_band = sto_end_lo_in || sto_end_hi_in;
     const bool has_avail = n_profiles != 0 || profiles || profile_of;
+    const bool has_eta = sto_eta_c_in || sto_eta_d_in;
+    if (has_eta) qq.flags |= DOPF_F_STO_EFFICIENCY;
     if (has_e0) qq.flags |= DOPF_F_STO_INITIAL_LEVEL;
     if (has_band) qq.flags |= DOPF_F_STO_TERMINAL_LEVEL;
     if (has_avail) qq.flags |= DOPF_F_GEN_AVAILABILITY;
@@ -74,15 +123,16 @@ extern "C" int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q
     // (callers read dopf_last_error(NULL): the temporary context's message has to outlive it)
     struct Guard { dopf_ctx *c; ~Guard() { keep_error(c); dopf_destroy(c); } } guard{c};
     DeviceGuard dev(c->device);
-    {   // e0 first (the band's reachability is checked from it), then the band, then the profiles; a refusal is the setter's
-        // code, and its message names this entry
+    {   // the efficiencies first (the level setters then check reachability under them), then e0 (the band's reachability is
+        // checked from it), then the band, then the profiles; a refusal is the setter's code, and its message names this entry
         rc = DOPF_OK;
-        if (has_e0) rc = dopf_set_storage_initial_level(c, sto_e0_in);
+        if (has_eta) rc = dopf_set_storage_efficiency(c, sto_eta_c_in, sto_eta_d_in);
+        if (!rc && has_e0) rc = dopf_set_storage_initial_level(c, sto_e0_in);
         if (!rc && has_band) rc = dopf_set_storage_terminal_level(c, sto_end_lo_in, sto_end_hi_in);
         if (!rc && has_avail) rc = dopf_set_generator_availability(c, n_profiles, profiles, profile_of);
         if (rc) {
             const std::string why = c->err;
-            return fail(c, rc, "dopf_central_solve_ex: %s", why.c_str());
+            return fail(c, rc, "%s: %s", entry, why.c_str());
         }
     }
     const DevView &v = c->v;
@@ -165,9 +215,7 @@ extern "C" int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q
         if (done || best.gap < 0.5 * last_gap || navg >= max_avg) {
             if (use_avg) {                  // restart from the average
                 const double sc = 1.0 / navg;
-                central_launch_scale_copy(v.P, cv.aP, sc, GT, c->main);
-                central_launch_scale_copy(v.D, cv.aD, sc, ST, c->main);
-                central_launch_scale_copy(v.C, cv.aC, sc, ST, c->main);
+                central_launch_scale_copy_primal(cv, c->plan, sc, c->main);      // (P, D, C: kept inside their boxes)
                 central_launch_scale_copy(cv.yE, cv.aE, sc, ST, c->main);
                 central_launch_scale_copy(cv.yb, cv.ab, sc, T, c->main);
                 central_launch_scale_copy(cv.yf, cv.af, sc, LT, c->main);
@@ -210,3 +258,5 @@ extern "C" int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q
     }
     return DOPF_OK;
 }
+
+}  // namespace

@@ -300,6 +300,7 @@ void central_launch_iteration(const CentralView &c, const Plan &p, const DevView
 void central_launch_metrics(const CentralView &c, const Plan &p, const DevView &vreduce, const double *XP, const double *XD, const double *XC,
                             const double *XE, const double *yb, const double *yf, double scale, hipStream_t s);
 void central_launch_scale_copy(double *dst, const double *src, double scale, size_t n, hipStream_t s);
+void central_launch_scale_copy_primal(const CentralView &c, const Plan &p, double scale, hipStream_t s);   // P, D, C from their running sums, inside the boxes
 
 // kernels_agents.hip
 void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s);

@@ -19,6 +19,9 @@
 //               K stays — box 0 <= P[g,t] <= cap[g,t] = gen_pmax[g] * f[prof[g]][t] (kc_gen<., AV>); level rows
 //               lb_t - e0 <= sum_{tau <= t} (C - D) <= ub_t - e0 with [lb_t, ub_t] = [0, e_max], [lo, hi] at t = T-1 (kc_sto<., LV>).
 //               Read from the arrays the ADMM kernels read: gen_prof(v), gen_avail_slot(v), sto_e0(v), sto_end_lo/hi(v).
+//               dopf_central_solve_lossy (DOPF_F_STO_EFFICIENCY): the level rows become lb_t - e0 <= sum_{tau <= t} (be C - al D) <= ub_t - e0,
+//               be = eta_c, al = 1 / eta_d from sto_eff_beta(v), sto_eff_alpha(v) — K itself changes, in the storages' columns only
+//               (kc_sto<., 3>); the injection D - C, and with it the balance and flow rows, stay.
 //   outputs     objective, P, D, C, E; system price = -yb (dual(EB) of the reference), nodal price = -(yb + ptdf' yf)
 //               (src/opf_central_reference.jl:66-79).
 #include "dopf_internal.h"
@@ -126,12 +129,19 @@ __global__ __launch_bounds__(512) void kc_gen(CentralView c, const double *X, do
 // ITER: D+, C+ from the gradient c -+ (pi - sum_{tau >= t} yE), levels of the extrapolated point by a prefix sum, the level
 // multipliers' proximal step, running sums. !ITER: metrics of the candidate (scale * XD, XC, XE): cost, reduced-cost term,
 // worst level violation, -sum max(yE, 0) e_max; the levels themselves are written to v.E.
-// LV (Plan::stoLV; 1: DOPF_F_STO_INITIAL_LEVEL, 2: DOPF_F_STO_TERMINAL_LEVEL, sto_e0(v) zeros without the first flag): the level
+// LV (Plan::stoLV; 1: DOPF_F_STO_INITIAL_LEVEL, 2: DOPF_F_STO_TERMINAL_LEVEL, 3: DOPF_F_STO_EFFICIENCY, sto_e0(v) zeros without the first flag): the level
 // prefix sums start from e0 (so v.E holds levels that include it), and the row of timestep t lies in [lb_t, ub_t] = [0, e_max],
 // with LV 2 [lo, hi] at t = T-1 — that one slot, k = (T-1) % K of lane (T-1) / K. The multiplier's proximal step projects onto
 // [lb_t, ub_t] (the row cumsum(C - D) onto [lb_t - e0, ub_t - e0]: the same step, e0 moved to the other side), the violation is
 // measured against it, and the dual objective gets the interval's support function sum max(yE, 0) (ub_t - e0) + min(yE, 0) (lb_t - e0):
 // with lb_t - e0 != 0 both signs of the multiplier count.
+// LV 3 (DOPF_F_STO_EFFICIENCY, dopf_central_solve_lossy): as LV 2 with the level rows e0 + sum_{tau <= t} (be C - al D), be = eta_c =
+// sto_eff_beta(v)[s], al = 1 / eta_d = sto_eff_alpha(v)[s] — the one extension that changes K itself. The reduced costs take the
+// multipliers' suffix sum with these coefficients (rD = mc + pi - al suf, rC = mc - pi + be suf), D and C get step sizes of their own
+// from their columns' sums of |K| (1 + absH + al (T - t), ... + be (T - t)), the row sum of a level row is (al + be) (t + 1), and the
+// levels are prefix sums of be C - al D. The injection D - C, the proximal step, the violation and the support-function term are
+// those of LV 2 (they are written in the level). Only al and be live across the solve: every use is a multiply. With al = be = 1
+// each new operation multiplies by exactly 1 (a fused multiply-add then rounds once, like the addition it stands for): LV 2's bits.
 template <bool ITER, int LV = 0>
 __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, const double *XC, const double *XE, double scale)
 {
@@ -152,7 +162,9 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
         const double mc = v.sto_mc[s], pm = v.sto_pmax[s], em = v.sto_emax[s];
         double e0 = 0.0, elo = 0.0, ehi = em;                 // LV: the level before timestep 0, the band of the last one
         if constexpr (LV >= 1) e0 = sto_e0(v)[s];
-        if constexpr (LV == 2) { elo = sto_end_lo(v)[s]; ehi = sto_end_hi(v)[s]; }
+        if constexpr (LV >= 2) { elo = sto_end_lo(v)[s]; ehi = sto_end_hi(v)[s]; }
+        [[maybe_unused]] double al = 1.0, be = 1.0;           // LV 3: 1 / eta_d, eta_c
+        if constexpr (LV == 3) { al = sto_eff_alpha(v)[s]; be = sto_eff_beta(v)[s]; }
         double yE[KMAX], d0[KMAX], c0[KMAX];
         double ysum = 0.0;
 #pragma unroll
@@ -178,22 +190,33 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
                 const double suf = total - before;            // sum_{tau >= t} yE
                 before += yE[k];
                 const double pi = c.pi[it.node + (size_t)N * t];
-                const double rD = mc + pi - suf, rC = mc - pi + suf;
+                double rD, rC;
+                if constexpr (LV == 3) { rD = mc + pi - al * suf; rC = mc - pi + be * suf; }
+                else { rD = mc + pi - suf; rC = mc - pi + suf; }
                 if (ITER) {
-                    const double tau = 1.0 / ((1.0 + absH + (double)(T - t)) * c.w);
-                    dn[k] = cclamp(d0[k] - tau * rD, 0.0, pm);
-                    cn[k] = cclamp(c0[k] - tau * rC, 0.0, pm);
+                    if constexpr (LV == 3) {
+                        const double tauD = 1.0 / ((1.0 + absH + al * (double)(T - t)) * c.w);
+                        const double tauC = 1.0 / ((1.0 + absH + be * (double)(T - t)) * c.w);
+                        dn[k] = cclamp(d0[k] - tauD * rD, 0.0, pm);
+                        cn[k] = cclamp(c0[k] - tauC * rC, 0.0, pm);
+                    } else {
+                        const double tau = 1.0 / ((1.0 + absH + (double)(T - t)) * c.w);
+                        dn[k] = cclamp(d0[k] - tau * rD, 0.0, pm);
+                        cn[k] = cclamp(c0[k] - tau * rC, 0.0, pm);
+                    }
                     const double bd = 2.0 * dn[k] - d0[k], bc = 2.0 * cn[k] - c0[k];
                     acc[k] += bd - bc;
-                    net += bc - bd;
+                    if constexpr (LV == 3) net += be * bc - al * bd;
+                    else net += bc - bd;
                 } else {
                     acc[k] += d0[k] - c0[k];
-                    net += c0[k] - d0[k];
+                    if constexpr (LV == 3) net += be * c0[k] - al * d0[k];
+                    else net += c0[k] - d0[k];
                     cost += mc * (d0[k] + c0[k]);
                     dpart += (fmin(rD, 0.0) + fmin(rC, 0.0)) * pm;
                     if constexpr (LV == 0) yterm += fmax(yE[k], 0.0) * em;
                     else {
-                        const bool last = LV == 2 && t == T - 1;
+                        const bool last = LV >= 2 && t == T - 1;
                         // (two fused steps, the first the one of LV 0: with e0 = 0 and the default band the same bits)
                         yterm = fma(fmax(yE[k], 0.0), (last ? ehi : em) - e0, yterm);
                         yterm = fma(fmin(yE[k], 0.0), (last ? elo : 0.0) - e0, yterm);
@@ -210,19 +233,26 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
             if (k < K && t < T) {
                 const size_t e = (size_t)s * T + t;
                 if (ITER) {
-                    lev += (2.0 * cn[k] - c0[k]) - (2.0 * dn[k] - d0[k]);
-                    const double sg = c.w / (2.0 * (double)(t + 1));
+                    double sg;
+                    if constexpr (LV == 3) {
+                        lev += be * (2.0 * cn[k] - c0[k]) - al * (2.0 * dn[k] - d0[k]);
+                        sg = c.w / ((al + be) * (double)(t + 1));
+                    } else {
+                        lev += (2.0 * cn[k] - c0[k]) - (2.0 * dn[k] - d0[k]);
+                        sg = c.w / (2.0 * (double)(t + 1));
+                    }
                     const double z = yE[k] + sg * lev;
                     double yn;
-                    if constexpr (LV == 2) { const bool last = t == T - 1; yn = z - sg * cclamp(z / sg, last ? elo : 0.0, last ? ehi : em); }
+                    if constexpr (LV >= 2) { const bool last = t == T - 1; yn = z - sg * cclamp(z / sg, last ? elo : 0.0, last ? ehi : em); }
                     else yn = z - sg * cclamp(z / sg, 0.0, em);
                     v.D[e] = dn[k]; v.C[e] = cn[k];
                     c.yE[e] = yn;
                     c.aD[e] += dn[k]; c.aC[e] += cn[k]; c.aE[e] += yn;
                 } else {
-                    lev += c0[k] - d0[k];
+                    if constexpr (LV == 3) lev += be * c0[k] - al * d0[k];
+                    else lev += c0[k] - d0[k];
                     v.E[e] = lev;
-                    if constexpr (LV == 2) { const bool last = t == T - 1; viol = fmax(viol, fmax((last ? elo : 0.0) - lev, lev - (last ? ehi : em))); }
+                    if constexpr (LV >= 2) { const bool last = t == T - 1; viol = fmax(viol, fmax((last ? elo : 0.0) - lev, lev - (last ? ehi : em))); }
                     else viol = fmax(viol, fmax(-lev, lev - em));
                 }
             }
@@ -340,6 +370,25 @@ __global__ __launch_bounds__(256) void kc_scale_copy(double *dst, const double *
     if (i < n) dst[i] = scale * src[i];
 }
 
+// the primal rows of the restart: dst = min(scale * src, upper end of the box). The running sum of n iterates inside [0, ub], times
+// 1 / n, can round to one ulp above ub; the restart point, and with it the returned point, has to lie in the box like every iterate
+// (inside the box the min is the identity: the bits of kc_scale_copy). GEN: rows of P, ub = gen_pmax[g], AV: cap[g,t] as kc_gen<., true>;
+// !GEN: rows of D or C, ub = sto_pmax[s].
+template <bool GEN, bool AV = false>
+__global__ __launch_bounds__(256) void kc_scale_copy_box(CentralView c, double *dst, const double *src, double scale, size_t n)
+{
+    const DevView &v = c.v;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int T = v.T, a = (int)(i / (size_t)T), t = (int)(i - (size_t)a * T);
+    double ub;
+    if constexpr (GEN) {
+        ub = v.gen_pmax[a];
+        if constexpr (AV) ub = avail_cap(*gen_avail_slot(v), T, gen_prof(v)[a], ub, t);
+    } else ub = v.sto_pmax[a];
+    dst[i] = fmin(scale * src[i], ub);
+}
+
 void central_launch_price(const CentralView &c, const double *yb, const double *yf, double scale, hipStream_t s)
 {
     hipLaunchKernelGGL(kc_price, dim3(c.v.T), dim3(256), (size_t)c.v.L * sizeof(double), s, c, yb, yf, scale);
@@ -358,7 +407,8 @@ template <bool ITER>
 static void launch_sto(const CentralView &c, const Plan &p, const double *XD, const double *XC, const double *XE, double scale, hipStream_t s)
 {
     if (!c.v.nStoItems) return;
-    if (p.stoLV == 2) hipLaunchKernelGGL((kc_sto<ITER, 2>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
+    if (p.stoLV == 3) hipLaunchKernelGGL((kc_sto<ITER, 3>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
+    else if (p.stoLV == 2) hipLaunchKernelGGL((kc_sto<ITER, 2>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
     else if (p.stoLV == 1) hipLaunchKernelGGL((kc_sto<ITER, 1>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
     else hipLaunchKernelGGL((kc_sto<ITER>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
 }
@@ -387,6 +437,20 @@ void central_launch_metrics(const CentralView &c, const Plan &p, const DevView &
 void central_launch_scale_copy(double *dst, const double *src, double scale, size_t n, hipStream_t s)
 {
     if (n) hipLaunchKernelGGL(kc_scale_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, src, scale, n);
+}
+
+// v.P / v.D / v.C = scale * (aP / aD / aC), kept inside their boxes
+void central_launch_scale_copy_primal(const CentralView &c, const Plan &p, double scale, hipStream_t s)
+{
+    const DevView &v = c.v;
+    const size_t GT = (size_t)v.G * v.T, ST = (size_t)v.S * v.T;
+    const dim3 gg((unsigned)((GT + 255) / 256)), gs((unsigned)((ST + 255) / 256));
+    if (GT && p.genAvail) hipLaunchKernelGGL((kc_scale_copy_box<true, true>), gg, dim3(256), 0, s, c, v.P, (const double *)c.aP, scale, GT);
+    else if (GT) hipLaunchKernelGGL((kc_scale_copy_box<true>), gg, dim3(256), 0, s, c, v.P, (const double *)c.aP, scale, GT);
+    if (ST) {
+        hipLaunchKernelGGL((kc_scale_copy_box<false>), gs, dim3(256), 0, s, c, v.D, (const double *)c.aD, scale, ST);
+        hipLaunchKernelGGL((kc_scale_copy_box<false>), gs, dim3(256), 0, s, c, v.C, (const double *)c.aC, scale, ST);
+    }
 }
 
 }  // namespace dopf

@@ -537,7 +537,7 @@ end
 
 """
     central_reference(nodes, generators, storages, lines; tol = 1e-9, max_iters = 200000,
-                      initial_level = nothing, terminal_level = nothing, availability = nothing)
+                      initial_level = nothing, terminal_level = nothing, availability = nothing, efficiency = nothing)
 
 What src/opf_central_reference.jl computes — objective, P, D, C, line utilisation, system price `dual.(EB)`, nodal price —
 from the whole problem as ONE LP, solved on the GPU by libdopf_hip's first-order method (no modelling layer, no licensed solver).
@@ -547,12 +547,16 @@ Returns a NamedTuple; matrices are units x timesteps like `value.(P).data`.
 timestep) and `availability = (profiles, profile_of)` (T x K and G 0-based indices, -1 = always `max_generation`) are the inputs of
 `set_initial_levels!`, `set_terminal_levels!` and `set_availability!`: with any of them the LP of a decentral run that uses them is
 solved (`dopf_central_solve_ex`, same checks as those setters), and `level` includes the initial level.
+
+`efficiency = (eta_c, eta_d)` (S values each in (0, 1]) is the input of `set_efficiency!`: the LP with lossy storages,
+`level = initial_level + cumsum(eta_c C - D / eta_d)`, solved by `dopf_central_solve_lossy` (called only when the keyword is set).
 """
 function central_reference(nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage}, lines::Vector{Line};
                            tol::Float64=1e-9, max_iters::Int=200000, device::Int=-1,
                            initial_level::Union{Nothing, Vector{Float64}}=nothing,
                            terminal_level::Union{Nothing, Tuple{Vector{Float64}, Vector{Float64}}}=nothing,
-                           availability::Union{Nothing, Tuple{Matrix{Float64}, Vector{Cint}}}=nothing)
+                           availability::Union{Nothing, Tuple{Matrix{Float64}, Vector{Cint}}}=nothing,
+                           efficiency::Union{Nothing, Tuple{Vector{Float64}, Vector{Float64}}}=nothing)
     N, L, T = length(nodes), length(lines), length(nodes[1].demand)
     G, S = length(generators), length(storages)
     node_to_id = Dict{Node, Int}(n => i for (i, n) in enumerate(nodes))
@@ -575,8 +579,10 @@ function central_reference(nodes::Vector{Node}, generators::Vector{Generator}, s
         error("central_reference: expected $S terminal bounds each")
     availability === nothing || (size(availability[1], 1) == T && length(availability[2]) == G) ||
         error("central_reference: expected $T rows of profiles and $G profile indices")
-    extended = initial_level !== nothing || terminal_level !== nothing || availability !== nothing
-    GC.@preserve demand ptdf f_max gen_mc gen_pmax gen_node sto_mc sto_pmax sto_emax sto_node initial_level terminal_level availability begin
+    efficiency === nothing || (length(efficiency[1]) == S && length(efficiency[2]) == S) ||
+        error("central_reference: expected $S efficiencies each")
+    extended = initial_level !== nothing || terminal_level !== nothing || availability !== nothing || efficiency !== nothing
+    GC.@preserve demand ptdf f_max gen_mc gen_pmax gen_node sto_mc sto_pmax sto_emax sto_node initial_level terminal_level availability efficiency begin
         prob = Ref(CProblem(N, L, T, G, S, pointer(demand), pointer(ptdf), pointer(f_max), pointer(gen_mc),
                             pointer(gen_pmax), pointer(gen_node), pointer(sto_mc), pointer(sto_pmax),
                             pointer(sto_emax), pointer(sto_node)))
@@ -588,11 +594,20 @@ function central_reference(nodes::Vector{Node}, generators::Vector{Generator}, s
             K = availability === nothing ? 0 : size(availability[1], 2)
             pf = availability === nothing ? Ptr{Cdouble}(C_NULL) : pointer(availability[1])      # T x K column-major = [t + T*k]
             po = availability === nothing ? Ptr{Cint}(C_NULL) : pointer(availability[2])
-            rc = ccall((:dopf_central_solve_ex, DOPF_LIB), Cint,
-                       (Ref{CProblem}, Ref{CParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cint}, Cdouble, Cint,
-                        Ref{CCentralResult}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
-                        Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
-                       prob, par, pe, plo, phi, K, pf, po, tol, max_iters, res, P, D, C, E, lambda, nodal, util, flow_upper, flow_lower)
+            if efficiency !== nothing
+                rc = ccall((:dopf_central_solve_lossy, DOPF_LIB), Cint,
+                           (Ref{CProblem}, Ref{CParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+                            Ptr{Cint}, Cdouble, Cint, Ref{CCentralResult}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                            Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                           prob, par, pe, plo, phi, pointer(efficiency[1]), pointer(efficiency[2]), K, pf, po, tol, max_iters, res, P, D, C, E,
+                           lambda, nodal, util, flow_upper, flow_lower)
+            else
+                rc = ccall((:dopf_central_solve_ex, DOPF_LIB), Cint,
+                           (Ref{CProblem}, Ref{CParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cint}, Cdouble, Cint,
+                            Ref{CCentralResult}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                            Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                           prob, par, pe, plo, phi, K, pf, po, tol, max_iters, res, P, D, C, E, lambda, nodal, util, flow_upper, flow_lower)
+            end
         else
             rc = ccall((:dopf_central_solve, DOPF_LIB), Cint,
                        (Ref{CProblem}, Ref{CParams}, Cdouble, Cint, Ref{CCentralResult}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},

@@ -171,7 +171,7 @@ typedef struct dopf_params {
                                   * DOPF_F_WIDE_NETWORK, on every chain. Runs on the general active-set body with the scan body behind it
                                   * (as with DOPF_F_STO_GENERAL) and on the long-horizon body; the lean body has no efficiencies. Wherever a level is formed from D and C — dopf_get_primal's E, dopf_set_state,
                                   * dopf_roll_horizon's new initial level — it is e0 + sum (eta_c C - D / eta_d). dopf_central_solve(_ex) ignores
-                                  * the flag: the device LP is lossless. */
+                                  * the flag; dopf_central_solve_lossy takes the efficiencies. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -395,6 +395,26 @@ int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q,
                           double *P, double *D, double *C, double *E,
                           double *system_price, double *nodal_price, double *line_utilization,
                           double *flow_upper_dual, double *flow_lower_dual);
+
+/* The same LP with lossy storages: dopf_central_solve_ex's arguments plus the input of DOPF_F_STO_EFFICIENCY, the parity target of a
+ * decentral run that uses it. sto_eta_c[S], sto_eta_d[S] (both or neither, in the caller's agent order, every value in (0, 1]; both NULL
+ * = all 1): the level rows become e0 + sum_{tau<=t} (eta_c C - D / eta_d) in [0, max_level] (in [lo, hi] at the last timestep), and the
+ * E output holds these levels. The injection D - C, the boxes and the objective stay. When the arrays are given the entry sets
+ * DOPF_F_STO_EFFICIENCY on its own context (a DOPF_F_STO_EFFICIENCY bit in q is ignored here too) and calls dopf_set_storage_efficiency
+ * before the other setters, so that the band's reachability from e0 is checked over
+ * [max(0, e0 - T pmax / eta_d), min(max_level, e0 + T eta_c pmax)]. Checks and codes are that setter's (a NaN, a value <= 0 or > 1, only
+ * one array) and, as for dopf_central_solve_ex, the other three's; the message names this entry, and no output is written. With both
+ * arrays NULL this is dopf_central_solve_ex; with both all 1 it returns the same bits. */
+int dopf_central_solve_lossy(const dopf_problem *p, const dopf_params *q,
+                             const double *sto_e0,
+                             const double *sto_end_lo, const double *sto_end_hi,
+                             const double *sto_eta_c, const double *sto_eta_d,
+                             int32_t n_profiles, const double *profiles,
+                             const int32_t *profile_of,
+                             double tol, int32_t max_iters, dopf_central_result *res,
+                             double *P, double *D, double *C, double *E,
+                             double *system_price, double *nodal_price, double *line_utilization,
+                             double *flow_upper_dual, double *flow_lower_dual);
 
 /* ---- consensus sum across GPUs inside the library (RCCL over xGMI, loaded at run time) -------------
  * Replaces nothing in the reference (it has no parallelism); what is distributed is the agent loop of
