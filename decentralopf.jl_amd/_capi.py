@@ -84,6 +84,7 @@ F_STO_INITIAL_LEVEL = 33554432
 F_STO_TERMINAL_LEVEL = 67108864
 F_GEN_AVAILABILITY = 134217728
 F_STO_EFFICIENCY = 268435456
+F_LINE_RATING = 536870912
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -191,6 +192,9 @@ class CApi:
         # storage efficiencies: optional — the oracle backend loads without them (Engine.set_efficiency then refuses)
         self._opt("set_storage_efficiency", C.c_int, [ctxp, c_double_p, c_double_p])
         self._opt("multi_set_storage_efficiency", C.c_int, [ctxp, c_double_p, c_double_p])
+        # line ratings: optional in the same way (Engine.set_line_rating then refuses)
+        self._opt("set_line_rating", C.c_int, [ctxp, c_double_p])
+        self._opt("multi_set_line_rating", C.c_int, [ctxp, c_double_p])
 
     def _opt(self, name, restype, argtypes):
         if hasattr(self.lib, self.prefix + name):
@@ -317,6 +321,28 @@ def _efficiency_params(api: CApi, params: Optional[DopfParams], sto_eta, S: int)
     return q, (ec, ed)
 
 
+def _rating_buffer(rating, L: int, T: int) -> np.ndarray:
+    """An (L, T) table as the C ABI's [l + L*t] buffer."""
+    return _f64(np.asarray(rating, dtype=np.float64).reshape(L, T).T, L * T)
+
+
+def _line_rating_params(api: CApi, params: Optional[DopfParams], line_rating, f_max, L: int, T: int):
+    """(params, rating) for an engine built with line_rating, an (L, T) table: the params with F_LINE_RATING added (a copy), the
+    table as float64 (L, T) — or (params, None) when there is nothing to set (line_rating None, or every column equal to f_max on
+    an API without line ratings)."""
+    if line_rating is None:
+        return params, None
+    r = np.asarray(line_rating, dtype=np.float64).reshape(L, T)
+    if not hasattr(api, "set_line_rating"):
+        if np.any(r != _f64(f_max, L)[:, None]):
+            raise DopfError(f"{api.prefix}*: this API has no line ratings (a rating other than f_max; the reference keeps one "
+                            "max_capacity per line)")
+        return params, None
+    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
+    q.flags |= F_LINE_RATING
+    return q, r.copy()
+
+
 def _availability_arrays(profiles, profile_of, T: int, G: int):
     """(K, profiles as float64 [t + T*k], profile_of as int32 (G,)) from a (K, T) array (or None) and G indices (or None)."""
     if profiles is None and profile_of is None:
@@ -352,13 +378,15 @@ class Engine:
     gen_avail (optional, K x T) / gen_avail_of (optional, G indices in [-1, K)): the generators' availability profiles — sets
     F_GEN_AVAILABILITY and calls dopf_set_generator_availability. sto_eta = (eta_c, eta_d) (optional, S values each): the storages'
     charge and discharge efficiencies — sets F_STO_EFFICIENCY and calls dopf_set_storage_efficiency (before the levels: their
-    reachability checks then see the efficiencies)."""
+    reachability checks then see the efficiencies). line_rating (optional, (L, T)): the lines' limits per timestep — sets
+    F_LINE_RATING and calls dopf_set_line_rating."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
                  mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
-                 sto_eta=None):
+                 sto_eta=None, line_rating=None):
         self.api = api
+        params, rating = _line_rating_params(api, params, line_rating, f_max, int(L), int(T))
         params, eta = _efficiency_params(api, params, sto_eta, _f64(sto_mc).size)
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
         params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
@@ -382,6 +410,7 @@ class Engine:
         self._e0 = None if e0 is None else e0.copy()
         self._band, self._avail = band, avail
         self._eta = eta
+        self._rating = rating
         self._ctx = C.c_void_p()
         args = [C.byref(self._ctx), C.byref(prob), C.byref(self.params)]
         if api.has_mode:
@@ -398,6 +427,8 @@ class Engine:
             self.set_terminal_levels(*band)
         if avail is not None:
             self.set_availability(*avail)
+        if rating is not None:
+            self.set_line_rating(rating)
 
     # -- lifecycle -----------------------------------------------------------------------------
     def close(self):
@@ -499,6 +530,16 @@ class Engine:
         self._chk(self.api.set_storage_efficiency(self._ctx, _dp(a), _dp(b)))
         self._eta = None if a is None and b is None else (a, b)
 
+    def set_line_rating(self, rating=None):
+        """dopf_set_line_rating: the lines' limits per timestep, an (L, T) array of finite values >= 0 (None = f_max in every
+        timestep); needs F_LINE_RATING. P, D, C, the duals, flows and the iteration counter stay; converged becomes False. Takes
+        effect at the next x-update. A backend without the entry: DopfError (unsupported)."""
+        if not hasattr(self.api, "set_line_rating"):
+            raise DopfError(f"{self.api.prefix}*: this API has no line ratings (unsupported)")
+        arr = None if rating is None else _rating_buffer(rating, self.L, self.T)
+        self._chk(self.api.set_line_rating(self._ctx, _dp(arr)))
+        self._rating = None if arr is None else arr.reshape(self.T, self.L).T.copy()
+
     def set_availability(self, profiles=None, profile_of=None):
         """dopf_set_generator_availability: K profiles (K x T, values in [0, 1]) and each generator's profile (G indices, -1 =
         max_generation); both None resets every generator to -1. Needs F_GEN_AVAILABILITY. Takes effect at the next x-update."""
@@ -540,6 +581,8 @@ class Engine:
             # (the initial levels now live on the device only; the host route, which reads self._e0, is never taken with this API)
             self._chk(self.api.roll_horizon(self._ctx, k, _dp(_f64(tail.T, self.N * k))))
             self._keep["demand"] = _f64(np.concatenate([self.demand()[:, k:], tail], axis=1).T)
+            if getattr(self, "_rating", None) is not None:          # (the library moved its table by the same rule)
+                self._rating = np.concatenate([self._rating[:, k:], np.repeat(self._rating[:, -1:], k, axis=1)], axis=1)
             return
         if self.S and not self.params.flags & F_STO_INITIAL_LEVEL:          # (the native entry's refusal, DOPF_E_UNSUPPORTED)
             raise DopfError(f"roll: the storages' levels after {k} steps become the next window's initial levels, which need "
@@ -548,7 +591,7 @@ class Engine:
         lam, mu, rho = self.get_duals()
         _, aU, aK, _, _ = self.get_consensus()
         w = shift_window(k, tail, demand=self.demand(), P=P, D=D, C=Cc, E=E, lam=lam, mu=mu, rho=rho, avg_U=aU, avg_K=aK,
-                         sto_emax=self._keep["sto_emax"])
+                         sto_emax=self._keep["sto_emax"], line_rating=getattr(self, "_rating", None))
         kw = dict(self._keep, demand=_f64(w["demand"].T))
         if self.S:
             kw["sto_e0"] = w["e0"]
@@ -558,6 +601,8 @@ class Engine:
             kw["gen_avail"], kw["gen_avail_of"] = self._avail
         if self._eta is not None:
             kw["sto_eta"] = self._eta
+        if "line_rating" in w:
+            kw["line_rating"] = w["line_rating"]
         new = Engine(self.api, N=self.N, L=self.L, T=self.T, params=self.params, mode=self._mode, **kw)
         new.set_state(P=w["P"], D=w["D"], C_=w["C"], avg_U=w["avg_U"], avg_K=w["avg_K"], lam=w["lam"], mu=w["mu"], rho=w["rho"],
                       iteration=2)
@@ -717,8 +762,9 @@ class MultiEngine:
 
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
-                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None):
+                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None):
         self.api = api
+        params, rating = _line_rating_params(api, params, line_rating, f_max, int(L), int(T))
         params, eta = _efficiency_params(api, params, sto_eta, _f64(sto_mc).size)
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
         params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
@@ -753,6 +799,15 @@ class MultiEngine:
             self.set_terminal_levels(*band)
         if avail is not None:
             self.set_availability(*avail)
+        if rating is not None:
+            self.set_line_rating(rating)
+
+    def set_line_rating(self, rating=None):
+        """dopf_multi_set_line_rating: the (L, T) table for every shard (None = f_max in every timestep)."""
+        if not hasattr(self.api, "multi_set_line_rating"):
+            raise DopfError(f"{self.api.prefix}*: this API has no line ratings (unsupported)")
+        arr = None if rating is None else _rating_buffer(rating, self.L, self.T)
+        self._chk(self.api.multi_set_line_rating(self._m, _dp(arr)))
 
     def set_availability(self, profiles=None, profile_of=None):
         """dopf_multi_set_generator_availability: K profiles (K x T) and all G generators' indices in the caller's order (every
@@ -822,7 +877,8 @@ class MultiEngine:
 
 def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                   sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
-                  sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None) -> dict:
+                  sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
+                  line_rating=None) -> dict:
     """dopf_central_solve: the central reference (src/opf_central_reference.jl) as one LP solved on the GPU by a first-order
     primal-dual method. Arguments as Engine (PackedProblem.engine_kwargs()). Returns objective, gap, iterations and the
     reference script's outputs in Julia shapes: P (G,T), D/C/E (S,T), system_price (T), nodal_price (N,T),
@@ -831,8 +887,12 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     inputs of the three problem extensions, as Engine takes them; with any of them given the call is dopf_central_solve_ex, which
     checks them as the setters do (DopfError with the setter's message), and E holds levels that include sto_e0.
     sto_eta = (eta_c, eta_d) (S each, in (0, 1]): the storages' charge and discharge efficiencies, as Engine takes them; whenever it is
-    given (all ones too) the call is dopf_central_solve_lossy, and E = sto_e0 + cumsum(eta_c C - D / eta_d)."""
+    given (all ones too) the call is dopf_central_solve_lossy, and E = sto_e0 + cumsum(eta_c C - D / eta_d).
+    line_rating: the device LP takes no line ratings; a table other than f_max in every timestep raises DopfError."""
     N, L, T = int(N), int(L), int(T)
+    if line_rating is not None and np.any(np.asarray(line_rating, dtype=np.float64).reshape(L, T) != _f64(f_max, L)[:, None]):
+        raise DopfError("dopf_central_solve*: the device LP takes no line ratings (it solves with f_max in every timestep); use "
+                        "central.solve_central_packed(..., line_rating=) for a case with ratings")
     gen_mc = _f64(gen_mc)
     sto_mc = _f64(sto_mc)
     G, S = gen_mc.size, sto_mc.size

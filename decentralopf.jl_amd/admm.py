@@ -166,6 +166,15 @@ class ADMM:
         flags=F_GEN_AVAILABILITY (set for you when a Generator has an availability series); takes effect at the next iteration."""
         self.engine.set_availability(profiles, profile_of)
 
+    def set_line_rating(self, rating=None) -> None:
+        """The lines' limits per timestep, an (L, T) array in the order of `lines` (None = max_capacity in every timestep):
+        |flow[l,t]| <= rating[l,t]. A rating of 0 pins the flow to 0; it does not take the line out of the PTDF. Not in the
+        reference (one max_capacity per line). Needs flags=F_LINE_RATING (set for you when a Line has a rating); the state and
+        the iteration counter stay, the run is no longer converged; takes effect at the next iteration."""
+        self.engine.set_line_rating(rating)
+        self.packed.line_rating = None if rating is None else np.asarray(rating, dtype=np.float64).reshape(self.packed.L, self.packed.T).copy()
+        self.convergence = Convergence()
+
     # -- a receding horizon ----------------------------------------------------------------------
     def _new_window(self, demand: np.ndarray) -> None:
         """the host's mirrors of the demand follow the engine's, and the recorded history starts anew for the new window"""
@@ -190,8 +199,12 @@ class ADMM:
         """The window advances by k steps (dopf_roll_horizon; the rule is horizon.shift_window's): demand_tail (N, k) is the demand
         of the k new steps, every storage starts from the level it had after step k, the state of the kept steps warm-starts
         the new window and the iteration counter becomes 2. The availability profiles are not moved: set the new window's with
-        set_availability. Not in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62)."""
+        set_availability. A line rating table moves with the window, its last column repeated: set the new window's forecast with
+        set_line_rating. Not in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62)."""
         self.engine.roll(k, demand_tail)
+        if self.packed.line_rating is not None:          # (moved with the window: the old last column behind the kept part)
+            r = np.asarray(self.packed.line_rating, dtype=np.float64)
+            self.packed.line_rating = np.concatenate([r[:, int(k):], np.repeat(r[:, -1:], int(k), axis=1)], axis=1)
         self._new_window(self.engine.demand())
 
     # -- one iteration -------------------------------------------------------------------------

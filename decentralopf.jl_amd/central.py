@@ -56,7 +56,7 @@ def _efficiencies(pp: PackedProblem, efficiency):
 
 
 def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None,
-                         availability=None, efficiency=None) -> CentralResult:
+                         availability=None, efficiency=None, line_rating=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
     tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
     side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference). terminal_level:
@@ -64,7 +64,8 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
     [0, max_level] as in the reference). availability: (profiles (K, T), profile_of (G,)), the upper bound of P[g,t] becomes
     gen_pmax[g] * profiles[profile_of[g], t] (gen_pmax for -1; None: the packed case's profiles, else gen_pmax as in the reference).
     efficiency: (eta_c, eta_d), (S,) each in (0, 1]: the storage-balance rows read E[t] - E[t-1] + D / eta_d - eta_c C = 0 (None:
-    the packed case's efficiencies, else all 1 as in the reference)."""
+    the packed case's efficiencies, else all 1 as in the reference). line_rating: (L, T), the right-hand sides of the two flow rows
+    become rating[l,t] (None: the packed case's table, else f_max in every timestep as in the reference)."""
     from scipy import sparse
     from scipy.optimize import linprog
     N, L, T, G, S = pp.N, pp.L, pp.T, pp.G, pp.S
@@ -123,7 +124,13 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
         lo = sparse.hstack([z(oI), -flow, z(nL), eyeL], format="csr")         # K - ptdf I = f_max
         rUp, rLo = r0, r0 + nL
         Aeq = sparse.vstack([Aeq, up, lo], format="csr")
-        beq += [np.repeat(pp.f_max, T), np.repeat(pp.f_max, T)]
+        if line_rating is None:
+            line_rating = pp.line_rating
+        if line_rating is None:
+            beq += [np.repeat(pp.f_max, T), np.repeat(pp.f_max, T)]
+        else:
+            cap = np.asarray(line_rating, dtype=np.float64).reshape(L, T).reshape(-1)
+            beq += [cap, cap]
     if terminal_level is None and (pp.sto_end_lo is not None or pp.sto_end_hi is not None):
         terminal_level = pp.terminal_band()
     if terminal_level is not None and S > 0:
@@ -184,6 +191,9 @@ def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Gene
     argument's, else the storages' own) are part of the LP (dopf_central_solve_lossy), as in central_reference."""
     from . import _capi
     pp = pack(nodes, generators, storages, lines)
+    if pp.line_rating is not None:
+        raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no line ratings and would "
+                         "solve with max_capacity in every timestep; use central_reference for a case with Line.rating")
     ec, ed = _efficiencies(pp, efficiency)
     if not lossy and (np.any(ec != 1.0) or np.any(ed != 1.0)):
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve_ex) has no storage efficiencies; "

@@ -158,6 +158,22 @@ int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta
     }
     return DOPF_OK;
 }
+
+// dopf_set_line_rating's checks: the flag, every entry finite and >= 0 (NULL: dopf_create's limits in every timestep)
+int check_line_rating(dopf_ctx *c, const double *rating)
+{
+    if (!(c->q.flags & DOPF_F_LINE_RATING))
+        return fail(c, DOPF_E_UNSUPPORTED, "line ratings need DOPF_F_LINE_RATING at dopf_create");
+    if (!rating) return DOPF_OK;
+    const int L = c->v.L, T = c->v.T;
+    for (int t = 0; t < T; ++t)
+        for (int l = 0; l < L; ++l) {
+            const double r = rating[l + (size_t)L * t];
+            if (!std::isfinite(r) || r < 0.0)
+                return fail(c, DOPF_E_INVALID, "dopf_set_line_rating: rating of line l = %d at t = %d is %g (finite and >= 0 wanted)", l, t, r);
+        }
+    return DOPF_OK;
+}
 }  // namespace dopf
 
 namespace {
@@ -790,7 +806,16 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
             for (int n = 0; n < N; ++n) pt[n + (size_t)N * l] = p->ptdf[l + (size_t)L * n];
         TRY(dev_upload(c, &v.ptdfT, pt));
     }
-    TRY(dev_upload(c, &v.fmax, std::vector<double>(p->f_max, p->f_max + L)));
+    if ((q->flags & DOPF_F_LINE_RATING) && L > 0) {
+        // DOPF_F_LINE_RATING: the L x T rating table, every timestep on f_max until the setter, and f_max itself behind it
+        // (line_fmax0); the graphs capture this address once
+        std::vector<double> tab(LT + (size_t)L);
+        for (int t = 0; t <= T; ++t) std::copy(p->f_max, p->f_max + L, tab.begin() + (size_t)L * t);
+        TRY(dev_upload(c, &v.fmax, tab));
+        v.fmax_ld = L;
+    } else {
+        TRY(dev_upload(c, &v.fmax, std::vector<double>(p->f_max, p->f_max + L)));
+    }
     TRY(dev_upload(c, &v.gen_mc, gmc)); TRY(dev_upload(c, &v.gen_pmax, gpm));
     {
         std::vector<double> mp(2 * (size_t)G);
@@ -1367,7 +1392,7 @@ static int agent_result(dopf_ctx *c, int32_t agent, const double *delta_in, doub
     HIPCHK(c, hipMemcpy(beg.data(), is_gen ? v.node_gen_beg : v.node_sto_beg, sizeof(int) * (N + 1), hipMemcpyDeviceToHost));
     int n = 0;
     while (n + 1 < N && row >= beg[n + 1]) ++n;
-    std::vector<double> dl(T), s(T), f((size_t)L * T), aU((size_t)L * T), aK((size_t)L * T), h(L), F(L);
+    std::vector<double> dl(T), s(T), f((size_t)L * T), aU((size_t)L * T), aK((size_t)L * T), h(L), F(v.fmax_ld ? (size_t)L * T : (size_t)L);
     if (delta_in) memcpy(dl.data(), delta_in, sizeof(double) * T);
     else HIPCHK(c, hipMemcpy(dl.data(), (is_gen ? v.dltG : v.dltS) + (size_t)row * T, sizeof(double) * T, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(s.data(), v.s_used, sizeof(double) * T, hipMemcpyDeviceToHost));
@@ -1377,20 +1402,21 @@ static int agent_result(dopf_ctx *c, int32_t agent, const double *delta_in, doub
         HIPCHK(c, hipMemcpy(aU.data(), v.avgU_used, sizeof(double) * LT, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(aK.data(), v.avgK_used, sizeof(double) * LT, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(h.data(), v.ptdf + (size_t)L * n, sizeof(double) * L, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(F.data(), v.fmax, sizeof(double) * L, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(F.data(), v.fmax, sizeof(double) * F.size(), hipMemcpyDeviceToHost));
     }
     const double w2 = 2.0 * v.w_flow, g = v.gamma;
     for (int t = 0; t < T; ++t) {
         double up = 0.0, lo = 0.0;
         for (int l = 0; l < L; ++l) {
             const size_t i = l + (size_t)L * t;
+            const double Fl = F[l + (size_t)v.fmax_ld * t];
             const double fl = f[i] + h[l] * dl[t];
-            const double u = std::max(0.0, (g * aU[i] - w2 * (fl - F[l])) / (w2 + g));
-            const double k = std::max(0.0, (g * aK[i] + w2 * (fl + F[l])) / (w2 + g));
+            const double u = std::max(0.0, (g * aU[i] - w2 * (fl - Fl)) / (w2 + g));
+            const double k = std::max(0.0, (g * aK[i] + w2 * (fl + Fl)) / (w2 + g));
             if (U) U[i] = u;
             if (K) K[i] = k;
-            up += (fl + u - F[l]) * (fl + u - F[l]);                                           // penalty_terms.jl:10-20
-            lo += (k - fl - F[l]) * (k - fl - F[l]);                                           // :23-37
+            up += (fl + u - Fl) * (fl + u - Fl);                                               // penalty_terms.jl:10-20
+            lo += (k - fl - Fl) * (k - fl - Fl);                                               // :23-37
         }
         if (pen) { pen[t] = (s[t] + dl[t]) * (s[t] + dl[t]); pen[T + t] = up; pen[2 * T + t] = lo; }   // :3-7
     }
@@ -1528,13 +1554,39 @@ int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const doubl
     return DOPF_OK;
 }
 
+int dopf_set_line_rating(dopf_ctx *c, const double *rating)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_line_rating(c, rating)) return rc;
+    DevView &v = c->v;
+    const int L = v.L, T = v.T;
+    if (L == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    const size_t LT = (size_t)L * T;
+    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again). NULL:
+    // the limits of dopf_create (kept behind the table) in every timestep. Then the derived state of the consensus step — the
+    // per-(l,t) flags of the slack sums among it — is formed again under the new limits, from the sums the last iteration left in
+    // the consensus buffer (on a communicator: the summed ones, the same on every rank; nothing is summed or exchanged here)
+    if (rating) {
+        HIPCHK(c, hipMemcpyAsync(const_cast<double *>(v.fmax), rating, LT * sizeof(double), hipMemcpyHostToDevice, c->main));
+        HIPCHK(c, hipStreamSynchronize(c->main));           // (the caller's array is the caller's again at return)
+    } else {
+        for (int t = 0; t < T; ++t)
+            HIPCHK(c, hipMemcpyAsync(const_cast<double *>(v.fmax) + (size_t)L * t, line_fmax0(v), L * sizeof(double), hipMemcpyDeviceToDevice, c->main));
+    }
+    launch_line_rating(v, c->plan, c->main);
+    HIPCHK(c, hipGetLastError());
+    c->quiet = false;                      // (flags are formed anew under the new limits)
+    return read_status(c);
+}
+
 // scratch of dopf_set_demand / dopf_roll_horizon, allocated at the first call (freed with the context's other arrays): the moved
-// per-timestep vectors (demand, 2 x lambda, 8 line vectors) | the caller's demand tail (up to N*(T-1)) | the new initial levels (S)
+// per-timestep vectors (demand, 2 x lambda, 8 line vectors, with DOPF_F_LINE_RATING the rating table) | the caller's demand tail (up to N*(T-1)) | the new initial levels (S)
 static int roll_scratch(dopf_ctx *c, double **out)
 {
     if (!c->roll_scratch) {
         const size_t NT = (size_t)c->v.N * c->v.T, LT = (size_t)c->v.L * c->v.T;
-        int rc = dev_alloc(c, &c->roll_scratch, 2 * NT + 2 * (size_t)c->v.T + 8 * LT + (size_t)c->v.S, false);
+        int rc = dev_alloc(c, &c->roll_scratch, 2 * NT + 2 * (size_t)c->v.T + (c->v.fmax_ld ? 9 : 8) * LT + (size_t)c->v.S, false);
         if (rc) return rc;
     }
     *out = c->roll_scratch;
@@ -1586,7 +1638,7 @@ int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
     const size_t NT = (size_t)N * T, LT = (size_t)L * T;
     double *scr = nullptr;
     if (int rc = roll_scratch(c, &scr)) return rc;
-    double *tail_d = scr + NT + 2 * (size_t)T + 8 * LT, *e0_d = tail_d + NT;
+    double *tail_d = scr + NT + 2 * (size_t)T + (v.fmax_ld ? 9 : 8) * LT, *e0_d = tail_d + NT;
     std::vector<double> e0s(S), e0c(S);
     if (S > 0) {
         // the new initial levels first, into scratch; checked as the setters check theirs before anything is overwritten
@@ -1607,6 +1659,7 @@ int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
     add(const_cast<double *>(v.demand), N, tail_d);
     add(v.lam, 1, nullptr); add(v.lam_used, 1, nullptr);
     for (double *p : {v.mu, v.mu_used, v.rho, v.rho_used, v.avgU, v.avgU_used, v.avgK, v.avgK_used}) add(p, L, nullptr);
+    if (v.fmax_ld) add(const_cast<double *>(v.fmax), L, nullptr);          // DOPF_F_LINE_RATING: a derating persists (the old last column)
     launch_roll_vecs(rv, T, k, c->main);
     if (S > 0) {
         HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_e0(v)), e0_d, sizeof(double) * S, hipMemcpyDeviceToDevice, c->main));

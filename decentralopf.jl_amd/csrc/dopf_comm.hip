@@ -735,6 +735,17 @@ int dopf_multi_set_generator_availability(dopf_multi *m, int32_t n_profiles, con
     return DOPF_OK;
 }
 
+int dopf_multi_set_line_rating(dopf_multi *m, const double *rating)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all tables as they were
+        for (int i = 0; i < m->n; ++i) {           // (every shard gets the whole table: replicated state)
+            const int rc = pass == 0 ? check_line_rating(m->ctx[i], rating) : dopf_set_line_rating(m->ctx[i], rating);
+            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
+        }
+    return DOPF_OK;
+}
+
 int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E)
 {
     if (!m) return DOPF_E_INVALID;

@@ -112,11 +112,13 @@ struct DevView {
     int max_iters;
     int keepDeltas;                 // DOPF_F_KEEP_DELTAS: dltG / dltS are written for every timestep (diagnostic getters)
     int rootCap;                    // iteration cap of the scan kernel's root search (80; 2 with DOPF_F_DEBUG_ROOT_CAP)
+    int fmax_ld;                    // the line limit of (l,t) is fmax[l + fmax_ld * t]: 0 (one limit per line), L with DOPF_F_LINE_RATING (the
+                                    // rating table). It sits in what was padding in front of gamma: the view keeps its size and every offset
     double gamma, w_flow, w_prox, eps, mask_thr, invA;
     double nAgents;                 // the divisor of avg_U / avg_K as a number: all ranks' agents (1 / invA without the rounding)
     double cp_ia, cp_idet, cp_s2;   // copper-plate box2 constants with a = w_prox + gamma, b = gamma: 1/a, 1/(a^2 - b^2), 2/(a + b) (host: no divisions per block)
     // problem (read-only)
-    const double *demand, *ptdf, *fmax;
+    const double *demand, *ptdf, *fmax;             // fmax: [l + fmax_ld*t] (DOPF_F_LINE_RATING: the L x T rating table, then dopf_create's L limits)
     const double *ptdfT;                            // [n + N*l]: the transpose, for the price kernel's node-major threads
     const double *gen_mc, *gen_pmax;
     const double2 *gen_mp;                          // [g] {mc, pmax} side by side: one 16-byte load per row (streaming blocks)
@@ -174,6 +176,10 @@ __host__ __device__ inline const double *sto_end_hi(const DevView &v) { return v
 // al = 1 / eta_d and be = eta_c of each storage, sorted order, ones until dopf_set_storage_efficiency. The level moves by be C - al D.
 __host__ __device__ inline const double *sto_eff_alpha(const DevView &v) { return v.sto_emax + 4 * (size_t)v.S; }
 __host__ __device__ inline const double *sto_eff_beta(const DevView &v) { return v.sto_emax + 5 * (size_t)v.S; }
+
+// the line limits dopf_create was given, one per line (what the central reference reads: it takes no ratings). Without
+// DOPF_F_LINE_RATING that is fmax itself; with it they sit behind the L x T table.
+__host__ __device__ inline const double *line_fmax0(const DevView &v) { return v.fmax + (size_t)v.fmax_ld * v.T; }
 
 // DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
 // gen_pmax[g] for k = -1. gen_state has room for both behind its G row states: the G profile indices (sorted order, -1 until
@@ -338,12 +344,15 @@ void launch_derive_level(const DevView &v, const Plan &p, hipStream_t s);   // E
 // dopf_set_demand / dopf_roll_horizon (kernels_consensus.hip). A per-timestep vector [j + stride*t] that moves by k
 // timesteps through the scratch (at off); tail: what follows the kept part (stride*k values), null: the old last timestep
 struct RollVec { double *p; const double *tail; size_t off; int stride; };
-struct RollVecs { RollVec a[11]; double *scratch; int n; };
+struct RollVecs { RollVec a[12]; double *scratch; int n; };
 void launch_roll_level(const DevView &v, const Plan &p, int k, bool from_E, double *out /* S, device */, hipStream_t s);   // clamped level after timestep k - 1
 void launch_roll_vecs(const RollVecs &rv, int T, int k, hipStream_t s);
 // P, D, C moved by k in place (k = 0: left alone), the node sums formed from the rows item by item, status (iteration <= 0: kept)
 // and the derived consensus state as dopf_set_state leaves them
 void launch_roll_state(const DevView &v, const Plan &p, int k, int iteration, hipStream_t s);
+// dopf_set_line_rating: status as dopf_set_demand leaves it, then the consensus step's derived state under the new limits — the
+// per-(l,t) flags, walk_any / tab_skip and the tables the price kernels write — from the sums in cons (no sums are formed or moved)
+void launch_line_rating(const DevView &v, const Plan &p, hipStream_t s);
 void launch_penalty_sums(const DevView &v, double *out /* [3][N][T], device */, hipStream_t s);   // Result.penalty_term, per node
 void launch_node_results(const DevView &v, double *gen, double *dis, double *chg, hipStream_t s);   // [n + N*t] each, device pointers   // consensus -> inj/s/flow/price (no dual step)
 

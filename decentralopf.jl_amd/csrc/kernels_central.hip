@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void kc_dual(CentralView c, const double *yb, 
             }
         }
         const size_t i = l + (size_t)L * t;
-        const double F = v.fmax[l];
+        const double F = line_fmax0(v)[l];      // (no ratings in the central reference: dopf_create's limits)
         if (ITER) {
             const double sg = c.w * c.sigF[l];
             const double z = c.yf[i] + sg * f;

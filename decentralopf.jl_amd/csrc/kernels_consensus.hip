@@ -50,7 +50,7 @@ __device__ __forceinline__ double block_sum256(double x, double *sh)
 __device__ __forceinline__ double line_term(const DevView &v, int l, int t, double h, double dl)
 {
     const double w2 = 2.0 * v.w_flow, g = v.gamma;
-    const double f = v.flow[l + v.L * t] + h * dl, F = v.fmax[l];
+    const double f = v.flow[l + v.L * t] + h * dl, F = v.fmax[l + v.fmax_ld * t];
     const double U = dmax0((g * v.avgU[l + v.L * t] - w2 * (f - F)) / (w2 + g));
     const double K = dmax0((g * v.avgK[l + v.L * t] + w2 * (f + F)) / (w2 + g));
     return w2 * h * ((f + U - F) - (K - f - F));
@@ -92,7 +92,7 @@ __device__ __forceinline__ void build_table(const DevView &v, const int n, const
         for (int u = 0; u < 4; ++u) {
             const int i = base + 64 * u + lane;
             const int l = (i < M2 ? i : 0) >> 1;
-            hh[u] = v.ptdf[l + L * n]; ff[u] = v.flow[l + L * t]; FF[u] = v.fmax[l];
+            hh[u] = v.ptdf[l + L * n]; ff[u] = v.flow[l + L * t]; FF[u] = v.fmax[l + v.fmax_ld * t];
             au[u] = v.avgU[l + L * t]; ak[u] = v.avgK[l + L * t];
         }
 #pragma unroll
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void k_slack(DevView v, const int cap)
             const int p = p0 + 256 * u < np ? p0 + 256 * u : tid;      // (a valid pair; result dropped below)
             const int tt = p / L, l = p - tt * L, t = t0 + tt;
             ls[u] = l; tts[u] = tt;
-            h[u] = v.ptdf[l + L * n]; f[u] = v.flow[l + L * t]; F[u] = v.fmax[l];
+            h[u] = v.ptdf[l + L * n]; f[u] = v.flow[l + L * t]; F[u] = v.fmax[l + v.fmax_ld * t];
             cu[u] = v.avgU[l + L * t]; ck[u] = v.avgK[l + L * t];
         }
 #pragma unroll
@@ -599,7 +599,7 @@ __global__ __launch_bounds__(256) void k_reduce(DevView v)
         double partial = 0.0;
         if (l < L && nbeg < nend) {
             const size_t rem = l + (size_t)L * t;
-            const double f = v.flow[rem], F = v.fmax[l], cu = v.avgU[rem], ck = v.avgK[rem];
+            const double f = v.flow[rem], F = v.fmax[l + v.fmax_ld * t], cu = v.avgU[rem], ck = v.avgK[rem];
             if (!v.walk_flag[rem]) {
                 // every agent of every node has this slack active, or none has: sum_a (aX -+ kap_n d_a) = A aX -+ (w2 inv) sum_n h_n D_n
                 const SlackCase c0 = slack_case(g, w2, inv, 0.0, f, F, cu, ck, 0.0);
@@ -878,7 +878,7 @@ __device__ __forceinline__ void dual_body(const DevView &v, size_t i, double &rl
             const double aU = v.invA * cU[i], aK = v.invA * cK[i];       // results.jl:108-112
             v.avgU[i] = aU;
             v.avgK[i] = aK;
-            const double mo = v.mu[i], ro = v.rho[i], F = v.fmax[l];
+            const double mo = v.mu[i], ro = v.rho[i], F = v.fmax[l + v.fmax_ld * t];
             const double mn = (mo + v.gamma * (f + aU - F)) * (aU <= v.mask_thr ? 1.0 : 0.0);   // :18-25
             const double rn = (ro + v.gamma * (aK - f - F)) * (aK <= v.mask_thr ? 1.0 : 0.0);   // :30-37
             v.mu_used[i] = mo; v.rho_used[i] = ro;
@@ -888,7 +888,7 @@ __device__ __forceinline__ void dual_body(const DevView &v, size_t i, double &rl
         }
         {   // what the next slack sums of (l,t) will need (k_slack / k_reduce)
             const double w2 = 2.0 * v.w_flow, inv = 1.0 / (w2 + v.gamma);
-            const int need = slack_needs_cases(v.gamma, w2, inv, f, v.fmax[l], v.avgU[i], v.avgK[i], v.line_reach[l]) ? 1 : 0;
+            const int need = slack_needs_cases(v.gamma, w2, inv, f, v.fmax[l + v.fmax_ld * t], v.avgU[i], v.avgK[i], v.line_reach[l]) ? 1 : 0;
             v.walk_flag[i] = need;
             if (need) atomicOr(&v.walk_any[t], 1);          // (zeroed by the caller before the sweep; an OR has no order)
         }
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(256) void k_dual_t(DevView v)
                 const double aU = v.invA * cU[i], aK = v.invA * cK[i];          // results.jl:108-112
                 v.avgU[i] = aU;
                 v.avgK[i] = aK;
-                const double mo = v.mu[i], ro = v.rho[i], F = v.fmax[l];
+                const double mo = v.mu[i], ro = v.rho[i], F = v.fmax[l + v.fmax_ld * t];
                 const double mn = (mo + v.gamma * (f + aU - F)) * (aU <= v.mask_thr ? 1.0 : 0.0);   // update_duals.jl:18-25
                 const double rn = (ro + v.gamma * (aK - f - F)) * (aK <= v.mask_thr ? 1.0 : 0.0);   // :30-37
                 v.mu_used[i] = mo; v.rho_used[i] = ro;
@@ -1026,7 +1026,7 @@ __global__ __launch_bounds__(256) void k_dual_t(DevView v)
             }
             // what the next slack sums of (l,t) will need (k_slack / k_reduce; the price kernel ORs them per timestep)
             const double w2 = 2.0 * v.w_flow, inv = 1.0 / (w2 + v.gamma);
-            v.walk_flag[i] = slack_needs_cases(v.gamma, w2, inv, f, v.fmax[l], v.avgU[i], v.avgK[i], v.line_reach[l]) ? 1 : 0;
+            v.walk_flag[i] = slack_needs_cases(v.gamma, w2, inv, f, v.fmax[l + v.fmax_ld * t], v.avgU[i], v.avgK[i], v.line_reach[l]) ? 1 : 0;
         }
     }
     if (UPDATE) {
@@ -1074,7 +1074,7 @@ __global__ __launch_bounds__(256) void k_price_t(DevView v)
         d[l] = x;
         nz |= x != 0.0;
         if (lin) {
-            const double f = v.flow[i], F = v.fmax[l];
+            const double f = v.flow[i], F = v.fmax[l + v.fmax_ld * t];
             const double U0 = dmax0((g * v.avgU[i] - w2 * (f - F)) * inv), K0 = dmax0((g * v.avgK[i] + w2 * (f + F)) * inv);
             Gl[l] = w2 * ((f + U0 - F) - (K0 - f - F));
             Sl[l] = w2 * (2.0 - ((U0 > 0.0 ? 1.0 : 0.0) + (K0 > 0.0 ? 1.0 : 0.0)) * w2 * inv);
@@ -1187,7 +1187,7 @@ __global__ __launch_bounds__(1024) void k_dual_price_t1024(DevView v)
     double f_old = 0.0, aU_old = 0.0, aK_old = 0.0, F = 0.0, cntp = 0.0;
     int wf = 0;
     if (lt || mine) {                            // (in flight while the flows are formed)
-        f_old = v.flow[i]; aU_old = v.avgU[i]; aK_old = v.avgK[i]; F = v.fmax[l];
+        f_old = v.flow[i]; aU_old = v.avgU[i]; aK_old = v.avgK[i]; F = v.fmax[l + v.fmax_ld * t];
     }
     if (mine) {
         wf = (QUIET || v.slackGlobal) ? 0 : v.walk_flag[i];       // (slackGlobal: the host runs this chain only while no line is flagged)
@@ -1898,7 +1898,7 @@ __global__ __launch_bounds__(64) void k_penalty_sums(DevView v, double *out /* [
             double au = 0.0, al = 0.0;
             for (int l = 0; l < L; ++l) {
                 const size_t i = l + (size_t)L * t;
-                const double F = v.fmax[l];
+                const double F = v.fmax[l + v.fmax_ld * t];
                 const double fl = v.flow_used[i] + v.ptdf[l + (size_t)L * n] * dl;
                 const double u = fmax(0.0, (g * v.avgU_used[i] - w2 * (fl - F)) / (w2 + g));
                 const double k = fmax(0.0, (g * v.avgK_used[i] + w2 * (fl + F)) / (w2 + g));
@@ -2102,6 +2102,12 @@ void launch_roll_state(const DevView &v, const Plan &p, int k, int iteration, hi
     if (v.nStoItems > 0) hipLaunchKernelGGL(k_roll_rows<true>, dim3(v.nStoItems), dim3(256), 0, s, v, k);
     hipLaunchKernelGGL(k_roll_node_sums, dim3(v.N * ((v.T + 31) / 32)), dim3(256), 0, s, v);
     hipLaunchKernelGGL(k_roll_status, dim3(1), dim3(64), 0, s, v, iteration);
+    launch_derive(v, p, s, false);
+}
+
+void launch_line_rating(const DevView &v, const Plan &p, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_roll_status, dim3(1), dim3(64), 0, s, v, 0);
     launch_derive(v, p, s, false);
 }
 

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_tables_wide(DevView v)
         for (int u = 0; u < 4; ++u) {
             const int i = base + 256 * u + tid;
             const int l = (i < M2 ? i : 0) >> 1;
-            hh[u] = v.ptdf[l + L * n]; ff[u] = v.flow[l + L * t]; FF[u] = v.fmax[l];
+            hh[u] = v.ptdf[l + L * n]; ff[u] = v.flow[l + L * t]; FF[u] = v.fmax[l + v.fmax_ld * t];
             au[u] = v.avgU[l + L * t]; ak[u] = v.avgK[l + L * t];
         }
         double kvs[4];
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void k_dual_tw(DevView v)
             const double aU = v.invA * cU[i], aK = v.invA * cK[i];          // results.jl:108-112
             v.avgU[i] = aU;
             v.avgK[i] = aK;
-            const double mo = v.mu[i], ro = v.rho[i], F = v.fmax[l];
+            const double mo = v.mu[i], ro = v.rho[i], F = v.fmax[l + v.fmax_ld * t];
             const double mn = (mo + v.gamma * (f + aU - F)) * (aU <= v.mask_thr ? 1.0 : 0.0);   // update_duals.jl:18-25
             const double rn = (ro + v.gamma * (aK - f - F)) * (aK <= v.mask_thr ? 1.0 : 0.0);   // :30-37
             v.mu_used[i] = mo; v.rho_used[i] = ro;
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256) void k_dual_tw(DevView v)
             rr = fabs(rn - ro);
         }
         const double w2 = 2.0 * v.w_flow, inv = 1.0 / (w2 + v.gamma);
-        v.walk_flag[i] = slack_needs_cases(v.gamma, w2, inv, f, v.fmax[l], v.avgU[i], v.avgK[i], v.line_reach[l]) ? 1 : 0;
+        v.walk_flag[i] = slack_needs_cases(v.gamma, w2, inv, f, v.fmax[l + v.fmax_ld * t], v.avgU[i], v.avgK[i], v.line_reach[l]) ? 1 : 0;
     }
     if (UPDATE) {
         __syncthreads();
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void k_price_tw(DevView v)
                 const size_t i = l + (size_t)L * t;
                 d[l - c0] = v.mu[i] - v.rho[i];
                 if (lin) {
-                    const double f = v.flow[i], F = v.fmax[l];
+                    const double f = v.flow[i], F = v.fmax[l + v.fmax_ld * t];
                     const double U0 = dmax0((g * v.avgU[i] - w2 * (f - F)) * inv), K0 = dmax0((g * v.avgK[i] + w2 * (f + F)) * inv);
                     Gl[l - c0] = w2 * ((f + U0 - F) - (K0 - f - F));
                     Sl[l - c0] = w2 * (2.0 - ((U0 > 0.0 ? 1.0 : 0.0) + (K0 > 0.0 ? 1.0 : 0.0)) * w2 * inv);
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256) void k_lines_wide(DevView v)
     double partial = 0.0;
     if (l < L && nbeg < nend) {
         const size_t rem = l + (size_t)L * t;
-        const double f = v.flow[rem], F = v.fmax[l], cu = v.avgU[rem], ck = v.avgK[rem];
+        const double f = v.flow[rem], F = v.fmax[l + v.fmax_ld * t], cu = v.avgU[rem], ck = v.avgK[rem];
         if (!v.walk_flag[rem]) {
             const SlackCase c0 = slack_case(g, w2, inv, 0.0, f, F, cu, ck, 0.0);
             const double a = which ? c0.aK : c0.aU;

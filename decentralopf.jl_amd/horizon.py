@@ -27,7 +27,7 @@ def _zeros(a: np.ndarray, k: int) -> np.ndarray:
 
 
 def shift_window(k: int, demand_tail, *, demand, P, D, C, E, lam, mu, rho, avg_U, avg_K, sto_emax,
-                 used: Optional[dict] = None) -> Dict[str, np.ndarray]:
+                 used: Optional[dict] = None, line_rating=None) -> Dict[str, np.ndarray]:
     """The state of the window that starts k steps later, 1 <= k <= T - 1. Matrices in Julia shape (rows, T): demand (N, T),
     P (G, T), D / C / E (S, T), mu / rho / avg_U / avg_K (L, T); lam (T,); demand_tail (N, k); sto_emax (S,). E is what
     get_primal returned for the old window (it includes that window's initial levels).
@@ -36,7 +36,10 @@ def shift_window(k: int, demand_tail, *, demand, P, D, C, E, lam, mu, rho, avg_U
     (persistence; the next x-update clamps it to the cap); D = C = 0; the duals and avg_U / avg_K = their old last column.
     e0[s] = min(max(E[s, k - 1], 0), max_level[s]): the level the old window reached where the new one starts.
 
-    Returns demand, P, D, C, lam, mu, rho, avg_U, avg_K, e0; with `used` (a dict with any of lam, mu, rho, avg_U, avg_K: what the
+    line_rating (L, T), the table of DOPF_F_LINE_RATING, moves like the duals: behind the kept part its old last column (a derating
+    persists until the caller sets a new table).
+
+    Returns demand, P, D, C, lam, mu, rho, avg_U, avg_K, e0 (and line_rating when given); with `used` (a dict with any of lam, mu, rho, avg_U, avg_K: what the
     last solve read) also a dict `used`, moved like the duals."""
     lam = np.asarray(lam, dtype=np.float64).reshape(-1)
     T = lam.size
@@ -57,6 +60,8 @@ def shift_window(k: int, demand_tail, *, demand, P, D, C, E, lam, mu, rho, avg_U
         lam=_persist(lam, k), mu=_persist(rows(mu), k), rho=_persist(rows(rho), k),
         avg_U=_persist(rows(avg_U), k), avg_K=_persist(rows(avg_K), k),
         e0=np.minimum(np.maximum(_mat(E, S, T)[:, k - 1], 0.0), em) + 0.0)
+    if line_rating is not None:
+        out["line_rating"] = _persist(rows(line_rating), k)
     if used is not None:
         out["used"] = {name: _persist(np.asarray(a, dtype=np.float64).reshape(-1) if name == "lam" else rows(a), k)
                        for name, a in used.items()}

@@ -130,6 +130,7 @@ const DOPF_F_STO_INITIAL_LEVEL = 33554432  # include/dopf.h
 const DOPF_F_STO_TERMINAL_LEVEL = 67108864  # include/dopf.h
 const DOPF_F_GEN_AVAILABILITY = 134217728  # include/dopf.h
 const DOPF_F_STO_EFFICIENCY = 268435456  # include/dopf.h
+const DOPF_F_LINE_RATING = 536870912  # include/dopf.h
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -148,7 +149,8 @@ horizon from a given level (see `set_initial_levels!`) need `flags = DOPF_F_STO_
 last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_TERMINAL_LEVEL`; generators that follow an
 availability profile (see `set_availability!`) need `flags = DOPF_F_GEN_AVAILABILITY`; storages with charge / discharge
 efficiencies below 1 (see `set_efficiency!`; the reference's `Storage` type, used verbatim, has no such fields) need
-`flags = DOPF_F_STO_EFFICIENCY`. Flags combine with `|`.
+`flags = DOPF_F_STO_EFFICIENCY`, and line limits per timestep (see `set_line_rating!`) `flags = DOPF_F_LINE_RATING`. Flags combine
+with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
@@ -272,6 +274,28 @@ function set_terminal_levels!(admm::ADMM, lo::Union{Nothing, Vector{Float64}}, h
         else
             dopf_check(ccall((:dopf_set_storage_terminal_level, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
                              admm.ctx, pl, ph), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    set_line_rating!(admm, rating)
+
+The lines' limits per timestep: `rating[l, t] >= 0`, an `L x T` matrix in the order of `lines` (`nothing` = `max_capacity` in every
+timestep), so that `-rating[l, t] <= flow[l, t] <= rating[l, t]`. The reference keeps one `max_capacity` per line
+(src/optimization/subproblems.jl:77-78); the ADMM must have been created with `flags = DOPF_F_LINE_RATING`. A rating of 0 pins the
+flow to 0; it does not take the line out of the PTDF. The state and the iteration counter stay; takes effect at the next iteration.
+"""
+function set_line_rating!(admm::ADMM, rating::Union{Nothing, Matrix{Float64}})
+    L, T = length(admm.L), length(admm.T)
+    rating === nothing || size(rating) == (L, T) || error("set_line_rating!: expected an $L x $T matrix")
+    pr = rating === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rating)      # (column-major: [l + L*t], the library's layout)
+    GC.@preserve rating begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_line_rating, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi, pr), admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_line_rating, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, pr), admm.ctx)
         end
     end
     return admm

@@ -15,6 +15,8 @@ a solar or wind profile, or a rolling horizon's renewable forecast (DOPF_F_GEN_A
 Storage.charge_efficiency / discharge_efficiency are not in the reference either (whose storages are lossless,
 src/optimization/subproblems.jl:150-156): eta_c, eta_d in (0, 1], the level follows E_t = E_{t-1} + eta_c C_t - D_t / eta_d
 (DOPF_F_STO_EFFICIENCY).
+Line.rating is not in the reference either (one max_capacity per line for the whole horizon, src/optimization/subproblems.jl:77-78):
+T limits >= 0, |flow[t]| <= rating[t] — a planned derating, a dynamic rating or a security margin per timestep (DOPF_F_LINE_RATING).
 """
 from __future__ import annotations
 
@@ -63,6 +65,7 @@ class Line:
     to: Node
     max_capacity: int
     susceptance: int
+    rating: Optional[Sequence[float]] = None        # T limits >= 0, one per timestep; None = max_capacity throughout (not in the reference)
 
 
 def calculate_ptdf(nodes: Sequence[Node], lines: Sequence[Line]) -> np.ndarray:
@@ -129,6 +132,7 @@ class PackedProblem:
     gen_avail_of: Optional[np.ndarray] = None   # (G,) int32 row of gen_avail per generator, -1 = always gen_pmax
     sto_eta_c: Optional[np.ndarray] = None      # (S,) Storage.charge_efficiency; None = all 1
     sto_eta_d: Optional[np.ndarray] = None      # (S,) Storage.discharge_efficiency; None = all 1
+    line_rating: Optional[np.ndarray] = None    # (L, T) Line.rating (max_capacity where a line has none); None = no line has one
 
     @property
     def G(self):
@@ -155,6 +159,8 @@ class PackedProblem:
             kw["gen_avail"], kw["gen_avail_of"] = self.availability()
         if self.has_efficiency():      # (engines then run with F_STO_EFFICIENCY)
             kw["sto_eta"] = self.efficiency()
+        if self.line_rating is not None:      # (engines then run with F_LINE_RATING)
+            kw["line_rating"] = np.asarray(self.line_rating, dtype=np.float64).reshape(self.L, self.T)
         return kw
 
     def efficiency(self):
@@ -211,7 +217,8 @@ class PackedProblem:
             gen_avail=self.gen_avail,
             gen_avail_of=None if self.gen_avail_of is None else self.gen_avail_of[g0:g1],
             sto_eta_c=None if self.sto_eta_c is None else self.sto_eta_c[s0:s1],
-            sto_eta_d=None if self.sto_eta_d is None else self.sto_eta_d[s0:s1])
+            sto_eta_d=None if self.sto_eta_d is None else self.sto_eta_d[s0:s1],
+            line_rating=self.line_rating)
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -241,6 +248,17 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
             rows.append(a)
         of.append(seen[key])
     has_avail = bool(rows)
+    # line ratings: a table only when some line has one (the others keep max_capacity in every timestep)
+    rating = None
+    if any(l.rating is not None for l in lines):
+        rating = np.empty((len(lines), T))
+        for i, l in enumerate(lines):
+            r = np.full(T, float(l.max_capacity)) if l.rating is None else f64(l.rating)
+            if r.shape != (T,):
+                raise ValueError(f"line {l.name}: rating needs {T} values, got {r.size}")
+            if not np.all(np.isfinite(r)) or np.any(r < 0.0):
+                raise ValueError(f"line {l.name}: rating values must be finite and >= 0")
+            rating[i] = r
     return PackedProblem(
         N=len(nodes), L=len(lines), T=T,
         demand=np.asarray([n.demand for n in nodes], dtype=np.float64).reshape(len(nodes), T),
@@ -259,4 +277,5 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         gen_avail=np.asarray(rows, dtype=np.float64).reshape(len(rows), T) if has_avail else None,
         gen_avail_of=i32(of) if has_avail else None,
         sto_eta_c=f64(s.charge_efficiency for s in storages),
-        sto_eta_d=f64(s.discharge_efficiency for s in storages))
+        sto_eta_d=f64(s.discharge_efficiency for s in storages),
+        line_rating=rating)

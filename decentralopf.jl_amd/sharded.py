@@ -124,6 +124,12 @@ class ShardedADMM:
         cut = lambda x: None if x is None else np.asarray(x, dtype=np.float64).reshape(self.problem.S)[s0:s1]
         self.engine.set_efficiency(cut(eta_c), cut(eta_d))
 
+    def set_line_rating(self, rating=None) -> None:
+        """The lines' limits per timestep ((L, T); None = f_max in every timestep): replicated state, so this rank sets the whole
+        table (dopf_set_line_rating; no sums move). Needs F_LINE_RATING in the params; every rank calls it with the same table
+        between the same two steps."""
+        self.engine.set_line_rating(rating)
+
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
         max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs

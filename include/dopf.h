@@ -172,6 +172,16 @@ typedef struct dopf_params {
                                   * (as with DOPF_F_STO_GENERAL) and on the long-horizon body; the lean body has no efficiencies. Wherever a level is formed from D and C — dopf_get_primal's E, dopf_set_state,
                                   * dopf_roll_horizon's new initial level — it is e0 + sum (eta_c C - D / eta_d). dopf_central_solve(_ex) ignores
                                   * the flag; dopf_central_solve_lossy takes the efficiencies. */
+#define DOPF_F_LINE_RATING 536870912 /* the lines follow a rating table: the context keeps a limit rating[l + L*t] per line and timestep
+                                  * (f_max[l] in every timestep until dopf_set_line_rating), and every place that read f_max[l] for timestep t
+                                  * reads rating[l,t]: -rating[l,t] <= flow[l,t] <= rating[l,t] instead of the reference's one max_capacity per
+                                  * line (src/optimization/subproblems.jl:77-78,176-177, src/optimization/update_duals.jl:17-39). Planned
+                                  * deratings, dynamic ratings and security margins that differ between the timesteps of a window
+                                  * are tables. Nothing else changes: the same chain and the same kernels run, the agents see the network
+                                  * through the breakpoint tables as before. With a table whose columns all equal f_max the results are those
+                                  * of the context without the flag, bit for bit, on every chain. dopf_get_agent_slacks, dopf_get_agent_penalty,
+                                  * dopf_get_penalty_sums and dopf_debug_table follow the table; dopf_roll_horizon moves it like mu and rho.
+                                  * dopf_central_solve, _ex and _lossy take no ratings: they solve with f_max, flag or not. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -333,6 +343,21 @@ int dopf_set_storage_efficiency(dopf_ctx *ctx, const double *eta_c, const double
  * array with n_profiles > 0. */
 int dopf_set_generator_availability(dopf_ctx *ctx, int32_t n_profiles, const double *profiles, const int32_t *profile_of);
 
+/* DOPF_F_LINE_RATING: the lines' limits per timestep, rating[l + L*t] (L x T, the layout of mu), every value finite and >= 0; NULL =
+ * f_max[l] of dopf_create in every timestep (also the table until the first call). May be called between any two calls that iterate,
+ * on every single-GPU chain (the wide chain included) and on contexts joined to a communicator or a peer exchange: the table is
+ * replicated state and the call moves no sums, so the rule is dopf_iterate's — every rank calls it with the same table between the
+ * same two iterations (a consensus buffer bound with dopf_bind_consensus must still hold the last summed vector). The values are
+ * copied before the call returns, in order on the context's stream, into the device array the captured iteration graphs read: the
+ * graphs stay valid. Then the state derived from the limits — the per-line flags that choose between the closed-form and the
+ * agent-by-agent slack sums, and the breakpoint tables of the settled timesteps — is formed again under the new table, before the
+ * next x-update. P, D, C, the duals, injections, flows, avg_U / avg_K and the iteration counter are kept; converged becomes 0, halt is
+ * formed again from max_iters and the residual maxima are cleared, as dopf_set_demand does. A rating of 0 pins the flow of that line
+ * and timestep to 0 (as far as the penalty enforces any limit); it does NOT take the line out of the PTDF — an outage that reroutes
+ * flows is a new dopf_problem. DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID, naming l and t and storing nothing, for a NaN, an
+ * Inf or a negative entry. With L == 0 the call returns DOPF_OK and does nothing. */
+int dopf_set_line_rating(dopf_ctx *ctx, const double *rating /* L x T, [l + L*t]; NULL = f_max in every timestep */);
+
 /* ---- a receding horizon: the window's demand and the window itself change in place -------------------------------
  * Replace nothing in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62). Both need no flag, work
  * on every single-GPU chain, keep the captured iteration graphs valid (they write the arrays the graphs read) and return after
@@ -348,7 +373,8 @@ int dopf_set_demand(dopf_ctx *ctx, const double *demand /* N x T, [n + N*t] */);
 /* dopf_roll_horizon: the window advances by k steps, 1 <= k <= T - 1, on the device: the new value at t is the old one at t + k for
  * t < T - k ("kept"); behind it ("tail"): demand = demand_tail, N x k, [n + N*j]; P = the old P[g, T-1] (persistence; the next
  * x-update clamps it to the cap, as for dopf_set_state); D = C = 0; lambda, mu, rho, avg_U, avg_K (and what the last solve read of
- * them) = their old values at T - 1. Each storage's initial level becomes min(max(E[s, k-1], 0), max_level[s]) with E what
+ * them) and, with DOPF_F_LINE_RATING, the rating table = their old values at T - 1 (a derating persists until the caller sets a new
+ * table). Each storage's initial level becomes min(max(E[s, k-1], 0), max_level[s]) with E what
  * dopf_get_primal returns just before the call. The terminal band and the availability table stay as they are: the band now
  * applies to the new window's end, and the caller sets the new window's profiles with dopf_set_generator_availability. Status:
  * iteration = 2, converged = 0, halt from max_iters, residual maxima cleared; the warm-start summaries are reset. By definition the
@@ -367,7 +393,8 @@ int dopf_roll_horizon(dopf_ctx *ctx, int32_t k, const double *demand_tail /* N x
  * Outputs (any may be NULL), layouts as in dopf_get_primal / dopf_get_consensus: P, D, C, E; system_price[T] = dual.(EB);
  * nodal_price[N*T] = lambda + sum_l (dual FlowUpper + dual FlowLower)[l,t] ptdf[l,:]; line_utilization[L*T] = ptdf * I;
  * flow_upper_dual[L*T] = dual.(FlowUpper), flow_lower_dual[L*T] = dual.(FlowLower) (opf_central_reference.jl:71-79: both are
- * d objective / d max_capacity <= 0, non-zero only where that limit binds). */
+ * d objective / d max_capacity <= 0, non-zero only where that limit binds). None of the three entries below takes the rating
+ * table of DOPF_F_LINE_RATING: they solve with f_max in every timestep (a DOPF_F_LINE_RATING bit in q changes nothing). */
 typedef struct dopf_central_result {
     double objective, dual_objective, primal_infeasibility, gap;
     int32_t iterations, converged;
@@ -466,6 +493,8 @@ int  dopf_multi_set_storage_initial_level(dopf_multi *m, const double *e0);
 /* dopf_set_storage_terminal_level for all storages, lo[S] and hi[S] in the caller's order (both NULL = the default band): each shard
  * gets its slice. Every shard's values are checked before any is stored. */
 int  dopf_multi_set_storage_terminal_level(dopf_multi *m, const double *lo, const double *hi);
+/* dopf_set_line_rating on every shard: each gets the whole table (replicated state); every shard is checked before any is stored. */
+int  dopf_multi_set_line_rating(dopf_multi *m, const double *rating /* L x T, [l + L*t]; NULL = f_max */);
 /* dopf_set_storage_efficiency for all storages, eta_c[S] and eta_d[S] in the caller's order (both NULL = all 1): each shard gets its
  * slice; every shard is checked before any is stored */
 int  dopf_multi_set_storage_efficiency(dopf_multi *m, const double *eta_c, const double *eta_d);
