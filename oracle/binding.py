@@ -22,9 +22,10 @@ MODE_LITERAL, MODE_EXACT = 0, 1
 
 
 class OracleApi(_capi.CApi):
-    """features=True also binds the setters of the three problem extensions (storage initial and terminal levels, generator
-    availability), so that Engine(sto_e0=..., sto_end_lo=..., gen_avail=...) and its set_* methods drive them. Without it the API
-    has none of them, as the reference has none, and _capi refuses any non-default value (tests/test_*_abi.py pin that guard)."""
+    """features=True also binds the setters of the five problem extensions (storage initial and terminal levels, generator
+    availability, storage efficiencies, line ratings), so that Engine(sto_e0=..., sto_end_lo=..., gen_avail=..., sto_eta=...,
+    line_rating=...) and its set_* methods drive them. Without it the API has none of them, as the reference has none, and _capi
+    refuses any non-default value (tests/test_*_abi.py pin that guard)."""
 
     def __init__(self, path: str = ORACLE_LIB, features: bool = False):
         super().__init__(path, "oracle_", create_extra=(C.c_int32,))
@@ -37,6 +38,13 @@ class OracleApi(_capi.CApi):
             self._sig("set_storage_initial_level", C.c_int, [ctxp, dp])
             self._sig("set_storage_terminal_level", C.c_int, [ctxp, dp, dp])
             self._sig("set_generator_availability", C.c_int, [ctxp, C.c_int32, dp, ip])
+            self._sig("set_storage_efficiency", C.c_int, [ctxp, dp, dp])
+            self._sig("set_line_rating", C.c_int, [ctxp, dp])
+        else:
+            # CApi binds these two wherever the library exports them; the plain oracle API has neither
+            for name in ("set_storage_efficiency", "set_line_rating"):
+                if hasattr(self, name):
+                    delattr(self, name)
 
 
 def set_threads(engine: _capi.Engine, n: int) -> None:

@@ -373,6 +373,10 @@ struct oracle_ctx {
     double *sto_e0, *sto_lo, *sto_hi;
     double *avail;          /* n_prof x T, [t + T*k] */
     int n_prof, *gen_prof;
+    /* DOPF_F_STO_EFFICIENCY / DOPF_F_LINE_RATING (the defaults until a setter is called: every efficiency 1, fmax[l] in every
+     * column of the table) */
+    double *sto_ec, *sto_ed;
+    double *rating;         /* L x T, [l + L*t] */
     dopf_params q;
     int A_global;
     /* admm.iteration (admm.jl:29), Convergence.all */
@@ -440,6 +444,10 @@ int oracle_create(oracle_ctx **out, const dopf_problem *p, const dopf_params *q,
     c->sto_e0 = dalloc(p->S); c->sto_lo = dalloc(p->S); c->sto_hi = dupd(p->sto_emax, p->S);
     c->gen_prof = (int *)calloc(p->G ? p->G : 1, sizeof(int));
     for (int g = 0; g < p->G; ++g) c->gen_prof[g] = -1;
+    c->sto_ec = dalloc(p->S); c->sto_ed = dalloc(p->S);
+    for (int s = 0; s < p->S; ++s) c->sto_ec[s] = c->sto_ed[s] = 1.0;
+    c->rating = dalloc(LT);
+    for (int t = 0; t < p->T; ++t) for (int l = 0; l < p->L; ++l) c->rating[l + (size_t)p->L * t] = c->fmax[l];
     c->iteration = 1;                                   /* admm.jl:29 */
     c->lam = dalloc(p->T); c->mu = dalloc(LT); c->rho = dalloc(LT);   /* zeros, admm.jl:34-36 */
     c->lam_used = dalloc(p->T); c->mu_used = dalloc(LT); c->rho_used = dalloc(LT);
@@ -467,6 +475,7 @@ void oracle_destroy(oracle_ctx *c)
     free(c->demand); free(c->ptdf); free(c->fmax); free(c->gen_mc); free(c->gen_pmax);
     free(c->sto_mc); free(c->sto_pmax); free(c->sto_emax); free(c->gen_node); free(c->sto_node);
     free(c->sto_e0); free(c->sto_lo); free(c->sto_hi); free(c->avail); free(c->gen_prof);
+    free(c->sto_ec); free(c->sto_ed); free(c->rating);
     free(c->lam); free(c->mu); free(c->rho); free(c->lam_used); free(c->mu_used); free(c->rho_used);
     free(c->P); free(c->D); free(c->C); free(c->E); free(c->agentU); free(c->agentK);
     free(c->ngen); free(c->ndis); free(c->nchg); free(c->inj); free(c->avgU); free(c->avgK);
@@ -508,14 +517,14 @@ static void literal_penalties(const oracle_ctx *c, qp_obj *o, int t, int own, in
         double fl = 0;
         for (int n = 0; n < N; ++n) fl += c->ptdf[l + L * n] * inj_const(c, n, t, own, pg, pd, pc);
         const double h = c->ptdf[l + L * own];
-        /* (sum_n ptdf[l,n] injection[n,t] + U[l,t] - f_max[l])^2, weight 10 */
+        /* (sum_n ptdf[l,n] injection[n,t] + U[l,t] - f_max[l])^2, weight 10 (f_max[l]: rating[l,t] under DOPF_F_LINE_RATING) */
         for (int k = 0; k < nv; ++k) { idx[k] = iv[k]; al[k] = h * av[k]; }
         idx[nv] = iU + l; al[nv] = 1.0;
-        qp_add_sq(o, wf, nv + 1, idx, al, fl - c->fmax[l]);
+        qp_add_sq(o, wf, nv + 1, idx, al, fl - c->rating[l + L * t]);
         /* (K[l,t] - sum_n ptdf[l,n] injection[n,t] - f_max[l])^2, weight 10 */
         for (int k = 0; k < nv; ++k) { idx[k] = iv[k]; al[k] = -h * av[k]; }
         idx[nv] = iK + l; al[nv] = 1.0;
-        qp_add_sq(o, wf, nv + 1, idx, al, -fl - c->fmax[l]);
+        qp_add_sq(o, wf, nv + 1, idx, al, -fl - c->rating[l + L * t]);
         /* (U - avg_U)^2 and (K - avg_K)^2, weight gamma/2 each */
         idx[0] = iU + l; al[0] = 1.0;
         qp_add_sq(o, gamma / 2, 1, idx, al, -c->avgU[l + L * t]);
@@ -590,8 +599,8 @@ static int literal_storage(oracle_ctx *c, int s, double *Dn, double *Cn, double 
         double one = 1.0;
         qp_add_sq(&o, c->q.w_prox / 2, 1, &iD, &one, -pD[t]);       /* :180 */
         qp_add_sq(&o, c->q.w_prox / 2, 1, &iC, &one, -pC[t]);       /* :181 */
-        /* StorageBalance: E[t] == (t == 1 ? e0 : E[t-1]) + C[t] - D[t]   :150-156 (e0 = 0 there) */
-        A[t * n + iE] = 1.0; A[t * n + iC] = -1.0; A[t * n + iD] = 1.0;
+        /* StorageBalance: E[t] == (t == 1 ? e0 : E[t-1]) + eta_c C[t] - D[t] / eta_d   :150-156 (e0 = 0, eta = 1 there) */
+        A[t * n + iE] = 1.0; A[t * n + iC] = -c->sto_ec[s]; A[t * n + iD] = 1.0 / c->sto_ed[s];
         if (t > 0) A[t * n + iE - 1] = -1.0;
         else b[t] = c->sto_e0[s];
     }
@@ -621,13 +630,13 @@ static int literal_storage(oracle_ctx *c, int s, double *Dn, double *Cn, double 
 static double slackU(const oracle_ctx *c, int l, int t, double h, double dlt)
 {
     const double w2 = 2 * c->q.w_flow, g = c->q.gamma;
-    double r = c->f_prev[l + c->L * t] + h * dlt - c->fmax[l];
+    double r = c->f_prev[l + c->L * t] + h * dlt - c->rating[l + c->L * t];
     return dmax(0.0, (g * c->avgU[l + c->L * t] - w2 * r) / (w2 + g));
 }
 static double slackK(const oracle_ctx *c, int l, int t, double h, double dlt)
 {
     const double w2 = 2 * c->q.w_flow, g = c->q.gamma;
-    double qv = c->f_prev[l + c->L * t] + h * dlt + c->fmax[l];
+    double qv = c->f_prev[l + c->L * t] + h * dlt + c->rating[l + c->L * t];
     return dmax(0.0, (g * c->avgK[l + c->L * t] + w2 * qv) / (w2 + g));
 }
 
@@ -642,7 +651,7 @@ static double psi_eval(const oracle_ctx *c, int n, int t, double dlt)
     for (int l = 0; l < L; ++l) {
         const double h = c->ptdf[l + L * n];
         if (fabs(h) < PTDF_NOISE) continue;
-        const double f = c->f_prev[l + L * t] + h * dlt, F = c->fmax[l];
+        const double f = c->f_prev[l + L * t] + h * dlt, F = c->rating[l + L * t];
         v += w2 * h * ((f + slackU(c, l, t, h, dlt) - F) - (slackK(c, l, t, h, dlt) - f - F));
     }
     return v;
@@ -679,7 +688,7 @@ static void build_table(oracle_ctx *c, int n, int t)
     for (int l = 0; l < L; ++l) {
         const double h = c->ptdf[l + L * n];
         if (fabs(h) < PTDF_NOISE) continue;
-        const double f = c->f_prev[l + L * t], F = c->fmax[l];
+        const double f = c->f_prev[l + L * t], F = c->rating[l + L * t];
         beta[m++] = (g * c->avgU[l + L * t] / w2 - f + F) / h;     /* U switches on/off */
         beta[m++] = (-g * c->avgK[l + L * t] / w2 - f - F) / h;    /* K switches on/off */
     }
@@ -727,10 +736,10 @@ static void box2(double a, double b, double rD, double rC, double pm, double *D,
     else { *C = Cf; *D = Df; }
 }
 
-typedef struct { int n, t; double mc, pm, D0, C0, elo, ehi; } sto_step;   /* elo, ehi: the bounds of the level after step t */
+typedef struct { int n, t; double mc, pm, D0, C0, elo, ehi, ec, ed; } sto_step;   /* elo, ehi: the bounds of the level after step t */
 
-/* (D,C)(nu) = argmin over the box of the step-t objective minus nu * (C - D); net charge
- * x = C - D is continuous and nondecreasing in nu. */
+/* (D,C)(nu) = argmin over the box of the step-t objective minus nu * (eta_c C - D / eta_d); net charge
+ * x = eta_c C - D / eta_d is continuous and nondecreasing in nu (eta = 1: x = C - D). */
 static void sto_eval(const oracle_ctx *c, const sto_step *st, double nu, double *D, double *C)
 {
     const size_t M2 = 2 * (size_t)c->L, at = (size_t)st->n + (size_t)c->N * st->t;
@@ -738,15 +747,17 @@ static void sto_eval(const oracle_ctx *c, const sto_step *st, double nu, double 
     const double *slope = c->tb_slope + at * (M2 + 1);
     const int m = c->tb_m[at];
     const double w = c->q.w_prox, q0 = st->D0 - st->C0;
+    const double nuD = nu / st->ed, nuC = nu * st->ec;     /* the level's price as D and as C see it */
     double anchor_b = 0.0, anchor_p = c->tb_psi0[at], sg = slope[0];
     if (m > 0) {
-        /* r(dlt) = dlt - (D(z) - C(z) - q0), z = Psi(dlt) + nu, is increasing: first kink with r >= 0 */
+        /* r(dlt) = dlt - (D(zD) - C(zC) - q0), zD = Psi(dlt) + nu / eta_d, zC = Psi(dlt) + nu eta_c, is increasing: first kink
+         * with r >= 0 */
         int lo = 0, hi = m;
         while (lo < hi) {
             int mid = (lo + hi) / 2;
-            double z = psi[mid] + nu;
-            double Dz = clampd(st->D0 - (st->mc + z) / w, 0.0, st->pm);
-            double Cz = clampd(st->C0 - (st->mc - z) / w, 0.0, st->pm);
+            double zD = psi[mid] + nuD, zC = psi[mid] + nuC;
+            double Dz = clampd(st->D0 - (st->mc + zD) / w, 0.0, st->pm);
+            double Cz = clampd(st->C0 - (st->mc - zC) / w, 0.0, st->pm);
             if (beta[mid] - (Dz - Cz - q0) >= 0.0) hi = mid; else lo = mid + 1;
         }
         const int j = lo, a = j < m ? j : m - 1;
@@ -754,10 +765,10 @@ static void sto_eval(const oracle_ctx *c, const sto_step *st, double nu, double 
     }
     /* on this piece Psi = theta + sg * q with q = D - C */
     const double theta = anchor_p - sg * (anchor_b + q0);
-    box2(w + sg, sg, w * st->D0 - st->mc - theta - nu, w * st->C0 - st->mc + theta + nu, st->pm, D, C);
+    box2(w + sg, sg, w * st->D0 - st->mc - theta - nuD, w * st->C0 - st->mc + theta + nuC, st->pm, D, C);
 }
 
-/* S_k(nu) of the forward recursion F_t = clamp(F_{t-1} + x_t(nu), elo_t, ehi_t), F_{-1} = e0, and the
+/* S_k(nu) of the forward recursion F_t = clamp(F_{t-1} + x_t(nu), elo_t, ehi_t), x_t = eta_c C_t - D_t / eta_d, F_{-1} = e0, and the
  * trajectory; returns the largest index <= k whose unclamped level leaves [elo_t, ehi_t] (or -1). */
 static int sto_scan(const oracle_ctx *c, const sto_step *st, int k, double e0, double nu,
                     double *Dv, double *Cv, double *Fv, double *Sv, double tol)
@@ -766,7 +777,7 @@ static int sto_scan(const oracle_ctx *c, const sto_step *st, int k, double e0, d
     int last = -1;
     for (int t = 0; t <= k; ++t) {
         sto_eval(c, &st[t], nu, &Dv[t], &Cv[t]);
-        double sv = e + (Cv[t] - Dv[t]);
+        double sv = e + (st[t].ec * Cv[t] - Dv[t] / st[t].ed);
         Sv[t] = sv;
         if (sv < st[t].elo - tol || sv > st[t].ehi + tol) last = t;
         e = clampd(sv, st[t].elo, st[t].ehi);
@@ -792,6 +803,7 @@ static int exact_storage(const oracle_ctx *c, int s, double *Dn, double *Cn, dou
         st[t].D0 = c->D[(size_t)T * s + t]; st[t].C0 = c->C[(size_t)T * s + t];
         st[t].elo = t == T - 1 ? c->sto_lo[s] : 0.0;
         st[t].ehi = t == T - 1 ? c->sto_hi[s] : emax;
+        st[t].ec = c->sto_ec[s]; st[t].ed = c->sto_ed[s];
     }
     double nu = 0.0;
     int k = T - 1, rc = 0;
@@ -844,7 +856,7 @@ static int exact_storage(const oracle_ctx *c, int s, double *Dn, double *Cn, dou
         k = v - 1;
     }
     double e = e0;
-    for (int t = 0; t < T; ++t) { e += Cn[t] - Dn[t]; En[t] = e; }
+    for (int t = 0; t < T; ++t) { e += c->sto_ec[s] * Cn[t] - Dn[t] / c->sto_ed[s]; En[t] = e; }
     free(st); free(Dv); free(Cv); free(Fv); free(Sv);
     return rc;
 }
@@ -990,8 +1002,8 @@ int oracle_apply_consensus(oracle_ctx *c)
             for (int n = 0; n < N; ++n) f += c->ptdf[l + L * n] * c->inj[n + N * t];
             c->flow[l + L * t] = f;                                        /* results.jl:114 */
             const double aU = c->avgU[l + L * t], aK = c->avgK[l + L * t];
-            double mn = (c->mu[l + L * t] + gamma * (f + aU - c->fmax[l])) * (aU <= c->q.mask_thr ? 1.0 : 0.0);   /* :18-25 */
-            double rn = (c->rho[l + L * t] + gamma * (aK - f - c->fmax[l])) * (aK <= c->q.mask_thr ? 1.0 : 0.0);  /* :30-37 */
+            double mn = (c->mu[l + L * t] + gamma * (f + aU - c->rating[l + L * t])) * (aU <= c->q.mask_thr ? 1.0 : 0.0);   /* :18-25 */
+            double rn = (c->rho[l + L * t] + gamma * (aK - f - c->rating[l + L * t])) * (aK <= c->q.mask_thr ? 1.0 : 0.0);  /* :30-37 */
             r_m = dmax(r_m, fabs(mn - c->mu[l + L * t]));
             r_r = dmax(r_r, fabs(rn - c->rho[l + L * t]));
             c->mu[l + L * t] = mn;
@@ -1046,14 +1058,14 @@ int oracle_get_duals_used(oracle_ctx *c, double *lambda, double *mu, double *rho
     cpy(lambda, c->lam_used, c->T); cpy(mu, c->mu_used, (size_t)c->L * c->T); cpy(rho, c->rho_used, (size_t)c->L * c->T);
     return DOPF_OK;
 }
-/* ResultStorage.level: E = e0 + cumsum(C - D) from the current e0, in k_derive_level's order */
+/* ResultStorage.level: E = e0 + cumsum(eta_c C - D / eta_d) from the current e0 and efficiencies, in k_derive_level's order */
 static void derive_levels(oracle_ctx *c)
 {
     const int T = c->T;
     for (int s = 0; s < c->S; ++s) {
         double e = c->sto_e0[s];
         for (int t = 0; t < T; ++t) {
-            e += c->C[(size_t)T * s + t] - c->D[(size_t)T * s + t];
+            e += c->sto_ec[s] * c->C[(size_t)T * s + t] - c->D[(size_t)T * s + t] / c->sto_ed[s];
             c->E[(size_t)T * s + t] = e;
         }
     }
@@ -1132,14 +1144,14 @@ int oracle_set_state(oracle_ctx *c, const double *P, const double *D, const doub
 }
 
 /* ------------------------------------------------------------------------------------------ */
-/* the three setters of include/dopf.h: same checks, same refusals, nothing stored on a refusal */
+/* the five setters of include/dopf.h: same checks, same refusals, nothing stored on a refusal  */
 /* ------------------------------------------------------------------------------------------ */
 
-/* the band [lo, hi] meets the end levels reachable from e0 in T steps of at most pm, [max(0, e0 - T pm), min(em, e0 + T pm)] */
-static int band_reachable(double e0, double lo, double hi, double pm, double em, int T)
+/* the band [lo, hi] meets the end levels reachable from e0 in T steps, each of which moves the level by at most eta_c pm up and
+ * pm / eta_d down: [max(0, e0 - T pm / eta_d), min(em, e0 + T eta_c pm)] (the device's order of operations; eta = 1: T pm) */
+static int band_reachable(double e0, double lo, double hi, double pm, double em, int T, double ec, double ed)
 {
-    const double span = (double)T * pm;
-    return lo <= fmin(em, e0 + span) && hi >= dmax(0.0, e0 - span);
+    return lo <= fmin(em, e0 + (double)T * ec * pm) && hi >= dmax(0.0, e0 - (double)T * (1.0 / ed) * pm);
 }
 
 int oracle_set_storage_initial_level(oracle_ctx *c, const double *e0)
@@ -1156,7 +1168,7 @@ int oracle_set_storage_initial_level(oracle_ctx *c, const double *e0)
             snprintf(c->err, sizeof c->err, "initial level of storage %d is %g, outside [0, max_level = %g]", s, x, c->sto_emax[s]);
             return DOPF_E_INVALID;
         }
-        if (band && !band_reachable(x, c->sto_lo[s], c->sto_hi[s], c->sto_pmax[s], c->sto_emax[s], c->T)) {
+        if (band && !band_reachable(x, c->sto_lo[s], c->sto_hi[s], c->sto_pmax[s], c->sto_emax[s], c->T, c->sto_ec[s], c->sto_ed[s])) {
             snprintf(c->err, sizeof c->err, "initial level %g of storage %d leaves its terminal band unreachable", x, s);
             return DOPF_E_INVALID;
         }
@@ -1182,7 +1194,7 @@ int oracle_set_storage_terminal_level(oracle_ctx *c, const double *lo, const dou
             snprintf(c->err, sizeof c->err, "terminal band of storage %d is [%g, %g], not inside [0, max_level = %g] (or empty)", s, l, h, em);
             return DOPF_E_INVALID;
         }
-        if (!band_reachable(c->sto_e0[s], l, h, c->sto_pmax[s], em, c->T)) {
+        if (!band_reachable(c->sto_e0[s], l, h, c->sto_pmax[s], em, c->T, c->sto_ec[s], c->sto_ed[s])) {
             snprintf(c->err, sizeof c->err, "terminal band [%g, %g] of storage %d is unreachable from its initial level %g", l, h, s, c->sto_e0[s]);
             return DOPF_E_INVALID;
         }
@@ -1222,6 +1234,62 @@ int oracle_set_generator_availability(oracle_ctx *c, int32_t K, const double *pr
     c->avail = tab;
     c->n_prof = K;
     for (int g = 0; g < G; ++g) c->gen_prof[g] = profile_of ? profile_of[g] : -1;
+    return DOPF_OK;
+}
+
+/* dopf_set_storage_efficiency: both arrays or neither (NULL: all 1), every value in (0, 1]; with DOPF_F_STO_TERMINAL_LEVEL the
+ * stored band must stay reachable from the stored e0 under the new pair */
+int oracle_set_storage_efficiency(oracle_ctx *c, const double *eta_c, const double *eta_d)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (!(c->q.flags & DOPF_F_STO_EFFICIENCY)) {
+        snprintf(c->err, sizeof c->err, "storage efficiencies need DOPF_F_STO_EFFICIENCY at create");
+        return DOPF_E_UNSUPPORTED;
+    }
+    if (!eta_c != !eta_d) {
+        snprintf(c->err, sizeof c->err, "storage efficiencies: eta_c and eta_d must both be given or both be NULL");
+        return DOPF_E_INVALID;
+    }
+    const int band = (c->q.flags & DOPF_F_STO_TERMINAL_LEVEL) != 0;
+    for (int s = 0; eta_c && s < c->S; ++s) {
+        const double ec = eta_c[s], ed = eta_d[s];
+        if (!(ec > 0.0 && ec <= 1.0) || !(ed > 0.0 && ed <= 1.0)) {
+            snprintf(c->err, sizeof c->err, "eta_c[%d] = %g, eta_d[%d] = %g: both must lie in (0, 1]", s, ec, s, ed);
+            return DOPF_E_INVALID;
+        }
+        if (band && !band_reachable(c->sto_e0[s], c->sto_lo[s], c->sto_hi[s], c->sto_pmax[s], c->sto_emax[s], c->T, ec, ed)) {
+            snprintf(c->err, sizeof c->err, "efficiencies eta_c = %g, eta_d = %g leave the terminal band [%g, %g] of storage %d unreachable "
+                     "from its initial level %g", ec, ed, c->sto_lo[s], c->sto_hi[s], s, c->sto_e0[s]);
+            return DOPF_E_INVALID;
+        }
+    }
+    for (int s = 0; s < c->S; ++s) {
+        c->sto_ec[s] = eta_c ? eta_c[s] : 1.0;
+        c->sto_ed[s] = eta_d ? eta_d[s] : 1.0;
+    }
+    return DOPF_OK;
+}
+
+/* dopf_set_line_rating: every entry finite and >= 0 (NULL: f_max[l] in every timestep); converged becomes false */
+int oracle_set_line_rating(oracle_ctx *c, const double *rating)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (!(c->q.flags & DOPF_F_LINE_RATING)) {
+        snprintf(c->err, sizeof c->err, "line ratings need DOPF_F_LINE_RATING at create");
+        return DOPF_E_UNSUPPORTED;
+    }
+    const int L = c->L, T = c->T;
+    for (int t = 0; rating && t < T; ++t)
+        for (int l = 0; l < L; ++l) {
+            const double r = rating[l + (size_t)L * t];
+            if (!isfinite(r) || r < 0.0) {
+                snprintf(c->err, sizeof c->err, "rating of line l = %d at t = %d is %g (finite and >= 0 wanted)", l, t, r);
+                return DOPF_E_INVALID;
+            }
+        }
+    for (int t = 0; t < T; ++t)
+        for (int l = 0; l < L; ++l) c->rating[l + (size_t)L * t] = rating ? rating[l + (size_t)L * t] + 0.0 : c->fmax[l];
+    c->converged = 0;
     return DOPF_OK;
 }
 

@@ -23,6 +23,12 @@
  *       timed CPU baseline. It is pinned by the golden files AND by the literal mode.
  *
  * The API mirrors include/dopf.h one to one (prefix oracle_ instead of dopf_), host memory only.
+ *
+ * Beyond the reference, both modes carry the five problem extensions of include/dopf.h (storage initial levels, terminal bands,
+ * generator availability, storage efficiencies, line ratings per timestep): the literal mode as the rows, bounds and right-hand
+ * sides they are in the QP, the exact mode as the device derives them, so the literal mode pins the exact mode
+ * (tests/test_oracle_features.py, tests/test_oracle_lossy_rated.py) and the exact mode pins every HIP chain
+ * (tests/test_gpu_feature_parity.py, tests/test_gpu_lossy_rated_parity.py). At their defaults none of them changes a bit.
  */
 #ifndef DOPF_ORACLE_H
 #define DOPF_ORACLE_H
@@ -68,6 +74,16 @@ int oracle_set_state(oracle_ctx *ctx, const double *P, const double *D, const do
 int oracle_set_storage_initial_level(oracle_ctx *ctx, const double *e0);
 int oracle_set_storage_terminal_level(oracle_ctx *ctx, const double *lo, const double *hi);
 int oracle_set_generator_availability(oracle_ctx *ctx, int32_t n_profiles, const double *profiles, const int32_t *profile_of);
+/* DOPF_F_STO_EFFICIENCY, DOPF_F_LINE_RATING: again the setters of include/dopf.h (same signatures, checks and refusals, nothing
+ * stored on a refusal, callable between any two iterations; defaults: every efficiency 1, f_max[l] in every timestep). With
+ * DOPF_F_STO_TERMINAL_LEVEL all three level setters check reachability over [max(0, e0 - T pmax / eta_d), min(emax, e0 + T eta_c pmax)].
+ * Literal mode: the storage-balance row reads E[t] - E[t-1] - eta_c C[t] + D[t] / eta_d = (t == 0 ? e0 : 0), and the two flow
+ * penalties take rating[l + L*t] where they took f_max[l]; nothing else in the QP changes. Exact mode: the level's price nu enters
+ * the step problem as nu / eta_d on the D side and nu eta_c on the C side, the recursion accumulates eta_c C - D / eta_d
+ * (DESIGN.md section 5m), and the slacks, the breakpoint tables and the dual, flag and mask step read rating[l + L*t]. With both
+ * flags absent, or present at their defaults, every result of both modes keeps its bits. */
+int oracle_set_storage_efficiency(oracle_ctx *ctx, const double *eta_c, const double *eta_d);
+int oracle_set_line_rating(oracle_ctx *ctx, const double *rating /* L*T, [l + L*t] */);
 
 /* Per-agent slack matrices of the last solve (ResultGenerator.U/K, ResultStorage.U/K,
  * src/structures/results.jl:1-17); agent index: generators 0..G-1 then storages G..G+S-1. */

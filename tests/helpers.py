@@ -227,3 +227,46 @@ class Features:
             e.set_terminal_levels(*self.band)
         if self.prof is not None:
             e.set_availability(*self.prof)
+
+
+class LossyRated(Features):
+    """Features with the two further inputs: one draw carries storage efficiencies (helpers_efficiency.draw_eta: lossy storages with
+    a few at (1, 1) among them) and a rating table (helpers_line_rating.draw_table: f_max times 0.3, 0.6, 1 or 1.5 per line and
+    timestep; zero: the entry of line 0 at t = 0 is exactly 0) beside e0, band and profiles. The band is drawn over the levels
+    reachable under the efficiencies (helpers_efficiency.draw_band_eff), so every setter accepts the draw."""
+
+    def __init__(self, pp, e0kind, bandkind, profkind, seed, eta=True, table=True, zero=False):
+        from helpers_efficiency import draw_band_eff, draw_eta
+        from helpers_line_rating import draw_table
+        rng = np.random.default_rng(seed)
+        self.S, self.emax, self.f_max, self.T = pp.S, pp.sto_emax.copy(), pp.f_max.copy(), pp.T
+        self.eta = draw_eta(pp.S, rng) if eta else None
+        ec, ed = self.eta if eta else (np.ones(pp.S), np.ones(pp.S))
+        self.e0 = draw_e0(pp, e0kind, rng) if e0kind else None
+        self.band = draw_band_eff(pp, self.e0 if self.e0 is not None else np.zeros(pp.S), ec, ed, bandkind, rng) if bandkind else None
+        self.prof = draw_profiles(pp, profkind, rng) if profkind else None
+        self.rating = draw_table(pp, seed) if table else None
+        if zero and table and pp.L:
+            self.rating[0, 0] = 0.0
+
+    @property
+    def flags(self):
+        return (Features.flags.fget(self) | (_capi.F_STO_EFFICIENCY if self.eta is not None else 0)
+                | (_capi.F_LINE_RATING if self.rating is not None else 0))
+
+    def apply(self, e):
+        if self.band is not None:
+            e.set_terminal_levels()             # the default band is reachable under any efficiencies and from any e0
+        if self.eta is not None:
+            e.set_efficiency(*self.eta)
+        Features.apply(self, e)
+        if self.rating is not None:
+            e.set_line_rating(self.rating)
+
+    # what the certificate of helpers_efficiency takes, with the defaults filled in
+    def cert_inputs(self):
+        ec, ed = self.eta if self.eta is not None else (np.ones(self.S), np.ones(self.S))
+        e0 = self.e0 if self.e0 is not None else np.zeros(self.S)
+        lo, hi = self.band if self.band is not None else (np.zeros(self.S), self.emax)
+        F = self.rating if self.rating is not None else np.repeat(self.f_max[:, None], self.T, axis=1)
+        return e0, lo, hi, ec, ed, F

@@ -27,9 +27,16 @@ def draw_eta(S, rng):
 
 
 def draw_band_eff(pp, e0, eta_c, eta_d, kind, rng):
-    """helpers.draw_band's kinds default / eq / cyclic over the efficiency-aware reachable range."""
+    """helpers.draw_band's kinds default / eq / cyclic / mix over the efficiency-aware reachable range (mix: an equality target,
+    lo = hi = e0, the highest reachable level as an equality, a band around the target, the default, in turn)."""
     rlo, rhi = reachable_eff(pp, e0, eta_c, eta_d)
     x = rlo + rng.uniform(0.0, 1.0, pp.S) * (rhi - rlo)
+    if kind == "mix":
+        k = np.arange(pp.S) % 5
+        mid = 0.5 * (rlo + rhi)
+        lo = np.select([k == 0, k == 1, k == 2, k == 3], [x, e0, rhi, np.minimum(x, mid)], 0.0)
+        hi = np.select([k == 0, k == 1, k == 2, k == 3], [x, e0, rhi, np.maximum(x, mid)], pp.sto_emax)
+        return lo, hi
     return {"default": (np.zeros(pp.S), pp.sto_emax.copy()), "eq": (x, x.copy()), "cyclic": (e0.copy(), e0.copy())}[kind]
 
 

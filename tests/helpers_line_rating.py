@@ -1,5 +1,5 @@
 """Helpers of the line-rating tests (DOPF_F_LINE_RATING), CPU and GPU: the cases and the table the tests share, the
-T = 1 column problems the oracle solves (it keeps one f_max per line: a column of the table is a problem of its own when no storage
+T = 1 column problems the oracle solves with one f_max per line (a column of the table is a problem of its own when no storage
 couples the timesteps), and Psi_{n,t} under a rating table for the storages' optimality certificate."""
 import copy
 import ctypes as C

@@ -1,8 +1,10 @@
-"""Line ratings per timestep (DOPF_F_LINE_RATING, dopf_set_line_rating) on the device. The CPU oracle keeps one f_max
-per line, so the references are: the flagless context, bit for bit, wherever the table's columns all equal f_max; without storages the
-oracle's exact mode column by column (timestep t of a run under a table is the T = 1 problem with f_max = rating[:, t]); with
-storages the breakpoint tables of a flagless context with f_max = rating[:, t] and a NumPy KKT certificate whose theta comes from Psi
-under the table; and the HiGHS LP for the optimum. Needs a real MI355X: pytest -m gpu."""
+"""Line ratings per timestep (DOPF_F_LINE_RATING, dopf_set_line_rating) on the device. The references here are: the
+flagless context, bit for bit, wherever the table's columns all equal f_max; without storages the oracle's exact mode column by
+column with one f_max per line (timestep t of a run under a table is the T = 1 problem with f_max = rating[:, t]); with storages the
+breakpoint tables of a flagless context with f_max = rating[:, t] and a NumPy KKT certificate whose theta comes from Psi under the
+table; and the HiGHS LP for the optimum. The CPU oracle takes the table itself since (oracle_set_line_rating): the slack getters'
+last leg uses it, and every chain is compared with it value for value, with storages, in tests/test_gpu_lossy_rated_parity.py.
+Needs a real MI355X: pytest -m gpu."""
 import copy
 import os
 import subprocess
@@ -393,6 +395,32 @@ def test_slack_and_penalty_getters_follow_the_table(hip_api, oracle_api, gen_cas
             worst = max(worst, dd / max(1.0, float(np.abs(want).max())))
             assert dd <= tol(want), (it, dd)
     print(f"slack and penalty getters vs the oracle's columns: worst relative difference {worst:.2e}")
+    # with storages the columns are coupled, and the reference is the oracle's exact mode under the same table: one step at a time
+    # (from the zero state, the HIP state reset to the oracle's after each), generators and storages
+    from conftest import build_oracle
+    from oracle.binding import OracleApi
+    fapi = OracleApi(build_oracle(), features=True)
+    pp = case(STOC)
+    rating = draw_table(pp)
+    h = rated_engine(hip_api, pp, _capi.F_KEEP_DELTAS, rating=rating, **KW)
+    o = _capi.Engine(fapi, params=_capi.default_params(flags=LR, **KW), mode=1, **pp.engine_kwargs())
+    o.set_line_rating(rating)
+    worst, active = 0.0, 0
+    for it in range(5):
+        h.iterate(1)
+        o.iterate(1)
+        for a in (0, 7, pp.G - 1, pp.G, pp.G + 3, pp.G + pp.S - 1):
+            U, K = h.get_agent_slacks(a)
+            Uo, Ko = np.zeros(pp.L * pp.T), np.zeros(pp.L * pp.T)
+            assert fapi.get_agent_slacks(o._ctx, a, Uo.ctypes.data_as(dp), Ko.ctypes.data_as(dp)) == 0
+            for got, ref in ((U, Uo.reshape(pp.T, pp.L).T), (K, Ko.reshape(pp.T, pp.L).T)):
+                dd = float(np.abs(got - ref).max())
+                worst = max(worst, dd / max(1.0, float(np.abs(ref).max())))
+                active += int(np.count_nonzero(ref))
+                assert dd <= tol(ref), (it, a, dd)
+        set_from(h, state_of(o), o.get_residuals()[3])
+    assert active > 0
+    print(f"slack getters with storages vs the oracle under the table: worst relative difference {worst:.2e}")
 
 
 # ---- 10. shards --------------------------------------------------------------------------------------------------------------------

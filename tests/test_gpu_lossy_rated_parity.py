@@ -1,0 +1,278 @@
+"""Storage efficiencies below 1 and line ratings per timestep (DESIGN.md sections 5m, 5o) on every chain, against the oracle's
+exact mode with the same inputs — alone, together, and with initial levels, terminal bands and availability profiles: one step at a
+time (the HIP state reset to the oracle's after every iteration; from the zero state and from a seeded dopf_set_state), the setters
+between iterate(n) calls of graph-replayed chains, free runs, and negative controls. The bounds are those of
+tests/test_gpu_feature_parity.py: 1e-9 scaled on copper plates, 1e-8 on networks, the cost 1e-9 relative. The exact mode itself
+is pinned by the literal QP in tests/test_oracle_lossy_rated.py. Needs a real MI355X: pytest -m gpu."""
+import time
+
+import numpy as np
+import pytest
+
+from conftest import build_oracle
+from decentralopf_jl_amd import _capi, synth
+from helpers import LossyRated, degenerate, draw_e0, engine, set_from, state_of
+from helpers_efficiency import draw_band_eff, draw_eta
+from helpers_line_rating import draw_table
+from test_gpu_feature_parity import compare, one_step
+
+pytestmark = pytest.mark.gpu
+
+IL, TL, AV = _capi.F_STO_INITIAL_LEVEL, _capi.F_STO_TERMINAL_LEVEL, _capi.F_GEN_AVAILABILITY
+EF, LR = _capi.F_STO_EFFICIENCY, _capi.F_LINE_RATING
+LH = _capi.F_LONG_HORIZON
+NET = dict(N=4, L=5, fmax_factor=0.7, fmax_min=5)
+NET30 = dict(N=30, L=45, fmax_factor=0.7, fmax_min=10)
+
+
+@pytest.fixture(scope="module")
+def fapi():
+    from oracle.binding import OracleApi
+    return OracleApi(build_oracle(), features=True)
+
+
+def seeded_state(pp, seed):
+    """a state for dopf_set_state that no run produced (tests/test_gpu_sto_efficiency.py, tests/test_gpu_line_rating.py)"""
+    rng = np.random.default_rng(seed)
+    return dict(P=rng.uniform(0, 1, (pp.G, pp.T)) * pp.gen_pmax[:, None], D=rng.uniform(0, 0.4, (pp.S, pp.T)) * pp.sto_pmax[:, None],
+                C=rng.uniform(0, 0.4, (pp.S, pp.T)) * pp.sto_pmax[:, None], avg_U=rng.uniform(0, 1, (pp.L, pp.T)),
+                avg_K=rng.uniform(0, 1, (pp.L, pp.T)), lam=rng.uniform(1, 30, pp.T), mu=rng.uniform(0, 1, (pp.L, pp.T)),
+                rho=rng.uniform(0, 1, (pp.L, pp.T)))
+
+
+def pair_step(h, o, iters, tol):
+    """one_step with the HIP iteration as dopf_local_update + dopf_apply_consensus (the sharded form at world 1)"""
+    worst = 0.0
+    for k in range(iters):
+        h.local_update()
+        h.apply_consensus()
+        o.iterate(1)
+        w, where, cost = compare(state_of(h), state_of(o), tol)
+        assert w <= tol and cost <= 1e-9, (k, where, w, cost)
+        worst = max(worst, w)
+        set_from(h, state_of(o), o.get_residuals()[3])
+    assert h.solver_failures() == 0
+    return worst
+
+
+def pair_of(hip_api, fapi, pp, feats, extra, gamma):
+    from oracle.binding import set_threads
+    h = engine(hip_api, pp, None, flags=feats.flags | extra, eps=0.0, gamma=gamma)
+    o = engine(fapi, pp, 1, flags=feats.flags, eps=0.0, gamma=gamma)
+    set_threads(o, 8)
+    for e in (h, o):
+        feats.apply(e)
+    return h, o
+
+
+def zero_then_seeded(h, o, pp, iters, seeded, expect, pair=False):
+    """`iters` single steps from the zero state, `seeded` from a seeded dopf_set_state on both; the worst scaled difference"""
+    tol = 1e-9 if pp.L == 0 else 1e-8
+    worst = pair_step(h, o, iters, tol) if pair else one_step(h, o, iters, tol, expect)
+    if seeded:
+        st = seeded_state(pp, 5)
+        set_from(h, st, 2)
+        set_from(o, st, 2)
+        worst = max(worst, pair_step(h, o, seeded, tol) if pair else one_step(h, o, seeded, tol))
+    return worst
+
+
+# ---- one step at a time ------------------------------------------------------------------------------------------------------------
+# name, case, extra flags, (e0, band, profiles), (eta, table), degenerate storages, gamma, iterations from the zero state,
+# expected dopf_timing fields. Every row then runs 2 more from a seeded state. A context with DOPF_F_STO_EFFICIENCY runs level
+# mode 3 of whichever body its chain has (never the lean one); the table reaches the storages through the breakpoint tables and
+# the chain through the slack sums and the dual, flag and mask step.
+
+CP = dict(n_gen=300, n_sto=24, T=24, seed=901)
+N45 = dict(n_gen=60, n_sto=12, T=24, seed=911, **NET)
+N3045 = dict(n_gen=120, n_sto=24, T=96, seed=41, **NET30)          # lines get flagged in the first iterations
+T1024C = dict(n_gen=200, n_sto=40, T=144, N=20, L=30, seed=51, fmax_factor=0.7, fmax_min=5)     # tests/test_gpu_line_rating.py: L*T > 4096
+LOSSY, RATED, BOTH = (True, False), (False, True), (True, True)
+ONE = [
+    # eta < 1 on copper plates
+    ("copper-fused", CP, 0, ("mix", "mix", "K3"), LOSSY, "emax0", 0.02, 6, dict(agents_fused=1, sto_lean=0, sto_long=0)),
+    ("copper-eta-alone", CP, 0, (None, None, None), LOSSY, "", 0.02, 4, dict(agents_fused=1, sto_lean=0, sto_long=0)),
+    ("copper-no-fuse", CP, _capi.F_NO_FUSE, ("mix", "cyclic", "KG"), LOSSY, "emax0+pmax0", 0.02, 5, dict(agents_fused=0, sto_long=0)),
+    ("copper-no-tail-fuse", CP, _capi.F_NO_TAIL_FUSE, ("inside", "eq", None), LOSSY, "", 0.02, 4, dict(tail_fused=0, sto_lean=0)),
+    ("copper-no-warm-scan", CP, _capi.F_NO_WARM_START, ("mix", "mix", "K3"), LOSSY, "pmax0", 0.02, 4, dict(sto_long=0)),
+    ("copper-debug-leave", CP, _capi.F_DEBUG_LEAVE, ("mix", "mix", "K3"), LOSSY, "emax0", 0.02, 4, dict(sto_long=0)),
+    ("copper-debug-long", CP, _capi.F_DEBUG_LONG_STO, ("mix", "mix", "K3"), LOSSY, "emax0", 0.02, 4, dict(sto_long=1)),
+    ("copper-odd-T25", dict(n_gen=200, n_sto=16, T=25, seed=902), 0, ("mix", "mix", "K3"), LOSSY, "emax0", 0.02, 4, dict(agents_fused=0)),
+    ("copper-T250-scan", dict(n_gen=30, n_sto=6, T=250, seed=903), 0, ("mix", "mix", "K3"), LOSSY, "emax0", 0.02, 4, dict(sto_long=0)),
+    ("copper-T600-long", dict(n_gen=20, n_sto=4, T=600, seed=905), LH, ("mix", "mix", "K3"), LOSSY, "", 0.02, 4, dict(sto_long=1)),
+    ("copper-T2049-long-tile-edge", dict(n_gen=8, n_sto=3, T=2049, seed=907), LH, ("mix", "cyclic", "K1"), LOSSY, "", 0.02, 2, dict(sto_long=1)),
+    # eta < 1 and a table on networks
+    ("net-4x5-T24", N45, 0, ("mix", "mix", "K3"), BOTH, "emax0", 0.03, 6, dict(wide_net=0, sto_lean=0)),
+    ("net-4x5-overlap", N45, _capi.F_OVERLAP_AGENTS, ("inside", "cyclic", "KG"), BOTH, "pmax0", 0.03, 4, dict(agents_fused=0)),
+    ("net-4x5-no-fuse", N45, _capi.F_NO_FUSE, ("mix", "eq", None), BOTH, "", 0.03, 4, dict(agents_fused=0)),
+    ("net-4x5-no-quiet", N45, _capi.F_NO_QUIET, ("inside", "eq", "K3"), BOTH, "", 0.03, 4, dict(quiet=0)),
+    ("net-4x5-debug-wide", N45, _capi.F_DEBUG_WIDE_NET, ("mix", "mix", "K3"), BOTH, "emax0", 0.03, 4, dict(wide_net=1)),
+    ("net-4x5-debug-long", N45, _capi.F_DEBUG_LONG_STO, ("mix", "mix", None), BOTH, "", 0.03, 4, dict(sto_long=1)),
+    ("net-4x5-T250-scan", dict(n_gen=20, n_sto=6, T=250, seed=912, **NET), 0, ("mix", "mix", "K3"), BOTH, "", 0.03, 4, dict(sto_long=0)),
+    ("net-4x5-T600-long", dict(n_gen=20, n_sto=4, T=600, seed=913, **NET), LH, ("mix", "eq", "K1"), BOTH, "", 0.03, 4, dict(sto_long=1)),
+    ("net-30x45-T96", N3045, 0, ("mix", "mix", "K3"), BOTH, "emax0", 0.01, 4, dict(agents_fused=1, wide_net=0)),
+    ("net-30x45-small-items", N3045, _capi.F_NET_SMALL_ITEMS, ("mix", "cyclic", "K3"), BOTH, "pmax0", 0.01, 4, dict(wide_net=0)),
+    ("net-30x45-debug-wide", N3045, _capi.F_DEBUG_WIDE_NET, ("mix", "mix", "K3"), BOTH, "emax0", 0.01, 4, dict(wide_net=1)),
+    # the one-launch dual / price kernel (L*T > 4096), which forms the slack sums too (slack_in_dual)
+    ("net-20x30-T144-one-launch-dual", T1024C, 0, ("mix", "mix", "K3"), BOTH, "", 0.01, 4, dict(wide_net=0, slack_in_dual=1)),
+    # a table alone: the problem's default storage body runs
+    ("net-4x5-T24-table-alone", N45, 0, (None, None, None), RATED, "", 0.03, 6, dict(wide_net=0)),
+    ("net-30x45-T96-table-alone", N3045, 0, (None, None, None), RATED, "", 0.01, 4, dict(agents_fused=1, wide_net=0)),
+]
+
+
+@pytest.mark.parametrize("name,case,extra,feat,what,degen,gamma,iters,expect", ONE, ids=[r[0] for r in ONE])
+def test_one_step_parity_lossy_and_rated(hip_api, fapi, name, case, extra, feat, what, degen, gamma, iters, expect):
+    pp = degenerate(synth.synthetic_case(**case), degen)
+    feats = LossyRated(pp, *feat, seed=case["seed"], eta=what[0], table=what[1], zero=what[1])
+    h, o = pair_of(hip_api, fapi, pp, feats, extra, gamma)
+    worst = zero_then_seeded(h, o, pp, iters, 2, expect)
+    print(f"{name}: worst one-step difference {worst:.2e} (scaled)")
+
+
+@pytest.mark.parametrize("case,what,gamma", [(CP, LOSSY, 0.02), (N45, BOTH, 0.03)], ids=["copper", "net-4x5"])
+def test_local_update_and_apply_consensus_pair(hip_api, fapi, case, what, gamma):
+    pp = degenerate(synth.synthetic_case(**case), "emax0")
+    feats = LossyRated(pp, "mix", "mix", "K3", seed=case["seed"] + 1, eta=what[0], table=what[1])
+    h, o = pair_of(hip_api, fapi, pp, feats, 0, gamma)
+    worst = zero_then_seeded(h, o, pp, 4, 2, None, pair=True)
+    print(f"local_update / apply_consensus pair: worst one-step difference {worst:.2e} (scaled)")
+
+
+def test_lean_body_on_a_network_under_a_table(hip_api, fapi):
+    """The lean storage body on a network (plan_chain: S * stoLPS / 256 >= 1024, the smallest such case: 4096 storages x 192
+    timesteps on the 4 x 5 grid) under a non-constant table, no other flag: one iteration from a seeded dopf_set_state and one from
+    its result. The oracle's share of this test is printed (two exact iterations of 4096 storages at 8 threads)."""
+    pp = synth.synthetic_case(n_gen=16, n_sto=4096, T=192, seed=921, **NET)
+    feats = LossyRated(pp, None, None, None, seed=921, eta=False, table=True, zero=True)
+    h, o = pair_of(hip_api, fapi, pp, feats, 0, 0.03)
+    st = seeded_state(pp, 5)
+    set_from(h, st, 2)
+    set_from(o, st, 2)
+    assert h.iterate_timed(1)["sto_lean"] == 1
+    spent = 0.0
+    worst = 0.0
+    for k in range(2):
+        if k:
+            h.iterate(1)
+        t0 = time.perf_counter()
+        o.iterate(1)
+        spent += time.perf_counter() - t0
+        w, where, cost = compare(state_of(h), state_of(o), 1e-8)
+        assert w <= 1e-8 and cost <= 1e-9, (k, where, w, cost)
+        worst = max(worst, w)
+        set_from(h, state_of(o), o.get_residuals()[3])
+    assert h.solver_failures() == 0
+    print(f"lean body on a network under a table: worst one-step difference {worst:.2e} (scaled), oracle {spent:.1f} s")
+
+
+# ---- the setters between iterate(n) calls: graphs of 16, 4 and 1 iterations replayed with the new values --------------------
+
+@pytest.mark.parametrize("case", [dict(n_gen=100, n_sto=10, T=24, seed=931), dict(n_gen=60, n_sto=12, T=24, seed=932, **NET)],
+                         ids=["copper", "net-4x5"])
+def test_setters_between_graph_replays(hip_api, fapi, case):
+    pp = synth.synthetic_case(**case)
+    A = pp.G + pp.S
+    kw = dict(eps=0.0, gamma=1.0 / A) if pp.L == 0 else dict(eps=0.0, gamma=1.0 / A, w_flow=0.3 / A)
+    flags = EF | LR | IL | TL
+    h = engine(hip_api, pp, None, flags=flags, **kw)
+    o = engine(fapi, pp, 1, flags=flags, **kw)
+    rng = np.random.default_rng(case["seed"])
+    tol = 1e-8 if pp.L == 0 else 1e-7
+    worst = 0.0
+    e0, ec, ed = np.zeros(pp.S), np.ones(pp.S), np.ones(pp.S)
+    for step, n in enumerate((1, 4, 16, 37, 1, 16, 4, 37)):
+        what = ("eta", "table", "e0+band")[step % 3]
+        kind = ("mix", "eq", "cyclic")[(step // 3) % 3]
+        if what == "eta":                       # new efficiencies under the default band, then a band reachable under them
+            ec, ed = draw_eta(pp.S, rng)
+            band = draw_band_eff(pp, e0, ec, ed, kind, rng)
+        elif what == "table":
+            table = draw_table(pp, seed=case["seed"] + step)
+        else:                                   # a new e0 under the default band, then a band reachable from it
+            e0 = draw_e0(pp, ("mix", "inside", "full")[(step // 3) % 3], rng)
+            band = draw_band_eff(pp, e0, ec, ed, kind, rng)
+        for e in (h, o):
+            if what == "eta":
+                e.set_terminal_levels()
+                e.set_efficiency(ec, ed)
+                e.set_terminal_levels(*band)
+            elif what == "table":
+                e.set_line_rating(table)
+            else:
+                e.set_terminal_levels()
+                e.set_initial_levels(e0)
+                e.set_terminal_levels(*band)
+        h.iterate(n)
+        o.iterate(n)
+        w, where, cost = compare(state_of(h), state_of(o), tol)
+        assert w <= tol, (step, n, where, w)
+        worst = max(worst, w)
+    assert h.solver_failures() == 0
+    print(f"setters between replays: worst {worst:.2e}")
+
+
+# ---- free runs ----------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["copper", "net-30x45-T96"])
+def test_free_running_with_all_five_features(hip_api, fapi, name):
+    if name == "copper":
+        pp = synth.synthetic_case(100, 10, 24, seed=941)
+        A = pp.G + pp.S
+        kw = dict(eps=0.0, gamma=1.0 / A)
+    else:
+        pp = synth.synthetic_case(120, 24, 96, N=30, L=45, seed=43, fmax_factor=0.8, fmax_min=10)
+        A = pp.G + pp.S
+        kw = dict(eps=0.0, gamma=1.0 / A, w_flow=0.3 / A)
+    feats = LossyRated(pp, "mix", "mix", "K3", seed=942)
+    h = engine(hip_api, pp, None, flags=feats.flags, **kw)
+    o = engine(fapi, pp, 1, flags=feats.flags, **kw)
+    for e in (h, o):
+        feats.apply(e)
+    from oracle.binding import set_threads
+    set_threads(o, 8)
+    h.iterate_timed(1)
+    o.iterate(1)
+    worst = 0.0
+    for n in (1, 3, 10, 15):
+        h.iterate(n)
+        o.iterate(n)
+        w, where, _ = compare(state_of(h), state_of(o), 1e-7)
+        assert w <= 1e-7, (n, where, w)
+        worst = max(worst, w)
+    assert h.solver_failures() == 0
+    print(f"free run {name}: worst {worst:.2e} (scaled)")
+
+
+# ---- negative controls ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("what", ["eta", "table"])
+def test_hip_with_the_input_against_the_oracle_at_its_default_fails(hip_api, fapi, what):
+    """HIP with eta < 1 (resp. the table) against the oracle with the flag but the defaults"""
+    pp = synth.synthetic_case(**(CP if what == "eta" else N45))
+    feats = LossyRated(pp, None, None, None, seed=951, eta=what == "eta", table=what == "table")
+    gamma = 0.02 if what == "eta" else 0.03
+    h = engine(hip_api, pp, None, flags=feats.flags, eps=0.0, gamma=gamma)
+    feats.apply(h)
+    o = engine(fapi, pp, 1, flags=feats.flags, eps=0.0, gamma=gamma)
+    with pytest.raises(AssertionError):
+        one_step(h, o, 4, 1e-9 if pp.L == 0 else 1e-8)
+
+
+def test_tables_that_differ_in_one_binding_entry_fail(hip_api, fapi):
+    """HIP and the oracle under tables that differ in one entry, by 1e-3 f_max, where mu is non-zero in the oracle's own run: the
+    dual step alone moves mu there by gamma 1e-3 f_max >= 1.5e-4, four orders above the bound once scaled."""
+    pp = synth.synthetic_case(**N45)
+    feats = LossyRated(pp, None, None, None, seed=N45["seed"], eta=False, table=True, zero=True)
+    o = engine(fapi, pp, 1, flags=feats.flags, eps=0.0, gamma=0.03)
+    feats.apply(o)
+    o.iterate(4)
+    mu = state_of(o)["mu"]
+    l, t = np.unravel_index(np.argmax(np.abs(mu)), mu.shape)
+    assert mu[l, t] != 0.0
+    h, o = pair_of(hip_api, fapi, pp, feats, 0, 0.03)
+    other = feats.rating.copy()
+    other[l, t] += 1e-3 * pp.f_max[l]
+    o.set_line_rating(other)
+    with pytest.raises(AssertionError):
+        one_step(h, o, 4, 1e-8)

@@ -1,5 +1,6 @@
-"""Storage charge / discharge efficiencies (DOPF_F_STO_EFFICIENCY) on the device. The CPU oracle has no efficiencies,
-so the new ground is pinned four ways: (i) the oracle's exact mode at eta = 1, one step at a time; (ii) an exact KKT certificate
+"""Storage charge / discharge efficiencies (DOPF_F_STO_EFFICIENCY) on the device. The CPU oracle takes efficiencies
+since (oracle_set_storage_efficiency), and every chain is compared with it value for value at eta < 1 in
+tests/test_gpu_lossy_rated_parity.py; this file, written before, pins the ground four ways without them: (i) the oracle's exact mode at eta = 1, one step at a time; (ii) an exact KKT certificate
 in NumPy at eta < 1 (helpers_efficiency.storage_kkt_violation_eff; on networks its theta comes from Psi_{n,t} evaluated in NumPy
 from the closed forms of DESIGN.md section 3, helpers_efficiency.theta_of); (iii) the identity that normalises the discharge efficiency away (copper plate and network); (iv) the HiGHS LP with
 lossy balance rows at convergence. Bounds: test 1 the one-step bound of tests/test_gpu_feature_parity.py (1e-9 scaled on copper
