@@ -19,6 +19,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/dopf.h"
 
 namespace dopf {
@@ -285,6 +287,37 @@ struct Plan {
 // k_agents / k_net_agents for kFusedPairs, the storage launches for all.
 constexpr int kStoPairs[][2] = {{8, 1}, {8, 2}, {8, 3}, {16, 3}, {32, 3}, {64, 3}, {64, 6}, {64, 8}};
 constexpr int kFusedPairs = 6, kAllPairs = 8;
+
+// f(LPS, NCH) for the plan's lane group, as std::integral_constant arguments, over the first NP pairs of kStoPairs only: a launch
+// family is instantiated for exactly those. plan_chain refuses a lane group that the families it chose do not cover.
+template <int NP, int I = 0, class F>
+void with_sto_pair(const Plan &p, F &&f)
+{
+    if constexpr (I < NP) {
+        if (p.stoLPS == kStoPairs[I][0] && p.stoNCH == kStoPairs[I][1])
+            f(std::integral_constant<int, kStoPairs[I][0]>{}, std::integral_constant<int, kStoPairs[I][1]>{});
+        else
+            with_sto_pair<NP, I + 1>(p, f);
+    }
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument (both are instantiated)
+template <class F>
+void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// f(integral_constant<int, LV>) for the plan's level mode p.stoLV (0 .. 3: all four instantiated)
+template <class F>
+void with_lv(int lv, F &&f)
+{
+    if (lv == 3) f(std::integral_constant<int, 3>{});
+    else if (lv == 2) f(std::integral_constant<int, 2>{});
+    else if (lv == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
 
 // the central reference's view (kernels_central.hip): the context's arrays (P, D, C, E, items, partial sums, cons) plus the
 // multipliers, running sums and step sizes of the primal-dual iteration

@@ -11,14 +11,20 @@
 //               price of each constant-price segment comes from a safeguarded Newton iteration.
 // Both kernels also produce the per-item partial sums of the agents' net injection and cost
 // (the agent loop of Result(...), src/structures/results.jl:72-106) in a fixed order.
-#include <type_traits>
-
 #include "dopf_internal.h"
 
 namespace dopf {
 
 #if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
 __device__ unsigned long long g_timeline[8192 * 8 + 8192 * 8];      // per wave of the storage body: wall-clock stamps (100 MHz)
+#endif
+// entry and exit stamps of a fused launch's blocks (the exit stamp once the whole block is through)
+#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
+#define DOPF_BLOCK_ENTER() { if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64(); }
+#define DOPF_BLOCK_EXIT() { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64(); }
+#else
+#define DOPF_BLOCK_ENTER()
+#define DOPF_BLOCK_EXIT()
 #endif
 #ifdef DOPF_BLOCK_STAMPS
 #define DOPF_TAIL_STAMP(i) { if (threadIdx.x == 0) g_timeline[(i)] = wall_clock64(); }
@@ -511,17 +517,12 @@ __device__ __forceinline__ void gen_update_body(const DevView &v)
     }
 }
 
-template <bool LINES>
+// (AV, here and in the kernels below: DOPF_F_GEN_AVAILABILITY, the generator bodies with the rows' caps. An argument of the kernel
+// itself, so the flagless instantiations keep their code: DESIGN.md 5j)
+template <bool LINES, bool AV = false>
 __global__ __launch_bounds__(512) void k_gen_update(DevView v)
 {
-    gen_update_body<LINES, false>(v);
-}
-
-// DOPF_F_GEN_AVAILABILITY: the same with the rows' caps (kernels of their own: the flagless ones keep their code)
-template <bool LINES>
-__global__ __launch_bounds__(512) void k_gen_update_av(DevView v)
-{
-    gen_update_body<LINES, true>(v);
+    gen_update_body<LINES, AV>(v);
 }
 
 // End of a generator block of the pair kernels: per-column sums of the R agent lanes and the block's cost, every sum in
@@ -729,20 +730,12 @@ __device__ __forceinline__ bool gen_pair_stream(const DevView &v, const int firs
 // MODE 0: partial rows for k_reduce; 1: sums into the accumulators, a later launch of the chain (k_sto) carries the tail block;
 // 2: no storage launch follows, this launch carries the tail block itself. (Instantiations of their own: the tail's registers
 // would cost the common kernel a wave per SIMD, and the chains without a tail keep the code they had.)
-template <int MODE>
+template <int MODE, bool AV = false>
 __global__ __launch_bounds__(512) void k_gen_update_pair(DevView v)
 {
     if (MODE == 2 && (int)blockIdx.x == v.nGenItems) { tail_block(v.self); return; }
     if (v.st->halt) return;
-    gen_pair_body<512, MODE != 0>(v, blockIdx.x);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(512) void k_gen_update_pair_av(DevView v)
-{
-    if (MODE == 2 && (int)blockIdx.x == v.nGenItems) { tail_block(v.self); return; }
-    if (v.st->halt) return;
-    gen_pair_body<512, MODE != 0, false, true>(v, blockIdx.x);
+    gen_pair_body<512, MODE != 0, false, AV>(v, blockIdx.x);
 }
 
 // Row skipping variant (used when a block sweeps many agents, so that its fixed cost is amortised): in a
@@ -848,53 +841,31 @@ __device__ __forceinline__ void gen_pair_skip_body(const DevView &v, const int b
     gen_pair_sums<BS, TAIL>(v, blk, tid, r, tt, acc0, acc1, cost, red, wc);
 }
 
-template <int MODE>
+template <int MODE, bool AV = false>
 __global__ __launch_bounds__(512) void k_gen_update_pair_skip(DevView v)
 {
     if (MODE == 2 && (int)blockIdx.x == v.nGenItems) { tail_block(v.self); return; }
     if (v.st->halt) return;
-    gen_pair_skip_body<512, MODE != 0>(v, blockIdx.x);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(512) void k_gen_update_pair_skip_av(DevView v)
-{
-    if (MODE == 2 && (int)blockIdx.x == v.nGenItems) { tail_block(v.self); return; }
-    if (v.st->halt) return;
-    gen_pair_skip_body<512, MODE != 0, true>(v, blockIdx.x);
-}
-
-// DOPF_F_GEN_AVAILABILITY (p.genAvail): the same choice among the kernels with the rows' caps
-static void launch_gen_update_av(const DevView &v, hipStream_t s)
-{
-    if (v.L > 0) hipLaunchKernelGGL(k_gen_update_av<true>, dim3(v.nGenItems), dim3(512), 0, s, v);
-    else if (v.genTT2 > 0 && v.tail && v.nStoItems == 0) {
-        if (v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip_av<2>, dim3(v.nGenItems + 1), dim3(512), 0, s, v);
-        else hipLaunchKernelGGL(k_gen_update_pair_av<2>, dim3(v.nGenItems + 1), dim3(512), 0, s, v);
-    } else if (v.genTT2 > 0 && v.tail) {
-        if (v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip_av<1>, dim3(v.nGenItems), dim3(512), 0, s, v);
-        else hipLaunchKernelGGL(k_gen_update_pair_av<1>, dim3(v.nGenItems), dim3(512), 0, s, v);
-    }
-    else if (v.genTT2 > 0 && v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip_av<0>, dim3(v.nGenItems), dim3(512), 0, s, v);
-    else if (v.genTT2 > 0) hipLaunchKernelGGL(k_gen_update_pair_av<0>, dim3(v.nGenItems), dim3(512), 0, s, v);
-    else hipLaunchKernelGGL(k_gen_update_av<false>, dim3(v.nGenItems), dim3(512), 0, s, v);
+    gen_pair_skip_body<512, MODE != 0, AV>(v, blockIdx.x);
 }
 
 void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s)
 {
     if (v.nGenItems == 0) return;
-    if (p.genAvail) { launch_gen_update_av(v, s); return; }
-    if (v.L > 0) hipLaunchKernelGGL(k_gen_update<true>, dim3(v.nGenItems), dim3(512), 0, s, v);
-    else if (v.genTT2 > 0 && v.tail && v.nStoItems == 0) {
-        if (v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip<2>, dim3(v.nGenItems + 1), dim3(512), 0, s, v);
-        else hipLaunchKernelGGL(k_gen_update_pair<2>, dim3(v.nGenItems + 1), dim3(512), 0, s, v);
-    } else if (v.genTT2 > 0 && v.tail) {
-        if (v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip<1>, dim3(v.nGenItems), dim3(512), 0, s, v);
-        else hipLaunchKernelGGL(k_gen_update_pair<1>, dim3(v.nGenItems), dim3(512), 0, s, v);
-    }
-    else if (v.genTT2 > 0 && v.genSkip) hipLaunchKernelGGL(k_gen_update_pair_skip<0>, dim3(v.nGenItems), dim3(512), 0, s, v);
-    else if (v.genTT2 > 0) hipLaunchKernelGGL(k_gen_update_pair<0>, dim3(v.nGenItems), dim3(512), 0, s, v);
-    else hipLaunchKernelGGL(k_gen_update<false>, dim3(v.nGenItems), dim3(512), 0, s, v);
+    with_bool(p.genAvail, [&](auto av) {
+        constexpr bool AV = decltype(av)::value;
+        if (v.L > 0) hipLaunchKernelGGL((k_gen_update<true, AV>), dim3(v.nGenItems), dim3(512), 0, s, v);
+        else if (v.genTT2 > 0 && v.tail && v.nStoItems == 0) {
+            if (v.genSkip) hipLaunchKernelGGL((k_gen_update_pair_skip<2, AV>), dim3(v.nGenItems + 1), dim3(512), 0, s, v);
+            else hipLaunchKernelGGL((k_gen_update_pair<2, AV>), dim3(v.nGenItems + 1), dim3(512), 0, s, v);
+        } else if (v.genTT2 > 0 && v.tail) {
+            if (v.genSkip) hipLaunchKernelGGL((k_gen_update_pair_skip<1, AV>), dim3(v.nGenItems), dim3(512), 0, s, v);
+            else hipLaunchKernelGGL((k_gen_update_pair<1, AV>), dim3(v.nGenItems), dim3(512), 0, s, v);
+        }
+        else if (v.genTT2 > 0 && v.genSkip) hipLaunchKernelGGL((k_gen_update_pair_skip<0, AV>), dim3(v.nGenItems), dim3(512), 0, s, v);
+        else if (v.genTT2 > 0) hipLaunchKernelGGL((k_gen_update_pair<0, AV>), dim3(v.nGenItems), dim3(512), 0, s, v);
+        else hipLaunchKernelGGL((k_gen_update<false, AV>), dim3(v.nGenItems), dim3(512), 0, s, v);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2431,9 +2402,7 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
     const int nS = v.nStoItems;
     const bool isGen = (int)blockIdx.x >= nS;
     const int gi = (int)blockIdx.x - nS, si = blockIdx.x;
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
-#endif
+    DOPF_BLOCK_ENTER();
     if (isGen) {
         if (v.st->halt) return;
         if (2 * v.genTT256 >= v.T) gen_lines_body2<256, DOPF_NET_GEN_FLIGHT>(v, gi, v.genTT256, v.genR);
@@ -2450,14 +2419,11 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents(DevView v)
             sto_cold_lines_call<LPS, NCH, LV>(v.self, si, left);
         }
     }
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
-#endif
+    DOPF_BLOCK_EXIT();
 }
 
-// DOPF_F_GEN_AVAILABILITY: the same kernel with the generator bodies' AV instantiations (a copy, not a shared body: as one
-// __forceinline__ body behind both, the flagless kernel's scalar spills moved — DESIGN.md 5j)
+// DOPF_F_GEN_AVAILABILITY: the same kernel with the generator bodies' AV instantiations. A copy, unlike the other kernels' AV argument:
+// as k_net_agents<.., AV> one flagless instantiation came out with two register pairs exchanged
 template <int LPS, int NCH, bool LEAN, int LV = 0>
 __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents_av(DevView v)
 {
@@ -2465,9 +2431,7 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents_av(DevView 
     const int nS = v.nStoItems;
     const bool isGen = (int)blockIdx.x >= nS;
     const int gi = (int)blockIdx.x - nS, si = blockIdx.x;
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
-#endif
+    DOPF_BLOCK_ENTER();
     if (isGen) {
         if (v.st->halt) return;
         if (2 * v.genTT256 >= v.T) gen_lines_body2<256, DOPF_NET_GEN_FLIGHT, true>(v, gi, v.genTT256, v.genR);
@@ -2484,10 +2448,7 @@ __global__ __launch_bounds__(256, DOPF_WARM_WAVES) void k_net_agents_av(DevView 
             sto_cold_lines_call<LPS, NCH, LV>(v.self, si, left);
         }
     }
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
-#endif
+    DOPF_BLOCK_EXIT();
 }
 
 // Warm start and, in the same block, the cold scan for what it left over: one launch for the storages of the big
@@ -2509,62 +2470,27 @@ __global__ __launch_bounds__(256, 3) void k_sto(DevView v)
 // ones (interleaving the two kinds in dispatch order starts the last storage blocks late and costs 50 %).
 // The launch runs at the storage code's 3 waves/SIMD, which starves the streaming generator blocks once the
 // grid is large, so dopf_create only fuses grids whose storage blocks are all resident from the start.
-template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT, int LV = 0>
+template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT, int LV = 0, bool AV = false>
 __global__ __launch_bounds__(256, 3) void k_agents(DevView v)
 {
     const int nS = v.nStoItems;
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
-#endif
+    DOPF_BLOCK_ENTER();
     if (TAIL && blockIdx.x == gridDim.x - 1) {
         tail_block(v.self);
     } else if (!SKIP && (int)blockIdx.x >= nS) {
         // generator block: its loads do not wait for the halt word
-        if (v.genBlocks > 0) gen_pair_stream<256, TAIL>(v, blockIdx.x - nS, v.genBlocks);
-        else gen_pair_body<256, TAIL, true>(v, blockIdx.x - nS);
+        if (v.genBlocks > 0) gen_pair_stream<256, TAIL, AV>(v, blockIdx.x - nS, v.genBlocks);
+        else gen_pair_body<256, TAIL, true, AV>(v, blockIdx.x - nS);
     } else {
         if ((int)blockIdx.x < nS) {
             const int left = sto_warm_body<LPS, NCH, false, TAIL, FULLT, LV>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
             if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT, LV>(v, blockIdx.x, left);            // __syncthreads: the sto_fail flags are visible)
         } else {
             if (v.st->halt) return;
-            gen_pair_skip_body<256, TAIL>(v, blockIdx.x - nS);
+            gen_pair_skip_body<256, TAIL, AV>(v, blockIdx.x - nS);
         }
     }
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
-#endif
-}
-
-// DOPF_F_GEN_AVAILABILITY: the same kernel with the generator bodies' AV instantiations (a copy, not a shared body: as one
-// __forceinline__ body behind both, the flagless kernel's scalar spills moved — DESIGN.md 5j)
-template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT, int LV = 0>
-__global__ __launch_bounds__(256, 3) void k_agents_av(DevView v)
-{
-    const int nS = v.nStoItems;
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
-#endif
-    if (TAIL && blockIdx.x == gridDim.x - 1) {
-        tail_block(v.self);
-    } else if (!SKIP && (int)blockIdx.x >= nS) {
-        // generator block: its loads do not wait for the halt word
-        if (v.genBlocks > 0) gen_pair_stream<256, TAIL, true>(v, blockIdx.x - nS, v.genBlocks);
-        else gen_pair_body<256, TAIL, true, true>(v, blockIdx.x - nS);
-    } else {
-        if ((int)blockIdx.x < nS) {
-            const int left = sto_warm_body<LPS, NCH, false, TAIL, FULLT, LV>(v, blockIdx.x, v.st->halt);   // (with something left over it ends on a
-            if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT, LV>(v, blockIdx.x, left);            // __syncthreads: the sto_fail flags are visible)
-        } else {
-            if (v.st->halt) return;
-            gen_pair_skip_body<256, TAIL, true>(v, blockIdx.x - nS);
-        }
-    }
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
-#endif
+    DOPF_BLOCK_EXIT();
 }
 
 // The same two launches with the lean copper-plate storage body (sto_lean.h): horizon == LPS * NCH, at most 32 lanes per storage.
@@ -2580,60 +2506,26 @@ __global__ __launch_bounds__(256, DOPF_LEAN_STO_WAVES) void k_sto_l(DevView v)
     sto_cold_body<LPS, NCH, false, TAIL, FULLT>(v, blockIdx.x, left);
 }
 
-template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT = true>
+template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT = true, bool AV = false>
 __global__ __launch_bounds__(256, 3) void k_agents_l(DevView v)
 {
     const int nS = v.nStoItems;
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
-#endif
+    DOPF_BLOCK_ENTER();
     if (TAIL && blockIdx.x == gridDim.x - 1) {
         tail_block(v.self);
     } else if (!SKIP && (int)blockIdx.x >= nS) {
-        if (v.genBlocks > 0) gen_pair_stream<256, TAIL>(v, blockIdx.x - nS, v.genBlocks);
-        else gen_pair_body<256, TAIL, true>(v, blockIdx.x - nS);
+        if (v.genBlocks > 0) gen_pair_stream<256, TAIL, AV>(v, blockIdx.x - nS, v.genBlocks);
+        else gen_pair_body<256, TAIL, true, AV>(v, blockIdx.x - nS);
     } else {
         if ((int)blockIdx.x < nS) {
             const int left = sto_lean_body<LPS, NCH, TAIL, false, FULLT>(v, blockIdx.x, v.st->halt);
             if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT>(v, blockIdx.x, left);
         } else {
             if (v.st->halt) return;
-            gen_pair_skip_body<256, TAIL>(v, blockIdx.x - nS);
+            gen_pair_skip_body<256, TAIL, AV>(v, blockIdx.x - nS);
         }
     }
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
-#endif
-}
-
-// DOPF_F_GEN_AVAILABILITY: the same kernel with the generator bodies' AV instantiations (a copy, not a shared body: as one
-// __forceinline__ body behind both, the flagless kernel's scalar spills moved — DESIGN.md 5j)
-template <int LPS, int NCH, bool SKIP, bool TAIL, bool FULLT = true>
-__global__ __launch_bounds__(256, 3) void k_agents_l_av(DevView v)
-{
-    const int nS = v.nStoItems;
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x] = wall_clock64();
-#endif
-    if (TAIL && blockIdx.x == gridDim.x - 1) {
-        tail_block(v.self);
-    } else if (!SKIP && (int)blockIdx.x >= nS) {
-        if (v.genBlocks > 0) gen_pair_stream<256, TAIL, true>(v, blockIdx.x - nS, v.genBlocks);
-        else gen_pair_body<256, TAIL, true, true>(v, blockIdx.x - nS);
-    } else {
-        if ((int)blockIdx.x < nS) {
-            const int left = sto_lean_body<LPS, NCH, TAIL, false, FULLT>(v, blockIdx.x, v.st->halt);
-            if (left >= 0) sto_cold_body<LPS, NCH, false, TAIL, FULLT>(v, blockIdx.x, left);
-        } else {
-            if (v.st->halt) return;
-            gen_pair_skip_body<256, TAIL, true>(v, blockIdx.x - nS);
-        }
-    }
-#if defined(DOPF_STATS) || defined(DOPF_BLOCK_STAMPS)
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < 8192 * 4) g_timeline[32768 + 2 * blockIdx.x + 1] = wall_clock64();
-#endif
+    DOPF_BLOCK_EXIT();
 }
 
 int debug_timeline(unsigned long long *out, int n)
@@ -2658,63 +2550,26 @@ bool sto_config_supported(int T, Plan *p)
     return false;
 }
 
-// f(LPS, NCH) for the plan's lane group, as std::integral_constant arguments, over the first NP pairs of kStoPairs only: a launch
-// family is instantiated for exactly those. plan_chain refuses a lane group that the families it chose do not cover.
-template <int NP, int I = 0, class F>
-static void with_sto_pair(const Plan &p, F &&f)
-{
-    if constexpr (I < NP) {
-        if (p.stoLPS == kStoPairs[I][0] && p.stoNCH == kStoPairs[I][1])
-            f(std::integral_constant<int, kStoPairs[I][0]>{}, std::integral_constant<int, kStoPairs[I][1]>{});
-        else
-            with_sto_pair<NP, I + 1>(p, f);
-    }
-}
-
-// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument (both are instantiated)
-template <class F>
-static void with_bool(bool b, F &&f)
-{
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-
-// f(integral_constant<int, LV>) for the plan's level mode p.stoLV (0 .. 3: all four instantiated)
-template <class F>
-static void with_lv(int lv, F &&f)
-{
-    if (lv == 3) f(std::integral_constant<int, 3>{});
-    else if (lv == 2) f(std::integral_constant<int, 2>{});
-    else if (lv == 1) f(std::integral_constant<int, 1>{});
-    else f(std::integral_constant<int, 0>{});
-}
-
 // (p.stoLV, DOPF_F_STO_INITIAL_LEVEL / DOPF_F_STO_TERMINAL_LEVEL: the general bodies' level-mode instantiations; plan_chain keeps such
 // contexts off the lean body)
 template <int LPS, int NCH>
 static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
 {
-    if (v.use_warm && v.L == 0) {            // (NCH <= 3 whenever the warm start is on)
-        constexpr int NC = NCH <= 3 ? NCH : 3;
+    constexpr int NC = NCH <= 3 ? NCH : 3;   // (NCH <= 3 whenever the warm start is on)
+    if (v.use_warm && v.L == 0) {
         const dim3 grid(v.nStoItems + (v.tail ? 1 : 0));
         with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NC, [&](auto full) {
             constexpr bool TL = decltype(tail)::value, FU = decltype(full)::value;
             if (p.stoLean) hipLaunchKernelGGL((k_sto_l<LPS, NC, TL, FU>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 3) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, 3>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 2) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, 2>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 1) hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, 1>), grid, dim3(256), 0, s, v);
-            else hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU>), grid, dim3(256), 0, s, v);
+            else with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((k_sto<LPS, NC, false, TL, FU, decltype(lv)::value>), grid, dim3(256), 0, s, v); });
         }); });
         return;
     }
     // with lines the two kernels stay apart: fused, the warm part runs 40 % slower (255 VGPRs, measured); k_sto_warm calls the scan
     // body itself for what it leaves over
     if (v.use_warm) {
-        if (p.stoLean) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
-        else if (p.stoLV == 3) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, 3>), dim3(v.nStoItems), dim3(256), 0, s, v);
-        else if (p.stoLV == 2) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, 2>), dim3(v.nStoItems), dim3(256), 0, s, v);
-        else if (p.stoLV == 1) hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false, 1>), dim3(v.nStoItems), dim3(256), 0, s, v);
-        else hipLaunchKernelGGL((k_sto_warm<LPS, (NCH <= 3 ? NCH : 3), true, false>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        if (p.stoLean) hipLaunchKernelGGL((k_sto_warm<LPS, NC, true, true>), dim3(v.nStoItems), dim3(256), 0, s, v);
+        else with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((k_sto_warm<LPS, NC, true, false, decltype(lv)::value>), dim3(v.nStoItems), dim3(256), 0, s, v); });
         return;
     }
     with_lv(p.stoLV, [&](auto lv) {
@@ -2728,22 +2583,12 @@ template <int LPS, int NCH>
 static void launch_agents_t(const DevView &v, const Plan &p, hipStream_t s)
 {
     const dim3 grid(v.nStoItems + (v.genBlocks > 0 && !v.genSkip ? v.genBlocks : v.nGenItems) + (v.tail ? 1 : 0));
-    with_bool(v.genSkip, [&](auto skip) { with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NCH, [&](auto full) {
-        constexpr bool SK = decltype(skip)::value, TL = decltype(tail)::value, FU = decltype(full)::value;
-        if (p.genAvail) {           // DOPF_F_GEN_AVAILABILITY: the generator blocks with the rows' caps, the same storage bodies
-            if (p.stoLean) hipLaunchKernelGGL((k_agents_l_av<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 3) hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU, 3>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 2) hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU, 2>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 1) hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU, 1>), grid, dim3(256), 0, s, v);
-            else hipLaunchKernelGGL((k_agents_av<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
-            return;
-        }
-        if (p.stoLean) hipLaunchKernelGGL((k_agents_l<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
-        else if (p.stoLV == 3) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 3>), grid, dim3(256), 0, s, v);
-        else if (p.stoLV == 2) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 2>), grid, dim3(256), 0, s, v);
-        else if (p.stoLV == 1) hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, 1>), grid, dim3(256), 0, s, v);
-        else hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU>), grid, dim3(256), 0, s, v);
-    }); }); });
+    // (p.genAvail, DOPF_F_GEN_AVAILABILITY: the generator blocks with the rows' caps, the same storage bodies)
+    with_bool(v.genSkip, [&](auto skip) { with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NCH, [&](auto full) { with_bool(p.genAvail, [&](auto av) {
+        constexpr bool SK = decltype(skip)::value, TL = decltype(tail)::value, FU = decltype(full)::value, AV = decltype(av)::value;
+        if (p.stoLean) hipLaunchKernelGGL((k_agents_l<LPS, NCH, SK, TL, FU, AV>), grid, dim3(256), 0, s, v);
+        else with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((k_agents<LPS, NCH, SK, TL, FU, decltype(lv)::value, AV>), grid, dim3(256), 0, s, v); });
+    }); }); }); });
 }
 
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s)
@@ -2754,21 +2599,16 @@ void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s)
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s)
 {
     const dim3 grid(v.nStoItems + v.nGenItems);
-    with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) {
-        if (p.genAvail) {           // DOPF_F_GEN_AVAILABILITY: the generator blocks with the rows' caps, the same storage bodies
-            if (p.stoLean) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 3) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false, 3>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 2) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false, 2>), grid, dim3(256), 0, s, v);
-            else if (p.stoLV == 1) hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false, 1>), grid, dim3(256), 0, s, v);
-            else hipLaunchKernelGGL((k_net_agents_av<decltype(lps)::value, decltype(nch)::value, false>), grid, dim3(256), 0, s, v);
-            return;
+    with_sto_pair<kFusedPairs>(p, [&](auto lps, auto nch) { with_bool(p.genAvail, [&](auto av) {
+        constexpr int LPS = decltype(lps)::value, NCH = decltype(nch)::value;
+        if constexpr (decltype(av)::value) {
+            if (p.stoLean) hipLaunchKernelGGL((k_net_agents_av<LPS, NCH, true>), grid, dim3(256), 0, s, v);
+            else with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((k_net_agents_av<LPS, NCH, false, decltype(lv)::value>), grid, dim3(256), 0, s, v); });
+        } else {
+            if (p.stoLean) hipLaunchKernelGGL((k_net_agents<LPS, NCH, true>), grid, dim3(256), 0, s, v);
+            else with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((k_net_agents<LPS, NCH, false, decltype(lv)::value>), grid, dim3(256), 0, s, v); });
         }
-        if (p.stoLean) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, true>), grid, dim3(256), 0, s, v);
-        else if (p.stoLV == 3) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 3>), grid, dim3(256), 0, s, v);
-        else if (p.stoLV == 2) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 2>), grid, dim3(256), 0, s, v);
-        else if (p.stoLV == 1) hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false, 1>), grid, dim3(256), 0, s, v);
-        else hipLaunchKernelGGL((k_net_agents<decltype(lps)::value, decltype(nch)::value, false>), grid, dim3(256), 0, s, v);
-    });
+    }); });
 }
 
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s)

@@ -399,18 +399,14 @@ template <bool ITER>
 static void launch_gen(const CentralView &c, const Plan &p, const double *X, double scale, hipStream_t s)
 {
     if (!c.v.nGenItems) return;
-    if (p.genAvail) hipLaunchKernelGGL((kc_gen<ITER, true>), dim3(c.v.nGenItems), dim3(512), 0, s, c, X, scale);
-    else hipLaunchKernelGGL((kc_gen<ITER>), dim3(c.v.nGenItems), dim3(512), 0, s, c, X, scale);
+    with_bool(p.genAvail, [&](auto av) { hipLaunchKernelGGL((kc_gen<ITER, decltype(av)::value>), dim3(c.v.nGenItems), dim3(512), 0, s, c, X, scale); });
 }
 
 template <bool ITER>
 static void launch_sto(const CentralView &c, const Plan &p, const double *XD, const double *XC, const double *XE, double scale, hipStream_t s)
 {
     if (!c.v.nStoItems) return;
-    if (p.stoLV == 3) hipLaunchKernelGGL((kc_sto<ITER, 3>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
-    else if (p.stoLV == 2) hipLaunchKernelGGL((kc_sto<ITER, 2>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
-    else if (p.stoLV == 1) hipLaunchKernelGGL((kc_sto<ITER, 1>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
-    else hipLaunchKernelGGL((kc_sto<ITER>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale);
+    with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((kc_sto<ITER, decltype(lv)::value>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale); });
 }
 
 void central_launch_iteration(const CentralView &c, const Plan &p, const DevView &vreduce, hipStream_t s)
@@ -445,8 +441,7 @@ void central_launch_scale_copy_primal(const CentralView &c, const Plan &p, doubl
     const DevView &v = c.v;
     const size_t GT = (size_t)v.G * v.T, ST = (size_t)v.S * v.T;
     const dim3 gg((unsigned)((GT + 255) / 256)), gs((unsigned)((ST + 255) / 256));
-    if (GT && p.genAvail) hipLaunchKernelGGL((kc_scale_copy_box<true, true>), gg, dim3(256), 0, s, c, v.P, (const double *)c.aP, scale, GT);
-    else if (GT) hipLaunchKernelGGL((kc_scale_copy_box<true>), gg, dim3(256), 0, s, c, v.P, (const double *)c.aP, scale, GT);
+    if (GT) with_bool(p.genAvail, [&](auto av) { hipLaunchKernelGGL((kc_scale_copy_box<true, decltype(av)::value>), gg, dim3(256), 0, s, c, v.P, (const double *)c.aP, scale, GT); });
     if (ST) {
         hipLaunchKernelGGL((kc_scale_copy_box<false>), gs, dim3(256), 0, s, c, v.D, (const double *)c.aD, scale, ST);
         hipLaunchKernelGGL((kc_scale_copy_box<false>), gs, dim3(256), 0, s, c, v.C, (const double *)c.aC, scale, ST);

@@ -56,17 +56,17 @@ def one_step(h, o, iters, tol, expect=None):
 
 CP = dict(n_gen=300, n_sto=24, T=24, seed=701)
 ONE = [
-    # k_agents<..., LV 2> (the fused copper plate on the general body) and k_agents_av
+    # k_agents<..., LV 2> (the fused copper plate on the general body) and k_agents<..., AV>
     ("copper-fused", CP, 0, ("mix", "mix", "K3"), "emax0", 0.02, 8, dict(agents_fused=1, sto_lean=0, sto_long=0)),
     # k_agents<..., LV 1> without a band, the lean body's chain otherwise
     ("copper-fused-e0-only", CP, 0, ("inside", None, None), "", 0.02, 6, dict(agents_fused=1, sto_lean=0)),
     # k_agents<..., LV 2> with the band alone (e0 slot all zeros)
     ("copper-fused-band-only", CP, 0, (None, "eq", None), "pmax0", 0.02, 6, dict(agents_fused=1, sto_lean=0)),
-    # k_sto<..., LV 2> + k_gen_update_pair_av: separate launches
+    # k_sto<..., LV 2> + k_gen_update_pair<MODE, AV>: separate launches
     ("copper-no-fuse", CP, _capi.F_NO_FUSE, ("mix", "cyclic", "KG"), "emax0+pmax0", 0.02, 6, dict(agents_fused=0, sto_long=0)),
-    # k_sto<..., LV 2> + k_gen_update_av (no row skipping)
+    # k_sto<..., LV 2> + k_gen_update<LINES, AV> (no row skipping)
     ("copper-no-fuse-no-skip", CP, _capi.F_NO_FUSE | _capi.F_NO_ROW_SKIP, ("full", "edge-lo", "K1"), "", 0.02, 5, dict(agents_fused=0)),
-    # odd T: the separate-launch chain with k_gen_update_av
+    # odd T: the separate-launch chain with k_gen_update<LINES, AV>
     ("copper-odd-T25", dict(n_gen=200, n_sto=16, T=25, seed=702), 0, ("mix", "mix", "K3"), "emax0", 0.02, 5, dict(agents_fused=0)),
     # k_sto_update<..., LV 2> (the scan body: 193 <= T <= 512)
     ("copper-T250-scan", dict(n_gen=30, n_sto=6, T=250, seed=703), 0, ("mix", "mix", "K3"), "emax0", 0.02, 4, dict(sto_long=0)),
@@ -95,9 +95,9 @@ ONE = [
     ("net-30x45-overlap", dict(n_gen=120, n_sto=24, T=96, seed=41, **NET30), _capi.F_OVERLAP_AGENTS, ("full", "edge-lo", "K3"), "", 0.01, 4, dict(agents_fused=0)),
     # the wide chain with k_net_agents / k_sto_warm at LV 2
     ("net-30x45-debug-wide", dict(n_gen=120, n_sto=24, T=96, seed=41, **NET30), _capi.F_DEBUG_WIDE_NET, ("mix", "mix", "K3"), "emax0", 0.01, 4, dict(wide_net=1)),
-    # generators alone: k_gen_update_pair_skip_av / the generator launch without storages
+    # generators alone: k_gen_update_pair_skip<MODE, AV> / the generator launch without storages
     ("copper-generators-only", dict(n_gen=400, n_sto=0, T=24, seed=712), 0, (None, None, "KG"), "", 0.02, 5, dict()),
-    # the lean copper body (no level flag): k_agents_l_av
+    # the lean copper body (no level flag): k_agents_l<..., AV>
     ("copper-lean-av", CP, 0, (None, None, "K3"), "", 0.02, 6, dict(agents_fused=1, sto_lean=1)),
     ("copper-lean-no-tail-fuse-av", CP, _capi.F_NO_TAIL_FUSE, (None, None, "K3"), "", 0.02, 5, dict(sto_lean=1)),
 ]
