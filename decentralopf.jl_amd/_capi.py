@@ -85,6 +85,7 @@ F_STO_TERMINAL_LEVEL = 67108864
 F_GEN_AVAILABILITY = 134217728
 F_STO_EFFICIENCY = 268435456
 F_LINE_RATING = 536870912
+F_GEN_QUADRATIC_COST = 1073741824
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -195,6 +196,9 @@ class CApi:
         # line ratings: optional in the same way (Engine.set_line_rating then refuses)
         self._opt("set_line_rating", C.c_int, [ctxp, c_double_p])
         self._opt("multi_set_line_rating", C.c_int, [ctxp, c_double_p])
+        # quadratic generator costs: optional in the same way (Engine.set_quadratic_cost then refuses)
+        self._opt("set_generator_quadratic_cost", C.c_int, [ctxp, c_double_p])
+        self._opt("multi_set_generator_quadratic_cost", C.c_int, [ctxp, c_double_p])
 
     def _opt(self, name, restype, argtypes):
         if hasattr(self.lib, self.prefix + name):
@@ -343,6 +347,22 @@ def _line_rating_params(api: CApi, params: Optional[DopfParams], line_rating, f_
     return q, r.copy()
 
 
+def _quadratic_cost_params(api: CApi, params: Optional[DopfParams], gen_c2, G: int):
+    """(params, c2) for an engine built with gen_c2: the params with F_GEN_QUADRATIC_COST added (a copy), c2 as float64 of length G
+    — or (params, None) when there is nothing to set (gen_c2 None, or all zeros on an API without quadratic costs)."""
+    if gen_c2 is None:
+        return params, None
+    c2 = _f64(gen_c2, G)
+    if not hasattr(api, "set_generator_quadratic_cost"):
+        if np.any(c2 != 0.0):
+            raise DopfError(f"{api.prefix}*: this API has no quadratic generator costs (a non-zero gen_c2; the reference keeps one "
+                            "constant marginal_costs per unit)")
+        return params, None
+    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
+    q.flags |= F_GEN_QUADRATIC_COST
+    return q, c2
+
+
 def _availability_arrays(profiles, profile_of, T: int, G: int):
     """(K, profiles as float64 [t + T*k], profile_of as int32 (G,)) from a (K, T) array (or None) and G indices (or None)."""
     if profiles is None and profile_of is None:
@@ -379,13 +399,15 @@ class Engine:
     F_GEN_AVAILABILITY and calls dopf_set_generator_availability. sto_eta = (eta_c, eta_d) (optional, S values each): the storages'
     charge and discharge efficiencies — sets F_STO_EFFICIENCY and calls dopf_set_storage_efficiency (before the levels: their
     reachability checks then see the efficiencies). line_rating (optional, (L, T)): the lines' limits per timestep — sets
-    F_LINE_RATING and calls dopf_set_line_rating."""
+    F_LINE_RATING and calls dopf_set_line_rating. gen_c2 (optional, G values >= 0): the generators' quadratic cost coefficients —
+    sets F_GEN_QUADRATIC_COST and calls dopf_set_generator_quadratic_cost."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
                  mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
-                 sto_eta=None, line_rating=None):
+                 sto_eta=None, line_rating=None, gen_c2=None):
         self.api = api
+        params, c2 = _quadratic_cost_params(api, params, gen_c2, _f64(gen_mc).size)
         params, rating = _line_rating_params(api, params, line_rating, f_max, int(L), int(T))
         params, eta = _efficiency_params(api, params, sto_eta, _f64(sto_mc).size)
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
@@ -411,6 +433,7 @@ class Engine:
         self._band, self._avail = band, avail
         self._eta = eta
         self._rating = rating
+        self._c2 = c2
         self._ctx = C.c_void_p()
         args = [C.byref(self._ctx), C.byref(prob), C.byref(self.params)]
         if api.has_mode:
@@ -429,6 +452,8 @@ class Engine:
             self.set_availability(*avail)
         if rating is not None:
             self.set_line_rating(rating)
+        if c2 is not None:
+            self.set_quadratic_cost(c2)
 
     # -- lifecycle -----------------------------------------------------------------------------
     def close(self):
@@ -540,6 +565,17 @@ class Engine:
         self._chk(self.api.set_line_rating(self._ctx, _dp(arr)))
         self._rating = None if arr is None else arr.reshape(self.T, self.L).T.copy()
 
+    def set_quadratic_cost(self, c2=None):
+        """dopf_set_generator_quadratic_cost: each generator's quadratic cost coefficient (G finite values >= 0, None = all 0): the
+        cost of generator g at output P is gen_mc[g] P + c2[g] P^2 / 2; needs F_GEN_QUADRATIC_COST. P, D, C, the duals and the
+        iteration counter stay; converged becomes False. Takes effect at the next x-update. A backend without the entry:
+        DopfError (unsupported)."""
+        if not hasattr(self.api, "set_generator_quadratic_cost"):
+            raise DopfError(f"{self.api.prefix}*: this API has no quadratic generator costs (unsupported)")
+        arr = None if c2 is None else _f64(c2, self.G)
+        self._chk(self.api.set_generator_quadratic_cost(self._ctx, _dp(arr)))
+        self._c2 = None if arr is None else arr.copy()
+
     def set_availability(self, profiles=None, profile_of=None):
         """dopf_set_generator_availability: K profiles (K x T, values in [0, 1]) and each generator's profile (G indices, -1 =
         max_generation); both None resets every generator to -1. Needs F_GEN_AVAILABILITY. Takes effect at the next x-update."""
@@ -603,6 +639,8 @@ class Engine:
             kw["sto_eta"] = self._eta
         if "line_rating" in w:
             kw["line_rating"] = w["line_rating"]
+        if getattr(self, "_c2", None) is not None:
+            kw["gen_c2"] = self._c2
         new = Engine(self.api, N=self.N, L=self.L, T=self.T, params=self.params, mode=self._mode, **kw)
         new.set_state(P=w["P"], D=w["D"], C_=w["C"], avg_U=w["avg_U"], avg_K=w["avg_K"], lam=w["lam"], mu=w["mu"], rho=w["rho"],
                       iteration=2)
@@ -762,8 +800,9 @@ class MultiEngine:
 
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
-                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None):
+                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None, gen_c2=None):
         self.api = api
+        params, c2 = _quadratic_cost_params(api, params, gen_c2, _f64(gen_mc).size)
         params, rating = _line_rating_params(api, params, line_rating, f_max, int(L), int(T))
         params, eta = _efficiency_params(api, params, sto_eta, _f64(sto_mc).size)
         params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
@@ -801,6 +840,16 @@ class MultiEngine:
             self.set_availability(*avail)
         if rating is not None:
             self.set_line_rating(rating)
+        if c2 is not None:
+            self.set_quadratic_cost(c2)
+
+    def set_quadratic_cost(self, c2=None):
+        """dopf_multi_set_generator_quadratic_cost: all G generators' quadratic cost coefficients in the caller's order (None = all
+        0); each shard gets its slice."""
+        if not hasattr(self.api, "multi_set_generator_quadratic_cost"):
+            raise DopfError(f"{self.api.prefix}*: this API has no quadratic generator costs (unsupported)")
+        arr = None if c2 is None else _f64(c2, self.G)
+        self._chk(self.api.multi_set_generator_quadratic_cost(self._m, _dp(arr)))
 
     def set_line_rating(self, rating=None):
         """dopf_multi_set_line_rating: the (L, T) table for every shard (None = f_max in every timestep)."""
@@ -878,7 +927,7 @@ class MultiEngine:
 def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                   sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                   sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
-                  line_rating=None) -> dict:
+                  line_rating=None, gen_c2=None) -> dict:
     """dopf_central_solve: the central reference (src/opf_central_reference.jl) as one LP solved on the GPU by a first-order
     primal-dual method. Arguments as Engine (PackedProblem.engine_kwargs()). Returns objective, gap, iterations and the
     reference script's outputs in Julia shapes: P (G,T), D/C/E (S,T), system_price (T), nodal_price (N,T),
@@ -888,8 +937,11 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     checks them as the setters do (DopfError with the setter's message), and E holds levels that include sto_e0.
     sto_eta = (eta_c, eta_d) (S each, in (0, 1]): the storages' charge and discharge efficiencies, as Engine takes them; whenever it is
     given (all ones too) the call is dopf_central_solve_lossy, and E = sto_e0 + cumsum(eta_c C - D / eta_d).
-    line_rating: the device LP takes no line ratings; a table other than f_max in every timestep raises DopfError."""
+    line_rating: the device LP takes no line ratings; a table other than f_max in every timestep raises DopfError.
+    gen_c2: the device LP takes no quadratic costs either; a non-zero coefficient raises DopfError."""
     N, L, T = int(N), int(L), int(T)
+    if gen_c2 is not None and np.any(np.asarray(gen_c2, dtype=np.float64) != 0.0):
+        raise DopfError("dopf_central_solve*: the device LP takes no quadratic generator costs (it solves with gen_mc alone)")
     if line_rating is not None and np.any(np.asarray(line_rating, dtype=np.float64).reshape(L, T) != _f64(f_max, L)[:, None]):
         raise DopfError("dopf_central_solve*: the device LP takes no line ratings (it solves with f_max in every timestep); use "
                         "central.solve_central_packed(..., line_rating=) for a case with ratings")

@@ -175,6 +175,16 @@ class ADMM:
         self.packed.line_rating = None if rating is None else np.asarray(rating, dtype=np.float64).reshape(self.packed.L, self.packed.T).copy()
         self.convergence = Convergence()
 
+    def set_quadratic_cost(self, c2=None) -> None:
+        """Each generator's quadratic cost coefficient (G values >= 0 in the order of `generators`; None = all 0): the cost of
+        output P is marginal_costs * P + c2 * P^2 / 2, and Result.total_costs follows it. Not in the reference (one constant
+        marginal_costs per unit, src/optimization/subproblems.jl:26-40). Needs flags=F_GEN_QUADRATIC_COST (set for you when a
+        Generator has quadratic_costs); the state and the iteration counter stay, the run is no longer converged; takes effect at
+        the next iteration."""
+        self.engine.set_quadratic_cost(c2)
+        self.packed.gen_c2 = None if c2 is None else np.asarray(c2, dtype=np.float64).reshape(self.packed.G).copy()
+        self.convergence = Convergence()
+
     # -- a receding horizon ----------------------------------------------------------------------
     def _new_window(self, demand: np.ndarray) -> None:
         """the host's mirrors of the demand follow the engine's, and the recorded history starts anew for the new window"""

@@ -68,6 +68,9 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
     become rating[l,t] (None: the packed case's table, else f_max in every timestep as in the reference)."""
     from scipy import sparse
     from scipy.optimize import linprog
+    if pp.has_quadratic_cost():
+        raise ValueError("solve_central_packed: the central problem here is an LP; a case with Generator.quadratic_costs is a QP and "
+                         "would be solved with the marginal costs alone")
     N, L, T, G, S = pp.N, pp.L, pp.T, pp.G, pp.S
     nP, nS, nI, nL = G * T, S * T, N * T, L * T
     oD, oC, oE, oI, oU, oK = nP, nP + nS, nP + 2 * nS, nP + 3 * nS, nP + 3 * nS + nI, nP + 3 * nS + nI + nL
@@ -191,6 +194,9 @@ def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Gene
     argument's, else the storages' own) are part of the LP (dopf_central_solve_lossy), as in central_reference."""
     from . import _capi
     pp = pack(nodes, generators, storages, lines)
+    if pp.has_quadratic_cost():
+        raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no quadratic generator "
+                         "costs and would solve with the marginal costs alone")
     if pp.line_rating is not None:
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no line ratings and would "
                          "solve with max_capacity in every timestep; use central_reference for a case with Line.rating")

@@ -174,6 +174,18 @@ int check_line_rating(dopf_ctx *c, const double *rating)
         }
     return DOPF_OK;
 }
+
+// dopf_set_generator_quadratic_cost's checks: the flag, every entry finite and >= 0 (NULL: all 0)
+int check_generator_quadratic_cost(dopf_ctx *c, const double *c2)
+{
+    if (!(c->q.flags & DOPF_F_GEN_QUADRATIC_COST))
+        return fail(c, DOPF_E_UNSUPPORTED, "quadratic generator costs need DOPF_F_GEN_QUADRATIC_COST at dopf_create");
+    if (!c2) return DOPF_OK;
+    for (int g = 0; g < c->v.G; ++g)
+        if (!std::isfinite(c2[g]) || c2[g] < 0.0)
+            return fail(c, DOPF_E_INVALID, "dopf_set_generator_quadratic_cost: c2[%d] is %g (finite and >= 0 wanted)", g, c2[g]);
+    return DOPF_OK;
+}
 }  // namespace dopf
 
 namespace {
@@ -287,7 +299,12 @@ Plan plan_chain(const Shape &sh, unsigned flags, int cus)
                   (L > 0 && (long long)S * p.stoLPS / 256 < 1024)) && !p.stoLong;
     p.genTT = std::min(T, 512);
     p.genR = 512 / p.genTT;
-    p.genTT2 = (L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
+    // DOPF_F_GEN_QUADRATIC_COST: the generators in k_gen_update's QC instantiations, a launch of their own on every shape — no pair
+    // or skip kernels (genTT2 = 0, and with it no one-launch tail: `pairs` below), no k_agents, no k_net_agents. The chain the
+    // same problem runs under DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T; the storages' launch of that chain, with the LV above
+    p.genQuad = G > 0 && (flags & DOPF_F_GEN_QUADRATIC_COST);
+    if (p.genQuad) flags |= DOPF_F_NO_FUSE;
+    p.genTT2 = (!p.genQuad && L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
     p.fuseAgents = p.genTT2 > 0 && p.genTT2 <= 256 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS));
     if (p.fuseAgents) {
         // one launch for all agents pays while its fixed cost matters and every storage block is resident from
@@ -816,7 +833,15 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     } else {
         TRY(dev_upload(c, &v.fmax, std::vector<double>(p->f_max, p->f_max + L)));
     }
-    TRY(dev_upload(c, &v.gen_mc, gmc)); TRY(dev_upload(c, &v.gen_pmax, gpm));
+    if (pl.genQuad) {
+        // DOPF_F_GEN_QUADRATIC_COST: the quadratic coefficients behind the marginal costs (gen_c2), all 0 until the setter
+        std::vector<double> mc2(gmc);
+        mc2.resize(2 * (size_t)G, 0.0);
+        TRY(dev_upload(c, &v.gen_mc, mc2));
+    } else {
+        TRY(dev_upload(c, &v.gen_mc, gmc));
+    }
+    TRY(dev_upload(c, &v.gen_pmax, gpm));
     {
         std::vector<double> mp(2 * (size_t)G);
         for (int i = 0; i < G; ++i) { mp[2 * (size_t)i] = gmc[i]; mp[2 * (size_t)i + 1] = gpm[i]; }
@@ -1578,6 +1603,24 @@ int dopf_set_line_rating(dopf_ctx *c, const double *rating)
     HIPCHK(c, hipGetLastError());
     c->quiet = false;                      // (flags are formed anew under the new limits)
     return read_status(c);
+}
+
+int dopf_set_generator_quadratic_cost(dopf_ctx *c, const double *c2)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_generator_quadratic_cost(c, c2)) return rc;
+    const int G = c->v.G;
+    if (G == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<double> h(G, 0.0);
+    if (c2)
+        for (int i = 0; i < G; ++i) h[i] = c2[c->gen_perm[i]] + 0.0;      // (+ 0.0: a -0.0 is stored as 0.0)
+    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again). The
+    // state stays; the stop test starts over, as after dopf_set_line_rating (nothing derived depends on the costs)
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(gen_c2(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    launch_reset_status(c->v, c->main);
+    HIPCHK(c, hipGetLastError());
+    return read_status(c);          // (synchronises: h may go)
 }
 
 // scratch of dopf_set_demand / dopf_roll_horizon, allocated at the first call (freed with the context's other arrays): the moved

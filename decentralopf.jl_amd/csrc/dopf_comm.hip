@@ -746,6 +746,18 @@ int dopf_multi_set_line_rating(dopf_multi *m, const double *rating)
     return DOPF_OK;
 }
 
+int dopf_multi_set_generator_quadratic_cost(dopf_multi *m, const double *c2)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all coefficients as they were
+        for (int i = 0; i < m->n; ++i) {
+            const double *ci = c2 ? c2 + m->g0[i] : nullptr;
+            const int rc = pass == 0 ? check_generator_quadratic_cost(m->ctx[i], ci) : dopf_set_generator_quadratic_cost(m->ctx[i], ci);
+            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
+        }
+    return DOPF_OK;
+}
+
 int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E)
 {
     if (!m) return DOPF_E_INVALID;

@@ -60,6 +60,7 @@ int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi);   //
 int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta_d);   // those of dopf_set_storage_efficiency
 int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of);   // dopf_set_generator_availability's
 int check_line_rating(dopf_ctx *c, const double *rating);   // those of dopf_set_line_rating (flag, finite, >= 0)
+int check_generator_quadratic_cost(dopf_ctx *c, const double *c2);   // those of dopf_set_generator_quadratic_cost (flag, finite, >= 0)
 void launch_demote_full_rows(const DevView &v, hipStream_t s);   // gen_state 1 -> 2 (the caps changed)
 // dopf_comm.hip
 int check_one_runtime(dopf_ctx *c);           // DOPF_E_UNSUPPORTED when two HIP runtimes are mapped into the process

@@ -122,7 +122,7 @@ struct DevView {
     // problem (read-only)
     const double *demand, *ptdf, *fmax;             // fmax: [l + fmax_ld*t] (DOPF_F_LINE_RATING: the L x T rating table, then dopf_create's L limits)
     const double *ptdfT;                            // [n + N*l]: the transpose, for the price kernel's node-major threads
-    const double *gen_mc, *gen_pmax;
+    const double *gen_mc, *gen_pmax;                // DOPF_F_GEN_QUADRATIC_COST: gen_mc has 2G entries, the quadratic coefficients behind the costs (gen_c2(v))
     const double2 *gen_mp;                          // [g] {mc, pmax} side by side: one 16-byte load per row (streaming blocks)
     const double *sto_mc, *sto_pmax, *sto_emax;     // DOPF_F_STO_INITIAL_LEVEL: sto_emax has 2S entries, the initial levels behind the max levels
                                                     // (sto_e0(v) below): the view, every kernel's argument, keeps its layout;
@@ -194,6 +194,10 @@ __host__ __device__ inline const double **gen_avail_slot(const DevView &v)
     return reinterpret_cast<const double **>(v.gen_state + ((2 * (size_t)v.G + 1) & ~(size_t)1));
 }
 inline size_t gen_state_ints(int G, bool avail) { return avail ? ((2 * (size_t)G + 1) & ~(size_t)1) + 2 : (size_t)G; }
+
+// DOPF_F_GEN_QUADRATIC_COST contexts only (gen_mc then has 2G entries): the generators' quadratic cost coefficients c2[g] behind the
+// marginal costs, sorted order, zeros until dopf_set_generator_quadratic_cost. The cost of row g at output P is gen_mc[g] P + c2[g] P^2 / 2.
+__host__ __device__ inline const double *gen_c2(const DevView &v) { return v.gen_mc + v.G; }
 
 // DOPF_F_GEN_AVAILABILITY (the AV instantiations of the generator bodies, kernels_agents.hip and kernels_central.hip): the row's upper bound at a timestep, cap = pmax * f with f
 // the row's profile value — one fp64 multiply, never contracted into the sums that add it (a kept row adds cap itself, and the full
@@ -269,6 +273,8 @@ struct Plan {
     bool sliceDual;                 // the one-block dual kernel may add k_reduce's slices itself (DevView::sliceDual)
     bool useWarm, stoLean;          // storage warm start (DevView::use_warm); the lean active-set body (sto_lean.h)
     bool genAvail;                  // DOPF_F_GEN_AVAILABILITY: the generator bodies that read the rows' profiles (nothing else of the plan changes)
+    bool genQuad;                   // DOPF_F_GEN_QUADRATIC_COST: the generators run in k_gen_update<.., .., QC> on every shape — no pair, skip or fused
+                                    // generator blocks, no one-launch tail (the chain of DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T)
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those
@@ -386,6 +392,8 @@ void launch_roll_state(const DevView &v, const Plan &p, int k, int iteration, hi
 // dopf_set_line_rating: status as dopf_set_demand leaves it, then the consensus step's derived state under the new limits — the
 // per-(l,t) flags, walk_any / tab_skip and the tables the price kernels write — from the sums in cons (no sums are formed or moved)
 void launch_line_rating(const DevView &v, const Plan &p, hipStream_t s);
+// dopf_set_generator_quadratic_cost: status as dopf_set_line_rating leaves it (nothing derived depends on the costs)
+void launch_reset_status(const DevView &v, hipStream_t s);
 void launch_penalty_sums(const DevView &v, double *out /* [3][N][T], device */, hipStream_t s);   // Result.penalty_term, per node
 void launch_node_results(const DevView &v, double *gen, double *dis, double *chg, hipStream_t s);   // [n + N*t] each, device pointers   // consensus -> inj/s/flow/price (no dual step)
 

@@ -262,7 +262,9 @@ __device__ __forceinline__ void lin_coef(double w, double iw, double kap, double
 // tiling, ceil(T / TT) column passes. k_gen_update<true> runs it with 512 threads, k_net_agents (generators and storages of a
 // network in ONE launch) with 256 and the same R — the same rows meet in the same order, the sums carry the same bits.
 // AV (DOPF_F_GEN_AVAILABILITY): the upper bound is the row's cap (avail_cap) instead of pmax; nothing else changes
-template <int BS, int FL = 4, bool AV = false>
+// QC (DOPF_F_GEN_QUADRATIC_COST): the row's cost is mc P + c2 P^2 / 2 (c2 = gen_c2(v)[g]). Around p0 that is the linear-cost step with
+// mc + c2 p0 for mc and w + c2 for w, both per row; with c2 = 0 every expression below carries the bits of QC = false
+template <int BS, int FL = 4, bool AV = false, bool QC = false>
 __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item, const int TT, const int R)
 {
     __shared__ double red[BS];
@@ -275,6 +277,8 @@ __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item,
     const double *ftab = nullptr;
     const int *prof = nullptr;
     if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
+    const double *c2v = nullptr;
+    if constexpr (QC) c2v = gen_c2(v);
 
     for (int tc = 0; tc < T; tc += TT) {
         const int t = tc + tt;
@@ -289,13 +293,14 @@ __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item,
             const double inv0 = rcp64(slope0 + w);             // (empty table: one piece for every agent of the node)
             const bool keepd = v.keepDeltas || v.walk_any[t];      // the change is needed agent by agent only for walked slack sums
             for (int g0 = it.a0 + r; g0 < it.a1; g0 += FL * R) {         // FL agents' rows in flight per lane (added in row order)
-                double mc[FL], pm[FL], p0[FL];
+                double mc[FL], pm[FL], p0[FL], c2[FL];
                 int pr[FL];
 #pragma unroll
                 for (int u = 0; u < FL; ++u) {
                     const int g = g0 + u * R < it.a1 ? g0 + u * R : g0;
                     mc[u] = v.gen_mc[g]; pm[u] = v.gen_pmax[g]; p0[u] = v.P[(size_t)g * T + t];
                     if constexpr (AV) pr[u] = prof[g];
+                    if constexpr (QC) c2[u] = c2v[g];
                 }
                 if constexpr (AV) {
 #pragma unroll
@@ -307,7 +312,20 @@ __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item,
                     if (g >= it.a1) break;
                     const size_t e = (size_t)g * T + t;
                     double dl;
-                    if (m == 0) {
+                    if constexpr (QC) {
+                        const double mq = mc[u] + c2[u] * p0[u], wq = w + c2[u];       // the row's marginal cost at p0, its curvature
+                        if (m == 0) {
+                            dl = -(mq + psi0) * rcp64(slope0 + wq);
+                        } else {
+                            int lo = 0, hi = m;           // first kink with psi + (w + c2) beta >= -(mc + c2 p0)
+                            while (lo < hi) {
+                                const int mid = (lo + hi) >> 1;
+                                if (psi[mid] + wq * beta[mid] >= -mq) hi = mid; else lo = mid + 1;
+                            }
+                            const int a = lo < m ? lo : m - 1;
+                            dl = beta[a] - (mq + psi[a] + wq * beta[a]) * rcp64(slope[lo] + wq);
+                        }
+                    } else if (m == 0) {
                         dl = -(mc[u] + psi0) * inv0;
                     } else {
                         int lo = 0, hi = m;           // first kink with psi + w beta >= -mc
@@ -323,6 +341,7 @@ __device__ __forceinline__ void gen_lines_body(const DevView &v, const int item,
                     if (keepd) v.dltG[e] = pn - p0[u];
                     acc += pn;
                     cost += mc[u] * pn;
+                    if constexpr (QC) cost += (0.5 * c2[u] * pn) * pn;       // (a statement of its own: with c2 = 0 it adds 0 to the same sum)
                 }
             }
         }
@@ -457,12 +476,12 @@ __device__ __forceinline__ void gen_lines_body2(const DevView &v, const int item
     }
 }
 
-template <bool LINES, bool AV>
+template <bool LINES, bool AV, bool QC = false>
 __device__ __forceinline__ void gen_update_body(const DevView &v)
 {
     if (v.st->halt) return;
     if (LINES) {
-        gen_lines_body<512, 4, AV>(v, blockIdx.x, v.genTT, v.genR);
+        gen_lines_body<512, 4, AV, QC>(v, blockIdx.x, v.genTT, v.genR);
         return;
     }
     __shared__ double red[512];
@@ -476,22 +495,33 @@ __device__ __forceinline__ void gen_update_body(const DevView &v)
     const double *ftab = nullptr;
     const int *prof = nullptr;
     if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
+    const double *c2v = nullptr;
+    if constexpr (QC) c2v = gen_c2(v);
 
     for (int tc = 0; tc < T; tc += TT) {
         const int t = tc + tt;
         double acc = 0.0;
         if (r < R && t < T) {
             // copper plate / no line touches this problem: Psi(d) = price + gamma (s + d)
-            const double shift = (v.price[it.node + N * t] + gam * v.s[t]) * inv;
+            const double psum = v.price[it.node + N * t] + gam * v.s[t];
+            const double shift = psum * inv;
 #pragma unroll 4
             for (int g = it.a0 + r; g < it.a1; g += R) {
                 const size_t e = (size_t)g * T + t;
                 const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
                 const double p0 = v.P[e];
-                const double pn = clampd(p0 - (mc * inv + shift), 0.0, AV ? avail_cap(ftab, T, prof[g], pm, t) : pm);
+                double pn;
+                if constexpr (QC) {
+                    // QC: d = -(mc + c2 p0 + price + gamma s) / (w + gamma + c2), the row's own reciprocal (c2 = 0: the bits of inv)
+                    const double c2 = c2v[g], iq = 1.0 / ((w + gam) + c2);
+                    pn = clampd(p0 - fma(mc + c2 * p0, iq, psum * iq), 0.0, AV ? avail_cap(ftab, T, prof[g], pm, t) : pm);
+                } else {
+                    pn = clampd(p0 - (mc * inv + shift), 0.0, AV ? avail_cap(ftab, T, prof[g], pm, t) : pm);
+                }
                 v.P[e] = pn;
                 acc += pn;
                 cost += mc * pn;
+                if constexpr (QC) cost += (0.5 * c2v[g] * pn) * pn;       // (a statement of its own: with c2 = 0 it adds 0 to the same sum)
             }
         }
         // fixed-order reduction over the R agent lanes that share a timestep (only LDS data crosses these barriers:
@@ -519,10 +549,12 @@ __device__ __forceinline__ void gen_update_body(const DevView &v)
 
 // (AV, here and in the kernels below: DOPF_F_GEN_AVAILABILITY, the generator bodies with the rows' caps. An argument of the kernel
 // itself, so the flagless instantiations keep their code: DESIGN.md 5j)
-template <bool LINES, bool AV = false>
+// (QC: DOPF_F_GEN_QUADRATIC_COST, the rows' quadratic cost terms; its contexts run their generators in this kernel on every shape —
+// plan_chain — so the pair, skip and fused generator blocks have no such argument: DESIGN.md 5p)
+template <bool LINES, bool AV = false, bool QC = false>
 __global__ __launch_bounds__(512) void k_gen_update(DevView v)
 {
-    gen_update_body<LINES, AV>(v);
+    gen_update_body<LINES, AV, QC>(v);
 }
 
 // End of a generator block of the pair kernels: per-column sums of the R agent lanes and the block's cost, every sum in
@@ -854,6 +886,11 @@ void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s)
     if (v.nGenItems == 0) return;
     with_bool(p.genAvail, [&](auto av) {
         constexpr bool AV = decltype(av)::value;
+        if (p.genQuad) {        // DOPF_F_GEN_QUADRATIC_COST: this kernel on every shape (plan_chain has switched the pair kernels and the tail off)
+            if (v.L > 0) hipLaunchKernelGGL((k_gen_update<true, AV, true>), dim3(v.nGenItems), dim3(512), 0, s, v);
+            else hipLaunchKernelGGL((k_gen_update<false, AV, true>), dim3(v.nGenItems), dim3(512), 0, s, v);
+            return;
+        }
         if (v.L > 0) hipLaunchKernelGGL((k_gen_update<true, AV>), dim3(v.nGenItems), dim3(512), 0, s, v);
         else if (v.genTT2 > 0 && v.tail && v.nStoItems == 0) {
             if (v.genSkip) hipLaunchKernelGGL((k_gen_update_pair_skip<2, AV>), dim3(v.nGenItems + 1), dim3(512), 0, s, v);

@@ -2111,4 +2111,9 @@ void launch_line_rating(const DevView &v, const Plan &p, hipStream_t s)
     launch_derive(v, p, s, false);
 }
 
+void launch_reset_status(const DevView &v, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_roll_status, dim3(1), dim3(64), 0, s, v, 0);
+}
+
 }  // namespace dopf

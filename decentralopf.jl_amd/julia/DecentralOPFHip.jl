@@ -131,6 +131,7 @@ const DOPF_F_STO_TERMINAL_LEVEL = 67108864  # include/dopf.h
 const DOPF_F_GEN_AVAILABILITY = 134217728  # include/dopf.h
 const DOPF_F_STO_EFFICIENCY = 268435456  # include/dopf.h
 const DOPF_F_LINE_RATING = 536870912  # include/dopf.h
+const DOPF_F_GEN_QUADRATIC_COST = 1073741824  # include/dopf.h
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -149,8 +150,8 @@ horizon from a given level (see `set_initial_levels!`) need `flags = DOPF_F_STO_
 last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_TERMINAL_LEVEL`; generators that follow an
 availability profile (see `set_availability!`) need `flags = DOPF_F_GEN_AVAILABILITY`; storages with charge / discharge
 efficiencies below 1 (see `set_efficiency!`; the reference's `Storage` type, used verbatim, has no such fields) need
-`flags = DOPF_F_STO_EFFICIENCY`, and line limits per timestep (see `set_line_rating!`) `flags = DOPF_F_LINE_RATING`. Flags combine
-with `|`.
+`flags = DOPF_F_STO_EFFICIENCY`, line limits per timestep (see `set_line_rating!`) `flags = DOPF_F_LINE_RATING`, and quadratic
+generator cost curves (see `set_quadratic_cost!`) `flags = DOPF_F_GEN_QUADRATIC_COST`. Flags combine with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
@@ -296,6 +297,29 @@ function set_line_rating!(admm::ADMM, rating::Union{Nothing, Matrix{Float64}})
             dopf_check_multi(ccall((:dopf_multi_set_line_rating, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi, pr), admm.multi)
         else
             dopf_check(ccall((:dopf_set_line_rating, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, pr), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    set_quadratic_cost!(admm, c2)
+
+The quadratic cost coefficient of each generator (`c2[g] >= 0`, in the order of `generators`; `nothing` = all 0): the cost of output
+`P` is `marginal_costs * P + c2 * P^2 / 2`. The reference keeps one constant `marginal_costs` per unit
+(src/optimization/subproblems.jl:26-40; its `Generator` type, used verbatim, has no such field); the ADMM must have been created
+with `flags = DOPF_F_GEN_QUADRATIC_COST`. The state and the iteration counter stay; takes effect at the next iteration.
+"""
+function set_quadratic_cost!(admm::ADMM, c2::Union{Nothing, Vector{Float64}})
+    G = length(admm.generators)
+    c2 === nothing || length(c2) == G || error("set_quadratic_cost!: expected $G coefficients, got $(length(c2))")
+    p = c2 === nothing ? Ptr{Cdouble}(C_NULL) : pointer(c2)
+    GC.@preserve c2 begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_generator_quadratic_cost, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi, p),
+                             admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_generator_quadratic_cost, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, p), admm.ctx)
         end
     end
     return admm

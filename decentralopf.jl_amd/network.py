@@ -17,6 +17,8 @@ src/optimization/subproblems.jl:150-156): eta_c, eta_d in (0, 1], the level foll
 (DOPF_F_STO_EFFICIENCY).
 Line.rating is not in the reference either (one max_capacity per line for the whole horizon, src/optimization/subproblems.jl:77-78):
 T limits >= 0, |flow[t]| <= rating[t] — a planned derating, a dynamic rating or a security margin per timestep (DOPF_F_LINE_RATING).
+Generator.quadratic_costs is not in the reference either (one constant marginal_costs per unit, src/optimization/subproblems.jl:26-40):
+c2 >= 0, the cost of output P is marginal_costs * P + c2 * P^2 / 2 — a polynomial cost curve (DOPF_F_GEN_QUADRATIC_COST).
 """
 from __future__ import annotations
 
@@ -41,6 +43,7 @@ class Generator:
     plot_color: str
     node: Node
     availability: Optional[Sequence[float]] = None      # T per-unit values in [0, 1]; None = always max_generation (not in the reference)
+    quadratic_costs: float = 0.0                        # c2 >= 0: the cost is marginal_costs * P + c2 * P^2 / 2 (not in the reference)
 
 
 @dataclass(eq=False)
@@ -133,6 +136,7 @@ class PackedProblem:
     sto_eta_c: Optional[np.ndarray] = None      # (S,) Storage.charge_efficiency; None = all 1
     sto_eta_d: Optional[np.ndarray] = None      # (S,) Storage.discharge_efficiency; None = all 1
     line_rating: Optional[np.ndarray] = None    # (L, T) Line.rating (max_capacity where a line has none); None = no line has one
+    gen_c2: Optional[np.ndarray] = None         # (G,) Generator.quadratic_costs; None = all 0
 
     @property
     def G(self):
@@ -161,7 +165,17 @@ class PackedProblem:
             kw["sto_eta"] = self.efficiency()
         if self.line_rating is not None:      # (engines then run with F_LINE_RATING)
             kw["line_rating"] = np.asarray(self.line_rating, dtype=np.float64).reshape(self.L, self.T)
+        if self.has_quadratic_cost():      # (engines then run with F_GEN_QUADRATIC_COST)
+            kw["gen_c2"] = self.quadratic_cost()
         return kw
+
+    def quadratic_cost(self):
+        """c2, float64 (G,), the default filled in: all 0."""
+        return np.zeros(self.G) if self.gen_c2 is None else np.asarray(self.gen_c2, dtype=np.float64)
+
+    def has_quadratic_cost(self) -> bool:
+        """Some generator has a quadratic cost term (a shard: some generator of the whole problem, so that every rank runs with the flag)."""
+        return bool(self.meta.get("quadratic_cost")) or (self.gen_c2 is not None and bool(np.any(np.asarray(self.gen_c2) != 0.0)))
 
     def efficiency(self):
         """(eta_c, eta_d), float64 (S,) each, the defaults filled in: all 1."""
@@ -210,7 +224,7 @@ class PackedProblem:
             sto_mc=self.sto_mc[s0:s1], sto_pmax=self.sto_pmax[s0:s1], sto_emax=self.sto_emax[s0:s1],
             sto_node=self.sto_node[s0:s1],
             meta=dict(self.meta, rank=rank, world=world, gen_range=(g0, g1), sto_range=(s0, s1),
-                      n_agents_global=self.G + self.S),
+                      n_agents_global=self.G + self.S, quadratic_cost=self.has_quadratic_cost()),
             sto_e0=None if self.sto_e0 is None else self.sto_e0[s0:s1],
             sto_end_lo=None if self.sto_end_lo is None else self.sto_end_lo[s0:s1],
             sto_end_hi=None if self.sto_end_hi is None else self.sto_end_hi[s0:s1],
@@ -218,7 +232,8 @@ class PackedProblem:
             gen_avail_of=None if self.gen_avail_of is None else self.gen_avail_of[g0:g1],
             sto_eta_c=None if self.sto_eta_c is None else self.sto_eta_c[s0:s1],
             sto_eta_d=None if self.sto_eta_d is None else self.sto_eta_d[s0:s1],
-            line_rating=self.line_rating)
+            line_rating=self.line_rating,
+            gen_c2=None if self.gen_c2 is None else self.gen_c2[g0:g1])
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -248,6 +263,9 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
             rows.append(a)
         of.append(seen[key])
     has_avail = bool(rows)
+    c2 = f64(g.quadratic_costs for g in generators)
+    if not np.all(np.isfinite(c2)) or np.any(c2 < 0.0):
+        raise ValueError("generator quadratic_costs must be finite and >= 0")
     # line ratings: a table only when some line has one (the others keep max_capacity in every timestep)
     rating = None
     if any(l.rating is not None for l in lines):
@@ -278,4 +296,5 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         gen_avail_of=i32(of) if has_avail else None,
         sto_eta_c=f64(s.charge_efficiency for s in storages),
         sto_eta_d=f64(s.discharge_efficiency for s in storages),
-        line_rating=rating)
+        line_rating=rating,
+        gen_c2=c2)

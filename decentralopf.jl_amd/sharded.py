@@ -130,6 +130,16 @@ class ShardedADMM:
         between the same two steps."""
         self.engine.set_line_rating(rating)
 
+    def set_quadratic_cost(self, c2=None) -> None:
+        """All generators' quadratic cost coefficients (problem.G values >= 0, global order; None = all 0): this rank sets its slice
+        (dopf_set_generator_quadratic_cost; the cost is local to the rank's agents, no sums move). Needs F_GEN_QUADRATIC_COST in the
+        params; every rank calls it between the same two steps."""
+        if c2 is None:
+            self.engine.set_quadratic_cost(None)
+            return
+        g0, g1 = self.shard.meta["gen_range"]
+        self.engine.set_quadratic_cost(np.asarray(c2, dtype=np.float64).reshape(self.problem.G)[g0:g1])
+
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
         max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs

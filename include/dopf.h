@@ -182,6 +182,19 @@ typedef struct dopf_params {
                                   * of the context without the flag, bit for bit, on every chain. dopf_get_agent_slacks, dopf_get_agent_penalty,
                                   * dopf_get_penalty_sums and dopf_debug_table follow the table; dopf_roll_horizon moves it like mu and rho.
                                   * dopf_central_solve, _ex and _lossy take no ratings: they solve with f_max, flag or not. */
+#define DOPF_F_GEN_QUADRATIC_COST 1073741824 /* generators have quadratic cost curves: the context keeps a coefficient c2[g] >= 0 per generator
+                                  * (all 0 until dopf_set_generator_quadratic_cost), and the cost of generator g at output P is
+                                  * gen_mc[g] P + c2[g] P^2 / 2 instead of the reference's one marginal_costs per unit
+                                  * (src/optimization/subproblems.jl:26-40). The generator's step around p0 = P[g,t] is the linear-cost step with
+                                  * gen_mc + c2 p0 for the cost and w_prox + c2 for the proximal weight, both per row. Contexts with the flag run
+                                  * their generators in a launch of their own (k_gen_update) on every shape: no pair or row-skipping kernels, no
+                                  * launch shared with the storages, no one-launch iteration — the chain the same problem runs under
+                                  * DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T. The storages, the consensus step and every other flag work as
+                                  * without it (DOPF_F_WIDE_NETWORK, DOPF_F_LONG_HORIZON, DOPF_F_GEN_AVAILABILITY, DOPF_F_LINE_RATING,
+                                  * DOPF_F_KEEP_DELTAS and the storage flags included). With every c2 = 0 the results are those of the flagless
+                                  * context on that chain, bit for bit. dopf_get_consensus' total_cost, and everything fed from it, is
+                                  * sum gen_mc P + c2 P^2 / 2 (+ the storages' costs). dopf_central_solve, _ex and _lossy solve the LP: they
+                                  * ignore the flag and the coefficients. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -358,6 +371,17 @@ int dopf_set_generator_availability(dopf_ctx *ctx, int32_t n_profiles, const dou
  * Inf or a negative entry. With L == 0 the call returns DOPF_OK and does nothing. */
 int dopf_set_line_rating(dopf_ctx *ctx, const double *rating /* L x T, [l + L*t]; NULL = f_max in every timestep */);
 
+/* DOPF_F_GEN_QUADRATIC_COST: the generators' quadratic cost coefficients, c2[G] in the caller's order of this context's generators,
+ * every value finite and >= 0; NULL = all 0 (also the value until the first call). The cost of generator g at output P becomes
+ * gen_mc[g] P + c2[g] P^2 / 2. Timing and copies as for dopf_set_storage_initial_level: callable between any two calls that iterate,
+ * the values are copied before the call returns, in order on the context's stream, into the device array the captured iteration
+ * graphs read (the graphs stay valid), and take effect at the next x-update. Status as for dopf_set_line_rating: P, D, C, the duals
+ * and the iteration counter are kept; converged becomes 0, halt is formed again from max_iters and the residual maxima are cleared.
+ * The coefficients have no time axis: dopf_roll_horizon and dopf_set_state leave them alone. Contexts joined to a communicator or a
+ * peer exchange need nothing else (the cost is local to the rank's agents). DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID,
+ * naming the entry and storing nothing, for a NaN, an Inf or a negative entry. With G == 0 the call returns DOPF_OK and does nothing. */
+int dopf_set_generator_quadratic_cost(dopf_ctx *ctx, const double *c2 /* G; NULL = all 0 */);
+
 /* ---- a receding horizon: the window's demand and the window itself change in place -------------------------------
  * Replace nothing in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62). Both need no flag, work
  * on every single-GPU chain, keep the captured iteration graphs valid (they write the arrays the graphs read) and return after
@@ -501,6 +525,9 @@ int  dopf_multi_set_storage_efficiency(dopf_multi *m, const double *eta_c, const
 /* all G generators in the caller's order; every shard gets the whole table and its slice of profile_of (checked for every shard
  * before any is stored) */
 int dopf_multi_set_generator_availability(dopf_multi *m, int32_t n_profiles, const double *profiles, const int32_t *profile_of);
+/* dopf_set_generator_quadratic_cost for all G generators, c2[G] in the caller's order (NULL = all 0): each shard gets its slice;
+ * every shard is checked before any value is stored */
+int dopf_multi_set_generator_quadratic_cost(dopf_multi *m, const double *c2);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);
