@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -184,21 +184,12 @@ class CApi:
             self._sig("multi_get_primal", C.c_int, [ctxp, c_double_p, c_double_p, c_double_p, c_double_p])
             self._sig("multi_size", C.c_int32, [ctxp])
             self._sig("multi_ctx", ctxp, [ctxp, C.c_int32])
-            self._sig("set_storage_initial_level", C.c_int, [ctxp, c_double_p])
-            self._sig("multi_set_storage_initial_level", C.c_int, [ctxp, c_double_p])
-            self._sig("set_storage_terminal_level", C.c_int, [ctxp, c_double_p, c_double_p])
-            self._sig("multi_set_storage_terminal_level", C.c_int, [ctxp, c_double_p, c_double_p])
-            self._sig("set_generator_availability", C.c_int, [ctxp, C.c_int32, c_double_p, c_int32_p])
-            self._sig("multi_set_generator_availability", C.c_int, [ctxp, C.c_int32, c_double_p, c_int32_p])
-        # storage efficiencies: optional — the oracle backend loads without them (Engine.set_efficiency then refuses)
-        self._opt("set_storage_efficiency", C.c_int, [ctxp, c_double_p, c_double_p])
-        self._opt("multi_set_storage_efficiency", C.c_int, [ctxp, c_double_p, c_double_p])
-        # line ratings: optional in the same way (Engine.set_line_rating then refuses)
-        self._opt("set_line_rating", C.c_int, [ctxp, c_double_p])
-        self._opt("multi_set_line_rating", C.c_int, [ctxp, c_double_p])
-        # quadratic generator costs: optional in the same way (Engine.set_quadratic_cost then refuses)
-        self._opt("set_generator_quadratic_cost", C.c_int, [ctxp, c_double_p])
-        self._opt("multi_set_generator_quadratic_cost", C.c_int, [ctxp, c_double_p])
+        # the problem extensions' setters (EXTENSIONS below). The older three belong to the HIP library's ABI; the later three are bound
+        # wherever the library exports them — the oracle backend loads without them (Engine's setter then refuses)
+        for x in EXTENSIONS:
+            if x.optional or prefix == "dopf_":
+                for name in (x.entry, "multi_" + x.entry):
+                    (self._opt if x.optional else self._sig)(name, C.c_int, [ctxp] + list(x.argtypes))
 
     def _opt(self, name, restype, argtypes):
         if hasattr(self.lib, self.prefix + name):
@@ -273,94 +264,22 @@ def default_params(**kw) -> DopfParams:
     return q
 
 
-def _initial_level_params(api: CApi, params: Optional[DopfParams], sto_e0, S: int):
-    """(params, e0) for an engine built with sto_e0: the params with F_STO_INITIAL_LEVEL added (a copy), e0 as float64 of
-    length S — or (params, None) when there is nothing to set (sto_e0 None, or all zeros on an API without initial levels)."""
-    if sto_e0 is None:
-        return params, None
-    e0 = _f64(sto_e0, S)
-    if not hasattr(api, "set_storage_initial_level"):
-        if np.any(e0 != 0.0):
-            raise DopfError(f"{api.prefix}*: this API has no storage initial levels (non-zero sto_e0; the reference starts "
-                            "every storage empty)")
-        return params, None
-    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
-    q.flags |= F_STO_INITIAL_LEVEL
-    return q, e0
-
-
-def _terminal_level_params(api: CApi, params: Optional[DopfParams], sto_end_lo, sto_end_hi, sto_emax, S: int):
-    """(params, (lo, hi)) for an engine built with a terminal band: the params with F_STO_TERMINAL_LEVEL added (a copy), the band
-    as float64 arrays of length S (a None side: 0 resp. sto_emax) — or (params, None) when there is nothing to set (both None, or
-    the default band [0, max_level] on an API without terminal levels)."""
-    if sto_end_lo is None and sto_end_hi is None:
-        return params, None
-    em = _f64(sto_emax, S)
-    lo = np.zeros(S) if sto_end_lo is None else _f64(sto_end_lo, S)
-    hi = em.copy() if sto_end_hi is None else _f64(sto_end_hi, S)
-    if not hasattr(api, "set_storage_terminal_level"):
-        if np.any(lo != 0.0) or np.any(hi != em):
-            raise DopfError(f"{api.prefix}*: this API has no storage terminal levels (a band other than [0, max_level]; the "
-                            "reference leaves the last level free)")
-        return params, None
-    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
-    q.flags |= F_STO_TERMINAL_LEVEL
-    return q, (lo, hi)
-
-
-def _efficiency_params(api: CApi, params: Optional[DopfParams], sto_eta, S: int):
-    """(params, (eta_c, eta_d)) for an engine built with sto_eta = (eta_c, eta_d): the params with F_STO_EFFICIENCY added (a copy),
-    both as float64 of length S — or (params, None) when there is nothing to set (sto_eta None, or all ones on an API without
-    efficiencies)."""
-    if sto_eta is None:
-        return params, None
-    ec, ed = _f64(sto_eta[0], S), _f64(sto_eta[1], S)
-    if not hasattr(api, "set_storage_efficiency"):
-        if np.any(ec != 1.0) or np.any(ed != 1.0):
-            raise DopfError(f"{api.prefix}*: this API has no storage efficiencies (a value other than 1; the reference's storages "
-                            "are lossless)")
-        return params, None
-    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
-    q.flags |= F_STO_EFFICIENCY
-    return q, (ec, ed)
+def _problem(N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax, sto_node):
+    """(prob, keep, G, S): the dopf_problem of the ten base arrays, and the arrays its pointers point into (keep them alive)."""
+    gen_mc, sto_mc = _f64(gen_mc), _f64(sto_mc)
+    G, S = gen_mc.size, sto_mc.size
+    keep = dict(demand=_f64(demand, N * T), ptdf=_f64(ptdf, L * N), f_max=_f64(f_max, L), gen_mc=gen_mc,
+                gen_pmax=_f64(gen_pmax, G), gen_node=_i32(gen_node, G), sto_mc=sto_mc, sto_pmax=_f64(sto_pmax, S),
+                sto_emax=_f64(sto_emax, S), sto_node=_i32(sto_node, S))
+    prob = DopfProblem(N=N, L=L, T=T, G=G, S=S)
+    for k, v in keep.items():
+        setattr(prob, k, v.ctypes.data_as(c_int32_p if v.dtype == np.int32 else c_double_p))
+    return prob, keep, G, S
 
 
 def _rating_buffer(rating, L: int, T: int) -> np.ndarray:
     """An (L, T) table as the C ABI's [l + L*t] buffer."""
     return _f64(np.asarray(rating, dtype=np.float64).reshape(L, T).T, L * T)
-
-
-def _line_rating_params(api: CApi, params: Optional[DopfParams], line_rating, f_max, L: int, T: int):
-    """(params, rating) for an engine built with line_rating, an (L, T) table: the params with F_LINE_RATING added (a copy), the
-    table as float64 (L, T) — or (params, None) when there is nothing to set (line_rating None, or every column equal to f_max on
-    an API without line ratings)."""
-    if line_rating is None:
-        return params, None
-    r = np.asarray(line_rating, dtype=np.float64).reshape(L, T)
-    if not hasattr(api, "set_line_rating"):
-        if np.any(r != _f64(f_max, L)[:, None]):
-            raise DopfError(f"{api.prefix}*: this API has no line ratings (a rating other than f_max; the reference keeps one "
-                            "max_capacity per line)")
-        return params, None
-    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
-    q.flags |= F_LINE_RATING
-    return q, r.copy()
-
-
-def _quadratic_cost_params(api: CApi, params: Optional[DopfParams], gen_c2, G: int):
-    """(params, c2) for an engine built with gen_c2: the params with F_GEN_QUADRATIC_COST added (a copy), c2 as float64 of length G
-    — or (params, None) when there is nothing to set (gen_c2 None, or all zeros on an API without quadratic costs)."""
-    if gen_c2 is None:
-        return params, None
-    c2 = _f64(gen_c2, G)
-    if not hasattr(api, "set_generator_quadratic_cost"):
-        if np.any(c2 != 0.0):
-            raise DopfError(f"{api.prefix}*: this API has no quadratic generator costs (a non-zero gen_c2; the reference keeps one "
-                            "constant marginal_costs per unit)")
-        return params, None
-    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
-    q.flags |= F_GEN_QUADRATIC_COST
-    return q, c2
 
 
 def _availability_arrays(profiles, profile_of, T: int, G: int):
@@ -372,25 +291,138 @@ def _availability_arrays(profiles, profile_of, T: int, G: int):
     return int(prof.shape[0]), np.ascontiguousarray(prof).ravel(), of
 
 
-def _availability_params(api: CApi, params: Optional[DopfParams], gen_avail, gen_avail_of, T: int, G: int):
-    """(params, (profiles, profile_of)) for an engine built with availability profiles: the params with F_GEN_AVAILABILITY added
-    (a copy) — or (params, None) when there is nothing to set (both None, or every generator on -1 / an all-ones profile on an API
-    without availability)."""
-    if gen_avail is None and gen_avail_of is None:
-        return params, None
-    K, prof, of = _availability_arrays(gen_avail, gen_avail_of, T, G)
-    if not hasattr(api, "set_generator_availability"):
-        used = [] if of is None else sorted({int(k) for k in of if k >= 0})
-        if any(k >= K or np.any(prof.reshape(K, T)[k] != 1.0) for k in used):
-            raise DopfError(f"{api.prefix}*: this API has no generator availability (a profile other than all ones; the "
-                            "reference keeps every generator at max_generation)")
-        return params, None
-    q = DopfParams.from_buffer_copy(params if params is not None else default_params())
-    q.flags |= F_GEN_AVAILABILITY
-    return q, (prof.reshape(K, T), of)
+# ---- the problem extensions ------------------------------------------------------------------------------------------------------
+# One row per optional input of the problem; CApi, Engine and MultiEngine read everything they do about an extension from its row.
+# `d` is whoever knows the sizes (an Engine or MultiEngine: d.L, d.T, d.G, d.S), `keep` the base arrays of _problem.
+
+class Extension(NamedTuple):
+    keys: tuple             # the constructor's keyword(s), and the mirror's keys
+    flag: int               # the DOPF_F_* that dopf_create needs
+    entry: str              # the C entry behind the prefix; "multi_" + entry is the dopf_multi form
+    argtypes: tuple         # its ctypes argtypes behind the context
+    setter: str             # the method of Engine, MultiEngine, ADMM and ShardedADMM
+    what: str               # "this API has no <what>": the setter's refusal on an API without the entry
+    why: str                # "this API has no <what> (<why>)": the constructor's refusal of a non-default value there
+    norm: Callable          # (d, *values) -> the arrays the entry takes, as the mirror keeps them (None stays None)
+    is_default: Callable    # (d, keep, *arrays) -> True where they say what a problem without the extension says
+    cargs: Callable = lambda d, *arrays: tuple(_dp(a) for a in arrays)      # (d, *arrays) -> the entry's arguments behind the context
+    fill: Optional[Callable] = None     # (d, keep, *arrays) -> arrays: how the constructor completes a value given in part
+    optional: bool = False  # bound wherever the library exports it, under any prefix, and the setter's refusal ends in " (unsupported)";
+    #                         False: part of the "dopf_" ABI, bound under that prefix alone
+
+    @property
+    def packed(self) -> bool:
+        """one keyword for several arrays: the constructor and the mirror hold them as a tuple"""
+        return len(self.keys) == 1 and len(self.argtypes) > 1
+
+    def refusal(self, api, setter: bool) -> str:
+        tail = (" (unsupported)" if self.optional else "") if setter else f" ({self.why})"
+        return f"{api.prefix}*: this API has no {self.what}{tail}"
 
 
-class Engine:
+def _per_storage(d, *values):
+    return tuple(None if v is None else _f64(v, d.S) for v in values)
+
+
+def _availability_norm(d, profiles, profile_of):
+    K, prof, of = _availability_arrays(profiles, profile_of, d.T, d.G)
+    return None if prof is None else prof.reshape(K, d.T), of
+
+
+def _availability_is_default(d, keep, prof, of):
+    used = [] if of is None else sorted({int(k) for k in of if k >= 0})
+    return not any(k >= prof.shape[0] or np.any(prof[k] != 1.0) for k in used)
+
+
+def _availability_cargs(d, prof, of):
+    return (0 if prof is None else prof.shape[0], _dp(None if prof is None else prof.ravel()),
+            None if of is None else of.ctypes.data_as(c_int32_p))
+
+
+# in the order the constructors apply them: the efficiencies before the levels, whose reachability checks then see them
+EXTENSIONS = (
+    Extension(keys=("sto_eta",), flag=F_STO_EFFICIENCY, entry="set_storage_efficiency", argtypes=(c_double_p, c_double_p),
+              setter="set_efficiency", optional=True,
+              what="storage efficiencies", why="a value other than 1; the reference's storages are lossless",
+              norm=_per_storage, is_default=lambda d, keep, ec, ed: not (np.any(ec != 1.0) or np.any(ed != 1.0))),
+    Extension(keys=("sto_e0",), flag=F_STO_INITIAL_LEVEL, entry="set_storage_initial_level", argtypes=(c_double_p,),
+              setter="set_initial_levels",
+              what="storage initial levels", why="non-zero sto_e0; the reference starts every storage empty",
+              norm=_per_storage, is_default=lambda d, keep, e0: not np.any(e0 != 0.0)),
+    Extension(keys=("sto_end_lo", "sto_end_hi"), flag=F_STO_TERMINAL_LEVEL, entry="set_storage_terminal_level",
+              argtypes=(c_double_p, c_double_p), setter="set_terminal_levels",
+              what="storage terminal levels", why="a band other than [0, max_level]; the reference leaves the last level free",
+              norm=_per_storage, is_default=lambda d, keep, lo, hi: not (np.any(lo != 0.0) or np.any(hi != keep["sto_emax"])),
+              fill=lambda d, keep, lo, hi: (np.zeros(d.S) if lo is None else lo, keep["sto_emax"].copy() if hi is None else hi)),
+    Extension(keys=("gen_avail", "gen_avail_of"), flag=F_GEN_AVAILABILITY, entry="set_generator_availability",
+              argtypes=(C.c_int32, c_double_p, c_int32_p), setter="set_availability",
+              what="generator availability",
+              why="a profile other than all ones; the reference keeps every generator at max_generation",
+              norm=_availability_norm, is_default=_availability_is_default, cargs=_availability_cargs),
+    Extension(keys=("line_rating",), flag=F_LINE_RATING, entry="set_line_rating", argtypes=(c_double_p,),
+              setter="set_line_rating", optional=True,
+              what="line ratings", why="a rating other than f_max; the reference keeps one max_capacity per line",
+              norm=lambda d, r: (None if r is None else np.asarray(r, dtype=np.float64).reshape(d.L, d.T),),
+              is_default=lambda d, keep, r: not np.any(r != keep["f_max"][:, None]),
+              cargs=lambda d, r: (_dp(None if r is None else _rating_buffer(r, d.L, d.T)),)),
+    Extension(keys=("gen_c2",), flag=F_GEN_QUADRATIC_COST, entry="set_generator_quadratic_cost", argtypes=(c_double_p,),
+              setter="set_quadratic_cost", optional=True,
+              what="quadratic generator costs", why="a non-zero gen_c2; the reference keeps one constant marginal_costs per unit",
+              norm=lambda d, c2: (None if c2 is None else _f64(c2, d.G),), is_default=lambda d, keep, c2: not np.any(c2 != 0.0)),
+)
+_BY_SETTER = {x.setter: x for x in EXTENSIONS}
+
+
+def _extensions(api: CApi, params: Optional[DopfParams], d, keep: dict, kw: dict):
+    """(params, todo) for a context built with the extensions' constructor keywords in kw: the params with the flags of those given
+    added (a copy), and todo, the (extension, arrays) to apply behind create, in EXTENSIONS' order. Nothing to set: a keyword left
+    None, or its default value on an API without the entry (a non-default value there: DopfError)."""
+    todo = []
+    for x in EXTENSIONS:
+        given = [kw.get(k) for k in x.keys]
+        if all(v is None for v in given):
+            continue
+        arrays = x.norm(d, *(given[0] if x.packed else given))
+        if all(a is None for a in arrays):
+            continue
+        if x.fill:
+            arrays = x.fill(d, keep, *arrays)
+        if not hasattr(api, x.entry):
+            if not x.is_default(d, keep, *arrays):
+                raise DopfError(x.refusal(api, setter=False))
+            continue
+        todo.append((x, arrays))
+    if todo:
+        params = DopfParams.from_buffer_copy(params if params is not None else default_params())
+        for x, _ in todo:
+            params.flags |= x.flag
+    return params, todo
+
+
+class _ExtensionSetters:
+    """What Engine and MultiEngine share of the extensions: the constructor's pass over EXTENSIONS and the one path of every setter.
+    The class says which object the entries take (_handle) and which form of the entry (_entry_prefix)."""
+    _entry_prefix = ""
+
+    def _set(self, setter: str, *values) -> dict:
+        """The extension's entry with the values normalised; returns them as the mirror holds them: {constructor keyword: value}."""
+        x = _BY_SETTER[setter]
+        fn = getattr(self.api, self._entry_prefix + x.entry, None)
+        if fn is None:
+            raise DopfError(x.refusal(self.api, setter=True))
+        arrays = x.norm(self, *values)
+        self._chk(fn(self._handle(), *x.cargs(self, *arrays)))
+        if all(a is None for a in arrays):
+            return dict.fromkeys(x.keys)
+        arrays = tuple(None if a is None else a.copy() for a in arrays)
+        return {x.keys[0]: arrays} if x.packed else dict(zip(x.keys, arrays))
+
+    def _apply(self, todo) -> None:
+        for x, arrays in todo:
+            getattr(self, x.setter)(*arrays)
+
+
+class Engine(_ExtensionSetters):
     """A context of the C ABI with numpy in/out. Mirrors include/dopf.h one to one.
     sto_e0 (optional, S values): the storages' initial levels — sets F_STO_INITIAL_LEVEL and calls
     dopf_set_storage_initial_level after create. sto_end_lo / sto_end_hi (optional, S values each): the band of the level
@@ -407,33 +439,16 @@ class Engine:
                  mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
                  sto_eta=None, line_rating=None, gen_c2=None):
         self.api = api
-        params, c2 = _quadratic_cost_params(api, params, gen_c2, _f64(gen_mc).size)
-        params, rating = _line_rating_params(api, params, line_rating, f_max, int(L), int(T))
-        params, eta = _efficiency_params(api, params, sto_eta, _f64(sto_mc).size)
-        params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
-        params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
-        params, avail = _availability_params(api, params, gen_avail, gen_avail_of, int(T), _f64(gen_mc).size)
         self.N, self.L, self.T = int(N), int(L), int(T)
-        gen_mc = _f64(gen_mc)
-        sto_mc = _f64(sto_mc)
-        self.G, self.S = gen_mc.size, sto_mc.size
-        keep = dict(
-            demand=_f64(demand, self.N * self.T), ptdf=_f64(ptdf, self.L * self.N),
-            f_max=_f64(f_max, self.L), gen_mc=gen_mc, gen_pmax=_f64(gen_pmax, self.G),
-            gen_node=_i32(gen_node, self.G), sto_mc=sto_mc, sto_pmax=_f64(sto_pmax, self.S),
-            sto_emax=_f64(sto_emax, self.S), sto_node=_i32(sto_node, self.S))
-        prob = DopfProblem(N=self.N, L=self.L, T=self.T, G=self.G, S=self.S)
-        for k, v in keep.items():
-            ptr = v.ctypes.data_as(c_int32_p if v.dtype == np.int32 else c_double_p)
-            setattr(prob, k, ptr)
+        prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
+                                              sto_mc, sto_pmax, sto_emax, sto_node)
+        params, todo = _extensions(api, params, self, keep, dict(
+            sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
+            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2))
         self.params = params if params is not None else default_params()
         # what a window change needs of the problem: the arrays as handed to create, and the inputs of the setters as they stand
-        self._keep, self._mode = keep, mode
-        self._e0 = None if e0 is None else e0.copy()
-        self._band, self._avail = band, avail
-        self._eta = eta
-        self._rating = rating
-        self._c2 = c2
+        # (by constructor keyword, in the form the constructor takes them)
+        self._keep, self._mode, self._mirror = keep, mode, {}
         self._ctx = C.c_void_p()
         args = [C.byref(self._ctx), C.byref(prob), C.byref(self.params)]
         if api.has_mode:
@@ -442,18 +457,14 @@ class Engine:
         if rc != 0:
             msg = api.last_error(None)
             raise DopfError(f"{api.prefix}create failed ({rc}): {msg.decode() if msg else ''}")
-        if eta is not None:
-            self.set_efficiency(*eta)
-        if e0 is not None:
-            self.set_initial_levels(e0)
-        if band is not None:
-            self.set_terminal_levels(*band)
-        if avail is not None:
-            self.set_availability(*avail)
-        if rating is not None:
-            self.set_line_rating(rating)
-        if c2 is not None:
-            self.set_quadratic_cost(c2)
+        self._apply(todo)
+
+    def _handle(self):
+        return self._ctx
+
+    @property
+    def _eta(self):
+        return self._mirror.get("sto_eta")
 
     # -- lifecycle -----------------------------------------------------------------------------
     def close(self):
@@ -528,62 +539,36 @@ class Engine:
     def set_initial_levels(self, e0=None):
         """dopf_set_storage_initial_level: the level of each storage before timestep 0 (S values, None = all 0); needs
         F_STO_INITIAL_LEVEL. Takes effect at the next x-update."""
-        if not hasattr(self.api, "set_storage_initial_level"):
-            raise DopfError(f"{self.api.prefix}*: this API has no storage initial levels")
-        arr = None if e0 is None else _f64(e0, self.S)
-        self._chk(self.api.set_storage_initial_level(self._ctx, _dp(arr)))
-        self._e0 = None if arr is None else arr.copy()
+        self._mirror.update(self._set("set_initial_levels", e0))
 
     def set_terminal_levels(self, lo=None, hi=None):
         """dopf_set_storage_terminal_level: the band [lo, hi] of each storage's level after the last timestep (S values each;
         both None = the default band [0, max_level]); needs F_STO_TERMINAL_LEVEL. Takes effect at the next x-update."""
-        if not hasattr(self.api, "set_storage_terminal_level"):
-            raise DopfError(f"{self.api.prefix}*: this API has no storage terminal levels")
-        a = None if lo is None else _f64(lo, self.S)
-        b = None if hi is None else _f64(hi, self.S)
-        self._chk(self.api.set_storage_terminal_level(self._ctx, _dp(a), _dp(b)))
-        self._band = None if a is None and b is None else (a, b)
+        self._mirror.update(self._set("set_terminal_levels", lo, hi))
 
     def set_efficiency(self, eta_c=None, eta_d=None):
         """dopf_set_storage_efficiency: each storage's charge and discharge efficiency in (0, 1] (S values each; both None = all
         1); needs F_STO_EFFICIENCY. The level then follows E_t = E_{t-1} + eta_c C_t - D_t / eta_d. Takes effect at the next
         x-update. A backend without the entry: DopfError (unsupported)."""
-        if not hasattr(self.api, "set_storage_efficiency"):
-            raise DopfError(f"{self.api.prefix}*: this API has no storage efficiencies (unsupported)")
-        a = None if eta_c is None else _f64(eta_c, self.S)
-        b = None if eta_d is None else _f64(eta_d, self.S)
-        self._chk(self.api.set_storage_efficiency(self._ctx, _dp(a), _dp(b)))
-        self._eta = None if a is None and b is None else (a, b)
+        self._mirror.update(self._set("set_efficiency", eta_c, eta_d))
 
     def set_line_rating(self, rating=None):
         """dopf_set_line_rating: the lines' limits per timestep, an (L, T) array of finite values >= 0 (None = f_max in every
         timestep); needs F_LINE_RATING. P, D, C, the duals, flows and the iteration counter stay; converged becomes False. Takes
         effect at the next x-update. A backend without the entry: DopfError (unsupported)."""
-        if not hasattr(self.api, "set_line_rating"):
-            raise DopfError(f"{self.api.prefix}*: this API has no line ratings (unsupported)")
-        arr = None if rating is None else _rating_buffer(rating, self.L, self.T)
-        self._chk(self.api.set_line_rating(self._ctx, _dp(arr)))
-        self._rating = None if arr is None else arr.reshape(self.T, self.L).T.copy()
+        self._mirror.update(self._set("set_line_rating", rating))
 
     def set_quadratic_cost(self, c2=None):
         """dopf_set_generator_quadratic_cost: each generator's quadratic cost coefficient (G finite values >= 0, None = all 0): the
         cost of generator g at output P is gen_mc[g] P + c2[g] P^2 / 2; needs F_GEN_QUADRATIC_COST. P, D, C, the duals and the
         iteration counter stay; converged becomes False. Takes effect at the next x-update. A backend without the entry:
         DopfError (unsupported)."""
-        if not hasattr(self.api, "set_generator_quadratic_cost"):
-            raise DopfError(f"{self.api.prefix}*: this API has no quadratic generator costs (unsupported)")
-        arr = None if c2 is None else _f64(c2, self.G)
-        self._chk(self.api.set_generator_quadratic_cost(self._ctx, _dp(arr)))
-        self._c2 = None if arr is None else arr.copy()
+        self._mirror.update(self._set("set_quadratic_cost", c2))
 
     def set_availability(self, profiles=None, profile_of=None):
         """dopf_set_generator_availability: K profiles (K x T, values in [0, 1]) and each generator's profile (G indices, -1 =
         max_generation); both None resets every generator to -1. Needs F_GEN_AVAILABILITY. Takes effect at the next x-update."""
-        if not hasattr(self.api, "set_generator_availability"):
-            raise DopfError(f"{self.api.prefix}*: this API has no generator availability")
-        K, prof, of = _availability_arrays(profiles, profile_of, self.T, self.G)
-        self._chk(self.api.set_generator_availability(self._ctx, K, _dp(prof), None if of is None else of.ctypes.data_as(c_int32_p)))
-        self._avail = None if prof is None and of is None else (None if prof is None else prof.reshape(K, self.T), of)
+        self._mirror.update(self._set("set_availability", profiles, profile_of))
 
     # -- a receding horizon --------------------------------------------------------------------
     def demand(self) -> np.ndarray:
@@ -614,11 +599,12 @@ class Engine:
             raise ValueError(f"roll: k = {k} outside [1, T - 1 = {self.T - 1}]")
         tail = np.asarray(demand_tail, dtype=np.float64).reshape(self.N, k)
         if native:
-            # (the initial levels now live on the device only; the host route, which reads self._e0, is never taken with this API)
+            # (the initial levels now live on the device only; the host route, which reads the mirror, is never taken with this API)
             self._chk(self.api.roll_horizon(self._ctx, k, _dp(_f64(tail.T, self.N * k))))
             self._keep["demand"] = _f64(np.concatenate([self.demand()[:, k:], tail], axis=1).T)
-            if getattr(self, "_rating", None) is not None:          # (the library moved its table by the same rule)
-                self._rating = np.concatenate([self._rating[:, k:], np.repeat(self._rating[:, -1:], k, axis=1)], axis=1)
+            r = self._mirror.get("line_rating")
+            if r is not None:          # (the library moved its table by the same rule)
+                self._mirror["line_rating"] = np.concatenate([r[:, k:], np.repeat(r[:, -1:], k, axis=1)], axis=1)
             return
         if self.S and not self.params.flags & F_STO_INITIAL_LEVEL:          # (the native entry's refusal, DOPF_E_UNSUPPORTED)
             raise DopfError(f"roll: the storages' levels after {k} steps become the next window's initial levels, which need "
@@ -627,20 +613,12 @@ class Engine:
         lam, mu, rho = self.get_duals()
         _, aU, aK, _, _ = self.get_consensus()
         w = shift_window(k, tail, demand=self.demand(), P=P, D=D, C=Cc, E=E, lam=lam, mu=mu, rho=rho, avg_U=aU, avg_K=aK,
-                         sto_emax=self._keep["sto_emax"], line_rating=getattr(self, "_rating", None))
-        kw = dict(self._keep, demand=_f64(w["demand"].T))
+                         sto_emax=self._keep["sto_emax"], line_rating=self._mirror.get("line_rating"))
+        kw = dict(self._keep, **self._mirror, demand=_f64(w["demand"].T))
         if self.S:
             kw["sto_e0"] = w["e0"]
-        if self._band is not None:
-            kw["sto_end_lo"], kw["sto_end_hi"] = self._band
-        if self._avail is not None:
-            kw["gen_avail"], kw["gen_avail_of"] = self._avail
-        if self._eta is not None:
-            kw["sto_eta"] = self._eta
         if "line_rating" in w:
             kw["line_rating"] = w["line_rating"]
-        if getattr(self, "_c2", None) is not None:
-            kw["gen_c2"] = self._c2
         new = Engine(self.api, N=self.N, L=self.L, T=self.T, params=self.params, mode=self._mode, **kw)
         new.set_state(P=w["P"], D=w["D"], C_=w["C"], avg_U=w["avg_U"], avg_K=w["avg_K"], lam=w["lam"], mu=w["mu"], rho=w["rho"],
                       iteration=2)
@@ -789,37 +767,27 @@ class _ShardView(Engine):
     def __init__(self, api: CApi, ctx, N, L, T, G, S):     # noqa: super().__init__ deliberately not called
         self.api, self._ctx = api, ctx
         self.N, self.L, self.T, self.G, self.S = N, L, T, G, S
+        self._mirror = {}
 
     def close(self):
         self._ctx = C.c_void_p()
 
 
-class MultiEngine:
+class MultiEngine(_ExtensionSetters):
     """One process, n GPUs: dopf_multi_* (the library shards the agents, owns the RCCL communicator and one host
     thread per device). Replicated state (duals, consensus, prices, residuals) is read from shard 0."""
+    _entry_prefix = "multi_"
 
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
                  sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None, gen_c2=None):
         self.api = api
-        params, c2 = _quadratic_cost_params(api, params, gen_c2, _f64(gen_mc).size)
-        params, rating = _line_rating_params(api, params, line_rating, f_max, int(L), int(T))
-        params, eta = _efficiency_params(api, params, sto_eta, _f64(sto_mc).size)
-        params, e0 = _initial_level_params(api, params, sto_e0, _f64(sto_mc).size)
-        params, band = _terminal_level_params(api, params, sto_end_lo, sto_end_hi, sto_emax, _f64(sto_mc).size)
-        params, avail = _availability_params(api, params, gen_avail, gen_avail_of, int(T), _f64(gen_mc).size)
         self.N, self.L, self.T = int(N), int(L), int(T)
-        gen_mc = _f64(gen_mc)
-        sto_mc = _f64(sto_mc)
-        self.G, self.S = gen_mc.size, sto_mc.size
-        keep = dict(
-            demand=_f64(demand, self.N * self.T), ptdf=_f64(ptdf, self.L * self.N),
-            f_max=_f64(f_max, self.L), gen_mc=gen_mc, gen_pmax=_f64(gen_pmax, self.G),
-            gen_node=_i32(gen_node, self.G), sto_mc=sto_mc, sto_pmax=_f64(sto_pmax, self.S),
-            sto_emax=_f64(sto_emax, self.S), sto_node=_i32(sto_node, self.S))
-        prob = DopfProblem(N=self.N, L=self.L, T=self.T, G=self.G, S=self.S)
-        for k, v in keep.items():
-            setattr(prob, k, v.ctypes.data_as(c_int32_p if v.dtype == np.int32 else c_double_p))
+        prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
+                                              sto_mc, sto_pmax, sto_emax, sto_node)
+        params, todo = _extensions(api, params, self, keep, dict(
+            sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
+            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2))
         self.params = params if params is not None else default_params()
         dev = None if devices is None else _i32(devices, n_gpus)
         self._m = C.c_void_p()
@@ -829,60 +797,37 @@ class MultiEngine:
             msg = api.multi_last_error(None)
             raise DopfError(f"dopf_multi_create failed ({rc}): {msg.decode() if msg else ''}")
         self.n = int(api.multi_size(self._m))
-        self._eta = None
-        if eta is not None:
-            self.set_efficiency(*eta)
-        if e0 is not None:
-            self.set_initial_levels(e0)
-        if band is not None:
-            self.set_terminal_levels(*band)
-        if avail is not None:
-            self.set_availability(*avail)
-        if rating is not None:
-            self.set_line_rating(rating)
-        if c2 is not None:
-            self.set_quadratic_cost(c2)
+        self._mirror = {}           # (of the extensions' inputs, the efficiencies alone)
+        self._apply(todo)
+
+    def _handle(self):
+        return self._m
 
     def set_quadratic_cost(self, c2=None):
         """dopf_multi_set_generator_quadratic_cost: all G generators' quadratic cost coefficients in the caller's order (None = all
         0); each shard gets its slice."""
-        if not hasattr(self.api, "multi_set_generator_quadratic_cost"):
-            raise DopfError(f"{self.api.prefix}*: this API has no quadratic generator costs (unsupported)")
-        arr = None if c2 is None else _f64(c2, self.G)
-        self._chk(self.api.multi_set_generator_quadratic_cost(self._m, _dp(arr)))
+        self._set("set_quadratic_cost", c2)
 
     def set_line_rating(self, rating=None):
         """dopf_multi_set_line_rating: the (L, T) table for every shard (None = f_max in every timestep)."""
-        if not hasattr(self.api, "multi_set_line_rating"):
-            raise DopfError(f"{self.api.prefix}*: this API has no line ratings (unsupported)")
-        arr = None if rating is None else _rating_buffer(rating, self.L, self.T)
-        self._chk(self.api.multi_set_line_rating(self._m, _dp(arr)))
+        self._set("set_line_rating", rating)
 
     def set_availability(self, profiles=None, profile_of=None):
         """dopf_multi_set_generator_availability: K profiles (K x T) and all G generators' indices in the caller's order (every
         shard gets the whole table and its slice); both None resets every generator to -1."""
-        K, prof, of = _availability_arrays(profiles, profile_of, self.T, self.G)
-        self._chk(self.api.multi_set_generator_availability(self._m, K, _dp(prof), None if of is None else of.ctypes.data_as(c_int32_p)))
+        self._set("set_availability", profiles, profile_of)
 
     def set_efficiency(self, eta_c=None, eta_d=None):
         """dopf_multi_set_storage_efficiency: all storages' efficiencies in the caller's order (both None = all 1)."""
-        if not hasattr(self.api, "multi_set_storage_efficiency"):
-            raise DopfError(f"{self.api.prefix}*: this API has no storage efficiencies (unsupported)")
-        a = None if eta_c is None else _f64(eta_c, self.S)
-        b = None if eta_d is None else _f64(eta_d, self.S)
-        self._chk(self.api.multi_set_storage_efficiency(self._m, _dp(a), _dp(b)))
-        self._eta = None if a is None and b is None else (a, b)
+        self._mirror.update(self._set("set_efficiency", eta_c, eta_d))
 
     def set_initial_levels(self, e0=None):
         """dopf_multi_set_storage_initial_level: all storages' initial levels in the caller's order (None = all 0)."""
-        arr = None if e0 is None else _f64(e0, self.S)
-        self._chk(self.api.multi_set_storage_initial_level(self._m, _dp(arr)))
+        self._set("set_initial_levels", e0)
 
     def set_terminal_levels(self, lo=None, hi=None):
         """dopf_multi_set_storage_terminal_level: all storages' terminal bands in the caller's order (both None = [0, max_level])."""
-        a = None if lo is None else _f64(lo, self.S)
-        b = None if hi is None else _f64(hi, self.S)
-        self._chk(self.api.multi_set_storage_terminal_level(self._m, _dp(a), _dp(b)))
+        self._set("set_terminal_levels", lo, hi)
 
     def _chk(self, rc):
         if rc != 0:
@@ -945,15 +890,7 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     if line_rating is not None and np.any(np.asarray(line_rating, dtype=np.float64).reshape(L, T) != _f64(f_max, L)[:, None]):
         raise DopfError("dopf_central_solve*: the device LP takes no line ratings (it solves with f_max in every timestep); use "
                         "central.solve_central_packed(..., line_rating=) for a case with ratings")
-    gen_mc = _f64(gen_mc)
-    sto_mc = _f64(sto_mc)
-    G, S = gen_mc.size, sto_mc.size
-    keep = dict(demand=_f64(demand, N * T), ptdf=_f64(ptdf, L * N), f_max=_f64(f_max, L), gen_mc=gen_mc,
-                gen_pmax=_f64(gen_pmax, G), gen_node=_i32(gen_node, G), sto_mc=sto_mc, sto_pmax=_f64(sto_pmax, S),
-                sto_emax=_f64(sto_emax, S), sto_node=_i32(sto_node, S))
-    prob = DopfProblem(N=N, L=L, T=T, G=G, S=S)
-    for k, v in keep.items():
-        setattr(prob, k, v.ctypes.data_as(c_int32_p if v.dtype == np.int32 else c_double_p))
+    prob, keep, G, S = _problem(N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax, sto_node)
     q = params if params is not None else default_params()
     res = DopfCentralResult()
     P, D, Cc, E = np.zeros(G * T), np.zeros(S * T), np.zeros(S * T), np.zeros(S * T)

@@ -172,8 +172,7 @@ class ADMM:
         reference (one max_capacity per line). Needs flags=F_LINE_RATING (set for you when a Line has a rating); the state and
         the iteration counter stay, the run is no longer converged; takes effect at the next iteration."""
         self.engine.set_line_rating(rating)
-        self.packed.line_rating = None if rating is None else np.asarray(rating, dtype=np.float64).reshape(self.packed.L, self.packed.T).copy()
-        self.convergence = Convergence()
+        self._replaced("line_rating", rating, (self.packed.L, self.packed.T))
 
     def set_quadratic_cost(self, c2=None) -> None:
         """Each generator's quadratic cost coefficient (G values >= 0 in the order of `generators`; None = all 0): the cost of
@@ -182,7 +181,11 @@ class ADMM:
         Generator has quadratic_costs); the state and the iteration counter stay, the run is no longer converged; takes effect at
         the next iteration."""
         self.engine.set_quadratic_cost(c2)
-        self.packed.gen_c2 = None if c2 is None else np.asarray(c2, dtype=np.float64).reshape(self.packed.G).copy()
+        self._replaced("gen_c2", c2, (self.packed.G,))
+
+    def _replaced(self, field_: str, value, shape) -> None:
+        """the packed problem follows an input that was replaced under a kept state, and the run is no longer converged"""
+        setattr(self.packed, field_, None if value is None else np.asarray(value, dtype=np.float64).reshape(shape).copy())
         self.convergence = Convergence()
 
     # -- a receding horizon ----------------------------------------------------------------------

@@ -74,12 +74,19 @@ static bool band_reachable_ctx(const dopf_ctx *c, int i, double e0, double lo, d
     return band_reachable(e0, lo, hi, c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T);
 }
 
+// every extension's first check: the context was created with the extension's flag (`what_needs`: "line ratings need")
+static int needs_flag(dopf_ctx *c, unsigned flag, const char *what_needs, const char *flag_name)
+{
+    if (c->q.flags & flag) return DOPF_OK;
+    return fail(c, DOPF_E_UNSUPPORTED, "%s %s at dopf_create", what_needs, flag_name);
+}
+#define NEEDS_FLAG(c, what_needs, flag) needs_flag(c, flag, what_needs, #flag)
+
 // dopf_set_storage_initial_level's checks: the flag, and 0 <= e0[s] <= emax[s] for the caller's storage s (no NaN); with
 // DOPF_F_STO_TERMINAL_LEVEL also that the stored band stays reachable from e0 (NULL: from 0)
 int check_initial_levels(dopf_ctx *c, const double *e0)
 {
-    if (!(c->q.flags & DOPF_F_STO_INITIAL_LEVEL))
-        return fail(c, DOPF_E_UNSUPPORTED, "storage initial levels need DOPF_F_STO_INITIAL_LEVEL at dopf_create");
+    if (int rc = NEEDS_FLAG(c, "storage initial levels need", DOPF_F_STO_INITIAL_LEVEL)) return rc;
     const bool band = (c->q.flags & DOPF_F_STO_TERMINAL_LEVEL) != 0;
     if (!e0 && !band) return DOPF_OK;
     for (int i = 0; i < c->v.S; ++i) {
@@ -94,12 +101,10 @@ int check_initial_levels(dopf_ctx *c, const double *e0)
     return DOPF_OK;
 }
 
-// dopf_set_storage_terminal_level's checks: the flag, both arrays or neither, 0 <= lo <= hi <= emax (no NaN), and the band reachable
-// from the stored initial level
+// dopf_set_generator_availability's checks: the flag, a table of K >= 0 profiles with every value in [0, 1] (no NaN), and every index in [-1, K)
 int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of)
 {
-    if (!(c->q.flags & DOPF_F_GEN_AVAILABILITY))
-        return fail(c, DOPF_E_UNSUPPORTED, "generator availability needs DOPF_F_GEN_AVAILABILITY at dopf_create");
+    if (int rc = NEEDS_FLAG(c, "generator availability needs", DOPF_F_GEN_AVAILABILITY)) return rc;
     if (K < 0) return fail(c, DOPF_E_INVALID, "n_profiles = %d < 0", K);
     if (K > 0 && !profiles) return fail(c, DOPF_E_INVALID, "profiles is NULL with n_profiles = %d", K);
     if (K > 0 && !profile_of) return fail(c, DOPF_E_INVALID, "profile_of is NULL with n_profiles = %d", K);
@@ -118,10 +123,11 @@ int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles,
     return DOPF_OK;
 }
 
+// dopf_set_storage_terminal_level's checks: the flag, both arrays or neither, 0 <= lo <= hi <= emax (no NaN), and the band reachable
+// from the stored initial level
 int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi)
 {
-    if (!(c->q.flags & DOPF_F_STO_TERMINAL_LEVEL))
-        return fail(c, DOPF_E_UNSUPPORTED, "storage terminal levels need DOPF_F_STO_TERMINAL_LEVEL at dopf_create");
+    if (int rc = NEEDS_FLAG(c, "storage terminal levels need", DOPF_F_STO_TERMINAL_LEVEL)) return rc;
     if (!lo && !hi) return DOPF_OK;
     if (!lo || !hi) return fail(c, DOPF_E_INVALID, "storage terminal levels: lo and hi must both be given or both be NULL");
     for (int i = 0; i < c->v.S; ++i) {
@@ -140,8 +146,7 @@ int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi)
 // DOPF_F_STO_TERMINAL_LEVEL also that the stored band stays reachable from the stored e0
 int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta_d)
 {
-    if (!(c->q.flags & DOPF_F_STO_EFFICIENCY))
-        return fail(c, DOPF_E_UNSUPPORTED, "storage efficiencies need DOPF_F_STO_EFFICIENCY at dopf_create");
+    if (int rc = NEEDS_FLAG(c, "storage efficiencies need", DOPF_F_STO_EFFICIENCY)) return rc;
     if (!eta_c && !eta_d) return DOPF_OK;          // (all 1: the widest reachable range, and the stored pair passed under a narrower one or this)
     if (!eta_c || !eta_d) return fail(c, DOPF_E_INVALID, "storage efficiencies: eta_c and eta_d must both be given or both be NULL");
     const bool band = (c->q.flags & DOPF_F_STO_TERMINAL_LEVEL) != 0;
@@ -162,8 +167,7 @@ int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta
 // dopf_set_line_rating's checks: the flag, every entry finite and >= 0 (NULL: dopf_create's limits in every timestep)
 int check_line_rating(dopf_ctx *c, const double *rating)
 {
-    if (!(c->q.flags & DOPF_F_LINE_RATING))
-        return fail(c, DOPF_E_UNSUPPORTED, "line ratings need DOPF_F_LINE_RATING at dopf_create");
+    if (int rc = NEEDS_FLAG(c, "line ratings need", DOPF_F_LINE_RATING)) return rc;
     if (!rating) return DOPF_OK;
     const int L = c->v.L, T = c->v.T;
     for (int t = 0; t < T; ++t)
@@ -178,8 +182,7 @@ int check_line_rating(dopf_ctx *c, const double *rating)
 // dopf_set_generator_quadratic_cost's checks: the flag, every entry finite and >= 0 (NULL: all 0)
 int check_generator_quadratic_cost(dopf_ctx *c, const double *c2)
 {
-    if (!(c->q.flags & DOPF_F_GEN_QUADRATIC_COST))
-        return fail(c, DOPF_E_UNSUPPORTED, "quadratic generator costs need DOPF_F_GEN_QUADRATIC_COST at dopf_create");
+    if (int rc = NEEDS_FLAG(c, "quadratic generator costs need", DOPF_F_GEN_QUADRATIC_COST)) return rc;
     if (!c2) return DOPF_OK;
     for (int g = 0; g < c->v.G; ++g)
         if (!std::isfinite(c2[g]) || c2[g] < 0.0)
@@ -1484,6 +1487,21 @@ int dopf_wide_net(const dopf_ctx *c, int32_t *out)
     return DOPF_OK;
 }
 
+// The per-agent setters' common step. h holds the defaults in the context's sorted order, perm.size() values per array; a caller's
+// array (a, then b behind it; NULL: the default stays) overwrites them through the permutation (+ 0.0: a -0.0 is stored as 0.0). One
+// copy to dst, ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again).
+// h must outlive the copy: the setter synchronises before it returns.
+static int stage_and_copy(dopf_ctx *c, const std::vector<int> &perm, std::vector<double> &h, const double *a, const double *b, const double *dst)
+{
+    const size_t n = perm.size();
+    for (size_t i = 0; i < n; ++i) {
+        if (a) h[i] = a[perm[i]] + 0.0;
+        if (b) h[n + i] = b[perm[i]] + 0.0;
+    }
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(dst), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    return DOPF_OK;
+}
+
 int dopf_set_storage_initial_level(dopf_ctx *c, const double *e0)
 {
     if (!c) return DOPF_E_INVALID;
@@ -1491,10 +1509,7 @@ int dopf_set_storage_initial_level(dopf_ctx *c, const double *e0)
     if (c->v.S == 0) return DOPF_OK;
     DeviceGuard guard(c->device);
     std::vector<double> h(c->v.S, 0.0);
-    if (e0)
-        for (int i = 0; i < c->v.S; ++i) h[i] = e0[c->sto_perm[i]] + 0.0;      // (+ 0.0: a -0.0 is stored as 0.0)
-    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again)
-    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_e0(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    if (int rc = stage_and_copy(c, c->sto_perm, h, e0, nullptr, sto_e0(c->v))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->sto_e0_h = h;                        // (what the terminal-level setter checks reachability from)
     return DOPF_OK;
@@ -1507,14 +1522,9 @@ int dopf_set_storage_terminal_level(dopf_ctx *c, const double *lo, const double 
     const int S = c->v.S;
     if (S == 0) return DOPF_OK;
     DeviceGuard guard(c->device);
-    std::vector<double> h(2 * (size_t)S);   // lo then hi: sto_end_hi(v) = sto_end_lo(v) + S
-    for (int i = 0; i < S; ++i) {
-        const int a = c->sto_perm[i];
-        h[i] = lo ? lo[a] + 0.0 : 0.0;                      // (+ 0.0: a -0.0 is stored as 0.0)
-        h[S + i] = hi ? hi[a] + 0.0 : c->sto_emax_h[i];
-    }
-    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again)
-    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_end_lo(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    std::vector<double> h(2 * (size_t)S, 0.0);   // lo then hi: sto_end_hi(v) = sto_end_lo(v) + S
+    std::copy(c->sto_emax_h.begin(), c->sto_emax_h.end(), h.begin() + S);
+    if (int rc = stage_and_copy(c, c->sto_perm, h, lo, hi, sto_end_lo(c->v))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->sto_lo_h.assign(h.begin(), h.begin() + S);
     c->sto_hi_h.assign(h.begin() + S, h.end());
@@ -1528,15 +1538,12 @@ int dopf_set_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *
     const int S = c->v.S;
     if (S == 0) return DOPF_OK;
     DeviceGuard guard(c->device);
-    std::vector<double> h(2 * (size_t)S, 1.0);   // al then be: sto_eff_beta(v) = sto_eff_alpha(v) + S
-    if (eta_c)
-        for (int i = 0; i < S; ++i) {
-            const int a = c->sto_perm[i];
-            h[i] = 1.0 / eta_d[a];
-            h[S + i] = eta_c[a];
-        }
-    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again)
-    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_eff_alpha(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    std::vector<double> h(2 * (size_t)S, 1.0), al;   // al then be: sto_eff_beta(v) = sto_eff_alpha(v) + S
+    if (eta_d) {
+        al.resize(S);
+        for (int a = 0; a < S; ++a) al[a] = 1.0 / eta_d[a];
+    }
+    if (int rc = stage_and_copy(c, c->sto_perm, h, eta_d ? al.data() : nullptr, eta_c, sto_eff_alpha(c->v))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->sto_al_h.assign(h.begin(), h.begin() + S);
     c->sto_be_h.assign(h.begin() + S, h.end());
@@ -1613,11 +1620,8 @@ int dopf_set_generator_quadratic_cost(dopf_ctx *c, const double *c2)
     if (G == 0) return DOPF_OK;
     DeviceGuard guard(c->device);
     std::vector<double> h(G, 0.0);
-    if (c2)
-        for (int i = 0; i < G; ++i) h[i] = c2[c->gen_perm[i]] + 0.0;      // (+ 0.0: a -0.0 is stored as 0.0)
-    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again). The
-    // state stays; the stop test starts over, as after dopf_set_line_rating (nothing derived depends on the costs)
-    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(gen_c2(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    // the state stays; the stop test starts over, as after dopf_set_line_rating (nothing derived depends on the costs)
+    if (int rc = stage_and_copy(c, c->gen_perm, h, c2, nullptr, gen_c2(c->v))) return rc;
     launch_reset_status(c->v, c->main);
     HIPCHK(c, hipGetLastError());
     return read_status(c);          // (synchronises: h may go)

@@ -246,6 +246,13 @@ int mfail(dopf_multi *m, int code, const char *msg)
     return code;
 }
 
+// shard i's refusal becomes the object's: its code, and its message behind the shard's number
+int shard_fail(dopf_multi *m, int i, int rc)
+{
+    snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i]));
+    return rc;
+}
+
 // run f(i) for every shard, each on its own host thread (a context is driven by one thread at a time; the
 // RCCL collectives of the n ranks must be in flight together)
 template <class F>
@@ -259,7 +266,23 @@ int for_each_shard(dopf_multi *m, F f)
         for (auto &t : th) t.join();
     }
     for (int i = 0; i < m->n; ++i)
-        if (rc[i]) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc[i]; }
+        if (rc[i]) return shard_fail(m, i, rc[i]);
+    return DOPF_OK;
+}
+
+// a shard's part of a caller's array: from its offset on (NULL stays NULL)
+template <class Tp>
+Tp *from(Tp *p, size_t off) { return p ? p + off : nullptr; }
+
+// The dopf_multi_set_* entries. each(f, i) calls f, the extension's check_* or its dopf_set_*, with shard i's context and arguments.
+// All or nothing: every shard is checked before any is set, so a refusal from any shard leaves every shard as it was.
+template <class Check, class Set, class Each>
+int multi_set(dopf_multi *m, Check check, Set set, Each each)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < m->n; ++i)
+            if (const int rc = pass == 0 ? each(check, i) : each(set, i)) return shard_fail(m, i, rc);
     return DOPF_OK;
 }
 
@@ -549,10 +572,9 @@ int dopf_multi_create(dopf_multi **out, const dopf_problem *p, const dopf_params
         cut(p->S, i, m->s0[i], m->s1[i]);
         dopf_problem pi = *p;
         pi.G = m->g1[i] - m->g0[i]; pi.S = m->s1[i] - m->s0[i];
-        pi.gen_mc = p->gen_mc ? p->gen_mc + m->g0[i] : nullptr; pi.gen_pmax = p->gen_pmax ? p->gen_pmax + m->g0[i] : nullptr;
-        pi.gen_node = p->gen_node ? p->gen_node + m->g0[i] : nullptr;
-        pi.sto_mc = p->sto_mc ? p->sto_mc + m->s0[i] : nullptr; pi.sto_pmax = p->sto_pmax ? p->sto_pmax + m->s0[i] : nullptr;
-        pi.sto_emax = p->sto_emax ? p->sto_emax + m->s0[i] : nullptr; pi.sto_node = p->sto_node ? p->sto_node + m->s0[i] : nullptr;
+        pi.gen_mc = from(p->gen_mc, m->g0[i]); pi.gen_pmax = from(p->gen_pmax, m->g0[i]); pi.gen_node = from(p->gen_node, m->g0[i]);
+        pi.sto_mc = from(p->sto_mc, m->s0[i]); pi.sto_pmax = from(p->sto_pmax, m->s0[i]);
+        pi.sto_emax = from(p->sto_emax, m->s0[i]); pi.sto_node = from(p->sto_node, m->s0[i]);
         dopf_params qi = *q;
         qi.device = dev[i];
         qi.stream = nullptr;
@@ -688,74 +710,39 @@ int dopf_multi_iterate(dopf_multi *m, int32_t n_iters, int32_t *iters_done, int3
 
 int dopf_multi_set_storage_initial_level(dopf_multi *m, const double *e0)
 {
-    if (!m) return DOPF_E_INVALID;
-    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all levels as they were
-        for (int i = 0; i < m->n; ++i) {
-            const double *ei = e0 ? e0 + m->s0[i] : nullptr;
-            const int rc = pass == 0 ? check_initial_levels(m->ctx[i], ei) : dopf_set_storage_initial_level(m->ctx[i], ei);
-            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
-        }
-    return DOPF_OK;
+    return multi_set(m, check_initial_levels, dopf_set_storage_initial_level,
+                     [&](auto f, int i) { return f(m->ctx[i], from(e0, m->s0[i])); });
 }
 
 int dopf_multi_set_storage_terminal_level(dopf_multi *m, const double *lo, const double *hi)
 {
-    if (!m) return DOPF_E_INVALID;
-    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all bands as they were
-        for (int i = 0; i < m->n; ++i) {
-            const double *li = lo ? lo + m->s0[i] : nullptr, *hi_ = hi ? hi + m->s0[i] : nullptr;
-            const int rc = pass == 0 ? check_terminal_levels(m->ctx[i], li, hi_) : dopf_set_storage_terminal_level(m->ctx[i], li, hi_);
-            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
-        }
-    return DOPF_OK;
+    return multi_set(m, check_terminal_levels, dopf_set_storage_terminal_level,
+                     [&](auto f, int i) { return f(m->ctx[i], from(lo, m->s0[i]), from(hi, m->s0[i])); });
 }
 
 int dopf_multi_set_storage_efficiency(dopf_multi *m, const double *eta_c, const double *eta_d)
 {
-    if (!m) return DOPF_E_INVALID;
-    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all efficiencies as they were
-        for (int i = 0; i < m->n; ++i) {
-            const double *ci = eta_c ? eta_c + m->s0[i] : nullptr, *di = eta_d ? eta_d + m->s0[i] : nullptr;
-            const int rc = pass == 0 ? check_storage_efficiency(m->ctx[i], ci, di) : dopf_set_storage_efficiency(m->ctx[i], ci, di);
-            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
-        }
-    return DOPF_OK;
+    return multi_set(m, check_storage_efficiency, dopf_set_storage_efficiency,
+                     [&](auto f, int i) { return f(m->ctx[i], from(eta_c, m->s0[i]), from(eta_d, m->s0[i])); });
 }
 
 int dopf_multi_set_generator_availability(dopf_multi *m, int32_t n_profiles, const double *profiles, const int32_t *profile_of)
 {
-    if (!m) return DOPF_E_INVALID;
-    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all profiles as they were
-        for (int i = 0; i < m->n; ++i) {           // (every shard gets the whole table and its slice of the indices)
-            const int32_t *pi = profile_of ? profile_of + m->g0[i] : nullptr;
-            const int rc = pass == 0 ? check_generator_availability(m->ctx[i], n_profiles, profiles, pi)
-                                     : dopf_set_generator_availability(m->ctx[i], n_profiles, profiles, pi);
-            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
-        }
-    return DOPF_OK;
+    // (every shard gets the whole table and its slice of the indices)
+    return multi_set(m, check_generator_availability, dopf_set_generator_availability,
+                     [&](auto f, int i) { return f(m->ctx[i], n_profiles, profiles, from(profile_of, m->g0[i])); });
 }
 
 int dopf_multi_set_line_rating(dopf_multi *m, const double *rating)
 {
-    if (!m) return DOPF_E_INVALID;
-    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all tables as they were
-        for (int i = 0; i < m->n; ++i) {           // (every shard gets the whole table: replicated state)
-            const int rc = pass == 0 ? check_line_rating(m->ctx[i], rating) : dopf_set_line_rating(m->ctx[i], rating);
-            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
-        }
-    return DOPF_OK;
+    // (every shard gets the whole table: replicated state)
+    return multi_set(m, check_line_rating, dopf_set_line_rating, [&](auto f, int i) { return f(m->ctx[i], rating); });
 }
 
 int dopf_multi_set_generator_quadratic_cost(dopf_multi *m, const double *c2)
 {
-    if (!m) return DOPF_E_INVALID;
-    for (int pass = 0; pass < 2; ++pass)           // check every shard first: a refusal leaves all coefficients as they were
-        for (int i = 0; i < m->n; ++i) {
-            const double *ci = c2 ? c2 + m->g0[i] : nullptr;
-            const int rc = pass == 0 ? check_generator_quadratic_cost(m->ctx[i], ci) : dopf_set_generator_quadratic_cost(m->ctx[i], ci);
-            if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
-        }
-    return DOPF_OK;
+    return multi_set(m, check_generator_quadratic_cost, dopf_set_generator_quadratic_cost,
+                     [&](auto f, int i) { return f(m->ctx[i], from(c2, m->g0[i])); });
 }
 
 int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E)
@@ -763,9 +750,8 @@ int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double
     if (!m) return DOPF_E_INVALID;
     const size_t T = (size_t)m->T;
     for (int i = 0; i < m->n; ++i) {
-        const int rc = dopf_get_primal(m->ctx[i], P ? P + T * m->g0[i] : nullptr, D ? D + T * m->s0[i] : nullptr,
-                                       C ? C + T * m->s0[i] : nullptr, E ? E + T * m->s0[i] : nullptr);
-        if (rc) { snprintf(m->err, 512, "shard %d: %s", i, dopf_last_error(m->ctx[i])); return rc; }
+        const size_t g = T * m->g0[i], s = T * m->s0[i];
+        if (const int rc = dopf_get_primal(m->ctx[i], from(P, g), from(D, s), from(C, s), from(E, s))) return shard_fail(m, i, rc);
     }
     return DOPF_OK;
 }

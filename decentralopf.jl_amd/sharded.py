@@ -95,34 +95,27 @@ class ShardedADMM:
     def sync(self):
         return self.engine.sync()
 
+    def _mine(self, x, which: str, dtype=np.float64):
+        """This rank's slice of a global per-agent array (which: "sto" or "gen"); None stays None."""
+        if x is None:
+            return None
+        a, b = self.shard.meta[which + "_range"]
+        return np.asarray(x, dtype=dtype).reshape(self.problem.S if which == "sto" else self.problem.G)[a:b]
+
     def set_initial_levels(self, e0=None) -> None:
         """All storages' levels before the first timestep (problem.S values, global order; None = all 0): this rank sets its
         slice (dopf_set_storage_initial_level). Needs F_STO_INITIAL_LEVEL in the params; every rank calls it between steps."""
-        if e0 is None:
-            self.engine.set_initial_levels(None)
-            return
-        s0, s1 = self.shard.meta["sto_range"]
-        self.engine.set_initial_levels(np.asarray(e0, dtype=np.float64).reshape(self.problem.S)[s0:s1])
+        self.engine.set_initial_levels(self._mine(e0, "sto"))
 
     def set_terminal_levels(self, lo=None, hi=None) -> None:
         """All storages' terminal bands (problem.S values each, global order; both None = [0, max_level]): this rank sets its
         slice (dopf_set_storage_terminal_level). Needs F_STO_TERMINAL_LEVEL in the params; every rank calls it between steps."""
-        if lo is None and hi is None:
-            self.engine.set_terminal_levels(None, None)
-            return
-        s0, s1 = self.shard.meta["sto_range"]
-        cut = lambda x: None if x is None else np.asarray(x, dtype=np.float64).reshape(self.problem.S)[s0:s1]
-        self.engine.set_terminal_levels(cut(lo), cut(hi))
+        self.engine.set_terminal_levels(self._mine(lo, "sto"), self._mine(hi, "sto"))
 
     def set_efficiency(self, eta_c=None, eta_d=None) -> None:
         """All storages' charge and discharge efficiencies (problem.S values each, global order; both None = all 1): this rank sets
         its slice (dopf_set_storage_efficiency). Needs F_STO_EFFICIENCY in the params; every rank calls it between steps."""
-        if eta_c is None and eta_d is None:
-            self.engine.set_efficiency(None, None)
-            return
-        s0, s1 = self.shard.meta["sto_range"]
-        cut = lambda x: None if x is None else np.asarray(x, dtype=np.float64).reshape(self.problem.S)[s0:s1]
-        self.engine.set_efficiency(cut(eta_c), cut(eta_d))
+        self.engine.set_efficiency(self._mine(eta_c, "sto"), self._mine(eta_d, "sto"))
 
     def set_line_rating(self, rating=None) -> None:
         """The lines' limits per timestep ((L, T); None = f_max in every timestep): replicated state, so this rank sets the whole
@@ -134,22 +127,13 @@ class ShardedADMM:
         """All generators' quadratic cost coefficients (problem.G values >= 0, global order; None = all 0): this rank sets its slice
         (dopf_set_generator_quadratic_cost; the cost is local to the rank's agents, no sums move). Needs F_GEN_QUADRATIC_COST in the
         params; every rank calls it between the same two steps."""
-        if c2 is None:
-            self.engine.set_quadratic_cost(None)
-            return
-        g0, g1 = self.shard.meta["gen_range"]
-        self.engine.set_quadratic_cost(np.asarray(c2, dtype=np.float64).reshape(self.problem.G)[g0:g1])
+        self.engine.set_quadratic_cost(self._mine(c2, "gen"))
 
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
         max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs
         F_GEN_AVAILABILITY in the params; every rank calls it between steps."""
-        if profiles is None and profile_of is None:
-            self.engine.set_availability(None, None)
-            return
-        g0, g1 = self.shard.meta["gen_range"]
-        of = None if profile_of is None else np.asarray(profile_of, dtype=np.int32).reshape(self.problem.G)[g0:g1]
-        self.engine.set_availability(profiles, of)
+        self.engine.set_availability(profiles, self._mine(profile_of, "gen", np.int32))
 
     def run(self, max_iters: int, check_every: int = 16):
         """Iterate until the stop test holds (checked every `check_every` iterations) or max_iters."""
