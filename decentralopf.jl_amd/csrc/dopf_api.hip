@@ -70,8 +70,8 @@ static bool band_reachable(double e0, double lo, double hi, double pm, double em
 static bool band_reachable_ctx(const dopf_ctx *c, int i, double e0, double lo, double hi)
 {
     if (c->q.flags & DOPF_F_STO_EFFICIENCY)
-        return band_reachable(e0, lo, hi, c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T, c->sto_al_h[i], c->sto_be_h[i]);
-    return band_reachable(e0, lo, hi, c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T);
+        return band_reachable(e0, lo, hi, c->sto_pmax_h[i], c->sto_at(kStoEmax, i), c->v.T, c->sto_at(kStoAlpha, i), c->sto_at(kStoBeta, i));
+    return band_reachable(e0, lo, hi, c->sto_pmax_h[i], c->sto_at(kStoEmax, i), c->v.T);
 }
 
 // every extension's first check: the context was created with the extension's flag (`what_needs`: "line ratings need")
@@ -92,11 +92,11 @@ int check_initial_levels(dopf_ctx *c, const double *e0)
     for (int i = 0; i < c->v.S; ++i) {
         const int a = c->sto_perm[i];
         const double x = e0 ? e0[a] : 0.0;
-        if (!(x >= 0.0 && x <= c->sto_emax_h[i]))
-            return fail(c, DOPF_E_INVALID, "initial level of storage %d is %g, outside [0, max_level = %g]", a, x, c->sto_emax_h[i]);
-        if (band && !band_reachable_ctx(c, i, x, c->sto_lo_h[i], c->sto_hi_h[i]))
+        if (!(x >= 0.0 && x <= c->sto_at(kStoEmax, i)))
+            return fail(c, DOPF_E_INVALID, "initial level of storage %d is %g, outside [0, max_level = %g]", a, x, c->sto_at(kStoEmax, i));
+        if (band && !band_reachable_ctx(c, i, x, c->sto_at(kStoEndLo, i), c->sto_at(kStoEndHi, i)))
             return fail(c, DOPF_E_INVALID, "initial level %g of storage %d leaves its terminal band [%g, %g] unreachable in %d steps of %g",
-                        x, a, c->sto_lo_h[i], c->sto_hi_h[i], c->v.T, c->sto_pmax_h[i]);
+                        x, a, c->sto_at(kStoEndLo, i), c->sto_at(kStoEndHi, i), c->v.T, c->sto_pmax_h[i]);
     }
     return DOPF_OK;
 }
@@ -132,12 +132,12 @@ int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi)
     if (!lo || !hi) return fail(c, DOPF_E_INVALID, "storage terminal levels: lo and hi must both be given or both be NULL");
     for (int i = 0; i < c->v.S; ++i) {
         const int a = c->sto_perm[i];
-        const double l = lo[a], h = hi[a], em = c->sto_emax_h[i];
+        const double l = lo[a], h = hi[a], em = c->sto_at(kStoEmax, i);
         if (!(l >= 0.0 && h <= em && l <= h))
             return fail(c, DOPF_E_INVALID, "terminal band of storage %d is [%g, %g], not inside [0, max_level = %g] (or empty)", a, l, h, em);
-        if (!band_reachable_ctx(c, i, c->sto_e0_h[i], l, h))
+        if (!band_reachable_ctx(c, i, c->sto_at(kStoE0, i), l, h))
             return fail(c, DOPF_E_INVALID, "terminal band [%g, %g] of storage %d is unreachable from its initial level %g in %d steps of %g",
-                        l, h, a, c->sto_e0_h[i], c->v.T, c->sto_pmax_h[i]);
+                        l, h, a, c->sto_at(kStoE0, i), c->v.T, c->sto_pmax_h[i]);
     }
     return DOPF_OK;
 }
@@ -156,9 +156,9 @@ int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta
         if (std::isnan(ec) || std::isnan(ed)) return fail(c, DOPF_E_INVALID, "%s[%d] is NaN", std::isnan(ec) ? "eta_c" : "eta_d", a);
         if (!(ec > 0.0 && ec <= 1.0)) return fail(c, DOPF_E_INVALID, "eta_c[%d] = %g outside (0, 1]", a, ec);
         if (!(ed > 0.0 && ed <= 1.0)) return fail(c, DOPF_E_INVALID, "eta_d[%d] = %g outside (0, 1]", a, ed);
-        if (band && !band_reachable(c->sto_e0_h[i], c->sto_lo_h[i], c->sto_hi_h[i], c->sto_pmax_h[i], c->sto_emax_h[i], c->v.T, 1.0 / ed, ec))
+        if (band && !band_reachable(c->sto_at(kStoE0, i), c->sto_at(kStoEndLo, i), c->sto_at(kStoEndHi, i), c->sto_pmax_h[i], c->sto_at(kStoEmax, i), c->v.T, 1.0 / ed, ec))
             return fail(c, DOPF_E_INVALID, "efficiencies eta_c[%d] = %g, eta_d[%d] = %g leave the terminal band [%g, %g] of storage %d unreachable "
-                        "from its initial level %g in %d steps of %g", a, ec, a, ed, c->sto_lo_h[i], c->sto_hi_h[i], a, c->sto_e0_h[i], c->v.T,
+                        "from its initial level %g in %d steps of %g", a, ec, a, ed, c->sto_at(kStoEndLo, i), c->sto_at(kStoEndHi, i), a, c->sto_at(kStoE0, i), c->v.T,
                         c->sto_pmax_h[i]);
     }
     return DOPF_OK;
@@ -229,191 +229,6 @@ int dev_upload(dopf_ctx *c, const Tp **out, const std::vector<Tp> &h)
     if (!h.empty()) HIPCHK(c, hipMemcpy(p, h.data(), h.size() * sizeof(Tp), hipMemcpyHostToDevice));
     *out = p;
     return DOPF_OK;
-}
-
-// split the node-sorted agent list into block work items that never cross a node boundary
-void make_items(const std::vector<int> &node_sorted, int N, int chunk, std::vector<Item> &items,
-                std::vector<int> &node_beg, std::vector<int> &node_item_beg)
-{
-    const int A = (int)node_sorted.size();
-    node_beg.assign(N + 1, 0);
-    for (int a = 0; a < A; ++a) node_beg[node_sorted[a] + 1]++;
-    for (int n = 0; n < N; ++n) node_beg[n + 1] += node_beg[n];
-    node_item_beg.assign(N + 1, 0);
-    items.clear();
-    for (int n = 0; n < N; ++n) {
-        node_item_beg[n] = (int)items.size();
-        for (int a = node_beg[n]; a < node_beg[n + 1]; a += chunk)
-            items.push_back(Item{a, std::min(a + chunk, node_beg[n + 1]), n, 0});
-    }
-    node_item_beg[N] = (int)items.size();
-}
-
-// the wide chain (net_wide.h): beyond 2048 lines, where k_tables' LDS (4 * 2L doubles) runs out, or at any L on request
-bool wide_chain(int L, unsigned flags) { return 2 * L > 4096 || (L > 0 && (flags & DOPF_F_DEBUG_WIDE_NET)); }
-
-// the quiet chain's dual/price kernel stages every partial row of its timestep in LDS: up to 96 KB of them
-bool quiet_rows_fit(int rows) { return rows > 0 && (size_t)rows * sizeof(double) <= 96 * 1024; }
-
-// agents per node -> work items of at most `chunk` agents that never cross a node boundary (make_items)
-int count_items(const std::vector<int> &per_node, int chunk)
-{
-    int n = 0;
-    for (int a : per_node) n += (a + chunk - 1) / chunk;
-    return n;
-}
-
-// XCD (of eight) whose blocks write generator item i's partial row (networks; storage item k: k % 8). k_net_agents: storages first
-int gen_row_xcd(const Plan &p, int i) { return ((p.fuseNet ? p.nStoItems : 0) + i) % 8; }
-
-// The problem's sizes and what plan_chain needs of its data
-struct Shape {
-    int N, L, T, G, S;
-    std::vector<int> gen_at, sto_at;    // generators / storages per node
-    int ki, kc;                         // fraction bits the fixed-point sums of the one-launch tail would keep (injection, cost)
-};
-
-// The launch chain of a context, decided once: dopf_create builds the items and rows from it, the launch functions
-// switch on it. No HIP call, no allocation. cus: the device's CUs (0: unknown). dopf_create has refused T > 512 without
-// DOPF_F_LONG_HORIZON and L > 2048 without DOPF_F_WIDE_NETWORK.
-Plan plan_chain(const Shape &sh, unsigned flags, int cus)
-{
-    const int N = sh.N, L = sh.L, T = sh.T, G = sh.G, S = sh.S;
-    Plan p{};
-    if (S > 0 && (!sto_config_supported(T, &p) || (flags & DOPF_F_DEBUG_LONG_STO))) p.stoLong = 1;
-    if (p.stoLong) { p.stoLPS = 64; p.stoNCH = 8; }         // (not read by the long body; keeps the one-wave paths' choices off)
-    p.wideNet = wide_chain(L, flags) ? 1 : 0;
-    p.useWarm = S > 0 && p.stoNCH <= 3 && !(flags & DOPF_F_NO_WARM_START);     // (the long body: NCH 8, off)
-    // The lean active-set body (sto_lean.h): 32-bit element offsets; on a network only where the storage blocks outnumber the
-    // chip's resident slots several times — its gain is instruction count, and a grid of one resident round is bound by one
-    // block's latency chain, which is no shorter (configs[3]: 114 us against 120 at 100 k agents; its 12.5 k share 43.3 against 41.1).
-    // DOPF_F_STO_INITIAL_LEVEL / DOPF_F_STO_TERMINAL_LEVEL: the general bodies' level-mode instantiations (a level before timestep 0;
-    // and a band after the last one); the lean body has none
-    p.stoE0 = S > 0 && (flags & DOPF_F_STO_INITIAL_LEVEL);
-    // DOPF_F_GEN_AVAILABILITY: the same chain, with the generator bodies' AV instantiations (cap <= gen_pmax: every bound derived
-    // from gen_pmax below and in dopf_create stays valid)
-    p.genAvail = G > 0 && (flags & DOPF_F_GEN_AVAILABILITY);
-    // DOPF_F_STO_EFFICIENCY: level mode 3 whatever the other two flags say (e0 and the band at their defaults without them) — one more
-    // instantiation per storage launch family; the chain is the one the same problem runs with the other two flags
-    p.stoEff = S > 0 && (flags & DOPF_F_STO_EFFICIENCY);
-    p.stoLV = S == 0 ? 0 : p.stoEff ? 3 : (flags & DOPF_F_STO_TERMINAL_LEVEL) ? 2 : (flags & DOPF_F_STO_INITIAL_LEVEL) ? 1 : 0;
-    p.stoLean = !((flags & (DOPF_F_STO_GENERAL | DOPF_F_STO_INITIAL_LEVEL | DOPF_F_STO_TERMINAL_LEVEL | DOPF_F_STO_EFFICIENCY)) ||
-                  (unsigned long long)S * T * sizeof(double) >= (1ull << 32) ||
-                  (L > 0 && (long long)S * p.stoLPS / 256 < 1024)) && !p.stoLong;
-    p.genTT = std::min(T, 512);
-    p.genR = 512 / p.genTT;
-    // DOPF_F_GEN_QUADRATIC_COST: the generators in k_gen_update's QC instantiations, a launch of their own on every shape — no pair
-    // or skip kernels (genTT2 = 0, and with it no one-launch tail: `pairs` below), no k_agents, no k_net_agents. The chain the
-    // same problem runs under DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T; the storages' launch of that chain, with the LV above
-    p.genQuad = G > 0 && (flags & DOPF_F_GEN_QUADRATIC_COST);
-    if (p.genQuad) flags |= DOPF_F_NO_FUSE;
-    p.genTT2 = (!p.genQuad && L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
-    p.fuseAgents = p.genTT2 > 0 && p.genTT2 <= 256 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS));
-    if (p.fuseAgents) {
-        // one launch for all agents pays while its fixed cost matters and every storage block is resident from
-        // the start (3 blocks of 256 per CU at the storage code's register count); see k_agents
-        const int ng = 256 / p.stoLPS;
-        const int sch = (std::max(ng, (S + 2047) / 2048) + ng - 1) / ng * ng;
-        const long long sto_blocks = (S + sch - 1) / sch + N - 1;
-        if (sto_blocks > 3 * 256 || (long long)G * T > (8ll << 20)) p.fuseAgents = false;
-    }
-    p.genR2 = p.genTT2 ? (p.fuseAgents ? 256 : 512) / p.genTT2 : 0;
-    // networks: generators and storages in one launch (k_net_agents) unless the storages run on a stream of their own
-    p.genTT256 = std::max(1, std::min((std::min(T, 512) + 1) / 2, 256 / p.genR));
-    p.fuseNet = L > 0 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS)) &&
-                p.genR * p.genTT256 <= 256;          // (T = 1: the 512-thread tiling has more agent lanes than such a block has threads)
-    // One-launch iterations (kernels_agents.hip, "the tail of the iteration inside the x-update launch"): the fixed-point sums need
-    // 8 fraction bits of the injection and a non-negative exponent of the cost (64 bits = sign + 53 value bits + the 10-bit arrival count)
-    const bool pairs = p.genTT2 > 0 && (S == 0 || p.useWarm) && G + S > 0;       // pair kernels / k_agents / k_sto
-    p.tail = N == 1 && L == 0 && pairs && sh.ki >= 8 && sh.kc >= 0 &&
-             !(flags & (DOPF_F_NO_TAIL_FUSE | DOPF_F_OVERLAP_AGENTS));          // (two streams: the storage launch does not follow the generators')
-
-    // work items
-    const int R = p.genTT2 ? p.genR2 : p.genR;
-    // ~2048 blocks fill the chip several times over; in the fused launch the generator blocks share the wave slots with
-    // the storage blocks and ~1536 somewhat larger ones come out ahead (measured on config2: 25.7 -> 24.0 us)
-    // (with lines ~1024 blocks: the 118-node share 93.8 -> 87.3 us per iteration, config3 at full size 204 -> 203)
-    // (networks, one launch for all agents: the generator blocks pass through the ~230 wave slots the storage blocks leave
-    // free at that kernel's register count — ~512 larger ones: the 118-node share 51.6 -> 49.5 us per iteration)
-    int target_items = p.fuseAgents ? 1536 : (L > 0 ? ((p.fuseNet && !(flags & DOPF_F_NET_SMALL_ITEMS)) ? 512 : 1024) : 2048);
-    if (const char *e = exp_env("DOPF_GEN_TARGET_ITEMS")) target_items = std::max(1, atoi(e));     // (experiments)
-    // streaming generator blocks (fused launch, one node): an item is ONE batch of loads, <= kGenStreamRows rows per lane
-    const bool stream = p.fuseAgents && N == 1;
-    if (stream) target_items = std::max(target_items, (G + kGenStreamRows * R - 1) / (kGenStreamRows * R));
-    int chunk = std::max(R, (G + target_items - 1) / target_items);
-    chunk = (chunk + R - 1) / R * R;
-    if (stream) chunk = std::min(chunk, kGenStreamRows * R);
-    p.genItem = chunk;
-    // (on short blocks the skip test costs more than the rows it saves: measured on config1/config2)
-    p.genSkip = (p.genTT2 > 0 && chunk >= 8 * R && !(flags & DOPF_F_NO_ROW_SKIP)) ? 1 : 0;
-    const int NG = S > 0 ? 256 / p.stoLPS : 1;
-    int sto_target = 2048;
-    const char *sto_env = exp_env("DOPF_STO_TARGET_ITEMS");
-    if (sto_env) sto_target = std::max(1, atoi(sto_env));     // (experiments)
-    int schunk = std::max(NG, (S + sto_target - 1) / sto_target);
-    schunk = (schunk + NG - 1) / NG * NG;
-    // Big copper plates (the storage solve is a launch of its own: config4): as many passes per block as make the launch ONE
-    // resident round — 3 blocks of 256 threads per CU at the storage code's register count — instead of several rounds of
-    // shorter blocks (the blocks' fixed cost — entry, constants, the block's sums — is paid per block, and a round's last
-    // blocks leave wave slots idle): config4 1 421 items of 2 passes -> 711 of 4: 78.7 -> 76.8 us per iteration. Only when that
-    // round is well filled (a half-empty round of long blocks loses: 569 blocks of 5 passes 84.3 us).
-    if (!p.fuseAgents && L == 0 && N == 1 && S > 0 && !sto_env) {
-        const int slots = 3 * (cus > 0 ? cus : 256) - 8, units = (S + NG - 1) / NG;
-        const int passes = (units + slots - 1) / slots;
-        if (passes >= 2 && (units + passes - 1) / passes >= (slots * 4) / 5) schunk = std::max(schunk, passes * NG);
-    }
-    if (p.stoLong) schunk = 1;         // the long body: one block per storage
-    p.stoItem = schunk;
-    p.nGenItems = count_items(sh.gen_at, chunk);
-    p.nStoItems = count_items(sh.sto_at, schunk);
-    if (p.fuseAgents && N == 1 && !p.genSkip && chunk <= kGenStreamRows * p.genR2) {
-        // as many generator blocks as find a wave slot next to the storage blocks (3 blocks of 256 per CU at the fused
-        // kernel's register count): all resident from the start; at least a quarter of the chip
-        int nb = 3 * 256 - p.nStoItems - (p.tail ? 1 : 0);        // (tail in the launch: one slot for the tail block)
-        if (const char *e = exp_env("DOPF_GEN_BLOCKS")) nb = atoi(e);          // (experiments)
-        p.genBlocks = std::min(p.nGenItems, std::max(nb, 192));
-    }
-    if ((p.nGenItems + p.nStoItems) / kAccRep + 2 > 1000) p.tail = false;     // (the 10-bit arrival count of a replica slot)
-    if (L > 0) {        // rows of the transposed partial sums per timestep (DevView::part_T): each XCD's rows padded to 16
-        int cnt[8] = {};
-        for (int i = 0; i < p.nGenItems; ++i) ++cnt[gen_row_xcd(p, i)];
-        for (int k = 0; k < p.nStoItems; ++k) cnt[k % 8] += 2;
-        for (int x = 0; x < 8; ++x) p.rowsT += (cnt[x] + 15) / 16 * 16;
-    }
-
-    // the consensus step
-    const size_t NT = (size_t)N * T, LT = (size_t)L * T, n1 = std::max(NT, LT);
-    if (p.wideNet) p.consensus = Consensus::Wide;
-    else if (n1 <= kSmallConsensus) p.consensus = Consensus::Small;
-    else if (L > 0 && L <= 256 && N <= 256) p.consensus = Consensus::T1024;
-    else if ((size_t)std::max(N, 3 * L) * sizeof(double) <= 48 * 1024) p.consensus = Consensus::DualT;
-    else p.consensus = Consensus::Generic;
-    p.sliceDual = p.consensus == Consensus::Small && NT <= 256;       // k_dual_price_small: 8 chunks of 32 entries
-    if (p.consensus == Consensus::T1024) {
-        // networks whose dual step is the one-launch kernel: it builds the tables too, with as many waves as find LDS scratch
-        // (<= 8) next to its own ~30 KB
-        const size_t per_wave = (4 * (size_t)(2 * L) + 1) * sizeof(double), own = 25 * 1024 + (4 * (size_t)N + 3 * (size_t)L) * sizeof(double);
-        p.tablesInDual = (int)std::min<size_t>(8, (128 * 1024 - std::min<size_t>(own, 128 * 1024)) / per_wave);
-        // the same kernel forms the slack sums of its timestep (see DevView::slackInDual); DOPF_F_NO_TAIL_FUSE keeps the
-        // k_reduce launch (the chain a sharded context runs: bitwise comparisons against it)
-        p.slackDual = !(flags & DOPF_F_NO_TAIL_FUSE);
-    }
-    // ... and, while no line is flagged, the node sums too (the quiet chain: no k_slack launch; DevView::quiet, dopf_iterate)
-    // (up to 32 rows per node: one batch of the eight lanes' four loads. configs[3] at full size has 25 and is where the gain
-    // ends — the node sums cost the dual kernel what k_slack and its boundary cost, 119.3 us per iteration either way)
-    p.quiet = p.slackDual && !(flags & (DOPF_F_KEEP_DELTAS | DOPF_F_NO_QUIET)) && quiet_rows_fit(p.rowsT);
-    // the same chain on a peer exchange (k_slack stays: its node sums are what is exchanged): a function of the problem's shape and
-    // the flags only — every rank decides alike
-    p.commQuiet = p.slackDual && !(flags & (DOPF_F_KEEP_DELTAS | DOPF_F_NO_QUIET));
-
-    // every launch family has kernels for a prefix of kStoPairs (kernels_agents.hip: with_sto_pair)
-    if (S > 0 && !p.stoLong) {
-        int at = 0;
-        while (at < kAllPairs && !(kStoPairs[at][0] == p.stoLPS && kStoPairs[at][1] == p.stoNCH)) ++at;
-        if (at >= ((p.fuseAgents || p.fuseNet) ? kFusedPairs : kAllPairs))
-            p.refusal = "no storage kernel is instantiated for this horizon and chain";
-    }
-    return p;
 }
 
 }  // namespace
@@ -614,6 +429,362 @@ int check_solver(dopf_ctx *c)
     return DOPF_OK;
 }
 
+// ---- dopf_create, stage by stage. The stages run in this order and every effect on the device — streams, allocations, copies,
+// ---- the first launch — happens in the order written here. A stage returns a code with its message in the context (validate and
+// ---- pick_device, which run before there is one: in dopf_last_error(NULL)'s buffer); dopf_create bails in one place.
+
+// the agents' data in the context's sorted order (sort_agents)
+struct Sorted {
+    std::vector<double> gmc, gpm, smc, spm, sem;
+    std::vector<int> gnode, snode;
+};
+
+// 1. the arguments' checks that need no device
+int validate(const dopf_problem *p, const dopf_params *q)
+{
+    if (p->N < 1 || p->T < 1 || p->L < 0 || p->G < 0 || p->S < 0)
+        return fail(nullptr, DOPF_E_INVALID, "bad sizes N=%d L=%d T=%d G=%d S=%d", p->N, p->L, p->T, p->G, p->S);
+    if (!(q->gamma > 0) || !(q->w_prox > 0) || !(q->w_flow > 0))
+        return fail(nullptr, DOPF_E_INVALID, "gamma, w_prox, w_flow must be positive");
+    if (!p->demand || (p->L > 0 && (!p->ptdf || !p->f_max)) || (p->G > 0 && (!p->gen_mc || !p->gen_pmax || !p->gen_node)) ||
+        (p->S > 0 && (!p->sto_mc || !p->sto_pmax || !p->sto_emax || !p->sto_node)))
+        return fail(nullptr, DOPF_E_INVALID, "null array in dopf_problem (every array with a positive extent must be given)");
+    for (int g = 0; g < p->G; ++g)
+        if (p->gen_node[g] < 0 || p->gen_node[g] >= p->N) return fail(nullptr, DOPF_E_INVALID, "gen_node[%d] out of range", g);
+    for (int s = 0; s < p->S; ++s)
+        if (p->sto_node[s] < 0 || p->sto_node[s] >= p->N) return fail(nullptr, DOPF_E_INVALID, "sto_node[%d] out of range", s);
+    if ((int64_t)p->G * p->T > (int64_t)1 << 40) return fail(nullptr, DOPF_E_INVALID, "problem too large");
+    Plan probe{};
+    if (p->S > 0 && !sto_config_supported(p->T, &probe) && !(q->flags & (DOPF_F_LONG_HORIZON | DOPF_F_DEBUG_LONG_STO)))
+        return fail(nullptr, DOPF_E_UNSUPPORTED, "storage kernel supports T <= 512 (got %d); longer horizons need DOPF_F_LONG_HORIZON", p->T);
+    if (2 * p->L > 4096 && !(q->flags & (DOPF_F_WIDE_NETWORK | DOPF_F_DEBUG_WIDE_NET)))
+        return fail(nullptr, DOPF_E_UNSUPPORTED, "table kernel supports L <= 2048 (got %d); wider networks need DOPF_F_WIDE_NETWORK", p->L);
+    if (wide_chain(p->L, q->flags)) {
+        // the kernels index the PTDF (l + L*n) and the line state (l + L*t) in 32-bit ints (net_wide.h, k_slack, line_term)
+        if ((int64_t)p->L * p->N >= ((int64_t)1 << 31) || (int64_t)p->L * p->T >= ((int64_t)1 << 31) || (int64_t)p->L >= ((int64_t)1 << 29))
+            return fail(nullptr, DOPF_E_UNSUPPORTED, "wide chain needs L*N and L*T below 2^31 (L=%d N=%d T=%d)", p->L, p->N, p->T);
+    }
+    return DOPF_OK;
+}
+
+// 2. the device: dopf_params::device, or the calling thread's current one
+int pick_device(const dopf_params *q, int *dev)
+{
+    if (int rc = check_one_runtime(nullptr)) return rc;
+    int ndev = 0;
+    hipError_t e0 = hipGetDeviceCount(&ndev);
+    if (e0 != hipSuccess || ndev < 1)
+        return fail(nullptr, DOPF_E_DEVICE, "no HIP device (%s); libdopf_hip has no CPU fallback", hipGetErrorString(e0));
+    *dev = q->device;
+    if (*dev < 0) hipGetDevice(dev);
+    if (*dev >= ndev) return fail(nullptr, DOPF_E_INVALID, "device %d of %d", *dev, ndev);
+    return DOPF_OK;
+}
+
+// ... and, for the wide chain, room on it. That chain keeps the worst-case table layout: tb_beta, tb_psi 2L, tb_slope
+// 2L + 1 doubles, psi0 and m per (n,t), and the slack partials part_U / part_K L doubles each per (n,t). Checked before anything
+// is allocated or launched.
+int wide_tables_fit(dopf_ctx *c, const dopf_problem *p)
+{
+    if (!wide_chain(p->L, c->q.flags)) return DOPF_OK;
+    const unsigned long long nt = (unsigned long long)p->N * p->T, l2 = 2ull * p->L;
+    const unsigned long long need = nt * ((3 * l2 + 1) * sizeof(double) + sizeof(double) + sizeof(int)) + 2 * nt * p->L * sizeof(double);
+    size_t freeb = 0, totalb = 0;
+    HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
+    if (need > freeb)
+        return fail(c, DOPF_E_NOMEM, "wide chain: the breakpoint tables and slack partials need %llu bytes, the device has %llu free",
+                    need, (unsigned long long)freeb);
+    return DOPF_OK;
+}
+
+// 3. the streams
+int create_streams(dopf_ctx *c)
+{
+    // (Round 3 ran big networks — configs[3] at full size — with the storage solve on a second stream by itself: 145 -> 136 us per
+    // iteration. With generators and storages in one launch whose generator blocks work on both column halves at once
+    // (k_net_agents) the one-stream form is ahead again, 117.8 vs 124.9 us; DOPF_F_OVERLAP_AGENTS stays for whoever asks.)
+    if (c->q.stream) { c->main = (hipStream_t)c->q.stream; c->own_main = false; }
+    else { HIPCHK(c, hipStreamCreateWithFlags(&c->main, hipStreamNonBlocking)); c->own_main = true; }
+    // the side stream exists only when it is used: HIP maps streams onto a few hardware queues (4 by default), and a
+    // process whose streams outnumber them pays barrier packets on every launch (measured: two contexts + PyTorch's
+    // own streams made a 118-node iteration 4x slower)
+    if (c->q.flags & DOPF_F_OVERLAP_AGENTS) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
+    }
+    return DOPF_OK;
+}
+
+// ... and the view's scalars that come straight from the arguments
+void set_scalars(DevView &v, const dopf_problem *p, const dopf_params *q)
+{
+    v.N = p->N; v.L = p->L; v.T = p->T; v.G = p->G; v.S = p->S; v.M2 = 2 * p->L;
+    v.gamma = q->gamma; v.w_flow = q->w_flow; v.w_prox = q->w_prox; v.eps = q->eps; v.mask_thr = q->mask_thr;
+    v.max_iters = q->max_iters;
+    v.rootCap = (q->flags & DOPF_F_DEBUG_ROOT_CAP) ? 2 : 80;
+    v.keepDeltas = (q->flags & DOPF_F_KEEP_DELTAS) ? 1 : 0;
+    v.debugLeave = (q->flags & DOPF_F_DEBUG_LEAVE) ? 1 : 0;
+    const int A = q->n_agents_global > 0 ? q->n_agents_global : p->G + p->S;
+    v.invA = A > 0 ? 1.0 / (double)A : 0.0;
+    v.nAgents = (double)A;
+    const double a0 = v.w_prox + v.gamma;
+    v.cp_ia = 1.0 / a0; v.cp_idet = 1.0 / (a0 * a0 - v.gamma * v.gamma); v.cp_s2 = 2.0 / (a0 + v.gamma);
+}
+
+// 4. the agents sorted by node (stable): the permutations into the context, sorted copies of their data into so
+int sort_agents(dopf_ctx *c, const dopf_problem *p, Sorted &so)
+{
+    const int G = p->G, S = p->S;
+    c->gen_perm.resize(G);
+    c->sto_perm.resize(S);
+    std::iota(c->gen_perm.begin(), c->gen_perm.end(), 0);
+    std::iota(c->sto_perm.begin(), c->sto_perm.end(), 0);
+    // generators: by node, then by marginal cost — a settled dispatch parks the cheap ones at pmax and the dear
+    // ones at 0, so the rows the generator kernel may skip (and the ones it must stream) become contiguous
+    std::stable_sort(c->gen_perm.begin(), c->gen_perm.end(), [&](int a, int b) {
+        return p->gen_node[a] != p->gen_node[b] ? p->gen_node[a] < p->gen_node[b] : p->gen_mc[a] < p->gen_mc[b];
+    });
+    std::stable_sort(c->sto_perm.begin(), c->sto_perm.end(), [&](int a, int b) { return p->sto_node[a] < p->sto_node[b]; });
+    so.gmc.resize(G); so.gpm.resize(G); so.gnode.resize(G);
+    so.smc.resize(S); so.spm.resize(S); so.sem.resize(S); so.snode.resize(S);
+    for (int i = 0; i < G; ++i) { int a = c->gen_perm[i]; so.gmc[i] = p->gen_mc[a]; so.gpm[i] = p->gen_pmax[a]; so.gnode[i] = p->gen_node[a]; }
+    for (int i = 0; i < S; ++i) { int a = c->sto_perm[i]; so.smc[i] = p->sto_mc[a]; so.spm[i] = p->sto_pmax[a]; so.sem[i] = p->sto_emax[a]; so.snode[i] = p->sto_node[a]; }
+    for (int i = 0; i < G; ++i) if (!(so.gpm[i] >= 0)) return fail(c, DOPF_E_INVALID, "negative generator capacity");
+    for (int i = 0; i < S; ++i) if (!(so.spm[i] >= 0) || !(so.sem[i] >= 0)) return fail(c, DOPF_E_INVALID, "negative storage capacity");
+    return DOPF_OK;
+}
+
+// 5. what plan_chain needs of the problem, and the fixed-point scales of the one-launch iterations from the problem's bounds —
+// |sum of net injections| <= sum of pmax (a storage's D - C lies in [-pmax, pmax]), |cost| <= T * sum |mc| pmax (storages: 2 pmax) —
+// so that no accumulator can overflow
+Shape shape_and_scales(const dopf_problem *p, const Sorted &so, TailView *tv)
+{
+    const int N = p->N, T = p->T, G = p->G, S = p->S;
+    Shape sh{N, p->L, T, G, S, std::vector<int>(N, 0), std::vector<int>(N, 0), -1, -1};
+    for (int i = 0; i < G; ++i) ++sh.gen_at[so.gnode[i]];
+    for (int i = 0; i < S; ++i) ++sh.sto_at[so.snode[i]];
+    long double bi = 1.0L, bc = 1.0L;
+    for (int i = 0; i < G; ++i) { bi += so.gpm[i]; bc += (long double)T * std::fabs(so.gmc[i]) * so.gpm[i]; }
+    for (int i = 0; i < S; ++i) { bi += so.spm[i]; bc += (long double)T * std::fabs(so.smc[i]) * 2.0 * so.spm[i]; }
+    if (std::isfinite((double)bi) && std::isfinite((double)bc)) {
+        sh.ki = 52 - (int)std::ceil(std::log2((double)bi));
+        sh.kc = 52 - (int)std::ceil(std::log2((double)bc));
+    }
+    tv->accStride = (T + 1 + 15) / 16 * 16;                   // replicas on 128-byte lines of their own
+    tv->scaleInj = std::ldexp(1.0, std::max(0, std::min(sh.ki, 60))); tv->invInj = 1.0 / tv->scaleInj;
+    tv->scaleCost = std::ldexp(1.0, std::max(0, std::min(sh.kc, 60))); tv->invCost = 1.0 / tv->scaleCost;
+    return sh;
+}
+
+// 6. the chain (dopf_plan.h), and what the kernels read of it
+int choose_plan(dopf_ctx *c, const Shape &sh)
+{
+    hipDeviceProp_t prop{};
+    const int cus = hipGetDeviceProperties(&prop, c->device) == hipSuccess ? prop.multiProcessorCount : 0;
+    const Plan &pl = c->plan = plan_chain(sh, c->q.flags, cus);
+    if (pl.refusal) return fail(c, DOPF_E_UNSUPPORTED, "%s (T=%d)", pl.refusal, sh.T);
+    DevView &v = c->v;
+    v.use_warm = pl.useWarm; v.genSkip = pl.genSkip; v.genBlocks = v.genRows = pl.genBlocks; v.tablesInDual = pl.tablesInDual;
+    v.genTT = pl.genTT; v.genR = pl.genR; v.genTT2 = pl.genTT2; v.genR2 = pl.genR2; v.genTT256 = pl.genTT256;
+    v.genChunk = sh.N == 1 ? pl.genItem : 0; v.stoChunk = sh.N == 1 ? pl.stoItem : 0;
+    return DOPF_OK;
+}
+
+// 7. the layout's scalars (make_layout, dopf_plan.h) into the view, and the dynamic LDS they ask for
+int set_layout(dopf_ctx *c, const Layout &lo)
+{
+    DevView &v = c->v;
+    v.nGenItems = (int)lo.gen_items.size(); v.nStoItems = (int)lo.sto_items.size();
+    v.maxNodeAgents = lo.maxNodeAgents; v.rowsN = lo.rowsN; v.rowsT = lo.rowsT; v.reduceRB = lo.reduceRB;
+    v.dualRowsOff = lo.dualRowsOff; v.dualSdOff = lo.dualSdOff; v.dualLdsBytes = lo.dualLdsBytes;
+    HIPCHK(c, raise_lds_limits(v, c->plan));
+    return DOPF_OK;
+}
+
+// a run of device allocations and uploads that stops at the first failure (rc: its code; the message is in the context)
+struct DevRun {
+    dopf_ctx *c;
+    int rc = DOPF_OK;
+    template <class Tp> void zeros(Tp **out, size_t n) { if (!rc) rc = dev_alloc(c, out, n); }
+    template <class Tp> void raw(Tp **out, size_t n) { if (!rc) rc = dev_alloc(c, out, n, false); }
+    template <class Tp> void upload(const Tp **out, const std::vector<Tp> &h) { if (!rc) rc = dev_upload(c, out, h); }
+};
+
+// 8. the problem on the device: the network (with the fmax block)
+int upload_network(dopf_ctx *c, const dopf_problem *p)
+{
+    DevView &v = c->v;
+    DevRun d{c};
+    const int N = p->N, L = p->L, T = p->T;
+    d.upload(&v.demand, std::vector<double>(p->demand, p->demand + (size_t)N * T));
+    d.upload(&v.ptdf, std::vector<double>(p->ptdf, p->ptdf + (size_t)L * N));
+    std::vector<double> pt((size_t)L * N);
+    for (int l = 0; l < L; ++l)
+        for (int n = 0; n < N; ++n) pt[n + (size_t)N * l] = p->ptdf[l + (size_t)L * n];
+    d.upload(&v.ptdfT, pt);
+    // DOPF_F_LINE_RATING: every timestep of the table on f_max until the setter; the graphs capture this address once
+    const bool rating = (c->q.flags & DOPF_F_LINE_RATING) && L > 0;
+    std::vector<double> fm(fmax_doubles(L, T, rating));
+    for (size_t at = 0; at < fm.size(); at += (size_t)L) std::copy(p->f_max, p->f_max + L, fm.begin() + at);
+    d.upload(&v.fmax, fm);
+    v.fmax_ld = rating ? L : 0;
+    return d.rc;
+}
+
+// 9. the agents (with the gen_mc block and the storage block, each extension's part at its default; the storage block's mirror) ...
+int upload_agents(dopf_ctx *c, const Sorted &so)
+{
+    DevView &v = c->v;
+    DevRun d{c};
+    const size_t G = (size_t)v.G, S = (size_t)v.S;
+    std::vector<double> mc(so.gmc);
+    mc.resize(gen_mc_doubles(v.G, c->plan.genQuad), 0.0);
+    d.upload(&v.gen_mc, mc);
+    d.upload(&v.gen_pmax, so.gpm);
+    std::vector<double> mp(2 * G);
+    for (size_t i = 0; i < G; ++i) { mp[2 * i] = so.gmc[i]; mp[2 * i + 1] = so.gpm[i]; }
+    const double *mpd = nullptr;
+    d.upload(&mpd, mp);
+    v.gen_mp = reinterpret_cast<const double2 *>(mpd);
+    d.upload(&v.sto_mc, so.smc); d.upload(&v.sto_pmax, so.spm);
+    c->sto_pmax_h = so.spm;
+    c->sto_h.resize((size_t)sto_slots(c->plan) * S);
+    for (int slot = 0; slot < sto_slots(c->plan); ++slot)
+        for (size_t i = 0; i < S; ++i) c->sto_slot_h(slot)[i] = sto_slot_default(slot, so.sem[i]);
+    d.upload(&v.sto_emax, c->sto_h);
+    return d.rc;
+}
+
+// ... then the layout's arrays, with the bounds on an iteration's moves per node and per line
+int upload_layout(dopf_ctx *c, const dopf_problem *p, const Sorted &so, const Layout &lo)
+{
+    DevView &v = c->v;
+    DevRun d{c};
+    const int N = v.N, L = v.L;
+    d.upload(&v.gen_items, lo.gen_items); d.upload(&v.sto_items, lo.sto_items);
+    d.upload(&v.node_gen_beg, lo.node_gen_beg); d.upload(&v.node_sto_beg, lo.node_sto_beg);
+    // a generator moves by at most pmax per iteration, a storage's net injection D - C by at most 2 pmax
+    std::vector<double> win(N, 0.0);
+    for (int i = 0; i < v.G; ++i) win[so.gnode[i]] = std::max(win[so.gnode[i]], so.gpm[i]);
+    for (int i = 0; i < v.S; ++i) win[so.snode[i]] = std::max(win[so.snode[i]], 2.0 * so.spm[i]);
+    for (int n = 0; n < N; ++n) win[n] = win[n] * (1.0 + 1e-9) + 1e-9;
+    d.upload(&v.node_win, win);
+    // per line: the largest |kap| W_n over the nodes, kap = w2 h / (w2 + gamma) — if the line's slack offset clears it,
+    // every agent of every node has that slack active (or inactive) and the sums are a dot product (k_reduce)
+    const double w2 = 2.0 * c->q.w_flow, inv = 1.0 / (w2 + c->q.gamma);
+    std::vector<double> reach(L, 0.0);
+    for (int l = 0; l < L; ++l)
+        for (int n = 0; n < N; ++n) reach[l] = std::max(reach[l], std::fabs(w2 * p->ptdf[l + (size_t)L * n] * inv) * win[n]);
+    for (int l = 0; l < L; ++l) reach[l] = reach[l] * (1.0 + 1e-9) + 1e-300;      // strictly beyond every node's own reach
+    d.upload(&v.line_reach, reach);
+    d.upload(&v.node_gitem_beg, lo.node_gitem_beg); d.upload(&v.node_sitem_beg, lo.node_sitem_beg);
+    return d.rc;
+}
+
+// 10. the state, zeroed (with the gen_state block: the row states, and DOPF_F_GEN_AVAILABILITY's part behind them)
+int alloc_state(dopf_ctx *c, const Layout &lo, TailView &tvh)
+{
+    DevView &v = c->v;
+    const Plan &pl = c->plan;
+    DevRun d{c};
+    const int N = v.N, L = v.L, T = v.T, G = v.G, S = v.S;
+    const size_t NT = (size_t)N * T, LT = (size_t)L * T;
+    d.zeros(&v.P, (size_t)G * T);
+    d.zeros(&v.gen_state, gen_state_ints(G, pl.genAvail));            // zero = "all zero", which is what P is now
+    if (pl.genAvail && !d.rc) {
+        // every generator on gen_pmax until the setter (gen_prof(v)); no table yet (its address, gen_avail_slot(v), is null)
+        c->gen_prof_h.assign(G, -1);
+        HIPCHK(c, hipMemcpyAsync(gen_prof(v), c->gen_prof_h.data(), sizeof(int) * G, hipMemcpyHostToDevice, c->main));
+    }
+    d.zeros(&v.D, (size_t)S * T); d.zeros(&v.C, (size_t)S * T); d.zeros(&v.E, (size_t)S * T);
+    if (L > 0) { d.zeros(&v.dltG, (size_t)G * T); d.zeros(&v.dltS, (size_t)S * T); }
+    d.zeros(&v.lam, T); d.zeros(&v.mu, LT); d.zeros(&v.rho, LT);
+    d.zeros(&v.lam_used, T); d.zeros(&v.mu_used, LT); d.zeros(&v.rho_used, LT);
+    d.zeros(&v.inj, NT); d.zeros(&v.s, T); d.zeros(&v.flow, LT);
+    d.zeros(&v.avgU, LT); d.zeros(&v.avgK, LT); d.zeros(&v.price, NT);
+    d.zeros(&v.s_used, T); d.zeros(&v.flow_used, LT); d.zeros(&v.avgU_used, LT); d.zeros(&v.avgK_used, LT);
+    if (L > 0) {
+        d.zeros(&v.tb_beta, NT * v.M2); d.zeros(&v.tb_psi, NT * v.M2);
+        d.zeros(&v.tb_slope, NT * (v.M2 + 1)); d.zeros(&v.tb_psi0, NT);
+        d.zeros(&v.tb_m, NT);
+        d.zeros(&v.part_U, NT * L); d.zeros(&v.part_K, NT * L); d.zeros(&v.node_dsum, NT);
+        d.zeros(&v.walk_flag, LT); d.zeros(&v.walk_any, T); d.zeros(&v.tab_skip, T);
+    }
+    d.zeros(&v.part_ginj, (size_t)v.nGenItems * T); d.zeros(&v.part_gcost, v.nGenItems);
+    d.zeros(&v.part_sinj, (size_t)v.nStoItems * T); d.zeros(&v.part_scost, v.nStoItems);
+    d.zeros(&v.part_sinj_w, (size_t)v.nStoItems * T); d.zeros(&v.part_scost_w, v.nStoItems);
+    if (L > 0) { d.upload(&v.row_of_pos, lo.row_of_pos); d.upload(&v.pos_of_row, lo.pos_of_row); }
+    if (L > 0) d.zeros(&v.part_T, (size_t)v.rowsT * T);      // (networks: the ADMM kernels' layout; the rows above serve dopf_central_solve)
+    if (L > 0) d.zeros(&v.prev_node, NT);
+    d.zeros(&v.nu_prev, (size_t)S * T); d.zeros(&v.nu_valid, S); d.zeros(&v.sto_fail, S);
+    d.zeros(&v.item_fail, v.nStoItems);
+    d.zeros(&v.part2, (size_t)N * v.reduceRB * T); d.zeros(&v.part2_cost, v.reduceRB);
+    d.zeros(&v.reduce_ticket, (size_t)N * ((T + 31) / 32));
+    d.zeros(&v.dual_ticket, 1);
+    if (pl.tail) {
+        d.zeros(&tvh.acc, (size_t)2 * kAccRep * tvh.accStride);
+        tvh.expect = agent_blocks(v);
+        TailView *tvd = nullptr;
+        d.raw(&tvd, 1);
+        if (d.rc) return d.rc;
+        HIPCHK(c, hipMemcpy(tvd, &tvh, sizeof tvh, hipMemcpyHostToDevice));
+        v.tailDev = tvd;
+    }
+    if (pl.wideNet) {
+        std::vector<double> na(N);
+        for (int n = 0; n < N; ++n)
+            na[n] = (double)((lo.node_gen_beg[n + 1] - lo.node_gen_beg[n]) + (lo.node_sto_beg[n + 1] - lo.node_sto_beg[n]));
+        d.upload(&v.node_na, na);
+    }
+    double *cons = nullptr;
+    d.zeros(&cons, NT + 2 * LT + 1);
+    c->own_cons = cons;
+    v.cons = cons;
+    d.zeros(&v.st, 1);
+    return d.rc;
+}
+
+// 11. the "no result yet" state — zeros everywhere, injection = -demand (helpers/results.jl:14-73) — and the view itself in device
+// memory (non-inlined device functions take a pointer to it)
+int first_state(dopf_ctx *c)
+{
+    DevView &v = c->v;
+    Status st0{};
+    st0.iteration = 1;                                      // admm.jl:29
+    st0.res_set = -1;
+    HIPCHK(c, hipMemcpyAsync(v.st, &st0, sizeof st0, hipMemcpyHostToDevice, c->main));
+    launch_derive(v, c->plan, c->main, false);     // all-zero primal state: the consensus buffer is already zero
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    c->host_st = st0;
+    DevView *dv = nullptr;
+    if (const int rc = dev_alloc(c, &dv, 1, false)) return rc;
+    v.self = dv;
+    HIPCHK(c, hipMemcpy(dv, &v, sizeof(DevView), hipMemcpyHostToDevice));
+    return DOPF_OK;
+}
+
+// stages 3 to 11 on the context's device
+int build_context(dopf_ctx *c, const dopf_problem *p)
+{
+    if (const int rc = wide_tables_fit(c, p)) return rc;
+    if (const int rc = create_streams(c)) return rc;
+    set_scalars(c->v, p, &c->q);
+    Sorted so;
+    if (const int rc = sort_agents(c, p, so)) return rc;
+    TailView tvh{};
+    const Shape sh = shape_and_scales(p, so, &tvh);
+    if (const int rc = choose_plan(c, sh)) return rc;
+    const Layout lo = make_layout(sh, c->plan);
+    if (const int rc = set_layout(c, lo)) return rc;
+    if (const int rc = upload_network(c, p)) return rc;
+    if (const int rc = upload_agents(c, so)) return rc;
+    if (const int rc = upload_layout(c, p, so, lo)) return rc;
+    if (const int rc = alloc_state(c, lo, tvh)) return rc;
+    return first_state(c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -634,332 +805,19 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
 {
     if (!out || !p || !q) return fail(nullptr, DOPF_E_INVALID, "null argument");
     *out = nullptr;
-    if (p->N < 1 || p->T < 1 || p->L < 0 || p->G < 0 || p->S < 0)
-        return fail(nullptr, DOPF_E_INVALID, "bad sizes N=%d L=%d T=%d G=%d S=%d", p->N, p->L, p->T, p->G, p->S);
-    if (!(q->gamma > 0) || !(q->w_prox > 0) || !(q->w_flow > 0))
-        return fail(nullptr, DOPF_E_INVALID, "gamma, w_prox, w_flow must be positive");
-    if (!p->demand || (p->L > 0 && (!p->ptdf || !p->f_max)) || (p->G > 0 && (!p->gen_mc || !p->gen_pmax || !p->gen_node)) ||
-        (p->S > 0 && (!p->sto_mc || !p->sto_pmax || !p->sto_emax || !p->sto_node)))
-        return fail(nullptr, DOPF_E_INVALID, "null array in dopf_problem (every array with a positive extent must be given)");
-    for (int g = 0; g < p->G; ++g)
-        if (p->gen_node[g] < 0 || p->gen_node[g] >= p->N) return fail(nullptr, DOPF_E_INVALID, "gen_node[%d] out of range", g);
-    for (int s = 0; s < p->S; ++s)
-        if (p->sto_node[s] < 0 || p->sto_node[s] >= p->N) return fail(nullptr, DOPF_E_INVALID, "sto_node[%d] out of range", s);
-    if ((int64_t)p->G * p->T > (int64_t)1 << 40) return fail(nullptr, DOPF_E_INVALID, "problem too large");
-    Plan probe{};
-    if (p->S > 0 && !sto_config_supported(p->T, &probe) && !(q->flags & (DOPF_F_LONG_HORIZON | DOPF_F_DEBUG_LONG_STO)))
-        return fail(nullptr, DOPF_E_UNSUPPORTED, "storage kernel supports T <= 512 (got %d); longer horizons need DOPF_F_LONG_HORIZON", p->T);
-    if (2 * p->L > 4096 && !(q->flags & (DOPF_F_WIDE_NETWORK | DOPF_F_DEBUG_WIDE_NET)))
-        return fail(nullptr, DOPF_E_UNSUPPORTED, "table kernel supports L <= 2048 (got %d); wider networks need DOPF_F_WIDE_NETWORK", p->L);
-    const bool wide = wide_chain(p->L, q->flags);
-    if (wide) {
-        // the kernels index the PTDF (l + L*n) and the line state (l + L*t) in 32-bit ints (net_wide.h, k_slack, line_term)
-        if ((int64_t)p->L * p->N >= ((int64_t)1 << 31) || (int64_t)p->L * p->T >= ((int64_t)1 << 31) || (int64_t)p->L >= ((int64_t)1 << 29))
-            return fail(nullptr, DOPF_E_UNSUPPORTED, "wide chain needs L*N and L*T below 2^31 (L=%d N=%d T=%d)", p->L, p->N, p->T);
-    }
-
-    if (int rc1 = check_one_runtime(nullptr)) return rc1;
-    int ndev = 0;
-    hipError_t e0 = hipGetDeviceCount(&ndev);
-    if (e0 != hipSuccess || ndev < 1)
-        return fail(nullptr, DOPF_E_DEVICE, "no HIP device (%s); libdopf_hip has no CPU fallback", hipGetErrorString(e0));
-    int dev = q->device;
-    if (dev < 0) hipGetDevice(&dev);
-    if (dev >= ndev) return fail(nullptr, DOPF_E_INVALID, "device %d of %d", dev, ndev);
-
+    if (int rc = validate(p, q)) return rc;
+    int dev = 0;
+    if (int rc = pick_device(q, &dev)) return rc;
     dopf_ctx *c = new (std::nothrow) dopf_ctx;
     if (!c) return fail(nullptr, DOPF_E_NOMEM, "out of host memory");
     c->device = dev;
     c->q = *q;
     DeviceGuard guard(dev);
-    int rc = DOPF_OK;
-    auto bail = [&](int code) { strncpy(g_create_err, c->err, 511); dopf_destroy(c); return code; };
-#define TRY(x) do { rc = (x); if (rc) return bail(rc); } while (0)
-#define HIPTRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(c, DOPF_E_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); return bail(DOPF_E_DEVICE); } } while (0)
-    if (wide) {
-        // the wide chain keeps the worst-case table layout: tb_beta, tb_psi 2L, tb_slope 2L + 1 doubles, psi0 and m per
-        // (n,t), and the slack partials part_U / part_K L doubles each per (n,t). Checked before anything is allocated or launched.
-        const unsigned long long nt = (unsigned long long)p->N * p->T, l2 = 2ull * p->L;
-        const unsigned long long need = nt * ((3 * l2 + 1) * sizeof(double) + sizeof(double) + sizeof(int)) + 2 * nt * p->L * sizeof(double);
-        size_t freeb = 0, totalb = 0;
-        HIPTRY(hipMemGetInfo(&freeb, &totalb));
-        if (need > freeb) {
-            fail(c, DOPF_E_NOMEM, "wide chain: the breakpoint tables and slack partials need %llu bytes, the device has %llu free",
-                 need, (unsigned long long)freeb);
-            return bail(DOPF_E_NOMEM);
-        }
+    if (const int rc = build_context(c, p)) {
+        keep_error(c);
+        dopf_destroy(c);
+        return rc;
     }
-
-    // (Round 3 ran big networks — configs[3] at full size — with the storage solve on a second stream by itself: 145 -> 136 us per
-    // iteration. With generators and storages in one launch whose generator blocks work on both column halves at once
-    // (k_net_agents) the one-stream form is ahead again, 117.8 vs 124.9 us; DOPF_F_OVERLAP_AGENTS stays for whoever asks.)
-    if (q->stream) { c->main = (hipStream_t)q->stream; c->own_main = false; }
-    else { HIPTRY(hipStreamCreateWithFlags(&c->main, hipStreamNonBlocking)); c->own_main = true; }
-    // the side stream exists only when it is used: HIP maps streams onto a few hardware queues (4 by default), and a
-    // process whose streams outnumber them pays barrier packets on every launch (measured: two contexts + PyTorch's
-    // own streams made a 118-node iteration 4x slower)
-    if (c->q.flags & DOPF_F_OVERLAP_AGENTS) {
-        HIPTRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-        HIPTRY(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-        HIPTRY(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
-    }
-
-    DevView &v = c->v;
-    const int N = p->N, L = p->L, T = p->T, G = p->G, S = p->S;
-    v.N = N; v.L = L; v.T = T; v.G = G; v.S = S; v.M2 = 2 * L;
-    v.gamma = q->gamma; v.w_flow = q->w_flow; v.w_prox = q->w_prox; v.eps = q->eps; v.mask_thr = q->mask_thr;
-    v.max_iters = q->max_iters;
-    v.rootCap = (q->flags & DOPF_F_DEBUG_ROOT_CAP) ? 2 : 80;
-    v.keepDeltas = (q->flags & DOPF_F_KEEP_DELTAS) ? 1 : 0;
-    v.debugLeave = (q->flags & DOPF_F_DEBUG_LEAVE) ? 1 : 0;
-    const int A = q->n_agents_global > 0 ? q->n_agents_global : G + S;
-    v.invA = A > 0 ? 1.0 / (double)A : 0.0;
-    v.nAgents = (double)A;
-    {
-        const double a0 = v.w_prox + v.gamma;
-        v.cp_ia = 1.0 / a0; v.cp_idet = 1.0 / (a0 * a0 - v.gamma * v.gamma); v.cp_s2 = 2.0 / (a0 + v.gamma);
-    }
-
-    // sort agents by node (stable), remember the permutation
-    c->gen_perm.resize(G);
-    c->sto_perm.resize(S);
-    std::iota(c->gen_perm.begin(), c->gen_perm.end(), 0);
-    std::iota(c->sto_perm.begin(), c->sto_perm.end(), 0);
-    // generators: by node, then by marginal cost — a settled dispatch parks the cheap ones at pmax and the dear
-    // ones at 0, so the rows the generator kernel may skip (and the ones it must stream) become contiguous
-    std::stable_sort(c->gen_perm.begin(), c->gen_perm.end(), [&](int a, int b) {
-        return p->gen_node[a] != p->gen_node[b] ? p->gen_node[a] < p->gen_node[b] : p->gen_mc[a] < p->gen_mc[b];
-    });
-    std::stable_sort(c->sto_perm.begin(), c->sto_perm.end(), [&](int a, int b) { return p->sto_node[a] < p->sto_node[b]; });
-    std::vector<double> gmc(G), gpm(G), smc(S), spm(S), sem(S);
-    std::vector<int> gnode(G), snode(S);
-    for (int i = 0; i < G; ++i) { int a = c->gen_perm[i]; gmc[i] = p->gen_mc[a]; gpm[i] = p->gen_pmax[a]; gnode[i] = p->gen_node[a]; }
-    for (int i = 0; i < S; ++i) { int a = c->sto_perm[i]; smc[i] = p->sto_mc[a]; spm[i] = p->sto_pmax[a]; sem[i] = p->sto_emax[a]; snode[i] = p->sto_node[a]; }
-    for (int i = 0; i < G; ++i) if (!(gpm[i] >= 0)) { fail(c, DOPF_E_INVALID, "negative generator capacity"); return bail(DOPF_E_INVALID); }
-    for (int i = 0; i < S; ++i) if (!(spm[i] >= 0) || !(sem[i] >= 0)) { fail(c, DOPF_E_INVALID, "negative storage capacity"); return bail(DOPF_E_INVALID); }
-
-    // the chain
-    Shape sh{N, L, T, G, S, std::vector<int>(N, 0), std::vector<int>(N, 0), -1, -1};
-    for (int i = 0; i < G; ++i) ++sh.gen_at[gnode[i]];
-    for (int i = 0; i < S; ++i) ++sh.sto_at[snode[i]];
-    TailView tvh{};
-    {
-        // One-launch iterations: fixed-point scales from the problem's bounds — |sum of net injections| <= sum of pmax (a storage's
-        // D - C lies in [-pmax, pmax]), |cost| <= T * sum |mc| pmax (storages: 2 pmax) — so that no accumulator can overflow
-        long double bi = 1.0L, bc = 1.0L;
-        for (int i = 0; i < G; ++i) { bi += gpm[i]; bc += (long double)T * std::fabs(gmc[i]) * gpm[i]; }
-        for (int i = 0; i < S; ++i) { bi += spm[i]; bc += (long double)T * std::fabs(smc[i]) * 2.0 * spm[i]; }
-        if (std::isfinite((double)bi) && std::isfinite((double)bc)) {
-            sh.ki = 52 - (int)std::ceil(std::log2((double)bi));
-            sh.kc = 52 - (int)std::ceil(std::log2((double)bc));
-        }
-        tvh.accStride = (T + 1 + 15) / 16 * 16;                   // replicas on 128-byte lines of their own
-        tvh.scaleInj = std::ldexp(1.0, std::max(0, std::min(sh.ki, 60))); tvh.invInj = 1.0 / tvh.scaleInj;
-        tvh.scaleCost = std::ldexp(1.0, std::max(0, std::min(sh.kc, 60))); tvh.invCost = 1.0 / tvh.scaleCost;
-    }
-    hipDeviceProp_t prop{};
-    const int cus = hipGetDeviceProperties(&prop, c->device) == hipSuccess ? prop.multiProcessorCount : 0;
-    const Plan &pl = c->plan = plan_chain(sh, q->flags, cus);
-    if (pl.refusal) { fail(c, DOPF_E_UNSUPPORTED, "%s (T=%d)", pl.refusal, T); return bail(DOPF_E_UNSUPPORTED); }
-    v.use_warm = pl.useWarm; v.genSkip = pl.genSkip; v.genBlocks = v.genRows = pl.genBlocks; v.tablesInDual = pl.tablesInDual;
-    v.genTT = pl.genTT; v.genR = pl.genR; v.genTT2 = pl.genTT2; v.genR2 = pl.genR2; v.genTT256 = pl.genTT256;
-    v.genChunk = N == 1 ? pl.genItem : 0; v.stoChunk = N == 1 ? pl.stoItem : 0;
-
-    // work items and rows
-    std::vector<Item> gitems, sitems;
-    std::vector<int> ngb, nsb, ngib, nsib, row_of_pos, pos_of_row;
-    make_items(gnode, N, pl.genItem, gitems, ngb, ngib);
-    make_items(snode, N, pl.stoItem, sitems, nsb, nsib);
-    v.maxNodeAgents = 0;
-    for (int n = 0; n < N; ++n) v.maxNodeAgents = std::max(v.maxNodeAgents, (ngb[n + 1] - ngb[n]) + (nsb[n + 1] - nsb[n]));
-    v.nGenItems = (int)gitems.size();
-    v.nStoItems = (int)sitems.size();
-    if (L > 0) {
-        // rows of the transposed partial sums (DevView::part_T): node n owns rows [g0 + 2 s0, ...) — its generator items, then two per storage item
-        // (node order: generator item i -> i + 2 s0, storage item k -> g0' + 2 k and the row behind it; then placed by the writer's XCD)
-        v.rowsN = v.nGenItems + 2 * v.nStoItems;
-        std::vector<int> xcd((size_t)v.rowsN, 0), cnt(8, 0), beg(9, 0);
-        for (int i = 0; i < v.nGenItems; ++i) {
-            gitems[i].row = i + 2 * nsib[gitems[i].node];
-            xcd[(size_t)gitems[i].row] = gen_row_xcd(pl, i);
-        }
-        for (int k = 0; k < v.nStoItems; ++k) {
-            sitems[k].row = ngib[sitems[k].node + 1] + 2 * k;
-            xcd[(size_t)sitems[k].row] = xcd[(size_t)sitems[k].row + 1] = k % 8;
-        }
-        for (int g = 0; g < v.rowsN; ++g) ++cnt[(size_t)xcd[(size_t)g]];
-        for (int x = 0; x < 8; ++x) beg[(size_t)x + 1] = beg[(size_t)x] + (cnt[(size_t)x] + 15) / 16 * 16;
-        v.rowsT = beg[8];           // (= pl.rowsT)
-        row_of_pos.assign((size_t)std::max(v.rowsT, 1), -1); pos_of_row.assign((size_t)std::max(v.rowsN, 1), 0);
-        std::vector<int> fillp(beg.begin(), beg.begin() + 8);
-        for (int g = 0; g < v.rowsN; ++g) { const int p_ = fillp[(size_t)xcd[(size_t)g]]++; row_of_pos[(size_t)p_] = g; pos_of_row[(size_t)g] = p_; }
-        for (int i = 0; i < v.nGenItems; ++i) gitems[i].row = pos_of_row[(size_t)gitems[i].row];
-        for (int k = 0; k < v.nStoItems; ++k) sitems[k].row = pos_of_row[(size_t)sitems[k].row];       // (the warm-start row: the next position)
-    }
-    {
-        // level-1 reduce blocks per node: ~16 items per block, at most 64 (and N*RB blocks in total)
-        int max_items = 1;
-        for (int n = 0; n < N; ++n)      // storage items: scan + warm rows; generators: items, or (one node, streaming) blocks
-            max_items = std::max(max_items, (v.genRows > 0 ? v.genRows : ngib[n + 1] - ngib[n]) + 2 * (nsib[n + 1] - nsib[n]));
-        v.reduceRB = std::max(1, std::min(64, (max_items + 31) / 32));
-        // Networks: nodes x timestep chunks already give hundreds of blocks, and more than one block per node means the
-        // two-level sum — an agent-scope release (a write-back of the XCD's L2) and a ticket in EVERY block. configs[3] at full
-        // size has a node with 36 partial rows: 2 blocks per node, 1 416 releases, k_reduce 38 us instead of 9. One block per
-        // node walks up to 128 rows (four passes of its 8 x 4 loads in flight) before a second one is worth its ticket.
-        if ((long long)N * ((T + 31) / 32) >= 128) v.reduceRB = std::max(1, std::min(64, (max_items + 127) / 128));
-    }
-    {   // dynamic LDS of k_dual_price_t1024: q[N] | d[L] | G[L] | S[L] | the rows of its timestep (quiet chain), later the tables'
-        // scratch | sd[N] win[N] na[N]
-        const size_t scratch = (size_t)pl.tablesInDual * (4 * (size_t)v.M2 + 1);
-        v.dualRowsOff = N + 3 * L;
-        v.dualSdOff = v.dualRowsOff + (int)std::max(scratch, (size_t)(quiet_rows_fit(v.rowsT) ? v.rowsN : 0));
-        v.dualLdsBytes = (int)(((size_t)v.dualSdOff + 3 * (size_t)N) * sizeof(double));
-    }
-    HIPTRY(raise_lds_limits(v, pl));
-
-    const size_t NT = (size_t)N * T, LT = (size_t)L * T;
-    TRY(dev_upload(c, &v.demand, std::vector<double>(p->demand, p->demand + NT)));
-    TRY(dev_upload(c, &v.ptdf, std::vector<double>(p->ptdf, p->ptdf + (size_t)L * N)));
-    {
-        std::vector<double> pt((size_t)L * N);
-        for (int l = 0; l < L; ++l)
-            for (int n = 0; n < N; ++n) pt[n + (size_t)N * l] = p->ptdf[l + (size_t)L * n];
-        TRY(dev_upload(c, &v.ptdfT, pt));
-    }
-    if ((q->flags & DOPF_F_LINE_RATING) && L > 0) {
-        // DOPF_F_LINE_RATING: the L x T rating table, every timestep on f_max until the setter, and f_max itself behind it
-        // (line_fmax0); the graphs capture this address once
-        std::vector<double> tab(LT + (size_t)L);
-        for (int t = 0; t <= T; ++t) std::copy(p->f_max, p->f_max + L, tab.begin() + (size_t)L * t);
-        TRY(dev_upload(c, &v.fmax, tab));
-        v.fmax_ld = L;
-    } else {
-        TRY(dev_upload(c, &v.fmax, std::vector<double>(p->f_max, p->f_max + L)));
-    }
-    if (pl.genQuad) {
-        // DOPF_F_GEN_QUADRATIC_COST: the quadratic coefficients behind the marginal costs (gen_c2), all 0 until the setter
-        std::vector<double> mc2(gmc);
-        mc2.resize(2 * (size_t)G, 0.0);
-        TRY(dev_upload(c, &v.gen_mc, mc2));
-    } else {
-        TRY(dev_upload(c, &v.gen_mc, gmc));
-    }
-    TRY(dev_upload(c, &v.gen_pmax, gpm));
-    {
-        std::vector<double> mp(2 * (size_t)G);
-        for (int i = 0; i < G; ++i) { mp[2 * (size_t)i] = gmc[i]; mp[2 * (size_t)i + 1] = gpm[i]; }
-        const double *d = nullptr;
-        TRY(dev_upload(c, &d, mp));
-        v.gen_mp = reinterpret_cast<const double2 *>(d);
-    }
-    TRY(dev_upload(c, &v.sto_mc, smc)); TRY(dev_upload(c, &v.sto_pmax, spm));
-    if (c->plan.stoE0 || c->plan.stoLV >= 2) {
-        // DOPF_F_STO_INITIAL_LEVEL: the initial levels behind the max levels (sto_e0), all 0 until the setter (and without that flag);
-        // DOPF_F_STO_TERMINAL_LEVEL: the terminal bands behind those (sto_end_lo, sto_end_hi), [0, emax] until the setter
-        c->sto_emax_h = sem;
-        c->sto_pmax_h = spm;
-        c->sto_e0_h.assign(S, 0.0);
-        c->sto_lo_h.assign(S, 0.0);
-        c->sto_hi_h = sem;
-        std::vector<double> em2(sem);
-        em2.resize(2 * (size_t)S, 0.0);
-        if (c->plan.stoLV >= 2) { em2.resize(3 * (size_t)S, 0.0); em2.insert(em2.end(), sem.begin(), sem.end()); }
-        if (c->plan.stoEff) {       // DOPF_F_STO_EFFICIENCY: al = 1 / eta_d and be = eta_c behind the bands (sto_eff_alpha, sto_eff_beta), ones until the setter
-            c->sto_al_h.assign(S, 1.0);
-            c->sto_be_h.assign(S, 1.0);
-            em2.resize(6 * (size_t)S, 1.0);
-        }
-        TRY(dev_upload(c, &v.sto_emax, em2));
-    } else {
-        TRY(dev_upload(c, &v.sto_emax, sem));
-    }
-    TRY(dev_upload(c, &v.gen_items, gitems)); TRY(dev_upload(c, &v.sto_items, sitems));
-    TRY(dev_upload(c, &v.node_gen_beg, ngb)); TRY(dev_upload(c, &v.node_sto_beg, nsb));
-    {
-        // a generator moves by at most pmax per iteration, a storage's net injection D - C by at most 2 pmax
-        std::vector<double> win(N, 0.0);
-        for (int i = 0; i < G; ++i) win[gnode[i]] = std::max(win[gnode[i]], gpm[i]);
-        for (int i = 0; i < S; ++i) win[snode[i]] = std::max(win[snode[i]], 2.0 * spm[i]);
-        for (int n = 0; n < N; ++n) win[n] = win[n] * (1.0 + 1e-9) + 1e-9;
-        TRY(dev_upload(c, &v.node_win, win));
-        // per line: the largest |kap| W_n over the nodes, kap = w2 h / (w2 + gamma) — if the line's slack offset clears it,
-        // every agent of every node has that slack active (or inactive) and the sums are a dot product (k_reduce)
-        const double w2 = 2.0 * q->w_flow, inv = 1.0 / (w2 + q->gamma);
-        std::vector<double> reach(L, 0.0);
-        for (int l = 0; l < L; ++l)
-            for (int n = 0; n < N; ++n) reach[l] = std::max(reach[l], std::fabs(w2 * p->ptdf[l + (size_t)L * n] * inv) * win[n]);
-        for (int l = 0; l < L; ++l) reach[l] = reach[l] * (1.0 + 1e-9) + 1e-300;      // strictly beyond every node's own reach
-        TRY(dev_upload(c, &v.line_reach, reach));
-    }
-    TRY(dev_upload(c, &v.node_gitem_beg, ngib)); TRY(dev_upload(c, &v.node_sitem_beg, nsib));
-    TRY(dev_alloc(c, &v.P, (size_t)G * T));
-    TRY(dev_alloc(c, &v.gen_state, gen_state_ints(G, pl.genAvail)));            // zero = "all zero", which is what P is now
-    if (pl.genAvail) {
-        // DOPF_F_GEN_AVAILABILITY: every generator on gen_pmax until the setter (gen_prof(v), behind the row states); no table yet
-        // (its address, behind those, is null)
-        c->gen_prof_h.assign(G, -1);
-        HIPTRY(hipMemcpyAsync(gen_prof(v), c->gen_prof_h.data(), sizeof(int) * G, hipMemcpyHostToDevice, c->main));
-    }
-    TRY(dev_alloc(c, &v.D, (size_t)S * T)); TRY(dev_alloc(c, &v.C, (size_t)S * T)); TRY(dev_alloc(c, &v.E, (size_t)S * T));
-    if (L > 0) { TRY(dev_alloc(c, &v.dltG, (size_t)G * T)); TRY(dev_alloc(c, &v.dltS, (size_t)S * T)); }
-    TRY(dev_alloc(c, &v.lam, T)); TRY(dev_alloc(c, &v.mu, LT)); TRY(dev_alloc(c, &v.rho, LT));
-    TRY(dev_alloc(c, &v.lam_used, T)); TRY(dev_alloc(c, &v.mu_used, LT)); TRY(dev_alloc(c, &v.rho_used, LT));
-    TRY(dev_alloc(c, &v.inj, NT)); TRY(dev_alloc(c, &v.s, T)); TRY(dev_alloc(c, &v.flow, LT));
-    TRY(dev_alloc(c, &v.avgU, LT)); TRY(dev_alloc(c, &v.avgK, LT)); TRY(dev_alloc(c, &v.price, NT));
-    TRY(dev_alloc(c, &v.s_used, T)); TRY(dev_alloc(c, &v.flow_used, LT)); TRY(dev_alloc(c, &v.avgU_used, LT)); TRY(dev_alloc(c, &v.avgK_used, LT));
-    if (L > 0) {
-        TRY(dev_alloc(c, &v.tb_beta, NT * v.M2)); TRY(dev_alloc(c, &v.tb_psi, NT * v.M2));
-        TRY(dev_alloc(c, &v.tb_slope, NT * (v.M2 + 1))); TRY(dev_alloc(c, &v.tb_psi0, NT));
-        TRY(dev_alloc(c, &v.tb_m, NT));
-        TRY(dev_alloc(c, &v.part_U, NT * L)); TRY(dev_alloc(c, &v.part_K, NT * L)); TRY(dev_alloc(c, &v.node_dsum, NT));
-        TRY(dev_alloc(c, &v.walk_flag, LT)); TRY(dev_alloc(c, &v.walk_any, T)); TRY(dev_alloc(c, &v.tab_skip, T));
-    }
-    TRY(dev_alloc(c, &v.part_ginj, (size_t)v.nGenItems * T)); TRY(dev_alloc(c, &v.part_gcost, v.nGenItems));
-    TRY(dev_alloc(c, &v.part_sinj, (size_t)v.nStoItems * T)); TRY(dev_alloc(c, &v.part_scost, v.nStoItems));
-    TRY(dev_alloc(c, &v.part_sinj_w, (size_t)v.nStoItems * T)); TRY(dev_alloc(c, &v.part_scost_w, v.nStoItems));
-    if (L > 0) { TRY(dev_upload(c, &v.row_of_pos, row_of_pos)); TRY(dev_upload(c, &v.pos_of_row, pos_of_row)); }
-    if (L > 0) TRY(dev_alloc(c, &v.part_T, (size_t)v.rowsT * T));      // (networks: the ADMM kernels' layout; the rows above serve dopf_central_solve)
-    if (L > 0) TRY(dev_alloc(c, &v.prev_node, NT));
-    TRY(dev_alloc(c, &v.nu_prev, (size_t)S * T)); TRY(dev_alloc(c, &v.nu_valid, S)); TRY(dev_alloc(c, &v.sto_fail, S));
-    TRY(dev_alloc(c, &v.item_fail, v.nStoItems));
-    TRY(dev_alloc(c, &v.part2, (size_t)N * v.reduceRB * T)); TRY(dev_alloc(c, &v.part2_cost, v.reduceRB));
-    TRY(dev_alloc(c, &v.reduce_ticket, (size_t)N * ((T + 31) / 32)));
-    TRY(dev_alloc(c, &v.dual_ticket, 1));
-    if (pl.tail) {
-        TRY(dev_alloc(c, &tvh.acc, (size_t)2 * kAccRep * tvh.accStride));
-        tvh.expect = (pl.fuseAgents && v.genBlocks > 0 && !v.genSkip ? v.genBlocks : v.nGenItems) + v.nStoItems;
-        TailView *tvd = nullptr;
-        TRY(dev_alloc(c, &tvd, 1, false));
-        HIPTRY(hipMemcpy(tvd, &tvh, sizeof tvh, hipMemcpyHostToDevice));
-        v.tailDev = tvd;
-    }
-    if (pl.wideNet) {
-        std::vector<double> na(N);
-        for (int n = 0; n < N; ++n) na[n] = (double)((ngb[n + 1] - ngb[n]) + (nsb[n + 1] - nsb[n]));
-        TRY(dev_upload(c, &v.node_na, na));
-    }
-    double *cons = nullptr;
-    TRY(dev_alloc(c, &cons, NT + 2 * LT + 1));
-    c->own_cons = cons;
-    v.cons = cons;
-    TRY(dev_alloc(c, &v.st, 1));
-    Status st0{};
-    st0.iteration = 1;                                      // admm.jl:29
-    st0.res_set = -1;
-    HIPTRY(hipMemcpyAsync(v.st, &st0, sizeof st0, hipMemcpyHostToDevice, c->main));
-    // "no result yet" state: zeros everywhere, injection = -demand (helpers/results.jl:14-73)
-    launch_derive(v, pl, c->main, false);     // all-zero primal state: the consensus buffer is already zero
-    HIPTRY(hipGetLastError());
-    HIPTRY(hipStreamSynchronize(c->main));
-    c->host_st = st0;
-    {   // the view itself in device memory (non-inlined device functions take a pointer to it)
-        DevView *dv = nullptr;
-        TRY(dev_alloc(c, &dv, 1, false));
-        v.self = dv;
-        HIPTRY(hipMemcpy(dv, &v, sizeof(DevView), hipMemcpyHostToDevice));
-    }
-#undef TRY
-#undef HIPTRY
     *out = c;
     return DOPF_OK;
 }
@@ -1502,33 +1360,35 @@ static int stage_and_copy(dopf_ctx *c, const std::vector<int> &perm, std::vector
     return DOPF_OK;
 }
 
+// The storage setters' common step: `n` slots of the storage block from slot `first` on (dopf_internal.h: StoSlot) take the caller's arrays
+// a and b (NULL: the slot's default), on the device and in the context's mirror
+static int set_sto_slots(dopf_ctx *c, int first, int n, const double *a, const double *b)
+{
+    const size_t S = (size_t)c->v.S;
+    DeviceGuard guard(c->device);
+    std::vector<double> h((size_t)n * S);
+    for (int k = 0; k < n; ++k)
+        for (size_t i = 0; i < S; ++i) h[k * S + i] = sto_slot_default(first + k, c->sto_at(kStoEmax, (int)i));
+    if (int rc = stage_and_copy(c, c->sto_perm, h, a, b, sto_slot(c->v, first))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    std::copy(h.begin(), h.end(), c->sto_slot_h(first));          // (what the other setters check reachability against)
+    return DOPF_OK;
+}
+
 int dopf_set_storage_initial_level(dopf_ctx *c, const double *e0)
 {
     if (!c) return DOPF_E_INVALID;
     if (int rc = check_initial_levels(c, e0)) return rc;
     if (c->v.S == 0) return DOPF_OK;
-    DeviceGuard guard(c->device);
-    std::vector<double> h(c->v.S, 0.0);
-    if (int rc = stage_and_copy(c, c->sto_perm, h, e0, nullptr, sto_e0(c->v))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->main));
-    c->sto_e0_h = h;                        // (what the terminal-level setter checks reachability from)
-    return DOPF_OK;
+    return set_sto_slots(c, kStoE0, 1, e0, nullptr);
 }
 
 int dopf_set_storage_terminal_level(dopf_ctx *c, const double *lo, const double *hi)
 {
     if (!c) return DOPF_E_INVALID;
     if (int rc = check_terminal_levels(c, lo, hi)) return rc;
-    const int S = c->v.S;
-    if (S == 0) return DOPF_OK;
-    DeviceGuard guard(c->device);
-    std::vector<double> h(2 * (size_t)S, 0.0);   // lo then hi: sto_end_hi(v) = sto_end_lo(v) + S
-    std::copy(c->sto_emax_h.begin(), c->sto_emax_h.end(), h.begin() + S);
-    if (int rc = stage_and_copy(c, c->sto_perm, h, lo, hi, sto_end_lo(c->v))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->main));
-    c->sto_lo_h.assign(h.begin(), h.begin() + S);
-    c->sto_hi_h.assign(h.begin() + S, h.end());
-    return DOPF_OK;
+    if (c->v.S == 0) return DOPF_OK;
+    return set_sto_slots(c, kStoEndLo, 2, lo, hi);
 }
 
 int dopf_set_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta_d)
@@ -1537,17 +1397,12 @@ int dopf_set_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *
     if (int rc = check_storage_efficiency(c, eta_c, eta_d)) return rc;
     const int S = c->v.S;
     if (S == 0) return DOPF_OK;
-    DeviceGuard guard(c->device);
-    std::vector<double> h(2 * (size_t)S, 1.0), al;   // al then be: sto_eff_beta(v) = sto_eff_alpha(v) + S
+    std::vector<double> al;
     if (eta_d) {
         al.resize(S);
         for (int a = 0; a < S; ++a) al[a] = 1.0 / eta_d[a];
     }
-    if (int rc = stage_and_copy(c, c->sto_perm, h, eta_d ? al.data() : nullptr, eta_c, sto_eff_alpha(c->v))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->main));
-    c->sto_al_h.assign(h.begin(), h.begin() + S);
-    c->sto_be_h.assign(h.begin() + S, h.end());
-    return DOPF_OK;
+    return set_sto_slots(c, kStoAlpha, 2, eta_d ? al.data() : nullptr, eta_c);
 }
 
 int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const double *profiles, const int32_t *profile_of)
@@ -1717,7 +1572,7 @@ int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
     HIPCHK(c, hipGetLastError());
     c->quiet = false;                      // (flags are formed anew from the moved state)
     c->level_from_primal = true;           // (a central solve's levels belonged to the old window)
-    if (S > 0) c->sto_e0_h = e0s;
+    if (S > 0) std::copy(e0s.begin(), e0s.end(), c->sto_slot_h(kStoE0));
     return read_status(c);
 }
 

@@ -32,11 +32,9 @@ struct dopf_ctx {
     double *getter_scratch = nullptr;      // 3 * N * T doubles, allocated at the first getter that needs them (freed with the context)
     double *roll_scratch = nullptr;        // dopf_set_demand / dopf_roll_horizon: the moved vectors, the demand tail, the new initial levels
     std::vector<int> gen_perm, sto_perm;   // sorted position -> caller's index
-    std::vector<double> sto_emax_h;        // DOPF_F_STO_INITIAL_LEVEL / _TERMINAL_LEVEL: the storages' max_level in sorted order (the setters' bounds)
-    std::vector<double> sto_pmax_h;        // DOPF_F_STO_TERMINAL_LEVEL: max charge / discharge per step, sorted order (reachability)
-    std::vector<double> sto_e0_h, sto_lo_h, sto_hi_h;   // the values on the device: initial levels, terminal bands (sorted order; each
-                                                        // setter checks reachability against the other's)
-    std::vector<double> sto_al_h, sto_be_h;   // DOPF_F_STO_EFFICIENCY: 1 / eta_d and eta_c on the device (sorted order; empty without the flag)
+    std::vector<double> sto_h;             // the storage block as it is on the device (dopf_internal.h: StoSlot, sto_slots(plan) slots of S
+                                           // values, sorted order): the setters' bounds, and what each checks reachability against
+    std::vector<double> sto_pmax_h;        // max charge / discharge per step, sorted order (reachability)
     std::vector<int> gen_prof_h;           // DOPF_F_GEN_AVAILABILITY: the generators' profile indices on the device (sorted order)
     double *gen_avail = nullptr;           // ... the profile table on the device (its address is in gen_avail_slot(v)) and the
     int gen_avail_cap = 0;                 //     profiles it has room for
@@ -47,6 +45,8 @@ struct dopf_ctx {
     bool tail_xchg = false;                // peer exchange inside the tail block of the one-launch iteration (copper plates)
     bool level_from_primal = true;         // dopf_get_primal rebuilds E = cumsum(C - D); false while a central solve's own levels are in v.E
     char err[512] = {0};
+    double *sto_slot_h(int slot) { return sto_h.data() + (size_t)slot * (size_t)v.S; }                  // a held slot of the mirror
+    double sto_at(int slot, int i) const { return sto_h[(size_t)slot * (size_t)v.S + (size_t)i]; }      // ... and sorted storage i of it
 };
 
 namespace dopf {

@@ -16,27 +16,16 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "../../include/dopf.h"
+#include "dopf_plan.h"
 
 namespace dopf {
-
-// Sizing knobs of the experiments (item and block counts, the exchange's rendezvous wait) are environment
-// variables of builds with -DDOPF_EXPERIMENTS only; none of them chooses a kernel. plan_chain reads them (and the exchange its own).
-#ifdef DOPF_EXPERIMENTS
-inline const char *exp_env(const char *name) { return getenv(name); }
-#else
-inline const char *exp_env(const char *) { return nullptr; }
-#endif
-
-// one block's share of the agent list: agents [a0, a1) all sit at `node`
-struct Item {
-    int a0, a1, node, row;          // row (networks): the item's row in DevView::part_T (a storage item's scan partial; its warm-start partial: row + 1)
-};
 
 // device-resident status word block (one per context)
 struct Status {
@@ -168,22 +157,44 @@ struct DevView {
     const double *node_na;                          // wide chain: [n] agents at node n as a number (k_reduce's naL, read from memory)
 };
 
-// the storages' initial levels (DOPF_F_STO_INITIAL_LEVEL contexts only: zeros until dopf_set_storage_initial_level), sorted order
-__host__ __device__ inline const double *sto_e0(const DevView &v) { return v.sto_emax + v.S; }
-// the band of each storage's level after the last timestep (DOPF_F_STO_TERMINAL_LEVEL contexts only: [0, emax] until
-// dopf_set_storage_terminal_level), sorted order
-__host__ __device__ inline const double *sto_end_lo(const DevView &v) { return v.sto_emax + 2 * (size_t)v.S; }
-__host__ __device__ inline const double *sto_end_hi(const DevView &v) { return v.sto_emax + 3 * (size_t)v.S; }
-// DOPF_F_STO_EFFICIENCY contexts only (sto_emax then has 6S entries; e0 and the band at their defaults without the other two flags):
-// al = 1 / eta_d and be = eta_c of each storage, sorted order, ones until dopf_set_storage_efficiency. The level moves by be C - al D.
-__host__ __device__ inline const double *sto_eff_alpha(const DevView &v) { return v.sto_emax + 4 * (size_t)v.S; }
-__host__ __device__ inline const double *sto_eff_beta(const DevView &v) { return v.sto_emax + 5 * (size_t)v.S; }
+// The view is every kernel's argument and keeps its layout: a longer DevView moved the register allocation of the fused storage
+// kernels. What the extensions add lives BEHIND arrays the view already names — the four blocks below — and
+// fmax_ld sits in what was padding in front of gamma.
+static_assert(sizeof(DevView) == 832, "DevView must keep its size");
+static_assert(offsetof(DevView, fmax_ld) == 172 && offsetof(DevView, gamma) == 176, "fmax_ld fills the padding in front of gamma");
 
-// the line limits dopf_create was given, one per line (what the central reference reads: it takes no ratings). Without
-// DOPF_F_LINE_RATING that is fmax itself; with it they sit behind the L x T table.
+// The storage block (v.sto_emax): S doubles per slot, sorted order, the slots a context holds in this order. The one description of
+// the format: dopf_create fills the block from it, the setters take their defaults and destinations from it, and the context's
+// host mirror (dopf_ctx::sto_h) has the same shape.
+//   emax           the max levels of dopf_create
+//   e0             initial levels (DOPF_F_STO_INITIAL_LEVEL: zeros until dopf_set_storage_initial_level)
+//   end_lo, end_hi the band of the level after the last timestep (DOPF_F_STO_TERMINAL_LEVEL: [0, emax] until
+//                  dopf_set_storage_terminal_level)
+//   alpha, beta    al = 1 / eta_d and be = eta_c (DOPF_F_STO_EFFICIENCY: ones until dopf_set_storage_efficiency); the level moves
+//                  by be C - al D
+enum StoSlot : int { kStoEmax, kStoE0, kStoEndLo, kStoEndHi, kStoAlpha, kStoBeta };
+// slots of a context's block, by the plan's level mode (Plan::stoLV): a mode holds every slot below its own, at the defaults
+constexpr int kStoSlotsOfLV[4] = {1, 2, 4, 6};
+inline int sto_slots(const Plan &p) { return kStoSlotsOfLV[p.stoLV]; }
+inline double sto_slot_default(int slot, double emax) { return slot == kStoEmax || slot == kStoEndHi ? emax : slot >= kStoAlpha ? 1.0 : 0.0; }
+__host__ __device__ inline const double *sto_slot(const DevView &v, int slot) { return v.sto_emax + (size_t)slot * (size_t)v.S; }
+__host__ __device__ inline const double *sto_e0(const DevView &v) { return sto_slot(v, kStoE0); }
+__host__ __device__ inline const double *sto_end_lo(const DevView &v) { return sto_slot(v, kStoEndLo); }
+__host__ __device__ inline const double *sto_end_hi(const DevView &v) { return sto_slot(v, kStoEndHi); }
+__host__ __device__ inline const double *sto_eff_alpha(const DevView &v) { return sto_slot(v, kStoAlpha); }
+__host__ __device__ inline const double *sto_eff_beta(const DevView &v) { return sto_slot(v, kStoBeta); }
+
+// The fmax block (v.fmax): one limit per line, or with DOPF_F_LINE_RATING (fmax_ld = L) the L x T rating table — every timestep on
+// dopf_create's limits until dopf_set_line_rating — and those L limits behind it (what the central reference reads: it takes no ratings)
+inline size_t fmax_doubles(int L, int T, bool rating) { return rating ? (size_t)L * T + (size_t)L : (size_t)L; }
 __host__ __device__ inline const double *line_fmax0(const DevView &v) { return v.fmax + (size_t)v.fmax_ld * v.T; }
 
-// DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
+// The gen_mc block (v.gen_mc): the marginal costs, and with DOPF_F_GEN_QUADRATIC_COST the quadratic coefficients c2[g] behind them,
+// sorted order, zeros until dopf_set_generator_quadratic_cost. The cost of row g at output P is gen_mc[g] P + c2[g] P^2 / 2.
+inline size_t gen_mc_doubles(int G, bool quad) { return quad ? 2 * (size_t)G : (size_t)G; }
+__host__ __device__ inline const double *gen_c2(const DevView &v) { return v.gen_mc + v.G; }
+
+// The gen_state block (v.gen_state; gen_state_ints). DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
 // gen_pmax[g] for k = -1. gen_state has room for both behind its G row states: the G profile indices (sorted order, -1 until
 // dopf_set_generator_availability), then, on the next 8-byte boundary, the device address of the profile table f (grown by the
 // setter). The view, every kernel's argument, keeps its layout: a longer DevView moved the register allocation of the fused
@@ -194,10 +205,6 @@ __host__ __device__ inline const double **gen_avail_slot(const DevView &v)
     return reinterpret_cast<const double **>(v.gen_state + ((2 * (size_t)v.G + 1) & ~(size_t)1));
 }
 inline size_t gen_state_ints(int G, bool avail) { return avail ? ((2 * (size_t)G + 1) & ~(size_t)1) + 2 : (size_t)G; }
-
-// DOPF_F_GEN_QUADRATIC_COST contexts only (gen_mc then has 2G entries): the generators' quadratic cost coefficients c2[g] behind the
-// marginal costs, sorted order, zeros until dopf_set_generator_quadratic_cost. The cost of row g at output P is gen_mc[g] P + c2[g] P^2 / 2.
-__host__ __device__ inline const double *gen_c2(const DevView &v) { return v.gen_mc + v.G; }
 
 // DOPF_F_GEN_AVAILABILITY (the AV instantiations of the generator bodies, kernels_agents.hip and kernels_central.hip): the row's upper bound at a timestep, cap = pmax * f with f
 // the row's profile value — one fp64 multiply, never contracted into the sums that add it (a kept row adds cap itself, and the full
@@ -213,18 +220,6 @@ __device__ __forceinline__ double avail_cap(const double *f, int T, int prof, do
 {
     return prof >= 0 ? avail_mul(pm, f[(size_t)prof * T + t]) : pm;
 }
-
-#ifndef DOPF_ACC_REP
-#define DOPF_ACC_REP 16
-#endif
-constexpr int kAccRep = DOPF_ACC_REP;     // replicas of the accumulators (a block adds into replica blockIdx % kAccRep: 1/16 of the adds per address)
-
-// consensus states up to this many (n,t) / (l,t) entries take the one-block dual step
-constexpr size_t kSmallConsensus = 4096;
-#ifndef DOPF_STREAM_ROWS
-#define DOPF_STREAM_ROWS 6
-#endif
-constexpr int kGenStreamRows = DOPF_STREAM_ROWS;          // rows per lane and item in the streaming generator blocks (one batch of loads)
 
 // check_convergence!, convergence.jl:1-31 (one thread). The status words a stop test starts from are loaded early by
 // callers that can (a load at the very end of a one-block kernel is a round trip on its critical path).
@@ -256,43 +251,6 @@ __device__ __forceinline__ void status_update(const DevView &v, double r0, doubl
 {
     status_update(v, status_load(v), r0, r1, r2);
 }
-
-// The consensus step (dual update, prices, stop test): k_dual_price_small (state <= kSmallConsensus entries), k_dual_price_t1024
-// (networks, N and L <= 256), k_dual_t + k_price_t (a timestep's vectors in 48 KB of LDS), k_dual + k_price, the wide chain (net_wide.h)
-enum class Consensus : int { Small, T1024, DualT, Generic, Wide };
-
-// The launch chain of a context: every create-time choice of which kernels run, made once by plan_chain
-// (dopf_api.hip). Kernels read the parts they need from DevView; the rest is read by the host's launch functions only.
-struct Plan {
-    const char *refusal;            // non-null: no kernel instantiation serves this problem (DOPF_E_UNSUPPORTED)
-    int stoLPS, stoNCH;             // storage lane group: lanes per storage x timesteps per lane (sto_config_supported)
-    int stoLong;                    // the long-horizon storage body (sto_long.h: DOPF_F_LONG_HORIZON beyond T = 512, DOPF_F_DEBUG_LONG_STO)
-    int wideNet;                    // the wide chain (net_wide.h: DOPF_F_WIDE_NETWORK beyond L = 2048, DOPF_F_DEBUG_WIDE_NET): no one-launch,
-                                    // quiet or tail chain
-    Consensus consensus;
-    bool sliceDual;                 // the one-block dual kernel may add k_reduce's slices itself (DevView::sliceDual)
-    bool useWarm, stoLean;          // storage warm start (DevView::use_warm); the lean active-set body (sto_lean.h)
-    bool genAvail;                  // DOPF_F_GEN_AVAILABILITY: the generator bodies that read the rows' profiles (nothing else of the plan changes)
-    bool genQuad;                   // DOPF_F_GEN_QUADRATIC_COST: the generators run in k_gen_update<.., .., QC> on every shape — no pair, skip or fused
-                                    // generator blocks, no one-launch tail (the chain of DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T)
-    bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
-    int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
-                                    // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those
-                                    // and efficiencies (DOPF_F_STO_EFFICIENCY; defaults for what the other two flags do not set)
-    bool stoEff;                    // DOPF_F_STO_EFFICIENCY: levels are e0 + cumsum(be C - al D) (k_derive_level_eff, k_roll_level_eff)
-    bool fuseAgents, fuseNet;       // generators + storages in one launch: k_agents (copper plate, even T), k_net_agents (networks)
-    bool tail;                      // the tail of the iteration in the x-update launch (DevView::tailDev)
-    bool slackDual;                 // the one-launch dual/price kernel may form the slack sums: no k_reduce (DevView::slackInDual)
-    bool quiet, commQuiet;          // the quiet chain may run: single GPU (DevView::quiet), on a peer exchange (DevView::slackGlobal)
-    int genTT, genR, genTT2, genR2, genTT256, genSkip, genBlocks, tablesInDual;     // (DevView)
-    int genItem, stoItem;           // agents per generator / storage work item
-    int nGenItems, nStoItems, rowsT;
-};
-
-// (lanes per storage, timesteps per lane) of the one-wave storage bodies. A launch family is instantiated for a prefix of the list:
-// k_agents / k_net_agents for kFusedPairs, the storage launches for all.
-constexpr int kStoPairs[][2] = {{8, 1}, {8, 2}, {8, 3}, {16, 3}, {32, 3}, {64, 3}, {64, 6}, {64, 8}};
-constexpr int kFusedPairs = 6, kAllPairs = 8;
 
 // f(LPS, NCH) for the plan's lane group, as std::integral_constant arguments, over the first NP pairs of kStoPairs only: a launch
 // family is instantiated for exactly those. plan_chain refuses a lane group that the families it chose do not cover.
@@ -347,12 +305,16 @@ void central_launch_metrics(const CentralView &c, const Plan &p, const DevView &
 void central_launch_scale_copy(double *dst, const double *src, double scale, size_t n, hipStream_t s);
 void central_launch_scale_copy_primal(const CentralView &c, const Plan &p, double scale, hipStream_t s);   // P, D, C from their running sums, inside the boxes
 
+// Blocks of an x-update that add their sums to the one-launch tail: the storage items and the generator items — or, in the fused
+// launch's streaming form (genBlocks > 0 only there), its generator blocks. The fused launch's grid (+ the tail block) and
+// TailView::expect are this one count.
+inline int agent_blocks(const DevView &v) { return v.nStoItems + (v.genBlocks > 0 && !v.genSkip ? v.genBlocks : v.nGenItems); }
+
 // kernels_agents.hip
 void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s);
-bool sto_config_supported(int T, Plan *p);
 int debug_timeline(unsigned long long *out, int n);     // DOPF_STATS builds: per-wave stamps of the storage body
 // kernels_consensus.hip
 hipError_t raise_lds_limits(const DevView &v, const Plan &p);        // dopf_create, on the context's device: the dynamic LDS the plan's kernels need

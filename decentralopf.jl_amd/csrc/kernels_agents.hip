@@ -2575,18 +2575,6 @@ int debug_timeline(unsigned long long *out, int n)
 #endif
 }
 
-bool sto_config_supported(int T, Plan *p)
-{
-    // lane group x consecutive timesteps per lane; 3 timesteps per lane keeps the kernel at 2 waves/SIMD
-    if (T <= 24) { p->stoLPS = 8; p->stoNCH = (T + 7) / 8; return true; }
-    if (T <= 48) { p->stoLPS = 16; p->stoNCH = 3; return true; }
-    if (T <= 96) { p->stoLPS = 32; p->stoNCH = 3; return true; }
-    if (T <= 192) { p->stoLPS = 64; p->stoNCH = 3; return true; }
-    if (T <= 384) { p->stoLPS = 64; p->stoNCH = 6; return true; }
-    if (T <= 512) { p->stoLPS = 64; p->stoNCH = 8; return true; }
-    return false;
-}
-
 // (p.stoLV, DOPF_F_STO_INITIAL_LEVEL / DOPF_F_STO_TERMINAL_LEVEL: the general bodies' level-mode instantiations; plan_chain keeps such
 // contexts off the lean body)
 template <int LPS, int NCH>
@@ -2619,7 +2607,7 @@ static void launch_sto_t(const DevView &v, const Plan &p, hipStream_t s)
 template <int LPS, int NCH>
 static void launch_agents_t(const DevView &v, const Plan &p, hipStream_t s)
 {
-    const dim3 grid(v.nStoItems + (v.genBlocks > 0 && !v.genSkip ? v.genBlocks : v.nGenItems) + (v.tail ? 1 : 0));
+    const dim3 grid(agent_blocks(v) + (v.tail ? 1 : 0));
     // (p.genAvail, DOPF_F_GEN_AVAILABILITY: the generator blocks with the rows' caps, the same storage bodies)
     with_bool(v.genSkip, [&](auto skip) { with_bool(v.tail, [&](auto tail) { with_bool(v.T == LPS * NCH, [&](auto full) { with_bool(p.genAvail, [&](auto av) {
         constexpr bool SK = decltype(skip)::value, TL = decltype(tail)::value, FU = decltype(full)::value, AV = decltype(av)::value;

@@ -1673,7 +1673,7 @@ __global__ __launch_bounds__(256) void k_dual_price_small(DevView v, XchgView x)
         // the ones the two-level kernel produces
         const int RB = v.reduceRB, N = v.N, T = v.T, R = 8;
         const int r = tid >> 5, tt = tid & 31;            // 8 slice lanes x 32 entries, as in k_reduce
-        // N*T <= 256 here (Plan::sliceDual, plan_chain in dopf_api.hip): up to 8 chunks of 32 entries, every load of every chunk
+        // N*T <= 256 here (Plan::sliceDual, plan_chain): up to 8 chunks of 32 entries, every load of every chunk
         // issued before the first use, ONE barrier
         double sc[8];
 #pragma unroll
