@@ -86,6 +86,7 @@ F_GEN_AVAILABILITY = 134217728
 F_STO_EFFICIENCY = 268435456
 F_LINE_RATING = 536870912
 F_GEN_QUADRATIC_COST = 1073741824
+F_GEN_RAMP = 32
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -186,7 +187,7 @@ class CApi:
             self._sig("multi_ctx", ctxp, [ctxp, C.c_int32])
         # the problem extensions' setters (EXTENSIONS below). The older three belong to the HIP library's ABI; the later three are bound
         # wherever the library exports them — the oracle backend loads without them (Engine's setter then refuses)
-        for x in EXTENSIONS:
+        for x in EXTENSIONS + EXTENSIONS_MORE:
             if x.optional or prefix == "dopf_":
                 for name in (x.entry, "multi_" + x.entry):
                     (self._opt if x.optional else self._sig)(name, C.c_int, [ctxp] + list(x.argtypes))
@@ -307,6 +308,7 @@ class Extension(NamedTuple):
     is_default: Callable    # (d, keep, *arrays) -> True where they say what a problem without the extension says
     cargs: Callable = lambda d, *arrays: tuple(_dp(a) for a in arrays)      # (d, *arrays) -> the entry's arguments behind the context
     fill: Optional[Callable] = None     # (d, keep, *arrays) -> arrays: how the constructor completes a value given in part
+    mirror: Optional[Callable] = None   # (*arrays) -> {constructor keyword: value} where the keywords are not the arrays one to one
     optional: bool = False  # bound wherever the library exports it, under any prefix, and the setter's refusal ends in " (unsupported)";
     #                         False: part of the "dopf_" ABI, bound under that prefix alone
 
@@ -370,15 +372,35 @@ EXTENSIONS = (
               what="quadratic generator costs", why="a non-zero gen_c2; the reference keeps one constant marginal_costs per unit",
               norm=lambda d, c2: (None if c2 is None else _f64(c2, d.G),), is_default=lambda d, keep, c2: not np.any(c2 != 0.0)),
 )
-_BY_SETTER = {x.setter: x for x in EXTENSIONS}
+
+
+def _ramp_norm(d, ramp, prev):
+    up, down = (None, None) if ramp is None else ramp
+    if (up is None) != (down is None):
+        raise ValueError("gen_ramp: ramp_up and ramp_down must both be given or both be None")
+    return (None if up is None else _f64(up, d.G), None if down is None else _f64(down, d.G), None if prev is None else _f64(prev, d.G))
+
+
+# The later extensions. EXTENSIONS keeps its six rows (tests/test_extensions_table.py pins them); everything that walks the table
+# walks EXTENSIONS + EXTENSIONS_MORE. The ramps come behind the availability, whose caps their check reads.
+EXTENSIONS_MORE = (
+    Extension(keys=("gen_ramp", "gen_prev"), flag=F_GEN_RAMP, entry="set_generator_ramp", argtypes=(c_double_p, c_double_p, c_double_p),
+              setter="set_ramp", optional=True,
+              what="generator ramp limits", why="a finite ramp or an anchor; the reference's generators move freely between steps",
+              norm=_ramp_norm,
+              is_default=lambda d, keep, up, down, prev: prev is None and (up is None or not (np.any(np.isfinite(up)) or np.any(np.isfinite(down)))),
+              mirror=lambda up, down, prev: dict(gen_ramp=None if up is None else (up, down), gen_prev=prev)),
+)
+_ALL_EXTENSIONS = EXTENSIONS + EXTENSIONS_MORE
+_BY_SETTER = {x.setter: x for x in _ALL_EXTENSIONS}
 
 
 def _extensions(api: CApi, params: Optional[DopfParams], d, keep: dict, kw: dict):
     """(params, todo) for a context built with the extensions' constructor keywords in kw: the params with the flags of those given
-    added (a copy), and todo, the (extension, arrays) to apply behind create, in EXTENSIONS' order. Nothing to set: a keyword left
+    added (a copy), and todo, the (extension, arrays) to apply behind create, in the order of EXTENSIONS + EXTENSIONS_MORE. Nothing to set: a keyword left
     None, or its default value on an API without the entry (a non-default value there: DopfError)."""
     todo = []
-    for x in EXTENSIONS:
+    for x in _ALL_EXTENSIONS:
         given = [kw.get(k) for k in x.keys]
         if all(v is None for v in given):
             continue
@@ -415,6 +437,8 @@ class _ExtensionSetters:
         if all(a is None for a in arrays):
             return dict.fromkeys(x.keys)
         arrays = tuple(None if a is None else a.copy() for a in arrays)
+        if x.mirror:
+            return x.mirror(*arrays)
         return {x.keys[0]: arrays} if x.packed else dict(zip(x.keys, arrays))
 
     def _apply(self, todo) -> None:
@@ -432,19 +456,21 @@ class Engine(_ExtensionSetters):
     charge and discharge efficiencies — sets F_STO_EFFICIENCY and calls dopf_set_storage_efficiency (before the levels: their
     reachability checks then see the efficiencies). line_rating (optional, (L, T)): the lines' limits per timestep — sets
     F_LINE_RATING and calls dopf_set_line_rating. gen_c2 (optional, G values >= 0): the generators' quadratic cost coefficients —
-    sets F_GEN_QUADRATIC_COST and calls dopf_set_generator_quadratic_cost."""
+    sets F_GEN_QUADRATIC_COST and calls dopf_set_generator_quadratic_cost. gen_ramp = (up, down) (optional, G values >= 0 each, inf =
+    no limit) / gen_prev (optional, G outputs of the step before the window): the generators' ramp limits and their anchor — sets
+    F_GEN_RAMP and calls dopf_set_generator_ramp (after the availability: its check reads the caps)."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
                  mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
-                 sto_eta=None, line_rating=None, gen_c2=None):
+                 sto_eta=None, line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                                               sto_mc, sto_pmax, sto_emax, sto_node)
         params, todo = _extensions(api, params, self, keep, dict(
             sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
-            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2))
+            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev))
         self.params = params if params is not None else default_params()
         # what a window change needs of the problem: the arrays as handed to create, and the inputs of the setters as they stand
         # (by constructor keyword, in the form the constructor takes them)
@@ -570,6 +596,15 @@ class Engine(_ExtensionSetters):
         max_generation); both None resets every generator to -1. Needs F_GEN_AVAILABILITY. Takes effect at the next x-update."""
         self._mirror.update(self._set("set_availability", profiles, profile_of))
 
+    def set_ramp(self, up=None, down=None, prev=None):
+        """dopf_set_generator_ramp: each generator's ramp limits (G values >= 0 each, inf = no limit; both None = all inf) and
+        optionally the outputs of the step before the window (prev, G values in [0, gen_pmax]; None = no anchor):
+        -down <= P[g,t] - P[g,t-1] <= up, and at t = 0 against prev; needs F_GEN_RAMP. P, D, C, the duals and the iteration counter
+        stay; converged becomes False. Takes effect at the next x-update. A backend without the entry: DopfError (unsupported)."""
+        if (up is None) != (down is None):
+            raise ValueError("set_ramp: up and down must both be given or both be None")
+        self._mirror.update(self._set("set_ramp", None if up is None else (up, down), prev))
+
     # -- a receding horizon --------------------------------------------------------------------
     def demand(self) -> np.ndarray:
         """The context's demand as it stands, (N, T)."""
@@ -592,7 +627,8 @@ class Engine(_ExtensionSetters):
         window's with set_availability."""
         from .horizon import shift_window
         k = int(k)
-        native = hasattr(self.api, "roll_horizon")
+        # (a context with ramp limits goes the host route on every API: the next window's anchor is the old P[:, k - 1])
+        native = hasattr(self.api, "roll_horizon") and not self.params.flags & F_GEN_RAMP
         if not 1 <= k <= self.T - 1:
             if native:
                 self._chk(self.api.roll_horizon(self._ctx, k, None))       # (the library's refusal and message)
@@ -619,6 +655,8 @@ class Engine(_ExtensionSetters):
             kw["sto_e0"] = w["e0"]
         if "line_rating" in w:
             kw["line_rating"] = w["line_rating"]
+        if self.params.flags & F_GEN_RAMP:
+            kw["gen_prev"] = P[:, k - 1].copy()
         new = Engine(self.api, N=self.N, L=self.L, T=self.T, params=self.params, mode=self._mode, **kw)
         new.set_state(P=w["P"], D=w["D"], C_=w["C"], avg_U=w["avg_U"], avg_K=w["avg_K"], lam=w["lam"], mu=w["mu"], rho=w["rho"],
                       iteration=2)
@@ -780,14 +818,15 @@ class MultiEngine(_ExtensionSetters):
 
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
-                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None, gen_c2=None):
+                 sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None, gen_c2=None,
+                 gen_ramp=None, gen_prev=None):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                                               sto_mc, sto_pmax, sto_emax, sto_node)
         params, todo = _extensions(api, params, self, keep, dict(
             sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
-            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2))
+            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev))
         self.params = params if params is not None else default_params()
         dev = None if devices is None else _i32(devices, n_gpus)
         self._m = C.c_void_p()
@@ -807,6 +846,13 @@ class MultiEngine(_ExtensionSetters):
         """dopf_multi_set_generator_quadratic_cost: all G generators' quadratic cost coefficients in the caller's order (None = all
         0); each shard gets its slice."""
         self._set("set_quadratic_cost", c2)
+
+    def set_ramp(self, up=None, down=None, prev=None):
+        """dopf_multi_set_generator_ramp: all G generators' ramp limits and (optionally) anchors in the caller's order (both ramps
+        None = all inf, prev None = no anchor); each shard gets its slice."""
+        if (up is None) != (down is None):
+            raise ValueError("set_ramp: up and down must both be given or both be None")
+        self._set("set_ramp", None if up is None else (up, down), prev)
 
     def set_line_rating(self, rating=None):
         """dopf_multi_set_line_rating: the (L, T) table for every shard (None = f_max in every timestep)."""
@@ -872,7 +918,7 @@ class MultiEngine(_ExtensionSetters):
 def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                   sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                   sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
-                  line_rating=None, gen_c2=None) -> dict:
+                  line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None) -> dict:
     """dopf_central_solve: the central reference (src/opf_central_reference.jl) as one LP solved on the GPU by a first-order
     primal-dual method. Arguments as Engine (PackedProblem.engine_kwargs()). Returns objective, gap, iterations and the
     reference script's outputs in Julia shapes: P (G,T), D/C/E (S,T), system_price (T), nodal_price (N,T),
@@ -883,8 +929,12 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     sto_eta = (eta_c, eta_d) (S each, in (0, 1]): the storages' charge and discharge efficiencies, as Engine takes them; whenever it is
     given (all ones too) the call is dopf_central_solve_lossy, and E = sto_e0 + cumsum(eta_c C - D / eta_d).
     line_rating: the device LP takes no line ratings; a table other than f_max in every timestep raises DopfError.
-    gen_c2: the device LP takes no quadratic costs either; a non-zero coefficient raises DopfError."""
+    gen_c2: the device LP takes no quadratic costs either; a non-zero coefficient raises DopfError.
+    gen_ramp, gen_prev: nor ramp limits; a finite ramp or an anchor raises DopfError."""
     N, L, T = int(N), int(L), int(T)
+    if gen_prev is not None or (gen_ramp is not None and any(np.any(np.isfinite(np.asarray(r, dtype=np.float64))) for r in gen_ramp)):
+        raise DopfError("dopf_central_solve*: the device LP takes no generator ramp limits (it lets every generator move freely); use "
+                        "central.solve_central_packed(..., gen_ramp=) for a case with ramps")
     if gen_c2 is not None and np.any(np.asarray(gen_c2, dtype=np.float64) != 0.0):
         raise DopfError("dopf_central_solve*: the device LP takes no quadratic generator costs (it solves with gen_mc alone)")
     if line_rating is not None and np.any(np.asarray(line_rating, dtype=np.float64).reshape(L, T) != _f64(f_max, L)[:, None]):

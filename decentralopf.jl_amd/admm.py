@@ -183,6 +183,17 @@ class ADMM:
         self.engine.set_quadratic_cost(c2)
         self._replaced("gen_c2", c2, (self.packed.G,))
 
+    def set_ramp(self, up=None, down=None, prev=None) -> None:
+        """Each generator's ramp limits (G values >= 0 each in the order of `generators`, inf = no limit; both None = all inf) and
+        optionally the outputs of the step before the window (prev; None = no anchor): -down <= P[t] - P[t-1] <= up, at t = 0 against
+        prev. Not in the reference (its generators move freely, src/optimization/subproblems.jl:26-40); copper plates only. Needs
+        flags=F_GEN_RAMP (set for you when a Generator has a finite ramp_up or ramp_down); the state and the iteration counter stay,
+        the run is no longer converged; takes effect at the next iteration."""
+        self.engine.set_ramp(up, down, prev)
+        G = self.packed.G
+        self.packed.gen_ramp = None if up is None else tuple(np.asarray(r, dtype=np.float64).reshape(G).copy() for r in (up, down))
+        self.convergence = Convergence()
+
     def _replaced(self, field_: str, value, shape) -> None:
         """the packed problem follows an input that was replaced under a kept state, and the run is no longer converged"""
         setattr(self.packed, field_, None if value is None else np.asarray(value, dtype=np.float64).reshape(shape).copy())

@@ -56,7 +56,7 @@ def _efficiencies(pp: PackedProblem, efficiency):
 
 
 def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None,
-                         availability=None, efficiency=None, line_rating=None) -> CentralResult:
+                         availability=None, efficiency=None, line_rating=None, gen_ramp=None, gen_prev=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
     tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
     side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference). terminal_level:
@@ -65,7 +65,9 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
     gen_pmax[g] * profiles[profile_of[g], t] (gen_pmax for -1; None: the packed case's profiles, else gen_pmax as in the reference).
     efficiency: (eta_c, eta_d), (S,) each in (0, 1]: the storage-balance rows read E[t] - E[t-1] + D / eta_d - eta_c C = 0 (None:
     the packed case's efficiencies, else all 1 as in the reference). line_rating: (L, T), the right-hand sides of the two flow rows
-    become rating[l,t] (None: the packed case's table, else f_max in every timestep as in the reference)."""
+    become rating[l,t] (None: the packed case's table, else f_max in every timestep as in the reference). gen_ramp: (up, down), (G,)
+    each, inf = no limit: the rows -down[g] <= P[g,t] - P[g,t-1] <= up[g] for t >= 1 (None: the packed case's ramps, else none as in
+    the reference); gen_prev: (G,) outputs of the step before the window, the same rows at t = 0 against them (None: no such rows)."""
     from scipy import sparse
     from scipy.optimize import linprog
     if pp.has_quadratic_cost():
@@ -141,7 +143,28 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
         last = oE + np.arange(S) * T + (T - 1)
         lb[last] = np.asarray(terminal_level[0], dtype=np.float64).reshape(S)
         ub[last] = np.asarray(terminal_level[1], dtype=np.float64).reshape(S)
-    res = linprog(c, A_eq=Aeq, b_eq=np.concatenate(beq), bounds=np.stack([lb, ub], axis=1), method="highs")
+    Aub = bub = None
+    if gen_ramp is None and pp.has_ramp():
+        gen_ramp = pp.ramp()
+    if (gen_ramp is not None or gen_prev is not None) and G > 0:
+        up, down = (np.full(G, np.inf),) * 2 if gen_ramp is None else (np.asarray(r, dtype=np.float64).reshape(G) for r in gen_ramp)
+        ur, uc, uv, bub = [], [], [], []
+        def ramp_rows(sign, limit):          # sign (P[g,t] - P[g,t-1]) <= limit[g], the generators with a finite limit; t = 0: against gen_prev
+            nonlocal Aub
+            for g in np.flatnonzero(np.isfinite(limit)):
+                for t in range(0 if gen_prev is not None else 1, T):
+                    r = len(bub)
+                    ur.append(r); uc.append(g * T + t); uv.append(sign)
+                    if t > 0:
+                        ur.append(r); uc.append(g * T + t - 1); uv.append(-sign)
+                    bub.append(limit[g] + (sign * float(np.asarray(gen_prev, dtype=np.float64).reshape(G)[g]) if t == 0 else 0.0))
+        ramp_rows(1.0, up)
+        ramp_rows(-1.0, down)
+        if bub:
+            Aub = sparse.csr_matrix((uv, (ur, uc)), shape=(len(bub), nv))
+            bub = np.asarray(bub)
+    res = linprog(c, A_ub=Aub, b_ub=bub if Aub is not None else None, A_eq=Aeq, b_eq=np.concatenate(beq),
+                  bounds=np.stack([lb, ub], axis=1), method="highs")
     if res.status != 0:
         raise RuntimeError(f"central LP: {res.message}")
     x = res.x
@@ -197,6 +220,9 @@ def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Gene
     if pp.has_quadratic_cost():
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no quadratic generator "
                          "costs and would solve with the marginal costs alone")
+    if pp.has_ramp():
+        raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no generator ramp limits "
+                         "and would let every generator move freely; use central_reference for a case with Generator.ramp_up / ramp_down")
     if pp.line_rating is not None:
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no line ratings and would "
                          "solve with max_capacity in every timestep; use central_reference for a case with Line.rating")

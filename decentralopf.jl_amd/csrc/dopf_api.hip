@@ -101,6 +101,47 @@ int check_initial_levels(dopf_ctx *c, const double *e0)
     return DOPF_OK;
 }
 
+// DOPF_F_GEN_RAMP: an anchored generator must be able to come down under its caps — lo_0 = max(0, p_prev - ramp_down),
+// lo_t = max(0, lo_{t-1} - ramp_down) <= cap[g,t] for every t. g: the caller's index (the message's); f: the generator's profile, or null
+static int ramp_anchor_fits(dopf_ctx *c, const char *entry, int g, double pm, double down, double prev, const double *f)
+{
+    if (std::isnan(prev)) return DOPF_OK;
+    double lo = prev;
+    for (int t = 0; t < c->v.T; ++t) {
+        lo = std::max(0.0, lo - down);
+        const double cap = f ? pm * f[t] : pm;
+        if (lo > cap)
+            return fail(c, DOPF_E_INVALID, "%s: generator g = %d cannot come down from p_prev = %g under its cap %g at t = %d (ramp_down = %g "
+                                           "leaves it at %g or above)", entry, g, prev, cap, t, down, lo);
+        if (lo == 0.0) break;
+    }
+    return DOPF_OK;
+}
+
+// dopf_set_generator_ramp's checks: the flag, both ramp arrays or neither, no NaN, ramps >= 0, p_prev in [0, gen_pmax], and every
+// anchored generator able to stay under its caps (the stored availability table)
+int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev)
+{
+    if (int rc = NEEDS_FLAG(c, "generator ramp limits need", DOPF_F_GEN_RAMP)) return rc;
+    if (!up != !down) return fail(c, DOPF_E_INVALID, "dopf_set_generator_ramp: ramp_up and ramp_down must both be given or both be NULL");
+    const int G = c->v.G, T = c->v.T;
+    for (int i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        const double pm = c->gen_ramp_h[i];
+        if (up) {
+            if (std::isnan(up[a]) || up[a] < 0.0) return fail(c, DOPF_E_INVALID, "dopf_set_generator_ramp: ramp_up[%d] is %g (>= 0 wanted)", a, up[a]);
+            if (std::isnan(down[a]) || down[a] < 0.0) return fail(c, DOPF_E_INVALID, "dopf_set_generator_ramp: ramp_down[%d] is %g (>= 0 wanted)", a, down[a]);
+        }
+        if (!prev) continue;
+        if (!(prev[a] >= 0.0 && prev[a] <= pm))
+            return fail(c, DOPF_E_INVALID, "dopf_set_generator_ramp: p_prev[%d] is %g, outside [0, gen_pmax = %g]", a, prev[a], pm);
+        const int k = c->gen_prof_h.empty() ? -1 : c->gen_prof_h[i];
+        if (int rc = ramp_anchor_fits(c, "dopf_set_generator_ramp", a, pm, down ? down[a] : INFINITY, prev[a],
+                                      k >= 0 ? c->gen_avail_h.data() + (size_t)k * T : nullptr)) return rc;
+    }
+    return DOPF_OK;
+}
+
 // dopf_set_generator_availability's checks: the flag, a table of K >= 0 profiles with every value in [0, 1] (no NaN), and every index in [-1, K)
 int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of)
 {
@@ -120,6 +161,12 @@ int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles,
         for (int g = 0; g < G; ++g)
             if (profile_of[g] < -1 || profile_of[g] >= K)
                 return fail(c, DOPF_E_INVALID, "profile_of[%d] = %d outside [-1, %d)", g, profile_of[g], K);
+    if (c->q.flags & DOPF_F_GEN_RAMP)      // the anchors of dopf_set_generator_ramp, under the new table
+        for (int i = 0; i < G; ++i) {
+            const int a = c->gen_perm[i], k = profile_of ? profile_of[a] : -1;
+            if (int rc = ramp_anchor_fits(c, "dopf_set_generator_availability", a, c->gen_ramp_h[i], c->gen_ramp_h[2 * (size_t)G + i],
+                                          c->gen_ramp_h[3 * (size_t)G + i], k >= 0 ? profiles + (size_t)k * T : nullptr)) return rc;
+        }
     return DOPF_OK;
 }
 
@@ -641,7 +688,26 @@ int upload_agents(dopf_ctx *c, const Sorted &so)
     std::vector<double> mc(so.gmc);
     mc.resize(gen_mc_doubles(v.G, c->plan.genQuad), 0.0);
     d.upload(&v.gen_mc, mc);
-    d.upload(&v.gen_pmax, so.gpm);
+    if (c->plan.genRamp) {
+        // DOPF_F_GEN_RAMP: the ramps (+inf), the anchor (NaN: none) and k_gen_ramp's scratch behind the capacities; the scratch is
+        // sized from the knots' bound and is never read before it is written
+        const size_t n = gen_pmax_doubles(v.G, v.T, v.nGenItems, true);
+        size_t freeb = 0, totalb = 0;
+        HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
+        if (n * sizeof(double) > freeb)
+            return fail(c, DOPF_E_NOMEM, "ramp limits: the knots of the generators' projection (2T + 2 per row in flight) need %llu bytes, the "
+                                         "device has %llu free", (unsigned long long)(n * sizeof(double)), (unsigned long long)freeb);
+        c->gen_ramp_h.assign(so.gpm.begin(), so.gpm.end());
+        c->gen_ramp_h.resize(3 * G, INFINITY);
+        c->gen_ramp_h.resize(4 * G, std::nan(""));
+        double *blk = nullptr;
+        d.raw(&blk, n);
+        if (d.rc) return d.rc;
+        HIPCHK(c, hipMemcpy(blk, c->gen_ramp_h.data(), 4 * G * sizeof(double), hipMemcpyHostToDevice));
+        v.gen_pmax = blk;
+    } else {
+        d.upload(&v.gen_pmax, so.gpm);
+    }
     std::vector<double> mp(2 * G);
     for (size_t i = 0; i < G; ++i) { mp[2 * i] = so.gmc[i]; mp[2 * i + 1] = so.gpm[i]; }
     const double *mpd = nullptr;
@@ -1438,6 +1504,7 @@ int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const doubl
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->gen_prof_h = pr;
+    if (c->q.flags & DOPF_F_GEN_RAMP) c->gen_avail_h.assign(profiles, profiles + need);      // (what dopf_set_generator_ramp checks its anchors against)
     return DOPF_OK;
 }
 
@@ -1480,6 +1547,29 @@ int dopf_set_generator_quadratic_cost(dopf_ctx *c, const double *c2)
     launch_reset_status(c->v, c->main);
     HIPCHK(c, hipGetLastError());
     return read_status(c);          // (synchronises: h may go)
+}
+
+int dopf_set_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_generator_ramp(c, up, down, prev)) return rc;
+    const size_t G = (size_t)c->v.G;
+    if (G == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<double> h(3 * G, INFINITY);
+    for (size_t i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        if (up) { h[i] = up[a] + 0.0; h[G + i] = down[a] + 0.0; }
+        h[2 * G + i] = prev ? prev[a] + 0.0 : std::nan("");
+    }
+    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again). The
+    // state stays; the stop test starts over, as after dopf_set_generator_quadratic_cost
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(gen_ramp_up(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    launch_reset_status(c->v, c->main);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = read_status(c)) return rc;          // (synchronises: h may go)
+    std::copy(h.begin(), h.end(), c->gen_ramp_h.begin() + G);
+    return DOPF_OK;
 }
 
 // scratch of dopf_set_demand / dopf_roll_horizon, allocated at the first call (freed with the context's other arrays): the moved
@@ -1531,6 +1621,9 @@ int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
     DevView &v = c->v;
     const int N = v.N, L = v.L, T = v.T, S = v.S;
     if (c->comm) return roll_checks(c, "dopf_roll_horizon", "demand_tail", demand_tail, 0, N, 0);
+    if (c->q.flags & DOPF_F_GEN_RAMP)
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: not on a context with DOPF_F_GEN_RAMP (the anchor p_prev of the next window is "
+                                           "the host's to set: build that window's context)");
     if (k < 1 || k >= T) return fail(c, DOPF_E_INVALID, "dopf_roll_horizon: k = %d outside [1, T - 1 = %d]", k, T - 1);
     if (int rc = roll_checks(c, "dopf_roll_horizon", "demand_tail", demand_tail, (size_t)N * k, N, T - k)) return rc;
     if (S > 0 && !(c->q.flags & DOPF_F_STO_INITIAL_LEVEL))

@@ -745,6 +745,12 @@ int dopf_multi_set_generator_quadratic_cost(dopf_multi *m, const double *c2)
                      [&](auto f, int i) { return f(m->ctx[i], from(c2, m->g0[i])); });
 }
 
+int dopf_multi_set_generator_ramp(dopf_multi *m, const double *ramp_up, const double *ramp_down, const double *p_prev)
+{
+    return multi_set(m, check_generator_ramp, dopf_set_generator_ramp,
+                     [&](auto f, int i) { return f(m->ctx[i], from(ramp_up, m->g0[i]), from(ramp_down, m->g0[i]), from(p_prev, m->g0[i])); });
+}
+
 int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E)
 {
     if (!m) return DOPF_E_INVALID;

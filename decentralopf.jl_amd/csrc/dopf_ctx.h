@@ -38,6 +38,8 @@ struct dopf_ctx {
     std::vector<int> gen_prof_h;           // DOPF_F_GEN_AVAILABILITY: the generators' profile indices on the device (sorted order)
     double *gen_avail = nullptr;           // ... the profile table on the device (its address is in gen_avail_slot(v)) and the
     int gen_avail_cap = 0;                 //     profiles it has room for
+    std::vector<double> gen_ramp_h;        // DOPF_F_GEN_RAMP: gen_pmax | ramp_up | ramp_down | p_prev (NaN: none) as on the device (sorted order), and
+    std::vector<double> gen_avail_h;       //     with DOPF_F_GEN_AVAILABILITY the profile table: what the two setters check the anchors against
     dopf::Status host_st{};
     dopf::Status *host_pin = nullptr;       // page-locked landing area of the status read-back (a pageable target is staged: slower)
     unsigned long long solver_fail_seen = 0;   // failures already reported through DOPF_E_SOLVER
@@ -61,6 +63,8 @@ int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta
 int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of);   // dopf_set_generator_availability's
 int check_line_rating(dopf_ctx *c, const double *rating);   // those of dopf_set_line_rating (flag, finite, >= 0)
 int check_generator_quadratic_cost(dopf_ctx *c, const double *c2);   // those of dopf_set_generator_quadratic_cost (flag, finite, >= 0)
+// those of dopf_set_generator_ramp (flag, no NaN, ramps >= 0 and both or neither, p_prev in [0, gen_pmax], the anchors under the caps)
+int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev);
 void launch_demote_full_rows(const DevView &v, hipStream_t s);   // gen_state 1 -> 2 (the caps changed)
 // dopf_comm.hip
 int check_one_runtime(dopf_ctx *c);           // DOPF_E_UNSUPPORTED when two HIP runtimes are mapped into the process

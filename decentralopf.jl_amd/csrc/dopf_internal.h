@@ -112,6 +112,7 @@ struct DevView {
     const double *demand, *ptdf, *fmax;             // fmax: [l + fmax_ld*t] (DOPF_F_LINE_RATING: the L x T rating table, then dopf_create's L limits)
     const double *ptdfT;                            // [n + N*l]: the transpose, for the price kernel's node-major threads
     const double *gen_mc, *gen_pmax;                // DOPF_F_GEN_QUADRATIC_COST: gen_mc has 2G entries, the quadratic coefficients behind the costs (gen_c2(v))
+                                                    // DOPF_F_GEN_RAMP: the ramps, the anchor and k_gen_ramp's scratch behind gen_pmax (gen_ramp_up(v) ..)
     const double2 *gen_mp;                          // [g] {mc, pmax} side by side: one 16-byte load per row (streaming blocks)
     const double *sto_mc, *sto_pmax, *sto_emax;     // DOPF_F_STO_INITIAL_LEVEL: sto_emax has 2S entries, the initial levels behind the max levels
                                                     // (sto_e0(v) below): the view, every kernel's argument, keeps its layout;
@@ -193,6 +194,19 @@ __host__ __device__ inline const double *line_fmax0(const DevView &v) { return v
 // sorted order, zeros until dopf_set_generator_quadratic_cost. The cost of row g at output P is gen_mc[g] P + c2[g] P^2 / 2.
 inline size_t gen_mc_doubles(int G, bool quad) { return quad ? 2 * (size_t)G : (size_t)G; }
 __host__ __device__ inline const double *gen_c2(const DevView &v) { return v.gen_mc + v.G; }
+
+// The gen_pmax block (v.gen_pmax): the generators' capacities, and with DOPF_F_GEN_RAMP behind them, G doubles each in sorted order,
+// ramp_up | ramp_down (+inf until dopf_set_generator_ramp) | p_prev (NaN: no anchor), then k_gen_ramp's scratch for the horizons
+// whose knots do not fit in LDS (T > kRampLdsT): per wave of the launch (kRampWaves per generator item) kRampRowDoubles(T) doubles —
+// T values c_t / y*_t, then the knots' x and v, 2T + 2 each (the bound of DESIGN.md 5r)
+constexpr int kRampLdsT = 128, kRampWaves = 8;
+__host__ __device__ inline size_t ramp_row_doubles(int T) { return 5 * (size_t)T + 4; }
+inline size_t ramp_scratch_doubles(int T, int nGenItems) { return T > kRampLdsT ? (size_t)nGenItems * kRampWaves * ramp_row_doubles(T) : 0; }
+inline size_t gen_pmax_doubles(int G, int T, int nGenItems, bool ramp) { return ramp ? 4 * (size_t)G + ramp_scratch_doubles(T, nGenItems) : (size_t)G; }
+__host__ __device__ inline const double *gen_ramp_up(const DevView &v) { return v.gen_pmax + v.G; }
+__host__ __device__ inline const double *gen_ramp_down(const DevView &v) { return v.gen_pmax + 2 * (size_t)v.G; }
+__host__ __device__ inline const double *gen_ramp_prev(const DevView &v) { return v.gen_pmax + 3 * (size_t)v.G; }
+__host__ __device__ inline double *gen_ramp_scratch(const DevView &v) { return const_cast<double *>(v.gen_pmax) + 4 * (size_t)v.G; }
 
 // The gen_state block (v.gen_state; gen_state_ints). DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
 // gen_pmax[g] for k = -1. gen_state has room for both behind its G row states: the G profile indices (sorted order, -1 until
@@ -312,6 +326,7 @@ inline int agent_blocks(const DevView &v) { return v.nStoItems + (v.genBlocks > 
 
 // kernels_agents.hip
 void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s);
+void launch_gen_ramp(const DevView &v, const Plan &p, hipStream_t s);       // gen_ramp.h: the generators of a DOPF_F_GEN_RAMP context
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s);
@@ -354,7 +369,7 @@ void launch_roll_state(const DevView &v, const Plan &p, int k, int iteration, hi
 // dopf_set_line_rating: status as dopf_set_demand leaves it, then the consensus step's derived state under the new limits — the
 // per-(l,t) flags, walk_any / tab_skip and the tables the price kernels write — from the sums in cons (no sums are formed or moved)
 void launch_line_rating(const DevView &v, const Plan &p, hipStream_t s);
-// dopf_set_generator_quadratic_cost: status as dopf_set_line_rating leaves it (nothing derived depends on the costs)
+// dopf_set_generator_quadratic_cost, dopf_set_generator_ramp: status as dopf_set_line_rating leaves it (nothing derived depends on the costs or the ramps)
 void launch_reset_status(const DevView &v, hipStream_t s);
 void launch_penalty_sums(const DevView &v, double *out /* [3][N][T], device */, hipStream_t s);   // Result.penalty_term, per node
 void launch_node_results(const DevView &v, double *gen, double *dis, double *chg, hipStream_t s);   // [n + N*t] each, device pointers   // consensus -> inj/s/flow/price (no dual step)

@@ -57,6 +57,8 @@ struct Plan {
     bool genAvail;                  // DOPF_F_GEN_AVAILABILITY: the generator bodies that read the rows' profiles (nothing else of the plan changes)
     bool genQuad;                   // DOPF_F_GEN_QUADRATIC_COST: the generators run in k_gen_update<.., .., QC> on every shape — no pair, skip or fused
                                     // generator blocks, no one-launch tail (the chain of DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T)
+    bool genRamp;                   // DOPF_F_GEN_RAMP (copper plates): the generators run in k_gen_ramp<AV, QC> — the chain of genQuad (no pair, skip or
+                                    // fused generator blocks, no one-launch tail), with the exact projection onto {box, ramps} for the rows that need it
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those
@@ -199,8 +201,12 @@ inline Plan plan_chain(const Shape &sh, unsigned flags, int cus)
     // or skip kernels (genTT2 = 0, and with it no one-launch tail: `pairs` below), no k_agents, no k_net_agents. The chain the
     // same problem runs under DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T; the storages' launch of that chain, with the LV above
     p.genQuad = G > 0 && (flags & DOPF_F_GEN_QUADRATIC_COST);
-    if (p.genQuad) flags |= DOPF_F_NO_FUSE;
-    p.genTT2 = (!p.genQuad && L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
+    // DOPF_F_GEN_RAMP: the same chain with k_gen_ramp as the generators' launch (copper plates only: on a network the row's derivative
+    // gains up to 2L kinks per step, another kernel)
+    p.genRamp = G > 0 && (flags & DOPF_F_GEN_RAMP);
+    if ((flags & DOPF_F_GEN_RAMP) && L > 0) p.refusal = "ramp limits run on copper plates; networks are not built yet";
+    if (p.genQuad || p.genRamp) flags |= DOPF_F_NO_FUSE;
+    p.genTT2 = (!p.genQuad && !p.genRamp && L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
     p.fuseAgents = p.genTT2 > 0 && p.genTT2 <= 256 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS));
     if (p.fuseAgents) {
         // one launch for all agents pays while its fixed cost matters and every storage block is resident from
@@ -301,7 +307,7 @@ inline Plan plan_chain(const Shape &sh, unsigned flags, int cus)
         int at = 0;
         while (at < kAllPairs && !(kStoPairs[at][0] == p.stoLPS && kStoPairs[at][1] == p.stoNCH)) ++at;
         if (at >= ((p.fuseAgents || p.fuseNet) ? kFusedPairs : kAllPairs))
-            p.refusal = "no storage kernel is instantiated for this horizon and chain";
+            if (!p.refusal) p.refusal = "no storage kernel is instantiated for this horizon and chain";
     }
     return p;
 }

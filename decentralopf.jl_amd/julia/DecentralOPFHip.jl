@@ -132,6 +132,7 @@ const DOPF_F_GEN_AVAILABILITY = 134217728  # include/dopf.h
 const DOPF_F_STO_EFFICIENCY = 268435456  # include/dopf.h
 const DOPF_F_LINE_RATING = 536870912  # include/dopf.h
 const DOPF_F_GEN_QUADRATIC_COST = 1073741824  # include/dopf.h
+const DOPF_F_GEN_RAMP = 32  # include/dopf.h
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -151,7 +152,8 @@ last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_T
 availability profile (see `set_availability!`) need `flags = DOPF_F_GEN_AVAILABILITY`; storages with charge / discharge
 efficiencies below 1 (see `set_efficiency!`; the reference's `Storage` type, used verbatim, has no such fields) need
 `flags = DOPF_F_STO_EFFICIENCY`, line limits per timestep (see `set_line_rating!`) `flags = DOPF_F_LINE_RATING`, and quadratic
-generator cost curves (see `set_quadratic_cost!`) `flags = DOPF_F_GEN_QUADRATIC_COST`. Flags combine with `|`.
+generator cost curves (see `set_quadratic_cost!`) `flags = DOPF_F_GEN_QUADRATIC_COST`; generator ramp limits on a copper plate (see
+`set_ramp!`) `flags = DOPF_F_GEN_RAMP`. Flags combine with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
@@ -320,6 +322,37 @@ function set_quadratic_cost!(admm::ADMM, c2::Union{Nothing, Vector{Float64}})
                              admm.multi)
         else
             dopf_check(ccall((:dopf_set_generator_quadratic_cost, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, p), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    set_ramp!(admm, ramp_up, ramp_down, p_prev=nothing)
+
+The ramp limits of each generator (`ramp_up[g], ramp_down[g] >= 0`, `Inf` = no limit, in the order of `generators`; both `nothing` =
+all `Inf`) and optionally the outputs of the step before the window (`p_prev`, in `[0, max_generation]`; `nothing` = no anchor):
+`-ramp_down <= P[g,t] - P[g,t-1] <= ramp_up`, at `t = 1` against `p_prev`. The reference's generators move freely between steps
+(src/optimization/subproblems.jl:26-40); the ADMM must have been created with `flags = DOPF_F_GEN_RAMP`, on a case without lines.
+The state and the iteration counter stay; takes effect at the next iteration.
+"""
+function set_ramp!(admm::ADMM, ramp_up::Union{Nothing, Vector{Float64}}, ramp_down::Union{Nothing, Vector{Float64}},
+                   p_prev::Union{Nothing, Vector{Float64}}=nothing)
+    G = length(admm.generators)
+    for a in (ramp_up, ramp_down, p_prev)
+        a === nothing || length(a) == G || error("set_ramp!: expected $G values, got $(length(a))")
+    end
+    (ramp_up === nothing) == (ramp_down === nothing) || error("set_ramp!: ramp_up and ramp_down must both be given or both be nothing")
+    pu = ramp_up === nothing ? Ptr{Cdouble}(C_NULL) : pointer(ramp_up)
+    pd = ramp_down === nothing ? Ptr{Cdouble}(C_NULL) : pointer(ramp_down)
+    pp = p_prev === nothing ? Ptr{Cdouble}(C_NULL) : pointer(p_prev)
+    GC.@preserve ramp_up ramp_down p_prev begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_generator_ramp, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                                   admm.multi, pu, pd, pp), admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_generator_ramp, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                             admm.ctx, pu, pd, pp), admm.ctx)
         end
     end
     return admm

@@ -19,6 +19,8 @@ Line.rating is not in the reference either (one max_capacity per line for the wh
 T limits >= 0, |flow[t]| <= rating[t] — a planned derating, a dynamic rating or a security margin per timestep (DOPF_F_LINE_RATING).
 Generator.quadratic_costs is not in the reference either (one constant marginal_costs per unit, src/optimization/subproblems.jl:26-40):
 c2 >= 0, the cost of output P is marginal_costs * P + c2 * P^2 / 2 — a polynomial cost curve (DOPF_F_GEN_QUADRATIC_COST).
+Generator.ramp_up / ramp_down are not in the reference either (its generators move freely between steps, src/optimization/subproblems.jl:26-40):
+-ramp_down <= P[t] - P[t-1] <= ramp_up, the limit on how fast a unit's output changes; copper plates only (DOPF_F_GEN_RAMP).
 """
 from __future__ import annotations
 
@@ -44,6 +46,8 @@ class Generator:
     node: Node
     availability: Optional[Sequence[float]] = None      # T per-unit values in [0, 1]; None = always max_generation (not in the reference)
     quadratic_costs: float = 0.0                        # c2 >= 0: the cost is marginal_costs * P + c2 * P^2 / 2 (not in the reference)
+    ramp_up: float = float("inf")                       # >= 0: P[t] - P[t-1] <= ramp_up; inf = no limit (not in the reference)
+    ramp_down: float = float("inf")                     # >= 0: P[t-1] - P[t] <= ramp_down; inf = no limit (not in the reference)
 
 
 @dataclass(eq=False)
@@ -137,6 +141,7 @@ class PackedProblem:
     sto_eta_d: Optional[np.ndarray] = None      # (S,) Storage.discharge_efficiency; None = all 1
     line_rating: Optional[np.ndarray] = None    # (L, T) Line.rating (max_capacity where a line has none); None = no line has one
     gen_c2: Optional[np.ndarray] = None         # (G,) Generator.quadratic_costs; None = all 0
+    gen_ramp: Optional[tuple] = None            # ((G,), (G,)) Generator.ramp_up, ramp_down; None = all inf
 
     @property
     def G(self):
@@ -167,7 +172,19 @@ class PackedProblem:
             kw["line_rating"] = np.asarray(self.line_rating, dtype=np.float64).reshape(self.L, self.T)
         if self.has_quadratic_cost():      # (engines then run with F_GEN_QUADRATIC_COST)
             kw["gen_c2"] = self.quadratic_cost()
+        if self.has_ramp():      # (engines then run with F_GEN_RAMP)
+            kw["gen_ramp"] = self.ramp()
         return kw
+
+    def ramp(self):
+        """(ramp_up, ramp_down), float64 (G,) each, the default filled in: all inf."""
+        if self.gen_ramp is None:
+            return np.full(self.G, np.inf), np.full(self.G, np.inf)
+        return tuple(np.asarray(r, dtype=np.float64) for r in self.gen_ramp)
+
+    def has_ramp(self) -> bool:
+        """Some generator has a finite ramp limit (a shard: some generator of the whole problem, so that every rank runs with the flag)."""
+        return bool(self.meta.get("ramp")) or (self.gen_ramp is not None and any(bool(np.any(np.isfinite(r))) for r in self.ramp()))
 
     def quadratic_cost(self):
         """c2, float64 (G,), the default filled in: all 0."""
@@ -224,7 +241,7 @@ class PackedProblem:
             sto_mc=self.sto_mc[s0:s1], sto_pmax=self.sto_pmax[s0:s1], sto_emax=self.sto_emax[s0:s1],
             sto_node=self.sto_node[s0:s1],
             meta=dict(self.meta, rank=rank, world=world, gen_range=(g0, g1), sto_range=(s0, s1),
-                      n_agents_global=self.G + self.S, quadratic_cost=self.has_quadratic_cost()),
+                      n_agents_global=self.G + self.S, quadratic_cost=self.has_quadratic_cost(), ramp=self.has_ramp()),
             sto_e0=None if self.sto_e0 is None else self.sto_e0[s0:s1],
             sto_end_lo=None if self.sto_end_lo is None else self.sto_end_lo[s0:s1],
             sto_end_hi=None if self.sto_end_hi is None else self.sto_end_hi[s0:s1],
@@ -233,7 +250,8 @@ class PackedProblem:
             sto_eta_c=None if self.sto_eta_c is None else self.sto_eta_c[s0:s1],
             sto_eta_d=None if self.sto_eta_d is None else self.sto_eta_d[s0:s1],
             line_rating=self.line_rating,
-            gen_c2=None if self.gen_c2 is None else self.gen_c2[g0:g1])
+            gen_c2=None if self.gen_c2 is None else self.gen_c2[g0:g1],
+            gen_ramp=None if self.gen_ramp is None else tuple(np.asarray(r)[g0:g1] for r in self.gen_ramp))
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -266,6 +284,9 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
     c2 = f64(g.quadratic_costs for g in generators)
     if not np.all(np.isfinite(c2)) or np.any(c2 < 0.0):
         raise ValueError("generator quadratic_costs must be finite and >= 0")
+    ramp = (f64(g.ramp_up for g in generators), f64(g.ramp_down for g in generators))
+    if any(np.any(np.isnan(r)) or np.any(r < 0.0) for r in ramp):
+        raise ValueError("generator ramp_up / ramp_down must be >= 0 (inf: no limit)")
     # line ratings: a table only when some line has one (the others keep max_capacity in every timestep)
     rating = None
     if any(l.rating is not None for l in lines):
@@ -297,4 +318,5 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         sto_eta_c=f64(s.charge_efficiency for s in storages),
         sto_eta_d=f64(s.discharge_efficiency for s in storages),
         line_rating=rating,
-        gen_c2=c2)
+        gen_c2=c2,
+        gen_ramp=ramp)

@@ -129,6 +129,12 @@ class ShardedADMM:
         params; every rank calls it between the same two steps."""
         self.engine.set_quadratic_cost(self._mine(c2, "gen"))
 
+    def set_ramp(self, up=None, down=None, prev=None) -> None:
+        """All generators' ramp limits and (optionally) anchors (problem.G values each, global order; both ramps None = all inf,
+        prev None = no anchor): this rank sets its slice (dopf_set_generator_ramp; the constraint is local to the rank's agents, no
+        sums move). Needs F_GEN_RAMP in the params; every rank calls it between the same two steps."""
+        self.engine.set_ramp(self._mine(up, "gen"), self._mine(down, "gen"), self._mine(prev, "gen"))
+
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
         max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs

@@ -195,6 +195,21 @@ typedef struct dopf_params {
                                   * context on that chain, bit for bit. dopf_get_consensus' total_cost, and everything fed from it, is
                                   * sum gen_mc P + c2 P^2 / 2 (+ the storages' costs). dopf_central_solve, _ex and _lossy solve the LP: they
                                   * ignore the flag and the coefficients. */
+#define DOPF_F_GEN_RAMP 32 /* generators have ramp limits (copper plates, L == 0): the context keeps ramp_up[g], ramp_down[g] >= 0 per
+                                  * generator (+inf, no limit, until dopf_set_generator_ramp) and optionally the output p_prev[g] of the step
+                                  * before the window. The generator's step keeps its objective and its box and gains
+                                  * -ramp_down <= P[g,t] - P[g,t-1] <= ramp_up for t = 1 .. T-1, and for t = 0 against p_prev where one is
+                                  * given: the only constraint that couples a generator's timesteps. The step is the exact Euclidean
+                                  * projection of the unconstrained step's centre onto {box, ramps}, by a forward dynamic programme over the
+                                  * derivative of the cost-to-go and a backward pass (k_gen_ramp): O(T x knots) for a row whose
+                                  * clamped step breaks a ramp, the clamped step itself (the bits of k_gen_update) for a row that does not.
+                                  * Contexts with the flag run their generators in a launch of their own, as DOPF_F_GEN_QUADRATIC_COST
+                                  * contexts do (no pair or row-skipping kernels, no launch shared with the storages, no one-launch
+                                  * iteration); the storages, the consensus step, DOPF_F_GEN_AVAILABILITY, DOPF_F_GEN_QUADRATIC_COST,
+                                  * DOPF_F_LONG_HORIZON and the storage flags work as without it. With every ramp +inf and no p_prev the
+                                  * results are those of the flagless context on that chain, bit for bit. dopf_create refuses the flag with
+                                  * L > 0 (DOPF_E_UNSUPPORTED), dopf_roll_horizon refuses a context with it (the anchor's roll is the
+                                  * host's: build the next window's context). dopf_central_solve, _ex and _lossy ignore the flag. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -382,6 +397,22 @@ int dopf_set_line_rating(dopf_ctx *ctx, const double *rating /* L x T, [l + L*t]
  * naming the entry and storing nothing, for a NaN, an Inf or a negative entry. With G == 0 the call returns DOPF_OK and does nothing. */
 int dopf_set_generator_quadratic_cost(dopf_ctx *ctx, const double *c2 /* G; NULL = all 0 */);
 
+/* DOPF_F_GEN_RAMP: the generators' ramp limits, ramp_up[G] and ramp_down[G] in the caller's order of this context's generators, every
+ * value >= 0 (0: constant output; +inf: no limit), both NULL or both given; both NULL = all +inf (also the value until the first
+ * call). p_prev[G] (optional; NULL = no anchor): the output of the step before the window, in [0, gen_pmax[g]]; the first step then
+ * obeys the ramps against it. Timing, copies and status as for dopf_set_generator_quadratic_cost: callable between any two calls that
+ * iterate, the values are copied before the call returns, in order on the context's stream, into the device arrays the captured
+ * iteration graphs read (the graphs stay valid), and take effect at the next x-update; P, D, C, the duals and the iteration counter
+ * are kept, converged becomes 0. A P that breaks a ramp (dopf_set_state) is only the proximal centre: the next x-update projects.
+ * Contexts joined to a communicator or a peer exchange need nothing else (the constraint is local to the rank's agents).
+ * DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID, naming the entry and storing nothing, for a NaN, a negative ramp, only one of
+ * the two ramp arrays, a p_prev outside [0, gen_pmax], or an anchored generator g that cannot stay under its caps: with
+ * lo_0 = max(0, p_prev - ramp_down), lo_t = max(0, lo_{t-1} - ramp_down), some lo_t > cap[g,t] (the message names g and t). In
+ * contexts with this flag dopf_set_generator_availability repeats that check under its new table. With G == 0 the call returns
+ * DOPF_OK and does nothing. */
+int dopf_set_generator_ramp(dopf_ctx *ctx, const double *ramp_up /* G; NULL = +inf */, const double *ramp_down /* G; NULL = +inf */,
+                            const double *p_prev /* G; NULL = no anchor */);
+
 /* ---- a receding horizon: the window's demand and the window itself change in place -------------------------------
  * Replace nothing in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62). Both need no flag, work
  * on every single-GPU chain, keep the captured iteration graphs valid (they write the arrays the graphs read) and return after
@@ -528,6 +559,9 @@ int dopf_multi_set_generator_availability(dopf_multi *m, int32_t n_profiles, con
 /* dopf_set_generator_quadratic_cost for all G generators, c2[G] in the caller's order (NULL = all 0): each shard gets its slice;
  * every shard is checked before any value is stored */
 int dopf_multi_set_generator_quadratic_cost(dopf_multi *m, const double *c2);
+/* dopf_set_generator_ramp for all G generators, arrays in the caller's order (NULL as there): each shard gets its slice; every shard
+ * is checked before any value is stored */
+int dopf_multi_set_generator_ramp(dopf_multi *m, const double *ramp_up, const double *ramp_down, const double *p_prev);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);
