@@ -87,6 +87,7 @@ F_STO_EFFICIENCY = 268435456
 F_LINE_RATING = 536870912
 F_GEN_QUADRATIC_COST = 1073741824
 F_GEN_RAMP = 32
+F_GEN_RAMP_NETWORK = 2147483648  # bit 31, the last of the int32 flag word (ctypes stores it as the sign bit; test it with `& ... != 0`)
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -418,6 +419,8 @@ def _extensions(api: CApi, params: Optional[DopfParams], d, keep: dict, kw: dict
         params = DopfParams.from_buffer_copy(params if params is not None else default_params())
         for x, _ in todo:
             params.flags |= x.flag
+            if x.flag == F_GEN_RAMP and d.L > 0:       # ramps on a network: the opt-in of k_gen_ramp_net's knot scratch
+                params.flags |= F_GEN_RAMP_NETWORK
     return params, todo
 
 
@@ -458,7 +461,7 @@ class Engine(_ExtensionSetters):
     F_LINE_RATING and calls dopf_set_line_rating. gen_c2 (optional, G values >= 0): the generators' quadratic cost coefficients —
     sets F_GEN_QUADRATIC_COST and calls dopf_set_generator_quadratic_cost. gen_ramp = (up, down) (optional, G values >= 0 each, inf =
     no limit) / gen_prev (optional, G outputs of the step before the window): the generators' ramp limits and their anchor — sets
-    F_GEN_RAMP and calls dopf_set_generator_ramp (after the availability: its check reads the caps)."""
+    F_GEN_RAMP (on a network F_GEN_RAMP_NETWORK too) and calls dopf_set_generator_ramp (after the availability: its check reads the caps)."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,

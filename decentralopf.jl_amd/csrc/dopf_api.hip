@@ -470,6 +470,10 @@ int check_solver(dopf_ctx *c)
     if (c->host_st.solver_fail > c->solver_fail_seen) {
         const unsigned long long n = c->host_st.solver_fail - c->solver_fail_seen;
         c->solver_fail_seen = c->host_st.solver_fail;
+        if (c->plan.genRampNet)
+            return fail(c, DOPF_E_SOLVER, "%llu sub-problem(s) were left unsolved (%llu since creation): a storage whose root search did not reach "
+                                          "its tolerance, or a generator row whose knots exceeded the capacity of DOPF_F_GEN_RAMP_NETWORK (%d)",
+                        n, (unsigned long long)c->host_st.solver_fail, ramp_net_knots(c->v.T, c->v.L));
         return fail(c, DOPF_E_SOLVER, "%llu storage sub-problem(s) did not reach the root search's tolerance (%llu since creation)",
                     n, (unsigned long long)c->host_st.solver_fail);
     }
@@ -691,12 +695,14 @@ int upload_agents(dopf_ctx *c, const Sorted &so)
     if (c->plan.genRamp) {
         // DOPF_F_GEN_RAMP: the ramps (+inf), the anchor (NaN: none) and k_gen_ramp's scratch behind the capacities; the scratch is
         // sized from the knots' bound and is never read before it is written
-        const size_t n = gen_pmax_doubles(v.G, v.T, v.nGenItems, true);
+        // (networks, DOPF_F_GEN_RAMP_NETWORK: the scratch of k_gen_ramp_net, at every T, with the tables' kinks beside the ramps' knots)
+        const size_t n = gen_pmax_doubles(v.G, v.T, v.nGenItems, true, c->plan.genRampNet ? v.L : 0);
         size_t freeb = 0, totalb = 0;
         HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
         if (n * sizeof(double) > freeb)
-            return fail(c, DOPF_E_NOMEM, "ramp limits: the knots of the generators' projection (2T + 2 per row in flight) need %llu bytes, the "
-                                         "device has %llu free", (unsigned long long)(n * sizeof(double)), (unsigned long long)freeb);
+            return fail(c, DOPF_E_NOMEM, "ramp limits: the knots of the generators' projection (%d per row in flight) need %llu bytes, the "
+                                         "device has %llu free", c->plan.genRampNet ? ramp_net_knots(v.T, v.L) : 2 * v.T + 2,
+                        (unsigned long long)(n * sizeof(double)), (unsigned long long)freeb);
         c->gen_ramp_h.assign(so.gpm.begin(), so.gpm.end());
         c->gen_ramp_h.resize(3 * G, INFINITY);
         c->gen_ramp_h.resize(4 * G, std::nan(""));

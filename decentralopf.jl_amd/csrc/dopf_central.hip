@@ -110,6 +110,10 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
     dopf_params qq = *q;
     qq.stream = nullptr;
     qq.flags &= ~(DOPF_F_OVERLAP_AGENTS | DOPF_F_STO_EFFICIENCY);     // (the caller's efficiency flag is ignored: lossless unless the arrays are given)
+    // the LP takes no ramps: a network context's two ramp flags (bit 31 is the word's sign bit: masked as a number) would only cost
+    // k_gen_ramp_net's scratch — and DOPF_F_GEN_RAMP_NETWORK alone is nothing dopf_create accepts
+    qq.flags &= 0x7fffffff;
+    if (p->L > 0) qq.flags &= ~DOPF_F_GEN_RAMP;
     // every input that is given sets its flag (the caller's own flags stay: a flag without its input is that feature's default)
     const bool has_e0 = sto_e0_in != nullptr, has_band = sto_end_lo_in || sto_end_hi_in;
     const bool has_avail = n_profiles != 0 || profiles || profile_of;

@@ -24,6 +24,7 @@
 
 #include "../../include/dopf.h"
 #include "dopf_plan.h"
+#include "ramp_dp.h"
 
 namespace dopf {
 
@@ -202,7 +203,16 @@ __host__ __device__ inline const double *gen_c2(const DevView &v) { return v.gen
 constexpr int kRampLdsT = 128, kRampWaves = 8;
 __host__ __device__ inline size_t ramp_row_doubles(int T) { return 5 * (size_t)T + 4; }
 inline size_t ramp_scratch_doubles(int T, int nGenItems) { return T > kRampLdsT ? (size_t)nGenItems * kRampWaves * ramp_row_doubles(T) : 0; }
-inline size_t gen_pmax_doubles(int G, int T, int nGenItems, bool ramp) { return ramp ? 4 * (size_t)G + ramp_scratch_doubles(T, nGenItems) : (size_t)G; }
+// ... on a network (DOPF_F_GEN_RAMP_NETWORK, k_gen_ramp_net; L > 0): at every T, per wave p0[T] | y*[T] | kx[K] | kv[K] with
+// K = ramp_net_knots(T, L) (ramp_dp.h) — a row's knots leave LDS as soon as the tables' kinks do not fit beside the ramps'
+inline size_t ramp_scratch_doubles(int T, int nGenItems, int L)
+{
+    return L > 0 ? (size_t)nGenItems * kRampWaves * ramp_net_row_doubles(T, L) : ramp_scratch_doubles(T, nGenItems);
+}
+inline size_t gen_pmax_doubles(int G, int T, int nGenItems, bool ramp, int L = 0)
+{
+    return ramp ? 4 * (size_t)G + ramp_scratch_doubles(T, nGenItems, L) : (size_t)G;
+}
 __host__ __device__ inline const double *gen_ramp_up(const DevView &v) { return v.gen_pmax + v.G; }
 __host__ __device__ inline const double *gen_ramp_down(const DevView &v) { return v.gen_pmax + 2 * (size_t)v.G; }
 __host__ __device__ inline const double *gen_ramp_prev(const DevView &v) { return v.gen_pmax + 3 * (size_t)v.G; }
@@ -327,6 +337,7 @@ inline int agent_blocks(const DevView &v) { return v.nStoItems + (v.genBlocks > 
 // kernels_agents.hip
 void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_gen_ramp(const DevView &v, const Plan &p, hipStream_t s);       // gen_ramp.h: the generators of a DOPF_F_GEN_RAMP context
+void launch_gen_ramp_net(const DevView &v, const Plan &p, hipStream_t s);   // gen_ramp_net.h: ... on a network (DOPF_F_GEN_RAMP_NETWORK)
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s);

@@ -59,6 +59,7 @@ struct Plan {
                                     // generator blocks, no one-launch tail (the chain of DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T)
     bool genRamp;                   // DOPF_F_GEN_RAMP (copper plates): the generators run in k_gen_ramp<AV, QC> — the chain of genQuad (no pair, skip or
                                     // fused generator blocks, no one-launch tail), with the exact projection onto {box, ramps} for the rows that need it
+    bool genRampNet;                // ... on a network (DOPF_F_GEN_RAMP_NETWORK, L > 0): k_gen_ramp_net<AV, QC>, the chain a network runs under DOPF_F_NO_FUSE
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those
@@ -201,10 +202,15 @@ inline Plan plan_chain(const Shape &sh, unsigned flags, int cus)
     // or skip kernels (genTT2 = 0, and with it no one-launch tail: `pairs` below), no k_agents, no k_net_agents. The chain the
     // same problem runs under DOPF_F_NO_FUSE | DOPF_F_NO_TAIL_FUSE at odd T; the storages' launch of that chain, with the LV above
     p.genQuad = G > 0 && (flags & DOPF_F_GEN_QUADRATIC_COST);
-    // DOPF_F_GEN_RAMP: the same chain with k_gen_ramp as the generators' launch (copper plates only: on a network the row's derivative
-    // gains up to 2L kinks per step, another kernel)
+    // DOPF_F_GEN_RAMP: the same chain with k_gen_ramp as the generators' launch on a copper plate; on a network the row's derivative
+    // gains up to 2L kinks per step — k_gen_ramp_net, behind DOPF_F_GEN_RAMP_NETWORK (its knot scratch grows with the tables: the
+    // caller asks for it). That flag alone is refused; with L == 0 it is ignored
     p.genRamp = G > 0 && (flags & DOPF_F_GEN_RAMP);
-    if ((flags & DOPF_F_GEN_RAMP) && L > 0) p.refusal = "ramp limits run on copper plates; networks are not built yet";
+    p.genRampNet = p.genRamp && L > 0 && (flags & DOPF_F_GEN_RAMP_NETWORK);
+    if ((flags & DOPF_F_GEN_RAMP) && L > 0 && !(flags & DOPF_F_GEN_RAMP_NETWORK))
+        p.refusal = "ramp limits run on copper plates; on a network they need DOPF_F_GEN_RAMP_NETWORK at dopf_create";
+    if ((flags & DOPF_F_GEN_RAMP_NETWORK) && !(flags & DOPF_F_GEN_RAMP))
+        p.refusal = "DOPF_F_GEN_RAMP_NETWORK means nothing without DOPF_F_GEN_RAMP";
     if (p.genQuad || p.genRamp) flags |= DOPF_F_NO_FUSE;
     p.genTT2 = (!p.genQuad && !p.genRamp && L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
     p.fuseAgents = p.genTT2 > 0 && p.genTT2 <= 256 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS));

@@ -133,6 +133,7 @@ const DOPF_F_STO_EFFICIENCY = 268435456  # include/dopf.h
 const DOPF_F_LINE_RATING = 536870912  # include/dopf.h
 const DOPF_F_GEN_QUADRATIC_COST = 1073741824  # include/dopf.h
 const DOPF_F_GEN_RAMP = 32  # include/dopf.h
+const DOPF_F_GEN_RAMP_NETWORK = typemin(Int32)  # include/dopf.h: 2147483648, bit 31 — the sign bit of the Cint flag word, and its last
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -152,14 +153,17 @@ last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_T
 availability profile (see `set_availability!`) need `flags = DOPF_F_GEN_AVAILABILITY`; storages with charge / discharge
 efficiencies below 1 (see `set_efficiency!`; the reference's `Storage` type, used verbatim, has no such fields) need
 `flags = DOPF_F_STO_EFFICIENCY`, line limits per timestep (see `set_line_rating!`) `flags = DOPF_F_LINE_RATING`, and quadratic
-generator cost curves (see `set_quadratic_cost!`) `flags = DOPF_F_GEN_QUADRATIC_COST`; generator ramp limits on a copper plate (see
-`set_ramp!`) `flags = DOPF_F_GEN_RAMP`. Flags combine with `|`.
+generator cost curves (see `set_quadratic_cost!`) `flags = DOPF_F_GEN_QUADRATIC_COST`; generator ramp limits (see `set_ramp!`) `flags = DOPF_F_GEN_RAMP` — on a case
+with lines the constructor adds `DOPF_F_GEN_RAMP_NETWORK`, the library's opt-in for the network step's knot scratch. Flags combine with `|`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
               w_flow::Float64=10.0, w_prox::Float64=1.0, eps::Float64=1e-3, mask_thr::Float64=1e-2, flags::Int=0)
     N, L, T = length(nodes), length(lines), length(nodes[1].demand)
     G, S = length(generators), length(storages)
+    if (flags & DOPF_F_GEN_RAMP) != 0 && L > 0
+        flags |= DOPF_F_GEN_RAMP_NETWORK         # ramps on a network: k_gen_ramp_net and its knot scratch (DESIGN.md 5s)
+    end
     node_to_id = Dict{Node, Int}(n => i for (i, n) in enumerate(nodes))
     demand = Float64[nodes[n].demand[t] for n in 1:N, t in 1:T]          # N x T, column-major = [n + N*t]
     ptdf = L > 0 ? Matrix{Float64}(calculate_ptdf(nodes, lines)) : zeros(Float64, 0, N)
@@ -333,7 +337,7 @@ end
 The ramp limits of each generator (`ramp_up[g], ramp_down[g] >= 0`, `Inf` = no limit, in the order of `generators`; both `nothing` =
 all `Inf`) and optionally the outputs of the step before the window (`p_prev`, in `[0, max_generation]`; `nothing` = no anchor):
 `-ramp_down <= P[g,t] - P[g,t-1] <= ramp_up`, at `t = 1` against `p_prev`. The reference's generators move freely between steps
-(src/optimization/subproblems.jl:26-40); the ADMM must have been created with `flags = DOPF_F_GEN_RAMP`, on a case without lines.
+(src/optimization/subproblems.jl:26-40); the ADMM must have been created with `flags = DOPF_F_GEN_RAMP` (with lines the constructor adds `DOPF_F_GEN_RAMP_NETWORK`).
 The state and the iteration counter stay; takes effect at the next iteration.
 """
 function set_ramp!(admm::ADMM, ramp_up::Union{Nothing, Vector{Float64}}, ramp_down::Union{Nothing, Vector{Float64}},

@@ -20,7 +20,7 @@ T limits >= 0, |flow[t]| <= rating[t] — a planned derating, a dynamic rating o
 Generator.quadratic_costs is not in the reference either (one constant marginal_costs per unit, src/optimization/subproblems.jl:26-40):
 c2 >= 0, the cost of output P is marginal_costs * P + c2 * P^2 / 2 — a polynomial cost curve (DOPF_F_GEN_QUADRATIC_COST).
 Generator.ramp_up / ramp_down are not in the reference either (its generators move freely between steps, src/optimization/subproblems.jl:26-40):
--ramp_down <= P[t] - P[t-1] <= ramp_up, the limit on how fast a unit's output changes; copper plates only (DOPF_F_GEN_RAMP).
+-ramp_down <= P[t] - P[t-1] <= ramp_up, the limit on how fast a unit's output changes (DOPF_F_GEN_RAMP; on a case with lines the engines add DOPF_F_GEN_RAMP_NETWORK).
 """
 from __future__ import annotations
 

@@ -208,8 +208,26 @@ typedef struct dopf_params {
                                   * iteration); the storages, the consensus step, DOPF_F_GEN_AVAILABILITY, DOPF_F_GEN_QUADRATIC_COST,
                                   * DOPF_F_LONG_HORIZON and the storage flags work as without it. With every ramp +inf and no p_prev the
                                   * results are those of the flagless context on that chain, bit for bit. dopf_create refuses the flag with
-                                  * L > 0 (DOPF_E_UNSUPPORTED), dopf_roll_horizon refuses a context with it (the anchor's roll is the
-                                  * host's: build the next window's context). dopf_central_solve, _ex and _lossy ignore the flag. */
+                                  * L > 0 (DOPF_E_UNSUPPORTED) unless DOPF_F_GEN_RAMP_NETWORK is given too, dopf_roll_horizon refuses a
+                                  * context with it (the anchor's roll is the host's: build the next window's context).
+                                  * dopf_central_solve, _ex and _lossy ignore the flag. */
+#define DOPF_F_GEN_RAMP_NETWORK 2147483648u /* ramp limits on a network (L > 0); meaningful only together with DOPF_F_GEN_RAMP, and an
+                                  * opt-in of its own because the network step needs memory that grows with the tables. A row's derivative
+                                  * per step is then mc + c2 x + Psi(x - p0) + w_prox (x - p0), piecewise linear with up to 2L kinks of the
+                                  * node's table, and the kinks are merged into the knots of the dynamic programme (k_gen_ramp_net,
+                                  * DESIGN.md 5s). A row in flight holds at most 2T + 2 + min(2 L T, 4096) knots, in a scratch allocated at
+                                  * dopf_create (DOPF_E_NOMEM, naming the bytes, where it does not fit). A row whose knots would exceed
+                                  * that capacity keeps its clamped step for the iteration and is counted: dopf_iterate returns
+                                  * DOPF_E_SOLVER and dopf_solver_failures() grows, as for a storage whose root search gave up. The chain
+                                  * is the one a network runs under DOPF_F_NO_FUSE; DOPF_F_LINE_RATING, DOPF_F_WIDE_NETWORK,
+                                  * DOPF_F_GEN_AVAILABILITY, DOPF_F_GEN_QUADRATIC_COST, DOPF_F_KEEP_DELTAS and the storage flags work as
+                                  * without it; with every ramp +inf and no p_prev the results are those of the flagless context on that
+                                  * chain, bit for bit. dopf_create refuses (DOPF_E_UNSUPPORTED) this flag without DOPF_F_GEN_RAMP, and
+                                  * DOPF_F_GEN_RAMP alone with L > 0; with L == 0 this flag is accepted and ignored (the copper-plate
+                                  * kernel runs, the same bits). dopf_roll_horizon goes on refusing every ramp context, dopf_central_solve,
+                                  * _ex and _lossy ignore the flag. This is bit 31, the LAST bit of dopf_params.flags (an int32_t whose
+                                  * size the ABI pins): the next create-time option needs a second flag word, for example in a
+                                  * dopf_create2. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
