@@ -88,6 +88,7 @@ F_LINE_RATING = 536870912
 F_GEN_QUADRATIC_COST = 1073741824
 F_GEN_RAMP = 32
 F_GEN_RAMP_NETWORK = 2147483648  # bit 31, the last of the int32 flag word (ctypes stores it as the sign bit; test it with `& ... != 0`)
+F2_GEN_ENERGY_BUDGET = 1  # the second flag word (DOPF_F2_*): the flags2 argument of dopf_create_ex / dopf_multi_create_ex
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 
@@ -186,9 +187,13 @@ class CApi:
             self._sig("multi_get_primal", C.c_int, [ctxp, c_double_p, c_double_p, c_double_p, c_double_p])
             self._sig("multi_size", C.c_int32, [ctxp])
             self._sig("multi_ctx", ctxp, [ctxp, C.c_int32])
+            # the creates with the second flag word (Engine and MultiEngine call them only with a non-zero word)
+            self._sig("create_ex", C.c_int, [C.POINTER(ctxp), C.POINTER(DopfProblem), C.POINTER(DopfParams), C.c_int32])
+            self._sig("multi_create_ex", C.c_int, [C.POINTER(ctxp), C.POINTER(DopfProblem), C.POINTER(DopfParams), C.c_int32, c_int32_p,
+                                                   C.c_int32])
         # the problem extensions' setters (EXTENSIONS below). The older three belong to the HIP library's ABI; the later three are bound
         # wherever the library exports them — the oracle backend loads without them (Engine's setter then refuses)
-        for x in EXTENSIONS + EXTENSIONS_MORE:
+        for x in _ALL_EXTENSIONS:
             if x.optional or prefix == "dopf_":
                 for name in (x.entry, "multi_" + x.entry):
                     (self._opt if x.optional else self._sig)(name, C.c_int, [ctxp] + list(x.argtypes))
@@ -312,6 +317,7 @@ class Extension(NamedTuple):
     mirror: Optional[Callable] = None   # (*arrays) -> {constructor keyword: value} where the keywords are not the arrays one to one
     optional: bool = False  # bound wherever the library exports it, under any prefix, and the setter's refusal ends in " (unsupported)";
     #                         False: part of the "dopf_" ABI, bound under that prefix alone
+    word: int = 1           # the flag word `flag` lives in: 1 = dopf_params.flags, 2 = the flags2 argument of dopf_create_ex
 
     @property
     def packed(self) -> bool:
@@ -392,14 +398,30 @@ EXTENSIONS_MORE = (
               is_default=lambda d, keep, up, down, prev: prev is None and (up is None or not (np.any(np.isfinite(up)) or np.any(np.isfinite(down)))),
               mirror=lambda up, down, prev: dict(gen_ramp=None if up is None else (up, down), gen_prev=prev)),
 )
-_ALL_EXTENSIONS = EXTENSIONS + EXTENSIONS_MORE
+
+
+def _budget_norm(d, e_min, e_max):
+    return (None if e_min is None else _f64(e_min, d.G), None if e_max is None else _f64(e_max, d.G))
+
+
+# The extensions whose flag lives in the second word (DOPF_F2_*: dopf_params.flags is full). The budgets come behind the availability,
+# whose caps their check reads.
+EXTENSIONS_WORD2 = (
+    Extension(keys=("gen_budget",), flag=F2_GEN_ENERGY_BUDGET, word=2, entry="set_generator_energy_budget", argtypes=(c_double_p, c_double_p),
+              setter="set_energy_budget", optional=True,
+              what="generator energy budgets", why="an energy_min above 0 or a finite energy_max; the reference's generators have no budget over the window",
+              norm=_budget_norm,
+              is_default=lambda d, keep, lo, hi: not ((lo is not None and np.any(lo != 0.0)) or (hi is not None and np.any(hi != np.inf)))),
+)
+_ALL_EXTENSIONS = EXTENSIONS + EXTENSIONS_MORE + EXTENSIONS_WORD2
 _BY_SETTER = {x.setter: x for x in _ALL_EXTENSIONS}
 
 
 def _extensions(api: CApi, params: Optional[DopfParams], d, keep: dict, kw: dict):
     """(params, todo) for a context built with the extensions' constructor keywords in kw: the params with the flags of those given
-    added (a copy), and todo, the (extension, arrays) to apply behind create, in the order of EXTENSIONS + EXTENSIONS_MORE. Nothing to set: a keyword left
-    None, or its default value on an API without the entry (a non-default value there: DopfError)."""
+    added (a copy), and todo, the (extension, arrays) to apply behind create, in the order of EXTENSIONS + EXTENSIONS_MORE + EXTENSIONS_WORD2.
+    Nothing to set: a keyword left None, or its default value on an API without the entry (a non-default value there: DopfError). The
+    flags of the second word are not in params: _flags2(todo) forms them."""
     todo = []
     for x in _ALL_EXTENSIONS:
         given = [kw.get(k) for k in x.keys]
@@ -415,13 +437,30 @@ def _extensions(api: CApi, params: Optional[DopfParams], d, keep: dict, kw: dict
                 raise DopfError(x.refusal(api, setter=False))
             continue
         todo.append((x, arrays))
-    if todo:
+    if any(x.word == 1 for x, _ in todo):
         params = DopfParams.from_buffer_copy(params if params is not None else default_params())
         for x, _ in todo:
+            if x.word != 1:
+                continue
             params.flags |= x.flag
             if x.flag == F_GEN_RAMP and d.L > 0:       # ramps on a network: the opt-in of k_gen_ramp_net's knot scratch
                 params.flags |= F_GEN_RAMP_NETWORK
     return params, todo
+
+
+def _needs_create_ex(api: CApi, flags2: int) -> None:
+    """A non-zero second word on an API without the entry that takes it: refused as the tables' rows refuse (DopfError)."""
+    if flags2 and not hasattr(api, "create_ex"):
+        raise DopfError(f"{api.prefix}*: this API has no second flag word (no create_ex; flags2 = {flags2})")
+
+
+def _flags2(todo) -> int:
+    """The second flag word of a context built with todo (what _extensions returned): the flags of its word-2 extensions."""
+    word = 0
+    for x, _ in todo:
+        if x.word == 2:
+            word |= x.flag
+    return word
 
 
 class _ExtensionSetters:
@@ -461,20 +500,26 @@ class Engine(_ExtensionSetters):
     F_LINE_RATING and calls dopf_set_line_rating. gen_c2 (optional, G values >= 0): the generators' quadratic cost coefficients —
     sets F_GEN_QUADRATIC_COST and calls dopf_set_generator_quadratic_cost. gen_ramp = (up, down) (optional, G values >= 0 each, inf =
     no limit) / gen_prev (optional, G outputs of the step before the window): the generators' ramp limits and their anchor — sets
-    F_GEN_RAMP (on a network F_GEN_RAMP_NETWORK too) and calls dopf_set_generator_ramp (after the availability: its check reads the caps)."""
+    F_GEN_RAMP (on a network F_GEN_RAMP_NETWORK too) and calls dopf_set_generator_ramp (after the availability: its check reads the caps).
+    gen_budget = (e_min, e_max) (optional, G values each; either may be None: 0 / inf): the generators' energy budgets over the window —
+    sets F2_GEN_ENERGY_BUDGET in the second flag word (self.flags2; the context is then created by dopf_create_ex) and calls
+    dopf_set_generator_energy_budget (after the availability too). flags2 (optional): further bits of that word, as Engine.roll passes
+    them to the context it rebuilds; on an API without create_ex a non-zero word is a DopfError."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
                  mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
-                 sto_eta=None, line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None):
+                 sto_eta=None, line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                                               sto_mc, sto_pmax, sto_emax, sto_node)
         params, todo = _extensions(api, params, self, keep, dict(
             sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
-            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev))
+            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget))
         self.params = params if params is not None else default_params()
+        self.flags2 = int(flags2) | _flags2(todo)
+        _needs_create_ex(api, self.flags2)
         # what a window change needs of the problem: the arrays as handed to create, and the inputs of the setters as they stand
         # (by constructor keyword, in the form the constructor takes them)
         self._keep, self._mode, self._mirror = keep, mode, {}
@@ -482,7 +527,10 @@ class Engine(_ExtensionSetters):
         args = [C.byref(self._ctx), C.byref(prob), C.byref(self.params)]
         if api.has_mode:
             args.append(C.c_int32(0 if mode is None else mode))
-        rc = api._create(*args)
+        if self.flags2:
+            rc = api.create_ex(*args, C.c_int32(self.flags2))
+        else:
+            rc = api._create(*args)
         if rc != 0:
             msg = api.last_error(None)
             raise DopfError(f"{api.prefix}create failed ({rc}): {msg.decode() if msg else ''}")
@@ -608,6 +656,12 @@ class Engine(_ExtensionSetters):
             raise ValueError("set_ramp: up and down must both be given or both be None")
         self._mirror.update(self._set("set_ramp", None if up is None else (up, down), prev))
 
+    def set_energy_budget(self, e_min=None, e_max=None):
+        """dopf_set_generator_energy_budget: each generator's energy budget over the window, e_min <= sum_t P[g,t] <= e_max (G values
+        each; e_min None = all 0, e_max None = all inf); needs F2_GEN_ENERGY_BUDGET. P, D, C, the duals and the iteration counter
+        stay; converged becomes False. Takes effect at the next x-update. A backend without the entry: DopfError (unsupported)."""
+        self._mirror.update(self._set("set_energy_budget", e_min, e_max))
+
     # -- a receding horizon --------------------------------------------------------------------
     def demand(self) -> np.ndarray:
         """The context's demand as it stands, (N, T)."""
@@ -631,7 +685,8 @@ class Engine(_ExtensionSetters):
         from .horizon import shift_window
         k = int(k)
         # (a context with ramp limits goes the host route on every API: the next window's anchor is the old P[:, k - 1])
-        native = hasattr(self.api, "roll_horizon") and not self.params.flags & F_GEN_RAMP
+        # (so does a context with energy budgets: what is left of them after k steps is formed below)
+        native = hasattr(self.api, "roll_horizon") and not self.params.flags & F_GEN_RAMP and not self.flags2 & F2_GEN_ENERGY_BUDGET
         if not 1 <= k <= self.T - 1:
             if native:
                 self._chk(self.api.roll_horizon(self._ctx, k, None))       # (the library's refusal and message)
@@ -660,7 +715,15 @@ class Engine(_ExtensionSetters):
             kw["line_rating"] = w["line_rating"]
         if self.params.flags & F_GEN_RAMP:
             kw["gen_prev"] = P[:, k - 1].copy()
-        new = Engine(self.api, N=self.N, L=self.L, T=self.T, params=self.params, mode=self._mode, **kw)
+        if self.flags2 & F2_GEN_ENERGY_BUDGET:
+            # what the k steps that leave the window delivered comes off both bounds (floored at 0); the new context's setter checks
+            # what is left against the caps, and its refusal is this call's
+            lo, hi = self._mirror.get("gen_budget") or (None, None)
+            used = P[:, :k].sum(axis=1)
+            lo = np.zeros(self.G) if lo is None else np.maximum(0.0, lo - used)
+            hi = np.full(self.G, np.inf) if hi is None else np.maximum(0.0, hi - used)
+            kw["gen_budget"] = (lo, hi)
+        new = Engine(self.api, N=self.N, L=self.L, T=self.T, params=self.params, mode=self._mode, flags2=self.flags2, **kw)
         new.set_state(P=w["P"], D=w["D"], C_=w["C"], avg_U=w["avg_U"], avg_K=w["avg_K"], lam=w["lam"], mu=w["mu"], rho=w["rho"],
                       iteration=2)
         self._adopt(new)
@@ -822,19 +885,21 @@ class MultiEngine(_ExtensionSetters):
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
                  sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None, gen_c2=None,
-                 gen_ramp=None, gen_prev=None):
+                 gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                                               sto_mc, sto_pmax, sto_emax, sto_node)
         params, todo = _extensions(api, params, self, keep, dict(
             sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
-            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev))
+            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget))
         self.params = params if params is not None else default_params()
+        self.flags2 = int(flags2) | _flags2(todo)
+        _needs_create_ex(api, self.flags2)
         dev = None if devices is None else _i32(devices, n_gpus)
         self._m = C.c_void_p()
-        rc = api.multi_create(C.byref(self._m), C.byref(prob), C.byref(self.params), int(n_gpus),
-                              None if dev is None else dev.ctypes.data_as(c_int32_p))
+        args = (C.byref(self._m), C.byref(prob), C.byref(self.params), int(n_gpus), None if dev is None else dev.ctypes.data_as(c_int32_p))
+        rc = api.multi_create_ex(*args, C.c_int32(self.flags2)) if self.flags2 else api.multi_create(*args)
         if rc != 0:
             msg = api.multi_last_error(None)
             raise DopfError(f"dopf_multi_create failed ({rc}): {msg.decode() if msg else ''}")
@@ -856,6 +921,11 @@ class MultiEngine(_ExtensionSetters):
         if (up is None) != (down is None):
             raise ValueError("set_ramp: up and down must both be given or both be None")
         self._set("set_ramp", None if up is None else (up, down), prev)
+
+    def set_energy_budget(self, e_min=None, e_max=None):
+        """dopf_multi_set_generator_energy_budget: all G generators' energy budgets in the caller's order (e_min None = all 0, e_max
+        None = all inf); each shard gets its slice."""
+        self._set("set_energy_budget", e_min, e_max)
 
     def set_line_rating(self, rating=None):
         """dopf_multi_set_line_rating: the (L, T) table for every shard (None = f_max in every timestep)."""
@@ -921,7 +991,7 @@ class MultiEngine(_ExtensionSetters):
 def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                   sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                   sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
-                  line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None) -> dict:
+                  line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None) -> dict:
     """dopf_central_solve: the central reference (src/opf_central_reference.jl) as one LP solved on the GPU by a first-order
     primal-dual method. Arguments as Engine (PackedProblem.engine_kwargs()). Returns objective, gap, iterations and the
     reference script's outputs in Julia shapes: P (G,T), D/C/E (S,T), system_price (T), nodal_price (N,T),
@@ -933,8 +1003,13 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     given (all ones too) the call is dopf_central_solve_lossy, and E = sto_e0 + cumsum(eta_c C - D / eta_d).
     line_rating: the device LP takes no line ratings; a table other than f_max in every timestep raises DopfError.
     gen_c2: the device LP takes no quadratic costs either; a non-zero coefficient raises DopfError.
-    gen_ramp, gen_prev: nor ramp limits; a finite ramp or an anchor raises DopfError."""
+    gen_ramp, gen_prev: nor ramp limits; a finite ramp or an anchor raises DopfError.
+    gen_budget: nor energy budgets; an e_min above 0 or a finite e_max raises DopfError."""
     N, L, T = int(N), int(L), int(T)
+    if gen_budget is not None and ((gen_budget[0] is not None and np.any(np.asarray(gen_budget[0], dtype=np.float64) != 0.0)) or
+                                   (gen_budget[1] is not None and np.any(np.asarray(gen_budget[1], dtype=np.float64) != np.inf))):
+        raise DopfError("dopf_central_solve*: the device LP takes no generator energy budgets (it bounds no generator's sum over the "
+                        "window); use central.solve_central_packed(..., gen_budget=) for a case with a budget")
     if gen_prev is not None or (gen_ramp is not None and any(np.any(np.isfinite(np.asarray(r, dtype=np.float64))) for r in gen_ramp)):
         raise DopfError("dopf_central_solve*: the device LP takes no generator ramp limits (it lets every generator move freely); use "
                         "central.solve_central_packed(..., gen_ramp=) for a case with ramps")

@@ -194,6 +194,18 @@ class ADMM:
         self.packed.gen_ramp = None if up is None else tuple(np.asarray(r, dtype=np.float64).reshape(G).copy() for r in (up, down))
         self.convergence = Convergence()
 
+    def set_energy_budget(self, e_min=None, e_max=None) -> None:
+        """Each generator's energy budget over the window (G values each in the order of `generators`; e_min None = all 0, e_max None
+        = all inf): e_min <= sum_t P[t] <= e_max. Not in the reference (its generators have no budget over the window). Needs the
+        second flag word's F2_GEN_ENERGY_BUDGET (set for you when a Generator has an energy_min or energy_max); the state and the
+        iteration counter stay, the run is no longer converged; takes effect at the next iteration."""
+        self.engine.set_energy_budget(e_min, e_max)
+        G = self.packed.G
+        lo = np.zeros(G) if e_min is None else np.asarray(e_min, dtype=np.float64).reshape(G).copy()
+        hi = np.full(G, np.inf) if e_max is None else np.asarray(e_max, dtype=np.float64).reshape(G).copy()
+        self.packed.gen_budget = None if e_min is None and e_max is None else (lo, hi)
+        self.convergence = Convergence()
+
     def _replaced(self, field_: str, value, shape) -> None:
         """the packed problem follows an input that was replaced under a kept state, and the run is no longer converged"""
         setattr(self.packed, field_, None if value is None else np.asarray(value, dtype=np.float64).reshape(shape).copy())

@@ -56,7 +56,7 @@ def _efficiencies(pp: PackedProblem, efficiency):
 
 
 def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None,
-                         availability=None, efficiency=None, line_rating=None, gen_ramp=None, gen_prev=None) -> CentralResult:
+                         availability=None, efficiency=None, line_rating=None, gen_ramp=None, gen_prev=None, gen_budget=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
     tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
     side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference). terminal_level:
@@ -67,7 +67,9 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
     the packed case's efficiencies, else all 1 as in the reference). line_rating: (L, T), the right-hand sides of the two flow rows
     become rating[l,t] (None: the packed case's table, else f_max in every timestep as in the reference). gen_ramp: (up, down), (G,)
     each, inf = no limit: the rows -down[g] <= P[g,t] - P[g,t-1] <= up[g] for t >= 1 (None: the packed case's ramps, else none as in
-    the reference); gen_prev: (G,) outputs of the step before the window, the same rows at t = 0 against them (None: no such rows)."""
+    the reference); gen_prev: (G,) outputs of the step before the window, the same rows at t = 0 against them (None: no such rows). gen_budget:
+    (e_min, e_max), (G,) each: the rows e_min[g] <= sum_t P[g,t] <= e_max[g], one per generator with an e_min above 0 and one per finite
+    e_max (None: the packed case's budgets, else none as in the reference)."""
     from scipy import sparse
     from scipy.optimize import linprog
     if pp.has_quadratic_cost():
@@ -144,11 +146,11 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
         lb[last] = np.asarray(terminal_level[0], dtype=np.float64).reshape(S)
         ub[last] = np.asarray(terminal_level[1], dtype=np.float64).reshape(S)
     Aub = bub = None
+    ur, uc, uv, bub = [], [], [], []
     if gen_ramp is None and pp.has_ramp():
         gen_ramp = pp.ramp()
     if (gen_ramp is not None or gen_prev is not None) and G > 0:
         up, down = (np.full(G, np.inf),) * 2 if gen_ramp is None else (np.asarray(r, dtype=np.float64).reshape(G) for r in gen_ramp)
-        ur, uc, uv, bub = [], [], [], []
         def ramp_rows(sign, limit):          # sign (P[g,t] - P[g,t-1]) <= limit[g], the generators with a finite limit; t = 0: against gen_prev
             nonlocal Aub
             for g in np.flatnonzero(np.isfinite(limit)):
@@ -160,9 +162,19 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
                     bub.append(limit[g] + (sign * float(np.asarray(gen_prev, dtype=np.float64).reshape(G)[g]) if t == 0 else 0.0))
         ramp_rows(1.0, up)
         ramp_rows(-1.0, down)
-        if bub:
-            Aub = sparse.csr_matrix((uv, (ur, uc)), shape=(len(bub), nv))
-            bub = np.asarray(bub)
+    if gen_budget is None and pp.has_budget():
+        gen_budget = pp.budget()
+    if gen_budget is not None and G > 0:
+        e_min = np.zeros(G) if gen_budget[0] is None else np.asarray(gen_budget[0], dtype=np.float64).reshape(G)
+        e_max = np.full(G, np.inf) if gen_budget[1] is None else np.asarray(gen_budget[1], dtype=np.float64).reshape(G)
+        for sign, bound, rowsof in ((1.0, e_max, np.flatnonzero(np.isfinite(e_max))), (-1.0, e_min, np.flatnonzero(e_min > 0.0))):
+            for g in rowsof:          # sign sum_t P[g,t] <= sign bound[g]
+                r = len(bub)
+                ur += [r] * T; uc += list(range(g * T, g * T + T)); uv += [sign] * T
+                bub.append(sign * bound[g])
+    if bub:
+        Aub = sparse.csr_matrix((uv, (ur, uc)), shape=(len(bub), nv))
+        bub = np.asarray(bub)
     res = linprog(c, A_ub=Aub, b_ub=bub if Aub is not None else None, A_eq=Aeq, b_eq=np.concatenate(beq),
                   bounds=np.stack([lb, ub], axis=1), method="highs")
     if res.status != 0:
@@ -223,6 +235,9 @@ def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Gene
     if pp.has_ramp():
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no generator ramp limits "
                          "and would let every generator move freely; use central_reference for a case with Generator.ramp_up / ramp_down")
+    if pp.has_budget():
+        raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no generator energy budgets "
+                         "and would bound no generator's sum over the window; use central_reference for a case with Generator.energy_min / energy_max")
     if pp.line_rating is not None:
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no line ratings and would "
                          "solve with max_capacity in every timestep; use central_reference for a case with Line.rating")

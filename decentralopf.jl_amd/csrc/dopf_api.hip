@@ -142,6 +142,39 @@ int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, cons
     return DOPF_OK;
 }
 
+// DOPF_F2_GEN_ENERGY_BUDGET: a generator must be able to deliver its minimum under its caps — e_min <= sum_t cap[g,t], the sum formed
+// in t order. g: the caller's index (the message's); f: the generator's profile, or null
+static int budget_min_fits(dopf_ctx *c, const char *entry, int g, double pm, double e_min, const double *f)
+{
+    if (!(e_min > 0.0)) return DOPF_OK;
+    double room = 0.0;
+    for (int t = 0; t < c->v.T; ++t) room += f ? pm * f[t] : pm;
+    if (e_min > room)
+        return fail(c, DOPF_E_INVALID, "%s: generator g = %d cannot deliver e_min = %g under its caps (sum_t cap[g,t] = %g)", entry, g, e_min, room);
+    return DOPF_OK;
+}
+
+// dopf_set_generator_energy_budget's checks: the flag, no NaN, e_min finite and >= 0, e_max >= 0, e_min <= e_max, and every minimum
+// deliverable under the caps (the stored availability table)
+int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max)
+{
+    if (!(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
+        return fail(c, DOPF_E_UNSUPPORTED, "generator energy budgets need DOPF_F2_GEN_ENERGY_BUDGET at dopf_create_ex");
+    const int G = c->v.G, T = c->v.T;
+    for (int i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        const double lo = e_min ? e_min[a] : 0.0, hi = e_max ? e_max[a] : INFINITY;
+        if (std::isnan(lo) || std::isinf(lo) || lo < 0.0)
+            return fail(c, DOPF_E_INVALID, "dopf_set_generator_energy_budget: e_min[%d] is %g (finite and >= 0 wanted)", a, lo);
+        if (std::isnan(hi) || hi < 0.0) return fail(c, DOPF_E_INVALID, "dopf_set_generator_energy_budget: e_max[%d] is %g (>= 0 wanted)", a, hi);
+        if (lo > hi) return fail(c, DOPF_E_INVALID, "dopf_set_generator_energy_budget: e_min[%d] = %g exceeds e_max[%d] = %g", a, lo, a, hi);
+        const int k = c->gen_prof_h.empty() ? -1 : c->gen_prof_h[i];
+        if (int rc = budget_min_fits(c, "dopf_set_generator_energy_budget", a, c->gen_budget_h[i], lo,
+                                     k >= 0 ? c->gen_avail_h.data() + (size_t)k * T : nullptr)) return rc;
+    }
+    return DOPF_OK;
+}
+
 // dopf_set_generator_availability's checks: the flag, a table of K >= 0 profiles with every value in [0, 1] (no NaN), and every index in [-1, K)
 int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of)
 {
@@ -166,6 +199,12 @@ int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles,
             const int a = c->gen_perm[i], k = profile_of ? profile_of[a] : -1;
             if (int rc = ramp_anchor_fits(c, "dopf_set_generator_availability", a, c->gen_ramp_h[i], c->gen_ramp_h[2 * (size_t)G + i],
                                           c->gen_ramp_h[3 * (size_t)G + i], k >= 0 ? profiles + (size_t)k * T : nullptr)) return rc;
+        }
+    if (c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET)      // the minima of dopf_set_generator_energy_budget, under the new table
+        for (int i = 0; i < G; ++i) {
+            const int a = c->gen_perm[i], k = profile_of ? profile_of[a] : -1;
+            if (int rc = budget_min_fits(c, "dopf_set_generator_availability", a, c->gen_budget_h[i], c->gen_budget_h[(size_t)G + i],
+                                         k >= 0 ? profiles + (size_t)k * T : nullptr)) return rc;
         }
     return DOPF_OK;
 }
@@ -474,6 +513,10 @@ int check_solver(dopf_ctx *c)
             return fail(c, DOPF_E_SOLVER, "%llu sub-problem(s) were left unsolved (%llu since creation): a storage whose root search did not reach "
                                           "its tolerance, or a generator row whose knots exceeded the capacity of DOPF_F_GEN_RAMP_NETWORK (%d)",
                         n, (unsigned long long)c->host_st.solver_fail, ramp_net_knots(c->v.T, c->v.L));
+        if (c->plan.genBudget)
+            return fail(c, DOPF_E_SOLVER, "%llu sub-problem(s) were left unsolved (%llu since creation): a storage whose root search did not reach "
+                                          "its tolerance, or a generator row whose energy budget's multiplier search spent its %d evaluations",
+                        n, (unsigned long long)c->host_st.solver_fail, kBudgetMaxEvals);
         return fail(c, DOPF_E_SOLVER, "%llu storage sub-problem(s) did not reach the root search's tolerance (%llu since creation)",
                     n, (unsigned long long)c->host_st.solver_fail);
     }
@@ -633,7 +676,7 @@ int choose_plan(dopf_ctx *c, const Shape &sh)
 {
     hipDeviceProp_t prop{};
     const int cus = hipGetDeviceProperties(&prop, c->device) == hipSuccess ? prop.multiProcessorCount : 0;
-    const Plan &pl = c->plan = plan_chain(sh, c->q.flags, cus);
+    const Plan &pl = c->plan = plan_chain(sh, c->q.flags, cus, (unsigned)c->flags2);
     if (pl.refusal) return fail(c, DOPF_E_UNSUPPORTED, "%s (T=%d)", pl.refusal, sh.T);
     DevView &v = c->v;
     v.use_warm = pl.useWarm; v.genSkip = pl.genSkip; v.genBlocks = v.genRows = pl.genBlocks; v.tablesInDual = pl.tablesInDual;
@@ -711,6 +754,12 @@ int upload_agents(dopf_ctx *c, const Sorted &so)
         if (d.rc) return d.rc;
         HIPCHK(c, hipMemcpy(blk, c->gen_ramp_h.data(), 4 * G * sizeof(double), hipMemcpyHostToDevice));
         v.gen_pmax = blk;
+    } else if (c->plan.genBudget) {
+        // DOPF_F2_GEN_ENERGY_BUDGET: the budgets behind the capacities, e_min (0) | e_max (+inf) until the setter
+        c->gen_budget_h.assign(so.gpm.begin(), so.gpm.end());
+        c->gen_budget_h.resize(2 * G, 0.0);
+        c->gen_budget_h.resize(gen_budget_doubles(v.G), INFINITY);
+        d.upload(&v.gen_pmax, c->gen_budget_h);
     } else {
         d.upload(&v.gen_pmax, so.gpm);
     }
@@ -873,10 +922,15 @@ void dopf_default_params(dopf_params *q)
 
 const char *dopf_last_error(const dopf_ctx *ctx) { return ctx ? ctx->err : g_create_err; }
 
-int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
+int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q) { return dopf_create_ex(out, p, q, 0); }
+
+int dopf_create_ex(dopf_ctx **out, const dopf_problem *p, const dopf_params *q, int32_t flags2)
 {
     if (!out || !p || !q) return fail(nullptr, DOPF_E_INVALID, "null argument");
     *out = nullptr;
+    if (const uint32_t unknown = (uint32_t)flags2 & ~(uint32_t)DOPF_F2_GEN_ENERGY_BUDGET)
+        return fail(nullptr, DOPF_E_INVALID, "dopf_create_ex: flags2 has the unknown bit %u (the second word knows DOPF_F2_GEN_ENERGY_BUDGET = 1)",
+                    unknown & (~unknown + 1u));
     if (int rc = validate(p, q)) return rc;
     int dev = 0;
     if (int rc = pick_device(q, &dev)) return rc;
@@ -884,6 +938,7 @@ int dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q)
     if (!c) return fail(nullptr, DOPF_E_NOMEM, "out of host memory");
     c->device = dev;
     c->q = *q;
+    c->flags2 = flags2;
     DeviceGuard guard(dev);
     if (const int rc = build_context(c, p)) {
         keep_error(c);
@@ -1510,7 +1565,7 @@ int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const doubl
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->gen_prof_h = pr;
-    if (c->q.flags & DOPF_F_GEN_RAMP) c->gen_avail_h.assign(profiles, profiles + need);      // (what dopf_set_generator_ramp checks its anchors against)
+    if ((c->q.flags & DOPF_F_GEN_RAMP) || (c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET)) c->gen_avail_h.assign(profiles, profiles + need);      // (what dopf_set_generator_ramp checks its anchors against, dopf_set_generator_energy_budget its minima)
     return DOPF_OK;
 }
 
@@ -1578,6 +1633,29 @@ int dopf_set_generator_ramp(dopf_ctx *c, const double *up, const double *down, c
     return DOPF_OK;
 }
 
+int dopf_set_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_generator_energy_budget(c, e_min, e_max)) return rc;
+    const size_t G = (size_t)c->v.G;
+    if (G == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<double> h(2 * G);
+    for (size_t i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        h[i] = e_min ? e_min[a] + 0.0 : 0.0;
+        h[G + i] = e_max ? e_max[a] + 0.0 : INFINITY;
+    }
+    // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again). The
+    // state stays; the stop test starts over, as after dopf_set_generator_ramp
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(gen_budget_min(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    launch_reset_status(c->v, c->main);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = read_status(c)) return rc;          // (synchronises: h may go)
+    std::copy(h.begin(), h.end(), c->gen_budget_h.begin() + G);
+    return DOPF_OK;
+}
+
 // scratch of dopf_set_demand / dopf_roll_horizon, allocated at the first call (freed with the context's other arrays): the moved
 // per-timestep vectors (demand, 2 x lambda, 8 line vectors, with DOPF_F_LINE_RATING the rating table) | the caller's demand tail (up to N*(T-1)) | the new initial levels (S)
 static int roll_scratch(dopf_ctx *c, double **out)
@@ -1630,6 +1708,9 @@ int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
     if (c->q.flags & DOPF_F_GEN_RAMP)
         return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: not on a context with DOPF_F_GEN_RAMP (the anchor p_prev of the next window is "
                                            "the host's to set: build that window's context)");
+    if (c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET)
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: not on a context with DOPF_F2_GEN_ENERGY_BUDGET (what is left of a budget after "
+                                           "k steps is the host's to work out: build that window's context)");
     if (k < 1 || k >= T) return fail(c, DOPF_E_INVALID, "dopf_roll_horizon: k = %d outside [1, T - 1 = %d]", k, T - 1);
     if (int rc = roll_checks(c, "dopf_roll_horizon", "demand_tail", demand_tail, (size_t)N * k, N, T - k)) return rc;
     if (S > 0 && !(c->q.flags & DOPF_F_STO_INITIAL_LEVEL))

@@ -535,6 +535,11 @@ void dopf_multi_destroy(dopf_multi *m)
 
 int dopf_multi_create(dopf_multi **out, const dopf_problem *p, const dopf_params *q, int32_t n_gpus, const int32_t *devices)
 {
+    return dopf_multi_create_ex(out, p, q, n_gpus, devices, 0);
+}
+
+int dopf_multi_create_ex(dopf_multi **out, const dopf_problem *p, const dopf_params *q, int32_t n_gpus, const int32_t *devices, int32_t flags2)
+{
     if (!out || !p || !q || n_gpus < 1) return mfail(nullptr, DOPF_E_INVALID, "bad argument");
     *out = nullptr;
     const bool host_sum = (q->flags & DOPF_F_COMM_HOST) != 0;
@@ -579,7 +584,7 @@ int dopf_multi_create(dopf_multi **out, const dopf_problem *p, const dopf_params
         qi.device = dev[i];
         qi.stream = nullptr;
         qi.n_agents_global = q->n_agents_global > 0 ? q->n_agents_global : p->G + p->S;
-        const int rc = dopf_create(&m->ctx[i], &pi, &qi);
+        const int rc = dopf_create_ex(&m->ctx[i], &pi, &qi, flags2);
         if (rc) {
             snprintf(g_multi_err, 512, "shard %d: %s", i, dopf_last_error(nullptr));
             dopf_multi_destroy(m);
@@ -749,6 +754,12 @@ int dopf_multi_set_generator_ramp(dopf_multi *m, const double *ramp_up, const do
 {
     return multi_set(m, check_generator_ramp, dopf_set_generator_ramp,
                      [&](auto f, int i) { return f(m->ctx[i], from(ramp_up, m->g0[i]), from(ramp_down, m->g0[i]), from(p_prev, m->g0[i])); });
+}
+
+int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, const double *e_max)
+{
+    return multi_set(m, check_generator_energy_budget, dopf_set_generator_energy_budget,
+                     [&](auto f, int i) { return f(m->ctx[i], from(e_min, m->g0[i]), from(e_max, m->g0[i])); });
 }
 
 int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double *E)

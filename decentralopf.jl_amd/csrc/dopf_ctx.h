@@ -40,6 +40,9 @@ struct dopf_ctx {
     int gen_avail_cap = 0;                 //     profiles it has room for
     std::vector<double> gen_ramp_h;        // DOPF_F_GEN_RAMP: gen_pmax | ramp_up | ramp_down | p_prev (NaN: none) as on the device (sorted order), and
     std::vector<double> gen_avail_h;       //     with DOPF_F_GEN_AVAILABILITY the profile table: what the two setters check the anchors against
+    int32_t flags2 = 0;                    // the second flag word (DOPF_F2_*, dopf_create_ex)
+    std::vector<double> gen_budget_h;      // DOPF_F2_GEN_ENERGY_BUDGET: gen_pmax | e_min | e_max as on the device (sorted order); gen_avail_h is
+                                           //     kept for these contexts too: what the two setters check e_min <= sum_t cap against
     dopf::Status host_st{};
     dopf::Status *host_pin = nullptr;       // page-locked landing area of the status read-back (a pageable target is staged: slower)
     unsigned long long solver_fail_seen = 0;   // failures already reported through DOPF_E_SOLVER
@@ -65,6 +68,8 @@ int check_line_rating(dopf_ctx *c, const double *rating);   // those of dopf_set
 int check_generator_quadratic_cost(dopf_ctx *c, const double *c2);   // those of dopf_set_generator_quadratic_cost (flag, finite, >= 0)
 // those of dopf_set_generator_ramp (flag, no NaN, ramps >= 0 and both or neither, p_prev in [0, gen_pmax], the anchors under the caps)
 int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev);
+// those of dopf_set_generator_energy_budget (flag, no NaN, 0 <= e_min <= e_max, e_min finite and <= sum_t cap)
+int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max);
 void launch_demote_full_rows(const DevView &v, hipStream_t s);   // gen_state 1 -> 2 (the caps changed)
 // dopf_comm.hip
 int check_one_runtime(dopf_ctx *c);           // DOPF_E_UNSUPPORTED when two HIP runtimes are mapped into the process

@@ -25,6 +25,7 @@
 #include "../../include/dopf.h"
 #include "dopf_plan.h"
 #include "ramp_dp.h"
+#include "budget_root.h"
 
 namespace dopf {
 
@@ -217,6 +218,12 @@ __host__ __device__ inline const double *gen_ramp_up(const DevView &v) { return 
 __host__ __device__ inline const double *gen_ramp_down(const DevView &v) { return v.gen_pmax + 2 * (size_t)v.G; }
 __host__ __device__ inline const double *gen_ramp_prev(const DevView &v) { return v.gen_pmax + 3 * (size_t)v.G; }
 __host__ __device__ inline double *gen_ramp_scratch(const DevView &v) { return const_cast<double *>(v.gen_pmax) + 4 * (size_t)v.G; }
+// ... with DOPF_F2_GEN_ENERGY_BUDGET (never together with the ramps: plan_chain) behind the capacities, G doubles each in sorted order,
+// e_min (0 until dopf_set_generator_energy_budget) | e_max (+inf until then). k_gen_budget keeps nothing else: a searched row forms its
+// steps again from P, which it overwrites last (gen_budget.h)
+inline size_t gen_budget_doubles(int G) { return 3 * (size_t)G; }
+__host__ __device__ inline const double *gen_budget_min(const DevView &v) { return v.gen_pmax + v.G; }
+__host__ __device__ inline const double *gen_budget_max(const DevView &v) { return v.gen_pmax + 2 * (size_t)v.G; }
 
 // The gen_state block (v.gen_state; gen_state_ints). DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
 // gen_pmax[g] for k = -1. gen_state has room for both behind its G row states: the G profile indices (sorted order, -1 until
@@ -338,6 +345,7 @@ inline int agent_blocks(const DevView &v) { return v.nStoItems + (v.genBlocks > 
 void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_gen_ramp(const DevView &v, const Plan &p, hipStream_t s);       // gen_ramp.h: the generators of a DOPF_F_GEN_RAMP context
 void launch_gen_ramp_net(const DevView &v, const Plan &p, hipStream_t s);   // gen_ramp_net.h: ... on a network (DOPF_F_GEN_RAMP_NETWORK)
+void launch_gen_budget(const DevView &v, const Plan &p, hipStream_t s);     // gen_budget.h: the generators of a DOPF_F2_GEN_ENERGY_BUDGET context
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s);

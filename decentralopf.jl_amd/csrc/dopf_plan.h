@@ -60,6 +60,8 @@ struct Plan {
     bool genRamp;                   // DOPF_F_GEN_RAMP (copper plates): the generators run in k_gen_ramp<AV, QC> — the chain of genQuad (no pair, skip or
                                     // fused generator blocks, no one-launch tail), with the exact projection onto {box, ramps} for the rows that need it
     bool genRampNet;                // ... on a network (DOPF_F_GEN_RAMP_NETWORK, L > 0): k_gen_ramp_net<AV, QC>, the chain a network runs under DOPF_F_NO_FUSE
+    bool genBudget;                 // DOPF_F2_GEN_ENERGY_BUDGET (the second flag word): k_gen_budget<LINES, AV, QC> (gen_budget.h) on the same chain, copper
+                                    // plates and networks; refused together with genRamp
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those
@@ -171,8 +173,8 @@ inline void place_items(const Shape &sh, int genItem, int stoItem, bool fuseNet,
 
 // The launch chain of a context, decided once: make_layout builds the items and rows from it, the launch functions
 // switch on it. No HIP call, no device allocation. cus: the device's CUs (0: unknown). dopf_create has refused T > 512 without
-// DOPF_F_LONG_HORIZON and L > 2048 without DOPF_F_WIDE_NETWORK.
-inline Plan plan_chain(const Shape &sh, unsigned flags, int cus)
+// DOPF_F_LONG_HORIZON and L > 2048 without DOPF_F_WIDE_NETWORK. flags2: the second flag word (DOPF_F2_*, dopf_create_ex).
+inline Plan plan_chain(const Shape &sh, unsigned flags, int cus, unsigned flags2 = 0)
 {
     const int N = sh.N, L = sh.L, T = sh.T, G = sh.G, S = sh.S;
     Plan p{};
@@ -211,8 +213,13 @@ inline Plan plan_chain(const Shape &sh, unsigned flags, int cus)
         p.refusal = "ramp limits run on copper plates; on a network they need DOPF_F_GEN_RAMP_NETWORK at dopf_create";
     if ((flags & DOPF_F_GEN_RAMP_NETWORK) && !(flags & DOPF_F_GEN_RAMP))
         p.refusal = "DOPF_F_GEN_RAMP_NETWORK means nothing without DOPF_F_GEN_RAMP";
-    if (p.genQuad || p.genRamp) flags |= DOPF_F_NO_FUSE;
-    p.genTT2 = (!p.genQuad && !p.genRamp && L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
+    // DOPF_F2_GEN_ENERGY_BUDGET: the same chain again with k_gen_budget as the generators' launch, on every shape. With ramps a row
+    // would carry two constraints that couple its timesteps (the ramp programme inside the multiplier search): refused
+    p.genBudget = G > 0 && (flags2 & DOPF_F2_GEN_ENERGY_BUDGET);
+    if ((flags2 & DOPF_F2_GEN_ENERGY_BUDGET) && (flags & DOPF_F_GEN_RAMP))
+        p.refusal = "DOPF_F2_GEN_ENERGY_BUDGET does not combine with DOPF_F_GEN_RAMP: one constraint that couples a generator's timesteps per context";
+    if (p.genQuad || p.genRamp || p.genBudget) flags |= DOPF_F_NO_FUSE;
+    p.genTT2 = (!p.genQuad && !p.genRamp && !p.genBudget && L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
     p.fuseAgents = p.genTT2 > 0 && p.genTT2 <= 256 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS));
     if (p.fuseAgents) {
         // one launch for all agents pays while its fixed cost matters and every storage block is resident from

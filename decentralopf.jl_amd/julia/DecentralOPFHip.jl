@@ -134,6 +134,7 @@ const DOPF_F_LINE_RATING = 536870912  # include/dopf.h
 const DOPF_F_GEN_QUADRATIC_COST = 1073741824  # include/dopf.h
 const DOPF_F_GEN_RAMP = 32  # include/dopf.h
 const DOPF_F_GEN_RAMP_NETWORK = typemin(Int32)  # include/dopf.h: 2147483648, bit 31 — the sign bit of the Cint flag word, and its last
+const DOPF_F2_GEN_ENERGY_BUDGET = 1  # include/dopf.h: the second flag word (the `flags2` keyword; dopf_create_ex)
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -155,10 +156,12 @@ efficiencies below 1 (see `set_efficiency!`; the reference's `Storage` type, use
 `flags = DOPF_F_STO_EFFICIENCY`, line limits per timestep (see `set_line_rating!`) `flags = DOPF_F_LINE_RATING`, and quadratic
 generator cost curves (see `set_quadratic_cost!`) `flags = DOPF_F_GEN_QUADRATIC_COST`; generator ramp limits (see `set_ramp!`) `flags = DOPF_F_GEN_RAMP` — on a case
 with lines the constructor adds `DOPF_F_GEN_RAMP_NETWORK`, the library's opt-in for the network step's knot scratch. Flags combine with `|`.
+`flags2` is the second flag word (`dopf_params.flags` is full): generator energy budgets over the window (see `set_energy_budget!`)
+need `flags2 = DOPF_F2_GEN_ENERGY_BUDGET`; a non-zero `flags2` creates the context through `dopf_create_ex` / `dopf_multi_create_ex`.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
-              w_flow::Float64=10.0, w_prox::Float64=1.0, eps::Float64=1e-3, mask_thr::Float64=1e-2, flags::Int=0)
+              w_flow::Float64=10.0, w_prox::Float64=1.0, eps::Float64=1e-3, mask_thr::Float64=1e-2, flags::Int=0, flags2::Int=0)
     N, L, T = length(nodes), length(lines), length(nodes[1].demand)
     G, S = length(generators), length(storages)
     if (flags & DOPF_F_GEN_RAMP) != 0 && L > 0
@@ -183,11 +186,16 @@ function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}
                             pointer(sto_emax), pointer(sto_node)))
         par = Ref(CParams(gamma, w_flow, w_prox, eps, mask_thr, max_iters, 0, device, flags, C_NULL))
         if n_gpus == 1
-            rc = ccall((:dopf_create, DOPF_LIB), Cint, (Ref{Ptr{Cvoid}}, Ref{CProblem}, Ref{CParams}), ctx, prob, par)
+            rc = flags2 == 0 ?
+                ccall((:dopf_create, DOPF_LIB), Cint, (Ref{Ptr{Cvoid}}, Ref{CProblem}, Ref{CParams}), ctx, prob, par) :
+                ccall((:dopf_create_ex, DOPF_LIB), Cint, (Ref{Ptr{Cvoid}}, Ref{CProblem}, Ref{CParams}, Cint), ctx, prob, par, flags2)
             dopf_check(rc, Ptr{Cvoid}(C_NULL))       # the library copies every input before returning
         else
-            rc = ccall((:dopf_multi_create, DOPF_LIB), Cint, (Ref{Ptr{Cvoid}}, Ref{CProblem}, Ref{CParams}, Cint, Ptr{Cint}),
-                       multi, prob, par, n_gpus, C_NULL)
+            rc = flags2 == 0 ?
+                ccall((:dopf_multi_create, DOPF_LIB), Cint, (Ref{Ptr{Cvoid}}, Ref{CProblem}, Ref{CParams}, Cint, Ptr{Cint}),
+                      multi, prob, par, n_gpus, C_NULL) :
+                ccall((:dopf_multi_create_ex, DOPF_LIB), Cint, (Ref{Ptr{Cvoid}}, Ref{CProblem}, Ref{CParams}, Cint, Ptr{Cint}, Cint),
+                      multi, prob, par, n_gpus, C_NULL, flags2)
             dopf_check_multi(rc, Ptr{Cvoid}(C_NULL))
             ctx[] = ccall((:dopf_multi_ctx, DOPF_LIB), Ptr{Cvoid}, (Ptr{Cvoid}, Cint), multi[], 0)   # replicated state: shard 0
         end
@@ -357,6 +365,33 @@ function set_ramp!(admm::ADMM, ramp_up::Union{Nothing, Vector{Float64}}, ramp_do
         else
             dopf_check(ccall((:dopf_set_generator_ramp, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
                              admm.ctx, pu, pd, pp), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    set_energy_budget!(admm, e_min, e_max)
+
+The energy budget of each generator over the window (`e_min[g] >= 0` finite, `e_max[g] >= e_min[g]`, `Inf` = no limit, in the order
+of `generators`; `nothing` = all 0 / all `Inf`, each on its own): `e_min <= sum_t P[g,t] <= e_max` — a reservoir's water, a minimum
+take, a fuel or emission cap. The reference's generators have no such row; the ADMM must have been created with
+`flags2 = DOPF_F2_GEN_ENERGY_BUDGET`. The state and the iteration counter stay; takes effect at the next iteration.
+"""
+function set_energy_budget!(admm::ADMM, e_min::Union{Nothing, Vector{Float64}}, e_max::Union{Nothing, Vector{Float64}})
+    G = length(admm.generators)
+    for a in (e_min, e_max)
+        a === nothing || length(a) == G || error("set_energy_budget!: expected $G values, got $(length(a))")
+    end
+    plo = e_min === nothing ? Ptr{Cdouble}(C_NULL) : pointer(e_min)
+    phi = e_max === nothing ? Ptr{Cdouble}(C_NULL) : pointer(e_max)
+    GC.@preserve e_min e_max begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_generator_energy_budget, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                                   admm.multi, plo, phi), admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_generator_energy_budget, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}),
+                             admm.ctx, plo, phi), admm.ctx)
         end
     end
     return admm

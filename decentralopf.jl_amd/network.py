@@ -21,6 +21,8 @@ Generator.quadratic_costs is not in the reference either (one constant marginal_
 c2 >= 0, the cost of output P is marginal_costs * P + c2 * P^2 / 2 — a polynomial cost curve (DOPF_F_GEN_QUADRATIC_COST).
 Generator.ramp_up / ramp_down are not in the reference either (its generators move freely between steps, src/optimization/subproblems.jl:26-40):
 -ramp_down <= P[t] - P[t-1] <= ramp_up, the limit on how fast a unit's output changes (DOPF_F_GEN_RAMP; on a case with lines the engines add DOPF_F_GEN_RAMP_NETWORK).
+Generator.energy_min / energy_max are not in the reference either: energy_min <= sum_t P[t] <= energy_max, the energy a unit delivers
+over the window — a reservoir's water, a minimum take, a fuel or emission cap (DOPF_F2_GEN_ENERGY_BUDGET, the second flag word).
 """
 from __future__ import annotations
 
@@ -48,6 +50,8 @@ class Generator:
     quadratic_costs: float = 0.0                        # c2 >= 0: the cost is marginal_costs * P + c2 * P^2 / 2 (not in the reference)
     ramp_up: float = float("inf")                       # >= 0: P[t] - P[t-1] <= ramp_up; inf = no limit (not in the reference)
     ramp_down: float = float("inf")                     # >= 0: P[t-1] - P[t] <= ramp_down; inf = no limit (not in the reference)
+    energy_min: float = 0.0                             # >= 0, finite: sum_t P[t] >= energy_min (not in the reference)
+    energy_max: float = float("inf")                    # >= energy_min: sum_t P[t] <= energy_max; inf = no limit (not in the reference)
 
 
 @dataclass(eq=False)
@@ -142,6 +146,7 @@ class PackedProblem:
     line_rating: Optional[np.ndarray] = None    # (L, T) Line.rating (max_capacity where a line has none); None = no line has one
     gen_c2: Optional[np.ndarray] = None         # (G,) Generator.quadratic_costs; None = all 0
     gen_ramp: Optional[tuple] = None            # ((G,), (G,)) Generator.ramp_up, ramp_down; None = all inf
+    gen_budget: Optional[tuple] = None          # ((G,), (G,)) Generator.energy_min, energy_max; None = all (0, inf)
 
     @property
     def G(self):
@@ -174,7 +179,20 @@ class PackedProblem:
             kw["gen_c2"] = self.quadratic_cost()
         if self.has_ramp():      # (engines then run with F_GEN_RAMP)
             kw["gen_ramp"] = self.ramp()
+        if self.has_budget():      # (engines then run with F2_GEN_ENERGY_BUDGET, through dopf_create_ex)
+            kw["gen_budget"] = self.budget()
         return kw
+
+    def budget(self):
+        """(energy_min, energy_max), float64 (G,) each, the defaults filled in: all 0, all inf."""
+        if self.gen_budget is None:
+            return np.zeros(self.G), np.full(self.G, np.inf)
+        return tuple(np.asarray(b, dtype=np.float64) for b in self.gen_budget)
+
+    def has_budget(self) -> bool:
+        """Some generator has an energy budget (a shard: some generator of the whole problem, so that every rank runs with the flag)."""
+        lo, hi = self.budget()
+        return bool(self.meta.get("budget")) or bool(np.any(lo != 0.0) or np.any(hi != np.inf))
 
     def ramp(self):
         """(ramp_up, ramp_down), float64 (G,) each, the default filled in: all inf."""
@@ -241,7 +259,8 @@ class PackedProblem:
             sto_mc=self.sto_mc[s0:s1], sto_pmax=self.sto_pmax[s0:s1], sto_emax=self.sto_emax[s0:s1],
             sto_node=self.sto_node[s0:s1],
             meta=dict(self.meta, rank=rank, world=world, gen_range=(g0, g1), sto_range=(s0, s1),
-                      n_agents_global=self.G + self.S, quadratic_cost=self.has_quadratic_cost(), ramp=self.has_ramp()),
+                      n_agents_global=self.G + self.S, quadratic_cost=self.has_quadratic_cost(), ramp=self.has_ramp(),
+                      budget=self.has_budget()),
             sto_e0=None if self.sto_e0 is None else self.sto_e0[s0:s1],
             sto_end_lo=None if self.sto_end_lo is None else self.sto_end_lo[s0:s1],
             sto_end_hi=None if self.sto_end_hi is None else self.sto_end_hi[s0:s1],
@@ -251,7 +270,8 @@ class PackedProblem:
             sto_eta_d=None if self.sto_eta_d is None else self.sto_eta_d[s0:s1],
             line_rating=self.line_rating,
             gen_c2=None if self.gen_c2 is None else self.gen_c2[g0:g1],
-            gen_ramp=None if self.gen_ramp is None else tuple(np.asarray(r)[g0:g1] for r in self.gen_ramp))
+            gen_ramp=None if self.gen_ramp is None else tuple(np.asarray(r)[g0:g1] for r in self.gen_ramp),
+            gen_budget=None if self.gen_budget is None else tuple(np.asarray(b)[g0:g1] for b in self.gen_budget))
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -287,6 +307,9 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
     ramp = (f64(g.ramp_up for g in generators), f64(g.ramp_down for g in generators))
     if any(np.any(np.isnan(r)) or np.any(r < 0.0) for r in ramp):
         raise ValueError("generator ramp_up / ramp_down must be >= 0 (inf: no limit)")
+    budget = (f64(g.energy_min for g in generators), f64(g.energy_max for g in generators))
+    if not np.all(np.isfinite(budget[0])) or np.any(budget[0] < 0.0) or np.any(np.isnan(budget[1])) or np.any(budget[1] < budget[0]):
+        raise ValueError("generator energy_min must be finite and >= 0, energy_max >= energy_min (inf: no limit)")
     # line ratings: a table only when some line has one (the others keep max_capacity in every timestep)
     rating = None
     if any(l.rating is not None for l in lines):
@@ -319,4 +342,5 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         sto_eta_d=f64(s.discharge_efficiency for s in storages),
         line_rating=rating,
         gen_c2=c2,
-        gen_ramp=ramp)
+        gen_ramp=ramp,
+        gen_budget=budget)

@@ -135,6 +135,12 @@ class ShardedADMM:
         sums move). Needs F_GEN_RAMP in the params; every rank calls it between the same two steps."""
         self.engine.set_ramp(self._mine(up, "gen"), self._mine(down, "gen"), self._mine(prev, "gen"))
 
+    def set_energy_budget(self, e_min=None, e_max=None) -> None:
+        """All generators' energy budgets over the window (problem.G values each, global order; e_min None = all 0, e_max None = all
+        inf): this rank sets its slice (dopf_set_generator_energy_budget; the constraint is local to the rank's agents, no sums
+        move). Needs F2_GEN_ENERGY_BUDGET in the second flag word; every rank calls it between the same two steps."""
+        self.engine.set_energy_budget(self._mine(e_min, "gen"), self._mine(e_max, "gen"))
+
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
         max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs

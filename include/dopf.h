@@ -227,7 +227,29 @@ typedef struct dopf_params {
                                   * kernel runs, the same bits). dopf_roll_horizon goes on refusing every ramp context, dopf_central_solve,
                                   * _ex and _lossy ignore the flag. This is bit 31, the LAST bit of dopf_params.flags (an int32_t whose
                                   * size the ABI pins): the next create-time option needs a second flag word, for example in a
-                                  * dopf_create2. */
+                                  * dopf_create2. (That word exists now: the flags2 argument of dopf_create_ex below, whose options are
+                                  * named DOPF_F2_*.) */
+/* ---- the second flag word: the flags2 argument of dopf_create_ex / dopf_multi_create_ex (dopf_params keeps its size). Its options are
+ * named DOPF_F2_*; a bit that is none of them is DOPF_E_INVALID. */
+#define DOPF_F2_GEN_ENERGY_BUDGET 1 /* generators have energy budgets over the window: the context keeps e_min[g] (0 until
+                                  * dopf_set_generator_energy_budget) and e_max[g] (+inf until then). The generator's step keeps its
+                                  * objective and its box (cap[g,t] under DOPF_F_GEN_AVAILABILITY, the c2 term under
+                                  * DOPF_F_GEN_QUADRATIC_COST) and gains e_min[g] <= sum_t P[g,t] <= e_max[g], one timestep counting 1. With a
+                                  * multiplier nu on that row the step is the one the library takes with gen_mc[g] + nu for gen_mc[g];
+                                  * phi(nu) = sum_t P[g,t](nu) is continuous, piecewise linear and non-increasing, and a row whose step at
+                                  * nu = 0 breaks its budget takes the step at the root of phi(nu) = the broken bound (k_gen_budget,
+                                  * a wave brackets the root and narrows the bracket until phi is linear on it, then solves).
+                                  * A row whose search reaches its cap of evaluations keeps its clamped step for the iteration and is
+                                  * counted: dopf_iterate returns DOPF_E_SOLVER and dopf_solver_failures() grows. Contexts with the flag run
+                                  * their generators in a launch of their own, the chain of DOPF_F_GEN_QUADRATIC_COST contexts (no pair or
+                                  * row-skipping kernels, no launch shared with the storages, no one-launch iteration), on copper plates and
+                                  * networks, DOPF_F_LONG_HORIZON and the wide chain included; with every budget at its default the results
+                                  * are those of the flagless context on that chain, bit for bit. dopf_get_consensus' cost is unchanged (a
+                                  * budget has no price); dopf_get_agent_slacks, dopf_get_agent_penalty and DOPF_F_KEEP_DELTAS see the
+                                  * projected step. Together with DOPF_F_GEN_RAMP the flag is refused (DOPF_E_UNSUPPORTED: two constraints
+                                  * that couple a row's timesteps need the ramp programme inside the multiplier search); dopf_roll_horizon
+                                  * refuses a context with it (what is left of a budget after k steps is the host's arithmetic);
+                                  * dopf_central_solve, _ex and _lossy take no budgets and ignore the bit. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -244,6 +266,9 @@ typedef struct dopf_params {
 void dopf_default_params(dopf_params *q);
 
 int  dopf_create(dopf_ctx **out, const dopf_problem *p, const dopf_params *q);
+/* dopf_create with the second flag word (DOPF_F2_*): dopf_create(out, p, q) is dopf_create_ex(out, p, q, 0). DOPF_E_INVALID, naming
+ * the bit, for a bit of flags2 that is no DOPF_F2_* option. */
+int dopf_create_ex(dopf_ctx **out, const dopf_problem *p, const dopf_params *q, int32_t flags2);
 void dopf_destroy(dopf_ctx *ctx);
 /* Message of the last error on ctx; with ctx == NULL the last dopf_create error (thread-local). */
 const char *dopf_last_error(const dopf_ctx *ctx);
@@ -431,6 +456,18 @@ int dopf_set_generator_quadratic_cost(dopf_ctx *ctx, const double *c2 /* G; NULL
 int dopf_set_generator_ramp(dopf_ctx *ctx, const double *ramp_up /* G; NULL = +inf */, const double *ramp_down /* G; NULL = +inf */,
                             const double *p_prev /* G; NULL = no anchor */);
 
+/* DOPF_F2_GEN_ENERGY_BUDGET: the generators' energy budgets over the window, e_min[G] and e_max[G] in the caller's order of this
+ * context's generators: e_min[g] <= sum_t P[g,t] <= e_max[g]. Either array may be NULL on its own (e_min: all 0, e_max: all +inf, also
+ * the values until the first call). Timing, copies and status as for dopf_set_generator_ramp: callable between any two calls that
+ * iterate, the values are copied before the call returns, in order on the context's stream, into the device arrays the captured
+ * iteration graphs read (the graphs stay valid), and take effect at the next x-update; P, D, C, the duals and the iteration counter
+ * are kept, converged becomes 0. Contexts joined to a communicator or a peer exchange need nothing else (the constraint is local to
+ * the rank's agents). DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID, naming the entry and storing nothing, for a NaN,
+ * e_min < 0, an infinite e_min, e_max < 0, e_min > e_max, or e_min[g] > sum_t cap[g,t] (the stored availability table). In contexts
+ * with this flag dopf_set_generator_availability repeats the last check under its new table. With G == 0 the call returns DOPF_OK
+ * and does nothing. */
+int dopf_set_generator_energy_budget(dopf_ctx *ctx, const double *e_min /* G; NULL = 0 */, const double *e_max /* G; NULL = +inf */);
+
 /* ---- a receding horizon: the window's demand and the window itself change in place -------------------------------
  * Replace nothing in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62). Both need no flag, work
  * on every single-GPU chain, keep the captured iteration graphs valid (they write the arrays the graphs read) and return after
@@ -554,6 +591,9 @@ int dopf_xchg_init(dopf_ctx *ctx, int32_t world, int32_t rank, const void *handl
 typedef struct dopf_multi dopf_multi;
 int  dopf_multi_create(dopf_multi **out, const dopf_problem *p, const dopf_params *q, int32_t n_gpus,
                        const int32_t *devices);
+/* dopf_multi_create with the second flag word, as dopf_create_ex: every shard is created with flags2 */
+int dopf_multi_create_ex(dopf_multi **out, const dopf_problem *p, const dopf_params *q, int32_t n_gpus,
+                         const int32_t *devices, int32_t flags2);
 void dopf_multi_destroy(dopf_multi *m);
 const char *dopf_multi_last_error(const dopf_multi *m);   /* m == NULL: last dopf_multi_create error */
 int  dopf_multi_iterate(dopf_multi *m, int32_t n_iters, int32_t *iters_done, int32_t *converged);
@@ -580,6 +620,9 @@ int dopf_multi_set_generator_quadratic_cost(dopf_multi *m, const double *c2);
 /* dopf_set_generator_ramp for all G generators, arrays in the caller's order (NULL as there): each shard gets its slice; every shard
  * is checked before any value is stored */
 int dopf_multi_set_generator_ramp(dopf_multi *m, const double *ramp_up, const double *ramp_down, const double *p_prev);
+/* dopf_set_generator_energy_budget for all G generators, arrays in the caller's order (NULL as there): each shard gets its slice;
+ * every shard is checked before any value is stored */
+int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, const double *e_max);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);
