@@ -5,7 +5,8 @@ The directory name contains a dot, so it is loaded through ``dopf_pkg.load()`` (
 the module name ``decentralopf_jl_amd``.
 """
 from . import _capi, admm, central, horizon, network, sharded, synth
-from .central import CentralResult, central_reference, central_reference_on_device, solve_central_packed
+from .central import (CentralResult, central_reference, central_reference_coupled_on_device, central_reference_on_device,
+                      solve_central_packed)
 from .admm import ADMM, calculate_iteration, export_results, get_nodal_price, run
 from .sharded import ShardedADMM
 from .horizon import shift_window
@@ -17,4 +18,4 @@ __all__ = ["DopfError", "Engine", "default_params", "hip_api", "Generator", "Lin
            "PackedProblem", "Storage", "calculate_ptdf", "pack", "three_node_case", "_capi",
            "network", "synth", "admm", "sharded", "ADMM", "calculate_iteration",
            "export_results", "get_nodal_price", "run", "ShardedADMM", "central", "CentralResult",
-           "central_reference", "central_reference_on_device", "solve_central_packed", "horizon", "shift_window"]
+           "central_reference", "central_reference_on_device", "central_reference_coupled_on_device", "solve_central_packed", "horizon", "shift_window"]

@@ -172,6 +172,10 @@ class CApi:
             self._sig("central_solve_lossy", C.c_int, [C.POINTER(DopfProblem), C.POINTER(DopfParams)] + [c_double_p] * 5 +
                                                       [C.c_int32, c_double_p, c_int32_p, C.c_double, C.c_int32,
                                                        C.POINTER(DopfCentralResult)] + [c_double_p] * 9)
+            # ... plus line_rating, ramp_up, ramp_down, p_prev, e_min, e_max in front of tol, and ramp_dual, budget_dual at the end
+            self._sig("central_solve_coupled", C.c_int, [C.POINTER(DopfProblem), C.POINTER(DopfParams)] + [c_double_p] * 5 +
+                                                        [C.c_int32, c_double_p, c_int32_p] + [c_double_p] * 6 +
+                                                        [C.c_double, C.c_int32, C.POINTER(DopfCentralResult)] + [c_double_p] * 11)
             self._sig("get_node_results", C.c_int, [ctxp, c_double_p, c_double_p, c_double_p])
             self._sig("last_call_ms", C.c_double, [ctxp])
             # consensus sum across GPUs inside the library (RCCL, loaded on first use)
@@ -1009,15 +1013,15 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     if gen_budget is not None and ((gen_budget[0] is not None and np.any(np.asarray(gen_budget[0], dtype=np.float64) != 0.0)) or
                                    (gen_budget[1] is not None and np.any(np.asarray(gen_budget[1], dtype=np.float64) != np.inf))):
         raise DopfError("dopf_central_solve*: the device LP takes no generator energy budgets (it bounds no generator's sum over the "
-                        "window); use central.solve_central_packed(..., gen_budget=) for a case with a budget")
+                        "window); use central_solve_coupled, or central.solve_central_packed(..., gen_budget=), for a case with a budget")
     if gen_prev is not None or (gen_ramp is not None and any(np.any(np.isfinite(np.asarray(r, dtype=np.float64))) for r in gen_ramp)):
         raise DopfError("dopf_central_solve*: the device LP takes no generator ramp limits (it lets every generator move freely); use "
-                        "central.solve_central_packed(..., gen_ramp=) for a case with ramps")
+                        "central_solve_coupled, or central.solve_central_packed(..., gen_ramp=), for a case with ramps")
     if gen_c2 is not None and np.any(np.asarray(gen_c2, dtype=np.float64) != 0.0):
         raise DopfError("dopf_central_solve*: the device LP takes no quadratic generator costs (it solves with gen_mc alone)")
     if line_rating is not None and np.any(np.asarray(line_rating, dtype=np.float64).reshape(L, T) != _f64(f_max, L)[:, None]):
         raise DopfError("dopf_central_solve*: the device LP takes no line ratings (it solves with f_max in every timestep); use "
-                        "central.solve_central_packed(..., line_rating=) for a case with ratings")
+                        "central_solve_coupled, or central.solve_central_packed(..., line_rating=), for a case with ratings")
     prob, keep, G, S = _problem(N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax, sto_node)
     q = params if params is not None else default_params()
     res = DopfCentralResult()
@@ -1049,3 +1053,50 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
                 P=P.reshape(G, T), D=D.reshape(S, T), C=Cc.reshape(S, T), E=E.reshape(S, T), system_price=lam,
                 nodal_price=nodal.reshape(T, N).T.copy(), line_utilization=flow.reshape(T, L).T.copy(),
                 flow_upper_dual=fu.reshape(T, L).T.copy(), flow_lower_dual=fl.reshape(T, L).T.copy())
+
+
+def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
+                          sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
+                          sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
+                          line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None) -> dict:
+    """dopf_central_solve_coupled: central_solve's LP with the constraints that couple a generator's timesteps and with per-timestep
+    line limits. Arguments as Engine (PackedProblem.engine_kwargs()); beyond central_solve's:
+    line_rating (L, T): the limits of the flow rows, as Engine takes them (None: f_max in every timestep).
+    gen_ramp = (ramp_up, ramp_down) (G each, inf = no limit), gen_prev (G outputs of the step before the window; None: no anchor).
+    gen_budget = (e_min, e_max) (G each; either may be None: 0, inf).
+    The call is always dopf_central_solve_coupled (with none of the four given it returns dopf_central_solve_lossy's bits); it checks
+    the inputs as the three setters do (DopfError with the entry's name). gen_c2: the device solve is an LP; a non-zero coefficient
+    raises DopfError. Returns central_solve's dict plus ramp_dual (G, T) and budget_dual (G,): d objective / d right-hand side of the
+    ramp row between t - 1 and t (t = 0: the anchor's row) and of the budget row — negative where the row's upper end binds, positive
+    where its lower end does."""
+    N, L, T = int(N), int(L), int(T)
+    if gen_c2 is not None and np.any(np.asarray(gen_c2, dtype=np.float64) != 0.0):
+        raise DopfError("dopf_central_solve_coupled: the device LP takes no quadratic generator costs (it solves with gen_mc alone)")
+    prob, keep, G, S = _problem(N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax, sto_node)
+    q = params if params is not None else default_params()
+    res = DopfCentralResult()
+    P, D, Cc, E = np.zeros(G * T), np.zeros(S * T), np.zeros(S * T), np.zeros(S * T)
+    lam, nodal, flow = np.zeros(T), np.zeros(N * T), np.zeros(L * T)
+    fu, fl = np.zeros(L * T), np.zeros(L * T)
+    rdual, bdual = np.zeros(G * T), np.zeros(G)
+    opt = lambda a, n: None if a is None else _f64(a, n)
+    e0, lo, hi = opt(sto_e0, S), opt(sto_end_lo, S), opt(sto_end_hi, S)
+    ec, ed = (None, None) if sto_eta is None else (_f64(sto_eta[0], S), _f64(sto_eta[1], S))
+    K, prof, of = _availability_arrays(gen_avail, gen_avail_of, T, G)
+    rating = None if line_rating is None else _f64(np.asarray(line_rating, dtype=np.float64).reshape(L, T).T, L * T)      # [l + L*t]
+    up, down = (None, None) if gen_ramp is None else (opt(gen_ramp[0], G), opt(gen_ramp[1], G))
+    prev = opt(gen_prev, G)
+    emin, emax = (None, None) if gen_budget is None else (opt(gen_budget[0], G), opt(gen_budget[1], G))
+    rc = api.central_solve_coupled(C.byref(prob), C.byref(q), _dp(e0), _dp(lo), _dp(hi), _dp(ec), _dp(ed), K, _dp(prof),
+                                   None if of is None else of.ctypes.data_as(c_int32_p), _dp(rating), _dp(up), _dp(down), _dp(prev),
+                                   _dp(emin), _dp(emax), float(tol), int(max_iters), C.byref(res), _dp(P), _dp(D), _dp(Cc), _dp(E),
+                                   _dp(lam), _dp(nodal), _dp(flow), _dp(fu), _dp(fl), _dp(rdual), _dp(bdual))
+    if rc != 0:
+        msg = api.last_error(None)
+        raise DopfError(f"dopf_central_solve_coupled failed ({rc}): {msg.decode() if msg else ''}")
+    return dict(objective=res.objective, dual_objective=res.dual_objective, primal_infeasibility=res.primal_infeasibility,
+                gap=res.gap, iterations=res.iterations, converged=bool(res.converged),
+                P=P.reshape(G, T), D=D.reshape(S, T), C=Cc.reshape(S, T), E=E.reshape(S, T), system_price=lam,
+                nodal_price=nodal.reshape(T, N).T.copy(), line_utilization=flow.reshape(T, L).T.copy(),
+                flow_upper_dual=fu.reshape(T, L).T.copy(), flow_lower_dual=fl.reshape(T, L).T.copy(),
+                ramp_dual=rdual.reshape(G, T), budget_dual=bdual)

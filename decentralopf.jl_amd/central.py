@@ -234,7 +234,8 @@ def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Gene
                          "costs and would solve with the marginal costs alone")
     if pp.has_ramp():
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no generator ramp limits "
-                         "and would let every generator move freely; use central_reference for a case with Generator.ramp_up / ramp_down")
+                         "and would let every generator move freely; use central_reference_coupled_on_device, or central_reference, "
+                         "for a case with Generator.ramp_up / ramp_down")
     if pp.has_budget():
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no generator energy budgets "
                          "and would bound no generator's sum over the window; use central_reference for a case with Generator.energy_min / energy_max")
@@ -264,3 +265,41 @@ def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Gene
     return CentralResult(objective=r["objective"], generation=r["P"], discharge=r["D"], charge=r["C"], level=r["E"], injection=inj,
                          line_utilization=r["line_utilization"], system_price=r["system_price"], flow_upper_dual=r["flow_upper_dual"],
                          flow_lower_dual=r["flow_lower_dual"], nodal_price=r["nodal_price"])
+
+
+def central_reference_coupled_on_device(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
+                                        lines: Sequence[Line], *, tol: float = 1e-9, max_iters: int = 200000, device: int = -1,
+                                        initial_level=None, terminal_level=None, efficiency=None, gen_ramp=None, gen_prev=None,
+                                        gen_budget=None, line_rating=None, duals: bool = False):
+    """central_reference_on_device for a case whose elements carry ramp limits (Generator.ramp_up / ramp_down), energy budgets
+    (Generator.energy_min / energy_max) or line ratings (Line.rating): the LP central_reference solves on the host, solved on the GPU
+    by dopf_central_solve_coupled (csrc/kernels_central.hip, kc_gen_rows). The storages' efficiencies are always part of it. gen_ramp =
+    (up, down), gen_budget = (e_min, e_max) and line_rating (L, T) override the elements' own; gen_prev (G,) are the outputs of the step
+    before the window, the anchor of the ramp rows at t = 0 (None: no anchor — the elements carry none). Quadratic costs are refused:
+    the device solve is an LP. Returns a CentralResult; with duals=True a pair of it and dict(ramp_dual (G, T), budget_dual (G,)),
+    d objective / d right-hand side of the ramp and budget rows (budget_dual: minus the water value of a capped generator)."""
+    from . import _capi
+    pp = pack(nodes, generators, storages, lines)
+    if pp.has_quadratic_cost():
+        raise ValueError("central_reference_coupled_on_device: the device LP (dopf_central_solve_coupled) takes no quadratic generator "
+                         "costs and would solve with the marginal costs alone")
+    kw = pp.engine_kwargs()
+    kw["sto_eta"] = _efficiencies(pp, efficiency)
+    if initial_level is not None:
+        kw["sto_e0"] = np.asarray(initial_level, dtype=np.float64).reshape(pp.S)
+    if terminal_level is not None:
+        kw["sto_end_lo"] = np.asarray(terminal_level[0], dtype=np.float64).reshape(pp.S)
+        kw["sto_end_hi"] = np.asarray(terminal_level[1], dtype=np.float64).reshape(pp.S)
+    for key, val in (("gen_ramp", gen_ramp), ("gen_prev", gen_prev), ("gen_budget", gen_budget), ("line_rating", line_rating)):
+        if val is not None:
+            kw[key] = val
+    r = _capi.central_solve_coupled(_capi.hip_api(), tol=tol, max_iters=max_iters, params=_capi.default_params(device=device), **kw)
+    if not r["converged"]:
+        raise RuntimeError(f"central LP on the device: gap {r['gap']:.2e} after {r['iterations']} iterations (infeasible case?)")
+    inj = -np.asarray(pp.demand, dtype=np.float64).copy()
+    np.add.at(inj, pp.gen_node, r["P"])
+    np.add.at(inj, pp.sto_node, r["D"] - r["C"])
+    out = CentralResult(objective=r["objective"], generation=r["P"], discharge=r["D"], charge=r["C"], level=r["E"], injection=inj,
+                        line_utilization=r["line_utilization"], system_price=r["system_price"], flow_upper_dual=r["flow_upper_dual"],
+                        flow_lower_dual=r["flow_lower_dual"], nodal_price=r["nodal_price"])
+    return (out, dict(ramp_dual=r["ramp_dual"], budget_dual=r["budget_dual"])) if duals else out

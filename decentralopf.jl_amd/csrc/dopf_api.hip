@@ -123,21 +123,28 @@ static int ramp_anchor_fits(dopf_ctx *c, const char *entry, int g, double pm, do
 int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev)
 {
     if (int rc = NEEDS_FLAG(c, "generator ramp limits need", DOPF_F_GEN_RAMP)) return rc;
-    if (!up != !down) return fail(c, DOPF_E_INVALID, "dopf_set_generator_ramp: ramp_up and ramp_down must both be given or both be NULL");
+    return check_generator_ramp_values(c, "dopf_set_generator_ramp", c->gen_ramp_h.data(), c->gen_avail_h.data(), up, down, prev);
+}
+
+// ... without the flag: the values alone, for `entry` (the name the messages carry). pmax: the capacities in sorted order; table:
+// the availability profiles [t + T*k] that the context's profile indices (gen_prof_h; none: every generator at its capacity) refer to
+int check_generator_ramp_values(dopf_ctx *c, const char *entry, const double *pmax, const double *table, const double *up, const double *down,
+                                const double *prev)
+{
+    if (!up != !down) return fail(c, DOPF_E_INVALID, "%s: ramp_up and ramp_down must both be given or both be NULL", entry);
     const int G = c->v.G, T = c->v.T;
     for (int i = 0; i < G; ++i) {
         const int a = c->gen_perm[i];
-        const double pm = c->gen_ramp_h[i];
+        const double pm = pmax[i];
         if (up) {
-            if (std::isnan(up[a]) || up[a] < 0.0) return fail(c, DOPF_E_INVALID, "dopf_set_generator_ramp: ramp_up[%d] is %g (>= 0 wanted)", a, up[a]);
-            if (std::isnan(down[a]) || down[a] < 0.0) return fail(c, DOPF_E_INVALID, "dopf_set_generator_ramp: ramp_down[%d] is %g (>= 0 wanted)", a, down[a]);
+            if (std::isnan(up[a]) || up[a] < 0.0) return fail(c, DOPF_E_INVALID, "%s: ramp_up[%d] is %g (>= 0 wanted)", entry, a, up[a]);
+            if (std::isnan(down[a]) || down[a] < 0.0) return fail(c, DOPF_E_INVALID, "%s: ramp_down[%d] is %g (>= 0 wanted)", entry, a, down[a]);
         }
         if (!prev) continue;
         if (!(prev[a] >= 0.0 && prev[a] <= pm))
-            return fail(c, DOPF_E_INVALID, "dopf_set_generator_ramp: p_prev[%d] is %g, outside [0, gen_pmax = %g]", a, prev[a], pm);
+            return fail(c, DOPF_E_INVALID, "%s: p_prev[%d] is %g, outside [0, gen_pmax = %g]", entry, a, prev[a], pm);
         const int k = c->gen_prof_h.empty() ? -1 : c->gen_prof_h[i];
-        if (int rc = ramp_anchor_fits(c, "dopf_set_generator_ramp", a, pm, down ? down[a] : INFINITY, prev[a],
-                                      k >= 0 ? c->gen_avail_h.data() + (size_t)k * T : nullptr)) return rc;
+        if (int rc = ramp_anchor_fits(c, entry, a, pm, down ? down[a] : INFINITY, prev[a], k >= 0 ? table + (size_t)k * T : nullptr)) return rc;
     }
     return DOPF_OK;
 }
@@ -160,17 +167,23 @@ int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double
 {
     if (!(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
         return fail(c, DOPF_E_UNSUPPORTED, "generator energy budgets need DOPF_F2_GEN_ENERGY_BUDGET at dopf_create_ex");
+    return check_generator_energy_budget_values(c, "dopf_set_generator_energy_budget", c->gen_budget_h.data(), c->gen_avail_h.data(), e_min, e_max);
+}
+
+// ... without the flag: the values alone, for `entry` (pmax, table: as check_generator_ramp_values)
+int check_generator_energy_budget_values(dopf_ctx *c, const char *entry, const double *pmax, const double *table, const double *e_min,
+                                         const double *e_max)
+{
     const int G = c->v.G, T = c->v.T;
     for (int i = 0; i < G; ++i) {
         const int a = c->gen_perm[i];
         const double lo = e_min ? e_min[a] : 0.0, hi = e_max ? e_max[a] : INFINITY;
         if (std::isnan(lo) || std::isinf(lo) || lo < 0.0)
-            return fail(c, DOPF_E_INVALID, "dopf_set_generator_energy_budget: e_min[%d] is %g (finite and >= 0 wanted)", a, lo);
-        if (std::isnan(hi) || hi < 0.0) return fail(c, DOPF_E_INVALID, "dopf_set_generator_energy_budget: e_max[%d] is %g (>= 0 wanted)", a, hi);
-        if (lo > hi) return fail(c, DOPF_E_INVALID, "dopf_set_generator_energy_budget: e_min[%d] = %g exceeds e_max[%d] = %g", a, lo, a, hi);
+            return fail(c, DOPF_E_INVALID, "%s: e_min[%d] is %g (finite and >= 0 wanted)", entry, a, lo);
+        if (std::isnan(hi) || hi < 0.0) return fail(c, DOPF_E_INVALID, "%s: e_max[%d] is %g (>= 0 wanted)", entry, a, hi);
+        if (lo > hi) return fail(c, DOPF_E_INVALID, "%s: e_min[%d] = %g exceeds e_max[%d] = %g", entry, a, lo, a, hi);
         const int k = c->gen_prof_h.empty() ? -1 : c->gen_prof_h[i];
-        if (int rc = budget_min_fits(c, "dopf_set_generator_energy_budget", a, c->gen_budget_h[i], lo,
-                                     k >= 0 ? c->gen_avail_h.data() + (size_t)k * T : nullptr)) return rc;
+        if (int rc = budget_min_fits(c, entry, a, pmax[i], lo, k >= 0 ? table + (size_t)k * T : nullptr)) return rc;
     }
     return DOPF_OK;
 }

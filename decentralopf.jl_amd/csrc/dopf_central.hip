@@ -13,6 +13,13 @@
 // rows' coefficients change, and with them the storages' gradient, step sizes and levels — all inside kc_sto<., 3>, which reads
 // sto_eff_alpha(v) / sto_eff_beta(v). The balance and flow rows act on the injection D - C, whose coefficients stay, so the step-size
 // block below (tauN, sigB, sigF) is that of the lossless LP. dopf_central_solve_ex is this entry without efficiencies.
+//
+// dopf_central_solve_coupled: the same with generator ramp limits, an anchor, energy budgets and a line-rating table. The
+// rating table goes through DOPF_F_LINE_RATING and dopf_set_line_rating on the temporary context (kc_dual<., true> reads it). The ramp
+// and budget arrays are checked by the setters' own checks (check_generator_ramp_values, check_generator_energy_budget_values) and
+// kept in allocations of this solve, in the context's sorted generator order: the temporary context has neither flag — the ADMM
+// kernels' scratch behind gen_pmax is nothing the LP needs, and the two never go together there. With any of the five arrays given
+// kc_gen_rows runs in kc_gen's place; its rows have multipliers (yR, yQ), running sums and restart copies like the others.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -43,6 +50,13 @@ struct Metrics {
     double pobj, dobj, pinf, gap;
 };
 
+// what dopf_central_solve_coupled takes and returns beyond dopf_central_solve_lossy (all null: that entry's body, its bits)
+struct Coupling {
+    const double *rating, *ramp_up, *ramp_down, *prev, *e_min, *e_max;
+    double *ramp_dual, *budget_dual;
+    bool rows() const { return ramp_up || ramp_down || prev || e_min || e_max; }
+};
+
 }  // namespace
 
 extern "C" int dopf_central_solve(const dopf_problem *p, const dopf_params *q, double tol, int32_t max_iters,
@@ -59,7 +73,7 @@ namespace {
 // the body of dopf_central_solve_ex / dopf_central_solve_lossy; entry: the name a refusal's message carries
 int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_params *q, const double *sto_e0_in,
                        const double *sto_end_lo_in, const double *sto_end_hi_in, const double *sto_eta_c_in, const double *sto_eta_d_in,
-                       int32_t n_profiles, const double *profiles, const int32_t *profile_of,
+                       int32_t n_profiles, const double *profiles, const int32_t *profile_of, const Coupling &cp,
                        double tol, int32_t max_iters,
                        dopf_central_result *res, double *P, double *D, double *C, double *E,
                        double *system_price, double *nodal_price, double *line_utilization,
@@ -76,7 +90,7 @@ extern "C" int dopf_central_solve_ex(const dopf_problem *p, const dopf_params *q
                                      double *flow_upper_dual, double *flow_lower_dual)
 {
     return central_solve_impl("dopf_central_solve_ex", p, q, sto_e0_in, sto_end_lo_in, sto_end_hi_in, nullptr, nullptr, n_profiles, profiles,
-                              profile_of, tol, max_iters, res, P, D, C, E, system_price, nodal_price, line_utilization, flow_upper_dual,
+                              profile_of, Coupling{}, tol, max_iters, res, P, D, C, E, system_price, nodal_price, line_utilization, flow_upper_dual,
                               flow_lower_dual);
 }
 
@@ -90,15 +104,36 @@ extern "C" int dopf_central_solve_lossy(const dopf_problem *p, const dopf_params
                                         double *flow_upper_dual, double *flow_lower_dual)
 {
     return central_solve_impl("dopf_central_solve_lossy", p, q, sto_e0_in, sto_end_lo_in, sto_end_hi_in, sto_eta_c_in, sto_eta_d_in, n_profiles,
-                              profiles, profile_of, tol, max_iters, res, P, D, C, E, system_price, nodal_price, line_utilization,
+                              profiles, profile_of, Coupling{}, tol, max_iters, res, P, D, C, E, system_price, nodal_price, line_utilization,
                               flow_upper_dual, flow_lower_dual);
+}
+
+extern "C" int dopf_central_solve_coupled(const dopf_problem *p, const dopf_params *q, const double *sto_e0_in,
+                                          const double *sto_end_lo_in, const double *sto_end_hi_in,
+                                          const double *sto_eta_c_in, const double *sto_eta_d_in,
+                                          int32_t n_profiles, const double *profiles, const int32_t *profile_of,
+                                          const double *line_rating, const double *gen_ramp_up, const double *gen_ramp_down,
+                                          const double *gen_prev, const double *gen_e_min, const double *gen_e_max,
+                                          double tol, int32_t max_iters,
+                                          dopf_central_result *res, double *P, double *D, double *C, double *E,
+                                          double *system_price, double *nodal_price, double *line_utilization,
+                                          double *flow_upper_dual, double *flow_lower_dual, double *ramp_dual, double *budget_dual)
+{
+    // the checks that need no values come first: they are seen without a device
+    static const char *const entry = "dopf_central_solve_coupled";
+    if (!gen_ramp_up != !gen_ramp_down) return fail(nullptr, DOPF_E_INVALID, "%s: ramp_up and ramp_down must both be given or both be NULL", entry);
+    if (!(tol > 0)) return fail(nullptr, DOPF_E_INVALID, "%s: tol = %g (> 0 wanted)", entry, tol);
+    if (max_iters < 1) return fail(nullptr, DOPF_E_INVALID, "%s: max_iters = %d (>= 1 wanted)", entry, max_iters);
+    const Coupling cp{line_rating, gen_ramp_up, gen_ramp_down, gen_prev, gen_e_min, gen_e_max, ramp_dual, budget_dual};
+    return central_solve_impl(entry, p, q, sto_e0_in, sto_end_lo_in, sto_end_hi_in, sto_eta_c_in, sto_eta_d_in, n_profiles, profiles, profile_of,
+                              cp, tol, max_iters, res, P, D, C, E, system_price, nodal_price, line_utilization, flow_upper_dual, flow_lower_dual);
 }
 
 namespace {
 
 int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_params *q, const double *sto_e0_in,
                        const double *sto_end_lo_in, const double *sto_end_hi_in, const double *sto_eta_c_in, const double *sto_eta_d_in,
-                       int32_t n_profiles, const double *profiles, const int32_t *profile_of,
+                       int32_t n_profiles, const double *profiles, const int32_t *profile_of, const Coupling &cp,
                        double tol, int32_t max_iters,
                        dopf_central_result *res, double *P, double *D, double *C, double *E,
                        double *system_price, double *nodal_price, double *line_utilization,
@@ -106,6 +141,10 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
 {
     if (!p || !q || !res || !(tol > 0) || max_iters < 1) return fail(nullptr, DOPF_E_INVALID, "bad argument");
     memset(res, 0, sizeof *res);
+    const bool has_rows = cp.rows() && p->G > 0, has_rating = cp.rating && p->L > 0;
+    // (kc_gen_rows holds a row in the registers of one wave, K = ceil(T/64) <= 8 timesteps per lane, as kc_sto does)
+    if (has_rows && p->T > 512)
+        return fail(nullptr, DOPF_E_UNSUPPORTED, "%s: the ramp and budget rows' sweep supports T <= 512 (got %d)", entry, p->T);
     dopf_ctx *c = nullptr;
     dopf_params qq = *q;
     qq.stream = nullptr;
@@ -122,6 +161,7 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
     if (has_e0) qq.flags |= DOPF_F_STO_INITIAL_LEVEL;
     if (has_band) qq.flags |= DOPF_F_STO_TERMINAL_LEVEL;
     if (has_avail) qq.flags |= DOPF_F_GEN_AVAILABILITY;
+    if (has_rating) qq.flags |= DOPF_F_LINE_RATING;
     int rc = dopf_create(&c, p, &qq);       // sorted agents, items, node maps, partial-sum arrays, P/D/C/E (zero)
     if (rc) return rc;
     // (callers read dopf_last_error(NULL): the temporary context's message has to outlive it)
@@ -134,6 +174,7 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
         if (!rc && has_e0) rc = dopf_set_storage_initial_level(c, sto_e0_in);
         if (!rc && has_band) rc = dopf_set_storage_terminal_level(c, sto_end_lo_in, sto_end_hi_in);
         if (!rc && has_avail) rc = dopf_set_generator_availability(c, n_profiles, profiles, profile_of);
+        if (!rc && has_rating) rc = dopf_set_line_rating(c, cp.rating);
         if (rc) {
             const std::string why = c->err;
             return fail(c, rc, "%s: %s", entry, why.c_str());
@@ -145,6 +186,29 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
 
     CentralView cv{};
     cv.v = v;
+    cv.rated = has_rating ? 1 : 0;
+    if (has_rows) {
+        // the ramps, the anchor and the budgets: the setters' checks under the availability table of this call (the context's profile
+        // indices refer to the caller's table), then the five arrays in the context's sorted order — the map dopf_get_primal uses
+        std::vector<double> pm(G), h(5 * (size_t)G);
+        for (int i = 0; i < G; ++i) pm[i] = p->gen_pmax[c->gen_perm[i]];
+        if ((rc = check_generator_ramp_values(c, entry, pm.data(), profiles, cp.ramp_up, cp.ramp_down, cp.prev))) return rc;
+        if ((rc = check_generator_energy_budget_values(c, entry, pm.data(), profiles, cp.e_min, cp.e_max))) return rc;
+        for (int i = 0; i < G; ++i) {
+            const int a = c->gen_perm[i];
+            h[i] = cp.ramp_up ? cp.ramp_up[a] + 0.0 : INFINITY;
+            h[(size_t)G + i] = cp.ramp_down ? cp.ramp_down[a] + 0.0 : INFINITY;
+            h[2 * (size_t)G + i] = cp.prev ? cp.prev[a] + 0.0 : std::nan("");
+            h[3 * (size_t)G + i] = cp.e_min ? cp.e_min[a] + 0.0 : 0.0;
+            h[4 * (size_t)G + i] = cp.e_max ? cp.e_max[a] + 0.0 : INFINITY;
+        }
+        double *d = nullptr;
+        if ((rc = calloc_dev(c, &d, h.size()))) return rc;
+        HIPCHK(c, hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        cv.rows_in = d;
+        if ((rc = calloc_dev(c, &cv.yR, GT)) || (rc = calloc_dev(c, &cv.aR, GT)) || (rc = calloc_dev(c, &cv.yQ, G)) ||
+            (rc = calloc_dev(c, &cv.aQ, G)) || (rc = calloc_dev(c, &cv.m_rows, 3 * (size_t)v.nGenItems))) return rc;
+    }
     cv.w = 1.0;
     cv.sigB = 1.0 / std::max(1, G + 2 * S);
     {   // diagonal step sizes (Pock & Chambolle, alpha = 1): column / row sums of |K|
@@ -180,20 +244,22 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
     vred.part_T = nullptr;                   // (kc_gen / kc_sto write partial rows, [row][t])
     vred.genRows = 0;                        // (kc_gen writes one partial row per item)
 
-    std::vector<double> mg(v.nGenItems), ms(3 * (size_t)v.nStoItems), md(3 * (size_t)T);
+    // (per generator item: kc_gen's reduced-cost term, or kc_gen_rows' three)
+    std::vector<double> mg((has_rows ? 3 : 1) * (size_t)v.nGenItems), ms(3 * (size_t)v.nStoItems), md(3 * (size_t)T);
     double dmax = 0.0;
     for (size_t i = 0; i < NT; ++i) dmax = std::max(dmax, std::fabs(p->demand[i]));
     auto metrics = [&](const double *XP, const double *XD, const double *XC, const double *XE, const double *yb, const double *yf,
-                       double scale, Metrics &m) -> int {
-        central_launch_metrics(cv, c->plan, vred, XP, XD, XC, XE, yb, yf, scale, c->main);
+                       const double *XR, const double *XQ, double scale, Metrics &m) -> int {
+        central_launch_metrics(cv, c->plan, vred, XP, XD, XC, XE, yb, yf, XR, XQ, scale, c->main);
         double cost = 0.0;
         HIPCHK(c, hipMemcpyAsync(&cost, v.cons + NT, sizeof(double), hipMemcpyDeviceToHost, c->main));
-        if (!mg.empty()) HIPCHK(c, hipMemcpyAsync(mg.data(), cv.m_gen, mg.size() * sizeof(double), hipMemcpyDeviceToHost, c->main));
+        if (!mg.empty()) HIPCHK(c, hipMemcpyAsync(mg.data(), has_rows ? cv.m_rows : cv.m_gen, mg.size() * sizeof(double), hipMemcpyDeviceToHost, c->main));
         if (!ms.empty()) HIPCHK(c, hipMemcpyAsync(ms.data(), cv.m_sto, ms.size() * sizeof(double), hipMemcpyDeviceToHost, c->main));
         HIPCHK(c, hipMemcpyAsync(md.data(), cv.m_dual, md.size() * sizeof(double), hipMemcpyDeviceToHost, c->main));
         HIPCHK(c, hipStreamSynchronize(c->main));
         double d = 0.0, inf = 0.0;
-        for (double x : mg) d += x;
+        if (has_rows) for (size_t i = 0; i < mg.size(); i += 3) { d += mg[i] + mg[i + 1]; inf = std::max(inf, mg[i + 2]); }
+        else for (double x : mg) d += x;
         for (size_t i = 0; i < ms.size(); i += 3) { d += ms[i] - ms[i + 2]; inf = std::max(inf, ms[i + 1]); }
         for (size_t t = 0; t < (size_t)T; ++t) { inf = std::max(inf, std::max(md[3 * t], md[3 * t + 1])); d += md[3 * t + 2]; }
         m.pobj = cost; m.dobj = d; m.pinf = std::max(inf, 0.0);
@@ -201,6 +267,39 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
         return DOPF_OK;
     };
 
+    // dopf_central_solve_coupled with any of its inputs: the primal weight follows the iterates (PDLP's update). At every restart
+    // w <- sqrt(w |dy| / |dx|) with dx, dy the primal and dual points' moves since the last restart, so that the step sizes balance
+    // the two distances still to go. With w = 1 throughout, the network case with ramps, anchors and budgets stalled at a gap of
+    // 2.3e-7 from iteration 60 000 to 200 000. The older entries keep w = 1, and with it their bits.
+    const bool adapt_w = has_rows || has_rating;
+    struct Anchored { double *cur, *anchor; size_t n; bool primal; };
+    std::vector<Anchored> moved;
+    double *diff_part = nullptr;
+    if (adapt_w) {
+        for (auto pr : {Anchored{v.P, nullptr, GT, true}, Anchored{v.D, nullptr, ST, true}, Anchored{v.C, nullptr, ST, true},
+                        Anchored{cv.yb, nullptr, (size_t)T, false}, Anchored{cv.yf, nullptr, LT, false}, Anchored{cv.yE, nullptr, ST, false},
+                        Anchored{cv.yR, nullptr, has_rows ? GT : 0, false}, Anchored{cv.yQ, nullptr, has_rows ? (size_t)G : 0, false}}) {
+            if (!pr.n) continue;
+            if ((rc = calloc_dev(c, &pr.anchor, pr.n))) return rc;          // (zeros: the starting point)
+            moved.push_back(pr);
+        }
+        if ((rc = calloc_dev(c, &diff_part, kCentralDiffBlocks))) return rc;
+    }
+    auto update_weight = [&]() -> int {
+        double d2[2] = {0.0, 0.0};           // dual, primal
+        std::vector<double> part(kCentralDiffBlocks);
+        for (const Anchored &a : moved) {
+            const int nb = central_diff_blocks(a.n);
+            central_launch_diff_sq(a.cur, a.anchor, a.n, diff_part, c->main);
+            HIPCHK(c, hipMemcpyAsync(part.data(), diff_part, nb * sizeof(double), hipMemcpyDeviceToHost, c->main));
+            HIPCHK(c, hipStreamSynchronize(c->main));
+            for (int i = 0; i < nb; ++i) d2[a.primal] += part[i];
+            HIPCHK(c, hipMemcpyAsync(a.anchor, a.cur, a.n * sizeof(double), hipMemcpyDeviceToDevice, c->main));
+        }
+        const double dx = std::sqrt(d2[1]), dy = std::sqrt(d2[0]);
+        if (dx > 1e-10 && dy > 1e-10) cv.w = std::exp(0.5 * std::log(dy / dx) + 0.5 * std::log(cv.w));
+        return DOPF_OK;
+    };
     const int batch = 200, max_avg = 4000;
     int it = 0, navg = 0;
     double last_gap = INFINITY;
@@ -211,8 +310,8 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
         for (int k = 0; k < nb; ++k) central_launch_iteration(cv, c->plan, vred, c->main);
         HIPCHK(c, hipGetLastError());
         it += nb; navg += nb;
-        if ((rc = metrics(v.P, v.D, v.C, cv.yE, cv.yb, cv.yf, 1.0, mc))) return rc;
-        if ((rc = metrics(cv.aP, cv.aD, cv.aC, cv.aE, cv.ab, cv.af, 1.0 / navg, ma))) return rc;
+        if ((rc = metrics(v.P, v.D, v.C, cv.yE, cv.yb, cv.yf, cv.yR, cv.yQ, 1.0, mc))) return rc;
+        if ((rc = metrics(cv.aP, cv.aD, cv.aC, cv.aE, cv.ab, cv.af, cv.aR, cv.aQ, 1.0 / navg, ma))) return rc;
         use_avg = ma.gap < mc.gap;
         const Metrics &best = use_avg ? ma : mc;
         done = best.gap <= tol;
@@ -223,17 +322,23 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
                 central_launch_scale_copy(cv.yE, cv.aE, sc, ST, c->main);
                 central_launch_scale_copy(cv.yb, cv.ab, sc, T, c->main);
                 central_launch_scale_copy(cv.yf, cv.af, sc, LT, c->main);
+                if (has_rows) {
+                    central_launch_scale_copy(cv.yR, cv.aR, sc, GT, c->main);
+                    central_launch_scale_copy(cv.yQ, cv.aQ, sc, G, c->main);
+                }
             }
             last_gap = best.gap;
+            if (adapt_w && (rc = update_weight())) return rc;
             for (auto pr : {std::make_pair(cv.aP, GT), std::make_pair(cv.aD, ST), std::make_pair(cv.aC, ST), std::make_pair(cv.aE, ST),
-                            std::make_pair(cv.ab, (size_t)T), std::make_pair(cv.af, LT)})
+                            std::make_pair(cv.ab, (size_t)T), std::make_pair(cv.af, LT), std::make_pair(cv.aR, has_rows ? GT : 0),
+                            std::make_pair(cv.aQ, has_rows ? (size_t)G : 0)})
                 if (pr.second) HIPCHK(c, hipMemsetAsync(pr.first, 0, pr.second * sizeof(double), c->main));
             navg = 0;
         }
     }
     // the accepted point is in v.P / v.D / v.C, (yb, yf, yE); its levels, injections and flows come from one more metrics pass
     Metrics mf{};
-    if ((rc = metrics(v.P, v.D, v.C, cv.yE, cv.yb, cv.yf, 1.0, mf))) return rc;
+    if ((rc = metrics(v.P, v.D, v.C, cv.yE, cv.yb, cv.yf, cv.yR, cv.yQ, 1.0, mf))) return rc;
     res->objective = mf.pobj; res->dual_objective = mf.dobj; res->primal_infeasibility = mf.pinf; res->gap = mf.gap;
     res->iterations = it; res->converged = mf.gap <= tol ? 1 : 0;
     c->level_from_primal = false;            // (the metrics pass has written the accepted point's levels into v.E)
@@ -259,6 +364,19 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
     for (size_t i = 0; i < LT; ++i) {
         if (flow_upper_dual) flow_upper_dual[i] = -std::max(yf[i], 0.0);
         if (flow_lower_dual) flow_lower_dual[i] = -std::max(-yf[i], 0.0);
+    }
+    // the ramp and budget rows' duals, d objective / d right-hand side like the others: negative where the row's upper end binds
+    // (more room there lowers the cost), positive where the lower end does; 0 for a generator without the row
+    if (cp.ramp_dual) {
+        std::vector<double> y(GT, 0.0);
+        if (has_rows && GT) HIPCHK(c, hipMemcpy(y.data(), cv.yR, sizeof(double) * GT, hipMemcpyDeviceToHost));
+        for (int i = 0; i < G; ++i)
+            for (int t = 0; t < T; ++t) cp.ramp_dual[t + (size_t)T * c->gen_perm[i]] = 0.0 - y[t + (size_t)T * i];
+    }
+    if (cp.budget_dual) {
+        std::vector<double> y(G, 0.0);
+        if (has_rows) HIPCHK(c, hipMemcpy(y.data(), cv.yQ, sizeof(double) * G, hipMemcpyDeviceToHost));
+        for (int i = 0; i < G; ++i) cp.budget_dual[c->gen_perm[i]] = 0.0 - y[i];
     }
     return DOPF_OK;
 }

@@ -70,6 +70,12 @@ int check_generator_quadratic_cost(dopf_ctx *c, const double *c2);   // those of
 int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev);
 // those of dopf_set_generator_energy_budget (flag, no NaN, 0 <= e_min <= e_max, e_min finite and <= sum_t cap)
 int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max);
+// the two without their flag checks, for a caller that keeps the arrays itself (dopf_central_solve_coupled; `entry`: the name the
+// messages carry). pmax: capacities in sorted order; table: the availability profiles [t + T*k] the context's gen_prof_h refers to
+int check_generator_ramp_values(dopf_ctx *c, const char *entry, const double *pmax, const double *table, const double *up, const double *down,
+                                const double *prev);
+int check_generator_energy_budget_values(dopf_ctx *c, const char *entry, const double *pmax, const double *table, const double *e_min,
+                                         const double *e_max);
 void launch_demote_full_rows(const DevView &v, hipStream_t s);   // gen_state 1 -> 2 (the caps changed)
 // dopf_comm.hip
 int check_one_runtime(dopf_ctx *c);           // DOPF_E_UNSUPPORTED when two HIP runtimes are mapped into the process

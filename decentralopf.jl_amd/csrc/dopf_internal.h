@@ -26,6 +26,7 @@
 #include "dopf_plan.h"
 #include "ramp_dp.h"
 #include "budget_root.h"
+#include "central_rows.h"
 
 namespace dopf {
 
@@ -326,14 +327,24 @@ struct CentralView {
     const double *sigF;                     // [l] 1 / sum_n |ptdf[l,n]| (units at n, a storage counting twice)
     double sigB, w;                         // 1 / (G + 2S); primal weight
     double *m_gen, *m_sto, *m_dual;         // metrics: per generator item [1], per storage item [3], per timestep [3]
+    // dopf_central_solve_coupled (central_rows.h). rows_in non-null: kc_gen_rows runs in kc_gen's place; rated: kc_dual<., true>
+    const double *rows_in;                  // [5][G], sorted order: ramp_up | ramp_down | p_prev (NaN: no anchor) | e_min | e_max
+    double *yR, *yQ;                        // multipliers: ramp rows [t + T*g] (t = 0: the anchor's row), budget rows [g]
+    double *aR, *aQ;                        // ... their running sums since the last restart
+    double *m_rows;                         // metrics: per generator item [3] reduced-cost term, rows' support term, worst row violation
+    int rated;                              // the flow rows' limits are the rating table v.fmax[l + L*t], not line_fmax0(v)[l]
 };
 
 // kernels_central.hip
 // (p: the context's plan — genAvail and stoLV select the sweeps' feature instantiations)
 void central_launch_iteration(const CentralView &c, const Plan &p, const DevView &vreduce, hipStream_t s);
+// (XR, XQ: the candidate's ramp and budget multipliers; read only with c.rows_in)
 void central_launch_metrics(const CentralView &c, const Plan &p, const DevView &vreduce, const double *XP, const double *XD, const double *XC,
-                            const double *XE, const double *yb, const double *yf, double scale, hipStream_t s);
+                            const double *XE, const double *yb, const double *yf, const double *XR, const double *XQ, double scale, hipStream_t s);
 void central_launch_scale_copy(double *dst, const double *src, double scale, size_t n, hipStream_t s);
+constexpr int kCentralDiffBlocks = 256;
+int central_diff_blocks(size_t n);           // blocks (= partial sums) central_launch_diff_sq writes for n values, at most kCentralDiffBlocks
+void central_launch_diff_sq(const double *a, const double *b, size_t n, double *part, hipStream_t s);   // part[block] = sum (a - b)^2
 void central_launch_scale_copy_primal(const CentralView &c, const Plan &p, double scale, hipStream_t s);   // P, D, C from their running sums, inside the boxes
 
 // Blocks of an x-update that add their sums to the one-launch tail: the storage items and the generator items — or, in the fused

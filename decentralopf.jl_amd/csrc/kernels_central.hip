@@ -22,8 +22,13 @@
 //               dopf_central_solve_lossy (DOPF_F_STO_EFFICIENCY): the level rows become lb_t - e0 <= sum_{tau <= t} (be C - al D) <= ub_t - e0,
 //               be = eta_c, al = 1 / eta_d from sto_eff_beta(v), sto_eff_alpha(v) — K itself changes, in the storages' columns only
 //               (kc_sto<., 3>); the injection D - C, and with it the balance and flow rows, stay.
+//               dopf_central_solve_coupled: more rows — ramp rows -rd <= P[g,t] - P[g,t-1] <= ru (t = 0: against an anchor) with
+//               multipliers yR[g,t], budget rows e_min <= sum_t P[g,t] <= e_max with yQ[g] (kc_gen_rows in kc_gen's place;
+//               central_rows.h) — and the flow rows' limits from a rating table (kc_dual<., true>).
 //   outputs     objective, P, D, C, E; system price = -yb (dual(EB) of the reference), nodal price = -(yb + ptdf' yf)
 //               (src/opf_central_reference.jl:66-79).
+#include <algorithm>
+
 #include "dopf_internal.h"
 
 namespace dopf {
@@ -282,10 +287,145 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
     }
 }
 
+// generators under ramp and budget rows (dopf_central_solve_coupled; central_rows.h holds the arithmetic, DESIGN.md 5u the rows and
+// step sizes): one wave per generator row, four rows of the item in flight per block, lane li owns the K = ceil(T/64) CONSECUTIVE
+// timesteps li*K .. li*K+K-1 (K <= 8) as in kc_sto. Consecutive, not lane-interleaved: a ramp row couples t with t - 1, so inside a
+// lane both neighbours are registers and only the lane boundary costs a shuffle — one __shfl_up per row for the differences (the
+// last slot of lane i-1 feeds the first slot of lane i; that lane is full whenever lane i holds a timestep) and one __shfl_down for
+// yR[t+1] in the reduced cost. Interleaved (t = k*64 + lane) every slot would need both. The loads are then strided by K doubles per
+// lane, but the K unrolled loads of a wave cover one contiguous range of the row: every cache line fetched is used in full.
+// ITER: x+ of every column, the extrapolated point 2x+ - x, the rows' values of it (differences; the row's sum by a wave reduction),
+// both multipliers' proximal steps, running sums. !ITER: metrics of the candidate scale * (X, XR, XQ): cost, sum min(rc, 0) cap,
+// the rows' support terms and worst violation, per item in c.m_rows. Either way the item's sums over its rows go to part_ginj through
+// LDS in a fixed order, as kc_sto's go to part_sinj.
+template <bool ITER, bool AV = false>
+__global__ __launch_bounds__(256) void kc_gen_rows(CentralView c, const double *X, const double *XR, const double *XQ, double scale)
+{
+    constexpr int KMAX = 8;
+    __shared__ double red[4][512];
+    __shared__ double redm[4][4];
+    const DevView &v = c.v;
+    const Item it = v.gen_items[blockIdx.x];
+    const int T = v.T, N = v.N;
+    const size_t G = (size_t)v.G;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int K = (T + 63) / 64, t0 = lane * K;
+    double acc[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
+    double cost = 0.0, dpart = 0.0, sup = 0.0, viol = 0.0;
+    const double absH = c.absHn[it.node], w = c.w;
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
+    for (int g = it.a0 + wv; g < it.a1; g += 4) {           // (wave-uniform trip count per wave)
+        const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
+        const double ru = c.rows_in[g], rd = c.rows_in[G + g], prev = c.rows_in[2 * G + g];
+        const double e_min = c.rows_in[3 * G + g], e_max = c.rows_in[4 * G + g];
+        const bool ramp = cr_has_ramp(ru, rd, prev), anch = cr_anchored(prev), bud = cr_has_budget(e_min, e_max);      // (wave-uniform)
+        const double yQ = bud ? (ITER ? c.yQ[g] : scale * XQ[g]) : 0.0;
+        double x0[KMAX], yR[KMAX], cap[KMAX], xb[KMAX];
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            const int t = t0 + k;
+            const bool ok = k < K && t < T;
+            const size_t e = (size_t)g * T + (ok ? t : 0);
+            x0[k] = ok ? (ITER ? v.P[e] : scale * X[e]) : 0.0;
+            yR[k] = ok && ramp ? (ITER ? c.yR[e] : scale * XR[e]) : 0.0;
+            cap[k] = pm;
+            if constexpr (AV) cap[k] = avail_cap(ftab, T, prof[g], pm, ok ? t : 0);
+        }
+        const double y_lane = __shfl_down(yR[0], 1);          // yR of the first step of the next lane (lane 63: never read, t + 1 = T there)
+        double lsum = 0.0, last = 0.0;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            const int t = t0 + k;
+            xb[k] = 0.0;
+            if (k < K && t < T) {
+                double y_next = k + 1 < K ? yR[k + 1 < KMAX ? k + 1 : k] : y_lane;
+                if (t + 1 >= T) y_next = 0.0;
+                const double rc = cr_reduced_cost(mc, c.pi[it.node + (size_t)N * t], yR[k], y_next, yQ);
+                if (ITER) {
+                    const double tau = cr_tau(absH, cr_ramp_rows_at(t, T, ramp, anch), bud ? 1 : 0, w);
+                    const double xn = cr_column_step(x0[k], tau, rc, cap[k]);
+                    const size_t e = (size_t)g * T + t;
+                    v.P[e] = xn;
+                    c.aP[e] += xn;
+                    xb[k] = 2.0 * xn - x0[k];
+                } else {
+                    xb[k] = x0[k];
+                    cost += mc * x0[k];
+                    dpart += cr_rc_term(rc, cap[k]);
+                }
+                acc[k] += xb[k];
+                lsum += xb[k];
+            }
+            if (k == K - 1) last = xb[k];
+        }
+        if (ramp) {
+            const double x_lane = __shfl_up(last, 1);         // the step before this lane's first (lane 0: t = 0 has no difference)
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                const int t = t0 + k;
+                if (k < K && t < T && (t >= 1 || anch)) {
+                    const double row = t >= 1 ? xb[k] - (k >= 1 ? xb[k >= 1 ? k - 1 : 0] : x_lane) : xb[k];
+                    const double lo = cr_ramp_lo(t, rd, prev), hi = cr_ramp_hi(t, ru, prev);
+                    if (ITER) {
+                        const size_t e = (size_t)g * T + t;
+                        const double yn = cr_prox(yR[k], cr_sigma_ramp(t, w), row, lo, hi);
+                        c.yR[e] = yn;
+                        c.aR[e] += yn;
+                    } else {
+                        sup += cr_support(yR[k], lo, hi);
+                        viol = fmax(viol, cr_violation(row, lo, hi));
+                    }
+                }
+            }
+        }
+        if (bud) {
+            for (int d = 32; d > 0; d >>= 1) lsum += __shfl_xor(lsum, d);      // (a + b = b + a: every lane holds the same bits)
+            if (lane == 0) {
+                if (ITER) {
+                    const double yn = cr_prox(yQ, cr_sigma_budget(T, w), lsum, e_min, e_max);
+                    c.yQ[g] = yn;
+                    c.aQ[g] += yn;
+                } else {
+                    sup += cr_support(yQ, e_min, e_max);
+                    viol = fmax(viol, cr_violation(lsum, e_min, e_max));
+                }
+            }
+        }
+    }
+    // per-item sums over the block's four waves (fixed order)
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) red[wv][lane * KMAX + k] = acc[k];
+    __syncthreads();
+    for (int i = tid; i < 64 * KMAX; i += 256) {
+        const int ln = i / KMAX, k = i - ln * KMAX, t = ln * K + k;
+        if (k < K && t < T) v.part_ginj[(size_t)blockIdx.x * T + t] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    }
+    if (!ITER) {
+        for (int d = 32; d > 0; d >>= 1) {
+            cost += __shfl_xor(cost, d); dpart += __shfl_xor(dpart, d); sup += __shfl_xor(sup, d);
+            viol = fmax(viol, __shfl_xor(viol, d));
+        }
+        if (lane == 0) { redm[wv][0] = cost; redm[wv][1] = dpart; redm[wv][2] = sup; redm[wv][3] = viol; }
+        __syncthreads();
+        if (tid == 0) {
+            v.part_gcost[blockIdx.x] = (redm[0][0] + redm[1][0]) + (redm[2][0] + redm[3][0]);
+            c.m_rows[3 * blockIdx.x + 0] = (redm[0][1] + redm[1][1]) + (redm[2][1] + redm[3][1]);
+            c.m_rows[3 * blockIdx.x + 1] = (redm[0][2] + redm[1][2]) + (redm[2][2] + redm[3][2]);
+            c.m_rows[3 * blockIdx.x + 2] = fmax(fmax(redm[0][3], redm[1][3]), fmax(redm[2][3], redm[3][3]));
+        }
+    }
+}
+
 // balance and flow rows of one timestep from the nodal sums in v.cons. ITER: the multipliers' steps (balance: free;
 // flows: proximal step of the interval's support function) and running sums. !ITER: worst violations and the dual
 // objective's terms -yb d_tot - sum |yf| f_max of the candidate scale * (yb, yf).
-template <bool ITER>
+// RT (dopf_central_solve_coupled with a rating table, on a DOPF_F_LINE_RATING context): the limit of (l,t) is the table's
+// v.fmax[l + L*t] — one load, in the proximal step, the violation and the |yf| F term; !RT: dopf_create's limits, as before.
+template <bool ITER, bool RT = false>
 __global__ __launch_bounds__(256) void kc_dual(CentralView c, const double *yb, const double *yf, double scale)
 {
     extern __shared__ double q[];            // N injections | N demands
@@ -327,7 +467,9 @@ __global__ __launch_bounds__(256) void kc_dual(CentralView c, const double *yb, 
             }
         }
         const size_t i = l + (size_t)L * t;
-        const double F = line_fmax0(v)[l];      // (no ratings in the central reference: dopf_create's limits)
+        double F;
+        if constexpr (RT) F = v.fmax[i];        // (the rating table of a DOPF_F_LINE_RATING context: [l + L*t])
+        else F = line_fmax0(v)[l];              // (dopf_create's limits)
         if (ITER) {
             const double sg = c.w * c.sigF[l];
             const double z = c.yf[i] + sg * f;
@@ -370,6 +512,22 @@ __global__ __launch_bounds__(256) void kc_scale_copy(double *dst, const double *
     if (i < n) dst[i] = scale * src[i];
 }
 
+// part[block] = sum over the block's share of (a - b)^2, grid-stride, summed in a fixed order (the primal weight's update at a restart
+// of dopf_central_solve_coupled: how far the primal and the dual point have moved since the last restart)
+__global__ __launch_bounds__(256) void kc_diff_sq(const double *a, const double *b, size_t n, double *part)
+{
+    __shared__ double red[256];
+    double s = 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const double d = a[i] - b[i];
+        s += d * d;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int sft = 128; sft > 0; sft >>= 1) { if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft]; __syncthreads(); }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
 // the primal rows of the restart: dst = min(scale * src, upper end of the box). The running sum of n iterates inside [0, ub], times
 // 1 / n, can round to one ulp above ub; the restart point, and with it the returned point, has to lie in the box like every iterate
 // (inside the box the min is the identity: the bits of kc_scale_copy). GEN: rows of P, ub = gen_pmax[g], AV: cap[g,t] as kc_gen<., true>;
@@ -395,11 +553,22 @@ void central_launch_price(const CentralView &c, const double *yb, const double *
 }
 
 // the generator / storage sweep of a context: the plan's feature instantiation (genAvail, stoLV), today's without the flags
+// (c.rows_in: the ramp and budget rows' sweep in kc_gen's place; XR, XQ: the candidate's multipliers of those rows)
 template <bool ITER>
-static void launch_gen(const CentralView &c, const Plan &p, const double *X, double scale, hipStream_t s)
+static void launch_gen(const CentralView &c, const Plan &p, const double *X, const double *XR, const double *XQ, double scale, hipStream_t s)
 {
     if (!c.v.nGenItems) return;
-    with_bool(p.genAvail, [&](auto av) { hipLaunchKernelGGL((kc_gen<ITER, decltype(av)::value>), dim3(c.v.nGenItems), dim3(512), 0, s, c, X, scale); });
+    if (c.rows_in)
+        with_bool(p.genAvail, [&](auto av) { hipLaunchKernelGGL((kc_gen_rows<ITER, decltype(av)::value>), dim3(c.v.nGenItems), dim3(256), 0, s, c, X, XR, XQ, scale); });
+    else
+        with_bool(p.genAvail, [&](auto av) { hipLaunchKernelGGL((kc_gen<ITER, decltype(av)::value>), dim3(c.v.nGenItems), dim3(512), 0, s, c, X, scale); });
+}
+
+template <bool ITER>
+static void launch_cdual(const CentralView &c, const double *yb, const double *yf, double scale, hipStream_t s)
+{
+    const size_t lds = 2 * (size_t)c.v.N * sizeof(double);
+    with_bool(c.rated != 0, [&](auto rt) { hipLaunchKernelGGL((kc_dual<ITER, decltype(rt)::value>), dim3(c.v.T), dim3(256), lds, s, c, yb, yf, scale); });
 }
 
 template <bool ITER>
@@ -411,23 +580,28 @@ static void launch_sto(const CentralView &c, const Plan &p, const double *XD, co
 
 void central_launch_iteration(const CentralView &c, const Plan &p, const DevView &vreduce, hipStream_t s)
 {
-    const DevView &v = c.v;
     central_launch_price(c, c.yb, c.yf, 1.0, s);
-    launch_gen<true>(c, p, nullptr, 1.0, s);
+    launch_gen<true>(c, p, nullptr, nullptr, nullptr, 1.0, s);
     launch_sto<true>(c, p, nullptr, nullptr, nullptr, 1.0, s);
     launch_reduce(vreduce, Plan{}, s);            // (nodal sums and cost: k_reduce, whatever chain the context runs)
-    hipLaunchKernelGGL(kc_dual<true>, dim3(v.T), dim3(256), 2 * (size_t)v.N * sizeof(double), s, c, (const double *)nullptr, (const double *)nullptr, 1.0);
+    launch_cdual<true>(c, nullptr, nullptr, 1.0, s);
 }
 
 void central_launch_metrics(const CentralView &c, const Plan &p, const DevView &vreduce, const double *XP, const double *XD, const double *XC, const double *XE,
-                            const double *yb, const double *yf, double scale, hipStream_t s)
+                            const double *yb, const double *yf, const double *XR, const double *XQ, double scale, hipStream_t s)
 {
-    const DevView &v = c.v;
     central_launch_price(c, yb, yf, scale, s);
-    launch_gen<false>(c, p, XP, scale, s);
+    launch_gen<false>(c, p, XP, XR, XQ, scale, s);
     launch_sto<false>(c, p, XD, XC, XE, scale, s);
     launch_reduce(vreduce, Plan{}, s);            // (nodal sums and cost: k_reduce, whatever chain the context runs)
-    hipLaunchKernelGGL(kc_dual<false>, dim3(v.T), dim3(256), 2 * (size_t)v.N * sizeof(double), s, c, yb, yf, scale);
+    launch_cdual<false>(c, yb, yf, scale, s);
+}
+
+// part[0 .. central_diff_blocks(n)) = the blocks' sums of (a - b)^2
+int central_diff_blocks(size_t n) { return (int)std::min<size_t>(kCentralDiffBlocks, (n + 255) / 256); }
+void central_launch_diff_sq(const double *a, const double *b, size_t n, double *part, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(kc_diff_sq, dim3(central_diff_blocks(n)), dim3(256), 0, s, a, b, n, part);
 }
 
 void central_launch_scale_copy(double *dst, const double *src, double scale, size_t n, hipStream_t s)

@@ -741,3 +741,82 @@ function central_reference(nodes::Vector{Node}, generators::Vector{Generator}, s
             level=permutedims(E), line_utilization=util, system_price=lambda, nodal_price=nodal,
             flow_upper_dual=flow_upper, flow_lower_dual=flow_lower)
 end
+
+"""
+    central_reference_coupled(nodes, generators, storages, lines; tol = 1e-9, max_iters = 200000,
+                              initial_level = nothing, terminal_level = nothing, availability = nothing, efficiency = nothing,
+                              line_rating = nothing, ramp = nothing, p_prev = nothing, energy_budget = nothing)
+
+`central_reference` with the inputs of `set_line_rating!`, `set_ramp!` and `set_energy_budget!`: the LP of a decentral run that uses
+them, solved on the GPU by `dopf_central_solve_coupled` (same checks as those setters; ramps and budgets may be given together).
+`line_rating` is L x T, `ramp = (up, down)` G values each (`Inf` = no limit), `p_prev` the G outputs of the step before the window,
+`energy_budget = (e_min, e_max)` G values each. Returns `central_reference`'s NamedTuple plus `ramp_dual` (G x T) and `budget_dual`
+(G): d objective / d right-hand side of the ramp row between t - 1 and t (t = 1: the anchor's row) and of the budget row, negative
+where the row's upper end binds and positive where its lower end does.
+"""
+function central_reference_coupled(nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage}, lines::Vector{Line};
+                                   tol::Float64=1e-9, max_iters::Int=200000, device::Int=-1,
+                                   initial_level::Union{Nothing, Vector{Float64}}=nothing,
+                                   terminal_level::Union{Nothing, Tuple{Vector{Float64}, Vector{Float64}}}=nothing,
+                                   availability::Union{Nothing, Tuple{Matrix{Float64}, Vector{Cint}}}=nothing,
+                                   efficiency::Union{Nothing, Tuple{Vector{Float64}, Vector{Float64}}}=nothing,
+                                   line_rating::Union{Nothing, Matrix{Float64}}=nothing,
+                                   ramp::Union{Nothing, Tuple{Vector{Float64}, Vector{Float64}}}=nothing,
+                                   p_prev::Union{Nothing, Vector{Float64}}=nothing,
+                                   energy_budget::Union{Nothing, Tuple{Vector{Float64}, Vector{Float64}}}=nothing)
+    N, L, T = length(nodes), length(lines), length(nodes[1].demand)
+    G, S = length(generators), length(storages)
+    node_to_id = Dict{Node, Int}(n => i for (i, n) in enumerate(nodes))
+    demand = Float64[nodes[n].demand[t] for n in 1:N, t in 1:T]
+    ptdf = L > 0 ? Matrix{Float64}(calculate_ptdf(nodes, lines)) : zeros(Float64, 0, N)
+    f_max = Float64[l.max_capacity for l in lines]
+    gen_mc = Float64[g.marginal_costs for g in generators]
+    gen_pmax = Float64[g.max_generation for g in generators]
+    gen_node = Cint[node_to_id[g.node] - 1 for g in generators]
+    sto_mc = Float64[s.marginal_costs for s in storages]
+    sto_pmax = Float64[s.max_power for s in storages]
+    sto_emax = Float64[s.max_level for s in storages]
+    sto_node = Cint[node_to_id[s.node] - 1 for s in storages]
+    P = zeros(T, G); D = zeros(T, S); C = zeros(T, S); E = zeros(T, S)
+    lambda = zeros(T); nodal = zeros(N, T); util = zeros(L, T)
+    flow_upper = zeros(L, T); flow_lower = zeros(L, T)
+    ramp_dual = zeros(T, G); budget_dual = zeros(G)
+    res = Ref(CCentralResult(0.0, 0.0, 0.0, 0.0, 0, 0))
+    initial_level === nothing || length(initial_level) == S || error("central_reference_coupled: expected $S initial levels")
+    terminal_level === nothing || (length(terminal_level[1]) == S && length(terminal_level[2]) == S) ||
+        error("central_reference_coupled: expected $S terminal bounds each")
+    availability === nothing || (size(availability[1], 1) == T && length(availability[2]) == G) ||
+        error("central_reference_coupled: expected $T rows of profiles and $G profile indices")
+    efficiency === nothing || (length(efficiency[1]) == S && length(efficiency[2]) == S) ||
+        error("central_reference_coupled: expected $S efficiencies each")
+    line_rating === nothing || size(line_rating) == (L, T) || error("central_reference_coupled: expected a $L x $T rating table")
+    ramp === nothing || (length(ramp[1]) == G && length(ramp[2]) == G) || error("central_reference_coupled: expected $G ramps each")
+    p_prev === nothing || length(p_prev) == G || error("central_reference_coupled: expected $G previous outputs")
+    energy_budget === nothing || (length(energy_budget[1]) == G && length(energy_budget[2]) == G) ||
+        error("central_reference_coupled: expected $G budget bounds each")
+    dptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve demand ptdf f_max gen_mc gen_pmax gen_node sto_mc sto_pmax sto_emax sto_node initial_level terminal_level availability efficiency line_rating ramp p_prev energy_budget begin
+        prob = Ref(CProblem(N, L, T, G, S, pointer(demand), pointer(ptdf), pointer(f_max), pointer(gen_mc),
+                            pointer(gen_pmax), pointer(gen_node), pointer(sto_mc), pointer(sto_pmax),
+                            pointer(sto_emax), pointer(sto_node)))
+        par = Ref(CParams(0.3, 10.0, 1.0, 1e-3, 1e-2, 0, 0, device, 0, C_NULL))
+        K = availability === nothing ? 0 : size(availability[1], 2)
+        po = availability === nothing ? Ptr{Cint}(C_NULL) : pointer(availability[2])
+        rc = ccall((:dopf_central_solve_coupled, DOPF_LIB), Cint,
+                   (Ref{CProblem}, Ref{CParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+                    Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cint,
+                    Ref{CCentralResult}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                    Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                   prob, par, dptr(initial_level), dptr(terminal_level === nothing ? nothing : terminal_level[1]),
+                   dptr(terminal_level === nothing ? nothing : terminal_level[2]), dptr(efficiency === nothing ? nothing : efficiency[1]),
+                   dptr(efficiency === nothing ? nothing : efficiency[2]), K, dptr(availability === nothing ? nothing : availability[1]), po,
+                   dptr(line_rating), dptr(ramp === nothing ? nothing : ramp[1]), dptr(ramp === nothing ? nothing : ramp[2]), dptr(p_prev),
+                   dptr(energy_budget === nothing ? nothing : energy_budget[1]), dptr(energy_budget === nothing ? nothing : energy_budget[2]),
+                   tol, max_iters, res, P, D, C, E, lambda, nodal, util, flow_upper, flow_lower, ramp_dual, budget_dual)
+        dopf_check(rc, Ptr{Cvoid}(C_NULL))
+    end
+    res[].converged == 0 && error("central LP: gap $(res[].gap) after $(res[].iterations) iterations")
+    return (objective=res[].objective, generation=permutedims(P), discharge=permutedims(D), charge=permutedims(C),
+            level=permutedims(E), line_utilization=util, system_price=lambda, nodal_price=nodal,
+            flow_upper_dual=flow_upper, flow_lower_dual=flow_lower, ramp_dual=permutedims(ramp_dual), budget_dual=budget_dual)
+end

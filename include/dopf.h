@@ -181,7 +181,8 @@ typedef struct dopf_params {
                                   * through the breakpoint tables as before. With a table whose columns all equal f_max the results are those
                                   * of the context without the flag, bit for bit, on every chain. dopf_get_agent_slacks, dopf_get_agent_penalty,
                                   * dopf_get_penalty_sums and dopf_debug_table follow the table; dopf_roll_horizon moves it like mu and rho.
-                                  * dopf_central_solve, _ex and _lossy take no ratings: they solve with f_max, flag or not. */
+                                  * dopf_central_solve, _ex and _lossy take no ratings: they solve with f_max, flag or not.
+                                  * dopf_central_solve_coupled takes a table as an argument. */
 #define DOPF_F_GEN_QUADRATIC_COST 1073741824 /* generators have quadratic cost curves: the context keeps a coefficient c2[g] >= 0 per generator
                                   * (all 0 until dopf_set_generator_quadratic_cost), and the cost of generator g at output P is
                                   * gen_mc[g] P + c2[g] P^2 / 2 instead of the reference's one marginal_costs per unit
@@ -210,7 +211,8 @@ typedef struct dopf_params {
                                   * results are those of the flagless context on that chain, bit for bit. dopf_create refuses the flag with
                                   * L > 0 (DOPF_E_UNSUPPORTED) unless DOPF_F_GEN_RAMP_NETWORK is given too, dopf_roll_horizon refuses a
                                   * context with it (the anchor's roll is the host's: build the next window's context).
-                                  * dopf_central_solve, _ex and _lossy ignore the flag. */
+                                  * dopf_central_solve, _ex and _lossy ignore the flag. dopf_central_solve_coupled ignores it too and
+                                  * takes the ramps and the anchor as arguments. */
 #define DOPF_F_GEN_RAMP_NETWORK 2147483648u /* ramp limits on a network (L > 0); meaningful only together with DOPF_F_GEN_RAMP, and an
                                   * opt-in of its own because the network step needs memory that grows with the tables. A row's derivative
                                   * per step is then mc + c2 x + Psi(x - p0) + w_prox (x - p0), piecewise linear with up to 2L kinks of the
@@ -225,7 +227,8 @@ typedef struct dopf_params {
                                   * chain, bit for bit. dopf_create refuses (DOPF_E_UNSUPPORTED) this flag without DOPF_F_GEN_RAMP, and
                                   * DOPF_F_GEN_RAMP alone with L > 0; with L == 0 this flag is accepted and ignored (the copper-plate
                                   * kernel runs, the same bits). dopf_roll_horizon goes on refusing every ramp context, dopf_central_solve,
-                                  * _ex and _lossy ignore the flag. This is bit 31, the LAST bit of dopf_params.flags (an int32_t whose
+                                  * _ex and _lossy ignore the flag (dopf_central_solve_coupled as well: it takes ramps as arguments, on
+                                  * copper plates and networks alike). This is bit 31, the LAST bit of dopf_params.flags (an int32_t whose
                                   * size the ABI pins): the next create-time option needs a second flag word, for example in a
                                   * dopf_create2. (That word exists now: the flags2 argument of dopf_create_ex below, whose options are
                                   * named DOPF_F2_*.) */
@@ -249,7 +252,8 @@ typedef struct dopf_params {
                                   * projected step. Together with DOPF_F_GEN_RAMP the flag is refused (DOPF_E_UNSUPPORTED: two constraints
                                   * that couple a row's timesteps need the ramp programme inside the multiplier search); dopf_roll_horizon
                                   * refuses a context with it (what is left of a budget after k steps is the host's arithmetic);
-                                  * dopf_central_solve, _ex and _lossy take no budgets and ignore the bit. */
+                                  * dopf_central_solve, _ex and _lossy take no budgets and ignore the bit. dopf_central_solve_coupled
+                                  * takes the budgets as arguments, together with ramps if the caller has both. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
@@ -552,6 +556,40 @@ int dopf_central_solve_lossy(const dopf_problem *p, const dopf_params *q,
                              double *P, double *D, double *C, double *E,
                              double *system_price, double *nodal_price, double *line_utilization,
                              double *flow_upper_dual, double *flow_lower_dual);
+
+/* The same LP with the constraints that couple a generator's timesteps, and with per-timestep line limits: dopf_central_solve_lossy's
+ * arguments plus the inputs of dopf_set_line_rating, dopf_set_generator_ramp and dopf_set_generator_energy_budget — the parity target
+ * of a decentral run that uses DOPF_F_LINE_RATING, DOPF_F_GEN_RAMP (with or without DOPF_F_GEN_RAMP_NETWORK) or
+ * DOPF_F2_GEN_ENERGY_BUDGET. All in the caller's agent order, each NULL = that input's default:
+ *   line_rating[L*T]  [l + L*t], every entry finite and >= 0 (NULL: f_max in every timestep): -rating <= flow[l,t] <= rating.
+ *   gen_ramp_up[G], gen_ramp_down[G]  both or neither, >= 0, +inf = no limit: -ramp_down <= P[g,t] - P[g,t-1] <= ramp_up for t >= 1.
+ *   gen_prev[G]  the outputs of the step before the window, in [0, gen_pmax]: the same row at t = 0 against them (NULL: no such row).
+ *   gen_e_min[G], gen_e_max[G]  0 <= e_min <= e_max, e_min finite (NULL: 0 and +inf): e_min <= sum_t P[g,t] <= e_max.
+ * Meaning, checks and codes are the three setters' — an anchored generator must be able to come down under its caps, and a minimum
+ * must fit under them, both under the availability table of this same call — except that budgets and ramps may be given together
+ * (two coupling rows are nothing to an LP; only the decentral step refuses the pair). ramp_up without ramp_down (or the reverse),
+ * tol <= 0 and max_iters < 1 are refused before a device is looked for. A refusal's message names this entry, and no output is written.
+ * Horizons beyond T = 512 are refused with ramps or budgets (DOPF_E_UNSUPPORTED). The flags of q that name these extensions are
+ * ignored, as by the other entries: what counts is the arrays. Two more outputs, both d objective / d right-hand side like the flow
+ * duals — negative where the row's upper end binds, positive where its lower end binds, 0 where neither does or the row does not exist:
+ *   ramp_dual[T*G]   [t + T*g]: the ramp row between t - 1 and t (t = 0: the anchor's row)
+ *   budget_dual[G]   the budget row: minus the price of generator g's energy over the window (the water value of a capped reservoir)
+ * primal_infeasibility includes the worst ramp and budget violation. With all six inputs NULL this is dopf_central_solve_lossy, bit for
+ * bit (the two duals are zeros). */
+int dopf_central_solve_coupled(const dopf_problem *p, const dopf_params *q,
+                               const double *sto_e0,
+                               const double *sto_end_lo, const double *sto_end_hi,
+                               const double *sto_eta_c, const double *sto_eta_d,
+                               int32_t n_profiles, const double *profiles,
+                               const int32_t *profile_of,
+                               const double *line_rating,
+                               const double *gen_ramp_up, const double *gen_ramp_down, const double *gen_prev,
+                               const double *gen_e_min, const double *gen_e_max,
+                               double tol, int32_t max_iters, dopf_central_result *res,
+                               double *P, double *D, double *C, double *E,
+                               double *system_price, double *nodal_price, double *line_utilization,
+                               double *flow_upper_dual, double *flow_lower_dual,
+                               double *ramp_dual, double *budget_dual);
 
 /* ---- consensus sum across GPUs inside the library (RCCL over xGMI, loaded at run time) -------------
  * Replaces nothing in the reference (it has no parallelism); what is distributed is the agent loop of
