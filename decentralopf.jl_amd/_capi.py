@@ -1008,7 +1008,10 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     line_rating: the device LP takes no line ratings; a table other than f_max in every timestep raises DopfError.
     gen_c2: the device LP takes no quadratic costs either; a non-zero coefficient raises DopfError.
     gen_ramp, gen_prev: nor ramp limits; a finite ramp or an anchor raises DopfError.
-    gen_budget: nor energy budgets; an e_min above 0 or a finite e_max raises DopfError."""
+    gen_budget: nor energy budgets; an e_min above 0 or a finite e_max raises DopfError.
+    T: any horizon. Beyond 512 timesteps the storages run on the long sweep (kc_sto_long); the entry sets DOPF_F_LONG_HORIZON on its own
+    context, so params needs no flag, and with F_LONG_HORIZON in params the result is the same bits. F_DEBUG_LONG_STO in params runs
+    that sweep at T <= 512 too (tests)."""
     N, L, T = int(N), int(L), int(T)
     if gen_budget is not None and ((gen_budget[0] is not None and np.any(np.asarray(gen_budget[0], dtype=np.float64) != 0.0)) or
                                    (gen_budget[1] is not None and np.any(np.asarray(gen_budget[1], dtype=np.float64) != np.inf))):
@@ -1068,7 +1071,9 @@ def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, ge
     the inputs as the three setters do (DopfError with the entry's name). gen_c2: the device solve is an LP; a non-zero coefficient
     raises DopfError. Returns central_solve's dict plus ramp_dual (G, T) and budget_dual (G,): d objective / d right-hand side of the
     ramp row between t - 1 and t (t = 0: the anchor's row) and of the budget row — negative where the row's upper end binds, positive
-    where its lower end does."""
+    where its lower end does.
+    T: any horizon, with ramps and budgets too. Beyond 512 timesteps the rows run on the long sweeps (kc_gen_rows_long, kc_sto_long);
+    params needs no flag for it. F_DEBUG_LONG_STO in params runs those sweeps at T <= 512 too (tests)."""
     N, L, T = int(N), int(L), int(T)
     if gen_c2 is not None and np.any(np.asarray(gen_c2, dtype=np.float64) != 0.0):
         raise DopfError("dopf_central_solve_coupled: the device LP takes no quadratic generator costs (it solves with gen_mc alone)")

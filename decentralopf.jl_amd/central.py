@@ -226,7 +226,8 @@ def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Gene
     no code with HiGHS. The elements' initial levels, terminal bands and availability series are part of the LP, as in
     central_reference; initial_level / terminal_level override the storages' own, as there. Without lossy=True the device LP is
     lossless: efficiencies other than 1 (the argument's, or the storages' own) raise ValueError. With lossy=True they (the
-    argument's, else the storages' own) are part of the LP (dopf_central_solve_lossy), as in central_reference."""
+    argument's, else the storages' own) are part of the LP (dopf_central_solve_lossy), as in central_reference. Any horizon is taken,
+    beyond 512 timesteps too; no flag is needed for it."""
     from . import _capi
     pp = pack(nodes, generators, storages, lines)
     if pp.has_quadratic_cost():
@@ -277,7 +278,8 @@ def central_reference_coupled_on_device(nodes: Sequence[Node], generators: Seque
     (up, down), gen_budget = (e_min, e_max) and line_rating (L, T) override the elements' own; gen_prev (G,) are the outputs of the step
     before the window, the anchor of the ramp rows at t = 0 (None: no anchor — the elements carry none). Quadratic costs are refused:
     the device solve is an LP. Returns a CentralResult; with duals=True a pair of it and dict(ramp_dual (G, T), budget_dual (G,)),
-    d objective / d right-hand side of the ramp and budget rows (budget_dual: minus the water value of a capped generator)."""
+    d objective / d right-hand side of the ramp and budget rows (budget_dual: minus the water value of a capped generator). Any horizon
+    is taken, beyond 512 timesteps too (kc_gen_rows_long, kc_sto_long); no flag is needed for it."""
     from . import _capi
     pp = pack(nodes, generators, storages, lines)
     if pp.has_quadratic_cost():

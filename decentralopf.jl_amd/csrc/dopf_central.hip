@@ -20,6 +20,10 @@
 // kept in allocations of this solve, in the context's sorted generator order: the temporary context has neither flag — the ADMM
 // kernels' scratch behind gen_pmax is nothing the LP needs, and the two never go together there. With any of the five arrays given
 // kc_gen_rows runs in kc_gen's place; its rows have multipliers (yR, yQ), running sums and restart copies like the others.
+//
+// Long horizons: every entry takes any T. Where a row couples timesteps — storages, ramps, budgets — beyond the one-wave
+// sweeps' horizon, the entry sets DOPF_F_LONG_HORIZON on the temporary context itself (what counts is the shape, as with the other
+// inputs), and kc_sto_long / kc_gen_rows_long run in kc_sto's / kc_gen_rows' place. The iteration around them is the same.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -142,9 +146,6 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
     if (!p || !q || !res || !(tol > 0) || max_iters < 1) return fail(nullptr, DOPF_E_INVALID, "bad argument");
     memset(res, 0, sizeof *res);
     const bool has_rows = cp.rows() && p->G > 0, has_rating = cp.rating && p->L > 0;
-    // (kc_gen_rows holds a row in the registers of one wave, K = ceil(T/64) <= 8 timesteps per lane, as kc_sto does)
-    if (has_rows && p->T > 512)
-        return fail(nullptr, DOPF_E_UNSUPPORTED, "%s: the ramp and budget rows' sweep supports T <= 512 (got %d)", entry, p->T);
     dopf_ctx *c = nullptr;
     dopf_params qq = *q;
     qq.stream = nullptr;
@@ -162,6 +163,10 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
     if (has_band) qq.flags |= DOPF_F_STO_TERMINAL_LEVEL;
     if (has_avail) qq.flags |= DOPF_F_GEN_AVAILABILITY;
     if (has_rating) qq.flags |= DOPF_F_LINE_RATING;
+    // ... and so does the shape: a row that couples timesteps beyond one wave's horizon runs on the long sweeps (kc_sto_long through
+    // the context's Plan::stoLong, kc_gen_rows_long through cv.longRows). The caller's DOPF_F_LONG_HORIZON is neither needed nor harmful
+    const bool long_horizon = p->T > kCentralWaveHorizon;
+    if (long_horizon && (p->S > 0 || has_rows)) qq.flags |= DOPF_F_LONG_HORIZON;
     int rc = dopf_create(&c, p, &qq);       // sorted agents, items, node maps, partial-sum arrays, P/D/C/E (zero)
     if (rc) return rc;
     // (callers read dopf_last_error(NULL): the temporary context's message has to outlive it)
@@ -187,6 +192,7 @@ int central_solve_impl(const char *entry, const dopf_problem *p, const dopf_para
     CentralView cv{};
     cv.v = v;
     cv.rated = has_rating ? 1 : 0;
+    cv.longRows = (long_horizon || (q->flags & DOPF_F_DEBUG_LONG_STO)) ? 1 : 0;
     if (has_rows) {
         // the ramps, the anchor and the budgets: the setters' checks under the availability table of this call (the context's profile
         // indices refer to the caller's table), then the five arrays in the context's sorted order — the map dopf_get_primal uses

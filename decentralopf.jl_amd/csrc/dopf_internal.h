@@ -333,7 +333,12 @@ struct CentralView {
     double *aR, *aQ;                        // ... their running sums since the last restart
     double *m_rows;                         // metrics: per generator item [3] reduced-cost term, rows' support term, worst row violation
     int rated;                              // the flow rows' limits are the rating table v.fmax[l + L*t], not line_fmax0(v)[l]
+    int longRows;                           // kc_gen_rows_long in kc_gen_rows' place: T > 512, or DOPF_F_DEBUG_LONG_STO (read with rows_in)
 };
+
+// the horizon kc_sto and kc_gen_rows hold in one wave's registers (64 lanes x 8 timesteps, the one-wave storage bodies' limit:
+// sto_config_supported); beyond it kc_sto_long and kc_gen_rows_long run
+constexpr int kCentralWaveHorizon = 64 * 8;
 
 // kernels_central.hip
 // (p: the context's plan — genAvail and stoLV select the sweeps' feature instantiations)

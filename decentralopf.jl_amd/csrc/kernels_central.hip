@@ -25,10 +25,13 @@
 //               dopf_central_solve_coupled: more rows — ramp rows -rd <= P[g,t] - P[g,t-1] <= ru (t = 0: against an anchor) with
 //               multipliers yR[g,t], budget rows e_min <= sum_t P[g,t] <= e_max with yQ[g] (kc_gen_rows in kc_gen's place;
 //               central_rows.h) — and the flow rows' limits from a rating table (kc_dual<., true>).
+//   horizons    kc_sto and kc_gen_rows hold a row in one wave's registers: T <= 512. Beyond it (every entry, no flag to set) kc_sto_long
+//               and kc_gen_rows_long walk a row in tiles of 2048 timesteps with a whole block (central_long.h).
 //   outputs     objective, P, D, C, E; system price = -yb (dual(EB) of the reference), nodal price = -(yb + ptdf' yf)
 //               (src/opf_central_reference.jl:66-79).
 #include <algorithm>
 
+#include "central_long.h"
 #include "dopf_internal.h"
 
 namespace dopf {
@@ -420,6 +423,311 @@ __global__ __launch_bounds__(256) void kc_gen_rows(CentralView c, const double *
     }
 }
 
+// ---- the long sweeps: rows beyond T = 512 (central_long.h holds the index arithmetic, DESIGN.md 5v the design) ----------------------
+// One block of 256 threads works on ONE row at a time and walks it in tiles of 2048 consecutive timesteps; thread i owns the 8
+// consecutive steps tile * 2048 + 8 i .. + 7. What kc_sto and kc_gen_rows pass between the lanes of a wave is passed between the
+// threads of the block (wave_prefix plus the four waves' totals through LDS, added in a fixed order), and what crosses a tile boundary
+// is a block-uniform carry. Element offsets are size_t, so the horizon is bounded by memory alone.
+
+// inclusive prefix sum over the block's 256 threads; total: the block's sum, the same bits in every thread. Every thread calls it.
+__device__ __forceinline__ double block_prefix(double x, int lane, int wv, double *wt, double &total)
+{
+    const double incl = wave_prefix(x, lane);
+    __syncthreads();                                          // (the readers of wt in the call before)
+    if (lane == 63) wt[wv] = incl;
+    __syncthreads();
+    const double w0 = wt[0], w1 = wt[1], w2 = wt[2], w3 = wt[3];
+    total = ((w0 + w1) + w2) + w3;
+    return incl + (wv == 0 ? 0.0 : wv == 1 ? w0 : wv == 2 ? w0 + w1 : (w0 + w1) + w2);
+}
+
+// storages on any horizon, in kc_sto's place when the context's plan has stoLong (T > 512, or DOPF_F_DEBUG_LONG_STO): the same LP rows,
+// step sizes and metrics, ITER, !ITER and LV with kc_sto's meaning. The reduced costs need sum_{tau >= t} yE: one read-only pass over
+// the row's yE gives the total, then ONE forward pass over the tiles takes suffix = total - prefix with the sum over the earlier tiles
+// as a carry, and in the same tile D+, C+, the extrapolated net, the level prefix (carry: the level at the end of the tile before, e0
+// in front of the first) and the multiplier's proximal step. part_sinj[item][t]: the thread that owns t stores for the item's first
+// storage and adds for later ones (under Plan::stoLong an item holds one storage).
+template <bool ITER, int LV = 0>
+__global__ __launch_bounds__(256) void kc_sto_long(CentralView c, const double *XD, const double *XC, const double *XE, double scale)
+{
+    constexpr int NS = kClSlots;
+    __shared__ double wt[4];
+    __shared__ double redm[4][4];
+    const DevView &v = c.v;
+    const Item it = v.sto_items[blockIdx.x];
+    const int T = v.T, N = v.N;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tiles = cl_tiles(T);
+    double cost = 0.0, dpart = 0.0, viol = 0.0, yterm = 0.0;
+    const double absH = c.absHn[it.node];
+    double *part = v.part_sinj + (size_t)blockIdx.x * T;
+    for (int s = it.a0; s < it.a1; ++s) {                    // (block-uniform)
+        const bool first = s == it.a0;
+        const double mc = v.sto_mc[s], pm = v.sto_pmax[s], em = v.sto_emax[s];
+        double e0 = 0.0, elo = 0.0, ehi = em;                 // LV: the level before timestep 0, the band of the last one
+        if constexpr (LV >= 1) e0 = sto_e0(v)[s];
+        if constexpr (LV >= 2) { elo = sto_end_lo(v)[s]; ehi = sto_end_hi(v)[s]; }
+        [[maybe_unused]] double al = 1.0, be = 1.0;           // LV 3: 1 / eta_d, eta_c
+        if constexpr (LV == 3) { al = sto_eff_alpha(v)[s]; be = sto_eff_beta(v)[s]; }
+        const size_t row = (size_t)s * T;
+        // the row's sum of yE: every thread its own slots, tile after tile, then the block's sum
+        double mine = 0.0;
+        for (int tile = 0; tile < tiles; ++tile) {
+            const long long f = cl_first(tile, tid);
+#pragma unroll
+            for (int k = 0; k < NS; ++k)
+                if (cl_live(f, k, T)) mine += ITER ? c.yE[row + (size_t)(f + k)] : scale * XE[row + (size_t)(f + k)];
+        }
+        double total;
+        block_prefix(mine, lane, wv, wt, total);
+        double ycarry = 0.0, lcarry = e0;                     // sum of yE over the tiles before; the level at their end
+        for (int tile = 0; tile < tiles; ++tile) {
+            const long long f = cl_first(tile, tid);
+            double yE[NS], d0[NS], c0[NS], dn[NS], cn[NS];
+            double ysum = 0.0;
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const bool ok = cl_live(f, k, T);
+                const size_t e = row + (ok ? (size_t)(f + k) : 0);
+                yE[k] = ok ? (ITER ? c.yE[e] : scale * XE[e]) : 0.0;
+                d0[k] = ok ? (ITER ? v.D[e] : scale * XD[e]) : 0.0;
+                c0[k] = ok ? (ITER ? v.C[e] : scale * XC[e]) : 0.0;
+                ysum += yE[k];
+            }
+            double tsum;
+            const double incl = block_prefix(ysum, lane, wv, wt, tsum);
+            double before = ycarry + (incl - ysum);           // sum of yE over the steps before this thread's first
+            ycarry += tsum;
+            double net = 0.0;
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                dn[k] = 0.0; cn[k] = 0.0;
+                if (cl_live(f, k, T)) {
+                    const int t = (int)(f + k);
+                    const double suf = total - before;        // sum_{tau >= t} yE
+                    before += yE[k];
+                    const double pi = c.pi[it.node + (size_t)N * t];
+                    double rD, rC, inj;
+                    if constexpr (LV == 3) { rD = mc + pi - al * suf; rC = mc - pi + be * suf; }
+                    else { rD = mc + pi - suf; rC = mc - pi + suf; }
+                    if (ITER) {
+                        if constexpr (LV == 3) {
+                            const double tauD = 1.0 / ((1.0 + absH + al * (double)(T - t)) * c.w);
+                            const double tauC = 1.0 / ((1.0 + absH + be * (double)(T - t)) * c.w);
+                            dn[k] = cclamp(d0[k] - tauD * rD, 0.0, pm);
+                            cn[k] = cclamp(c0[k] - tauC * rC, 0.0, pm);
+                        } else {
+                            const double tau = 1.0 / ((1.0 + absH + (double)(T - t)) * c.w);
+                            dn[k] = cclamp(d0[k] - tau * rD, 0.0, pm);
+                            cn[k] = cclamp(c0[k] - tau * rC, 0.0, pm);
+                        }
+                        const double bd = 2.0 * dn[k] - d0[k], bc = 2.0 * cn[k] - c0[k];
+                        inj = bd - bc;
+                        if constexpr (LV == 3) net += be * bc - al * bd;
+                        else net += bc - bd;
+                    } else {
+                        inj = d0[k] - c0[k];
+                        if constexpr (LV == 3) net += be * c0[k] - al * d0[k];
+                        else net += c0[k] - d0[k];
+                        cost += mc * (d0[k] + c0[k]);
+                        dpart += (fmin(rD, 0.0) + fmin(rC, 0.0)) * pm;
+                        if constexpr (LV == 0) yterm += fmax(yE[k], 0.0) * em;
+                        else {
+                            const bool last = LV >= 2 && t == T - 1;
+                            yterm = fma(fmax(yE[k], 0.0), (last ? ehi : em) - e0, yterm);
+                            yterm = fma(fmin(yE[k], 0.0), (last ? elo : 0.0) - e0, yterm);
+                        }
+                    }
+                    part[t] = first ? inj : part[t] + inj;
+                }
+            }
+            double ntot;
+            const double inclE = block_prefix(net, lane, wv, wt, ntot);
+            double lev = lcarry + (inclE - net);              // level before this thread's first step
+            lcarry += ntot;
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                if (cl_live(f, k, T)) {
+                    const int t = (int)(f + k);
+                    const size_t e = row + (size_t)t;
+                    if (ITER) {
+                        double sg;
+                        if constexpr (LV == 3) {
+                            lev += be * (2.0 * cn[k] - c0[k]) - al * (2.0 * dn[k] - d0[k]);
+                            sg = c.w / ((al + be) * (double)(t + 1));
+                        } else {
+                            lev += (2.0 * cn[k] - c0[k]) - (2.0 * dn[k] - d0[k]);
+                            sg = c.w / (2.0 * (double)(t + 1));
+                        }
+                        const double z = yE[k] + sg * lev;
+                        double yn;
+                        if constexpr (LV >= 2) { const bool last = t == T - 1; yn = z - sg * cclamp(z / sg, last ? elo : 0.0, last ? ehi : em); }
+                        else yn = z - sg * cclamp(z / sg, 0.0, em);
+                        v.D[e] = dn[k]; v.C[e] = cn[k];
+                        c.yE[e] = yn;
+                        c.aD[e] += dn[k]; c.aC[e] += cn[k]; c.aE[e] += yn;
+                    } else {
+                        if constexpr (LV == 3) lev += be * c0[k] - al * d0[k];
+                        else lev += c0[k] - d0[k];
+                        v.E[e] = lev;
+                        if constexpr (LV >= 2) { const bool last = t == T - 1; viol = fmax(viol, fmax((last ? elo : 0.0) - lev, lev - (last ? ehi : em))); }
+                        else viol = fmax(viol, fmax(-lev, lev - em));
+                    }
+                }
+            }
+        }
+    }
+    if (!ITER) {
+        for (int d = 32; d > 0; d >>= 1) {
+            cost += __shfl_xor(cost, d); dpart += __shfl_xor(dpart, d); yterm += __shfl_xor(yterm, d);
+            viol = fmax(viol, __shfl_xor(viol, d));
+        }
+        if (lane == 0) { redm[wv][0] = cost; redm[wv][1] = dpart; redm[wv][2] = viol; redm[wv][3] = yterm; }
+        __syncthreads();
+        if (tid == 0) {
+            v.part_scost[blockIdx.x] = (redm[0][0] + redm[1][0]) + (redm[2][0] + redm[3][0]);
+            c.m_sto[3 * blockIdx.x + 0] = (redm[0][1] + redm[1][1]) + (redm[2][1] + redm[3][1]);
+            c.m_sto[3 * blockIdx.x + 1] = fmax(fmax(redm[0][2], redm[1][2]), fmax(redm[2][2], redm[3][2]));
+            c.m_sto[3 * blockIdx.x + 2] = (redm[0][3] + redm[1][3]) + (redm[2][3] + redm[3][3]);
+        }
+    }
+}
+
+// generators under ramp and budget rows on any horizon, in kc_gen_rows' place when T > 512 (or DOPF_F_DEBUG_LONG_STO): the item's rows
+// one after another, the whole block on one row, all row arithmetic through central_rows.h as there. A ramp row couples t with t - 1 and
+// the column of t reads yR[t+1]:
+//   yR[t+1] of a thread's last slot is the next thread's first slot — or, for the tile's last thread, the next tile's — and is read
+//   from memory with the thread's own loads, BEFORE the tile's barrier; its owner writes it after that barrier (the next tile's first
+//   slot: after the next tile's), so what is read is this iteration's old value;
+//   the difference at a thread's first slot takes the left neighbour's last xb through LDS (two buffers in turn: one barrier per tile),
+//   at a tile's first slot the tile before's last xb as a carry; t = 0 is today's: no difference without an anchor.
+// The budget row's sum is kept per thread across the tiles and summed over the block once per row, after the last tile; its proximal
+// step follows there. part_ginj[item][t]: the owning thread stores for the item's first generator and adds for later ones.
+template <bool ITER, bool AV = false>
+__global__ __launch_bounds__(256) void kc_gen_rows_long(CentralView c, const double *X, const double *XR, const double *XQ, double scale)
+{
+    constexpr int NS = kClSlots;
+    __shared__ double hand[2][kClThreads];
+    __shared__ double wsum[4];
+    __shared__ double redm[4][4];
+    const DevView &v = c.v;
+    const Item it = v.gen_items[blockIdx.x];
+    const int T = v.T, N = v.N;
+    const size_t G = (size_t)v.G;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tiles = cl_tiles(T);
+    double cost = 0.0, dpart = 0.0, sup = 0.0, viol = 0.0;
+    const double absH = c.absHn[it.node], w = c.w;
+    const double *ftab = nullptr;
+    const int *prof = nullptr;
+    if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
+    double *part = v.part_ginj + (size_t)blockIdx.x * T;
+    int buf = 0;                                              // which half of hand[] this tile writes (block-uniform)
+    for (int g = it.a0; g < it.a1; ++g) {                    // (block-uniform)
+        const bool first = g == it.a0;
+        const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
+        const double ru = c.rows_in[g], rd = c.rows_in[G + g], prev = c.rows_in[2 * G + g];
+        const double e_min = c.rows_in[3 * G + g], e_max = c.rows_in[4 * G + g];
+        const bool ramp = cr_has_ramp(ru, rd, prev), anch = cr_anchored(prev), bud = cr_has_budget(e_min, e_max);      // (block-uniform)
+        const double yQ = bud ? (ITER ? c.yQ[g] : scale * XQ[g]) : 0.0;
+        const size_t row = (size_t)g * T;
+        double lsum = 0.0, xcarry = 0.0;                      // this thread's share of sum_t xb; the last xb of the tile before
+        for (int tile = 0; tile < tiles; ++tile) {
+            const long long f = cl_first(tile, tid);
+            double x0[NS], yR[NS], cap[NS], xb[NS];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const bool ok = cl_live(f, k, T);
+                const size_t e = row + (ok ? (size_t)(f + k) : 0);
+                x0[k] = ok ? (ITER ? v.P[e] : scale * X[e]) : 0.0;
+                yR[k] = ok && ramp ? (ITER ? c.yR[e] : scale * XR[e]) : 0.0;
+                cap[k] = pm;
+                if constexpr (AV) cap[k] = avail_cap(ftab, T, prof[g], pm, ok ? (int)(f + k) : 0);
+            }
+            double y_hand = 0.0;                              // yR of the step behind this thread's last slot
+            if (ramp && cl_live(f, NS, T)) y_hand = ITER ? c.yR[row + (size_t)(f + NS)] : scale * XR[row + (size_t)(f + NS)];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                xb[k] = 0.0;
+                if (cl_live(f, k, T)) {
+                    const int t = (int)(f + k);
+                    double y_next = k + 1 < NS ? yR[k + 1 < NS ? k + 1 : k] : y_hand;
+                    if (t + 1 >= T) y_next = 0.0;
+                    const double rc = cr_reduced_cost(mc, c.pi[it.node + (size_t)N * t], yR[k], y_next, yQ);
+                    if (ITER) {
+                        const double tau = cr_tau(absH, cr_ramp_rows_at(t, T, ramp, anch), bud ? 1 : 0, w);
+                        const double xn = cr_column_step(x0[k], tau, rc, cap[k]);
+                        const size_t e = row + (size_t)t;
+                        v.P[e] = xn;
+                        c.aP[e] += xn;
+                        xb[k] = 2.0 * xn - x0[k];
+                    } else {
+                        xb[k] = x0[k];
+                        cost += mc * x0[k];
+                        dpart += cr_rc_term(rc, cap[k]);
+                    }
+                    part[t] = first ? xb[k] : part[t] + xb[k];
+                    lsum += xb[k];
+                }
+            }
+            hand[buf][tid] = xb[NS - 1];
+            __syncthreads();
+            const double x_left = tid ? hand[buf][tid - 1] : xcarry;      // the step before this thread's first (t = 0: never read)
+            xcarry = hand[buf][kClThreads - 1];               // (a full tile's last step; behind the last tile nobody reads it)
+            buf ^= 1;
+            if (ramp) {
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    if (cl_live(f, k, T) && (f + k >= 1 || anch)) {
+                        const int t = (int)(f + k);
+                        const double rowv = t >= 1 ? xb[k] - (k >= 1 ? xb[k >= 1 ? k - 1 : 0] : x_left) : xb[k];
+                        const double lo = cr_ramp_lo(t, rd, prev), hi = cr_ramp_hi(t, ru, prev);
+                        if (ITER) {
+                            const size_t e = row + (size_t)t;
+                            const double yn = cr_prox(yR[k], cr_sigma_ramp(t, w), rowv, lo, hi);
+                            c.yR[e] = yn;
+                            c.aR[e] += yn;
+                        } else {
+                            sup += cr_support(yR[k], lo, hi);
+                            viol = fmax(viol, cr_violation(rowv, lo, hi));
+                        }
+                    }
+                }
+            }
+        }
+        if (bud) {
+            for (int d = 32; d > 0; d >>= 1) lsum += __shfl_xor(lsum, d);      // (a + b = b + a: every lane holds the same bits)
+            if (lane == 0) wsum[wv] = lsum;
+            __syncthreads();
+            if (tid == 0) {                                   // (wsum is written again only behind the next row's first barrier)
+                const double total = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+                if (ITER) {
+                    const double yn = cr_prox(yQ, cr_sigma_budget(T, w), total, e_min, e_max);
+                    c.yQ[g] = yn;
+                    c.aQ[g] += yn;
+                } else {
+                    sup += cr_support(yQ, e_min, e_max);
+                    viol = fmax(viol, cr_violation(total, e_min, e_max));
+                }
+            }
+        }
+    }
+    if (!ITER) {
+        for (int d = 32; d > 0; d >>= 1) {
+            cost += __shfl_xor(cost, d); dpart += __shfl_xor(dpart, d); sup += __shfl_xor(sup, d);
+            viol = fmax(viol, __shfl_xor(viol, d));
+        }
+        if (lane == 0) { redm[wv][0] = cost; redm[wv][1] = dpart; redm[wv][2] = sup; redm[wv][3] = viol; }
+        __syncthreads();
+        if (tid == 0) {
+            v.part_gcost[blockIdx.x] = (redm[0][0] + redm[1][0]) + (redm[2][0] + redm[3][0]);
+            c.m_rows[3 * blockIdx.x + 0] = (redm[0][1] + redm[1][1]) + (redm[2][1] + redm[3][1]);
+            c.m_rows[3 * blockIdx.x + 1] = (redm[0][2] + redm[1][2]) + (redm[2][2] + redm[3][2]);
+            c.m_rows[3 * blockIdx.x + 2] = fmax(fmax(redm[0][3], redm[1][3]), fmax(redm[2][3], redm[3][3]));
+        }
+    }
+}
+
 // balance and flow rows of one timestep from the nodal sums in v.cons. ITER: the multipliers' steps (balance: free;
 // flows: proximal step of the interval's support function) and running sums. !ITER: worst violations and the dual
 // objective's terms -yb d_tot - sum |yf| f_max of the candidate scale * (yb, yf).
@@ -558,7 +866,9 @@ template <bool ITER>
 static void launch_gen(const CentralView &c, const Plan &p, const double *X, const double *XR, const double *XQ, double scale, hipStream_t s)
 {
     if (!c.v.nGenItems) return;
-    if (c.rows_in)
+    if (c.rows_in && c.longRows)            // (T > 512, or DOPF_F_DEBUG_LONG_STO: the whole block on one row, tile after tile)
+        with_bool(p.genAvail, [&](auto av) { hipLaunchKernelGGL((kc_gen_rows_long<ITER, decltype(av)::value>), dim3(c.v.nGenItems), dim3(256), 0, s, c, X, XR, XQ, scale); });
+    else if (c.rows_in)
         with_bool(p.genAvail, [&](auto av) { hipLaunchKernelGGL((kc_gen_rows<ITER, decltype(av)::value>), dim3(c.v.nGenItems), dim3(256), 0, s, c, X, XR, XQ, scale); });
     else
         with_bool(p.genAvail, [&](auto av) { hipLaunchKernelGGL((kc_gen<ITER, decltype(av)::value>), dim3(c.v.nGenItems), dim3(512), 0, s, c, X, scale); });
@@ -575,7 +885,9 @@ template <bool ITER>
 static void launch_sto(const CentralView &c, const Plan &p, const double *XD, const double *XC, const double *XE, double scale, hipStream_t s)
 {
     if (!c.v.nStoItems) return;
-    with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((kc_sto<ITER, decltype(lv)::value>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale); });
+    if (p.stoLong)                          // (T > 512, or DOPF_F_DEBUG_LONG_STO: one block per storage, tile after tile)
+        with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((kc_sto_long<ITER, decltype(lv)::value>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale); });
+    else with_lv(p.stoLV, [&](auto lv) { hipLaunchKernelGGL((kc_sto<ITER,decltype(lv)::value>), dim3(c.v.nStoItems), dim3(256), 0, s, c, XD, XC, XE, scale); });
 }
 
 void central_launch_iteration(const CentralView &c, const Plan &p, const DevView &vreduce, hipStream_t s)

@@ -147,7 +147,8 @@ sharded over that many devices inside the library, one RCCL all-reduce per itera
 library, a few microseconds instead of tens for the small vector of a copper plate), `record`, and the
 reference's literals `w_flow = 10`, `w_prox = 1`, `eps = 1e-3`, `mask_thr = 1e-2`.
 Storages on horizons beyond 512 timesteps (an hourly year: T = 8 760) need `flags = DOPF_F_LONG_HORIZON`
-(the long-horizon storage body; without the flag the library refuses them). Networks of more than 2 048 lines
+(the long-horizon storage body; without the flag the library refuses them). The central references on the device
+(`central_reference`, `central_reference_coupled`) take such horizons without any flag. Networks of more than 2 048 lines
 need `flags = DOPF_F_WIDE_NETWORK` (the wide-network chain; without it the library refuses them). Storages that start a
 horizon from a given level (see `set_initial_levels!`) need `flags = DOPF_F_STO_INITIAL_LEVEL`; storages whose level after the
 last timestep is bounded (see `set_terminal_levels!`) need `flags = DOPF_F_STO_TERMINAL_LEVEL`; generators that follow an

@@ -508,7 +508,10 @@ int dopf_roll_horizon(dopf_ctx *ctx, int32_t k, const double *demand_tail /* N x
  * nodal_price[N*T] = lambda + sum_l (dual FlowUpper + dual FlowLower)[l,t] ptdf[l,:]; line_utilization[L*T] = ptdf * I;
  * flow_upper_dual[L*T] = dual.(FlowUpper), flow_lower_dual[L*T] = dual.(FlowLower) (opf_central_reference.jl:71-79: both are
  * d objective / d max_capacity <= 0, non-zero only where that limit binds). None of the three entries below takes the rating
- * table of DOPF_F_LINE_RATING: they solve with f_max in every timestep (a DOPF_F_LINE_RATING bit in q changes nothing). */
+ * table of DOPF_F_LINE_RATING: they solve with f_max in every timestep (a DOPF_F_LINE_RATING bit in q changes nothing).
+ * All four entries take any horizon and need no flag for it: beyond T = 512 the rows that couple timesteps (storage levels, ramps,
+ * budgets) run on the long sweeps (csrc/central_long.h), and the entry sets DOPF_F_LONG_HORIZON on its own context itself — what counts
+ * is the shape. With the flag in q and without it the results are the same bits; the horizon is bounded by device memory alone. */
 typedef struct dopf_central_result {
     double objective, dual_objective, primal_infeasibility, gap;
     int32_t iterations, converged;
@@ -569,7 +572,7 @@ int dopf_central_solve_lossy(const dopf_problem *p, const dopf_params *q,
  * must fit under them, both under the availability table of this same call — except that budgets and ramps may be given together
  * (two coupling rows are nothing to an LP; only the decentral step refuses the pair). ramp_up without ramp_down (or the reverse),
  * tol <= 0 and max_iters < 1 are refused before a device is looked for. A refusal's message names this entry, and no output is written.
- * Horizons beyond T = 512 are refused with ramps or budgets (DOPF_E_UNSUPPORTED). The flags of q that name these extensions are
+ * Ramps and budgets are taken on any horizon, beyond T = 512 too, with no flag in q. The flags of q that name these extensions are
  * ignored, as by the other entries: what counts is the arrays. Two more outputs, both d objective / d right-hand side like the flow
  * duals — negative where the row's upper end binds, positive where its lower end binds, 0 where neither does or the row does not exist:
  *   ramp_dual[T*G]   [t + T*g]: the ramp row between t - 1 and t (t = 0: the anchor's row)
