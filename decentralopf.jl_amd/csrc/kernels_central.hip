@@ -27,16 +27,24 @@
 //               central_rows.h) — and the flow rows' limits from a rating table (kc_dual<., true>).
 //   horizons    kc_sto and kc_gen_rows hold a row in one wave's registers: T <= 512. Beyond it (every entry, no flag to set) kc_sto_long
 //               and kc_gen_rows_long walk a row in tiles of 2048 timesteps with a whole block (central_long.h).
+//   one text    A one-wave sweep and its long twin differ in who owns which timestep, how a neighbour's value arrives (a shuffle; LDS
+//               and a tile carry) and how the item's sums are kept (a per-lane acc[]; part[t]). Everything else exists once: the level
+//               rows' arithmetic in central_sto.h and the generator rows' in central_rows.h (plain C++, pinned on the CPU), a slot's
+//               loads, stores and metrics in sto_primal_slot / sto_level_slot and gen_column_slot / gen_ramp_slot / gen_budget_row,
+//               the reductions in block_tree_sum / block_tree_max, block_metrics and item_sums_store.
 //   outputs     objective, P, D, C, E; system price = -yb (dual(EB) of the reference), nodal price = -(yb + ptdf' yf)
 //               (src/opf_central_reference.jl:66-79).
 #include <algorithm>
 
 #include "central_long.h"
+#include "central_sto.h"
 #include "dopf_internal.h"
 
 namespace dopf {
 
-__device__ __forceinline__ double cclamp(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+constexpr int KMAX = 8;                     // timesteps per lane in the one-wave sweeps (kc_sto, kc_gen_rows)
+static_assert(kCentralWaveHorizon == 64 * KMAX, "dopf_central.hip switches to the long sweeps where a wave's registers end");
+static_assert(kClSlots == 8, "the long sweeps' slot loops and the hand-over of yR[t+1] are written for 8 slots per thread");
 
 // inclusive prefix sum over the 64 lanes of a wave
 __device__ __forceinline__ double wave_prefix(double x, int lane)
@@ -46,6 +54,70 @@ __device__ __forceinline__ double wave_prefix(double x, int lane)
         if (lane >= d) x += y;
     }
     return x;
+}
+
+// sum / maximum of x over the block's NT threads through red[NT], pairs at strides NT/2, NT/4, ... 1; the same bits in every thread.
+// again: red is written again after the call (one more barrier).
+template <int NT>
+__device__ __forceinline__ double block_tree_sum(double *red, int tid, double x, bool again)
+{
+    red[tid] = x;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
+    const double r = red[0];
+    if (again) __syncthreads();
+    return r;
+}
+
+template <int NT>
+__device__ __forceinline__ double block_tree_max(double *red, int tid, double x, bool again)
+{
+    red[tid] = x;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) { if (tid < s) red[tid] = fmax(red[tid], red[tid + s]); __syncthreads(); }
+    const double r = red[0];
+    if (again) __syncthreads();
+    return r;
+}
+
+// the !ITER tail of the four row sweeps: four per-thread values over the block's four waves in a fixed order (an xor reduction in the
+// wave, then (w0 + w1) + (w2 + w3) by thread 0), value MAXI a maximum and the others sums. On return thread 0 holds the block's four.
+template <int MAXI>
+__device__ __forceinline__ void block_metrics(double (&m)[4], double (*redm)[4], int tid)
+{
+    const int lane = tid & 63, wv = tid >> 6;
+    for (int d = 32; d > 0; d >>= 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const double o = __shfl_xor(m[i], d);
+            m[i] = i == MAXI ? fmax(m[i], o) : m[i] + o;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) redm[wv][i] = m[i];
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            m[i] = i == MAXI ? fmax(fmax(redm[0][i], redm[1][i]), fmax(redm[2][i], redm[3][i]))
+                             : (redm[0][i] + redm[1][i]) + (redm[2][i] + redm[3][i]);
+    }
+}
+
+// the one-wave sweeps' item sums: part[item][t] (part: v.part_sinj or v.part_ginj) = the four waves' acc of timestep t, added in a fixed
+// order (lane ln's slot k is t = ln K + k)
+__device__ __forceinline__ void item_sums_store(const double (&acc)[KMAX], double (*red)[64 * KMAX], double *part, int K, int T, int tid, int lane,
+                                                int wv)
+{
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) red[wv][lane * KMAX + k] = acc[k];
+    __syncthreads();
+    for (int i = tid; i < 64 * KMAX; i += 256) {
+        const int ln = i / KMAX, k = i - ln * KMAX, t = ln * K + k;
+        if (k < K && t < T) part[(size_t)blockIdx.x * T + t] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    }
 }
 
 // pi[n,t] = yb[t] + sum_l ptdf[l,n] yf[l,t]   (the column of K' every unit at node n sees), candidate = scale * (yb, yf)
@@ -99,7 +171,7 @@ __global__ __launch_bounds__(512) void kc_gen(CentralView c, const double *X, do
                 if constexpr (AV) pm = avail_cap(ftab, T, prof[g], pm, t);
                 if (ITER) {
                     const double x0 = v.P[e];
-                    const double xn = cclamp(x0 - tau * (mc + pi), 0.0, pm);
+                    const double xn = cs_clamp(x0 - tau * (mc + pi), 0.0, pm);
                     v.P[e] = xn;
                     c.aP[e] += xn;
                     acc += 2.0 * xn - x0;
@@ -121,15 +193,83 @@ __global__ __launch_bounds__(512) void kc_gen(CentralView c, const double *X, do
         __syncthreads();
     }
     if (!ITER) {
-        red[tid] = cost;
-        __syncthreads();
-        for (int sft = 256; sft > 0; sft >>= 1) { if (tid < sft) red[tid] += red[tid + sft]; __syncthreads(); }
-        if (tid == 0) v.part_gcost[blockIdx.x] = red[0];
-        __syncthreads();
-        red[tid] = dpart;
-        __syncthreads();
-        for (int sft = 256; sft > 0; sft >>= 1) { if (tid < sft) red[tid] += red[tid + sft]; __syncthreads(); }
-        if (tid == 0) c.m_gen[blockIdx.x] = red[0];
+        const double csum = block_tree_sum<512>(red, tid, cost, true), dsum = block_tree_sum<512>(red, tid, dpart, false);
+        if (tid == 0) { v.part_gcost[blockIdx.x] = csum; c.m_gen[blockIdx.x] = dsum; }
+    }
+}
+
+// ---- the storage sweeps' slots: what kc_sto and kc_sto_long do for one (storage, timestep), the arithmetic from central_sto.h. The
+// kernels keep what differs: who owns t, how the scans' sums arrive, how the item's injections are accumulated. --------------------------
+struct StoMetrics {
+    double cost = 0.0, dpart = 0.0, viol = 0.0, yterm = 0.0;
+};
+
+// the item's cost and c.m_sto[3 item ..]: reduced-cost term, worst level violation, support term
+__device__ __forceinline__ void sto_metrics_store(const CentralView &c, const StoMetrics &m, double (*redm)[4], int tid)
+{
+    double r[4] = {m.cost, m.dpart, m.viol, m.yterm};
+    block_metrics<2>(r, redm, tid);
+    if (tid == 0) {
+        c.v.part_scost[blockIdx.x] = r[0];
+        c.m_sto[3 * blockIdx.x + 0] = r[1];
+        c.m_sto[3 * blockIdx.x + 1] = r[2];
+        c.m_sto[3 * blockIdx.x + 2] = r[3];
+    }
+}
+
+template <int LV>
+__device__ __forceinline__ StoRow sto_row_load(const DevView &v, int s)
+{
+    const double mc = v.sto_mc[s], pm = v.sto_pmax[s], em = v.sto_emax[s];
+    StoRow r{mc, pm, em, 0.0, 0.0, em, 1.0, 1.0};
+    if constexpr (LV >= 1) r.e0 = sto_e0(v)[s];                                          // the level before timestep 0
+    if constexpr (LV >= 2) { r.elo = sto_end_lo(v)[s]; r.ehi = sto_end_hi(v)[s]; }       // the band of the last one
+    if constexpr (LV == 3) { r.al = sto_eff_alpha(v)[s]; r.be = sto_eff_beta(v)[s]; }    // 1 / eta_d, eta_c
+    return r;
+}
+
+// the columns of timestep t, suf = sum_{tau >= t} yE. ITER: D+, C+ into dn, cn. !ITER: the candidate's cost, reduced-cost and support
+// terms into m. Either way dnet is what the slot adds to the level and the injection D - C is returned (ITER: both of the
+// extrapolated point).
+template <bool ITER, int LV>
+__device__ __forceinline__ double sto_primal_slot(const CentralView &c, int node, const StoRow &r, double absH, int t, double suf, double yE,
+                                                  double d0, double c0, double &dn, double &cn, double &dnet, StoMetrics &m)
+{
+    const int T = c.v.T;
+    double rD, rC;
+    cs_reduced_costs<LV>(r, c.pi[node + (size_t)c.v.N * t], suf, rD, rC);
+    if (ITER) {
+        cs_column_steps<LV>(r, absH, c.w, T, t, d0, c0, rD, rC, dn, cn);
+        const double bd = cs_extra(dn, d0), bc = cs_extra(cn, c0);
+        dnet = cs_net<LV>(r, bd, bc);
+        return bd - bc;
+    }
+    dnet = cs_net<LV>(r, d0, c0);
+    m.cost += r.mc * (d0 + c0);
+    m.dpart += cs_rc_term(rD, rC, r.pm);
+    m.yterm = cs_support<LV>(r, yE, t, T, m.yterm);
+    return d0 - c0;
+}
+
+// the level row of timestep t at element offset e = s T + t; lev: the level before t on entry, after t on return. ITER: the multiplier's
+// proximal step, the slot's stores and running sums. !ITER: the candidate's level to v.E, its violation into m.
+template <bool ITER, int LV>
+__device__ __forceinline__ void sto_level_slot(const CentralView &c, const StoRow &r, size_t e, int t, double yE, double d0, double c0,
+                                               double dn, double cn, double &lev, StoMetrics &m)
+{
+    const DevView &v = c.v;
+    const int T = v.T;
+    if (ITER) {
+        lev += cs_net<LV>(r, cs_extra(dn, d0), cs_extra(cn, c0));
+        const double sg = cs_sigma<LV>(r, c.w, t);
+        const double yn = cs_prox<LV>(r, yE + sg * lev, sg, t, T);
+        v.D[e] = dn; v.C[e] = cn;
+        c.yE[e] = yn;
+        c.aD[e] += dn; c.aC[e] += cn; c.aE[e] += yn;
+    } else {
+        lev += cs_net<LV>(r, d0, c0);
+        v.E[e] = lev;
+        m.viol = fmax(m.viol, cs_violation<LV>(r, lev, t, T));
     }
 }
 
@@ -153,26 +293,20 @@ __global__ __launch_bounds__(512) void kc_gen(CentralView c, const double *X, do
 template <bool ITER, int LV = 0>
 __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, const double *XC, const double *XE, double scale)
 {
-    constexpr int KMAX = 8;
-    __shared__ double red[4][512];
+    __shared__ double red[4][64 * KMAX];
     __shared__ double redm[4][4];
     const DevView &v = c.v;
     const Item it = v.sto_items[blockIdx.x];
-    const int T = v.T, N = v.N;
+    const int T = v.T;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int K = (T + 63) / 64, t0 = lane * K;
     double acc[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
-    double cost = 0.0, dpart = 0.0, viol = 0.0, yterm = 0.0;
+    StoMetrics m;
     const double absH = c.absHn[it.node];
     for (int s = it.a0 + wv; s < it.a1; s += 4) {           // (wave-uniform trip count per wave)
-        const double mc = v.sto_mc[s], pm = v.sto_pmax[s], em = v.sto_emax[s];
-        double e0 = 0.0, elo = 0.0, ehi = em;                 // LV: the level before timestep 0, the band of the last one
-        if constexpr (LV >= 1) e0 = sto_e0(v)[s];
-        if constexpr (LV >= 2) { elo = sto_end_lo(v)[s]; ehi = sto_end_hi(v)[s]; }
-        [[maybe_unused]] double al = 1.0, be = 1.0;           // LV 3: 1 / eta_d, eta_c
-        if constexpr (LV == 3) { al = sto_eff_alpha(v)[s]; be = sto_eff_beta(v)[s]; }
+        const StoRow r = sto_row_load<LV>(v, s);
         double yE[KMAX], d0[KMAX], c0[KMAX];
         double ysum = 0.0;
 #pragma unroll
@@ -197,96 +331,111 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
             if (k < K && t < T) {
                 const double suf = total - before;            // sum_{tau >= t} yE
                 before += yE[k];
-                const double pi = c.pi[it.node + (size_t)N * t];
-                double rD, rC;
-                if constexpr (LV == 3) { rD = mc + pi - al * suf; rC = mc - pi + be * suf; }
-                else { rD = mc + pi - suf; rC = mc - pi + suf; }
-                if (ITER) {
-                    if constexpr (LV == 3) {
-                        const double tauD = 1.0 / ((1.0 + absH + al * (double)(T - t)) * c.w);
-                        const double tauC = 1.0 / ((1.0 + absH + be * (double)(T - t)) * c.w);
-                        dn[k] = cclamp(d0[k] - tauD * rD, 0.0, pm);
-                        cn[k] = cclamp(c0[k] - tauC * rC, 0.0, pm);
-                    } else {
-                        const double tau = 1.0 / ((1.0 + absH + (double)(T - t)) * c.w);
-                        dn[k] = cclamp(d0[k] - tau * rD, 0.0, pm);
-                        cn[k] = cclamp(c0[k] - tau * rC, 0.0, pm);
-                    }
-                    const double bd = 2.0 * dn[k] - d0[k], bc = 2.0 * cn[k] - c0[k];
-                    acc[k] += bd - bc;
-                    if constexpr (LV == 3) net += be * bc - al * bd;
-                    else net += bc - bd;
-                } else {
-                    acc[k] += d0[k] - c0[k];
-                    if constexpr (LV == 3) net += be * c0[k] - al * d0[k];
-                    else net += c0[k] - d0[k];
-                    cost += mc * (d0[k] + c0[k]);
-                    dpart += (fmin(rD, 0.0) + fmin(rC, 0.0)) * pm;
-                    if constexpr (LV == 0) yterm += fmax(yE[k], 0.0) * em;
-                    else {
-                        const bool last = LV >= 2 && t == T - 1;
-                        // (two fused steps, the first the one of LV 0: with e0 = 0 and the default band the same bits)
-                        yterm = fma(fmax(yE[k], 0.0), (last ? ehi : em) - e0, yterm);
-                        yterm = fma(fmin(yE[k], 0.0), (last ? elo : 0.0) - e0, yterm);
-                    }
-                }
+                double dnet;
+                acc[k] += sto_primal_slot<ITER, LV>(c, it.node, r, absH, t, suf, yE[k], d0[k], c0[k], dn[k], cn[k], dnet, m);
+                net += dnet;
             }
         }
         const double inclE = wave_prefix(net, lane);
         double lev = inclE - net;                             // level before this lane's first step
-        if constexpr (LV >= 1) lev += e0;
+        if constexpr (LV >= 1) lev += r.e0;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             const int t = t0 + k;
-            if (k < K && t < T) {
-                const size_t e = (size_t)s * T + t;
-                if (ITER) {
-                    double sg;
-                    if constexpr (LV == 3) {
-                        lev += be * (2.0 * cn[k] - c0[k]) - al * (2.0 * dn[k] - d0[k]);
-                        sg = c.w / ((al + be) * (double)(t + 1));
-                    } else {
-                        lev += (2.0 * cn[k] - c0[k]) - (2.0 * dn[k] - d0[k]);
-                        sg = c.w / (2.0 * (double)(t + 1));
-                    }
-                    const double z = yE[k] + sg * lev;
-                    double yn;
-                    if constexpr (LV >= 2) { const bool last = t == T - 1; yn = z - sg * cclamp(z / sg, last ? elo : 0.0, last ? ehi : em); }
-                    else yn = z - sg * cclamp(z / sg, 0.0, em);
-                    v.D[e] = dn[k]; v.C[e] = cn[k];
-                    c.yE[e] = yn;
-                    c.aD[e] += dn[k]; c.aC[e] += cn[k]; c.aE[e] += yn;
-                } else {
-                    if constexpr (LV == 3) lev += be * c0[k] - al * d0[k];
-                    else lev += c0[k] - d0[k];
-                    v.E[e] = lev;
-                    if constexpr (LV >= 2) { const bool last = t == T - 1; viol = fmax(viol, fmax((last ? elo : 0.0) - lev, lev - (last ? ehi : em))); }
-                    else viol = fmax(viol, fmax(-lev, lev - em));
-                }
-            }
+            if (k < K && t < T) sto_level_slot<ITER, LV>(c, r, (size_t)s * T + t, t, yE[k], d0[k], c0[k], dn[k], cn[k], lev, m);
         }
     }
-    // per-item sums over the block's four waves (fixed order)
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) red[wv][lane * KMAX + k] = acc[k];
-    __syncthreads();
-    for (int i = tid; i < 64 * KMAX; i += 256) {
-        const int ln = i / KMAX, k = i - ln * KMAX, t = ln * K + k;
-        if (k < K && t < T) v.part_sinj[(size_t)blockIdx.x * T + t] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    item_sums_store(acc, red, v.part_sinj, K, T, tid, lane, wv);
+    if (!ITER) sto_metrics_store(c, m, redm, tid);
+}
+
+// ---- the generator row sweeps' slots: what kc_gen_rows and kc_gen_rows_long do for one (generator, timestep) and for a budget row, the
+// arithmetic from central_rows.h. The kernels keep what differs: who owns t, how yR[t+1] and xb[t-1] arrive, how the sums are kept. ------
+struct GenRow {
+    double mc, pm, ru, rd, prev, e_min, e_max, yQ;
+    bool ramp, anch, bud;                   // (uniform over the threads that work on the row)
+};
+
+struct RowMetrics {
+    double cost = 0.0, dpart = 0.0, sup = 0.0, viol = 0.0;
+};
+
+// the item's cost and c.m_rows[3 item ..]: reduced-cost term, the rows' support terms, their worst violation
+__device__ __forceinline__ void row_metrics_store(const CentralView &c, const RowMetrics &m, double (*redm)[4], int tid)
+{
+    double r[4] = {m.cost, m.dpart, m.sup, m.viol};
+    block_metrics<3>(r, redm, tid);
+    if (tid == 0) {
+        c.v.part_gcost[blockIdx.x] = r[0];
+        c.m_rows[3 * blockIdx.x + 0] = r[1];
+        c.m_rows[3 * blockIdx.x + 1] = r[2];
+        c.m_rows[3 * blockIdx.x + 2] = r[3];
     }
-    if (!ITER) {
-        for (int d = 32; d > 0; d >>= 1) {
-            cost += __shfl_xor(cost, d); dpart += __shfl_xor(dpart, d); yterm += __shfl_xor(yterm, d);
-            viol = fmax(viol, __shfl_xor(viol, d));
-        }
-        if (lane == 0) { redm[wv][0] = cost; redm[wv][1] = dpart; redm[wv][2] = viol; redm[wv][3] = yterm; }
-        __syncthreads();
-        if (tid == 0) {
-            v.part_scost[blockIdx.x] = (redm[0][0] + redm[1][0]) + (redm[2][0] + redm[3][0]);
-            c.m_sto[3 * blockIdx.x + 0] = (redm[0][1] + redm[1][1]) + (redm[2][1] + redm[3][1]);
-            c.m_sto[3 * blockIdx.x + 1] = fmax(fmax(redm[0][2], redm[1][2]), fmax(redm[2][2], redm[3][2]));
-            c.m_sto[3 * blockIdx.x + 2] = (redm[0][3] + redm[1][3]) + (redm[2][3] + redm[3][3]);
-        }
+}
+
+template <bool ITER>
+__device__ __forceinline__ GenRow gen_row_load(const CentralView &c, const double *XQ, double scale, int g)
+{
+    const size_t G = (size_t)c.v.G;
+    GenRow r;
+    r.mc = c.v.gen_mc[g]; r.pm = c.v.gen_pmax[g];
+    r.ru = c.rows_in[g]; r.rd = c.rows_in[G + g]; r.prev = c.rows_in[2 * G + g];
+    r.e_min = c.rows_in[3 * G + g]; r.e_max = c.rows_in[4 * G + g];
+    r.ramp = cr_has_ramp(r.ru, r.rd, r.prev); r.anch = cr_anchored(r.prev); r.bud = cr_has_budget(r.e_min, r.e_max);
+    r.yQ = r.bud ? (ITER ? c.yQ[g] : scale * XQ[g]) : 0.0;
+    return r;
+}
+
+// the column of timestep t at element offset e = g T + t; y_next: yR[t+1] as the caller found it (read only where t + 1 < T).
+// ITER: x+ stored, the extrapolated point returned. !ITER: the candidate's cost and reduced-cost term into m, x returned.
+template <bool ITER>
+__device__ __forceinline__ double gen_column_slot(const CentralView &c, int node, const GenRow &r, double absH, size_t e, int t, double x0,
+                                                  double yR, double y_next, double cap, RowMetrics &m)
+{
+    const int T = c.v.T;
+    if (t + 1 >= T) y_next = 0.0;
+    const double rc = cr_reduced_cost(r.mc, c.pi[node + (size_t)c.v.N * t], yR, y_next, r.yQ);
+    if (ITER) {
+        const double tau = cr_tau(absH, cr_ramp_rows_at(t, T, r.ramp, r.anch), r.bud ? 1 : 0, c.w);
+        const double xn = cr_column_step(x0, tau, rc, cap);
+        c.v.P[e] = xn;
+        c.aP[e] += xn;
+        return 2.0 * xn - x0;
+    }
+    m.cost += r.mc * x0;
+    m.dpart += cr_rc_term(rc, cap);
+    return x0;
+}
+
+// ramp row t (t >= 1, or t = 0 with an anchor) of a generator with ramp rows; xb: the column slot's value at t, x_left: at t - 1
+// (t = 0: not read). ITER: the multiplier's proximal step. !ITER: the row's support term and violation into m.
+template <bool ITER>
+__device__ __forceinline__ void gen_ramp_slot(const CentralView &c, const GenRow &r, size_t e, int t, double yR, double xb, double x_left,
+                                              RowMetrics &m)
+{
+    const double row = t >= 1 ? xb - x_left : xb;
+    const double lo = cr_ramp_lo(t, r.rd, r.prev), hi = cr_ramp_hi(t, r.ru, r.prev);
+    if (ITER) {
+        const double yn = cr_prox(yR, cr_sigma_ramp(t, c.w), row, lo, hi);
+        c.yR[e] = yn;
+        c.aR[e] += yn;
+    } else {
+        m.sup += cr_support(yR, lo, hi);
+        m.viol = fmax(m.viol, cr_violation(row, lo, hi));
+    }
+}
+
+// the budget row of generator g, total = sum_t xb[t]; one thread per row calls it
+template <bool ITER>
+__device__ __forceinline__ void gen_budget_row(const CentralView &c, const GenRow &r, int g, double total, RowMetrics &m)
+{
+    if (ITER) {
+        const double yn = cr_prox(r.yQ, cr_sigma_budget(c.v.T, c.w), total, r.e_min, r.e_max);
+        c.yQ[g] = yn;
+        c.aQ[g] += yn;
+    } else {
+        m.sup += cr_support(r.yQ, r.e_min, r.e_max);
+        m.viol = fmax(m.viol, cr_violation(total, r.e_min, r.e_max));
     }
 }
 
@@ -304,29 +453,23 @@ __global__ __launch_bounds__(256) void kc_sto(CentralView c, const double *XD, c
 template <bool ITER, bool AV = false>
 __global__ __launch_bounds__(256) void kc_gen_rows(CentralView c, const double *X, const double *XR, const double *XQ, double scale)
 {
-    constexpr int KMAX = 8;
-    __shared__ double red[4][512];
+    __shared__ double red[4][64 * KMAX];
     __shared__ double redm[4][4];
     const DevView &v = c.v;
     const Item it = v.gen_items[blockIdx.x];
-    const int T = v.T, N = v.N;
-    const size_t G = (size_t)v.G;
+    const int T = v.T;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int K = (T + 63) / 64, t0 = lane * K;
     double acc[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
-    double cost = 0.0, dpart = 0.0, sup = 0.0, viol = 0.0;
-    const double absH = c.absHn[it.node], w = c.w;
+    RowMetrics m;
+    const double absH = c.absHn[it.node];
     const double *ftab = nullptr;
     const int *prof = nullptr;
     if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
     for (int g = it.a0 + wv; g < it.a1; g += 4) {           // (wave-uniform trip count per wave)
-        const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
-        const double ru = c.rows_in[g], rd = c.rows_in[G + g], prev = c.rows_in[2 * G + g];
-        const double e_min = c.rows_in[3 * G + g], e_max = c.rows_in[4 * G + g];
-        const bool ramp = cr_has_ramp(ru, rd, prev), anch = cr_anchored(prev), bud = cr_has_budget(e_min, e_max);      // (wave-uniform)
-        const double yQ = bud ? (ITER ? c.yQ[g] : scale * XQ[g]) : 0.0;
+        const GenRow r = gen_row_load<ITER>(c, XQ, scale, g);
         double x0[KMAX], yR[KMAX], cap[KMAX], xb[KMAX];
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
@@ -334,9 +477,9 @@ __global__ __launch_bounds__(256) void kc_gen_rows(CentralView c, const double *
             const bool ok = k < K && t < T;
             const size_t e = (size_t)g * T + (ok ? t : 0);
             x0[k] = ok ? (ITER ? v.P[e] : scale * X[e]) : 0.0;
-            yR[k] = ok && ramp ? (ITER ? c.yR[e] : scale * XR[e]) : 0.0;
-            cap[k] = pm;
-            if constexpr (AV) cap[k] = avail_cap(ftab, T, prof[g], pm, ok ? t : 0);
+            yR[k] = ok && r.ramp ? (ITER ? c.yR[e] : scale * XR[e]) : 0.0;
+            cap[k] = r.pm;
+            if constexpr (AV) cap[k] = avail_cap(ftab, T, prof[g], r.pm, ok ? t : 0);
         }
         const double y_lane = __shfl_down(yR[0], 1);          // yR of the first step of the next lane (lane 63: never read, t + 1 = T there)
         double lsum = 0.0, last = 0.0;
@@ -345,82 +488,29 @@ __global__ __launch_bounds__(256) void kc_gen_rows(CentralView c, const double *
             const int t = t0 + k;
             xb[k] = 0.0;
             if (k < K && t < T) {
-                double y_next = k + 1 < K ? yR[k + 1 < KMAX ? k + 1 : k] : y_lane;
-                if (t + 1 >= T) y_next = 0.0;
-                const double rc = cr_reduced_cost(mc, c.pi[it.node + (size_t)N * t], yR[k], y_next, yQ);
-                if (ITER) {
-                    const double tau = cr_tau(absH, cr_ramp_rows_at(t, T, ramp, anch), bud ? 1 : 0, w);
-                    const double xn = cr_column_step(x0[k], tau, rc, cap[k]);
-                    const size_t e = (size_t)g * T + t;
-                    v.P[e] = xn;
-                    c.aP[e] += xn;
-                    xb[k] = 2.0 * xn - x0[k];
-                } else {
-                    xb[k] = x0[k];
-                    cost += mc * x0[k];
-                    dpart += cr_rc_term(rc, cap[k]);
-                }
+                const double y_next = k + 1 < K ? yR[k + 1 < KMAX ? k + 1 : k] : y_lane;
+                xb[k] = gen_column_slot<ITER>(c, it.node, r, absH, (size_t)g * T + t, t, x0[k], yR[k], y_next, cap[k], m);
                 acc[k] += xb[k];
                 lsum += xb[k];
             }
             if (k == K - 1) last = xb[k];
         }
-        if (ramp) {
+        if (r.ramp) {
             const double x_lane = __shfl_up(last, 1);         // the step before this lane's first (lane 0: t = 0 has no difference)
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) {
                 const int t = t0 + k;
-                if (k < K && t < T && (t >= 1 || anch)) {
-                    const double row = t >= 1 ? xb[k] - (k >= 1 ? xb[k >= 1 ? k - 1 : 0] : x_lane) : xb[k];
-                    const double lo = cr_ramp_lo(t, rd, prev), hi = cr_ramp_hi(t, ru, prev);
-                    if (ITER) {
-                        const size_t e = (size_t)g * T + t;
-                        const double yn = cr_prox(yR[k], cr_sigma_ramp(t, w), row, lo, hi);
-                        c.yR[e] = yn;
-                        c.aR[e] += yn;
-                    } else {
-                        sup += cr_support(yR[k], lo, hi);
-                        viol = fmax(viol, cr_violation(row, lo, hi));
-                    }
-                }
+                if (k < K && t < T && (t >= 1 || r.anch))
+                    gen_ramp_slot<ITER>(c, r, (size_t)g * T + t, t, yR[k], xb[k], k >= 1 ? xb[k >= 1 ? k - 1 : 0] : x_lane, m);
             }
         }
-        if (bud) {
+        if (r.bud) {
             for (int d = 32; d > 0; d >>= 1) lsum += __shfl_xor(lsum, d);      // (a + b = b + a: every lane holds the same bits)
-            if (lane == 0) {
-                if (ITER) {
-                    const double yn = cr_prox(yQ, cr_sigma_budget(T, w), lsum, e_min, e_max);
-                    c.yQ[g] = yn;
-                    c.aQ[g] += yn;
-                } else {
-                    sup += cr_support(yQ, e_min, e_max);
-                    viol = fmax(viol, cr_violation(lsum, e_min, e_max));
-                }
-            }
+            if (lane == 0) gen_budget_row<ITER>(c, r, g, lsum, m);
         }
     }
-    // per-item sums over the block's four waves (fixed order)
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) red[wv][lane * KMAX + k] = acc[k];
-    __syncthreads();
-    for (int i = tid; i < 64 * KMAX; i += 256) {
-        const int ln = i / KMAX, k = i - ln * KMAX, t = ln * K + k;
-        if (k < K && t < T) v.part_ginj[(size_t)blockIdx.x * T + t] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-    }
-    if (!ITER) {
-        for (int d = 32; d > 0; d >>= 1) {
-            cost += __shfl_xor(cost, d); dpart += __shfl_xor(dpart, d); sup += __shfl_xor(sup, d);
-            viol = fmax(viol, __shfl_xor(viol, d));
-        }
-        if (lane == 0) { redm[wv][0] = cost; redm[wv][1] = dpart; redm[wv][2] = sup; redm[wv][3] = viol; }
-        __syncthreads();
-        if (tid == 0) {
-            v.part_gcost[blockIdx.x] = (redm[0][0] + redm[1][0]) + (redm[2][0] + redm[3][0]);
-            c.m_rows[3 * blockIdx.x + 0] = (redm[0][1] + redm[1][1]) + (redm[2][1] + redm[3][1]);
-            c.m_rows[3 * blockIdx.x + 1] = (redm[0][2] + redm[1][2]) + (redm[2][2] + redm[3][2]);
-            c.m_rows[3 * blockIdx.x + 2] = fmax(fmax(redm[0][3], redm[1][3]), fmax(redm[2][3], redm[3][3]));
-        }
-    }
+    item_sums_store(acc, red, v.part_ginj, K, T, tid, lane, wv);
+    if (!ITER) row_metrics_store(c, m, redm, tid);
 }
 
 // ---- the long sweeps: rows beyond T = 512 (central_long.h holds the index arithmetic, DESIGN.md 5v the design) ----------------------
@@ -442,7 +532,7 @@ __device__ __forceinline__ double block_prefix(double x, int lane, int wv, doubl
 }
 
 // storages on any horizon, in kc_sto's place when the context's plan has stoLong (T > 512, or DOPF_F_DEBUG_LONG_STO): the same LP rows,
-// step sizes and metrics, ITER, !ITER and LV with kc_sto's meaning. The reduced costs need sum_{tau >= t} yE: one read-only pass over
+// step sizes and metrics — kc_sto's slot functions — ITER, !ITER and LV with kc_sto's meaning. The reduced costs need sum_{tau >= t} yE: one read-only pass over
 // the row's yE gives the total, then ONE forward pass over the tiles takes suffix = total - prefix with the sum over the earlier tiles
 // as a carry, and in the same tile D+, C+, the extrapolated net, the level prefix (carry: the level at the end of the tile before, e0
 // in front of the first) and the multiplier's proximal step. part_sinj[item][t]: the thread that owns t stores for the item's first
@@ -455,20 +545,15 @@ __global__ __launch_bounds__(256) void kc_sto_long(CentralView c, const double *
     __shared__ double redm[4][4];
     const DevView &v = c.v;
     const Item it = v.sto_items[blockIdx.x];
-    const int T = v.T, N = v.N;
+    const int T = v.T;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int tiles = cl_tiles(T);
-    double cost = 0.0, dpart = 0.0, viol = 0.0, yterm = 0.0;
+    StoMetrics m;
     const double absH = c.absHn[it.node];
     double *part = v.part_sinj + (size_t)blockIdx.x * T;
     for (int s = it.a0; s < it.a1; ++s) {                    // (block-uniform)
         const bool first = s == it.a0;
-        const double mc = v.sto_mc[s], pm = v.sto_pmax[s], em = v.sto_emax[s];
-        double e0 = 0.0, elo = 0.0, ehi = em;                 // LV: the level before timestep 0, the band of the last one
-        if constexpr (LV >= 1) e0 = sto_e0(v)[s];
-        if constexpr (LV >= 2) { elo = sto_end_lo(v)[s]; ehi = sto_end_hi(v)[s]; }
-        [[maybe_unused]] double al = 1.0, be = 1.0;           // LV 3: 1 / eta_d, eta_c
-        if constexpr (LV == 3) { al = sto_eff_alpha(v)[s]; be = sto_eff_beta(v)[s]; }
+        const StoRow r = sto_row_load<LV>(v, s);
         const size_t row = (size_t)s * T;
         // the row's sum of yE: every thread its own slots, tile after tile, then the block's sum
         double mine = 0.0;
@@ -480,7 +565,7 @@ __global__ __launch_bounds__(256) void kc_sto_long(CentralView c, const double *
         }
         double total;
         block_prefix(mine, lane, wv, wt, total);
-        double ycarry = 0.0, lcarry = e0;                     // sum of yE over the tiles before; the level at their end
+        double ycarry = 0.0, lcarry = r.e0;                   // sum of yE over the tiles before; the level at their end
         for (int tile = 0; tile < tiles; ++tile) {
             const long long f = cl_first(tile, tid);
             double yE[NS], d0[NS], c0[NS], dn[NS], cn[NS];
@@ -506,38 +591,9 @@ __global__ __launch_bounds__(256) void kc_sto_long(CentralView c, const double *
                     const int t = (int)(f + k);
                     const double suf = total - before;        // sum_{tau >= t} yE
                     before += yE[k];
-                    const double pi = c.pi[it.node + (size_t)N * t];
-                    double rD, rC, inj;
-                    if constexpr (LV == 3) { rD = mc + pi - al * suf; rC = mc - pi + be * suf; }
-                    else { rD = mc + pi - suf; rC = mc - pi + suf; }
-                    if (ITER) {
-                        if constexpr (LV == 3) {
-                            const double tauD = 1.0 / ((1.0 + absH + al * (double)(T - t)) * c.w);
-                            const double tauC = 1.0 / ((1.0 + absH + be * (double)(T - t)) * c.w);
-                            dn[k] = cclamp(d0[k] - tauD * rD, 0.0, pm);
-                            cn[k] = cclamp(c0[k] - tauC * rC, 0.0, pm);
-                        } else {
-                            const double tau = 1.0 / ((1.0 + absH + (double)(T - t)) * c.w);
-                            dn[k] = cclamp(d0[k] - tau * rD, 0.0, pm);
-                            cn[k] = cclamp(c0[k] - tau * rC, 0.0, pm);
-                        }
-                        const double bd = 2.0 * dn[k] - d0[k], bc = 2.0 * cn[k] - c0[k];
-                        inj = bd - bc;
-                        if constexpr (LV == 3) net += be * bc - al * bd;
-                        else net += bc - bd;
-                    } else {
-                        inj = d0[k] - c0[k];
-                        if constexpr (LV == 3) net += be * c0[k] - al * d0[k];
-                        else net += c0[k] - d0[k];
-                        cost += mc * (d0[k] + c0[k]);
-                        dpart += (fmin(rD, 0.0) + fmin(rC, 0.0)) * pm;
-                        if constexpr (LV == 0) yterm += fmax(yE[k], 0.0) * em;
-                        else {
-                            const bool last = LV >= 2 && t == T - 1;
-                            yterm = fma(fmax(yE[k], 0.0), (last ? ehi : em) - e0, yterm);
-                            yterm = fma(fmin(yE[k], 0.0), (last ? elo : 0.0) - e0, yterm);
-                        }
-                    }
+                    double dnet;
+                    const double inj = sto_primal_slot<ITER, LV>(c, it.node, r, absH, t, suf, yE[k], d0[k], c0[k], dn[k], cn[k], dnet, m);
+                    net += dnet;
                     part[t] = first ? inj : part[t] + inj;
                 }
             }
@@ -549,52 +605,16 @@ __global__ __launch_bounds__(256) void kc_sto_long(CentralView c, const double *
             for (int k = 0; k < NS; ++k) {
                 if (cl_live(f, k, T)) {
                     const int t = (int)(f + k);
-                    const size_t e = row + (size_t)t;
-                    if (ITER) {
-                        double sg;
-                        if constexpr (LV == 3) {
-                            lev += be * (2.0 * cn[k] - c0[k]) - al * (2.0 * dn[k] - d0[k]);
-                            sg = c.w / ((al + be) * (double)(t + 1));
-                        } else {
-                            lev += (2.0 * cn[k] - c0[k]) - (2.0 * dn[k] - d0[k]);
-                            sg = c.w / (2.0 * (double)(t + 1));
-                        }
-                        const double z = yE[k] + sg * lev;
-                        double yn;
-                        if constexpr (LV >= 2) { const bool last = t == T - 1; yn = z - sg * cclamp(z / sg, last ? elo : 0.0, last ? ehi : em); }
-                        else yn = z - sg * cclamp(z / sg, 0.0, em);
-                        v.D[e] = dn[k]; v.C[e] = cn[k];
-                        c.yE[e] = yn;
-                        c.aD[e] += dn[k]; c.aC[e] += cn[k]; c.aE[e] += yn;
-                    } else {
-                        if constexpr (LV == 3) lev += be * c0[k] - al * d0[k];
-                        else lev += c0[k] - d0[k];
-                        v.E[e] = lev;
-                        if constexpr (LV >= 2) { const bool last = t == T - 1; viol = fmax(viol, fmax((last ? elo : 0.0) - lev, lev - (last ? ehi : em))); }
-                        else viol = fmax(viol, fmax(-lev, lev - em));
-                    }
+                    sto_level_slot<ITER, LV>(c, r, row + (size_t)t, t, yE[k], d0[k], c0[k], dn[k], cn[k], lev, m);
                 }
             }
         }
     }
-    if (!ITER) {
-        for (int d = 32; d > 0; d >>= 1) {
-            cost += __shfl_xor(cost, d); dpart += __shfl_xor(dpart, d); yterm += __shfl_xor(yterm, d);
-            viol = fmax(viol, __shfl_xor(viol, d));
-        }
-        if (lane == 0) { redm[wv][0] = cost; redm[wv][1] = dpart; redm[wv][2] = viol; redm[wv][3] = yterm; }
-        __syncthreads();
-        if (tid == 0) {
-            v.part_scost[blockIdx.x] = (redm[0][0] + redm[1][0]) + (redm[2][0] + redm[3][0]);
-            c.m_sto[3 * blockIdx.x + 0] = (redm[0][1] + redm[1][1]) + (redm[2][1] + redm[3][1]);
-            c.m_sto[3 * blockIdx.x + 1] = fmax(fmax(redm[0][2], redm[1][2]), fmax(redm[2][2], redm[3][2]));
-            c.m_sto[3 * blockIdx.x + 2] = (redm[0][3] + redm[1][3]) + (redm[2][3] + redm[3][3]);
-        }
-    }
+    if (!ITER) sto_metrics_store(c, m, redm, tid);
 }
 
 // generators under ramp and budget rows on any horizon, in kc_gen_rows' place when T > 512 (or DOPF_F_DEBUG_LONG_STO): the item's rows
-// one after another, the whole block on one row, all row arithmetic through central_rows.h as there. A ramp row couples t with t - 1 and
+// one after another, the whole block on one row, every slot through kc_gen_rows' slot functions. A ramp row couples t with t - 1 and
 // the column of t reads yR[t+1]:
 //   yR[t+1] of a thread's last slot is the next thread's first slot — or, for the tile's last thread, the next tile's — and is read
 //   from memory with the thread's own loads, BEFORE the tile's barrier; its owner writes it after that barrier (the next tile's first
@@ -612,12 +632,11 @@ __global__ __launch_bounds__(256) void kc_gen_rows_long(CentralView c, const dou
     __shared__ double redm[4][4];
     const DevView &v = c.v;
     const Item it = v.gen_items[blockIdx.x];
-    const int T = v.T, N = v.N;
-    const size_t G = (size_t)v.G;
+    const int T = v.T;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int tiles = cl_tiles(T);
-    double cost = 0.0, dpart = 0.0, sup = 0.0, viol = 0.0;
-    const double absH = c.absHn[it.node], w = c.w;
+    RowMetrics m;
+    const double absH = c.absHn[it.node];
     const double *ftab = nullptr;
     const int *prof = nullptr;
     if constexpr (AV) { ftab = *gen_avail_slot(v); prof = gen_prof(v); }
@@ -625,11 +644,7 @@ __global__ __launch_bounds__(256) void kc_gen_rows_long(CentralView c, const dou
     int buf = 0;                                              // which half of hand[] this tile writes (block-uniform)
     for (int g = it.a0; g < it.a1; ++g) {                    // (block-uniform)
         const bool first = g == it.a0;
-        const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
-        const double ru = c.rows_in[g], rd = c.rows_in[G + g], prev = c.rows_in[2 * G + g];
-        const double e_min = c.rows_in[3 * G + g], e_max = c.rows_in[4 * G + g];
-        const bool ramp = cr_has_ramp(ru, rd, prev), anch = cr_anchored(prev), bud = cr_has_budget(e_min, e_max);      // (block-uniform)
-        const double yQ = bud ? (ITER ? c.yQ[g] : scale * XQ[g]) : 0.0;
+        const GenRow r = gen_row_load<ITER>(c, XQ, scale, g);
         const size_t row = (size_t)g * T;
         double lsum = 0.0, xcarry = 0.0;                      // this thread's share of sum_t xb; the last xb of the tile before
         for (int tile = 0; tile < tiles; ++tile) {
@@ -640,32 +655,19 @@ __global__ __launch_bounds__(256) void kc_gen_rows_long(CentralView c, const dou
                 const bool ok = cl_live(f, k, T);
                 const size_t e = row + (ok ? (size_t)(f + k) : 0);
                 x0[k] = ok ? (ITER ? v.P[e] : scale * X[e]) : 0.0;
-                yR[k] = ok && ramp ? (ITER ? c.yR[e] : scale * XR[e]) : 0.0;
-                cap[k] = pm;
-                if constexpr (AV) cap[k] = avail_cap(ftab, T, prof[g], pm, ok ? (int)(f + k) : 0);
+                yR[k] = ok && r.ramp ? (ITER ? c.yR[e] : scale * XR[e]) : 0.0;
+                cap[k] = r.pm;
+                if constexpr (AV) cap[k] = avail_cap(ftab, T, prof[g], r.pm, ok ? (int)(f + k) : 0);
             }
             double y_hand = 0.0;                              // yR of the step behind this thread's last slot
-            if (ramp && cl_live(f, NS, T)) y_hand = ITER ? c.yR[row + (size_t)(f + NS)] : scale * XR[row + (size_t)(f + NS)];
+            if (r.ramp && cl_live(f, NS, T)) y_hand = ITER ? c.yR[row + (size_t)(f + NS)] : scale * XR[row + (size_t)(f + NS)];
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 xb[k] = 0.0;
                 if (cl_live(f, k, T)) {
                     const int t = (int)(f + k);
-                    double y_next = k + 1 < NS ? yR[k + 1 < NS ? k + 1 : k] : y_hand;
-                    if (t + 1 >= T) y_next = 0.0;
-                    const double rc = cr_reduced_cost(mc, c.pi[it.node + (size_t)N * t], yR[k], y_next, yQ);
-                    if (ITER) {
-                        const double tau = cr_tau(absH, cr_ramp_rows_at(t, T, ramp, anch), bud ? 1 : 0, w);
-                        const double xn = cr_column_step(x0[k], tau, rc, cap[k]);
-                        const size_t e = row + (size_t)t;
-                        v.P[e] = xn;
-                        c.aP[e] += xn;
-                        xb[k] = 2.0 * xn - x0[k];
-                    } else {
-                        xb[k] = x0[k];
-                        cost += mc * x0[k];
-                        dpart += cr_rc_term(rc, cap[k]);
-                    }
+                    const double y_next = k + 1 < NS ? yR[k + 1 < NS ? k + 1 : k] : y_hand;
+                    xb[k] = gen_column_slot<ITER>(c, it.node, r, absH, row + (size_t)t, t, x0[k], yR[k], y_next, cap[k], m);
                     part[t] = first ? xb[k] : part[t] + xb[k];
                     lsum += xb[k];
                 }
@@ -675,57 +677,25 @@ __global__ __launch_bounds__(256) void kc_gen_rows_long(CentralView c, const dou
             const double x_left = tid ? hand[buf][tid - 1] : xcarry;      // the step before this thread's first (t = 0: never read)
             xcarry = hand[buf][kClThreads - 1];               // (a full tile's last step; behind the last tile nobody reads it)
             buf ^= 1;
-            if (ramp) {
+            if (r.ramp) {
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
-                    if (cl_live(f, k, T) && (f + k >= 1 || anch)) {
+                    if (cl_live(f, k, T) && (f + k >= 1 || r.anch)) {
                         const int t = (int)(f + k);
-                        const double rowv = t >= 1 ? xb[k] - (k >= 1 ? xb[k >= 1 ? k - 1 : 0] : x_left) : xb[k];
-                        const double lo = cr_ramp_lo(t, rd, prev), hi = cr_ramp_hi(t, ru, prev);
-                        if (ITER) {
-                            const size_t e = row + (size_t)t;
-                            const double yn = cr_prox(yR[k], cr_sigma_ramp(t, w), rowv, lo, hi);
-                            c.yR[e] = yn;
-                            c.aR[e] += yn;
-                        } else {
-                            sup += cr_support(yR[k], lo, hi);
-                            viol = fmax(viol, cr_violation(rowv, lo, hi));
-                        }
+                        gen_ramp_slot<ITER>(c, r, row + (size_t)t, t, yR[k], xb[k], k >= 1 ? xb[k >= 1 ? k - 1 : 0] : x_left, m);
                     }
                 }
             }
         }
-        if (bud) {
+        if (r.bud) {
             for (int d = 32; d > 0; d >>= 1) lsum += __shfl_xor(lsum, d);      // (a + b = b + a: every lane holds the same bits)
             if (lane == 0) wsum[wv] = lsum;
             __syncthreads();
-            if (tid == 0) {                                   // (wsum is written again only behind the next row's first barrier)
-                const double total = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-                if (ITER) {
-                    const double yn = cr_prox(yQ, cr_sigma_budget(T, w), total, e_min, e_max);
-                    c.yQ[g] = yn;
-                    c.aQ[g] += yn;
-                } else {
-                    sup += cr_support(yQ, e_min, e_max);
-                    viol = fmax(viol, cr_violation(total, e_min, e_max));
-                }
-            }
+            // (wsum is written again only behind the next row's first barrier)
+            if (tid == 0) gen_budget_row<ITER>(c, r, g, (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]), m);
         }
     }
-    if (!ITER) {
-        for (int d = 32; d > 0; d >>= 1) {
-            cost += __shfl_xor(cost, d); dpart += __shfl_xor(dpart, d); sup += __shfl_xor(sup, d);
-            viol = fmax(viol, __shfl_xor(viol, d));
-        }
-        if (lane == 0) { redm[wv][0] = cost; redm[wv][1] = dpart; redm[wv][2] = sup; redm[wv][3] = viol; }
-        __syncthreads();
-        if (tid == 0) {
-            v.part_gcost[blockIdx.x] = (redm[0][0] + redm[1][0]) + (redm[2][0] + redm[3][0]);
-            c.m_rows[3 * blockIdx.x + 0] = (redm[0][1] + redm[1][1]) + (redm[2][1] + redm[3][1]);
-            c.m_rows[3 * blockIdx.x + 1] = (redm[0][2] + redm[1][2]) + (redm[2][2] + redm[3][2]);
-            c.m_rows[3 * blockIdx.x + 2] = fmax(fmax(redm[0][3], redm[1][3]), fmax(redm[2][3], redm[3][3]));
-        }
-    }
+    if (!ITER) row_metrics_store(c, m, redm, tid);
 }
 
 // balance and flow rows of one timestep from the nodal sums in v.cons. ITER: the multipliers' steps (balance: free;
@@ -751,16 +721,7 @@ __global__ __launch_bounds__(256) void kc_dual(CentralView c, const double *yb, 
         part += x;
         dsum += dm;
     }
-    red[tid] = part;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
-    const double bal = red[0];
-    __syncthreads();
-    red[tid] = dsum;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
-    const double dtot = red[0];
-    __syncthreads();
+    const double bal = block_tree_sum<256>(red, tid, part, true), dtot = block_tree_sum<256>(red, tid, dsum, true);
     double fviol = 0.0, fterm = 0.0;
     for (int l = tid; l < L; l += 256) {
         double f = 0.0, fd = 0.0;                // flow of the injections, flow of the demand alone
@@ -781,7 +742,7 @@ __global__ __launch_bounds__(256) void kc_dual(CentralView c, const double *yb, 
         if (ITER) {
             const double sg = c.w * c.sigF[l];
             const double z = c.yf[i] + sg * f;
-            const double yn = z - sg * cclamp(z / sg, -F, F);
+            const double yn = z - sg * cs_clamp(z / sg, -F, F);
             c.yf[i] = yn;
             c.af[i] += yn;
         } else {
@@ -797,17 +758,10 @@ __global__ __launch_bounds__(256) void kc_dual(CentralView c, const double *yb, 
             c.ab[t] += yn;
         }
     } else {
-        red[tid] = fterm;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
-        const double ft = red[0];
-        __syncthreads();
-        red[tid] = fviol;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] = fmax(red[tid], red[tid + s]); __syncthreads(); }
+        const double ft = block_tree_sum<256>(red, tid, fterm, true), fv = block_tree_max<256>(red, tid, fviol, false);
         if (tid == 0) {
             c.m_dual[3 * t + 0] = fabs(bal);
-            c.m_dual[3 * t + 1] = red[0];
+            c.m_dual[3 * t + 1] = fv;
             c.m_dual[3 * t + 2] = -scale * yb[t] * dtot - ft;
         }
     }
@@ -830,10 +784,8 @@ __global__ __launch_bounds__(256) void kc_diff_sq(const double *a, const double 
         const double d = a[i] - b[i];
         s += d * d;
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int sft = 128; sft > 0; sft >>= 1) { if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft]; __syncthreads(); }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+    const double sum = block_tree_sum<256>(red, threadIdx.x, s, false);
+    if (threadIdx.x == 0) part[blockIdx.x] = sum;
 }
 
 // the primal rows of the restart: dst = min(scale * src, upper end of the box). The running sum of n iterates inside [0, ub], times
