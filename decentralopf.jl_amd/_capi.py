@@ -91,6 +91,10 @@ F_GEN_RAMP_NETWORK = 2147483648  # bit 31, the last of the int32 flag word (ctyp
 F2_GEN_ENERGY_BUDGET = 1  # the second flag word (DOPF_F2_*): the flags2 argument of dopf_create_ex / dopf_multi_create_ex
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
+TRACE_DUALS = 1       # dopf_trace_begin's `what` (DOPF_TRACE_*): lambda, mu, rho
+TRACE_CONSENSUS = 2   # injection, avg_U, avg_K, line_util
+TRACE_PRIMAL = 4      # P, D, C (E is derived when read)
+TRACE_ALL = 7
 
 
 class DopfError(RuntimeError):
@@ -178,6 +182,12 @@ class CApi:
                                                         [C.c_double, C.c_int32, C.POINTER(DopfCentralResult)] + [c_double_p] * 11)
             self._sig("get_node_results", C.c_int, [ctxp, c_double_p, c_double_p, c_double_p])
             self._sig("last_call_ms", C.c_double, [ctxp])
+            # the iteration history on the device (Engine.trace_*)
+            self._sig("trace_begin", C.c_int, [ctxp, C.c_int32, C.c_int32])
+            self._sig("trace_end", C.c_int, [ctxp])
+            self._sig("trace_reset", C.c_int, [ctxp])
+            self._sig("trace_info", C.c_int, [ctxp] + [c_int32_p] * 4)
+            self._sig("trace_read", C.c_int, [ctxp, C.c_int32, C.c_int32, c_double_p, c_int32_p, c_int32_p] + [c_double_p] * 11)
             # consensus sum across GPUs inside the library (RCCL, loaded on first use)
             self._sig("comm_unique_id", C.c_int, [C.c_void_p])
             self._sig("comm_init", C.c_int, [ctxp, C.c_int32, C.c_int32, C.c_void_p])
@@ -599,6 +609,58 @@ class Engine(_ExtensionSetters):
     def last_call_ms(self) -> float:
         """F_TIME_CALLS: device-side milliseconds of the last iterate() call's launches (-1 if not measured)."""
         return float(self.api.last_call_ms(self._ctx))
+
+    # -- the iteration history on the device (dopf_trace_*) --------------------------------------
+    def trace_begin(self, what: int = TRACE_ALL, capacity: int = 64):
+        """dopf_trace_begin: from now on every computed iteration of iterate() writes one slot of a device ring of `capacity` slots:
+        the row (residuals, total cost, iteration, converged) and the sections `what` selects (TRACE_DUALS | TRACE_CONSENSUS |
+        TRACE_PRIMAL; 0 = the row alone). A backend without the entries: DopfError."""
+        if not hasattr(self.api, "trace_begin"):
+            raise DopfError(f"{self.api.prefix}*: this API has no trace (dopf_trace_*)")
+        self._chk(self.api.trace_begin(self._ctx, int(what), int(capacity)))
+
+    def trace_end(self):
+        self._chk(self.api.trace_end(self._ctx))
+
+    def trace_reset(self):
+        """dopf_trace_reset: recorded = 0 again, same ring, same sections."""
+        self._chk(self.api.trace_reset(self._ctx))
+
+    def trace_info(self):
+        """(what, capacity, held, recorded); zeros without a trace."""
+        v = [C.c_int32(0) for _ in range(4)]
+        self._chk(self.api.trace_info(self._ctx, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def trace_read(self, first: int, n: int) -> dict:
+        """dopf_trace_read: held slots [first, first + n), oldest first, as a dict of arrays with the slot as the leading axis and
+        the getters' shapes behind it: lam_res, mu_res, rho_res, total_cost, iteration, converged (n each), and of the sections the
+        trace selected lam (n, T), mu, rho (n, L, T); inj (n, N, T), avg_U, avg_K, flow (n, L, T); P (n, G, T), D, C, E (n, S, T)."""
+        what = self.trace_info()[0]
+        first, n = int(first), int(n)
+        m = max(n, 0)
+        N, L, T, G, S = self.N, self.L, self.T, self.G, self.S
+        rows = np.zeros(4 * m)
+        it, conv = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+        sizes = (("lam", TRACE_DUALS, T), ("mu", TRACE_DUALS, L * T), ("rho", TRACE_DUALS, L * T),
+                 ("inj", TRACE_CONSENSUS, N * T), ("avg_U", TRACE_CONSENSUS, L * T), ("avg_K", TRACE_CONSENSUS, L * T),
+                 ("flow", TRACE_CONSENSUS, L * T), ("P", TRACE_PRIMAL, G * T), ("D", TRACE_PRIMAL, S * T), ("C", TRACE_PRIMAL, S * T),
+                 ("E", TRACE_PRIMAL, S * T))
+        buf = {k: (np.zeros(m * size) if what & bit else None) for k, bit, size in sizes}
+        self._chk(self.api.trace_read(self._ctx, first, n, _dp(rows), it.ctypes.data_as(c_int32_p), conv.ctypes.data_as(c_int32_p),
+                                      *[_dp(buf[k]) for k, _, _ in sizes]))
+        r = rows.reshape(m, 4)
+        out = dict(lam_res=r[:, 0].copy(), mu_res=r[:, 1].copy(), rho_res=r[:, 2].copy(), total_cost=r[:, 3].copy(),
+                   iteration=it, converged=conv)
+        cm = lambda v, rows_: v.reshape(m, T, rows_).transpose(0, 2, 1).copy()          # [r + rows*t] per slot -> (rows, T)
+        am = lambda v, rows_: v.reshape(m, rows_, T)                                     # [t + T*row] per slot
+        if what & TRACE_DUALS:
+            out.update(lam=buf["lam"].reshape(m, T), mu=cm(buf["mu"], L), rho=cm(buf["rho"], L))
+        if what & TRACE_CONSENSUS:
+            out.update(inj=cm(buf["inj"], N), avg_U=cm(buf["avg_U"], L), avg_K=cm(buf["avg_K"], L), flow=cm(buf["flow"], L))
+        if what & TRACE_PRIMAL:
+            out.update(P=am(buf["P"], G), D=am(buf["D"], S), C=am(buf["C"], S), E=am(buf["E"], S))
+        return out
 
     def solver_failures(self) -> int:
         return int(self.api.solver_failures(self._ctx))

@@ -333,6 +333,69 @@ def run(admm: ADMM, chunk: int = 64) -> ADMM:
     return admm
 
 
+def _result_of_slot(admm: ADMM, sl: dict, i: int) -> Result:
+    """The Result of slot i of a trace read (Engine.trace_read with all sections): what ADMM._fetch_result builds from the getters
+    after that iteration. The node results are summed here, in NumPy, from the slot's P, D and C."""
+    p = admm.packed
+    P, D, C, E = sl["P"][i], sl["D"][i], sl["C"][i], sl["E"][i]
+    u2r: Dict[int, object] = {}
+    for k, g in enumerate(admm.generators):
+        u2r[id(g)] = ResultGenerator(g, P[k].copy())
+    for k, s in enumerate(admm.storages):
+        u2r[id(s)] = ResultStorage(s, D[k].copy(), C[k].copy(), E[k].copy())
+    ng, nd, nc = (np.zeros((p.N, p.T)) for _ in range(3))
+    np.add.at(ng, np.asarray(p.gen_node, dtype=np.int64), P)
+    np.add.at(nd, np.asarray(p.sto_node, dtype=np.int64), D)
+    np.add.at(nc, np.asarray(p.sto_node, dtype=np.int64), C)
+    n2r = {id(n): ResultNode(n, ng[k].copy(), nd[k].copy(), nc[k].copy()) for k, n in enumerate(admm.nodes)}
+    return Result(u2r, P.sum(axis=0) if P.size else np.zeros(p.T), D.sum(axis=0) if D.size else np.zeros(p.T),
+                  C.sum(axis=0) if C.size else np.zeros(p.T), sl["avg_U"][i].copy(), sl["avg_K"][i].copy(), float(sl["total_cost"][i]),
+                  sl["inj"][i].copy(), sl["flow"][i].copy(), n2r, None)
+
+
+def run_recorded(admm: ADMM, chunk: int = 64) -> ADMM:
+    """run(admm) with the history recorded on the device (dopf_trace_*): the iterations run `chunk` at a time, back to back, each
+    writing its slot of a device ring, and the host reads a chunk's slots afterwards — one round trip per chunk where run makes
+    one, and five to seven blocking copies, per iteration. Appends to admm.results, lambdas, mues, rhos and convergence exactly
+    what run appends. Needs ADMM(..., record=True); the units' slacks and penalty terms are not in a trace (record_slacks=True:
+    ValueError)."""
+    if not admm.record:
+        raise ValueError("run_recorded records the iteration history: build ADMM(..., record=True) (or call run)")
+    if admm.record_slacks:
+        raise ValueError("run_recorded: the units' slacks and penalty terms are not part of a trace (record_slacks=True): call run")
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"run_recorded: chunk = {chunk} < 1")
+    e = admm.engine
+    cap, eps = admm.params.max_iters, admm.params.eps
+    e.trace_begin(_capi.TRACE_ALL, chunk)
+    try:
+        while not admm.convergence.all and not (cap > 0 and admm.iteration > cap):
+            e.trace_reset()
+            done, _ = e.iterate(chunk)
+            sl = e.trace_read(0, done)
+            c = admm.convergence
+            for i in range(done):
+                admm.results.append(_result_of_slot(admm, sl, i))
+                admm.lambdas.append(sl["lam"][i].copy())
+                admm.mues.append(sl["mu"][i].copy())
+                admm.rhos.append(sl["rho"][i].copy())
+                if admm.iteration != 1:          # (as ADMM._after: the first iteration has no residuals)
+                    c.lambda_res.append(np.abs(admm.lambdas[-1] - admm.lambdas[-2]))
+                    c.mue_res.append(np.abs(admm.mues[-1] - admm.mues[-2]))
+                    c.rho_res.append(np.abs(admm.rhos[-1] - admm.rhos[-2]))
+                    c.lambda_, c.mue, c.rho = (float(sl[k][i]) < eps for k in ("lam_res", "mu_res", "rho_res"))
+                conv = bool(sl["converged"][i])
+                c.all = conv
+                admm.iteration = int(sl["iteration"][i]) + (0 if conv else 1)
+            if done == 0:           # (halted before the call: the counter and the flag as the engine has them)
+                admm._after(0)
+                break
+    finally:
+        e.trace_end()
+    return admm
+
+
 def get_nodal_price(admm: ADMM, iteration: Optional[int] = None) -> np.ndarray:
     """lambda_t + sum_l (mu + rho)[l,t] ptdf[l,:] with the duals of `iteration` (1-based, default
     admm.iteration = the duals the last solve used, as src/opf_admm_decentral.jl:9 does)."""

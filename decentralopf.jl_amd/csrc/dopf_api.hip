@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "dopf_ctx.h"
+#include "trace.h"
 
 using namespace dopf;
 
@@ -357,6 +358,16 @@ void drop_graphs(dopf_ctx *c)
     }
 }
 
+// the device memory of the context's trace (the stream is idle, or the caller has synchronised)
+void trace_release(dopf_ctx *c)
+{
+    dopf_ctx::Trace &t = c->trace;
+    if (t.ring) hipFree(t.ring);
+    if (t.blk) hipFree(t.blk);
+    if (t.level) hipFree(t.level);
+    t = dopf_ctx::Trace{};
+}
+
 int read_status(dopf_ctx *c)
 {
     // (every dopf_iterate ends here: on short calls — 20 iterations of 30 us — the read-back is a visible share of the call)
@@ -474,6 +485,15 @@ void enqueue_apply(dopf_ctx *c, const Step &st, const hipEvent_t *ev = nullptr)
     if (ev) for (int k : {E_D1, E_X0, E_X1}) hipEventRecord(ev[k], c->main);
 }
 
+// k_trace's argument for the context's active trace
+TraceView trace_view(const dopf_ctx *c)
+{
+    const dopf_ctx::Trace &t = c->trace;
+    unsigned long long units = 0;
+    for (int k = 0; k < kTraceSections; ++k) units += (t.lay.n[k] + 1) / 2;
+    return TraceView{c->v.st, t.blk, t.ring, t.capacity, (unsigned long long)t.lay.slot_bytes, units};
+}
+
 // one iteration of the chain on the context's stream; a sharded context (dopf_comm_init) puts the all-reduce
 // of the consensus buffer between the local sums and the dual step. ev: dopf_iterate_timed's events for this iteration.
 int enqueue_iteration(dopf_ctx *c, bool quiet = false, const hipEvent_t *ev = nullptr)
@@ -483,6 +503,7 @@ int enqueue_iteration(dopf_ctx *c, bool quiet = false, const hipEvent_t *ev = nu
     if (st.comm_quiet) launch_xchg(c->v, *comm_xchg(c), c->main, true);
     else if (!st.like_single) { const int rc = comm_enqueue_allreduce(c); if (rc) return rc; }
     enqueue_apply(c, st, ev);
+    if (c->trace.active) launch_trace(trace_view(c), c->main);      // dopf_trace_*: the iteration's slot, behind its last kernel
     return DOPF_OK;
 }
 
@@ -970,6 +991,7 @@ void dopf_destroy(dopf_ctx *c)
     if (c->side) hipStreamSynchronize(c->side);
     drop_graphs(c);
     comm_release(c);
+    trace_release(c);
     for (void *p : c->allocs) hipFree(p);
     if (c->evFork) hipEventDestroy(c->evFork);
     if (c->evJoin) hipEventDestroy(c->evJoin);
@@ -1056,6 +1078,7 @@ int dopf_iterate_timed(dopf_ctx *c, int32_t n_iters, dopf_timing *out)
     if (!c || !out || n_iters < 1 || n_iters > 4096) return fail(c, DOPF_E_INVALID, "bad argument");
     DeviceGuard guard(c->device);
     if (c->comm) return fail(c, DOPF_E_INVALID, "dopf_iterate_timed drives the single-GPU chain: not on a context joined to a communicator");
+    if (c->trace.active) return fail(c, DOPF_E_INVALID, "dopf_iterate_timed: not while a trace is active (dopf_iterate alone advances a traced context)");
     const bool quiet = c->quiet && quiet_allowed(c);          // (the chain dopf_iterate would launch now)
     struct Events {                                     // destroyed on every way out
         std::vector<hipEvent_t> v;
@@ -1103,6 +1126,7 @@ int dopf_iterate_timed(dopf_ctx *c, int32_t n_iters, dopf_timing *out)
 int dopf_local_update(dopf_ctx *c)
 {
     if (!c) return DOPF_E_INVALID;
+    if (c->trace.active) return fail(c, DOPF_E_INVALID, "dopf_local_update: not while a trace is active (dopf_iterate alone advances a traced context)");
     DeviceGuard guard(c->device);
     c->quiet = false;                      // (iterations driven from outside: the next dopf_iterate looks at the flags before it trusts them)
     enqueue_local(c, make_step(c, false, true));
@@ -1113,6 +1137,7 @@ int dopf_local_update(dopf_ctx *c)
 int dopf_apply_consensus(dopf_ctx *c)
 {
     if (!c) return DOPF_E_INVALID;
+    if (c->trace.active) return fail(c, DOPF_E_INVALID, "dopf_apply_consensus: not while a trace is active (dopf_iterate alone advances a traced context)");
     DeviceGuard guard(c->device);
     c->quiet = false;
     enqueue_apply(c, make_step(c, false, true));
@@ -1767,6 +1792,176 @@ int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
     c->level_from_primal = true;           // (a central solve's levels belonged to the old window)
     if (S > 0) std::copy(e0s.begin(), e0s.end(), c->sto_slot_h(kStoE0));
     return read_status(c);
+}
+
+// ---- dopf_trace_*: the iteration history on the device ---------------------------------------------------------------
+
+static int trace_needs_active(dopf_ctx *c, const char *entry)
+{
+    if (c->trace.active) return DOPF_OK;
+    return fail(c, DOPF_E_INVALID, "%s: no trace is active (dopf_trace_begin first)", entry);
+}
+
+int dopf_trace_begin(dopf_ctx *c, int32_t what, int32_t capacity)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (const uint32_t unknown = (uint32_t)what & ~(uint32_t)kTraceKnown)
+        return fail(c, DOPF_E_INVALID, "dopf_trace_begin: what has the unknown bit %u (DOPF_TRACE_DUALS = 1, DOPF_TRACE_CONSENSUS = 2, "
+                                       "DOPF_TRACE_PRIMAL = 4)", unknown & (~unknown + 1u));
+    if (capacity < 1) return fail(c, DOPF_E_INVALID, "dopf_trace_begin: capacity = %d < 1", capacity);
+    if (c->trace.active) return fail(c, DOPF_E_INVALID, "dopf_trace_begin: a trace is active already (dopf_trace_end first)");
+    if (c->comm)
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_trace_begin: not on a context joined to a communicator or a peer exchange (a sharded "
+                                           "history is not recorded)");
+    DeviceGuard guard(c->device);
+    const DevView &v = c->v;
+    dopf_ctx::Trace t{};
+    t.what = what; t.capacity = capacity;
+    t.lay = trace_layout(v.N, v.L, v.T, v.G, v.S, what);
+    const bool levels = (what & kTracePrimal) && v.S > 0;
+    t.level_slots = levels ? std::min(capacity, 64) : 0;
+    // (the ring, the levels' scratch of dopf_trace_read, the trace block; a product beyond 64 bits counts as all of them)
+    const unsigned __int128 need128 = (unsigned __int128)capacity * t.lay.slot_bytes +
+                                      (unsigned __int128)t.level_slots * v.S * v.T * sizeof(double) + sizeof(TraceBlock);
+    const unsigned long long need = need128 > (unsigned __int128)~0ull ? ~0ull : (unsigned long long)need128;
+    if (int rc = read_status(c)) return rc;         // (synchronises; iters_total as the device has it)
+    size_t freeb = 0, totalb = 0;
+    HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
+    if (need > freeb)
+        return fail(c, DOPF_E_NOMEM, "trace: the ring of %d slots of %llu bytes needs %llu bytes, the device has %llu free",
+                    capacity, (unsigned long long)t.lay.slot_bytes, need, (unsigned long long)freeb);
+    t.base = c->host_st.iters_total;
+    TraceBlock hb;
+    trace_fill_block(&hb, t.lay, v, t.base);
+    c->trace = t;
+    dopf_ctx::Trace &tr = c->trace;
+    hipError_t e = hipMalloc((void **)&tr.ring, (size_t)capacity * t.lay.slot_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&tr.blk, sizeof(TraceBlock));
+    if (e == hipSuccess && levels) e = hipMalloc((void **)&tr.level, (size_t)t.level_slots * v.S * v.T * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(tr.blk, &hb, sizeof hb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        trace_release(c);
+        (void)hipGetLastError();
+        return fail(c, e == hipErrorOutOfMemory ? DOPF_E_NOMEM : DOPF_E_DEVICE, "trace: allocating the ring of %d slots of %llu bytes (%llu bytes): %s",
+                    capacity, (unsigned long long)t.lay.slot_bytes, need, hipGetErrorString(e));
+    }
+    tr.active = true;
+    drop_graphs(c);             // the chain gains a launch: captured again at the next dopf_iterate
+    return DOPF_OK;
+}
+
+int dopf_trace_end(dopf_ctx *c)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = trace_needs_active(c, "dopf_trace_end")) return rc;
+    DeviceGuard guard(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    drop_graphs(c);             // the chain loses its last launch
+    trace_release(c);
+    return DOPF_OK;
+}
+
+int dopf_trace_reset(dopf_ctx *c)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = trace_needs_active(c, "dopf_trace_reset")) return rc;
+    DeviceGuard guard(c->device);
+    if (int rc = read_status(c)) return rc;
+    // ordered on the context's stream; the graphs read base at this address (no capture again)
+    c->trace.base = c->host_st.iters_total;
+    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&c->trace.blk->base), c->trace.base, 1, c->main));
+    return DOPF_OK;
+}
+
+int dopf_trace_info(dopf_ctx *c, int32_t *what, int32_t *capacity, int32_t *held, int32_t *recorded)
+{
+    if (!c) return DOPF_E_INVALID;
+    // (no trace: all zeros. recorded needs no read-back: dopf_iterate alone advances a traced context, and it ends with a status read)
+    const dopf_ctx::Trace &t = c->trace;
+    const int rec = t.active ? c->host_st.iters_total - t.base : 0;
+    if (what) *what = t.what;
+    if (capacity) *capacity = t.capacity;
+    if (held) *held = t.active ? trace_held(rec, t.capacity) : 0;
+    if (recorded) *recorded = rec;
+    return DOPF_OK;
+}
+
+int dopf_trace_read(dopf_ctx *c, int32_t first, int32_t n, double *rows, int32_t *iteration, int32_t *converged,
+                    double *lambda, double *mu, double *rho, double *injection, double *avg_U, double *avg_K, double *line_util,
+                    double *P, double *D, double *C, double *E)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = trace_needs_active(c, "dopf_trace_read")) return rc;
+    const dopf_ctx::Trace &t = c->trace;
+    const DevView &v = c->v;
+    const int rec = c->host_st.iters_total - t.base, held = trace_held(rec, t.capacity);
+    if (first < 0 || n < 0 || (long long)first + n > held)
+        return fail(c, DOPF_E_INVALID, "dopf_trace_read: slots [%d, %d) outside the %d held (recorded %d, capacity %d)", first, first + n, held,
+                    rec, t.capacity);
+    double *out[kTraceSections] = {lambda, mu, rho, injection, avg_U, avg_K, line_util, P, D, C};
+    static const char *const names[kTraceSections] = {"lambda", "mu", "rho", "injection", "avg_U", "avg_K", "line_util", "P", "D", "C"};
+    static const char *const bits[3] = {"DOPF_TRACE_DUALS", "DOPF_TRACE_CONSENSUS", "DOPF_TRACE_PRIMAL"};
+    for (int k = 0; k < kTraceSections; ++k)
+        if (out[k] && !(t.what & trace_bit_of(k)))
+            return fail(c, DOPF_E_INVALID, "dopf_trace_read: %s is given, but the trace was begun without %s", names[k],
+                        bits[trace_bit_of(k) == kTraceDuals ? 0 : trace_bit_of(k) == kTraceConsensus ? 1 : 2]);
+    if (E && !(t.what & kTracePrimal))
+        return fail(c, DOPF_E_INVALID, "dopf_trace_read: E is given, but the trace was begun without DOPF_TRACE_PRIMAL");
+    if (n == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    const size_t sb = t.lay.slot_bytes, T = (size_t)v.T, ST = (size_t)v.S * T;
+    const bool levels = E && v.S > 0;
+    // whole slots come over in runs that are contiguous in the ring, on the context's stream behind what is queued there, a few MiB
+    // at a time; the sections are taken apart here. With E: level_slots slots at a time, whose levels k_derive_level(_eff) forms
+    // from the slot's D and C under the initial levels and efficiencies stored now.
+    size_t batch = std::max<size_t>(1, ((size_t)8 << 20) / sb);
+    if (levels) batch = std::min(batch, (size_t)t.level_slots);
+    batch = std::min(batch, (size_t)n);
+    std::vector<char> stage(batch * sb);
+    std::vector<double> lev(levels ? batch * ST : 0);
+    const int oldest = trace_oldest(rec, t.capacity);
+    for (int done = 0; done < n;) {
+        const int ring0 = (int)(((long long)oldest + first + done) % t.capacity);
+        const int cnt = (int)std::min<size_t>(batch, (size_t)std::min(n - done, t.capacity - ring0));
+        const char *src = t.ring + (size_t)ring0 * sb;
+        HIPCHK(c, hipMemcpyAsync(stage.data(), src, (size_t)cnt * sb, hipMemcpyDeviceToHost, c->main));
+        if (levels) {
+            for (int j = 0; j < cnt; ++j) {
+                DevView vs = v;
+                vs.D = reinterpret_cast<double *>(const_cast<char *>(src) + (size_t)j * sb + t.lay.off[kSecD]);
+                vs.C = reinterpret_cast<double *>(const_cast<char *>(src) + (size_t)j * sb + t.lay.off[kSecC]);
+                vs.E = t.level + (size_t)j * ST;
+                launch_derive_level(vs, c->plan, c->main);
+            }
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(lev.data(), t.level, (size_t)cnt * ST * sizeof(double), hipMemcpyDeviceToHost, c->main));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        for (int j = 0; j < cnt; ++j) {
+            const char *slot = stage.data() + (size_t)j * sb;
+            const size_t i = (size_t)done + j;
+            TraceRow row;
+            memcpy(&row, slot, sizeof row);
+            if (rows) { memcpy(rows + 4 * i, row.res, 3 * sizeof(double)); rows[4 * i + 3] = row.total_cost; }
+            if (iteration) iteration[i] = row.iteration;
+            if (converged) converged[i] = row.converged;
+            for (int k = 0; k < kTraceSections; ++k) {
+                const size_t len = t.lay.n[k];
+                if (!out[k] || len == 0) continue;
+                const char *sec = slot + t.lay.off[k];
+                if (k < kSecP) { memcpy(out[k] + len * i, sec, len * sizeof(double)); continue; }
+                // device rows are in node-sorted order; hand them back in the caller's agent order
+                const std::vector<int> &perm = k == kSecP ? c->gen_perm : c->sto_perm;
+                for (size_t r = 0; r < perm.size(); ++r)
+                    memcpy(out[k] + len * i + (size_t)perm[r] * T, sec + r * T * sizeof(double), T * sizeof(double));
+            }
+            if (levels)
+                for (size_t r = 0; r < c->sto_perm.size(); ++r)
+                    memcpy(E + ST * i + (size_t)c->sto_perm[r] * T, lev.data() + (size_t)j * ST + r * T, T * sizeof(double));
+        }
+        done += cnt;
+    }
+    return DOPF_OK;
 }
 
 int dopf_debug_stats(dopf_ctx *c, uint64_t *out3 /* 15 values */)

@@ -372,6 +372,7 @@ extern "C" {
 int dopf_xchg_export(dopf_ctx *c, int32_t world, void *handle64)
 {
     if (!c || !handle64 || world < 1 || world > kXchgMaxWorld) return fail(c, DOPF_E_INVALID, "bad argument (world <= %d)", kXchgMaxWorld);
+    if (c && c->trace.active) return fail(c, DOPF_E_INVALID, "dopf_xchg_export: not while a trace is active (dopf_trace_end first: a sharded history is not recorded)");
     if (c->comm) return fail(c, DOPF_E_INVALID, "context already has a communicator");
     DeviceGuard guard(c->device);
     dopf_comm_state *cs = new (std::nothrow) dopf_comm_state;
@@ -392,6 +393,7 @@ int dopf_xchg_export(dopf_ctx *c, int32_t world, void *handle64)
 
 int dopf_xchg_init(dopf_ctx *c, int32_t world, int32_t rank, const void *handles)
 {
+    if (c && c->trace.active) return fail(c, DOPF_E_INVALID, "dopf_xchg_init: not while a trace is active (dopf_trace_end first: a sharded history is not recorded)");
     if (!c || !handles || !c->comm || !c->comm->p2p || c->comm->world != world || rank < 0 || rank >= world || c->comm->xv.world)
         return fail(c, DOPF_E_INVALID, "bad argument (dopf_xchg_export first, same world)");
     DeviceGuard guard(c->device);
@@ -499,6 +501,7 @@ int dopf_comm_init(dopf_ctx *c, int32_t world, int32_t rank, const void *id128)
 {
     if (!c || world < 1 || rank < 0 || rank >= world || !id128) return fail(c, DOPF_E_INVALID, "bad argument");
     if (c->comm) return fail(c, DOPF_E_INVALID, "context already has a communicator");
+    if (c && c->trace.active) return fail(c, DOPF_E_INVALID, "dopf_comm_init: not while a trace is active (dopf_trace_end first: a sharded history is not recorded)");
     const Rccl *r = rccl();
     if (!r) return fail(c, g_rccl.code, "%s", g_rccl.err);
     DeviceGuard guard(c->device);

@@ -5,8 +5,10 @@
 #include <vector>
 
 #include "dopf_internal.h"
+#include "trace_layout.h"
 
 struct dopf_comm_state;     // dopf_comm.hip: RCCL communicator of a sharded context
+namespace dopf { struct TraceBlock; }   // trace.h
 
 struct dopf_ctx {
     dopf::DevView v{};
@@ -49,6 +51,18 @@ struct dopf_ctx {
     dopf_comm_state *comm = nullptr;       // non-null: dopf_iterate runs local_update -> all-reduce -> apply_consensus
     bool tail_xchg = false;                // peer exchange inside the tail block of the one-launch iteration (copper plates)
     bool level_from_primal = true;         // dopf_get_primal rebuilds E = cumsum(C - D); false while a central solve's own levels are in v.E
+    // dopf_trace_* (DESIGN.md 5w): run-time state of the context, not part of the plan. While active, enqueue_iteration ends with
+    // k_trace, and dopf_iterate is the only entry that advances the context.
+    struct Trace {
+        bool active = false;
+        int what = 0, capacity = 0;
+        int base = 0;                       // host_st.iters_total at begin / reset: recorded = host_st.iters_total - base
+        dopf::TraceLayout lay{};
+        char *ring = nullptr;               // capacity slots of lay.slot_bytes
+        dopf::TraceBlock *blk = nullptr;    // the trace block in device memory (base, the segment table)
+        double *level = nullptr;            // dopf_trace_read: the levels of level_slots slots at a time (S * T doubles each)
+        int level_slots = 0;
+    } trace;
     char err[512] = {0};
     double *sto_slot_h(int slot) { return sto_h.data() + (size_t)slot * (size_t)v.S; }                  // a held slot of the mirror
     double sto_at(int slot, int i) const { return sto_h[(size_t)slot * (size_t)v.S + (size_t)i]; }      // ... and sorted storage i of it
@@ -60,6 +74,7 @@ int fail(dopf_ctx *c, int code, const char *fmt, ...);
 void keep_error(const dopf_ctx *c);          // the context's message becomes what dopf_last_error(NULL) returns
 void drop_graphs(dopf_ctx *c);
 int read_status(dopf_ctx *c);
+void trace_release(dopf_ctx *c);             // frees an active trace's device memory (dopf_trace_end, dopf_destroy)
 int check_initial_levels(dopf_ctx *c, const double *e0);   // the checks of dopf_set_storage_initial_level (flag, 0 <= e0 <= emax)
 int check_terminal_levels(dopf_ctx *c, const double *lo, const double *hi);   // those of dopf_set_storage_terminal_level
 int check_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *eta_d);   // those of dopf_set_storage_efficiency

@@ -135,6 +135,9 @@ const DOPF_F_GEN_QUADRATIC_COST = 1073741824  # include/dopf.h
 const DOPF_F_GEN_RAMP = 32  # include/dopf.h
 const DOPF_F_GEN_RAMP_NETWORK = typemin(Int32)  # include/dopf.h: 2147483648, bit 31 — the sign bit of the Cint flag word, and its last
 const DOPF_F2_GEN_ENERGY_BUDGET = 1  # include/dopf.h: the second flag word (the `flags2` keyword; dopf_create_ex)
+const DOPF_TRACE_DUALS = 1      # include/dopf.h: dopf_trace_begin's `what` — lambda, mu, rho
+const DOPF_TRACE_CONSENSUS = 2  # injection, avg_U, avg_K, line_util
+const DOPF_TRACE_PRIMAL = 4     # P, D, C (E is derived when read)
 
 """
     ADMM(gamma, nodes, generators, storages, lines; max_iters=0, n_gpus=1, record=false, ...)
@@ -579,6 +582,70 @@ end
 function run!(admm::ADMM; chunk::Int=64)
     while !admm.convergence.all
         calculate_iteration!(admm; n=chunk) == 0 && break      # iteration cap reached
+    end
+    return admm
+end
+
+"""
+    run_recorded!(admm; chunk = 64)
+
+`run!` with the history recorded on the device (dopf_trace_*, include/dopf.h): the iterations run `chunk` at a time, back to back,
+each writing its slot of a device ring, and the host reads a chunk's slots afterwards — one round trip per chunk where
+`calculate_iteration!` with `admm.record` makes one, and its blocking copies, per iteration. Pushes to `admm.results`, `lambdas`,
+`mues`, `rhos` and `convergence` what `run!` pushes (the residual vectors from consecutive duals; the node results summed here from
+the slot's P, D and C). Needs `ADMM(...; record=true)` and a single device (`n_gpus = 1`: a sharded history is not recorded).
+"""
+function run_recorded!(admm::ADMM; chunk::Int=64)
+    admm.record || error("run_recorded! records the iteration history (create ADMM(...; record=true))")
+    admm.multi == C_NULL || error("run_recorded!: a sharded history is not recorded (n_gpus = 1)")
+    chunk >= 1 || error("run_recorded!: chunk = $chunk < 1")
+    N, L, T = length(admm.N), length(admm.L), length(admm.T)
+    G, S = length(admm.generators), length(admm.storages)
+    gen_node = Int[admm.node_to_id[g.node] for g in admm.generators]
+    sto_node = Int[admm.node_to_id[s.node] for s in admm.storages]
+    what = DOPF_TRACE_DUALS | DOPF_TRACE_CONSENSUS | DOPF_TRACE_PRIMAL
+    dopf_check(ccall((:dopf_trace_begin, DOPF_LIB), Cint, (Ptr{Cvoid}, Cint, Cint), admm.ctx, what, chunk), admm.ctx)
+    try
+        while !admm.convergence.all
+            dopf_check(ccall((:dopf_trace_reset, DOPF_LIB), Cint, (Ptr{Cvoid},), admm.ctx), admm.ctx)
+            done = Ref{Cint}(0); conv = Ref{Cint}(0)
+            dopf_check(ccall((:dopf_iterate, DOPF_LIB), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}, Ref{Cint}), admm.ctx, chunk, done, conv), admm.ctx)
+            n = Int(done[])
+            n == 0 && break                                   # iteration cap reached
+            w = Ref{Cint}(0); cap = Ref{Cint}(0); held = Ref{Cint}(0); rec = Ref{Cint}(0)
+            dopf_check(ccall((:dopf_trace_info, DOPF_LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Cint}, Ref{Cint}),
+                             admm.ctx, w, cap, held, rec), admm.ctx)
+            Int(held[]) == n || error("trace: $(held[]) slots held after $n iterations")
+            rows = zeros(4, n); its = zeros(Cint, n); cvs = zeros(Cint, n)
+            lam = zeros(T, n); mu = zeros(L, T, n); rho = zeros(L, T, n)
+            inj = zeros(N, T, n); aU = zeros(L, T, n); aK = zeros(L, T, n); fl = zeros(L, T, n)
+            P = zeros(T, G, n); D = zeros(T, S, n); C = zeros(T, S, n); E = zeros(T, S, n)
+            dopf_check(ccall((:dopf_trace_read, DOPF_LIB), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                              Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                             admm.ctx, 0, n, rows, its, cvs, lam, mu, rho, inj, aU, aK, fl, P, D, C, E), admm.ctx)
+            for i in 1:n
+                # ResultNode.{generation, discharge, charge} (src/structures/results.jl:19-35): the units of a node, summed here
+                ng = zeros(N, T); nd = zeros(N, T); nc = zeros(N, T)
+                for g in 1:G
+                    ng[gen_node[g], :] += P[:, g, i]
+                end
+                for s in 1:S
+                    nd[sto_node[s], :] += D[:, s, i]
+                    nc[sto_node[s], :] += C[:, s, i]
+                end
+                push!(admm.results, (generation=P[:, :, i], discharge=D[:, :, i], charge=C[:, :, i], level=E[:, :, i],
+                                     injection=inj[:, :, i], avg_U=aU[:, :, i], avg_K=aK[:, :, i], line_utilization=fl[:, :, i],
+                                     total_costs=rows[4, i], node_generation=ng, node_discharge=nd, node_charge=nc))
+                push!(admm.lambdas, lam[:, i]); push!(admm.mues, mu[:, :, i]); push!(admm.rhos, rho[:, :, i])
+                push!(admm.convergence.lambda_res, abs.(admm.lambdas[end] - admm.lambdas[end-1]))
+                push!(admm.convergence.mue_res, abs.(admm.mues[end] - admm.mues[end-1]))
+                push!(admm.convergence.rho_res, abs.(admm.rhos[end] - admm.rhos[end-1]))
+            end
+            dopf_refresh!(admm, cvs[n] != 0)
+        end
+    finally
+        ccall((:dopf_trace_end, DOPF_LIB), Cint, (Ptr{Cvoid},), admm.ctx)
     end
     return admm
 end

@@ -29,6 +29,8 @@
  *   dopf_get_nodal_price   replaces  get_nodal_price(iteration) src/helpers/network_elements.jl:16-25
  *   dopf_set_state         (no reference counterpart: resume / trajectory tests; the reference
  *                                    keeps whole histories in admm.results / admm.lambdas instead)
+ *   dopf_trace_*           replaces  those histories: admm.lambdas / mues / rhos / results / convergence, one
+ *                                    entry per iteration (src/structures/admm.jl, src/optimization/run.jl:1-16)
  *
  * Conventions
  *   - all matrices are Julia column-major: demand[n + N*t], ptdf[l + L*n], mu[l + L*t];
@@ -497,6 +499,44 @@ int dopf_set_demand(dopf_ctx *ctx, const double *demand /* N x T, [n + N*t] */);
  * DOPF_E_INVALID for k < 1, k >= T, a NULL demand_tail, a NaN / Inf in it, or a stored terminal band that is unreachable from the
  * new initial levels; DOPF_E_UNSUPPORTED with storages in a context without DOPF_F_STO_INITIAL_LEVEL. */
 int dopf_roll_horizon(dopf_ctx *ctx, int32_t k, const double *demand_tail /* N x k, [n + N*j] */);
+
+/* ---- the iteration history on the device ---------------------------------------------------------------
+ * The reference's data product is the history of a run: admm.lambdas, admm.mues, admm.rhos, admm.results and admm.convergence hold
+ * one entry per iteration (src/structures/admm.jl, src/optimization/run.jl:1-16). A trace records it without a host round trip per
+ * iteration: while one is active, dopf_iterate(n) keeps running its n iterations back to back, and every COMPUTED iteration writes
+ * one slot of a ring in device memory (one more kernel per iteration). A slot always holds a row: the three residual
+ * maxima and the total cost exactly as dopf_get_residuals and dopf_get_consensus return them right after that iteration, the
+ * value admm.iteration had DURING that solve, and converged. `what` adds array sections (0: the row alone, the convergence curve): */
+#define DOPF_TRACE_DUALS     1   /* lambda[T], mu[L*T], rho[L*T] after the iteration's update (dopf_get_duals) */
+#define DOPF_TRACE_CONSENSUS 2   /* injection[N*T], avg_U, avg_K, line_util[L*T each] (dopf_get_consensus) */
+#define DOPF_TRACE_PRIMAL    4   /* P[T*G], D, C[T*S] (dopf_get_primal; E is derived when read) */
+/* The ring keeps the last `capacity` slots. recorded counts the slots written since begin or reset, held = min(recorded, capacity);
+ * dopf_trace_read indexes the held slots oldest first, 0 <= first, first + n <= held, and does not consume them. Its outputs are
+ * slot-major — rows[4*i ..] = lam_res, mu_res, rho_res, total_cost of slot first + i; lambda[t + T*i], mu[l + L*t + L*T*i],
+ * P[t + T*g + T*G*i], ... in the getters' layouts and the caller's agent order — and any pointer may be NULL. By definition slot i
+ * equals, bit for bit, what the getters return when called after that iteration; E is what dopf_get_primal forms from the slot's D
+ * and C under the initial levels and efficiencies stored when it is READ. The copies are ordered on the context's stream behind the
+ * work already queued there.
+ * dopf_trace_begin and dopf_trace_end let the iteration graphs be captured again at the next dopf_iterate (the chain gains or loses a
+ * launch); dopf_trace_reset (recorded = 0 again, same ring) and dopf_trace_read do not. A context that never begins a trace launches
+ * what it always launched. While a trace is active dopf_iterate alone advances the context: dopf_iterate_timed, dopf_local_update,
+ * dopf_apply_consensus, dopf_comm_init, dopf_xchg_export and dopf_xchg_init return DOPF_E_INVALID; the setters (dopf_set_state,
+ * dopf_set_demand, dopf_roll_horizon, the extensions') keep working, and the rows' iteration shows what they did to the counter.
+ * dopf_destroy frees an active trace. dopf_trace_info without a trace reports zeros.
+ * DOPF_E_INVALID: an unknown bit in what, capacity < 1, a second begin without an end, read / reset / end without a trace, a read
+ * range outside the held slots, a non-NULL pointer for a section that what did not select (the message names it). DOPF_E_NOMEM,
+ * naming the bytes, when capacity slots do not fit on the device. DOPF_E_UNSUPPORTED on a context joined to a communicator or a
+ * peer exchange (a sharded history is not recorded). */
+int dopf_trace_begin(dopf_ctx *ctx, int32_t what, int32_t capacity);
+int dopf_trace_end(dopf_ctx *ctx);
+int dopf_trace_reset(dopf_ctx *ctx);
+int dopf_trace_info(dopf_ctx *ctx, int32_t *what, int32_t *capacity, int32_t *held, int32_t *recorded);
+int dopf_trace_read(dopf_ctx *ctx, int32_t first, int32_t n,
+                    double *rows /* 4*n: lam_res, mu_res, rho_res, total_cost */,
+                    int32_t *iteration /* n */, int32_t *converged /* n */,
+                    double *lambda, double *mu, double *rho,
+                    double *injection, double *avg_U, double *avg_K, double *line_util,
+                    double *P, double *D, double *C, double *E);
 
 /* ---- the central reference on the device ---------------------------------------------------------------
  * Replaces src/opf_central_reference.jl:16-81 (one JuMP model of the whole multi-period DC-OPF, solved by Gurobi): the same
