@@ -89,6 +89,7 @@ F_GEN_QUADRATIC_COST = 1073741824
 F_GEN_RAMP = 32
 F_GEN_RAMP_NETWORK = 2147483648  # bit 31, the last of the int32 flag word (ctypes stores it as the sign bit; test it with `& ... != 0`)
 F2_GEN_ENERGY_BUDGET = 1  # the second flag word (DOPF_F2_*): the flags2 argument of dopf_create_ex / dopf_multi_create_ex
+F2_GEN_RAMP_BUDGET = 8  # ... ramp limits and energy budgets on the same generators (copper plates): the opt-in of the pair search's scratch
 COMM_ID_BYTES = 128
 XCHG_HANDLE_BYTES = 64
 TRACE_DUALS = 1       # dopf_trace_begin's `what` (DOPF_TRACE_*): lambda, mu, rho
@@ -468,12 +469,18 @@ def _needs_create_ex(api: CApi, flags2: int) -> None:
         raise DopfError(f"{api.prefix}*: this API has no second flag word (no create_ex; flags2 = {flags2})")
 
 
-def _flags2(todo) -> int:
-    """The second flag word of a context built with todo (what _extensions returned): the flags of its word-2 extensions."""
+def _flags2(todo, L: int = 0) -> int:
+    """The second flag word of a context built with todo (what _extensions returned): the flags of its word-2 extensions — and, for
+    ramps and budgets together on a copper plate (L == 0), F2_GEN_RAMP_BUDGET, the opt-in of k_gen_ramp_budget's scratch,
+    the way _extensions adds F_GEN_RAMP_NETWORK for ramps on a network. With lines it is not added: the library's refusal of the two
+    flags together surfaces as it is."""
     word = 0
     for x, _ in todo:
         if x.word == 2:
             word |= x.flag
+    setters = {x.setter for x, _ in todo}
+    if "set_ramp" in setters and "set_energy_budget" in setters and L == 0:
+        word |= F2_GEN_RAMP_BUDGET
     return word
 
 
@@ -532,7 +539,7 @@ class Engine(_ExtensionSetters):
             sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
             sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget))
         self.params = params if params is not None else default_params()
-        self.flags2 = int(flags2) | _flags2(todo)
+        self.flags2 = int(flags2) | _flags2(todo, self.L)
         _needs_create_ex(api, self.flags2)
         # what a window change needs of the problem: the arrays as handed to create, and the inputs of the setters as they stand
         # (by constructor keyword, in the form the constructor takes them)
@@ -960,7 +967,7 @@ class MultiEngine(_ExtensionSetters):
             sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
             sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget))
         self.params = params if params is not None else default_params()
-        self.flags2 = int(flags2) | _flags2(todo)
+        self.flags2 = int(flags2) | _flags2(todo, self.L)
         _needs_create_ex(api, self.flags2)
         dev = None if devices is None else _i32(devices, n_gpus)
         self._m = C.c_void_p()

@@ -119,12 +119,18 @@ static int ramp_anchor_fits(dopf_ctx *c, const char *entry, int g, double pm, do
     return DOPF_OK;
 }
 
+static int ramp_budget_rows_fit(dopf_ctx *c, const char *entry, bool given_ramp, const double *up, const double *down, const double *prev,
+                                bool given_budget, const double *e_min, const double *e_max, bool given_table, const double *profiles,
+                                const int32_t *profile_of);
+
 // dopf_set_generator_ramp's checks: the flag, both ramp arrays or neither, no NaN, ramps >= 0, p_prev in [0, gen_pmax], and every
 // anchored generator able to stay under its caps (the stored availability table)
 int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev)
 {
     if (int rc = NEEDS_FLAG(c, "generator ramp limits need", DOPF_F_GEN_RAMP)) return rc;
-    return check_generator_ramp_values(c, "dopf_set_generator_ramp", c->gen_ramp_h.data(), c->gen_avail_h.data(), up, down, prev);
+    if (int rc = check_generator_ramp_values(c, "dopf_set_generator_ramp", c->gen_ramp_h.data(), c->gen_avail_h.data(), up, down, prev)) return rc;
+    // DOPF_F2_GEN_RAMP_BUDGET: ... and every row jointly feasible with its stored budget
+    return ramp_budget_rows_fit(c, "dopf_set_generator_ramp", true, up, down, prev, false, nullptr, nullptr, false, nullptr, nullptr);
 }
 
 // ... without the flag: the values alone, for `entry` (the name the messages carry). pmax: the capacities in sorted order; table:
@@ -162,13 +168,86 @@ static int budget_min_fits(dopf_ctx *c, const char *entry, int g, double pm, dou
     return DOPF_OK;
 }
 
+// DOPF_F2_GEN_RAMP_BUDGET: a row must be feasible under caps, ramps, anchor and budget at once. hi_t: the pointwise-largest path
+// (forward hi_0 = min(cap_0, prev + up), hi_t = min(cap_t, hi_{t-1} + up), then backward hi_t = min(hi_t, hi_{t+1} + down)); lo_t: the
+// pointwise-smallest (forward with down, backward with up, from 0). The feasible paths form a lattice, so both are feasible where any
+// path is, and the row is feasible exactly when lo_t <= hi_t for all t, e_min <= sum hi_t and sum lo_t <= e_max (sums in t order).
+// g: the caller's index (the message's); f: the generator's profile, or null; prev: NaN = no anchor
+static int ramp_budget_fits(dopf_ctx *c, const char *entry, int g, double pm, double up, double down, double prev, double e_min,
+                            double e_max, const double *f)
+{
+    const int T = c->v.T;
+    std::vector<double> hi((size_t)T), lo((size_t)T);
+    for (int t = 0; t < T; ++t) {
+        const double cap = f ? pm * f[t] : pm;
+        if (t == 0) {
+            hi[0] = std::isnan(prev) ? cap : std::min(cap, prev + up);
+            lo[0] = std::isnan(prev) ? 0.0 : std::max(0.0, prev - down);
+        } else {
+            hi[(size_t)t] = std::min(cap, hi[(size_t)t - 1] + up);
+            lo[(size_t)t] = std::max(0.0, lo[(size_t)t - 1] - down);
+        }
+    }
+    for (int t = T - 2; t >= 0; --t) {
+        hi[(size_t)t] = std::min(hi[(size_t)t], hi[(size_t)t + 1] + down);
+        lo[(size_t)t] = std::max(lo[(size_t)t], lo[(size_t)t + 1] - up);
+    }
+    double shi = 0.0, slo = 0.0;
+    for (int t = 0; t < T; ++t) {
+        if (lo[(size_t)t] > hi[(size_t)t])
+            return fail(c, DOPF_E_INVALID, "%s: generator g = %d has no path under its caps, ramps and anchor at t = %d (at least %g, at most %g)",
+                        entry, g, t, lo[(size_t)t], hi[(size_t)t]);
+        shi += hi[(size_t)t];
+        slo += lo[(size_t)t];
+    }
+    if (e_min > shi)
+        return fail(c, DOPF_E_INVALID, "%s: generator g = %d cannot deliver e_min = %g under its caps, ramps and anchor (the largest path sums to %g)",
+                    entry, g, e_min, shi);
+    if (slo > e_max)
+        return fail(c, DOPF_E_INVALID, "%s: generator g = %d cannot stay under e_max = %g under its ramps and anchor (the smallest path sums to %g)",
+                    entry, g, e_max, slo);
+    return DOPF_OK;
+}
+
+// ... for every row of a context with the bit: the stored ramps (gen_ramp_h), budgets (gen_budget_h), profile indices and table, each
+// replaced by the caller's where one is given (up / down / prev, e_min / e_max: the caller's order; given_ramp / given_budget say whether
+// the call sets them — a NULL then means the default; profiles / profile_of: the availability setter's arguments, with given_table)
+static int ramp_budget_rows_fit(dopf_ctx *c, const char *entry, bool given_ramp, const double *up, const double *down, const double *prev,
+                                bool given_budget, const double *e_min, const double *e_max, bool given_table, const double *profiles,
+                                const int32_t *profile_of)
+{
+    if (!c->plan.genRampBudget) return DOPF_OK;
+    const size_t G = (size_t)c->v.G;
+    const int T = c->v.T;
+    for (size_t i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        double u = c->gen_ramp_h[G + i], d = c->gen_ramp_h[2 * G + i], pv = c->gen_ramp_h[3 * G + i];
+        double lo = c->gen_budget_h[G + i], hi = c->gen_budget_h[2 * G + i];
+        if (given_ramp) { u = up ? up[a] : INFINITY; d = down ? down[a] : INFINITY; pv = prev ? prev[a] : std::nan(""); }
+        if (given_budget) { lo = e_min ? e_min[a] : 0.0; hi = e_max ? e_max[a] : INFINITY; }
+        const double *f = nullptr;
+        if (given_table) {
+            const int k = profile_of ? profile_of[a] : -1;
+            if (k >= 0) f = profiles + (size_t)k * T;
+        } else {
+            const int k = c->gen_prof_h.empty() ? -1 : c->gen_prof_h[i];
+            if (k >= 0) f = c->gen_avail_h.data() + (size_t)k * T;
+        }
+        if (int rc = ramp_budget_fits(c, entry, a, c->gen_ramp_h[i], u, d, pv, lo, hi, f)) return rc;
+    }
+    return DOPF_OK;
+}
+
 // dopf_set_generator_energy_budget's checks: the flag, no NaN, e_min finite and >= 0, e_max >= 0, e_min <= e_max, and every minimum
 // deliverable under the caps (the stored availability table)
 int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max)
 {
     if (!(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
         return fail(c, DOPF_E_UNSUPPORTED, "generator energy budgets need DOPF_F2_GEN_ENERGY_BUDGET at dopf_create_ex");
-    return check_generator_energy_budget_values(c, "dopf_set_generator_energy_budget", c->gen_budget_h.data(), c->gen_avail_h.data(), e_min, e_max);
+    if (int rc = check_generator_energy_budget_values(c, "dopf_set_generator_energy_budget", c->gen_budget_h.data(), c->gen_avail_h.data(), e_min, e_max))
+        return rc;
+    // DOPF_F2_GEN_RAMP_BUDGET: ... and every row jointly feasible with its stored ramps and anchor
+    return ramp_budget_rows_fit(c, "dopf_set_generator_energy_budget", false, nullptr, nullptr, nullptr, true, e_min, e_max, false, nullptr, nullptr);
 }
 
 // ... without the flag: the values alone, for `entry` (pmax, table: as check_generator_ramp_values)
@@ -220,7 +299,9 @@ int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles,
             if (int rc = budget_min_fits(c, "dopf_set_generator_availability", a, c->gen_budget_h[i], c->gen_budget_h[(size_t)G + i],
                                          k >= 0 ? profiles + (size_t)k * T : nullptr)) return rc;
         }
-    return DOPF_OK;
+    // DOPF_F2_GEN_RAMP_BUDGET: the stored ramps and budgets together, under the new table
+    return ramp_budget_rows_fit(c, "dopf_set_generator_availability", false, nullptr, nullptr, nullptr, false, nullptr, nullptr, true, profiles,
+                                profile_of);
 }
 
 // dopf_set_storage_terminal_level's checks: the flag, both arrays or neither, 0 <= lo <= hi <= emax (no NaN), and the band reachable
@@ -547,6 +628,10 @@ int check_solver(dopf_ctx *c)
             return fail(c, DOPF_E_SOLVER, "%llu sub-problem(s) were left unsolved (%llu since creation): a storage whose root search did not reach "
                                           "its tolerance, or a generator row whose knots exceeded the capacity of DOPF_F_GEN_RAMP_NETWORK (%d)",
                         n, (unsigned long long)c->host_st.solver_fail, ramp_net_knots(c->v.T, c->v.L));
+        if (c->plan.genRampBudget)
+            return fail(c, DOPF_E_SOLVER, "%llu sub-problem(s) were left unsolved (%llu since creation): a storage whose root search did not reach "
+                                          "its tolerance, or a generator row whose multiplier search under ramps and budget spent its %d evaluations "
+                                          "or %d rounds", n, (unsigned long long)c->host_st.solver_fail, kBudgetMaxEvals, kRampBudgetMaxRounds);
         if (c->plan.genBudget)
             return fail(c, DOPF_E_SOLVER, "%llu sub-problem(s) were left unsolved (%llu since creation): a storage whose root search did not reach "
                                           "its tolerance, or a generator row whose energy budget's multiplier search spent its %d evaluations",
@@ -769,7 +854,29 @@ int upload_agents(dopf_ctx *c, const Sorted &so)
     std::vector<double> mc(so.gmc);
     mc.resize(gen_mc_doubles(v.G, c->plan.genQuad), 0.0);
     d.upload(&v.gen_mc, mc);
-    if (c->plan.genRamp) {
+    if (c->plan.genRampBudget) {
+        // DOPF_F2_GEN_RAMP_BUDGET: ramps (+inf), anchor (NaN), budgets (0, +inf) and k_gen_ramp_budget's scratch behind the capacities;
+        // the scratch is never read before it is written. Both host mirrors keep the shapes their setters know
+        const size_t n = gen_ramp_budget_doubles(v.G, v.T, v.nGenItems);
+        size_t freeb = 0, totalb = 0;
+        HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
+        if (n * sizeof(double) > freeb)
+            return fail(c, DOPF_E_NOMEM, "ramp limits with energy budgets: the pair search's candidates (64 x %d doubles per row in flight, %d rows "
+                                         "per generator item) need %llu bytes, the device has %llu free", (int)ramp_row_doubles(v.T), kRampWaves,
+                        (unsigned long long)(n * sizeof(double)), (unsigned long long)freeb);
+        c->gen_ramp_h.assign(so.gpm.begin(), so.gpm.end());
+        c->gen_ramp_h.resize(3 * G, INFINITY);
+        c->gen_ramp_h.resize(4 * G, std::nan(""));
+        c->gen_budget_h.assign(so.gpm.begin(), so.gpm.end());
+        c->gen_budget_h.resize(2 * G, 0.0);
+        c->gen_budget_h.resize(gen_budget_doubles(v.G), INFINITY);
+        double *blk = nullptr;
+        d.raw(&blk, n);
+        if (d.rc) return d.rc;
+        HIPCHK(c, hipMemcpy(blk, c->gen_ramp_h.data(), 4 * G * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(blk + 4 * G, c->gen_budget_h.data() + G, 2 * G * sizeof(double), hipMemcpyHostToDevice));
+        v.gen_pmax = blk;
+    } else if (c->plan.genRamp) {
         // DOPF_F_GEN_RAMP: the ramps (+inf), the anchor (NaN: none) and k_gen_ramp's scratch behind the capacities; the scratch is
         // sized from the knots' bound and is never read before it is written
         // (networks, DOPF_F_GEN_RAMP_NETWORK: the scratch of k_gen_ramp_net, at every T, with the tables' kinks beside the ramps' knots)
@@ -962,9 +1069,9 @@ int dopf_create_ex(dopf_ctx **out, const dopf_problem *p, const dopf_params *q, 
 {
     if (!out || !p || !q) return fail(nullptr, DOPF_E_INVALID, "null argument");
     *out = nullptr;
-    if (const uint32_t unknown = (uint32_t)flags2 & ~(uint32_t)DOPF_F2_GEN_ENERGY_BUDGET)
-        return fail(nullptr, DOPF_E_INVALID, "dopf_create_ex: flags2 has the unknown bit %u (the second word knows DOPF_F2_GEN_ENERGY_BUDGET = 1)",
-                    unknown & (~unknown + 1u));
+    if (const uint32_t unknown = (uint32_t)flags2 & ~(uint32_t)(DOPF_F2_GEN_ENERGY_BUDGET | DOPF_F2_GEN_RAMP_BUDGET))
+        return fail(nullptr, DOPF_E_INVALID, "dopf_create_ex: flags2 has the unknown bit %u (the second word knows DOPF_F2_GEN_ENERGY_BUDGET = 1 "
+                                             "and DOPF_F2_GEN_RAMP_BUDGET = 8)", unknown & (~unknown + 1u));
     if (int rc = validate(p, q)) return rc;
     int dev = 0;
     if (int rc = pick_device(q, &dev)) return rc;
@@ -1686,7 +1793,9 @@ int dopf_set_generator_energy_budget(dopf_ctx *c, const double *e_min, const dou
     }
     // ordered on the context's stream behind what is queued there; the graphs read the same device array (no capture again). The
     // state stays; the stop test starts over, as after dopf_set_generator_ramp
-    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(gen_budget_min(c->v)), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+    // (DOPF_F2_GEN_RAMP_BUDGET: the budgets sit behind the ramps and the anchor)
+    const double *dst = c->plan.genRampBudget ? gen_rb_min(c->v) : gen_budget_min(c->v);
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(dst), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
     launch_reset_status(c->v, c->main);
     HIPCHK(c, hipGetLastError());
     if (int rc = read_status(c)) return rc;          // (synchronises: h may go)

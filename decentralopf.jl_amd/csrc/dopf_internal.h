@@ -26,6 +26,7 @@
 #include "dopf_plan.h"
 #include "ramp_dp.h"
 #include "budget_root.h"
+#include "ramp_budget.h"
 #include "central_rows.h"
 
 namespace dopf {
@@ -225,6 +226,18 @@ __host__ __device__ inline double *gen_ramp_scratch(const DevView &v) { return c
 inline size_t gen_budget_doubles(int G) { return 3 * (size_t)G; }
 __host__ __device__ inline const double *gen_budget_min(const DevView &v) { return v.gen_pmax + v.G; }
 __host__ __device__ inline const double *gen_budget_max(const DevView &v) { return v.gen_pmax + 2 * (size_t)v.G; }
+// ... with DOPF_F2_GEN_RAMP_BUDGET (both at once, copper plates) the ramps keep their places and the budgets follow them:
+// pmax | ramp_up | ramp_down | p_prev | e_min | e_max, then k_gen_ramp_budget's scratch, at every T — per wave of the launch
+// (kRampWaves per generator item) the row's centres c[T] and, for each of the 64 candidates a round of the pair search runs, the work
+// arrays of the ramp programme, ramp_row_doubles(T), interleaved [slot][lane]
+__host__ __device__ inline size_t ramp_budget_wave_doubles(int T) { return (size_t)T + 64 * ramp_row_doubles(T); }
+inline size_t gen_ramp_budget_doubles(int G, int T, int nGenItems)
+{
+    return 6 * (size_t)G + (size_t)nGenItems * kRampWaves * ramp_budget_wave_doubles(T);
+}
+__host__ __device__ inline const double *gen_rb_min(const DevView &v) { return v.gen_pmax + 4 * (size_t)v.G; }
+__host__ __device__ inline const double *gen_rb_max(const DevView &v) { return v.gen_pmax + 5 * (size_t)v.G; }
+__host__ __device__ inline double *gen_rb_scratch(const DevView &v) { return const_cast<double *>(v.gen_pmax) + 6 * (size_t)v.G; }
 
 // The gen_state block (v.gen_state; gen_state_ints). DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
 // gen_pmax[g] for k = -1. gen_state has room for both behind its G row states: the G profile indices (sorted order, -1 until
@@ -362,6 +375,7 @@ void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_gen_ramp(const DevView &v, const Plan &p, hipStream_t s);       // gen_ramp.h: the generators of a DOPF_F_GEN_RAMP context
 void launch_gen_ramp_net(const DevView &v, const Plan &p, hipStream_t s);   // gen_ramp_net.h: ... on a network (DOPF_F_GEN_RAMP_NETWORK)
 void launch_gen_budget(const DevView &v, const Plan &p, hipStream_t s);     // gen_budget.h: the generators of a DOPF_F2_GEN_ENERGY_BUDGET context
+void launch_gen_ramp_budget(const DevView &v, const Plan &p, hipStream_t s);   // gen_ramp_budget.h: ... of a DOPF_F2_GEN_RAMP_BUDGET context
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);
 void launch_agents_fused(const DevView &v, const Plan &p, hipStream_t s);

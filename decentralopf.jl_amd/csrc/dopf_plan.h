@@ -61,7 +61,9 @@ struct Plan {
                                     // fused generator blocks, no one-launch tail), with the exact projection onto {box, ramps} for the rows that need it
     bool genRampNet;                // ... on a network (DOPF_F_GEN_RAMP_NETWORK, L > 0): k_gen_ramp_net<AV, QC>, the chain a network runs under DOPF_F_NO_FUSE
     bool genBudget;                 // DOPF_F2_GEN_ENERGY_BUDGET (the second flag word): k_gen_budget<LINES, AV, QC> (gen_budget.h) on the same chain, copper
-                                    // plates and networks; refused together with genRamp
+                                    // plates and networks; refused together with genRamp unless ...
+    bool genRampBudget;             // DOPF_F2_GEN_RAMP_BUDGET (copper plates, with genRamp and genBudget): k_gen_ramp_budget<AV, QC> (gen_ramp_budget.h)
+                                    // on the same chain — the ramp programme inside the budget's multiplier search
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those
@@ -216,8 +218,17 @@ inline Plan plan_chain(const Shape &sh, unsigned flags, int cus, unsigned flags2
     // DOPF_F2_GEN_ENERGY_BUDGET: the same chain again with k_gen_budget as the generators' launch, on every shape. With ramps a row
     // would carry two constraints that couple its timesteps (the ramp programme inside the multiplier search): refused
     p.genBudget = G > 0 && (flags2 & DOPF_F2_GEN_ENERGY_BUDGET);
-    if ((flags2 & DOPF_F2_GEN_ENERGY_BUDGET) && (flags & DOPF_F_GEN_RAMP))
+    if ((flags2 & DOPF_F2_GEN_ENERGY_BUDGET) && (flags & DOPF_F_GEN_RAMP) && !(flags2 & DOPF_F2_GEN_RAMP_BUDGET))
         p.refusal = "DOPF_F2_GEN_ENERGY_BUDGET does not combine with DOPF_F_GEN_RAMP: one constraint that couples a generator's timesteps per context";
+    // DOPF_F2_GEN_RAMP_BUDGET: the pair on a copper plate, the same chain with k_gen_ramp_budget as the generators' launch (the ramp
+    // programme inside the multiplier search; its scratch grows with T: the caller asks for it). Alone it is refused, as on a network
+    p.genRampBudget = G > 0 && L == 0 && (flags2 & DOPF_F2_GEN_RAMP_BUDGET) && (flags2 & DOPF_F2_GEN_ENERGY_BUDGET) && (flags & DOPF_F_GEN_RAMP);
+    if (flags2 & DOPF_F2_GEN_RAMP_BUDGET) {
+        if (!((flags2 & DOPF_F2_GEN_ENERGY_BUDGET) && (flags & DOPF_F_GEN_RAMP)))
+            p.refusal = "DOPF_F2_GEN_RAMP_BUDGET means nothing without DOPF_F_GEN_RAMP and DOPF_F2_GEN_ENERGY_BUDGET";
+        else if (L > 0)
+            p.refusal = "DOPF_F2_GEN_RAMP_BUDGET runs on copper plates: DOPF_F_GEN_RAMP and DOPF_F2_GEN_ENERGY_BUDGET do not combine on a network";
+    }
     if (p.genQuad || p.genRamp || p.genBudget) flags |= DOPF_F_NO_FUSE;
     p.genTT2 = (!p.genQuad && !p.genRamp && !p.genBudget && L == 0 && T % 2 == 0 && T / 2 <= 512) ? T / 2 : 0;
     p.fuseAgents = p.genTT2 > 0 && p.genTT2 <= 256 && G > 0 && S > 0 && p.useWarm && !(flags & (DOPF_F_NO_FUSE | DOPF_F_OVERLAP_AGENTS));

@@ -884,6 +884,7 @@ __global__ __launch_bounds__(512) void k_gen_update_pair_skip(DevView v)
 void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s)
 {
     if (v.nGenItems == 0) return;
+    if (p.genRampBudget) { launch_gen_ramp_budget(v, p, s); return; }      // DOPF_F2_GEN_RAMP_BUDGET: k_gen_ramp_budget<AV, QC> (gen_ramp_budget.h)
     if (p.genBudget) { launch_gen_budget(v, p, s); return; }       // DOPF_F2_GEN_ENERGY_BUDGET: k_gen_budget<LINES, AV, QC> (gen_budget.h)
     if (p.genRampNet) { launch_gen_ramp_net(v, p, s); return; }    // ... on a network: k_gen_ramp_net<AV, QC> (gen_ramp_net.h)
     if (p.genRamp) { launch_gen_ramp(v, p, s); return; }       // DOPF_F_GEN_RAMP: k_gen_ramp<AV, QC> (gen_ramp.h)
@@ -2396,6 +2397,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
 #include "gen_ramp.h"
 #include "gen_ramp_net.h"
 #include "gen_budget.h"
+#include "gen_ramp_budget.h"
 namespace dopf {
 
 // The scan body as a function of its own (networks): called by k_sto_warm for the rare item the active-set body leaves

@@ -135,6 +135,7 @@ const DOPF_F_GEN_QUADRATIC_COST = 1073741824  # include/dopf.h
 const DOPF_F_GEN_RAMP = 32  # include/dopf.h
 const DOPF_F_GEN_RAMP_NETWORK = typemin(Int32)  # include/dopf.h: 2147483648, bit 31 — the sign bit of the Cint flag word, and its last
 const DOPF_F2_GEN_ENERGY_BUDGET = 1  # include/dopf.h: the second flag word (the `flags2` keyword; dopf_create_ex)
+const DOPF_F2_GEN_RAMP_BUDGET = 8  # include/dopf.h: ramp limits and energy budgets on the same generators (copper plates)
 const DOPF_TRACE_DUALS = 1      # include/dopf.h: dopf_trace_begin's `what` — lambda, mu, rho
 const DOPF_TRACE_CONSENSUS = 2  # injection, avg_U, avg_K, line_util
 const DOPF_TRACE_PRIMAL = 4     # P, D, C (E is derived when read)
@@ -162,6 +163,9 @@ generator cost curves (see `set_quadratic_cost!`) `flags = DOPF_F_GEN_QUADRATIC_
 with lines the constructor adds `DOPF_F_GEN_RAMP_NETWORK`, the library's opt-in for the network step's knot scratch. Flags combine with `|`.
 `flags2` is the second flag word (`dopf_params.flags` is full): generator energy budgets over the window (see `set_energy_budget!`)
 need `flags2 = DOPF_F2_GEN_ENERGY_BUDGET`; a non-zero `flags2` creates the context through `dopf_create_ex` / `dopf_multi_create_ex`.
+With `flags = DOPF_F_GEN_RAMP` and `flags2 = DOPF_F2_GEN_ENERGY_BUDGET` together on a case without lines the constructor adds
+`DOPF_F2_GEN_RAMP_BUDGET`, the library's opt-in for the scratch of the step that keeps both (DESIGN.md 5x); with lines it adds nothing
+and the library's refusal of the two together comes back as it is.
 """
 function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}, storages::Vector{Storage},
               lines::Vector{Line}; max_iters::Int=0, device::Int=-1, n_gpus::Int=1, record::Bool=false,
@@ -170,6 +174,9 @@ function ADMM(gamma::Float64, nodes::Vector{Node}, generators::Vector{Generator}
     G, S = length(generators), length(storages)
     if (flags & DOPF_F_GEN_RAMP) != 0 && L > 0
         flags |= DOPF_F_GEN_RAMP_NETWORK         # ramps on a network: k_gen_ramp_net and its knot scratch (DESIGN.md 5s)
+    end
+    if (flags & DOPF_F_GEN_RAMP) != 0 && (flags2 & DOPF_F2_GEN_ENERGY_BUDGET) != 0 && L == 0
+        flags2 |= DOPF_F2_GEN_RAMP_BUDGET        # ramps and budgets on a copper plate: k_gen_ramp_budget and its scratch (DESIGN.md 5x)
     end
     node_to_id = Dict{Node, Int}(n => i for (i, n) in enumerate(nodes))
     demand = Float64[nodes[n].demand[t] for n in 1:N, t in 1:T]          # N x T, column-major = [n + N*t]

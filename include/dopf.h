@@ -214,7 +214,8 @@ typedef struct dopf_params {
                                   * L > 0 (DOPF_E_UNSUPPORTED) unless DOPF_F_GEN_RAMP_NETWORK is given too, dopf_roll_horizon refuses a
                                   * context with it (the anchor's roll is the host's: build the next window's context).
                                   * dopf_central_solve, _ex and _lossy ignore the flag. dopf_central_solve_coupled ignores it too and
-                                  * takes the ramps and the anchor as arguments. */
+                                  * takes the ramps and the anchor as arguments. Energy budgets on the same generators (copper plates):
+                                  * DOPF_F2_GEN_RAMP_BUDGET, in the second flag word. */
 #define DOPF_F_GEN_RAMP_NETWORK 2147483648u /* ramp limits on a network (L > 0); meaningful only together with DOPF_F_GEN_RAMP, and an
                                   * opt-in of its own because the network step needs memory that grows with the tables. A row's derivative
                                   * per step is then mc + c2 x + Psi(x - p0) + w_prox (x - p0), piecewise linear with up to 2L kinks of the
@@ -255,7 +256,32 @@ typedef struct dopf_params {
                                   * that couple a row's timesteps need the ramp programme inside the multiplier search); dopf_roll_horizon
                                   * refuses a context with it (what is left of a budget after k steps is the host's arithmetic);
                                   * dopf_central_solve, _ex and _lossy take no budgets and ignore the bit. dopf_central_solve_coupled
-                                  * takes the budgets as arguments, together with ramps if the caller has both. */
+                                  * takes the budgets as arguments, together with ramps if the caller has both. On a copper plate
+                                  * DOPF_F2_GEN_RAMP_BUDGET lifts that refusal: the pair then runs in one context. */
+#define DOPF_F2_GEN_RAMP_BUDGET 8 /* ramp limits and energy budgets on the same generators (copper plates, L == 0); meaningful only together
+                                  * with DOPF_F_GEN_RAMP and DOPF_F2_GEN_ENERGY_BUDGET, and an opt-in of its own because the step needs
+                                  * scratch that grows with T. The generator's step keeps its objective and its box (cap[g,t] under
+                                  * DOPF_F_GEN_AVAILABILITY, the c2 term under DOPF_F_GEN_QUADRATIC_COST) and obeys the ramps, the anchor
+                                  * included, and e_min[g] <= sum_t P[g,t] <= e_max[g] at once: the exact minimiser, not a sequence of two
+                                  * projections. With a multiplier nu on the budget row the step is the ramp projection of the centres
+                                  * c_t - nu / q; its sum is continuous, piecewise linear and non-increasing in nu, and two candidates with
+                                  * the same active set bracket a stretch on which it is linear (k_gen_ramp_budget). A row
+                                  * whose clamped step keeps both constraints keeps the bits of k_gen_update, one that needs only the
+                                  * budget's search those of k_gen_budget, one that needs only the ramps' repair those of k_gen_ramp; the
+                                  * others run the pair search, 64 candidate multipliers per round, in a scratch of
+                                  * 64 x (5T + 4) + T doubles per wave and 8 waves per generator item, allocated at dopf_create
+                                  * (DOPF_E_NOMEM, naming the bytes, where it does not fit). A row whose search spends its rounds keeps
+                                  * its step at nu = 0 for the iteration and is counted: dopf_iterate returns DOPF_E_SOLVER and
+                                  * dopf_solver_failures() grows. The chain is the one DOPF_F_GEN_RAMP contexts run. The three setters
+                                  * dopf_set_generator_ramp, dopf_set_generator_energy_budget and dopf_set_generator_availability keep
+                                  * their meaning, timing and status rules and also check, before anything is stored, that every row is
+                                  * jointly feasible: with hi_t the pointwise-largest and lo_t the pointwise-smallest path under caps, ramps
+                                  * and anchor, lo_t <= hi_t for every t, e_min <= sum_t hi_t and sum_t lo_t <= e_max (DOPF_E_INVALID,
+                                  * naming g and the failing sum; the feasible paths form a lattice, so the check is exact). dopf_create
+                                  * refuses (DOPF_E_UNSUPPORTED) the bit without both of the other two flags, and with L > 0 (a network
+                                  * row's knots are 64 times too many for this design); with G == 0 it is accepted and ignored. The two
+                                  * older flags without the bit behave as before. dopf_roll_horizon goes on refusing the context;
+                                  * dopf_central_solve* ignore the bit. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
  * (how long an exchange kernel waits for a lost peer). Tuning knobs of the experiments (item counts, block counts, launch splits)
