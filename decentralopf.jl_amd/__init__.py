@@ -9,7 +9,7 @@ from .central import (CentralResult, central_reference, central_reference_couple
                       solve_central_packed)
 from .admm import ADMM, calculate_iteration, export_results, get_nodal_price, run, run_recorded
 from .sharded import ShardedADMM
-from .horizon import shift_window
+from .horizon import shift_coupled, shift_window
 from ._capi import DopfError, Engine, default_params, hip_api
 from .network import (Generator, Line, Node, PackedProblem, Storage, calculate_ptdf, pack,
                       three_node_case)
@@ -18,4 +18,5 @@ __all__ = ["DopfError", "Engine", "default_params", "hip_api", "Generator", "Lin
            "PackedProblem", "Storage", "calculate_ptdf", "pack", "three_node_case", "_capi",
            "network", "synth", "admm", "sharded", "ADMM", "calculate_iteration",
            "export_results", "get_nodal_price", "run", "run_recorded", "ShardedADMM", "central", "CentralResult",
-           "central_reference", "central_reference_on_device", "central_reference_coupled_on_device", "solve_central_packed", "horizon", "shift_window"]
+           "central_reference", "central_reference_on_device", "central_reference_coupled_on_device", "solve_central_packed", "horizon", "shift_window",
+           "shift_coupled"]

@@ -157,6 +157,10 @@ class CApi:
         # the receding-horizon entries: optional — a library of the same ABI may lack them (Engine.roll then goes the host route)
         self._opt("set_demand", C.c_int, [ctxp, c_double_p])
         self._opt("roll_horizon", C.c_int, [ctxp, C.c_int32, c_double_p])
+        # ... for contexts with ramp limits or energy budgets (Engine.roll_coupled), and the getter its mirrors follow
+        self._opt("roll_horizon_coupled", C.c_int, [ctxp, C.c_int32, c_double_p, C.c_int32, c_double_p, c_int32_p, C.c_int32,
+                                                    c_double_p, c_double_p])
+        self._opt("get_generator_coupling", C.c_int, [ctxp] + [c_double_p] * 5)
         if prefix == "dopf_":
             self._sig("bind_consensus", C.c_int, [ctxp, C.c_void_p])
             self._sig("solver_failures", C.c_int64, [ctxp])
@@ -800,6 +804,51 @@ class Engine(_ExtensionSetters):
         new.set_state(P=w["P"], D=w["D"], C_=w["C"], avg_U=w["avg_U"], avg_K=w["avg_K"], lam=w["lam"], mu=w["mu"], rho=w["rho"],
                       iteration=2)
         self._adopt(new)
+
+    def generator_coupling(self) -> dict:
+        """dopf_get_generator_coupling: ramp_up, ramp_down, p_prev (NaN: no anchor), e_min, e_max as the context holds them, G values
+        each (a context without the flag: inf, inf, NaN, 0, inf). A backend without the entry: DopfError."""
+        if not hasattr(self.api, "get_generator_coupling"):
+            raise DopfError(f"{self.api.prefix}*: this API has no get_generator_coupling")
+        names = ("ramp_up", "ramp_down", "p_prev", "e_min", "e_max")
+        out = {n: np.empty(self.G) for n in names}
+        self._chk(self.api.get_generator_coupling(self._ctx, *(_dp(out[n]) for n in names)))
+        return out
+
+    def roll_coupled(self, k: int, demand_tail, *, availability=None, budget=None):
+        """dopf_roll_horizon_coupled: roll for a context with ramp limits or energy budgets, in place — the context, its scratch
+        and its graphs stay. The rule is horizon.shift_window's plus horizon.shift_coupled's: the anchor becomes P[:, k - 1], and
+        what the k leaving steps delivered comes off both budgets, floored at 0. availability = (profiles, profile_of), as
+        set_availability takes them ((None, None): every generator back to max_generation): the new window's table, checked together
+        with the new anchor and budgets; None: the stored table stays. budget = (e_min, e_max), as set_energy_budget takes them: the
+        new window's own budgets instead of what is left. A refusal (DopfError) leaves the context as it was. A backend without
+        the entry: DopfError (Engine.roll's host route serves there)."""
+        if not hasattr(self.api, "roll_horizon_coupled"):
+            raise DopfError(f"{self.api.prefix}*: this API has no roll_horizon_coupled")
+        k = int(k)
+        if not 1 <= k <= self.T - 1:
+            self._chk(self.api.roll_horizon_coupled(self._ctx, k, None, -1, None, None, 0, None, None))       # (the library's refusal and message)
+            raise ValueError(f"roll_coupled: k = {k} outside [1, T - 1 = {self.T - 1}]")
+        tail = np.asarray(demand_tail, dtype=np.float64).reshape(self.N, k)
+        K, prof, of = -1, None, None
+        if availability is not None:
+            prof, of = _availability_norm(self, *availability)
+            K = 0 if prof is None else prof.shape[0]
+        lo, hi = (None, None) if budget is None else _budget_norm(self, *budget)
+        self._chk(self.api.roll_horizon_coupled(
+            self._ctx, k, _dp(_f64(tail.T, self.N * k)), K, _dp(None if prof is None else prof.ravel()),
+            None if of is None else of.ctypes.data_as(c_int32_p), 0 if budget is None else 1, _dp(lo), _dp(hi)))
+        self._keep["demand"] = _f64(np.concatenate([self.demand()[:, k:], tail], axis=1).T)
+        now = self.generator_coupling()              # (the device's arithmetic, not a second evaluation of the rule)
+        if self.params.flags & F_GEN_RAMP:
+            self._mirror["gen_prev"] = now["p_prev"]
+        if self.flags2 & F2_GEN_ENERGY_BUDGET:
+            self._mirror["gen_budget"] = (now["e_min"], now["e_max"])
+        if availability is not None:
+            self._mirror.update(gen_avail=None if prof is None else prof.copy(), gen_avail_of=None if of is None else of.copy())
+        r = self._mirror.get("line_rating")
+        if r is not None:          # (the library moved its table by the same rule)
+            self._mirror["line_rating"] = np.concatenate([r[:, k:], np.repeat(r[:, -1:], k, axis=1)], axis=1)
 
     def _adopt(self, new: "Engine"):
         """This engine goes on as `new`: its own context is destroyed, new's context and host mirrors move here, and `new` is left

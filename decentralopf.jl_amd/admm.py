@@ -243,6 +243,19 @@ class ADMM:
             self.packed.line_rating = np.concatenate([r[:, int(k):], np.repeat(r[:, -1:], int(k), axis=1)], axis=1)
         self._new_window(self.engine.demand())
 
+    def roll_coupled(self, k: int, demand_tail, *, availability=None, budget=None) -> None:
+        """roll for a case with ramp limits or energy budgets, in place (dopf_roll_horizon_coupled; horizon.shift_coupled has the
+        rule): the ramps' anchor becomes the output of step k - 1, and what the k leaving steps delivered comes off both budgets,
+        floored at 0. availability = (profiles, profile_of): the new window's table, checked together with the new anchor;
+        budget = (e_min, e_max): the new window's own budgets instead of what is left. Everything else as roll."""
+        self.engine.roll_coupled(k, demand_tail, availability=availability, budget=budget)
+        if self.packed.line_rating is not None:          # (moved with the window: the old last column behind the kept part)
+            r = np.asarray(self.packed.line_rating, dtype=np.float64)
+            self.packed.line_rating = np.concatenate([r[:, int(k):], np.repeat(r[:, -1:], int(k), axis=1)], axis=1)
+        if self.packed.gen_budget is not None:           # (what the device left of them)
+            self.packed.gen_budget = tuple(b.copy() for b in self.engine._mirror["gen_budget"])
+        self._new_window(self.engine.demand())
+
     # -- one iteration -------------------------------------------------------------------------
     def _fetch_result(self) -> Result:
         P, D, C, E = self.engine.get_primal()

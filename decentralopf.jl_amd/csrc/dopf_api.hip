@@ -268,8 +268,9 @@ int check_generator_energy_budget_values(dopf_ctx *c, const char *entry, const d
     return DOPF_OK;
 }
 
-// dopf_set_generator_availability's checks: the flag, a table of K >= 0 profiles with every value in [0, 1] (no NaN), and every index in [-1, K)
-int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of)
+// the form of dopf_set_generator_availability's arguments: the flag, a table of K >= 0 profiles with every value in [0, 1] (no NaN), and
+// every index in [-1, K)
+static int check_availability_table(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of)
 {
     if (int rc = NEEDS_FLAG(c, "generator availability needs", DOPF_F_GEN_AVAILABILITY)) return rc;
     if (K < 0) return fail(c, DOPF_E_INVALID, "n_profiles = %d < 0", K);
@@ -287,6 +288,14 @@ int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles,
         for (int g = 0; g < G; ++g)
             if (profile_of[g] < -1 || profile_of[g] >= K)
                 return fail(c, DOPF_E_INVALID, "profile_of[%d] = %d outside [-1, %d)", g, profile_of[g], K);
+    return DOPF_OK;
+}
+
+// dopf_set_generator_availability's checks: the table's form, and the stored anchors, minima and pairs under the new table
+int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles, const int32_t *profile_of)
+{
+    if (int rc = check_availability_table(c, K, profiles, profile_of)) return rc;
+    const int T = c->v.T, G = c->v.G;
     if (c->q.flags & DOPF_F_GEN_RAMP)      // the anchors of dopf_set_generator_ramp, under the new table
         for (int i = 0; i < G; ++i) {
             const int a = c->gen_perm[i], k = profile_of ? profile_of[a] : -1;
@@ -1677,17 +1686,12 @@ int dopf_set_storage_efficiency(dopf_ctx *c, const double *eta_c, const double *
     return set_sto_slots(c, kStoAlpha, 2, eta_d ? al.data() : nullptr, eta_c);
 }
 
-int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const double *profiles, const int32_t *profile_of)
+// a checked table and the generators' indices (pr: sorted order) on their way to the device, on the context's stream; the caller
+// synchronises before profiles and pr go, and keeps the host mirrors (dopf_set_generator_availability, dopf_roll_horizon_coupled)
+static int queue_availability(dopf_ctx *c, int32_t n_profiles, const double *profiles, const std::vector<int> &pr)
 {
-    if (!c) return DOPF_E_INVALID;
-    if (int rc = check_generator_availability(c, n_profiles, profiles, profile_of)) return rc;
     DevView &v = c->v;
     const int G = v.G, T = v.T;
-    if (G == 0) return DOPF_OK;
-    DeviceGuard guard(c->device);
-    std::vector<int> pr(G, -1);
-    if (profile_of)
-        for (int i = 0; i < G; ++i) pr[i] = profile_of[c->gen_perm[i]];
     const size_t need = (size_t)n_profiles * T;
     if (n_profiles > c->gen_avail_cap) {
         // the table grows: a new allocation, whose address goes into gen_avail_slot(v) behind everything queued (the kernels read it
@@ -1708,6 +1712,21 @@ int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const doubl
     HIPCHK(c, hipMemcpyAsync(gen_prof(v), pr.data(), sizeof(int) * G, hipMemcpyHostToDevice, c->main));
     launch_demote_full_rows(v, c->main);
     HIPCHK(c, hipGetLastError());
+    return DOPF_OK;
+}
+
+int dopf_set_generator_availability(dopf_ctx *c, int32_t n_profiles, const double *profiles, const int32_t *profile_of)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_generator_availability(c, n_profiles, profiles, profile_of)) return rc;
+    const int G = c->v.G;
+    if (G == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<int> pr(G, -1);
+    if (profile_of)
+        for (int i = 0; i < G; ++i) pr[i] = profile_of[c->gen_perm[i]];
+    const size_t need = (size_t)n_profiles * c->v.T;
+    if (int rc = queue_availability(c, n_profiles, profiles, pr)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->main));
     c->gen_prof_h = pr;
     if ((c->q.flags & DOPF_F_GEN_RAMP) || (c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET)) c->gen_avail_h.assign(profiles, profiles + need);      // (what dopf_set_generator_ramp checks its anchors against, dopf_set_generator_energy_budget its minima)
@@ -1805,14 +1824,20 @@ int dopf_set_generator_energy_budget(dopf_ctx *c, const double *e_min, const dou
 
 // scratch of dopf_set_demand / dopf_roll_horizon, allocated at the first call (freed with the context's other arrays): the moved
 // per-timestep vectors (demand, 2 x lambda, 8 line vectors, with DOPF_F_LINE_RATING the rating table) | the caller's demand tail (up to N*(T-1)) | the new initial levels (S)
-static int roll_scratch(dopf_ctx *c, double **out)
+// | dopf_roll_horizon_coupled: the new anchor, what is left of e_min and e_max, what was spent (G each). The offsets are formed here alone
+struct RollScratch { double *vecs, *tail, *e0, *gen; };
+static int roll_scratch(dopf_ctx *c, RollScratch *out)
 {
+    const size_t NT = (size_t)c->v.N * c->v.T, LT = (size_t)c->v.L * c->v.T, S = (size_t)c->v.S, G = (size_t)c->v.G;
+    const size_t vecs = NT + 2 * (size_t)c->v.T + (c->v.fmax_ld ? 9 : 8) * LT;
     if (!c->roll_scratch) {
-        const size_t NT = (size_t)c->v.N * c->v.T, LT = (size_t)c->v.L * c->v.T;
-        int rc = dev_alloc(c, &c->roll_scratch, 2 * NT + 2 * (size_t)c->v.T + (c->v.fmax_ld ? 9 : 8) * LT + (size_t)c->v.S, false);
+        int rc = dev_alloc(c, &c->roll_scratch, vecs + NT + S + 4 * G, false);
         if (rc) return rc;
     }
-    *out = c->roll_scratch;
+    out->vecs = c->roll_scratch;
+    out->tail = out->vecs + vecs;
+    out->e0 = out->tail + NT;
+    out->gen = out->e0 + S;
     return DOPF_OK;
 }
 
@@ -1846,52 +1871,115 @@ int dopf_set_demand(dopf_ctx *c, const double *demand)
     return read_status(c);
 }
 
-int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
+// what dopf_roll_horizon_coupled takes beyond dopf_roll_horizon's arguments
+struct RollCoupling {
+    int32_t n_profiles;                    // -1: the stored table stays
+    const double *profiles;
+    const int32_t *profile_of;
+    int32_t set_budget;                    // != 0: e_min / e_max are the new window's budgets (NULL: 0 / +inf)
+    const double *e_min, *e_max;
+};
+
+// the generators' host mirrors as the next window will have them, in the shapes the context keeps (sorted order). The setters' checks
+// read the context's mirrors, so the roll's checks run with these swapped in, and they are swapped in for good once the commit is queued
+struct GenWindow {
+    std::vector<double> ramp, budget, avail;
+    std::vector<int> prof;
+    void swap(dopf_ctx *c) { c->gen_ramp_h.swap(ramp); c->gen_budget_h.swap(budget); c->gen_avail_h.swap(avail); c->gen_prof_h.swap(prof); }
+};
+
+// the three setters' checks on the next window: the new anchor under the stored ramps, the new budgets, both under the table that
+// will be in force, and with DOPF_F2_GEN_RAMP_BUDGET every row's joint feasibility. The context's mirrors are as before at return
+static int check_gen_window(dopf_ctx *c, const char *entry, GenWindow &w)
 {
-    if (!c) return DOPF_E_INVALID;
+    const size_t G = (size_t)c->v.G;
+    const bool ramp = c->plan.genRamp, budget = c->plan.genBudget;
+    std::vector<double> up, down, prev, lo, hi;          // (the checks read the caller's order)
+    if (ramp) { up.resize(G); down.resize(G); prev.resize(G); }
+    if (budget) { lo.resize(G); hi.resize(G); }
+    for (size_t i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        if (ramp) { up[a] = w.ramp[G + i]; down[a] = w.ramp[2 * G + i]; prev[a] = w.ramp[3 * G + i]; }
+        if (budget) { lo[a] = w.budget[G + i]; hi[a] = w.budget[2 * G + i]; }
+    }
+    w.swap(c);
+    int rc = DOPF_OK;
+    if (ramp) rc = check_generator_ramp_values(c, entry, c->gen_ramp_h.data(), c->gen_avail_h.data(), up.data(), down.data(), prev.data());
+    if (!rc && budget) rc = check_generator_energy_budget_values(c, entry, c->gen_budget_h.data(), c->gen_avail_h.data(), lo.data(), hi.data());
+    if (!rc) rc = ramp_budget_rows_fit(c, entry, false, nullptr, nullptr, nullptr, false, nullptr, nullptr, false, nullptr, nullptr);
+    w.swap(c);
+    return rc;
+}
+
+// the body of dopf_roll_horizon and dopf_roll_horizon_coupled (cp: the latter's inputs, null for the former, whose caller has refused
+// the contexts with an anchor or a budget)
+static int roll_window(dopf_ctx *c, const char *entry, int32_t k, const double *demand_tail, const RollCoupling *cp)
+{
     DevView &v = c->v;
     const int N = v.N, L = v.L, T = v.T, S = v.S;
-    if (c->comm) return roll_checks(c, "dopf_roll_horizon", "demand_tail", demand_tail, 0, N, 0);
-    if (c->q.flags & DOPF_F_GEN_RAMP)
-        return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: not on a context with DOPF_F_GEN_RAMP (the anchor p_prev of the next window is "
-                                           "the host's to set: build that window's context)");
-    if (c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET)
-        return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: not on a context with DOPF_F2_GEN_ENERGY_BUDGET (what is left of a budget after "
-                                           "k steps is the host's to work out: build that window's context)");
-    if (k < 1 || k >= T) return fail(c, DOPF_E_INVALID, "dopf_roll_horizon: k = %d outside [1, T - 1 = %d]", k, T - 1);
-    if (int rc = roll_checks(c, "dopf_roll_horizon", "demand_tail", demand_tail, (size_t)N * k, N, T - k)) return rc;
+    const size_t G = (size_t)v.G;
+    if (k < 1 || k >= T) return fail(c, DOPF_E_INVALID, "%s: k = %d outside [1, T - 1 = %d]", entry, k, T - 1);
+    if (int rc = roll_checks(c, entry, "demand_tail", demand_tail, (size_t)N * k, N, T - k)) return rc;
     if (S > 0 && !(c->q.flags & DOPF_F_STO_INITIAL_LEVEL))
-        return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: the storages' levels after %d steps become the next window's initial levels, "
-                                           "which need DOPF_F_STO_INITIAL_LEVEL at dopf_create", k);
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: the storages' levels after %d steps become the next window's initial levels, "
+                                           "which need DOPF_F_STO_INITIAL_LEVEL at dopf_create", entry, k);
+    // the generator part: the anchor, what is left of the stored budgets (or the caller's new ones), the caller's table
+    const bool ramp = cp && c->plan.genRamp, budget = cp && c->plan.genBudget, table = cp && G > 0 && cp->n_profiles >= 0;
+    const bool left = budget && !cp->set_budget, gens = ramp || budget || table;
     DeviceGuard guard(c->device);
-    const size_t NT = (size_t)N * T, LT = (size_t)L * T;
-    double *scr = nullptr;
+    RollScratch scr{};
     if (int rc = roll_scratch(c, &scr)) return rc;
-    double *tail_d = scr + NT + 2 * (size_t)T + (v.fmax_ld ? 9 : 8) * LT, *e0_d = tail_d + NT;
-    std::vector<double> e0s(S), e0c(S);
-    if (S > 0) {
-        // the new initial levels first, into scratch; checked as the setters check theirs before anything is overwritten
-        launch_roll_level(v, c->plan, k, !c->level_from_primal, e0_d, c->main);
+    double *const budget_d = const_cast<double *>(c->plan.genRampBudget ? gen_rb_min(v) : gen_budget_min(v));     // e_min | e_max (contexts with budgets)
+    std::vector<double> e0s(S), e0c(S), gh(gens ? 3 * G : 0);
+    GenWindow w;
+    if (S > 0 || ramp || left) {
+        // the new initial levels, anchors and budgets first, into scratch (the rows are still the old window's); checked as the setters
+        // check theirs before anything is overwritten
+        launch_roll_level(v, c->plan, k, !c->level_from_primal, scr.e0, c->main);
+        if (ramp || left) launch_roll_gen_window(v, k, left ? budget_d : nullptr, left ? budget_d + G : nullptr, scr.gen, c->main);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(e0s.data(), e0_d, sizeof(double) * S, hipMemcpyDeviceToHost, c->main));
+        if (S > 0) HIPCHK(c, hipMemcpyAsync(e0s.data(), scr.e0, sizeof(double) * S, hipMemcpyDeviceToHost, c->main));
+        if (ramp) HIPCHK(c, hipMemcpyAsync(gh.data(), scr.gen, sizeof(double) * G, hipMemcpyDeviceToHost, c->main));
+        if (left) HIPCHK(c, hipMemcpyAsync(gh.data() + G, scr.gen + G, sizeof(double) * 2 * G, hipMemcpyDeviceToHost, c->main));
         HIPCHK(c, hipStreamSynchronize(c->main));
+    }
+    if (S > 0) {
         for (int i = 0; i < S; ++i) e0c[c->sto_perm[i]] = e0s[i];          // (check_initial_levels reads the caller's order)
         if (int rc = check_initial_levels(c, e0c.data())) return rc;
     }
-    HIPCHK(c, hipMemcpyAsync(tail_d, demand_tail, sizeof(double) * N * k, hipMemcpyHostToDevice, c->main));
+    if (gens) {
+        w.ramp = c->gen_ramp_h; w.budget = c->gen_budget_h; w.avail = c->gen_avail_h; w.prof = c->gen_prof_h;
+        for (size_t i = 0; i < G; ++i) {
+            const int a = c->gen_perm[i];
+            if (ramp) w.ramp[3 * G + i] = gh[i];
+            if (left) { w.budget[G + i] = gh[G + i]; w.budget[2 * G + i] = gh[2 * G + i]; }
+            else if (budget) { w.budget[G + i] = cp->e_min ? cp->e_min[a] + 0.0 : 0.0; w.budget[2 * G + i] = cp->e_max ? cp->e_max[a] + 0.0 : INFINITY; }
+            if (table) w.prof[i] = cp->profile_of ? cp->profile_of[a] : -1;
+        }
+        if (table && (ramp || budget)) w.avail.assign(cp->profiles, cp->profiles + (size_t)cp->n_profiles * T);      // (kept for these contexts alone, as the setter keeps it)
+        if (int rc = check_gen_window(c, entry, w)) return rc;
+        // the commit, on the context's stream in the arrays the graphs read: the table as its setter queues it (a table larger than
+        // any before is a new allocation, and the graphs are captured again), the anchor and the budgets from the scratch
+        if (table)
+            if (int rc = queue_availability(c, cp->n_profiles, cp->profiles, w.prof)) return rc;
+        if (ramp) HIPCHK(c, hipMemcpyAsync(const_cast<double *>(gen_ramp_prev(v)), scr.gen, sizeof(double) * G, hipMemcpyDeviceToDevice, c->main));
+        if (left) HIPCHK(c, hipMemcpyAsync(budget_d, scr.gen + G, sizeof(double) * 2 * G, hipMemcpyDeviceToDevice, c->main));
+        else if (budget) HIPCHK(c, hipMemcpyAsync(budget_d, w.budget.data() + G, sizeof(double) * 2 * G, hipMemcpyHostToDevice, c->main));
+    }
+    HIPCHK(c, hipMemcpyAsync(scr.tail, demand_tail, sizeof(double) * N * k, hipMemcpyHostToDevice, c->main));
     RollVecs rv{};
-    rv.scratch = scr;
+    rv.scratch = scr.vecs;
     size_t off = 0;
     auto add = [&](double *p, int stride, const double *tail) {
         if (stride > 0) { rv.a[rv.n++] = RollVec{p, tail, off, stride}; off += (size_t)stride * T; }
     };
-    add(const_cast<double *>(v.demand), N, tail_d);
+    add(const_cast<double *>(v.demand), N, scr.tail);
     add(v.lam, 1, nullptr); add(v.lam_used, 1, nullptr);
     for (double *p : {v.mu, v.mu_used, v.rho, v.rho_used, v.avgU, v.avgU_used, v.avgK, v.avgK_used}) add(p, L, nullptr);
     if (v.fmax_ld) add(const_cast<double *>(v.fmax), L, nullptr);          // DOPF_F_LINE_RATING: a derating persists (the old last column)
     launch_roll_vecs(rv, T, k, c->main);
     if (S > 0) {
-        HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_e0(v)), e0_d, sizeof(double) * S, hipMemcpyDeviceToDevice, c->main));
+        HIPCHK(c, hipMemcpyAsync(const_cast<double *>(sto_e0(v)), scr.e0, sizeof(double) * S, hipMemcpyDeviceToDevice, c->main));
         HIPCHK(c, hipMemsetAsync(v.nu_valid, 0, sizeof(int) * S, c->main));   // stored prices no longer match the state
     }
     if (v.G > 0) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v.gen_state), 2, (size_t)v.G, c->main));   // nor do the row summaries of P
@@ -1900,7 +1988,55 @@ int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
     c->quiet = false;                      // (flags are formed anew from the moved state)
     c->level_from_primal = true;           // (a central solve's levels belonged to the old window)
     if (S > 0) std::copy(e0s.begin(), e0s.end(), c->sto_slot_h(kStoE0));
-    return read_status(c);
+    if (gens) w.swap(c);                   // (the commit is queued: a later setter's checks see the new window)
+    return read_status(c);                 // (synchronises: the caller's arrays and w may go)
+}
+
+int dopf_roll_horizon(dopf_ctx *c, int32_t k, const double *demand_tail)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (c->comm) return roll_checks(c, "dopf_roll_horizon", "demand_tail", demand_tail, 0, c->v.N, 0);
+    if (c->q.flags & DOPF_F_GEN_RAMP)
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: not on a context with DOPF_F_GEN_RAMP (the anchor p_prev of the next window is "
+                                           "the host's to set: build that window's context)");
+    if (c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET)
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_roll_horizon: not on a context with DOPF_F2_GEN_ENERGY_BUDGET (what is left of a budget after "
+                                           "k steps is the host's to work out: build that window's context)");
+    return roll_window(c, "dopf_roll_horizon", k, demand_tail, nullptr);
+}
+
+int dopf_roll_horizon_coupled(dopf_ctx *c, int32_t k, const double *demand_tail, int32_t n_profiles, const double *profiles,
+                              const int32_t *profile_of, int32_t set_budget, const double *e_min, const double *e_max)
+{
+    if (!c) return DOPF_E_INVALID;
+    const char *entry = "dopf_roll_horizon_coupled";
+    if (c->comm) return roll_checks(c, entry, "demand_tail", demand_tail, 0, c->v.N, 0);
+    if (n_profiles < -1) return fail(c, DOPF_E_INVALID, "%s: n_profiles = %d < -1 (-1: the stored table stays)", entry, n_profiles);
+    if (n_profiles >= 0 && !(c->q.flags & DOPF_F_GEN_AVAILABILITY))
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: an availability table (n_profiles = %d) needs DOPF_F_GEN_AVAILABILITY at dopf_create", entry, n_profiles);
+    if (set_budget && !(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: set_budget = %d needs DOPF_F2_GEN_ENERGY_BUDGET at dopf_create_ex", entry, set_budget);
+    if (n_profiles >= 0)
+        if (int rc = check_availability_table(c, n_profiles, profiles, profile_of)) return rc;
+    const RollCoupling cp{n_profiles, profiles, profile_of, set_budget, e_min, e_max};
+    return roll_window(c, entry, k, demand_tail, &cp);
+}
+
+// the stored ramps, anchor and budgets from the host mirrors (no device call); without the matching flag: the defaults
+int dopf_get_generator_coupling(dopf_ctx *c, double *ramp_up, double *ramp_down, double *p_prev, double *e_min, double *e_max)
+{
+    if (!c) return DOPF_E_INVALID;
+    const size_t G = (size_t)c->v.G;
+    const bool ramp = c->plan.genRamp, budget = c->plan.genBudget;
+    for (size_t i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        if (ramp_up) ramp_up[a] = ramp ? c->gen_ramp_h[G + i] : INFINITY;
+        if (ramp_down) ramp_down[a] = ramp ? c->gen_ramp_h[2 * G + i] : INFINITY;
+        if (p_prev) p_prev[a] = ramp ? c->gen_ramp_h[3 * G + i] : std::nan("");
+        if (e_min) e_min[a] = budget ? c->gen_budget_h[G + i] : 0.0;
+        if (e_max) e_max[a] = budget ? c->gen_budget_h[2 * G + i] : INFINITY;
+    }
+    return DOPF_OK;
 }
 
 // ---- dopf_trace_*: the iteration history on the device ---------------------------------------------------------------

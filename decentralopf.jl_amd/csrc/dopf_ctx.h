@@ -32,7 +32,7 @@ struct dopf_ctx {
     std::vector<void *> allocs;
     void *own_cons = nullptr;
     double *getter_scratch = nullptr;      // 3 * N * T doubles, allocated at the first getter that needs them (freed with the context)
-    double *roll_scratch = nullptr;        // dopf_set_demand / dopf_roll_horizon: the moved vectors, the demand tail, the new initial levels
+    double *roll_scratch = nullptr;        // dopf_roll_horizon(_coupled): the moved vectors, the demand tail, the new initial levels, the new anchors and budgets
     std::vector<int> gen_perm, sto_perm;   // sorted position -> caller's index
     std::vector<double> sto_h;             // the storage block as it is on the device (dopf_internal.h: StoSlot, sto_slots(plan) slots of S
                                            // values, sorted order): the setters' bounds, and what each checks reachability against

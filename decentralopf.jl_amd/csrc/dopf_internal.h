@@ -411,6 +411,9 @@ void launch_derive_level(const DevView &v, const Plan &p, hipStream_t s);   // E
 struct RollVec { double *p; const double *tail; size_t off; int stride; };
 struct RollVecs { RollVec a[12]; double *scratch; int n; };
 void launch_roll_level(const DevView &v, const Plan &p, int k, bool from_E, double *out /* S, device */, hipStream_t s);   // clamped level after timestep k - 1
+// dopf_roll_horizon_coupled, before the rows move: out = P[:, k-1] | e_min' | e_max' | spent, G doubles each, sorted
+// order; e_min / e_max: the stored bounds on the device, or both null (the anchor alone is written)
+void launch_roll_gen_window(const DevView &v, int k, const double *e_min, const double *e_max, double *out /* 4G, device */, hipStream_t s);
 void launch_roll_vecs(const RollVecs &rv, int T, int k, hipStream_t s);
 // P, D, C moved by k in place (k = 0: left alone), the node sums formed from the rows item by item, status (iteration <= 0: kept)
 // and the derived consensus state as dopf_set_state leaves them

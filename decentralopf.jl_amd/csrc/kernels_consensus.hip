@@ -1970,6 +1970,27 @@ __global__ __launch_bounds__(256) void k_roll_level_eff(DevView v, int k, int fr
     out[s] = e != e ? e : fmin(fmax(e, 0.0), v.sto_emax[s]) + 0.0;
 }
 
+// dopf_roll_horizon_coupled: what couples a generator's timesteps, for the window that starts k steps later. One lane
+// per generator (sorted order), before k_roll_rows moves the rows: out[g] = P[g, k-1], the next anchor, bit for bit; with budgets
+// (e_min / e_max: the stored bounds, or null) spent = ((P[g,0] + P[g,1]) + ..) + P[g,k-1] — left to right from P[g,0], the order is
+// part of the contract (np.cumsum's) — into out[3G + g], and what is left of both bounds, floored at 0, into out[G + g] and
+// out[2G + g]. +inf stays +inf; a NaN (a diverged state) stays NaN, as in k_roll_level, so that the setters' checks refuse the roll
+__global__ __launch_bounds__(256) void k_roll_gen_window(DevView v, int k, const double *e_min /* G, or null */, const double *e_max, double *out /* 4G */)
+{
+    const int T = v.T, G = v.G;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    const double *row = v.P + (size_t)g * T;
+    out[g] = row[k - 1];
+    if (!e_min) return;
+    double spent = row[0];
+    for (int t = 1; t < k; ++t) spent += row[t];
+    const double lo = e_min[g] - spent, hi = e_max[g] - spent;
+    out[(size_t)G + g] = lo != lo ? lo : fmax(lo, 0.0) + 0.0;
+    out[2 * (size_t)G + g] = hi != hi ? hi : fmax(hi, 0.0) + 0.0;
+    out[3 * (size_t)G + g] = spent;
+}
+
 // One block per work item (the x-update's own items: rows [a0, a1) of one node), STO: a storage item (rows of D and C) instead of
 // a generator item (rows of P). Thread = (row lane r, column tt): W = min(T, 256) columns x R = 256 / W rows at a time.
 // k > 0: every row moves left by k IN PLACE — new[t] = old[t + k] for t < T - k, behind it old[T - 1] (P: persistence) or 0 (D, C).
@@ -2083,6 +2104,11 @@ void launch_roll_level(const DevView &v, const Plan &p, int k, bool from_E, doub
 {
     if (v.S > 0 && p.stoEff) hipLaunchKernelGGL(k_roll_level_eff, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, k, from_E ? 1 : 0, out);
     else if (v.S > 0) hipLaunchKernelGGL(k_roll_level, dim3((unsigned)((v.S + 255) / 256)), dim3(256), 0, s, v, p.stoE0 ? sto_e0(v) : nullptr, k, from_E ? 1 : 0, out);
+}
+
+void launch_roll_gen_window(const DevView &v, int k, const double *e_min, const double *e_max, double *out, hipStream_t s)
+{
+    if (v.G > 0) hipLaunchKernelGGL(k_roll_gen_window, dim3((unsigned)((v.G + 255) / 256)), dim3(256), 0, s, v, k, e_min, e_max, out);
 }
 
 void launch_roll_vecs(const RollVecs &rv, int T, int k, hipStream_t s)

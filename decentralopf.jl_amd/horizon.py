@@ -6,7 +6,7 @@ dopf_set_state). Not in the reference, which builds a new ADMM(...) per window (
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -65,4 +65,28 @@ def shift_window(k: int, demand_tail, *, demand, P, D, C, E, lam, mu, rho, avg_U
     if used is not None:
         out["used"] = {name: _persist(np.asarray(a, dtype=np.float64).reshape(-1) if name == "lam" else rows(a), k)
                        for name, a in used.items()}
+    return out
+
+
+def shift_coupled(k: int, P, *, budget: Optional[Tuple] = None) -> Dict[str, object]:
+    """What couples a generator's timesteps, for the window that starts k steps later: the rule of dopf_roll_horizon_coupled
+    (include/dopf.h) in NumPy, the specification the device is tested against. P (G, T): the rows of the old window.
+
+    gen_prev = P[:, k - 1], the output of the step before the new window (the ramps' anchor). With budget = (e_min, e_max) (G values
+    each; either may be None: 0 / inf) also gen_budget = (lo', hi'): what the k steps that leave the window delivered,
+    spent[g] = ((P[g, 0] + P[g, 1]) + ...) + P[g, k - 1] — summed left to right from P[g, 0]; the order is part of the rule — comes off
+    both bounds, floored at 0 (inf stays inf)."""
+    P = np.asarray(P, dtype=np.float64)
+    P = P.reshape(P.shape[0], -1) if P.ndim == 2 else P.reshape(1, -1)
+    G, T = P.shape
+    k = int(k)
+    if not 1 <= k <= T - 1:
+        raise ValueError(f"k = {k} outside [1, T - 1 = {T - 1}]")
+    out: Dict[str, object] = dict(gen_prev=P[:, k - 1].copy())
+    if budget is not None:
+        lo, hi = budget
+        lo = np.zeros(G) if lo is None else np.asarray(lo, dtype=np.float64).reshape(G)
+        hi = np.full(G, np.inf) if hi is None else np.asarray(hi, dtype=np.float64).reshape(G)
+        spent = np.cumsum(P[:, :k], axis=1)[:, -1]
+        out["gen_budget"] = (np.maximum(0.0, lo - spent) + 0.0, np.maximum(0.0, hi - spent) + 0.0)
     return out

@@ -511,6 +511,57 @@ function roll_horizon!(admm::ADMM, k::Int, demand_tail::Matrix{Float64})
     return dopf_new_window!(admm, vcat(admm.total_demand[k+1:end], vec(sum(demand_tail, dims=1))))
 end
 
+"""
+    roll_horizon_coupled!(admm, k, demand_tail; availability=nothing, budget=nothing)
+
+`roll_horizon!` for an ADMM with ramp limits or energy budgets, in place on the device: the ramps' anchor becomes the output of step
+`k` (`P[g, k]`, 1-based), and what the `k` leaving steps delivered comes off both budgets, floored at 0. `availability =
+(profiles, profile_of)` as `set_availability!` takes them (`(nothing, nothing)`: every generator back to `max_generation`) is the new
+window's table, checked together with the new anchor and budgets; `nothing`: the stored table stays. `budget = (e_min, e_max)` as
+`set_energy_budget!` takes them: the new window's own budgets instead of what is left. A refusal leaves the context as it was.
+The reference builds a new `ADMM(...)` per window (src/structures/admm.jl:23-62). One GPU only (`n_gpus == 1`).
+"""
+function roll_horizon_coupled!(admm::ADMM, k::Int, demand_tail::Matrix{Float64}; availability=nothing, budget=nothing)
+    N, T, G = length(admm.N), length(admm.T), length(admm.generators)
+    size(demand_tail) == (N, k) || error("roll_horizon_coupled!: expected a $N x $k demand tail, got $(size(demand_tail))")
+    admm.multi == C_NULL || error("roll_horizon_coupled!: one GPU only (no dopf_multi_* wrapper)")
+    profiles, profile_of = availability === nothing ? (nothing, nothing) : availability
+    (profiles === nothing) == (profile_of === nothing) || error("roll_horizon_coupled!: give both profiles and profile_of, or neither")
+    profiles === nothing || size(profiles, 1) == T || error("roll_horizon_coupled!: expected $T rows of profiles, got $(size(profiles, 1))")
+    profile_of === nothing || length(profile_of) == G || error("roll_horizon_coupled!: expected $G profile indices")
+    K = availability === nothing ? -1 : (profiles === nothing ? 0 : size(profiles, 2))
+    e_min, e_max = budget === nothing ? (nothing, nothing) : budget
+    for a in (e_min, e_max)
+        a === nothing || length(a) == G || error("roll_horizon_coupled!: expected $G values, got $(length(a))")
+    end
+    pp = profiles === nothing ? Ptr{Cdouble}(C_NULL) : pointer(profiles)        # T x K column-major = [t + T*k]
+    po = profile_of === nothing ? Ptr{Cint}(C_NULL) : pointer(profile_of)
+    plo = e_min === nothing ? Ptr{Cdouble}(C_NULL) : pointer(e_min)
+    phi = e_max === nothing ? Ptr{Cdouble}(C_NULL) : pointer(e_max)
+    GC.@preserve profiles profile_of e_min e_max begin
+        dopf_check(ccall((:dopf_roll_horizon_coupled, DOPF_LIB), Cint,
+                         (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                         admm.ctx, k, demand_tail, K, pp, po, budget === nothing ? 0 : 1, plo, phi), admm.ctx)
+    end
+    return dopf_new_window!(admm, vcat(admm.total_demand[k+1:end], vec(sum(demand_tail, dims=1))))
+end
+
+"""
+    generator_coupling(admm)
+
+`(ramp_up, ramp_down, p_prev, e_min, e_max)` as the context holds them, one value per generator in the order of `generators`
+(`p_prev` is `NaN` where no anchor is stored; without the flags: `Inf`, `Inf`, `NaN`, 0, `Inf`). After `roll_horizon_coupled!` they
+are what the device computed. One GPU only (`n_gpus == 1`).
+"""
+function generator_coupling(admm::ADMM)
+    admm.multi == C_NULL || error("generator_coupling: one GPU only (no dopf_multi_* wrapper)")
+    G = length(admm.generators)
+    up = zeros(G); down = zeros(G); prev = zeros(G); lo = zeros(G); hi = zeros(G)
+    dopf_check(ccall((:dopf_get_generator_coupling, DOPF_LIB), Cint,
+                     (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}), admm.ctx, up, down, prev, lo, hi), admm.ctx)
+    return (ramp_up=up, ramp_down=down, p_prev=prev, e_min=lo, e_max=hi)
+end
+
 """The fields of the reference's Result (src/structures/results.jl:37-48) for the last solved iteration."""
 function dopf_result(admm::ADMM)
     N, L, T = length(admm.N), length(admm.L), length(admm.T)

@@ -212,7 +212,8 @@ typedef struct dopf_params {
                                   * DOPF_F_LONG_HORIZON and the storage flags work as without it. With every ramp +inf and no p_prev the
                                   * results are those of the flagless context on that chain, bit for bit. dopf_create refuses the flag with
                                   * L > 0 (DOPF_E_UNSUPPORTED) unless DOPF_F_GEN_RAMP_NETWORK is given too, dopf_roll_horizon refuses a
-                                  * context with it (the anchor's roll is the host's: build the next window's context).
+                                  * context with it (the anchor's roll is the host's: build the next window's context, or use
+                                  * dopf_roll_horizon_coupled, which moves the anchor on the device).
                                   * dopf_central_solve, _ex and _lossy ignore the flag. dopf_central_solve_coupled ignores it too and
                                   * takes the ramps and the anchor as arguments. Energy budgets on the same generators (copper plates):
                                   * DOPF_F2_GEN_RAMP_BUDGET, in the second flag word. */
@@ -254,7 +255,8 @@ typedef struct dopf_params {
                                   * budget has no price); dopf_get_agent_slacks, dopf_get_agent_penalty and DOPF_F_KEEP_DELTAS see the
                                   * projected step. Together with DOPF_F_GEN_RAMP the flag is refused (DOPF_E_UNSUPPORTED: two constraints
                                   * that couple a row's timesteps need the ramp programme inside the multiplier search); dopf_roll_horizon
-                                  * refuses a context with it (what is left of a budget after k steps is the host's arithmetic);
+                                  * refuses a context with it (what is left of a budget after k steps is the host's arithmetic, or
+                                  * dopf_roll_horizon_coupled's on the device);
                                   * dopf_central_solve, _ex and _lossy take no budgets and ignore the bit. dopf_central_solve_coupled
                                   * takes the budgets as arguments, together with ramps if the caller has both. On a copper plate
                                   * DOPF_F2_GEN_RAMP_BUDGET lifts that refusal: the pair then runs in one context. */
@@ -280,7 +282,8 @@ typedef struct dopf_params {
                                   * naming g and the failing sum; the feasible paths form a lattice, so the check is exact). dopf_create
                                   * refuses (DOPF_E_UNSUPPORTED) the bit without both of the other two flags, and with L > 0 (a network
                                   * row's knots are 64 times too many for this design); with G == 0 it is accepted and ignored. The two
-                                  * older flags without the bit behave as before. dopf_roll_horizon goes on refusing the context;
+                                  * older flags without the bit behave as before. dopf_roll_horizon goes on refusing the context
+                                  * (dopf_roll_horizon_coupled rolls it, with the joint check on the next window);
                                   * dopf_central_solve* ignore the bit. */
 /* Everything else that steers kernel selection is decided from the problem's shape ("which chain runs"). The
  * library reads two environment variables, neither of which changes results: DOPF_GUARD (debug allocator) and DOPF_XCHG_TIMEOUT_MS
@@ -523,8 +526,44 @@ int dopf_set_demand(dopf_ctx *ctx, const double *demand /* N x T, [n + N*t] */);
  * context is then in the state of a fresh context of the shifted problem after the same setters and dopf_set_state(shifted arrays,
  * iteration = 2). The new initial levels are computed and checked first: a refusal leaves the context as it was.
  * DOPF_E_INVALID for k < 1, k >= T, a NULL demand_tail, a NaN / Inf in it, or a stored terminal band that is unreachable from the
- * new initial levels; DOPF_E_UNSUPPORTED with storages in a context without DOPF_F_STO_INITIAL_LEVEL. */
+ * new initial levels; DOPF_E_UNSUPPORTED with storages in a context without DOPF_F_STO_INITIAL_LEVEL, and on a context with
+ * DOPF_F_GEN_RAMP or DOPF_F2_GEN_ENERGY_BUDGET: those roll with dopf_roll_horizon_coupled below. */
 int dopf_roll_horizon(dopf_ctx *ctx, int32_t k, const double *demand_tail /* N x k, [n + N*j] */);
+/* dopf_roll_horizon_coupled: dopf_roll_horizon's rule, unchanged, plus a rule for the state that couples a generator's timesteps
+ * (DESIGN.md 5y), so that a context with ramp limits or energy budgets keeps its arrays, its scratch and its captured graphs over a
+ * receding-horizon run. With P the rows just before the call, every value in the caller's generator order:
+ *   anchor p_prev[g] (DOPF_F_GEN_RAMP)            = P[g, k-1], bit for bit, also where none was stored before
+ *   ramp_up, ramp_down, c2, the terminal band     unchanged
+ *   budgets (DOPF_F2_GEN_ENERGY_BUDGET), set_budget == 0: spent[g] = ((P[g,0] + P[g,1]) + ..) + P[g,k-1], summed left to right from
+ *                                                 P[g,0]; e_min = fmax(0, e_min - spent), e_max = fmax(0, e_max - spent); +inf stays
+ *   budgets, set_budget != 0                      e_min / e_max as dopf_set_generator_energy_budget takes them (either may be NULL:
+ *                                                 0 / +inf): the new window's own budgets
+ *   availability, n_profiles == -1                the stored table and indices stay, as in dopf_roll_horizon
+ *   availability, n_profiles >= 0                 the new window's table and indices, as dopf_set_generator_availability takes them
+ *                                                 (0 with both NULL: every generator back to -1); needs DOPF_F_GEN_AVAILABILITY
+ * The table and the budgets are arguments, not setter calls behind the roll, because the new anchor and what is left of the budgets
+ * must be feasible under the NEW window's caps: the stored table does not move with the window, so the old table under the new
+ * anchor (or the new table under the old anchor) may be refused where the new window is feasible; and with DOPF_F2_GEN_RAMP_BUDGET
+ * what is left of e_max can be less than the slowest way down from the new anchor delivers, so that the caller has to state the
+ * new window's budget. All checks run before anything is overwritten, and a refusal leaves every getter as it was: first
+ * dopf_roll_horizon's (k, the tail, a communicator or peer exchange, storages without DOPF_F_STO_INITIAL_LEVEL, the band's
+ * reachability), then those of dopf_set_generator_ramp, dopf_set_generator_energy_budget and dopf_set_generator_availability on the
+ * new anchor, the new budgets and the table that will be in force, the joint check of DOPF_F2_GEN_RAMP_BUDGET included (DOPF_E_INVALID;
+ * the messages name this entry and the caller's g). DOPF_E_INVALID for n_profiles < -1; DOPF_E_UNSUPPORTED for a table without
+ * DOPF_F_GEN_AVAILABILITY and for set_budget != 0 without DOPF_F2_GEN_ENERGY_BUDGET. On a context with neither flag, with
+ * n_profiles == -1 and set_budget == 0, the entry is dopf_roll_horizon bit for bit; with G == 0 the generator part does nothing.
+ * Status, the warm-start summaries and timing as after dopf_roll_horizon; the graphs stay valid (a table larger than any before
+ * follows dopf_set_generator_availability's rule: a new allocation, and the graphs are captured again). While a trace is active the
+ * entry works as the setters do. There is no dopf_multi_* wrapper. */
+int dopf_roll_horizon_coupled(dopf_ctx *ctx, int32_t k, const double *demand_tail /* N x k, [n + N*j] */,
+                              int32_t n_profiles /* -1: the table stays */, const double *profiles /* n_profiles x T, [t + T*p] */,
+                              const int32_t *profile_of /* G */, int32_t set_budget, const double *e_min /* G; NULL = 0 */,
+                              const double *e_max /* G; NULL = +inf */);
+/* The stored ramp limits, anchor (NaN: none) and energy budgets, G values each in the caller's order; any pointer may be NULL. They
+ * come from the context's host copies: no device call, callable at any time. Without DOPF_F_GEN_RAMP the ramps are +inf and the
+ * anchor NaN, without DOPF_F2_GEN_ENERGY_BUDGET the budgets are 0 and +inf. After dopf_roll_horizon_coupled they hold what the
+ * device computed, which lets a host mirror follow the device's arithmetic. */
+int dopf_get_generator_coupling(dopf_ctx *ctx, double *ramp_up, double *ramp_down, double *p_prev, double *e_min, double *e_max);
 
 /* ---- the iteration history on the device ---------------------------------------------------------------
  * The reference's data product is the history of a run: admm.lambdas, admm.mues, admm.rhos, admm.results and admm.convergence hold
