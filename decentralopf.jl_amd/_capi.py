@@ -161,6 +161,7 @@ class CApi:
         self._opt("roll_horizon_coupled", C.c_int, [ctxp, C.c_int32, c_double_p, C.c_int32, c_double_p, c_int32_p, C.c_int32,
                                                     c_double_p, c_double_p])
         self._opt("get_generator_coupling", C.c_int, [ctxp] + [c_double_p] * 5)
+        self._opt("get_generator_min_output", C.c_int, [ctxp, c_double_p])
         if prefix == "dopf_":
             self._sig("bind_consensus", C.c_int, [ctxp, C.c_void_p])
             self._sig("solver_failures", C.c_int64, [ctxp])
@@ -432,13 +433,31 @@ EXTENSIONS_WORD2 = (
               norm=_budget_norm,
               is_default=lambda d, keep, lo, hi: not ((lo is not None and np.any(lo != 0.0)) or (hi is not None and np.any(hi != np.inf)))),
 )
-_ALL_EXTENSIONS = EXTENSIONS + EXTENSIONS_MORE + EXTENSIONS_WORD2
+
+def _floor_norm(d, p_min):
+    """zeros are what None says (the entry's NULL: the context runs the kernels without floors); a NaN passes on to the entry's refusal"""
+    if p_min is None:
+        return (None,)
+    a = _f64(p_min, d.G)
+    return (a if np.any(a != 0.0) else None,)
+
+
+# Minimum output has no flag of its own (both words are spoken for: DESIGN.md 5z): it runs on the ramp kernels, so its row's flag is the
+# ramps' — a floor alone creates a ramp context with infinite ramps. Applied behind the ramps, whose limits and anchor its check reads.
+EXTENSIONS_FLOOR = (
+    Extension(keys=("gen_min_output",), flag=F_GEN_RAMP, entry="set_generator_min_output", argtypes=(c_double_p,),
+              setter="set_min_output", optional=True,
+              what="generator minimum output", why="a min_generation above 0; the reference's generators may go down to 0",
+              norm=_floor_norm, is_default=lambda d, keep, p: p is None or not np.any(p != 0.0)),
+)
+_ALL_EXTENSIONS = EXTENSIONS + EXTENSIONS_MORE + EXTENSIONS_WORD2 + EXTENSIONS_FLOOR
 _BY_SETTER = {x.setter: x for x in _ALL_EXTENSIONS}
 
 
 def _extensions(api: CApi, params: Optional[DopfParams], d, keep: dict, kw: dict):
     """(params, todo) for a context built with the extensions' constructor keywords in kw: the params with the flags of those given
-    added (a copy), and todo, the (extension, arrays) to apply behind create, in the order of EXTENSIONS + EXTENSIONS_MORE + EXTENSIONS_WORD2.
+    added (a copy), and todo, the (extension, arrays) to apply behind create, in the order of EXTENSIONS + EXTENSIONS_MORE + EXTENSIONS_WORD2 +
+    EXTENSIONS_FLOOR.
     Nothing to set: a keyword left None, or its default value on an API without the entry (a non-default value there: DopfError). The
     flags of the second word are not in params: _flags2(todo) forms them."""
     todo = []
@@ -529,19 +548,23 @@ class Engine(_ExtensionSetters):
     gen_budget = (e_min, e_max) (optional, G values each; either may be None: 0 / inf): the generators' energy budgets over the window —
     sets F2_GEN_ENERGY_BUDGET in the second flag word (self.flags2; the context is then created by dopf_create_ex) and calls
     dopf_set_generator_energy_budget (after the availability too). flags2 (optional): further bits of that word, as Engine.roll passes
-    them to the context it rebuilds; on an API without create_ex a non-zero word is a DopfError."""
+    them to the context it rebuilds; on an API without create_ex a non-zero word is a DopfError. gen_min_output (optional, G values in
+    [0, gen_pmax]): the generators' must-run floors — sets F_GEN_RAMP (on a network F_GEN_RAMP_NETWORK too: the floors run on the ramp
+    kernels) and calls dopf_set_generator_min_output behind the ramps; all zeros is what None says."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
                  mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
-                 sto_eta=None, line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0):
+                 sto_eta=None, line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0,
+                 gen_min_output=None):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                                               sto_mc, sto_pmax, sto_emax, sto_node)
         params, todo = _extensions(api, params, self, keep, dict(
             sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
-            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget))
+            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget,
+            gen_min_output=gen_min_output))
         self.params = params if params is not None else default_params()
         self.flags2 = int(flags2) | _flags2(todo, self.L)
         _needs_create_ex(api, self.flags2)
@@ -738,6 +761,21 @@ class Engine(_ExtensionSetters):
         each; e_min None = all 0, e_max None = all inf); needs F2_GEN_ENERGY_BUDGET. P, D, C, the duals and the iteration counter
         stay; converged becomes False. Takes effect at the next x-update. A backend without the entry: DopfError (unsupported)."""
         self._mirror.update(self._set("set_energy_budget", e_min, e_max))
+
+    def set_min_output(self, p_min=None):
+        """dopf_set_generator_min_output: each generator's must-run floor (G values in [0, gen_pmax]; None or all zeros = none):
+        min(p_min[g], cap[g,t]) <= P[g,t] <= cap[g,t]; needs F_GEN_RAMP (the floors run on the ramp kernels; no budgets). P, D, C, the
+        duals and the iteration counter stay; converged becomes False. Takes effect at the next x-update. A backend without the
+        entry: DopfError (unsupported)."""
+        self._mirror.update(self._set("set_min_output", p_min))
+
+    def min_output(self) -> np.ndarray:
+        """dopf_get_generator_min_output: the floors as the context holds them, G values. A backend without the entry: DopfError."""
+        if not hasattr(self.api, "get_generator_min_output"):
+            raise DopfError(f"{self.api.prefix}*: this API has no get_generator_min_output")
+        out = np.empty(self.G)
+        self._chk(self.api.get_generator_min_output(self._ctx, _dp(out)))
+        return out
 
     # -- a receding horizon --------------------------------------------------------------------
     def demand(self) -> np.ndarray:
@@ -1007,14 +1045,15 @@ class MultiEngine(_ExtensionSetters):
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
                  sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None, gen_c2=None,
-                 gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0):
+                 gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0, gen_min_output=None):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                                               sto_mc, sto_pmax, sto_emax, sto_node)
         params, todo = _extensions(api, params, self, keep, dict(
             sto_e0=sto_e0, sto_end_lo=sto_end_lo, sto_end_hi=sto_end_hi, gen_avail=gen_avail, gen_avail_of=gen_avail_of,
-            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget))
+            sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget,
+            gen_min_output=gen_min_output))
         self.params = params if params is not None else default_params()
         self.flags2 = int(flags2) | _flags2(todo, self.L)
         _needs_create_ex(api, self.flags2)
@@ -1048,6 +1087,11 @@ class MultiEngine(_ExtensionSetters):
         """dopf_multi_set_generator_energy_budget: all G generators' energy budgets in the caller's order (e_min None = all 0, e_max
         None = all inf); each shard gets its slice."""
         self._set("set_energy_budget", e_min, e_max)
+
+    def set_min_output(self, p_min=None):
+        """dopf_multi_set_generator_min_output: all G generators' must-run floors in the caller's order (None or all zeros = none);
+        every shard is checked before any stores."""
+        self._set("set_min_output", p_min)
 
     def set_line_rating(self, rating=None):
         """dopf_multi_set_line_rating: the (L, T) table for every shard (None = f_max in every timestep)."""
@@ -1113,7 +1157,7 @@ class MultiEngine(_ExtensionSetters):
 def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                   sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                   sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
-                  line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None) -> dict:
+                  line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, gen_min_output=None) -> dict:
     """dopf_central_solve: the central reference (src/opf_central_reference.jl) as one LP solved on the GPU by a first-order
     primal-dual method. Arguments as Engine (PackedProblem.engine_kwargs()). Returns objective, gap, iterations and the
     reference script's outputs in Julia shapes: P (G,T), D/C/E (S,T), system_price (T), nodal_price (N,T),
@@ -1127,10 +1171,14 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     gen_c2: the device LP takes no quadratic costs either; a non-zero coefficient raises DopfError.
     gen_ramp, gen_prev: nor ramp limits; a finite ramp or an anchor raises DopfError.
     gen_budget: nor energy budgets; an e_min above 0 or a finite e_max raises DopfError.
+    gen_min_output: nor must-run floors; a value above 0 raises DopfError.
     T: any horizon. Beyond 512 timesteps the storages run on the long sweep (kc_sto_long); the entry sets DOPF_F_LONG_HORIZON on its own
     context, so params needs no flag, and with F_LONG_HORIZON in params the result is the same bits. F_DEBUG_LONG_STO in params runs
     that sweep at T <= 512 too (tests)."""
     N, L, T = int(N), int(L), int(T)
+    if gen_min_output is not None and np.any(np.asarray(gen_min_output, dtype=np.float64) != 0.0):
+        raise DopfError("dopf_central_solve*: the device LP takes no generator minimum output (its generators' lower bound is 0); use "
+                        "central.solve_central_packed(..., gen_min_output=) for a case with a floor")
     if gen_budget is not None and ((gen_budget[0] is not None and np.any(np.asarray(gen_budget[0], dtype=np.float64) != 0.0)) or
                                    (gen_budget[1] is not None and np.any(np.asarray(gen_budget[1], dtype=np.float64) != np.inf))):
         raise DopfError("dopf_central_solve*: the device LP takes no generator energy budgets (it bounds no generator's sum over the "
@@ -1179,7 +1227,7 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
 def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                           sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                           sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
-                          line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None) -> dict:
+                          line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, gen_min_output=None) -> dict:
     """dopf_central_solve_coupled: central_solve's LP with the constraints that couple a generator's timesteps and with per-timestep
     line limits. Arguments as Engine (PackedProblem.engine_kwargs()); beyond central_solve's:
     line_rating (L, T): the limits of the flow rows, as Engine takes them (None: f_max in every timestep).
@@ -1187,7 +1235,7 @@ def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, ge
     gen_budget = (e_min, e_max) (G each; either may be None: 0, inf).
     The call is always dopf_central_solve_coupled (with none of the four given it returns dopf_central_solve_lossy's bits); it checks
     the inputs as the three setters do (DopfError with the entry's name). gen_c2: the device solve is an LP; a non-zero coefficient
-    raises DopfError. Returns central_solve's dict plus ramp_dual (G, T) and budget_dual (G,): d objective / d right-hand side of the
+    raises DopfError, and so does a gen_min_output above 0 (the device LP's generators go down to 0). Returns central_solve's dict plus ramp_dual (G, T) and budget_dual (G,): d objective / d right-hand side of the
     ramp row between t - 1 and t (t = 0: the anchor's row) and of the budget row — negative where the row's upper end binds, positive
     where its lower end does.
     T: any horizon, with ramps and budgets too. Beyond 512 timesteps the rows run on the long sweeps (kc_gen_rows_long, kc_sto_long);
@@ -1195,6 +1243,9 @@ def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, ge
     N, L, T = int(N), int(L), int(T)
     if gen_c2 is not None and np.any(np.asarray(gen_c2, dtype=np.float64) != 0.0):
         raise DopfError("dopf_central_solve_coupled: the device LP takes no quadratic generator costs (it solves with gen_mc alone)")
+    if gen_min_output is not None and np.any(np.asarray(gen_min_output, dtype=np.float64) != 0.0):
+        raise DopfError("dopf_central_solve_coupled: the device LP takes no generator minimum output (its generators' lower bound is "
+                        "0); use central.solve_central_packed(..., gen_min_output=) for a case with a floor")
     prob, keep, G, S = _problem(N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax, sto_node)
     q = params if params is not None else default_params()
     res = DopfCentralResult()

@@ -206,6 +206,15 @@ class ADMM:
         self.packed.gen_budget = None if e_min is None and e_max is None else (lo, hi)
         self.convergence = Convergence()
 
+    def set_min_output(self, p_min=None) -> None:
+        """Each generator's must-run floor (G values in [0, max_generation] in the order of `generators`; None = all 0):
+        min(p_min, cap[t]) <= P[t], a floor that follows an availability profile down; p_min = max_generation is a must-take unit.
+        Not in the reference (its generators go down to 0). Runs on the ramp kernels: needs flags=F_GEN_RAMP (set for you when a
+        Generator has a min_generation), and does not combine with energy budgets; the state and the iteration counter stay, the
+        run is no longer converged; takes effect at the next iteration."""
+        self.engine.set_min_output(p_min)
+        self._replaced("gen_min_output", p_min, (self.packed.G,))
+
     def _replaced(self, field_: str, value, shape) -> None:
         """the packed problem follows an input that was replaced under a kept state, and the run is no longer converged"""
         setattr(self.packed, field_, None if value is None else np.asarray(value, dtype=np.float64).reshape(shape).copy())

@@ -56,7 +56,8 @@ def _efficiencies(pp: PackedProblem, efficiency):
 
 
 def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None,
-                         availability=None, efficiency=None, line_rating=None, gen_ramp=None, gen_prev=None, gen_budget=None) -> CentralResult:
+                         availability=None, efficiency=None, line_rating=None, gen_ramp=None, gen_prev=None, gen_budget=None,
+                         gen_min_output=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
     tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
     side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference). terminal_level:
@@ -69,7 +70,9 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
     each, inf = no limit: the rows -down[g] <= P[g,t] - P[g,t-1] <= up[g] for t >= 1 (None: the packed case's ramps, else none as in
     the reference); gen_prev: (G,) outputs of the step before the window, the same rows at t = 0 against them (None: no such rows). gen_budget:
     (e_min, e_max), (G,) each: the rows e_min[g] <= sum_t P[g,t] <= e_max[g], one per generator with an e_min above 0 and one per finite
-    e_max (None: the packed case's budgets, else none as in the reference)."""
+    e_max (None: the packed case's budgets, else none as in the reference). gen_min_output: (G,) must-run floors: the lower bound of
+    P[g,t] becomes min(p_min[g], its upper bound) — the floor follows an outage down (None: the packed case's floors, else 0 as in the
+    reference). The parity target of dopf_set_generator_min_output."""
     from scipy import sparse
     from scipy.optimize import linprog
     if pp.has_quadratic_cost():
@@ -96,6 +99,11 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
         f = np.ones((G, T))
         f[of >= 0] = prof[of[of >= 0]]
         ub[:nP] = np.where((of >= 0)[:, None], pm[:, None] * f, pm[:, None]).reshape(-1)      # one multiply, as the kernels
+    if gen_min_output is None and pp.has_min_output():
+        gen_min_output = pp.min_output()
+    if gen_min_output is not None and G > 0:
+        lb = np.array(lb, dtype=np.float64)
+        lb[:nP] = np.minimum(np.repeat(np.asarray(gen_min_output, dtype=np.float64).reshape(G), T), ub[:nP])
     tt = np.arange(T)
     rows, cols, vals, beq = [], [], [], []
     # I[n,t] - sum of the node's units = -demand[n,t]          rows n*T + t
@@ -233,6 +241,9 @@ def central_reference_on_device(nodes: Sequence[Node], generators: Sequence[Gene
     if pp.has_quadratic_cost():
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no quadratic generator "
                          "costs and would solve with the marginal costs alone")
+    if pp.has_min_output():
+        raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no generator minimum "
+                         "output and would let every generator go down to 0; use central_reference for a case with Generator.min_generation")
     if pp.has_ramp():
         raise ValueError("central_reference_on_device: the device LP (dopf_central_solve, _ex, _lossy) takes no generator ramp limits "
                          "and would let every generator move freely; use central_reference_coupled_on_device, or central_reference, "
@@ -285,6 +296,9 @@ def central_reference_coupled_on_device(nodes: Sequence[Node], generators: Seque
     if pp.has_quadratic_cost():
         raise ValueError("central_reference_coupled_on_device: the device LP (dopf_central_solve_coupled) takes no quadratic generator "
                          "costs and would solve with the marginal costs alone")
+    if pp.has_min_output():
+        raise ValueError("central_reference_coupled_on_device: the device LP (dopf_central_solve_coupled) takes no generator minimum "
+                         "output and would let every generator go down to 0; use central_reference for a case with Generator.min_generation")
     kw = pp.engine_kwargs()
     kw["sto_eta"] = _efficiencies(pp, efficiency)
     if initial_level is not None:

@@ -123,12 +123,81 @@ static int ramp_budget_rows_fit(dopf_ctx *c, const char *entry, bool given_ramp,
                                 bool given_budget, const double *e_min, const double *e_max, bool given_table, const double *profiles,
                                 const int32_t *profile_of);
 
+// dopf_set_generator_min_output: a row with a floor needs a path inside floor_t = min(p_min, cap_t) <= P_t <= cap_t under its ramps and
+// anchor. The forward intervals F_0 = [max(floor_0, prev - down), min(cap_0, prev + up)] ([floor_0, cap_0] without an anchor),
+// F_t = [max(floor_t, lo_{t-1} - down), min(cap_t, hi_{t-1} + up)] hold exactly the values a path can have at t: the row is feasible
+// exactly when none is empty (a point of F_{T-1} traces back through them). At p_min = 0 this is ramp_anchor_fits.
+// g: the caller's index (the message's); f: the generator's profile, or null; prev: NaN = no anchor
+static int ramp_floor_fits(dopf_ctx *c, const char *entry, int g, double pm, double p_min, double up, double down, double prev, const double *f)
+{
+    double lo = 0.0, hi = 0.0;
+    for (int t = 0; t < c->v.T; ++t) {
+        const double cap = f ? pm * f[t] : pm, fl = std::min(p_min, cap);
+        if (t == 0 && std::isnan(prev)) { lo = fl; hi = cap; }
+        else if (t == 0) { lo = std::max(fl, prev - down); hi = std::min(cap, prev + up); }
+        else { lo = std::max(fl, lo - down); hi = std::min(cap, hi + up); }
+        if (lo > hi)
+            return fail(c, DOPF_E_INVALID, "%s: generator g = %d has no path between its floor and its cap under its ramps and anchor at t = %d "
+                                           "(at least %g, at most %g; p_min = %g)", entry, g, t, lo, hi, p_min);
+    }
+    return DOPF_OK;
+}
+
+// ... for every row with a floor above 0: the stored floors (gen_min_h), ramps, anchor, profile indices and table, each replaced by the
+// caller's where one is given (p_min, up / down / prev: the caller's order; given_ramp says whether the call sets the ramps — a NULL
+// then means the default; profiles / profile_of: the availability setter's arguments, with given_table)
+static int ramp_floor_rows_fit(dopf_ctx *c, const char *entry, const double *p_min, bool given_ramp, const double *up, const double *down,
+                               const double *prev, bool given_table, const double *profiles, const int32_t *profile_of)
+{
+    if (!c->plan.genRamp || (!p_min && !c->plan.genMinOut)) return DOPF_OK;
+    const size_t G = (size_t)c->v.G;
+    const int T = c->v.T;
+    for (size_t i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        const double pmn = p_min ? p_min[a] : c->gen_min_h[i];
+        if (!(pmn > 0.0)) continue;
+        double u = c->gen_ramp_h[G + i], d = c->gen_ramp_h[2 * G + i], pv = c->gen_ramp_h[3 * G + i];
+        if (given_ramp) { u = up ? up[a] : INFINITY; d = down ? down[a] : INFINITY; pv = prev ? prev[a] : std::nan(""); }
+        const double *f = nullptr;
+        if (given_table) {
+            const int k = profile_of ? profile_of[a] : -1;
+            if (k >= 0) f = profiles + (size_t)k * T;
+        } else {
+            const int k = c->gen_prof_h.empty() ? -1 : c->gen_prof_h[i];
+            if (k >= 0) f = c->gen_avail_h.data() + (size_t)k * T;
+        }
+        if (int rc = ramp_floor_fits(c, entry, a, c->gen_ramp_h[i], pmn, u, d, pv, f)) return rc;
+    }
+    return DOPF_OK;
+}
+
+// dopf_set_generator_min_output's checks: the ramp flag, no budget, 0 <= p_min <= gen_pmax (finite), and every row with a floor has a
+// path under the stored ramps, anchor and availability table
+int check_generator_min_output(dopf_ctx *c, const double *p_min)
+{
+    if (!(c->q.flags & DOPF_F_GEN_RAMP))
+        return fail(c, DOPF_E_UNSUPPORTED, "minimum output runs on the ramp kernels: it needs DOPF_F_GEN_RAMP at dopf_create (on a network "
+                                           "DOPF_F_GEN_RAMP_NETWORK too; the ramps stay +inf until they are set)");
+    if (c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET)
+        return fail(c, DOPF_E_UNSUPPORTED, "minimum output does not combine with DOPF_F2_GEN_ENERGY_BUDGET (nor with the pair, "
+                                           "DOPF_F2_GEN_RAMP_BUDGET): floors inside the multiplier search are not built");
+    if (!p_min) return DOPF_OK;
+    for (int i = 0; i < c->v.G; ++i) {
+        const int a = c->gen_perm[i];
+        if (!(p_min[a] >= 0.0 && p_min[a] <= c->gen_ramp_h[i]))
+            return fail(c, DOPF_E_INVALID, "dopf_set_generator_min_output: p_min[%d] is %g, outside [0, gen_pmax = %g]", a, p_min[a], c->gen_ramp_h[i]);
+    }
+    return ramp_floor_rows_fit(c, "dopf_set_generator_min_output", p_min, false, nullptr, nullptr, nullptr, false, nullptr, nullptr);
+}
+
 // dopf_set_generator_ramp's checks: the flag, both ramp arrays or neither, no NaN, ramps >= 0, p_prev in [0, gen_pmax], and every
 // anchored generator able to stay under its caps (the stored availability table)
 int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev)
 {
     if (int rc = NEEDS_FLAG(c, "generator ramp limits need", DOPF_F_GEN_RAMP)) return rc;
     if (int rc = check_generator_ramp_values(c, "dopf_set_generator_ramp", c->gen_ramp_h.data(), c->gen_avail_h.data(), up, down, prev)) return rc;
+    // dopf_set_generator_min_output: ... and every row with a stored floor keeps a path under the new ramps and anchor
+    if (int rc = ramp_floor_rows_fit(c, "dopf_set_generator_ramp", nullptr, true, up, down, prev, false, nullptr, nullptr)) return rc;
     // DOPF_F2_GEN_RAMP_BUDGET: ... and every row jointly feasible with its stored budget
     return ramp_budget_rows_fit(c, "dopf_set_generator_ramp", true, up, down, prev, false, nullptr, nullptr, false, nullptr, nullptr);
 }
@@ -302,6 +371,9 @@ int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles,
             if (int rc = ramp_anchor_fits(c, "dopf_set_generator_availability", a, c->gen_ramp_h[i], c->gen_ramp_h[2 * (size_t)G + i],
                                           c->gen_ramp_h[3 * (size_t)G + i], k >= 0 ? profiles + (size_t)k * T : nullptr)) return rc;
         }
+    // the floors of dopf_set_generator_min_output, under the new table
+    if (int rc = ramp_floor_rows_fit(c, "dopf_set_generator_availability", nullptr, false, nullptr, nullptr, nullptr, true, profiles, profile_of))
+        return rc;
     if (c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET)      // the minima of dopf_set_generator_energy_budget, under the new table
         for (int i = 0; i < G; ++i) {
             const int a = c->gen_perm[i], k = profile_of ? profile_of[a] : -1;
@@ -899,11 +971,14 @@ int upload_agents(dopf_ctx *c, const Sorted &so)
         c->gen_ramp_h.assign(so.gpm.begin(), so.gpm.end());
         c->gen_ramp_h.resize(3 * G, INFINITY);
         c->gen_ramp_h.resize(4 * G, std::nan(""));
+        c->gen_min_h.assign(G, 0.0);
         double *blk = nullptr;
         d.raw(&blk, n);
         if (d.rc) return d.rc;
         HIPCHK(c, hipMemcpy(blk, c->gen_ramp_h.data(), 4 * G * sizeof(double), hipMemcpyHostToDevice));
         v.gen_pmax = blk;
+        // the floors of dopf_set_generator_min_output behind the scratch: zeros until then
+        HIPCHK(c, hipMemset(const_cast<double *>(gen_min_output(v)), 0, G * sizeof(double)));
     } else if (c->plan.genBudget) {
         // DOPF_F2_GEN_ENERGY_BUDGET: the budgets behind the capacities, e_min (0) | e_max (+inf) until the setter
         c->gen_budget_h.assign(so.gpm.begin(), so.gpm.end());
@@ -1797,6 +1872,44 @@ int dopf_set_generator_ramp(dopf_ctx *c, const double *up, const double *down, c
     return DOPF_OK;
 }
 
+int dopf_set_generator_min_output(dopf_ctx *c, const double *p_min)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_generator_min_output(c, p_min)) return rc;
+    const size_t G = (size_t)c->v.G;
+    if (G == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    std::vector<double> h(G, 0.0);
+    if (p_min)
+        for (size_t i = 0; i < G; ++i) h[i] = p_min[c->gen_perm[i]] + 0.0;
+    // the first array switches the context to the MN instantiations of its generator kernel, NULL switches back: other kernels, so the
+    // iteration graphs are captured again at the next dopf_iterate (as after a grown availability table). Between two arrays the graphs
+    // read the same device array (no capture again)
+    const bool on = p_min != nullptr;
+    if (on != c->plan.genMinOut) {
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        c->plan.genMinOut = on;
+        drop_graphs(c);
+    }
+    // ordered on the context's stream behind what is queued there. The state stays (a P below its floor is a proximal centre: the next
+    // x-update clamps it); the stop test starts over, as after dopf_set_generator_ramp
+    HIPCHK(c, hipMemcpyAsync(const_cast<double *>(gen_min_output(c->v)), h.data(), G * sizeof(double), hipMemcpyHostToDevice, c->main));
+    launch_reset_status(c->v, c->main);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = read_status(c)) return rc;          // (synchronises: h may go)
+    c->gen_min_h = h;
+    return DOPF_OK;
+}
+
+// the stored floors from the host mirror (no device call); a context without DOPF_F_GEN_RAMP holds none: zeros
+int dopf_get_generator_min_output(dopf_ctx *c, double *p_min)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (!p_min) return c->v.G == 0 ? DOPF_OK : fail(c, DOPF_E_INVALID, "dopf_get_generator_min_output: p_min is NULL");
+    for (int i = 0; i < c->v.G; ++i) p_min[c->gen_perm[i]] = c->gen_min_h.empty() ? 0.0 : c->gen_min_h[(size_t)i];
+    return DOPF_OK;
+}
+
 int dopf_set_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max)
 {
     if (!c) return DOPF_E_INVALID;
@@ -1906,6 +2019,7 @@ static int check_gen_window(dopf_ctx *c, const char *entry, GenWindow &w)
     int rc = DOPF_OK;
     if (ramp) rc = check_generator_ramp_values(c, entry, c->gen_ramp_h.data(), c->gen_avail_h.data(), up.data(), down.data(), prev.data());
     if (!rc && budget) rc = check_generator_energy_budget_values(c, entry, c->gen_budget_h.data(), c->gen_avail_h.data(), lo.data(), hi.data());
+    if (!rc) rc = ramp_floor_rows_fit(c, entry, nullptr, false, nullptr, nullptr, nullptr, false, nullptr, nullptr);     // (the stored floors stay)
     if (!rc) rc = ramp_budget_rows_fit(c, entry, false, nullptr, nullptr, nullptr, false, nullptr, nullptr, false, nullptr, nullptr);
     w.swap(c);
     return rc;

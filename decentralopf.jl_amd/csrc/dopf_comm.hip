@@ -759,6 +759,12 @@ int dopf_multi_set_generator_ramp(dopf_multi *m, const double *ramp_up, const do
                      [&](auto f, int i) { return f(m->ctx[i], from(ramp_up, m->g0[i]), from(ramp_down, m->g0[i]), from(p_prev, m->g0[i])); });
 }
 
+int dopf_multi_set_generator_min_output(dopf_multi *m, const double *p_min)
+{
+    return multi_set(m, check_generator_min_output, dopf_set_generator_min_output,
+                     [&](auto f, int i) { return f(m->ctx[i], from(p_min, m->g0[i])); });
+}
+
 int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, const double *e_max)
 {
     return multi_set(m, check_generator_energy_budget, dopf_set_generator_energy_budget,

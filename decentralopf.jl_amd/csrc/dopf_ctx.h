@@ -42,6 +42,7 @@ struct dopf_ctx {
     int gen_avail_cap = 0;                 //     profiles it has room for
     std::vector<double> gen_ramp_h;        // DOPF_F_GEN_RAMP: gen_pmax | ramp_up | ramp_down | p_prev (NaN: none) as on the device (sorted order), and
     std::vector<double> gen_avail_h;       //     with DOPF_F_GEN_AVAILABILITY the profile table: what the two setters check the anchors against
+    std::vector<double> gen_min_h;         // ... and the floors p_min of dopf_set_generator_min_output as on the device (sorted order; zeros until then)
     int32_t flags2 = 0;                    // the second flag word (DOPF_F2_*, dopf_create_ex)
     std::vector<double> gen_budget_h;      // DOPF_F2_GEN_ENERGY_BUDGET: gen_pmax | e_min | e_max as on the device (sorted order); gen_avail_h is
                                            //     kept for these contexts too: what the two setters check e_min <= sum_t cap against
@@ -83,6 +84,8 @@ int check_line_rating(dopf_ctx *c, const double *rating);   // those of dopf_set
 int check_generator_quadratic_cost(dopf_ctx *c, const double *c2);   // those of dopf_set_generator_quadratic_cost (flag, finite, >= 0)
 // those of dopf_set_generator_ramp (flag, no NaN, ramps >= 0 and both or neither, p_prev in [0, gen_pmax], the anchors under the caps)
 int check_generator_ramp(dopf_ctx *c, const double *up, const double *down, const double *prev);
+// those of dopf_set_generator_min_output (the ramp flag, no budget, 0 <= p_min <= gen_pmax, a path for every row with a floor)
+int check_generator_min_output(dopf_ctx *c, const double *p_min);
 // those of dopf_set_generator_energy_budget (flag, no NaN, 0 <= e_min <= e_max, e_min finite and <= sum_t cap)
 int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max);
 // the two without their flag checks, for a caller that keeps the arrays itself (dopf_central_solve_coupled; `entry`: the name the

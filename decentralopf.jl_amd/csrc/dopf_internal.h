@@ -205,21 +205,28 @@ __host__ __device__ inline const double *gen_c2(const DevView &v) { return v.gen
 // T values c_t / y*_t, then the knots' x and v, 2T + 2 each (the bound of DESIGN.md 5r)
 constexpr int kRampLdsT = 128, kRampWaves = 8;
 __host__ __device__ inline size_t ramp_row_doubles(int T) { return 5 * (size_t)T + 4; }
-inline size_t ramp_scratch_doubles(int T, int nGenItems) { return T > kRampLdsT ? (size_t)nGenItems * kRampWaves * ramp_row_doubles(T) : 0; }
+__host__ __device__ inline size_t ramp_scratch_doubles(int T, int nGenItems) { return T > kRampLdsT ? (size_t)nGenItems * kRampWaves * ramp_row_doubles(T) : 0; }
 // ... on a network (DOPF_F_GEN_RAMP_NETWORK, k_gen_ramp_net; L > 0): at every T, per wave p0[T] | y*[T] | kx[K] | kv[K] with
 // K = ramp_net_knots(T, L) (ramp_dp.h) — a row's knots leave LDS as soon as the tables' kinks do not fit beside the ramps'
-inline size_t ramp_scratch_doubles(int T, int nGenItems, int L)
+__host__ __device__ inline size_t ramp_scratch_doubles(int T, int nGenItems, int L)
 {
     return L > 0 ? (size_t)nGenItems * kRampWaves * ramp_net_row_doubles(T, L) : ramp_scratch_doubles(T, nGenItems);
 }
+// ... and behind the scratch, where the four arrays and the scratch keep their places, the floors p_min[G] of
+// dopf_set_generator_min_output (sorted order, zeros until then): read by the MN instantiations of k_gen_ramp and
+// k_gen_ramp_net alone (gen_min_output(v): a ramp context with lines is a DOPF_F_GEN_RAMP_NETWORK one, its scratch the network's)
 inline size_t gen_pmax_doubles(int G, int T, int nGenItems, bool ramp, int L = 0)
 {
-    return ramp ? 4 * (size_t)G + ramp_scratch_doubles(T, nGenItems, L) : (size_t)G;
+    return ramp ? 5 * (size_t)G + ramp_scratch_doubles(T, nGenItems, L) : (size_t)G;
 }
 __host__ __device__ inline const double *gen_ramp_up(const DevView &v) { return v.gen_pmax + v.G; }
 __host__ __device__ inline const double *gen_ramp_down(const DevView &v) { return v.gen_pmax + 2 * (size_t)v.G; }
 __host__ __device__ inline const double *gen_ramp_prev(const DevView &v) { return v.gen_pmax + 3 * (size_t)v.G; }
 __host__ __device__ inline double *gen_ramp_scratch(const DevView &v) { return const_cast<double *>(v.gen_pmax) + 4 * (size_t)v.G; }
+__host__ __device__ inline const double *gen_min_output(const DevView &v)
+{
+    return v.gen_pmax + 4 * (size_t)v.G + ramp_scratch_doubles(v.T, v.nGenItems, v.L);
+}
 // ... with DOPF_F2_GEN_ENERGY_BUDGET (never together with the ramps: plan_chain) behind the capacities, G doubles each in sorted order,
 // e_min (0 until dopf_set_generator_energy_budget) | e_max (+inf until then). k_gen_budget keeps nothing else: a searched row forms its
 // steps again from P, which it overwrites last (gen_budget.h)
@@ -421,7 +428,7 @@ void launch_roll_state(const DevView &v, const Plan &p, int k, int iteration, hi
 // dopf_set_line_rating: status as dopf_set_demand leaves it, then the consensus step's derived state under the new limits — the
 // per-(l,t) flags, walk_any / tab_skip and the tables the price kernels write — from the sums in cons (no sums are formed or moved)
 void launch_line_rating(const DevView &v, const Plan &p, hipStream_t s);
-// dopf_set_generator_quadratic_cost, dopf_set_generator_ramp: status as dopf_set_line_rating leaves it (nothing derived depends on the costs or the ramps)
+// dopf_set_generator_quadratic_cost, dopf_set_generator_ramp, dopf_set_generator_min_output: status as dopf_set_line_rating leaves it (nothing derived depends on the costs or the ramps)
 void launch_reset_status(const DevView &v, hipStream_t s);
 void launch_penalty_sums(const DevView &v, double *out /* [3][N][T], device */, hipStream_t s);   // Result.penalty_term, per node
 void launch_node_results(const DevView &v, double *gen, double *dis, double *chg, hipStream_t s);   // [n + N*t] each, device pointers   // consensus -> inj/s/flow/price (no dual step)

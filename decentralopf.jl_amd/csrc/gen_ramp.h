@@ -4,6 +4,7 @@
 // Row g keeps its separable quadratic objective and its box 0 <= P[g,t] <= cap[g,t] and gains
 //     -down <= P[g,t] - P[g,t-1] <= up (t >= 1),   -down <= P[g,0] - prev <= up (anchored rows),
 // so its step is the Euclidean projection of c, c_t = the unclamped step of gen_update_body, onto {box, ramps}.
+// With floors (dopf_set_generator_min_output; the MN instantiations) the box is fmin(p_min[g], cap[g,t]) <= P[g,t] <= cap[g,t].
 //
 // One block per generator item, kRampWaves waves, in three phases:
 //  1. a wave per row, lanes over t (P is agent-major: a row's T values are consecutive, the wave's loads and stores are whole
@@ -40,11 +41,14 @@ __device__ __forceinline__ double ramp_argmin(const double *kx, const double *kv
 // come between; clip to [0, cap_t]; add q (x - c_t). At most two knots more per step: n <= 2T. Backward: P[T-1] = y*_{T-1},
 // P[t-1] = clamp(y*_{t-1}, P[t] - up, P[t] + down). cy holds c_t on entry, y*_t behind the step that used c_t.
 // up, down: finite (the caller caps them at pmax: a ramp of pmax or more never binds inside [0, pmax]).
-template <bool AV>
+// MN (dopf_set_generator_min_output): the box of step t is [fmin(pmn, cap_t), cap_t] — a floor that follows the cap down
+// — in [0, cap_t]'s place; the setter has made sure that a path exists.
+template <bool AV, bool MN = false>
 __device__ __forceinline__ void ramp_repair(double *Prow, double *cy, double *kx, double *kv, int T, double q, double up, double down,
-                                         double prev, double pm, const double *ftab, int prof)
+                                         double prev, double pm, const double *ftab, int prof, double pmn = 0.0)
 {
     double lo = 0.0, hi = AV ? avail_cap(ftab, T, prof, pm, 0) : pm;
+    if constexpr (MN) lo = fmin(pmn, hi);
     if (prev == prev) { lo = fmax(lo, prev - down); hi = fmin(hi, prev + up); }
     hi = fmax(hi, lo);
     kx[0] = lo; kv[0] = q * (lo - cy[0]);
@@ -66,7 +70,8 @@ __device__ __forceinline__ void ramp_repair(double *Prow, double *cy, double *kx
         kx[k + 1] = y + up; kv[k + 1] = 0.0;
         // clip to [lo, hi]: the value at lo from the right (the last knot at or below it), at hi from the left (the first at or above)
         const double cap = AV ? avail_cap(ftab, T, prof, pm, t) : pm;
-        lo = fmax(0.0, kx[0]);
+        if constexpr (MN) lo = fmax(fmin(pmn, cap), kx[0]);
+        else lo = fmax(0.0, kx[0]);
         hi = fmax(fmin(cap, kx[n2 - 1]), lo);
         int a = 0, b = n2 - 1;
         while (a + 1 < n2 && kx[a + 1] <= lo) ++a;
@@ -93,7 +98,9 @@ __device__ __forceinline__ void ramp_repair(double *Prow, double *cy, double *kx
     }
 }
 
-template <bool AV, bool QC>
+// MN: the rows' floors (gen_min_output(v)) are read and the box is [fmin(p_min, cap), cap]; the MN = false instantiations are the
+// kernels of the contexts that never set a floor
+template <bool AV, bool QC, bool MN>
 __global__ __launch_bounds__(512) void k_gen_ramp(DevView v)
 {
     if (v.st->halt) return;
@@ -111,6 +118,8 @@ __global__ __launch_bounds__(512) void k_gen_ramp(DevView v)
     const double *c2v = nullptr;
     if constexpr (QC) c2v = gen_c2(v);
     const double *upv = gen_ramp_up(v), *dnv = gen_ramp_down(v), *pvv = gen_ramp_prev(v);
+    const double *mnv = nullptr;
+    if constexpr (MN) mnv = gen_min_output(v);
 
     // the wave's c_t / y*_t and knots: LDS, or (long horizons) its scratch behind gen_pmax
     double *cy = s_cy[wave], *kx = s_kx[wave], *kv = s_kv[wave];
@@ -124,8 +133,9 @@ __global__ __launch_bounds__(512) void k_gen_ramp(DevView v)
         const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
         const double up = upv[g], dn = dnv[g], prev = pvv[g];
         const int pr = AV ? prof[g] : -1;
-        double c2 = 0.0, iq = inv;
+        double c2 = 0.0, iq = inv, pmn = 0.0;
         if constexpr (QC) { c2 = c2v[g]; iq = 1.0 / ((w + gam) + c2); }
+        if constexpr (MN) pmn = mnv[g];
         double *Prow = v.P + (size_t)g * T;
         double left = prev;                         // the value in front of the chunk's first timestep (NaN: none)
         bool bad = false;
@@ -139,7 +149,12 @@ __global__ __launch_bounds__(512) void k_gen_ramp(DevView v)
                 double c;
                 if constexpr (QC) c = p0 - fma(mc + c2 * p0, iq, psum * iq);
                 else c = p0 - fma(mc, inv, psum * inv);       // (mc * inv + shift as gen_update_body's loop contracts it)
-                pn = clampd(c, 0.0, AV ? avail_cap(ftab, T, pr, pm, t) : pm);
+                if constexpr (MN) {
+                    const double cap = AV ? avail_cap(ftab, T, pr, pm, t) : pm;
+                    pn = clampd(c, fmin(pmn, cap), cap);
+                } else {
+                    pn = clampd(c, 0.0, AV ? avail_cap(ftab, T, pr, pm, t) : pm);
+                }
                 Prow[t] = pn;
                 cy[t] = c;
             }
@@ -154,7 +169,7 @@ __global__ __launch_bounds__(512) void k_gen_ramp(DevView v)
         if (__any(bad)) {
             __threadfence_block();                  // the wave's c_t, before lane 0 reads them
             if (lane == 0)
-                ramp_repair<AV>(Prow, cy, kx, kv, T, (w + gam) + c2, fmin(up, pm), fmin(dn, pm), prev, pm, ftab, pr);
+                ramp_repair<AV, MN>(Prow, cy, kx, kv, T, (w + gam) + c2, fmin(up, pm), fmin(dn, pm), prev, pm, ftab, pr, pmn);
             __threadfence_block();
         }
     }
@@ -202,7 +217,10 @@ void launch_gen_ramp(const DevView &v, const Plan &p, hipStream_t s)
     if (v.nGenItems == 0) return;
     with_bool(p.genAvail, [&](auto av) {
         with_bool(p.genQuad, [&](auto qc) {
-            hipLaunchKernelGGL((k_gen_ramp<decltype(av)::value, decltype(qc)::value>), dim3(v.nGenItems), dim3(512), 0, s, v);
+            with_bool(p.genMinOut, [&](auto mn) {
+                hipLaunchKernelGGL((k_gen_ramp<decltype(av)::value, decltype(qc)::value, decltype(mn)::value>), dim3(v.nGenItems), dim3(512),
+                                   0, s, v);
+            });
         });
     });
 }

@@ -29,7 +29,9 @@ struct RampRowTab {
     size_t node, N;
     int M2, T, prof;
     double mc, c2, w, pm;
+    double pmn;                     // the row's p_min (read by floor() only: ramp_repair_pwl<true>)
     __device__ __forceinline__ double cap(int t) const { return AV ? avail_cap(ftab, T, prof, pm, t) : pm; }
+    __device__ __forceinline__ double floor(int t) const { return fmin(pmn, cap(t)); }
     __device__ __forceinline__ RampStepTab step(int t) const
     {
         const size_t at = node + N * (size_t)t;
@@ -37,7 +39,8 @@ struct RampRowTab {
     }
 };
 
-template <bool AV, bool QC>
+// MN: as k_gen_ramp's — the box is [fmin(p_min, cap), cap] (dopf_set_generator_min_output)
+template <bool AV, bool QC, bool MN>
 __global__ __launch_bounds__(512) void k_gen_ramp_net(DevView v)
 {
     if (v.st->halt) return;
@@ -54,6 +57,8 @@ __global__ __launch_bounds__(512) void k_gen_ramp_net(DevView v)
     const double *c2v = nullptr;
     if constexpr (QC) c2v = gen_c2(v);
     const double *upv = gen_ramp_up(v), *dnv = gen_ramp_down(v), *pvv = gen_ramp_prev(v);
+    const double *mnv = nullptr;
+    if constexpr (MN) mnv = gen_min_output(v);
 
     // the wave's scratch: p0[T] | y*[T] | kx[K] | kv[K]
     const int K = ramp_net_knots(T, v.L);
@@ -65,8 +70,9 @@ __global__ __launch_bounds__(512) void k_gen_ramp_net(DevView v)
         const double mc = v.gen_mc[g], pm = v.gen_pmax[g];
         const double up = upv[g], dn = dnv[g], prev = pvv[g];
         const int pr = AV ? prof[g] : -1;
-        double c2 = 0.0;
+        double c2 = 0.0, pmn = 0.0;
         if constexpr (QC) c2 = c2v[g];
+        if constexpr (MN) pmn = mnv[g];
         double *Prow = v.P + (size_t)g * T;
         double left = prev;                         // the value in front of the chunk's first timestep (NaN: none)
         bool bad = false;
@@ -111,7 +117,8 @@ __global__ __launch_bounds__(512) void k_gen_ramp_net(DevView v)
                     const int a = lo < m ? lo : m - 1;
                     dl = beta[a] - (mc + psi[a] + w * beta[a]) * rcp64(slope[lo] + w);
                 }
-                pn = clampd(p0 + dl, 0.0, cap);
+                if constexpr (MN) pn = clampd(p0 + dl, fmin(pmn, cap), cap);
+                else pn = clampd(p0 + dl, 0.0, cap);
                 Prow[t] = pn;
                 if (keepd) v.dltG[(size_t)g * T + t] = pn - p0;
                 p0s[t] = p0;
@@ -134,8 +141,8 @@ __global__ __launch_bounds__(512) void k_gen_ramp_net(DevView v)
             int ok = 1;
             if (lane == 0) {
                 const RampRowTab<AV> row{v.tb_beta, v.tb_psi, v.tb_slope, v.tb_psi0, v.tb_m, p0s, ftab, (size_t)it.node, (size_t)N,
-                                         v.M2, T, pr, mc, c2, w, pm};
-                ok = ramp_repair_pwl(row, Prow, cy, kx, kv, cap_k, T, fmin(up, pm), fmin(dn, pm), prev) ? 1 : 0;
+                                         v.M2, T, pr, mc, c2, w, pm, pmn};
+                ok = ramp_repair_pwl<MN>(row, Prow, cy, kx, kv, cap_k, T, fmin(up, pm), fmin(dn, pm), prev) ? 1 : 0;
                 if (!ok) atomicAdd(&v.st->solver_fail, 1ull);       // the clamped step stays in the row
             }
             __threadfence_block();
@@ -190,7 +197,10 @@ void launch_gen_ramp_net(const DevView &v, const Plan &p, hipStream_t s)
     if (v.nGenItems == 0) return;
     with_bool(p.genAvail, [&](auto av) {
         with_bool(p.genQuad, [&](auto qc) {
-            hipLaunchKernelGGL((k_gen_ramp_net<decltype(av)::value, decltype(qc)::value>), dim3(v.nGenItems), dim3(512), 0, s, v);
+            with_bool(p.genMinOut, [&](auto mn) {
+                hipLaunchKernelGGL((k_gen_ramp_net<decltype(av)::value, decltype(qc)::value, decltype(mn)::value>), dim3(v.nGenItems),
+                                   dim3(512), 0, s, v);
+            });
         });
     });
 }

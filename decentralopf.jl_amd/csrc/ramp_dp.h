@@ -8,7 +8,8 @@
 //     int m() const              kinks of phi_t (0: one line)
 //     double kink(int j) const   their x, ascending (j < m)
 //     double phi(double x, int &piece) const   phi_t(x); piece: a cursor that only moves up while x does (start it at 0)
-// and a row type hands out cap(t) and step(t).
+// and a row type hands out cap(t) and step(t) — and, only where ramp_repair_pwl is asked for floors (FLOOR), floor(t) <= cap(t): the
+// box of step t is then floor(t) <= x_t <= cap(t) (dopf_set_generator_min_output).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -133,13 +134,15 @@ DOPF_DP_FN int dp_add_phi(const Step &st, double *kx, double *kv, int n, int K)
 // (y* + up, 0) come between; clip to [0, cap_t]; add phi_t (dp_add_phi). Backward: x[T-1] = y*_{T-1},
 // x[t-1] = clamp(y*_{t-1}, x[t] - up, x[t] + down). cy: T doubles of scratch (y*_t). up, down: finite (the caller caps them at the
 // row's largest cap: such a ramp never binds). prev: NaN = no anchor. Returns false — out (T values) untouched, nothing written
-// beyond kx[K - 1], kv[K - 1] — where the knots would exceed K.
-template <class Row>
+// beyond kx[K - 1], kv[K - 1] — where the knots would exceed K. FLOOR: the lower end of step t's box is row.floor(t) in 0's place
+// (a row type without floor() serves the default; the caller has made sure that a path exists: dopf_set_generator_min_output).
+template <bool FLOOR = false, class Row>
 DOPF_DP_FN bool ramp_repair_pwl(const Row &row, double *out, double *cy, double *kx, double *kv, int K, int T, double up, double down,
                                 double prev)
 {
     if (K < 2) return false;
     double lo = 0.0, hi = row.cap(0);
+    if constexpr (FLOOR) lo = row.floor(0);
     if (prev == prev) { lo = dp_max(lo, prev - down); hi = dp_min(hi, prev + up); }
     hi = dp_max(hi, lo);
     kx[0] = lo; kv[0] = 0.0;
@@ -162,7 +165,8 @@ DOPF_DP_FN bool ramp_repair_pwl(const Row &row, double *out, double *cy, double 
         kx[k] = y - down; kv[k] = 0.0;
         kx[k + 1] = y + up; kv[k + 1] = 0.0;
         // clip to [lo, hi]: the value at lo from the right (the last knot at or below it), at hi from the left (the first at or above)
-        lo = dp_max(0.0, kx[0]);
+        if constexpr (FLOOR) lo = dp_max(row.floor(t), kx[0]);
+        else lo = dp_max(0.0, kx[0]);
         hi = dp_max(dp_min(row.cap(t), kx[n2 - 1]), lo);
         int a = 0, b = n2 - 1;
         while (a + 1 < n2 && kx[a + 1] <= lo) ++a;

@@ -382,6 +382,42 @@ function set_ramp!(admm::ADMM, ramp_up::Union{Nothing, Vector{Float64}}, ramp_do
 end
 
 """
+    set_min_output!(admm, p_min)
+
+The must-run floor of each generator (`0 <= p_min[g] <= max_generation`, in the order of `generators`; `nothing` = all 0):
+`min(p_min[g], cap[g,t]) <= P[g,t]` — the floor follows an availability profile down, and `p_min = max_generation` is a must-take
+unit. The reference's generators go down to 0. Minimum output runs on the ramp kernels: the ADMM must have been created with
+`flags = DOPF_F_GEN_RAMP` (with lines the constructor adds `DOPF_F_GEN_RAMP_NETWORK`; the ramps stay `Inf` until `set_ramp!`), and
+it does not combine with `DOPF_F2_GEN_ENERGY_BUDGET`. The state and the iteration counter stay; takes effect at the next iteration.
+"""
+function set_min_output!(admm::ADMM, p_min::Union{Nothing, Vector{Float64}})
+    G = length(admm.generators)
+    p_min === nothing || length(p_min) == G || error("set_min_output!: expected $G values, got $(length(p_min))")
+    p = p_min === nothing ? Ptr{Cdouble}(C_NULL) : pointer(p_min)
+    GC.@preserve p_min begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_generator_min_output, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi, p),
+                             admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_generator_min_output, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, p), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    min_output(admm)
+
+The floors as the context holds them (`dopf_get_generator_min_output`; a multi-GPU ADMM: not available).
+"""
+function min_output(admm::ADMM)
+    admm.multi == C_NULL || error("min_output: not on a multi-GPU ADMM")
+    out = zeros(Float64, length(admm.generators))
+    GC.@preserve out dopf_check(ccall((:dopf_get_generator_min_output, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, pointer(out)), admm.ctx)
+    return out
+end
+
+"""
     set_energy_budget!(admm, e_min, e_max)
 
 The energy budget of each generator over the window (`e_min[g] >= 0` finite, `e_max[g] >= e_min[g]`, `Inf` = no limit, in the order

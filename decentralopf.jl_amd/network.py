@@ -23,6 +23,9 @@ Generator.ramp_up / ramp_down are not in the reference either (its generators mo
 -ramp_down <= P[t] - P[t-1] <= ramp_up, the limit on how fast a unit's output changes (DOPF_F_GEN_RAMP; on a case with lines the engines add DOPF_F_GEN_RAMP_NETWORK).
 Generator.energy_min / energy_max are not in the reference either: energy_min <= sum_t P[t] <= energy_max, the energy a unit delivers
 over the window — a reservoir's water, a minimum take, a fuel or emission cap (DOPF_F2_GEN_ENERGY_BUDGET, the second flag word).
+Generator.min_generation is not in the reference either (its generators' lower bound is 0): min(min_generation, cap[t]) <= P[t] — a
+must-run floor that follows an outage down; min_generation = max_generation is a must-take unit (dopf_set_generator_min_output, on
+the ramp kernels: the engines create the context with DOPF_F_GEN_RAMP).
 """
 from __future__ import annotations
 
@@ -52,6 +55,7 @@ class Generator:
     ramp_down: float = float("inf")                     # >= 0: P[t-1] - P[t] <= ramp_down; inf = no limit (not in the reference)
     energy_min: float = 0.0                             # >= 0, finite: sum_t P[t] >= energy_min (not in the reference)
     energy_max: float = float("inf")                    # >= energy_min: sum_t P[t] <= energy_max; inf = no limit (not in the reference)
+    min_generation: float = 0.0                         # in [0, max_generation]: P[t] >= min(min_generation, cap[t]) (not in the reference)
 
 
 @dataclass(eq=False)
@@ -147,6 +151,7 @@ class PackedProblem:
     gen_c2: Optional[np.ndarray] = None         # (G,) Generator.quadratic_costs; None = all 0
     gen_ramp: Optional[tuple] = None            # ((G,), (G,)) Generator.ramp_up, ramp_down; None = all inf
     gen_budget: Optional[tuple] = None          # ((G,), (G,)) Generator.energy_min, energy_max; None = all (0, inf)
+    gen_min_output: Optional[np.ndarray] = None     # (G,) Generator.min_generation; None = all 0
 
     @property
     def G(self):
@@ -181,7 +186,17 @@ class PackedProblem:
             kw["gen_ramp"] = self.ramp()
         if self.has_budget():      # (engines then run with F2_GEN_ENERGY_BUDGET, through dopf_create_ex)
             kw["gen_budget"] = self.budget()
+        if self.gen_min_output is not None and np.any(np.asarray(self.gen_min_output) != 0.0):
+            kw["gen_min_output"] = self.min_output()      # (engines then run with F_GEN_RAMP: the floors run on the ramp kernels)
         return kw
+
+    def min_output(self):
+        """min_generation, float64 (G,), the default filled in: all 0."""
+        return np.zeros(self.G) if self.gen_min_output is None else np.asarray(self.gen_min_output, dtype=np.float64)
+
+    def has_min_output(self) -> bool:
+        """Some generator has a floor (a shard: some generator of the whole problem, so that every rank runs with the ramp flag)."""
+        return bool(self.meta.get("min_output")) or bool(np.any(self.min_output() != 0.0))
 
     def budget(self):
         """(energy_min, energy_max), float64 (G,) each, the defaults filled in: all 0, all inf."""
@@ -202,7 +217,9 @@ class PackedProblem:
 
     def has_ramp(self) -> bool:
         """Some generator has a finite ramp limit (a shard: some generator of the whole problem, so that every rank runs with the flag)."""
-        return bool(self.meta.get("ramp")) or (self.gen_ramp is not None and any(bool(np.any(np.isfinite(r))) for r in self.ramp()))
+        if self.meta.get("ramp") or self.meta.get("min_output"):      # (a floor runs on the ramp kernels: the shards of such a problem all take the flag)
+            return True
+        return self.gen_ramp is not None and any(bool(np.any(np.isfinite(r))) for r in self.ramp())
 
     def quadratic_cost(self):
         """c2, float64 (G,), the default filled in: all 0."""
@@ -260,7 +277,7 @@ class PackedProblem:
             sto_node=self.sto_node[s0:s1],
             meta=dict(self.meta, rank=rank, world=world, gen_range=(g0, g1), sto_range=(s0, s1),
                       n_agents_global=self.G + self.S, quadratic_cost=self.has_quadratic_cost(), ramp=self.has_ramp(),
-                      budget=self.has_budget()),
+                      budget=self.has_budget(), min_output=self.has_min_output()),
             sto_e0=None if self.sto_e0 is None else self.sto_e0[s0:s1],
             sto_end_lo=None if self.sto_end_lo is None else self.sto_end_lo[s0:s1],
             sto_end_hi=None if self.sto_end_hi is None else self.sto_end_hi[s0:s1],
@@ -271,7 +288,8 @@ class PackedProblem:
             line_rating=self.line_rating,
             gen_c2=None if self.gen_c2 is None else self.gen_c2[g0:g1],
             gen_ramp=None if self.gen_ramp is None else tuple(np.asarray(r)[g0:g1] for r in self.gen_ramp),
-            gen_budget=None if self.gen_budget is None else tuple(np.asarray(b)[g0:g1] for b in self.gen_budget))
+            gen_budget=None if self.gen_budget is None else tuple(np.asarray(b)[g0:g1] for b in self.gen_budget),
+            gen_min_output=None if self.gen_min_output is None else np.asarray(self.gen_min_output)[g0:g1])
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],
@@ -310,6 +328,9 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
     budget = (f64(g.energy_min for g in generators), f64(g.energy_max for g in generators))
     if not np.all(np.isfinite(budget[0])) or np.any(budget[0] < 0.0) or np.any(np.isnan(budget[1])) or np.any(budget[1] < budget[0]):
         raise ValueError("generator energy_min must be finite and >= 0, energy_max >= energy_min (inf: no limit)")
+    pmin = f64(g.min_generation for g in generators)
+    if not np.all(np.isfinite(pmin)) or np.any(pmin < 0.0) or np.any(pmin > f64(g.max_generation for g in generators)):
+        raise ValueError("generator min_generation must lie in [0, max_generation]")
     # line ratings: a table only when some line has one (the others keep max_capacity in every timestep)
     rating = None
     if any(l.rating is not None for l in lines):
@@ -343,4 +364,5 @@ def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Seque
         line_rating=rating,
         gen_c2=c2,
         gen_ramp=ramp,
-        gen_budget=budget)
+        gen_budget=budget,
+        gen_min_output=pmin)

@@ -129,6 +129,11 @@ class ShardedADMM:
         params; every rank calls it between the same two steps."""
         self.engine.set_quadratic_cost(self._mine(c2, "gen"))
 
+    def set_min_output(self, p_min=None) -> None:
+        """All generators' must-run floors (problem.G values, global order; None = all 0): this rank sets its slice
+        (dopf_set_generator_min_output; the bound is local to the rank's agents, no exchange). Every rank must call it."""
+        self.engine.set_min_output(self._mine(p_min, "gen"))
+
     def set_ramp(self, up=None, down=None, prev=None) -> None:
         """All generators' ramp limits and (optionally) anchors (problem.G values each, global order; both ramps None = all inf,
         prev None = no anchor): this rank sets its slice (dopf_set_generator_ramp; the constraint is local to the rank's agents, no

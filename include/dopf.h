@@ -491,6 +491,36 @@ int dopf_set_generator_quadratic_cost(dopf_ctx *ctx, const double *c2 /* G; NULL
 int dopf_set_generator_ramp(dopf_ctx *ctx, const double *ramp_up /* G; NULL = +inf */, const double *ramp_down /* G; NULL = +inf */,
                             const double *p_prev /* G; NULL = no anchor */);
 
+/* Minimum output (must-run floors): p_min[G] in the caller's order of this context's generators, 0 <= p_min[g] <=
+ * gen_pmax[g], finite; NULL = all 0 (also the value until the first call). The box of row g at timestep t becomes
+ *     floor[g,t] <= P[g,t] <= cap[g,t],   floor[g,t] = fmin(p_min[g], cap[g,t])
+ * with cap[g,t] = gen_pmax[g], or gen_pmax[g] * f[prof[g]][t] under DOPF_F_GEN_AVAILABILITY: the floor follows an outage down (cap = 0
+ * gives floor = 0), and p_min = gen_pmax means "must take whatever is available". The objective, the ramps, the anchor, the c2 term,
+ * the injections and the consensus step stay as they are; p_min has no time axis. There is no create-time flag of its own: minimum
+ * output runs on the ramp kernels, so the context needs DOPF_F_GEN_RAMP (on a network DOPF_F_GEN_RAMP_NETWORK too); the ramps stay
+ * +inf until dopf_set_generator_ramp, so a must-take unit is a ramp context with infinite ramps. The library does NOT check that the
+ * floors of a node or a plate fit under the demand: an over-committed system does not converge, exactly as an under-supplied one does
+ * not. Timing, copies and status as for dopf_set_generator_ramp: callable between any two calls that iterate, the values are copied
+ * before the call returns, in order on the context's stream, into a device array the kernels read, and take effect at the next
+ * x-update; P, D, C, the duals and the iteration counter are kept, converged becomes 0, halt is formed again from max_iters and the
+ * residual maxima are cleared. A P below its floor (dopf_set_state) is only the proximal centre: the next x-update clamps it. The
+ * first call with an array switches the context to the floor instantiations of its generator kernel, a NULL call switches back; either
+ * switch drops the captured iteration graphs, which are captured again at the next dopf_iterate (the rule of a grown availability
+ * table); between two arrays the graphs stay valid. dopf_roll_horizon_coupled leaves p_min alone; dopf_central_solve* ignore it.
+ * DOPF_E_UNSUPPORTED without DOPF_F_GEN_RAMP, and on a context with DOPF_F2_GEN_ENERGY_BUDGET (the pair DOPF_F2_GEN_RAMP_BUDGET
+ * included: floors inside the multiplier search are not built). DOPF_E_INVALID, naming the entry and storing nothing, for a NaN, an
+ * Inf, a negative value, a value above gen_pmax, or a row g without a path: with the forward intervals
+ *     F_0 = [max(floor_0, p_prev - ramp_down), min(cap_0, p_prev + ramp_up)]   ([floor_0, cap_0] without an anchor),
+ *     F_t = [max(floor_t, lo_{t-1} - ramp_down), min(cap_t, hi_{t-1} + ramp_up)]
+ * the first t with lo_t > hi_t is refused (the message names g, t and both ends). The check is exact — a point of F_{T-1} traces back
+ * through the intervals — and at p_min = 0 it is dopf_set_generator_ramp's. dopf_set_generator_ramp, dopf_set_generator_availability
+ * and dopf_roll_horizon_coupled repeat it for every row with a stored p_min > 0 under their new ramps, anchor or table, before
+ * anything is overwritten. With G == 0 the call returns DOPF_OK and does nothing. */
+int dopf_set_generator_min_output(dopf_ctx *ctx, const double *p_min /* G; NULL = all 0 */);
+/* The stored floors, G values in the caller's order, from the context's host copy: no device call, callable at any time. Zeros on a
+ * context without DOPF_F_GEN_RAMP. */
+int dopf_get_generator_min_output(dopf_ctx *ctx, double *p_min /* G */);
+
 /* DOPF_F2_GEN_ENERGY_BUDGET: the generators' energy budgets over the window, e_min[G] and e_max[G] in the caller's order of this
  * context's generators: e_min[g] <= sum_t P[g,t] <= e_max[g]. Either array may be NULL on its own (e_min: all 0, e_max: all +inf, also
  * the values until the first call). Timing, copies and status as for dopf_set_generator_ramp: callable between any two calls that
@@ -769,6 +799,9 @@ int dopf_multi_set_generator_ramp(dopf_multi *m, const double *ramp_up, const do
 /* dopf_set_generator_energy_budget for all G generators, arrays in the caller's order (NULL as there): each shard gets its slice;
  * every shard is checked before any value is stored */
 int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, const double *e_max);
+/* dopf_set_generator_min_output for all G generators, p_min in the caller's order (NULL as there): each shard gets its slice; every
+ * shard is checked before any stores */
+int dopf_multi_set_generator_min_output(dopf_multi *m, const double *p_min);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);
