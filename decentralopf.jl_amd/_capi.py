@@ -162,6 +162,9 @@ class CApi:
                                                     c_double_p, c_double_p])
         self._opt("get_generator_coupling", C.c_int, [ctxp] + [c_double_p] * 5)
         self._opt("get_generator_min_output", C.c_int, [ctxp, c_double_p])
+        # the budget rows' multipliers of the last x-update (Engine.budget_price, MultiEngine.budget_price)
+        self._opt("get_generator_budget_price", C.c_int, [ctxp, c_double_p])
+        self._opt("multi_get_generator_budget_price", C.c_int, [ctxp, c_double_p])
         if prefix == "dopf_":
             self._sig("bind_consensus", C.c_int, [ctxp, C.c_void_p])
             self._sig("solver_failures", C.c_int64, [ctxp])
@@ -777,6 +780,20 @@ class Engine(_ExtensionSetters):
         self._chk(self.api.get_generator_min_output(self._ctx, _dp(out)))
         return out
 
+    def budget_price(self) -> np.ndarray:
+        """dopf_get_generator_budget_price: nu[g], the multiplier the last computed x-update put on generator g's budget row (the
+        number the kernels add to gen_mc[g]; the water value of the decentral run), G values: > 0 where e_max held the row down,
+        < 0 where e_min pushed it up, 0 for a free row and for one whose search gave up. Zeros before the first iteration; the
+        setters leave it alone. Recording is opt-in without F2_GEN_RAMP_BUDGET: the FIRST call switches the context to the kernels
+        that store the prices (graphs are captured again) and returns zeros; call it once after the constructor, then every call
+        returns the last iteration's prices. At convergence -budget_dual of central_solve_coupled where that dual is unique. Needs
+        F2_GEN_ENERGY_BUDGET (DopfError, unsupported, without); a backend without the entry: DopfError."""
+        if not hasattr(self.api, "get_generator_budget_price"):
+            raise DopfError(f"{self.api.prefix}*: this API has no get_generator_budget_price")
+        out = np.zeros(self.G)
+        self._chk(self.api.get_generator_budget_price(self._ctx, _dp(out)))
+        return out
+
     # -- a receding horizon --------------------------------------------------------------------
     def demand(self) -> np.ndarray:
         """The context's demand as it stands, (N, T)."""
@@ -1142,6 +1159,14 @@ class MultiEngine(_ExtensionSetters):
         E = np.zeros(self.S * self.T)
         self._chk(self.api.multi_get_primal(self._m, _dp(P), _dp(D), _dp(Cc), _dp(E)))
         return (P.reshape(self.G, self.T), D.reshape(self.S, self.T), Cc.reshape(self.S, self.T), E.reshape(self.S, self.T))
+
+    def budget_price(self) -> np.ndarray:
+        """dopf_multi_get_generator_budget_price: Engine.budget_price for all shards' rows in the caller's order, G values."""
+        if not hasattr(self.api, "multi_get_generator_budget_price"):
+            raise DopfError(f"{self.api.prefix}*: this API has no multi_get_generator_budget_price")
+        out = np.zeros(self.G)
+        self._chk(self.api.multi_get_generator_budget_price(self._m, _dp(out)))
+        return out
 
     def shard(self, i: int = 0) -> Engine:
         """Engine view of shard i's context (getters for the replicated state; do not iterate it directly)."""

@@ -206,6 +206,15 @@ class ADMM:
         self.packed.gen_budget = None if e_min is None and e_max is None else (lo, hi)
         self.convergence = Convergence()
 
+    def budget_price(self) -> np.ndarray:
+        """The water values of the run: nu[g], the multiplier the last computed iteration put on generator g's energy budget (G values
+        in the order of `generators`, in the unit of marginal_cost): > 0 where energy_max holds the unit down, < 0 where energy_min
+        pushes it up, 0 for a unit without a budget or with room in it. Not in the reference. Recording starts with the FIRST call (it
+        switches the generator kernel and returns zeros): call it once before iterating. Zeros before the first iteration; the
+        setters leave the values alone until the next iteration. At convergence minus the budget dual of the central LP
+        (_capi.central_solve_coupled's budget_dual) where that dual is unique. Needs F2_GEN_ENERGY_BUDGET, as set_energy_budget."""
+        return self.engine.budget_price()
+
     def set_min_output(self, p_min=None) -> None:
         """Each generator's must-run floor (G values in [0, max_generation] in the order of `generators`; None = all 0):
         min(p_min, cap[t]) <= P[t], a floor that follows an availability profile down; p_min = max_generation is a must-take unit.

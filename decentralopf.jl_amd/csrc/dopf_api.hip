@@ -950,13 +950,15 @@ int upload_agents(dopf_ctx *c, const Sorted &so)
         c->gen_ramp_h.resize(4 * G, std::nan(""));
         c->gen_budget_h.assign(so.gpm.begin(), so.gpm.end());
         c->gen_budget_h.resize(2 * G, 0.0);
-        c->gen_budget_h.resize(gen_budget_doubles(v.G), INFINITY);
+        c->gen_budget_h.resize(3 * G, INFINITY);
         double *blk = nullptr;
         d.raw(&blk, n);
         if (d.rc) return d.rc;
         HIPCHK(c, hipMemcpy(blk, c->gen_ramp_h.data(), 4 * G * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(blk + 4 * G, c->gen_budget_h.data() + G, 2 * G * sizeof(double), hipMemcpyHostToDevice));
         v.gen_pmax = blk;
+        // the budget prices of dopf_get_generator_budget_price behind the scratch: zeros until the first x-update
+        HIPCHK(c, hipMemset(c->gen_budget_price_d(), 0, G * sizeof(double)));
     } else if (c->plan.genRamp) {
         // DOPF_F_GEN_RAMP: the ramps (+inf), the anchor (NaN: none) and k_gen_ramp's scratch behind the capacities; the scratch is
         // sized from the knots' bound and is never read before it is written
@@ -983,8 +985,11 @@ int upload_agents(dopf_ctx *c, const Sorted &so)
         // DOPF_F2_GEN_ENERGY_BUDGET: the budgets behind the capacities, e_min (0) | e_max (+inf) until the setter
         c->gen_budget_h.assign(so.gpm.begin(), so.gpm.end());
         c->gen_budget_h.resize(2 * G, 0.0);
-        c->gen_budget_h.resize(gen_budget_doubles(v.G), INFINITY);
-        d.upload(&v.gen_pmax, c->gen_budget_h);
+        c->gen_budget_h.resize(3 * G, INFINITY);
+        // (the device block is the mirror and, behind it, the budget prices of dopf_get_generator_budget_price: zeros until the first x-update)
+        std::vector<double> blk(c->gen_budget_h);
+        blk.resize(gen_budget_doubles(v.G), 0.0);
+        d.upload(&v.gen_pmax, blk);
     } else {
         d.upload(&v.gen_pmax, so.gpm);
     }
@@ -1907,6 +1912,31 @@ int dopf_get_generator_min_output(dopf_ctx *c, double *p_min)
     if (!c) return DOPF_E_INVALID;
     if (!p_min) return c->v.G == 0 ? DOPF_OK : fail(c, DOPF_E_INVALID, "dopf_get_generator_min_output: p_min is NULL");
     for (int i = 0; i < c->v.G; ++i) p_min[c->gen_perm[i]] = c->gen_min_h.empty() ? 0.0 : c->gen_min_h[(size_t)i];
+    return DOPF_OK;
+}
+
+// the multipliers of the last computed x-update, as k_gen_budget<.., PR = true> / k_gen_ramp_budget stored them (sorted order on the device)
+int dopf_get_generator_budget_price(dopf_ctx *c, double *nu)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (!(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_get_generator_budget_price: the context was created without DOPF_F2_GEN_ENERGY_BUDGET");
+    const size_t G = (size_t)c->v.G;
+    if (G == 0) return DOPF_OK;
+    if (!nu) return fail(c, DOPF_E_INVALID, "dopf_get_generator_budget_price: nu is NULL");
+    DeviceGuard guard(c->device);
+    // the first call switches a budget context to the PR instantiations of k_gen_budget, which store the prices (the store costs
+    // time: DESIGN.md 5za): other kernels, so the iteration graphs are captured again at the next dopf_iterate, as after the first
+    // dopf_set_generator_min_output. The pair's kernel (DOPF_F2_GEN_RAMP_BUDGET) always stores: nothing to switch there
+    if (c->plan.genBudget && !c->plan.genRampBudget && !c->plan.genBudgetPrice) {
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        c->plan.genBudgetPrice = true;
+        drop_graphs(c);
+    }
+    std::vector<double> h(G);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->gen_budget_price_d(), G * sizeof(double), hipMemcpyDeviceToHost, c->main));
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    for (size_t i = 0; i < G; ++i) nu[c->gen_perm[i]] = h[i];
     return DOPF_OK;
 }
 

@@ -782,4 +782,12 @@ int dopf_multi_get_primal(dopf_multi *m, double *P, double *D, double *C, double
     return DOPF_OK;
 }
 
+int dopf_multi_get_generator_budget_price(dopf_multi *m, double *nu)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int i = 0; i < m->n; ++i)
+        if (const int rc = dopf_get_generator_budget_price(m->ctx[i], from(nu, m->g0[i]))) return shard_fail(m, i, rc);
+    return DOPF_OK;
+}
+
 }  // extern "C"

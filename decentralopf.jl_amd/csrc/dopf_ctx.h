@@ -67,6 +67,9 @@ struct dopf_ctx {
     char err[512] = {0};
     double *sto_slot_h(int slot) { return sto_h.data() + (size_t)slot * (size_t)v.S; }                  // a held slot of the mirror
     double sto_at(int slot, int i) const { return sto_h[(size_t)slot * (size_t)v.S + (size_t)i]; }      // ... and sorted storage i of it
+    // the context's budget prices on the device (dopf_internal.h: gen_budget_price(v, pair)): the layout comes from the plan here, so
+    // that no host caller states it by hand
+    double *gen_budget_price_d() const { return dopf::gen_budget_price(v, plan.genRampBudget); }
 };
 
 namespace dopf {

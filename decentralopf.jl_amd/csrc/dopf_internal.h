@@ -230,7 +230,9 @@ __host__ __device__ inline const double *gen_min_output(const DevView &v)
 // ... with DOPF_F2_GEN_ENERGY_BUDGET (never together with the ramps: plan_chain) behind the capacities, G doubles each in sorted order,
 // e_min (0 until dopf_set_generator_energy_budget) | e_max (+inf until then). k_gen_budget keeps nothing else: a searched row forms its
 // steps again from P, which it overwrites last (gen_budget.h)
-inline size_t gen_budget_doubles(int G) { return 3 * (size_t)G; }
+// ... and behind them the rows' budget prices price[G] (sorted order, zeros from dopf_create on): the multiplier the last
+// computed x-update put on each budget row, stored by k_gen_budget and read by dopf_get_generator_budget_price alone
+inline size_t gen_budget_doubles(int G) { return 4 * (size_t)G; }
 __host__ __device__ inline const double *gen_budget_min(const DevView &v) { return v.gen_pmax + v.G; }
 __host__ __device__ inline const double *gen_budget_max(const DevView &v) { return v.gen_pmax + 2 * (size_t)v.G; }
 // ... with DOPF_F2_GEN_RAMP_BUDGET (both at once, copper plates) the ramps keep their places and the budgets follow them:
@@ -240,11 +242,20 @@ __host__ __device__ inline const double *gen_budget_max(const DevView &v) { retu
 __host__ __device__ inline size_t ramp_budget_wave_doubles(int T) { return (size_t)T + 64 * ramp_row_doubles(T); }
 inline size_t gen_ramp_budget_doubles(int G, int T, int nGenItems)
 {
-    return 6 * (size_t)G + (size_t)nGenItems * kRampWaves * ramp_budget_wave_doubles(T);
+    return 7 * (size_t)G + (size_t)nGenItems * kRampWaves * ramp_budget_wave_doubles(T);
 }
 __host__ __device__ inline const double *gen_rb_min(const DevView &v) { return v.gen_pmax + 4 * (size_t)v.G; }
 __host__ __device__ inline const double *gen_rb_max(const DevView &v) { return v.gen_pmax + 5 * (size_t)v.G; }
 __host__ __device__ inline double *gen_rb_scratch(const DevView &v) { return const_cast<double *>(v.gen_pmax) + 6 * (size_t)v.G; }
+// The budget prices (dopf_get_generator_budget_price), G doubles behind what either layout held before them, so that every other
+// offset stays: behind e_max on a DOPF_F2_GEN_ENERGY_BUDGET context, behind the pair search's scratch on a DOPF_F2_GEN_RAMP_BUDGET
+// one (as p_min sits behind the ramp scratch). The view does not say which of the two it is: the kernels know (k_gen_ramp_budget:
+// pair = true), the host passes Plan::genRampBudget
+__host__ __device__ inline double *gen_budget_price(const DevView &v, bool pair)
+{
+    double *const blk = const_cast<double *>(v.gen_pmax);
+    return pair ? blk + 6 * (size_t)v.G + (size_t)v.nGenItems * kRampWaves * ramp_budget_wave_doubles(v.T) : blk + 3 * (size_t)v.G;
+}
 
 // The gen_state block (v.gen_state; gen_state_ints). DOPF_F_GEN_AVAILABILITY (the generator bodies' AV instantiations): cap[g,t] = gen_pmax[g] * f[t + T*k] with k = gen_prof(v)[g],
 // gen_pmax[g] for k = -1. gen_state has room for both behind its G row states: the G profile indices (sorted order, -1 until

@@ -66,6 +66,8 @@ struct Plan {
                                     // on the same chain — the ramp programme inside the budget's multiplier search
     bool genMinOut;                 // the MN instantiations of k_gen_ramp / k_gen_ramp_net. The one entry plan_chain never sets: no
                                     // flag asks for it — dopf_set_generator_min_output switches it on a genRamp context (and drops the graphs)
+    bool genBudgetPrice;            // the PR instantiations of k_gen_budget, which store the rows' budget prices. Like genMinOut never set by
+                                    // plan_chain: the first dopf_get_generator_budget_price switches it on a genBudget context (and drops the graphs)
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those

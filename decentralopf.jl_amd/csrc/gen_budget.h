@@ -16,6 +16,8 @@
 //     step is formed again at every candidate (the loads hit the cache the first pass filled): nothing is kept per timestep, no LDS
 //     and no scratch, at any T. A row whose search reaches kBudgetMaxEvals keeps its clamped step and counts in Status::solver_fail
 //     (dopf_iterate: DOPF_E_SOLVER);
+//     In the PR instantiations lane 0 stores the row's nu behind the budgets (gen_budget_price(v, false)): what
+//     dopf_get_generator_budget_price hands out;
 //  3. the item's sums from the stored rows, in k_gen_update's order with its tiling: the same bits whenever the rows are.
 #pragma once
 
@@ -110,7 +112,10 @@ __device__ __forceinline__ double budget_wave_sum(double x)
     return x;
 }
 
-template <bool LINES, bool AV, bool QC>
+// PR: lane 0 stores every row's multiplier for dopf_get_generator_budget_price. The store measured 0.75 us per iteration on config2
+// with default budgets, so it is an instantiation of its own, which a context runs from its first call of that entry on
+// (Plan::genBudgetPrice); the PR = false instantiations are the code of before
+template <bool LINES, bool AV, bool QC, bool PR>
 __global__ __launch_bounds__(512) void k_gen_budget(DevView v)
 {
     if (v.st->halt) return;
@@ -184,6 +189,12 @@ __global__ __launch_bounds__(512) void k_gen_budget(DevView v)
                 if (v.keepDeltas || v.walk_any[t]) v.dltG[(size_t)g * T + t] = pn - p0;
             }
         }
+        // PR: the row's budget price (dopf_get_generator_budget_price): 0.0 for a row with default budgets, one whose step at nu = 0
+        // keeps its budget and one whose search gave up, else nu*. Behind the row's store loop: in front of it the wait that opens
+        // the loop would cover the store's round trip. g is the wave's: a scalar index, no address registers per lane
+        if constexpr (PR) {
+            if (lane == 0) gen_budget_price(v, false)[__builtin_amdgcn_readfirstlane(g)] = nu;
+        }
     }
     __syncthreads();
 
@@ -231,8 +242,10 @@ void launch_gen_budget(const DevView &v, const Plan &p, hipStream_t s)
     with_bool(v.L > 0, [&](auto ln) {
         with_bool(p.genAvail, [&](auto av) {
             with_bool(p.genQuad, [&](auto qc) {
-                hipLaunchKernelGGL((k_gen_budget<decltype(ln)::value, decltype(av)::value, decltype(qc)::value>), dim3(v.nGenItems),
-                                   dim3(512), 0, s, v);
+                with_bool(p.genBudgetPrice, [&](auto pr) {
+                    hipLaunchKernelGGL((k_gen_budget<decltype(ln)::value, decltype(av)::value, decltype(qc)::value, decltype(pr)::value>),
+                                       dim3(v.nGenItems), dim3(512), 0, s, v);
+                });
             });
         });
     });

@@ -14,6 +14,8 @@
 //     y* and knots interleaved [slot][lane] in the wave's scratch — lanes at the same slot touch one line — sums and signatures
 //     travel by shuffles, and the search (ramp_budget_search) is the same on every lane. The row stored is the programme's own output
 //     at nu*, written by lane 0. A row whose search gives up keeps its step at nu = 0 and counts in Status::solver_fail.
+// Lane 0 stores the multiplier the storing branch put on the budget row behind the scratch (gen_budget_price(v, true)): 0 from 1 and
+// 3, nu* from 2 and 4, 0 where a search gave up.
 // Then the item's sums from the stored rows, in k_gen_update's order with its tiling: the same bits whenever the rows are.
 #pragma once
 
@@ -72,6 +74,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
     if constexpr (QC) c2v = gen_c2(v);
     const double *upv = gen_ramp_up(v), *dnv = gen_ramp_down(v), *pvv = gen_ramp_prev(v);
     const double *emin = gen_rb_min(v), *emax = gen_rb_max(v);
+    double *const nuv = gen_budget_price(v, true);
 
     // the wave's scratch: c[T] (read beyond kRampLdsT only) | the 64 lanes' work arrays, whose head serves ramp_repair beyond kRampLdsT
     double *wsc = gen_rb_scratch(v) + ((size_t)blockIdx.x * kRampWaves + wave) * ramp_budget_wave_doubles(T);
@@ -131,6 +134,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
         const bool bad0 = sweep(mc, true, !budgeted, phi0);
         const bool in0 = !budgeted || (phi0 >= elo && phi0 <= ehi);
         bool pair = false;
+        // the row's budget price (dopf_get_generator_budget_price): what the branch that stores the row put on its budget row
+        double rowNu = 0.0;
         if (!bad0 && in0) {
             if (budgeted) sweep(mc, false, true, phi0);         // 1. the clamped step
         } else if (!bad0) {
@@ -159,6 +164,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
                 sweep(mc, false, true, sum);                    // the clamped step stays in the row (it keeps the ramps)
             } else if (!sweep(mc + nu, false, false, sum)) {
                 sweep(mc + nu, false, true, sum);               // the relaxed problem's minimiser keeps the ramps: optimal
+                rowNu = nu;
             } else {
                 pair = true;
             }
@@ -190,6 +196,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
             bool ok = rc == 1;
             if (ok && lane == 0) ok = bt.run(nu, Prow);
             ok = __shfl((int)ok, 0) != 0;
+            if (ok) rowNu = nu;
             if (!ok) {
                 if (lane == 0) atomicAdd(&v.st->solver_fail, 1ull);
                 double sum;
@@ -197,6 +204,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
             }
             __threadfence_block();
         }
+        if (lane == 0) nuv[__builtin_amdgcn_readfirstlane(g)] = rowNu;       // (g is the wave's: a scalar index)
     }
     __syncthreads();
 

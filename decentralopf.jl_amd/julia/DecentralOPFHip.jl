@@ -445,6 +445,29 @@ function set_energy_budget!(admm::ADMM, e_min::Union{Nothing, Vector{Float64}}, 
 end
 
 """
+    budget_price(admm)
+
+The water values of the run (`dopf_get_generator_budget_price`; a multi-GPU ADMM: `dopf_multi_get_generator_budget_price`): `nu[g]`,
+the multiplier the last computed iteration put on generator g's energy budget, in the order of `generators` and the unit of the
+marginal costs — `> 0` where `e_max` holds the unit down, `< 0` where `e_min` pushes it up, `0` for a unit without a budget or with
+room in it. Recording starts with the FIRST call, which switches the generator kernel and returns zeros (a context with
+`DOPF_F2_GEN_RAMP_BUDGET` records from the start): call it once before iterating. Zeros before the first iteration; the setters leave the values alone. At convergence `-budget_dual` of
+`central_reference_coupled` where that dual is unique. The ADMM must have been created with `flags2 = DOPF_F2_GEN_ENERGY_BUDGET`.
+"""
+function budget_price(admm::ADMM)
+    out = zeros(Float64, length(admm.generators))
+    GC.@preserve out begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_get_generator_budget_price, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi,
+                                   pointer(out)), admm.multi)
+        else
+            dopf_check(ccall((:dopf_get_generator_budget_price, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, pointer(out)), admm.ctx)
+        end
+    end
+    return out
+end
+
+"""
     set_efficiency!(admm, eta_c, eta_d)
 
 The charge and discharge efficiency of each storage (`eta_c[s]`, `eta_d[s]` in `(0, 1]`, in the order of `storages`; `nothing`

@@ -146,6 +146,27 @@ class ShardedADMM:
         move). Needs F2_GEN_ENERGY_BUDGET in the second flag word; every rank calls it between the same two steps."""
         self.engine.set_energy_budget(self._mine(e_min, "gen"), self._mine(e_max, "gen"))
 
+    def budget_price(self, all_reduce: Optional[Callable[[np.ndarray], np.ndarray]] = None) -> np.ndarray:
+        """All generators' budget prices (problem.G values, global order): this rank's slice (dopf_get_generator_budget_price; the
+        price is local to the rank's agents) in a vector of zeros, summed over the ranks — every entry has one owner, so the sum
+        gathers. On the product path the sum is a torch.distributed all-reduce on the rank's device, and every rank must call; a host
+        library, or a caller that moves the data itself, passes all_reduce (vector -> the ranks' sum). One rank needs neither. As
+        Engine.budget_price: the first call starts the recording and returns zeros."""
+        a, b = self.shard.meta["gen_range"]
+        out = np.zeros(self.problem.G)
+        out[a:b] = self.engine.budget_price()
+        if all_reduce is not None:
+            return np.asarray(all_reduce(out), dtype=np.float64)
+        if self.world == 1:
+            return out
+        if self._tensor is None:
+            raise ValueError("a host library needs an all_reduce callable")
+        import torch
+        import torch.distributed as dist
+        t = torch.from_numpy(out).to(self._tensor.device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t.cpu().numpy()
+
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
         max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs

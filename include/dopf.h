@@ -532,6 +532,29 @@ int dopf_get_generator_min_output(dopf_ctx *ctx, double *p_min /* G */);
  * with this flag dopf_set_generator_availability repeats the last check under its new table. With G == 0 the call returns DOPF_OK
  * and does nothing. */
 int dopf_set_generator_energy_budget(dopf_ctx *ctx, const double *e_min /* G; NULL = 0 */, const double *e_max /* G; NULL = +inf */);
+/* The budget prices (water values) of the decentral run: nu[g] is the multiplier the last computed x-update put on
+ * generator g's budget row e_min[g] <= sum_t P[g,t] <= e_max[g] — the number the generator kernels add to gen_mc[g] to form the
+ * row, in the unit of gen_mc (cost per unit of energy). Sign convention: nu[g] > 0 where e_max held the row down, nu[g] < 0 where
+ * e_min pushed it up, and nu[g] = 0 for a row with default budgets, for a row whose step at nu = 0 kept its budget, and for a row
+ * whose search gave up (that row keeps its step at nu = 0 and counts in dopf_solver_failures). At a fixed point of the iteration
+ * the proximal and consensus terms vanish and the row's optimality system is the central LP's, so at convergence
+ * nu[g] = -budget_dual[g] of dopf_central_solve_coupled wherever the LP's dual is unique. G values in the caller's generator
+ * order. The call synchronises the context's stream and copies G doubles; it works while a trace is active, as the other getters
+ * do, and on contexts joined to a communicator or a peer exchange (the price is local to the rank's agents). Before the first
+ * iteration the values are zeros. Recording is opt-in on a context without DOPF_F2_GEN_RAMP_BUDGET: storing the prices costs its
+ * generator kernel time, so such a context records nothing until the FIRST call of this entry, which switches it
+ * to the price-storing instantiations of that kernel — other kernels, so the captured iteration graphs are dropped and captured
+ * again at the next dopf_iterate, the rule of the first dopf_set_generator_min_output — and returns what is stored: zeros. From the
+ * next computed x-update on every call returns that x-update's prices; there is no way back. A caller who wants prices calls the
+ * entry once after dopf_create_ex (dopf_multi: every shard is switched by dopf_multi_get_generator_budget_price); one who never
+ * calls it runs the kernels of before. A DOPF_F2_GEN_RAMP_BUDGET context records from its first iteration on, nothing is switched.
+ * The values are "of the last x-update": dopf_set_generator_energy_budget, dopf_set_state,
+ * dopf_set_demand, dopf_roll_horizon_coupled and the other setters leave them alone (after a roll they still describe the window
+ * before it), and so does a dopf_iterate on a halted context, whose launches compute nothing. The trace (dopf_trace_*) does not
+ * record the budget prices, and the multipliers of the ramp rows are not returned (on a DOPF_F2_GEN_RAMP_BUDGET context nu is the
+ * budget row's multiplier alone). DOPF_E_UNSUPPORTED without DOPF_F2_GEN_ENERGY_BUDGET; DOPF_E_INVALID for a NULL pointer with
+ * G > 0; with G == 0 the call returns DOPF_OK and does nothing. */
+int dopf_get_generator_budget_price(dopf_ctx *ctx, double *nu /* G */);
 
 /* ---- a receding horizon: the window's demand and the window itself change in place -------------------------------
  * Replace nothing in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62). Both need no flag, work
@@ -802,6 +825,8 @@ int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, c
 /* dopf_set_generator_min_output for all G generators, p_min in the caller's order (NULL as there): each shard gets its slice; every
  * shard is checked before any stores */
 int dopf_multi_set_generator_min_output(dopf_multi *m, const double *p_min);
+/* dopf_get_generator_budget_price of all shards' rows in the caller's order, like dopf_multi_get_primal: G values */
+int dopf_multi_get_generator_budget_price(dopf_multi *m, double *nu /* G */);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);

@@ -6,6 +6,8 @@ shape, the settings below in ONE process, each timed as the device-side span of 
   (c) the flag with every tenth row held to 60 % of the energy it delivers in (a)'s settled state, so that its budget binds; with it
       the share of rows whose clamped step breaks the budget in the iteration behind the timed ones (formed on the host from the state:
       those rows ran the search);
+  (e) as (b), (f) as (c), with the budget prices recorded: dopf_get_generator_budget_price called once before the first iteration, which
+      switches the context to the price-storing instantiations of k_gen_budget (DESIGN.md 5za); (b) and (c) never call it;
   (d) no flag at all — the default chain (fused launch, one-launch tail): (a) against (d) is what the chain costs.
 (b) against (a) is the cost of the feature's kernel on rows that need no search, (c) against (a) with a tenth of the rows searched. No
 threshold is fixed in advance.
@@ -27,10 +29,13 @@ pp = bench.make_problem(synth, wl)
 A = pp.G + pp.S
 APART = _capi.F_NO_FUSE | _capi.F_NO_TAIL_FUSE
 BUDGET = getattr(_capi, "F2_GEN_ENERGY_BUDGET", 0)
-runs = {"(a) flagless, launches apart": (APART, 0, False), "(d) flagless, default chain": (0, 0, False)}
+runs = {"(a) flagless, launches apart": (APART, 0, False, False), "(d) flagless, default chain": (0, 0, False, False)}
 if BUDGET:      # (the parent commit has no such flag: there the script reports (a) and (d) alone)
-    runs["(b) default budgets"] = (0, BUDGET, False)
-    runs["(c) a tenth of the rows bind"] = (0, BUDGET, True)
+    runs["(b) default budgets"] = (0, BUDGET, False, False)
+    runs["(c) a tenth of the rows bind"] = (0, BUDGET, True, False)
+    if hasattr(_capi.Engine, "budget_price"):
+        runs["(e) (b) with prices recorded"] = (0, BUDGET, False, True)
+        runs["(f) (c) with prices recorded"] = (0, BUDGET, True, True)
 
 
 def searched(e, hi):
@@ -46,7 +51,7 @@ def searched(e, hi):
 api = _capi.hip_api()
 res, share, energy, fails = {}, [], None, 0
 for rnd in range(rounds):
-    for name, (flags, flags2, bind) in runs.items():
+    for name, (flags, flags2, bind, price) in runs.items():
         kw = dict(flags2=flags2) if flags2 else {}
         e = _capi.Engine(api, params=_capi.default_params(gamma=1.0 / A, eps=0.0, flags=flags | _capi.F_TIME_CALLS), **kw, **pp.engine_kwargs())
         hi = None
@@ -54,6 +59,8 @@ for rnd in range(rounds):
             hi = np.full(pp.G, np.inf)
             hi[::10] = 0.6 * energy[::10]
             e.set_energy_budget(None, hi)
+        if price:
+            e.budget_price()
         e.iterate(200)                               # settle (row summaries, warm starts)
         e.iterate(400)
         res.setdefault(name, []).append(1000.0 * e.last_call_ms() / 400)

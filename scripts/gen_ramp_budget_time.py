@@ -36,7 +36,8 @@ if PAIR:      # (the commit before has no such flag: there the script reports (a
 
 def scratch_bytes():
     """plan_chain's generator items on a one-node plate (2048 wanted, whole tiles of 512 / min(T, 512) rows), 8 waves each, T centres
-    and 64 x (5T + 4) work doubles per wave, behind the 6 G doubles of capacities, ramps, anchor and budgets"""
+    and 64 x (5T + 4) work doubles per wave, behind the 6 G doubles of capacities, ramps, anchor and budgets (the G budget prices
+    behind the scratch are not counted)"""
     R = 512 // min(pp.T, 512)
     chunk = -(-max(R, -(-pp.G // 2048)) // R) * R
     items = -(-pp.G // chunk)
