@@ -165,6 +165,9 @@ class CApi:
         # the budget rows' multipliers of the last x-update (Engine.budget_price, MultiEngine.budget_price)
         self._opt("get_generator_budget_price", C.c_int, [ctxp, c_double_p])
         self._opt("multi_get_generator_budget_price", C.c_int, [ctxp, c_double_p])
+        # the ramp rows' multipliers of the last x-update (Engine.ramp_price, MultiEngine.ramp_price)
+        self._opt("get_generator_ramp_price", C.c_int, [ctxp, c_double_p])
+        self._opt("multi_get_generator_ramp_price", C.c_int, [ctxp, c_double_p])
         if prefix == "dopf_":
             self._sig("bind_consensus", C.c_int, [ctxp, C.c_void_p])
             self._sig("solver_failures", C.c_int64, [ctxp])
@@ -794,6 +797,21 @@ class Engine(_ExtensionSetters):
         self._chk(self.api.get_generator_budget_price(self._ctx, _dp(out)))
         return out
 
+    def ramp_price(self) -> np.ndarray:
+        """dopf_get_generator_ramp_price: rp[g, t], the multiplier the last computed x-update put on generator g's ramp row between
+        t-1 and t (t = 0: the anchor's row, 0 without an anchor), (G, T) in the unit of gen_mc: > 0 where ramp-up held the unit
+        back, < 0 where ramp-down held it up, 0 for a row whose clamped step kept its ramps and for one whose pair search gave up.
+        Recording is opt-in: the FIRST call allocates the array on the device, switches the context to the kernels that store the
+        prices (graphs are captured again) and returns zeros; call it once after the constructor, then every call returns the last
+        iteration's prices. Zeros before the first iteration; the setters leave it alone. At convergence -ramp_dual of
+        central_solve_coupled where that dual is unique. Needs F_GEN_RAMP on a copper plate (DopfError, unsupported, without the
+        flag and with lines: network rows are not priced); a backend without the entry: DopfError."""
+        if not hasattr(self.api, "get_generator_ramp_price"):
+            raise DopfError(f"{self.api.prefix}*: this API has no get_generator_ramp_price")
+        out = np.zeros(self.G * self.T)
+        self._chk(self.api.get_generator_ramp_price(self._ctx, _dp(out)))
+        return out.reshape(self.G, self.T)
+
     # -- a receding horizon --------------------------------------------------------------------
     def demand(self) -> np.ndarray:
         """The context's demand as it stands, (N, T)."""
@@ -1167,6 +1185,14 @@ class MultiEngine(_ExtensionSetters):
         out = np.zeros(self.G)
         self._chk(self.api.multi_get_generator_budget_price(self._m, _dp(out)))
         return out
+
+    def ramp_price(self) -> np.ndarray:
+        """dopf_multi_get_generator_ramp_price: Engine.ramp_price for all shards' rows in the caller's order, (G, T)."""
+        if not hasattr(self.api, "multi_get_generator_ramp_price"):
+            raise DopfError(f"{self.api.prefix}*: this API has no multi_get_generator_ramp_price")
+        out = np.zeros(self.G * self.T)
+        self._chk(self.api.multi_get_generator_ramp_price(self._m, _dp(out)))
+        return out.reshape(self.G, self.T)
 
     def shard(self, i: int = 0) -> Engine:
         """Engine view of shard i's context (getters for the replicated state; do not iterate it directly)."""

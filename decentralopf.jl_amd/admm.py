@@ -215,6 +215,16 @@ class ADMM:
         (_capi.central_solve_coupled's budget_dual) where that dual is unique. Needs F2_GEN_ENERGY_BUDGET, as set_energy_budget."""
         return self.engine.budget_price()
 
+    def ramp_price(self) -> np.ndarray:
+        """The ramp prices of the run: rp[g, t], the multiplier the last computed iteration put on generator g's ramp row between t-1
+        and t (t = 0: the row against the anchor), (G, T) in the order of `generators` and the unit of marginal_cost — what one more
+        unit per step of flexibility of g is worth at t: > 0 where ramp_up holds the unit back, < 0 where ramp_down holds it up, 0
+        where no ramp binds. Not in the reference. Recording starts with the FIRST call (it switches the generator kernel and
+        returns zeros): call it once before iterating. Zeros before the first iteration; the setters leave the values alone until
+        the next iteration. At convergence minus the ramp dual of the central LP (_capi.central_solve_coupled's ramp_dual) where
+        that dual is unique. Needs F_GEN_RAMP on a copper plate, as set_ramp."""
+        return self.engine.ramp_price()
+
     def set_min_output(self, p_min=None) -> None:
         """Each generator's must-run floor (G values in [0, max_generation] in the order of `generators`; None = all 0):
         min(p_min, cap[t]) <= P[t], a floor that follows an availability profile down; p_min = max_generation is a must-take unit.

@@ -1940,6 +1940,49 @@ int dopf_get_generator_budget_price(dopf_ctx *c, double *nu)
     return DOPF_OK;
 }
 
+// the ramp rows' multipliers of the last computed x-update, as k_gen_ramp<.., RP = true> / k_gen_ramp_budget<.., RP = true> stored
+// them (sorted order on the device, T per row); the array is the context's own, allocated by the first call
+int dopf_get_generator_ramp_price(dopf_ctx *c, double *rp)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (!(c->q.flags & DOPF_F_GEN_RAMP))
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_get_generator_ramp_price: the context was created without DOPF_F_GEN_RAMP");
+    if (c->v.L > 0)
+        return fail(c, DOPF_E_UNSUPPORTED, "dopf_get_generator_ramp_price: network rows are not priced (k_gen_ramp_net keeps no centre, and a "
+                                           "row's gradient there needs the node's table); L = %d", c->v.L);
+    const size_t G = (size_t)c->v.G, T = (size_t)c->v.T;
+    if (G == 0) return DOPF_OK;
+    if (!rp) return fail(c, DOPF_E_INVALID, "dopf_get_generator_ramp_price: rp is NULL");
+    DeviceGuard guard(c->device);
+    // the first call: the array, zeroed, and the RP instantiations of the context's generator kernel — other kernels, so the iteration
+    // graphs are captured again at the next dopf_iterate, as after the first dopf_set_generator_min_output. No way back
+    if (!c->plan.genRampPrice) {
+        const unsigned long long need = (unsigned long long)G * T * sizeof(double);
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        size_t freeb = 0, totalb = 0;
+        HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
+        void *p = nullptr;
+        hipError_t e = need > freeb ? hipErrorOutOfMemory : hipMalloc(&p, need);
+        if (e == hipSuccess) {
+            c->allocs.push_back(p);
+            e = hipMemset(p, 0, need);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, e == hipErrorOutOfMemory ? DOPF_E_NOMEM : DOPF_E_DEVICE,
+                        "dopf_get_generator_ramp_price: the ramp prices (T x G doubles) need %llu bytes, the device has %llu free: %s", need,
+                        (unsigned long long)freeb, hipGetErrorString(e));
+        }
+        c->plan.genRampPrice = (double *)p;
+        drop_graphs(c);
+    }
+    std::vector<double> h(G * T);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->plan.genRampPrice, G * T * sizeof(double), hipMemcpyDeviceToHost, c->main));
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    for (size_t i = 0; i < G; ++i) std::copy(h.begin() + i * T, h.begin() + (i + 1) * T, rp + (size_t)c->gen_perm[i] * T);
+    return DOPF_OK;
+}
+
 int dopf_set_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max)
 {
     if (!c) return DOPF_E_INVALID;

@@ -790,4 +790,14 @@ int dopf_multi_get_generator_budget_price(dopf_multi *m, double *nu)
     return DOPF_OK;
 }
 
+// (rows are T long: shard i's slice begins at row g0[i])
+int dopf_multi_get_generator_ramp_price(dopf_multi *m, double *rp)
+{
+    if (!m) return DOPF_E_INVALID;
+    const size_t T = (size_t)m->T;
+    for (int i = 0; i < m->n; ++i)
+        if (const int rc = dopf_get_generator_ramp_price(m->ctx[i], from(rp, T * m->g0[i]))) return shard_fail(m, i, rc);
+    return DOPF_OK;
+}
+
 }  // extern "C"

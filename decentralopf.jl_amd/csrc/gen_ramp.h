@@ -15,7 +15,24 @@
 //  3. the item's sums from the stored rows, in k_gen_update's order with k_gen_update's tiling: the same bits whenever the rows are.
 #pragma once
 
+#include "ramp_price.h"
+
 namespace dopf {
+
+// the box of step t as ramp_price (ramp_price.h) takes it: cap_t, and the floor fmin(p_min, cap_t) (MN) or 0
+template <bool AV>
+struct RampCap {
+    const double *ftab;
+    double pm;
+    int T, prof;
+    __device__ __forceinline__ double operator()(int t) const { return AV ? avail_cap(ftab, T, prof, pm, t) : pm; }
+};
+template <bool AV, bool MN>
+struct RampFloor {
+    RampCap<AV> cap;
+    double pmn;
+    __device__ __forceinline__ double operator()(int t) const { return MN ? fmin(pmn, cap(t)) : 0.0; }
+};
 
 // h'(x) between two knots (xa <= x <= xb); equal values need no slope (and no finite xb - xa)
 __device__ __forceinline__ double ramp_interp(double xa, double va, double xb, double vb, double x)
@@ -99,9 +116,13 @@ __device__ __forceinline__ void ramp_repair(double *Prow, double *cy, double *kx
 }
 
 // MN: the rows' floors (gen_min_output(v)) are read and the box is [fmin(p_min, cap), cap]; the MN = false instantiations are the
-// kernels of the contexts that never set a floor
-template <bool AV, bool QC, bool MN>
-__global__ __launch_bounds__(512) void k_gen_ramp(DevView v)
+// kernels of the contexts that never set a floor.
+// RP (dopf_get_generator_ramp_price): the rows' ramp multipliers go into rpv, T doubles per row in sorted order — zeros
+// for a row that needs no repair (lanes over t: whole lines); for a repaired row the wave copies its centres there before ramp_repair
+// overwrites them, and lane 0 runs ramp_price behind the repair, in place over them, its intervals in the row's kx / kv, which are
+// free by then. RP = false (rpv unused) is the code of before: what a context runs until its first call of that entry
+template <bool AV, bool QC, bool MN, bool RP>
+__global__ __launch_bounds__(512) void k_gen_ramp(DevView v, double *rpv)
 {
     if (v.st->halt) return;
     constexpr int NK = 2 * kRampLdsT + 2;
@@ -166,7 +187,23 @@ __global__ __launch_bounds__(512) void k_gen_ramp(DevView v)
             }
             left = __shfl(pn, 63);
         }
-        if (__any(bad)) {
+        if constexpr (RP) {
+            double *rrow = rpv + (size_t)g * T;
+            if (__any(bad)) {
+                __threadfence_block();              // the wave's c_t, before the wave reads them
+                for (int t = lane; t < T; t += 64) rrow[t] = cy[t];
+                __threadfence_block();              // ... and their copy, before lane 0 does
+                if (lane == 0) {
+                    ramp_repair<AV, MN>(Prow, cy, kx, kv, T, (w + gam) + c2, fmin(up, pm), fmin(dn, pm), prev, pm, ftab, pr, pmn);
+                    // the stored ramps: an infinite one is never tight. T <= kRampLdsT or the scratch's 2T + 2: room for T intervals
+                    const RampCap<AV> cap{ftab, pm, T, pr};
+                    ramp_price(Prow, rrow, 0.0, (w + gam) + c2, RampFloor<AV, MN>{cap, pmn}, cap, T, up, dn, prev, pm, kx, kv, rrow);
+                }
+                __threadfence_block();
+            } else {
+                for (int t = lane; t < T; t += 64) rrow[t] = 0.0;
+            }
+        } else if (__any(bad)) {
             __threadfence_block();                  // the wave's c_t, before lane 0 reads them
             if (lane == 0)
                 ramp_repair<AV, MN>(Prow, cy, kx, kv, T, (w + gam) + c2, fmin(up, pm), fmin(dn, pm), prev, pm, ftab, pr, pmn);
@@ -218,8 +255,10 @@ void launch_gen_ramp(const DevView &v, const Plan &p, hipStream_t s)
     with_bool(p.genAvail, [&](auto av) {
         with_bool(p.genQuad, [&](auto qc) {
             with_bool(p.genMinOut, [&](auto mn) {
-                hipLaunchKernelGGL((k_gen_ramp<decltype(av)::value, decltype(qc)::value, decltype(mn)::value>), dim3(v.nGenItems), dim3(512),
-                                   0, s, v);
+                with_bool(p.genRampPrice != nullptr, [&](auto rp) {
+                    hipLaunchKernelGGL((k_gen_ramp<decltype(av)::value, decltype(qc)::value, decltype(mn)::value, decltype(rp)::value>),
+                                       dim3(v.nGenItems), dim3(512), 0, s, v, p.genRampPrice);
+                });
             });
         });
     });

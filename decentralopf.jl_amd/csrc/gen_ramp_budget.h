@@ -55,8 +55,12 @@ struct RampBudgetBatch {
     }
 };
 
-template <bool AV, bool QC>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k_gen_ramp_budget(DevView v)
+// RP (dopf_get_generator_ramp_price): the rows' ramp multipliers go into rpv, T doubles per row in sorted order. By
+// branch: 1 and 2 (the ramps kept) zeros; 3 where its sum keeps the budget: ramp_price of the repaired row (shift 0); 4: ramp_price of
+// the programme's row under its nu (shift = nu / q), zeros where the search gave up. cs keeps the centres, the row's kx / kv are free
+// behind the repair and behind bt.run. RP = false (rpv unused) is the code of before
+template <bool AV, bool QC, bool RP>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k_gen_ramp_budget(DevView v, double *rpv)
 {
     if (v.st->halt) return;
     constexpr int NK = 2 * kRampLdsT + 2;
@@ -136,6 +140,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
         bool pair = false;
         // the row's budget price (dopf_get_generator_budget_price): what the branch that stores the row put on its budget row
         double rowNu = 0.0;
+        // RP: the shift of the centres under which the stored row is a ramp projection (NaN: its ramps were kept, or its search gave up)
+        double rpShift = __builtin_nan("");
         if (!bad0 && in0) {
             if (budgeted) sweep(mc, false, true, phi0);         // 1. the clamped step
         } else if (!bad0) {
@@ -181,6 +187,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
                 phi0 = budget_wave_sum(part);
                 pair = !(phi0 >= elo && phi0 <= ehi);
             }
+            if constexpr (RP) { if (!pair) rpShift = 0.0; }
         }
         if (pair) {
             // 4. the pair search: phi0 is the sum of the step at nu = 0, which breaks the budget
@@ -197,6 +204,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
             if (ok && lane == 0) ok = bt.run(nu, Prow);
             ok = __shfl((int)ok, 0) != 0;
             if (ok) rowNu = nu;
+            if constexpr (RP) { if (ok) rpShift = nu / q; }
             if (!ok) {
                 if (lane == 0) atomicAdd(&v.st->solver_fail, 1ull);
                 double sum;
@@ -205,6 +213,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
             __threadfence_block();
         }
         if (lane == 0) nuv[__builtin_amdgcn_readfirstlane(g)] = rowNu;       // (g is the wave's: a scalar index)
+        if constexpr (RP) {
+            double *rrow = rpv + (size_t)__builtin_amdgcn_readfirstlane(g) * T;
+            if (rpShift == rpShift) {
+                // (the stored ramps: an infinite one is never tight; no floors on a budget context)
+                const RampCap<AV> cap{ftab, pm, T, pr};
+                if (lane == 0)
+                    ramp_price(Prow, cs, rpShift, (w + gam) + c2, RampFloor<AV, false>{cap, 0.0}, cap, T, up, dn, prev, pm, kx, kv, rrow);
+            } else {
+                for (int t = lane; t < T; t += 64) rrow[t] = 0.0;
+            }
+        }
     }
     __syncthreads();
 
@@ -250,7 +269,10 @@ void launch_gen_ramp_budget(const DevView &v, const Plan &p, hipStream_t s)
     if (v.nGenItems == 0) return;
     with_bool(p.genAvail, [&](auto av) {
         with_bool(p.genQuad, [&](auto qc) {
-            hipLaunchKernelGGL((k_gen_ramp_budget<decltype(av)::value, decltype(qc)::value>), dim3(v.nGenItems), dim3(512), 0, s, v);
+            with_bool(p.genRampPrice != nullptr, [&](auto rp) {
+                hipLaunchKernelGGL((k_gen_ramp_budget<decltype(av)::value, decltype(qc)::value, decltype(rp)::value>), dim3(v.nGenItems),
+                                   dim3(512), 0, s, v, p.genRampPrice);
+            });
         });
     });
 }

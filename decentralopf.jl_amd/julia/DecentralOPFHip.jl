@@ -468,6 +468,32 @@ function budget_price(admm::ADMM)
 end
 
 """
+    ramp_price(admm)
+
+The ramp prices of the run (`dopf_get_generator_ramp_price`; a multi-GPU ADMM: `dopf_multi_get_generator_ramp_price`): a `G x T`
+matrix, `rp[g, t]` the multiplier the last computed iteration put on generator g's ramp row between `t-1` and `t` (the first column:
+the row against the anchor `p_prev`, `0` without one), in the order of `generators` and the unit of the marginal costs — `> 0` where
+`ramp_up` holds the unit back, `< 0` where `ramp_down` holds it up, `0` where no ramp binds. Recording starts with the FIRST call,
+which switches the generator kernel and returns zeros: call it once before iterating. Zeros before the first iteration; the setters
+leave the values alone. At convergence `-ramp_dual` of `central_reference_coupled` where that dual is unique. The ADMM must have been
+created with `DOPF_F_GEN_RAMP` on a copper plate (network rows are not priced).
+"""
+function ramp_price(admm::ADMM)
+    G = length(admm.generators)
+    T = length(admm.T)
+    out = zeros(Float64, T * G)
+    GC.@preserve out begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_get_generator_ramp_price, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi,
+                                   pointer(out)), admm.multi)
+        else
+            dopf_check(ccall((:dopf_get_generator_ramp_price, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, pointer(out)), admm.ctx)
+        end
+    end
+    return permutedims(reshape(out, T, G))
+end
+
+"""
     set_efficiency!(admm, eta_c, eta_d)
 
 The charge and discharge efficiency of each storage (`eta_c[s]`, `eta_d[s]` in `(0, 1]`, in the order of `storages`; `nothing`

@@ -167,6 +167,27 @@ class ShardedADMM:
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         return t.cpu().numpy()
 
+    def ramp_price(self, all_reduce: Optional[Callable[[np.ndarray], np.ndarray]] = None) -> np.ndarray:
+        """All generators' ramp prices ((problem.G, T), global order): this rank's rows (dopf_get_generator_ramp_price; the price is
+        local to the rank's rows) in an array of zeros, summed over the ranks — every entry has one owner, so the sum gathers — as
+        budget_price does: torch.distributed on the product path (every rank must call), a caller's all_reduce (array -> the ranks'
+        sum) otherwise; one rank needs neither. As Engine.ramp_price: the first call starts the recording and returns zeros."""
+        a, b = self.shard.meta["gen_range"]
+        mine = np.asarray(self.engine.ramp_price(), dtype=np.float64)
+        out = np.zeros((self.problem.G, mine.shape[1]))
+        out[a:b] = mine
+        if all_reduce is not None:
+            return np.asarray(all_reduce(out), dtype=np.float64)
+        if self.world == 1:
+            return out
+        if self._tensor is None:
+            raise ValueError("a host library needs an all_reduce callable")
+        import torch
+        import torch.distributed as dist
+        t = torch.from_numpy(out).to(self._tensor.device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t.cpu().numpy()
+
     def set_availability(self, profiles=None, profile_of=None) -> None:
         """The generators' availability (K x T profiles, problem.G indices in global order; both None = every generator at
         max_generation): this rank sets the whole table and its slice of the indices (dopf_set_generator_availability). Needs

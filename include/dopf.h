@@ -555,6 +555,32 @@ int dopf_set_generator_energy_budget(dopf_ctx *ctx, const double *e_min /* G; NU
  * budget row's multiplier alone). DOPF_E_UNSUPPORTED without DOPF_F2_GEN_ENERGY_BUDGET; DOPF_E_INVALID for a NULL pointer with
  * G > 0; with G == 0 the call returns DOPF_OK and does nothing. */
 int dopf_get_generator_budget_price(dopf_ctx *ctx, double *nu /* G */);
+/* The ramp prices of the decentral run: rp[t + T*g] is the multiplier the last computed x-update put on generator
+ * g's ramp row -ramp_down <= P[g,t] - P[g,t-1] <= ramp_up between t-1 and t (t = 0: the anchor's row against p_prev, 0 without an
+ * anchor) — what one more unit per step of flexibility of unit g is worth at step t, in the unit of gen_mc, in the caller's
+ * generator order. Sign convention: rp > 0 where ramp-up held the unit back, rp < 0 where ramp-down held it up; rp = 0 for a row
+ * whose clamped step kept its ramps and for a row whose pair search gave up (dopf_solver_failures). Where a row's multipliers are
+ * not unique (a step on a box end and a ramp reach at once) the vector nearest 0, step by step from the horizon's end, is returned.
+ * The values are read off the stored row and its centres (csrc/ramp_price.h), not off the programme that repaired it. At a fixed
+ * point of the iteration the proximal and consensus terms vanish and the row's optimality system is the central LP's, so at
+ * convergence rp = -ramp_dual of dopf_central_solve_coupled wherever the LP's dual is unique: the sign rule of the budget price. On
+ * a DOPF_F2_GEN_RAMP_BUDGET context it is the ramp rows' multiplier under that row's nu (dopf_get_generator_budget_price). The
+ * floors of dopf_set_generator_min_output are the lower ends of the boxes the values are formed with.
+ * Recording is opt-in: the FIRST call of this entry allocates T*G doubles of the context's own on the device and zeroes them
+ * (DOPF_E_NOMEM, naming the bytes, where they do not fit), switches the context to the price-recording instantiations of its
+ * generator kernel — other kernels, so the call synchronises the context's stream and the captured iteration graphs are dropped and
+ * captured again at the next dopf_iterate, the rule of the first dopf_set_generator_min_output — and returns what is stored: zeros.
+ * From the next computed x-update on every call returns that x-update's prices; there is no way back, and a floor set afterwards
+ * keeps the context recording. A context that never calls the entry runs the kernels of before (dopf_multi: every shard is
+ * switched by dopf_multi_get_generator_ramp_price). The values are "of the last x-update": dopf_set_generator_ramp,
+ * dopf_set_generator_min_output, dopf_set_state, dopf_set_demand, dopf_roll_horizon_coupled and the other setters leave them alone
+ * (after a roll they still describe the window before it), and so does a dopf_iterate on a halted context, whose launches compute
+ * nothing. Before the first iteration the values are zeros. The call copies T*G doubles; it works while a trace is active (the
+ * trace does not record the ramp prices) and on contexts joined to a communicator or a peer exchange (the price is local to the
+ * rank's rows). DOPF_E_UNSUPPORTED without DOPF_F_GEN_RAMP, and with L > 0: network rows are not priced (k_gen_ramp_net keeps no
+ * centre, and a row's gradient there needs the node's table). DOPF_E_INVALID for a NULL pointer with G > 0; with G == 0 the call
+ * returns DOPF_OK and does nothing. */
+int dopf_get_generator_ramp_price(dopf_ctx *ctx, double *rp /* T*G, [t + T*g] */);
 
 /* ---- a receding horizon: the window's demand and the window itself change in place -------------------------------
  * Replace nothing in the reference, which builds a new ADMM(...) per window (src/structures/admm.jl:23-62). Both need no flag, work
@@ -827,6 +853,8 @@ int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, c
 int dopf_multi_set_generator_min_output(dopf_multi *m, const double *p_min);
 /* dopf_get_generator_budget_price of all shards' rows in the caller's order, like dopf_multi_get_primal: G values */
 int dopf_multi_get_generator_budget_price(dopf_multi *m, double *nu /* G */);
+/* dopf_get_generator_ramp_price of all shards' rows in the caller's order, like dopf_multi_get_primal: T*G values */
+int dopf_multi_get_generator_ramp_price(dopf_multi *m, double *rp /* T*G, [t + T*g] */);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
  * shard 0 with the dopf_get_* calls above. */
 dopf_ctx *dopf_multi_ctx(dopf_multi *m, int32_t i);
