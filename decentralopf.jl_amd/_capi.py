@@ -165,6 +165,13 @@ class CApi:
         # the budget rows' multipliers of the last x-update (Engine.budget_price, MultiEngine.budget_price)
         self._opt("get_generator_budget_price", C.c_int, [ctxp, c_double_p])
         self._opt("multi_get_generator_budget_price", C.c_int, [ctxp, c_double_p])
+        # budgets per sub-window (Engine.set_energy_budget_windows, .energy_budget_windows, .budget_window_price and MultiEngine's): no
+        # flag of their own, so they travel beside the extension tables, as the price getters do
+        self._opt("set_generator_energy_budget_windows", C.c_int, [ctxp, C.c_int32, c_int32_p, c_double_p, c_double_p])
+        self._opt("get_generator_energy_budget_windows", C.c_int, [ctxp, c_int32_p, c_int32_p, c_double_p, c_double_p])
+        self._opt("get_generator_budget_window_price", C.c_int, [ctxp, c_double_p])
+        self._opt("multi_set_generator_energy_budget_windows", C.c_int, [ctxp, C.c_int32, c_int32_p, c_double_p, c_double_p])
+        self._opt("multi_get_generator_budget_window_price", C.c_int, [ctxp, c_double_p])
         # the ramp rows' multipliers of the last x-update (Engine.ramp_price, MultiEngine.ramp_price)
         self._opt("get_generator_ramp_price", C.c_int, [ctxp, c_double_p])
         self._opt("multi_get_generator_ramp_price", C.c_int, [ctxp, c_double_p])
@@ -537,6 +544,39 @@ class _ExtensionSetters:
         for x, arrays in todo:
             getattr(self, x.setter)(*arrays)
 
+    def set_energy_budget_windows(self, win_end=None, e_min=None, e_max=None):
+        """dopf_set_generator_energy_budget_windows (MultiEngine: dopf_multi_...): one energy budget per generator and sub-window of
+        the horizon. win_end: the windows' ends (strictly increasing, the last one T; window j covers win_end[j-1] <= t < win_end[j]);
+        e_min / e_max: (G, n_win) in the caller's generator order (None = all 0 / all inf). win_end None removes the table. Needs
+        F2_GEN_ENERGY_BUDGET without F2_GEN_RAMP_BUDGET, and no whole-horizon budget stored (set_energy_budget(None, None) first). P, D,
+        C, the duals and the iteration counter stay; converged becomes False. While a table is set, set_energy_budget with an array,
+        budget_price and roll are refused (DopfError). A backend without the entry: DopfError."""
+        name = self._entry_prefix + "set_generator_energy_budget_windows"
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise DopfError(f"{self.api.prefix}*: this API has no {name}")
+        if win_end is None:
+            if e_min is not None or e_max is not None:
+                raise ValueError("set_energy_budget_windows: budgets without win_end")
+            self._chk(fn(self._handle(), 0, None, None, None))
+            self._mirror.pop("gen_budget_windows", None)
+            return
+        ends = np.ascontiguousarray(np.asarray(win_end, dtype=np.int32).reshape(-1))
+        n = self.G * ends.size
+        lo = None if e_min is None else _f64(np.asarray(e_min, dtype=np.float64).reshape(self.G, ends.size), n)
+        hi = None if e_max is None else _f64(np.asarray(e_max, dtype=np.float64).reshape(self.G, ends.size), n)
+        self._chk(fn(self._handle(), int(ends.size), ends.ctypes.data_as(c_int32_p), _dp(lo), _dp(hi)))
+        self._mirror["gen_budget_windows"] = (ends.copy(), None if lo is None else lo.reshape(self.G, ends.size).copy(),
+                                              None if hi is None else hi.reshape(self.G, ends.size).copy())
+
+    def _budget_window_price(self, handle, n_win: int) -> np.ndarray:
+        name = self._entry_prefix + "get_generator_budget_window_price"
+        if not hasattr(self.api, name):
+            raise DopfError(f"{self.api.prefix}*: this API has no {name}")
+        out = np.zeros(self.G * max(n_win, 1))
+        self._chk(getattr(self.api, name)(handle, _dp(out)))
+        return out[:self.G * n_win].reshape(self.G, n_win)
+
 
 class Engine(_ExtensionSetters):
     """A context of the C ABI with numpy in/out. Mirrors include/dopf.h one to one.
@@ -556,13 +596,15 @@ class Engine(_ExtensionSetters):
     dopf_set_generator_energy_budget (after the availability too). flags2 (optional): further bits of that word, as Engine.roll passes
     them to the context it rebuilds; on an API without create_ex a non-zero word is a DopfError. gen_min_output (optional, G values in
     [0, gen_pmax]): the generators' must-run floors — sets F_GEN_RAMP (on a network F_GEN_RAMP_NETWORK too: the floors run on the ramp
-    kernels) and calls dopf_set_generator_min_output behind the ramps; all zeros is what None says."""
+    kernels) and calls dopf_set_generator_min_output behind the ramps; all zeros is what None says. gen_budget_windows = (win_end,
+    e_min, e_max) (optional; (G, n_win) budgets, either may be None): energy budgets per sub-window — sets F2_GEN_ENERGY_BUDGET and calls
+    dopf_set_generator_energy_budget_windows behind everything else."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
                  mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
                  sto_eta=None, line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0,
-                 gen_min_output=None):
+                 gen_min_output=None, gen_budget_windows=None):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
@@ -572,7 +614,8 @@ class Engine(_ExtensionSetters):
             sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget,
             gen_min_output=gen_min_output))
         self.params = params if params is not None else default_params()
-        self.flags2 = int(flags2) | _flags2(todo, self.L)
+        # (a table of budgets per sub-window runs on a budget context: it asks for the budgets' flag)
+        self.flags2 = int(flags2) | _flags2(todo, self.L) | (F2_GEN_ENERGY_BUDGET if gen_budget_windows is not None else 0)
         _needs_create_ex(api, self.flags2)
         # what a window change needs of the problem: the arrays as handed to create, and the inputs of the setters as they stand
         # (by constructor keyword, in the form the constructor takes them)
@@ -589,6 +632,8 @@ class Engine(_ExtensionSetters):
             msg = api.last_error(None)
             raise DopfError(f"{api.prefix}create failed ({rc}): {msg.decode() if msg else ''}")
         self._apply(todo)
+        if gen_budget_windows is not None:          # (behind the tables' to-do list: its check reads the availability's caps)
+            self.set_energy_budget_windows(*gen_budget_windows)
 
     def _handle(self):
         return self._ctx
@@ -797,6 +842,30 @@ class Engine(_ExtensionSetters):
         self._chk(self.api.get_generator_budget_price(self._ctx, _dp(out)))
         return out
 
+    def energy_budget_windows(self):
+        """dopf_get_generator_energy_budget_windows: (win_end, e_min, e_max) as the context holds them — n_win ends and two (G, n_win)
+        arrays — or None while no table is set. A backend without the entry: DopfError."""
+        if not hasattr(self.api, "get_generator_energy_budget_windows"):
+            raise DopfError(f"{self.api.prefix}*: this API has no get_generator_energy_budget_windows")
+        n = C.c_int32(0)
+        self._chk(self.api.get_generator_energy_budget_windows(self._ctx, C.byref(n), None, None, None))
+        if n.value == 0:
+            return None
+        ends = np.zeros(self.T, dtype=np.int32)
+        lo, hi = np.zeros(self.G * n.value), np.zeros(self.G * n.value)
+        self._chk(self.api.get_generator_energy_budget_windows(self._ctx, C.byref(n), ends.ctypes.data_as(c_int32_p), _dp(lo), _dp(hi)))
+        return ends[:n.value].copy(), lo.reshape(self.G, n.value), hi.reshape(self.G, n.value)
+
+    def budget_window_price(self) -> np.ndarray:
+        """dopf_get_generator_budget_window_price: nu[g, j], the multiplier the last computed x-update put on window j's budget row of
+        generator g, (G, n_win), with budget_price's sign convention: 0 for a free window, one whose clamped step keeps its budget
+        and one whose search gave up. Always recorded while a table is set (DopfError without one); zeros before the first iteration
+        after the table's allocation. At convergence minus the host LP's dual of that row where it is unique."""
+        n = C.c_int32(0)
+        if hasattr(self.api, "get_generator_energy_budget_windows"):
+            self._chk(self.api.get_generator_energy_budget_windows(self._ctx, C.byref(n), None, None, None))
+        return self._budget_window_price(self._ctx, int(n.value))
+
     def ramp_price(self) -> np.ndarray:
         """dopf_get_generator_ramp_price: rp[g, t], the multiplier the last computed x-update put on generator g's ramp row between
         t-1 and t (t = 0: the anchor's row, 0 without an anchor), (G, T) in the unit of gen_mc: > 0 where ramp-up held the unit
@@ -834,6 +903,8 @@ class Engine(_ExtensionSetters):
         window's with set_availability."""
         from .horizon import shift_window
         k = int(k)
+        if self._mirror.get("gen_budget_windows") is not None:       # (the library's refusal and message: a table does not roll)
+            self._chk(self.api.roll_horizon_coupled(self._ctx, k, None, -1, None, None, 0, None, None))
         # (a context with ramp limits goes the host route on every API: the next window's anchor is the old P[:, k - 1])
         # (so does a context with energy budgets: what is left of them after k steps is formed below)
         native = hasattr(self.api, "roll_horizon") and not self.params.flags & F_GEN_RAMP and not self.flags2 & F2_GEN_ENERGY_BUDGET
@@ -1080,7 +1151,7 @@ class MultiEngine(_ExtensionSetters):
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
                  sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None, gen_c2=None,
-                 gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0, gen_min_output=None):
+                 gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0, gen_min_output=None, gen_budget_windows=None):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
@@ -1090,7 +1161,7 @@ class MultiEngine(_ExtensionSetters):
             sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget,
             gen_min_output=gen_min_output))
         self.params = params if params is not None else default_params()
-        self.flags2 = int(flags2) | _flags2(todo, self.L)
+        self.flags2 = int(flags2) | _flags2(todo, self.L) | (F2_GEN_ENERGY_BUDGET if gen_budget_windows is not None else 0)
         _needs_create_ex(api, self.flags2)
         dev = None if devices is None else _i32(devices, n_gpus)
         self._m = C.c_void_p()
@@ -1100,8 +1171,10 @@ class MultiEngine(_ExtensionSetters):
             msg = api.multi_last_error(None)
             raise DopfError(f"dopf_multi_create failed ({rc}): {msg.decode() if msg else ''}")
         self.n = int(api.multi_size(self._m))
-        self._mirror = {}           # (of the extensions' inputs, the efficiencies alone)
+        self._mirror = {}           # (of the extensions' inputs, the efficiencies and the budget windows alone)
         self._apply(todo)
+        if gen_budget_windows is not None:
+            self.set_energy_budget_windows(*gen_budget_windows)
 
     def _handle(self):
         return self._m
@@ -1186,6 +1259,17 @@ class MultiEngine(_ExtensionSetters):
         self._chk(self.api.multi_get_generator_budget_price(self._m, _dp(out)))
         return out
 
+    def energy_budget_windows(self):
+        """(win_end, e_min, e_max) as set_energy_budget_windows stored them ((G, n_win) arrays in the caller's order; None for a
+        table given as None), or None while no table is set: the host mirror."""
+        return self._mirror.get("gen_budget_windows")
+
+    def budget_window_price(self) -> np.ndarray:
+        """dopf_multi_get_generator_budget_window_price: Engine.budget_window_price for all shards' rows in the caller's order,
+        (G, n_win)."""
+        w = self._mirror.get("gen_budget_windows")
+        return self._budget_window_price(self._m, 0 if w is None else int(w[0].size))
+
     def ramp_price(self) -> np.ndarray:
         """dopf_multi_get_generator_ramp_price: Engine.ramp_price for all shards' rows in the caller's order, (G, T)."""
         if not hasattr(self.api, "multi_get_generator_ramp_price"):
@@ -1205,10 +1289,18 @@ class MultiEngine(_ExtensionSetters):
         return _ShardView(self.api, ctx, self.N, self.L, self.T, cut(self.G), cut(self.S))
 
 
+def _no_budget_windows(gen_budget_windows) -> None:
+    """The device LP's front ends refuse a case with budgets per sub-window, as they refuse floors."""
+    if gen_budget_windows is not None:
+        raise DopfError("dopf_central_solve*: the device LP takes no energy budgets per sub-window (its budget rows span the whole "
+                        "horizon); use central.solve_central_packed(..., gen_budget_windows=) for a case with a table")
+
+
 def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                   sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                   sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
-                  line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, gen_min_output=None) -> dict:
+                  line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, gen_min_output=None,
+                  gen_budget_windows=None) -> dict:
     """dopf_central_solve: the central reference (src/opf_central_reference.jl) as one LP solved on the GPU by a first-order
     primal-dual method. Arguments as Engine (PackedProblem.engine_kwargs()). Returns objective, gap, iterations and the
     reference script's outputs in Julia shapes: P (G,T), D/C/E (S,T), system_price (T), nodal_price (N,T),
@@ -1223,10 +1315,12 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     gen_ramp, gen_prev: nor ramp limits; a finite ramp or an anchor raises DopfError.
     gen_budget: nor energy budgets; an e_min above 0 or a finite e_max raises DopfError.
     gen_min_output: nor must-run floors; a value above 0 raises DopfError.
+    gen_budget_windows: nor budgets per sub-window; a table raises DopfError.
     T: any horizon. Beyond 512 timesteps the storages run on the long sweep (kc_sto_long); the entry sets DOPF_F_LONG_HORIZON on its own
     context, so params needs no flag, and with F_LONG_HORIZON in params the result is the same bits. F_DEBUG_LONG_STO in params runs
     that sweep at T <= 512 too (tests)."""
     N, L, T = int(N), int(L), int(T)
+    _no_budget_windows(gen_budget_windows)
     if gen_min_output is not None and np.any(np.asarray(gen_min_output, dtype=np.float64) != 0.0):
         raise DopfError("dopf_central_solve*: the device LP takes no generator minimum output (its generators' lower bound is 0); use "
                         "central.solve_central_packed(..., gen_min_output=) for a case with a floor")
@@ -1278,7 +1372,8 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
 def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node, sto_mc, sto_pmax, sto_emax,
                           sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                           sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
-                          line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, gen_min_output=None) -> dict:
+                          line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, gen_min_output=None,
+                          gen_budget_windows=None) -> dict:
     """dopf_central_solve_coupled: central_solve's LP with the constraints that couple a generator's timesteps and with per-timestep
     line limits. Arguments as Engine (PackedProblem.engine_kwargs()); beyond central_solve's:
     line_rating (L, T): the limits of the flow rows, as Engine takes them (None: f_max in every timestep).
@@ -1286,12 +1381,13 @@ def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, ge
     gen_budget = (e_min, e_max) (G each; either may be None: 0, inf).
     The call is always dopf_central_solve_coupled (with none of the four given it returns dopf_central_solve_lossy's bits); it checks
     the inputs as the three setters do (DopfError with the entry's name). gen_c2: the device solve is an LP; a non-zero coefficient
-    raises DopfError, and so does a gen_min_output above 0 (the device LP's generators go down to 0). Returns central_solve's dict plus ramp_dual (G, T) and budget_dual (G,): d objective / d right-hand side of the
+    raises DopfError, and so does a gen_min_output above 0 (the device LP's generators go down to 0) and a gen_budget_windows table. Returns central_solve's dict plus ramp_dual (G, T) and budget_dual (G,): d objective / d right-hand side of the
     ramp row between t - 1 and t (t = 0: the anchor's row) and of the budget row — negative where the row's upper end binds, positive
     where its lower end does.
     T: any horizon, with ramps and budgets too. Beyond 512 timesteps the rows run on the long sweeps (kc_gen_rows_long, kc_sto_long);
     params needs no flag for it. F_DEBUG_LONG_STO in params runs those sweeps at T <= 512 too (tests)."""
     N, L, T = int(N), int(L), int(T)
+    _no_budget_windows(gen_budget_windows)
     if gen_c2 is not None and np.any(np.asarray(gen_c2, dtype=np.float64) != 0.0):
         raise DopfError("dopf_central_solve_coupled: the device LP takes no quadratic generator costs (it solves with gen_mc alone)")
     if gen_min_output is not None and np.any(np.asarray(gen_min_output, dtype=np.float64) != 0.0):

@@ -215,6 +215,28 @@ class ADMM:
         (_capi.central_solve_coupled's budget_dual) where that dual is unique. Needs F2_GEN_ENERGY_BUDGET, as set_energy_budget."""
         return self.engine.budget_price()
 
+    def set_energy_budget_windows(self, win_end=None, e_min=None, e_max=None) -> None:
+        """One energy budget per generator and sub-window of the horizon: win_end are the windows' ends (strictly increasing, the last
+        one T; window j covers win_end[j-1] <= t < win_end[j]), e_min / e_max (G, n_win) in the order of `generators` (None = all 0 /
+        all inf): e_min[g,j] <= sum_{t in window j} P[t] <= e_max[g,j] — a daily allotment inside a weekly horizon. win_end None removes
+        the table. Not in the reference. Needs F2_GEN_ENERGY_BUDGET (set for you when the packed problem carries a table) and no
+        whole-horizon budget at the same time; the state and the iteration counter stay, the run is no longer converged; roll and
+        roll_coupled are refused while a table is set (remove it, roll, set the next window's)."""
+        self.engine.set_energy_budget_windows(win_end, e_min, e_max)
+        self.packed.gen_budget_windows = None if win_end is None else tuple(
+            None if a is None else a.copy() for a in self.engine._mirror["gen_budget_windows"])
+        self.convergence = Convergence()
+
+    def energy_budget_windows(self):
+        """(win_end, e_min, e_max) as the context holds them, or None while no table is set."""
+        return self.engine.energy_budget_windows()
+
+    def budget_window_price(self) -> np.ndarray:
+        """The water values per sub-window: nu[g, j], the multiplier the last computed iteration put on generator g's budget of window j,
+        (G, n_win), with budget_price's sign convention. Always recorded while a table is set. At convergence minus the window rows'
+        duals of the host LP (central.solve_central_packed(gen_budget_windows=)) where they are unique."""
+        return self.engine.budget_window_price()
+
     def ramp_price(self) -> np.ndarray:
         """The ramp prices of the run: rp[g, t], the multiplier the last computed iteration put on generator g's ramp row between t-1
         and t (t = 0: the row against the anchor), (G, T) in the order of `generators` and the unit of marginal_cost — what one more

@@ -24,7 +24,7 @@ sign convention (d objective / d right-hand side).
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -44,6 +44,7 @@ class CentralResult:
     flow_upper_dual: np.ndarray     # (L, T)  dual.(FlowUpper)
     flow_lower_dual: np.ndarray     # (L, T)  dual.(FlowLower)
     nodal_price: np.ndarray         # (N, T)
+    budget_window_dual: Optional[np.ndarray] = None     # (G, n_win) with gen_budget_windows: d objective / d right-hand side of the window rows
 
 
 def _efficiencies(pp: PackedProblem, efficiency):
@@ -57,7 +58,7 @@ def _efficiencies(pp: PackedProblem, efficiency):
 
 def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level=None, terminal_level=None,
                          availability=None, efficiency=None, line_rating=None, gen_ramp=None, gen_prev=None, gen_budget=None,
-                         gen_min_output=None) -> CentralResult:
+                         gen_min_output=None, gen_budget_windows=None) -> CentralResult:
     """The LP on a packed case (any size HiGHS can take; synthetic cases with 1e5 agents go through
     tests/central_lp.aggregate_* first). initial_level: (S,) level of each storage before the first timestep, the right-hand
     side of its storage-balance row at t = 0 (None: the packed case's sto_e0, else 0 as in the reference). terminal_level:
@@ -72,7 +73,12 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
     (e_min, e_max), (G,) each: the rows e_min[g] <= sum_t P[g,t] <= e_max[g], one per generator with an e_min above 0 and one per finite
     e_max (None: the packed case's budgets, else none as in the reference). gen_min_output: (G,) must-run floors: the lower bound of
     P[g,t] becomes min(p_min[g], its upper bound) — the floor follows an outage down (None: the packed case's floors, else 0 as in the
-    reference). The parity target of dopf_set_generator_min_output."""
+    reference). The parity target of dopf_set_generator_min_output. gen_budget_windows: (win_end (n_win,), e_min, e_max (G, n_win) each or
+    None): one inequality pair per generator and window, e_min[g,j] <= sum_{win_end[j-1] <= t < win_end[j]} P[g,t] <= e_max[g,j] (a row
+    per e_min above 0 and per finite e_max; None: the packed case's table, else none). The result's budget_window_dual[g,j] is then
+    d objective / d right-hand side of that pair: negative where e_max binds, positive where e_min does, as
+    _capi.central_solve_coupled's budget_dual — minus dopf_get_generator_budget_window_price at convergence. An infeasible table
+    raises RuntimeError, as every infeasible case. The parity target of dopf_set_generator_energy_budget_windows."""
     from scipy import sparse
     from scipy.optimize import linprog
     if pp.has_quadratic_cost():
@@ -180,6 +186,23 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
                 r = len(bub)
                 ur += [r] * T; uc += list(range(g * T, g * T + T)); uv += [sign] * T
                 bub.append(sign * bound[g])
+    if gen_budget_windows is None and pp.has_budget_windows():
+        gen_budget_windows = pp.budget_windows()
+    win_rows = []          # (row of A_ub, g, j, sign)
+    if gen_budget_windows is not None and G > 0:
+        ends = np.asarray(gen_budget_windows[0], dtype=np.int64).reshape(-1)
+        nw = ends.size
+        if nw < 1 or ends[-1] != T or np.any(np.diff(np.concatenate([[0], ends])) <= 0):
+            raise ValueError(f"gen_budget_windows: the ends {ends.tolist()} are not strictly increasing from above 0 up to T = {T}")
+        w_min = np.zeros((G, nw)) if gen_budget_windows[1] is None else np.asarray(gen_budget_windows[1], dtype=np.float64).reshape(G, nw)
+        w_max = np.full((G, nw), np.inf) if gen_budget_windows[2] is None else np.asarray(gen_budget_windows[2], dtype=np.float64).reshape(G, nw)
+        for sign, bound, wanted in ((1.0, w_max, np.isfinite(w_max)), (-1.0, w_min, w_min > 0.0)):
+            for g, j in zip(*np.nonzero(wanted)):          # sign sum_{t in window j} P[g,t] <= sign bound[g,j]
+                t0, t1 = (0 if j == 0 else int(ends[j - 1])), int(ends[j])
+                r = len(bub)
+                ur += [r] * (t1 - t0); uc += list(range(g * T + t0, g * T + t1)); uv += [sign] * (t1 - t0)
+                bub.append(sign * bound[g, j])
+                win_rows.append((r, g, j, sign))
     if bub:
         Aub = sparse.csr_matrix((uv, (ur, uc)), shape=(len(bub), nv))
         bub = np.asarray(bub)
@@ -200,7 +223,13 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
             fl = m[rLo:rLo + nL].reshape(L, T)
     ptdf = np.asarray(pp.ptdf, dtype=np.float64).reshape(L, N)
     nodal = lam[None, :] + ptdf.T @ (fu + fl) if L > 0 else np.tile(lam, (N, 1))      # opf_central_reference.jl:71-79
-    return CentralResult(objective=float(res.fun), generation=x[:nP].reshape(G, T), discharge=x[oD:oD + nS].reshape(S, T),
+    wdual = None
+    if gen_budget_windows is not None and G > 0:
+        wdual = np.zeros((G, nw))
+        if duals:
+            for r, g, j, sign in win_rows:          # (a <= row's marginal is d objective / d its right-hand side, sign x the bound)
+                wdual[g, j] += sign * res.ineqlin.marginals[r]
+    return CentralResult(budget_window_dual=wdual, objective=float(res.fun), generation=x[:nP].reshape(G, T), discharge=x[oD:oD + nS].reshape(S, T),
                          charge=x[oC:oC + nS].reshape(S, T), level=x[oE:oE + nS].reshape(S, T), injection=inj,
                          line_utilization=ptdf @ inj if L > 0 else np.zeros((0, T)), system_price=lam,
                          flow_upper_dual=fu, flow_lower_dual=fl, nodal_price=nodal)

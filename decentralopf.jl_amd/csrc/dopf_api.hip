@@ -307,12 +307,74 @@ static int ramp_budget_rows_fit(dopf_ctx *c, const char *entry, bool given_ramp,
     return DOPF_OK;
 }
 
+// dopf_set_generator_energy_budget_windows: window j's minimum must be deliverable under the window's caps — e_min <= sum of cap[g,t]
+// over t0 <= t < t1, formed in t order. g: the caller's index (the message's); f: the generator's profile, or null
+static int budget_win_min_fits(dopf_ctx *c, const char *entry, int g, int j, int t0, int t1, double pm, double e_min, const double *f)
+{
+    if (!(e_min > 0.0)) return DOPF_OK;
+    double room = 0.0;
+    for (int t = t0; t < t1; ++t) room += f ? pm * f[t] : pm;
+    if (e_min > room)
+        return fail(c, DOPF_E_INVALID, "%s: generator g = %d cannot deliver e_min = %g in window j = %d (t = %d .. %d) under its caps (their sum is %g)",
+                    entry, g, e_min, j, t0, t1 - 1, room);
+    return DOPF_OK;
+}
+
+// dopf_set_generator_energy_budget_windows' checks, in the order of include/dopf.h; n_win == 0 (remove the table) needs the flag and
+// NULL pointers alone
+int check_generator_energy_budget_windows(dopf_ctx *c, int32_t n_win, const int32_t *win_end, const double *e_min, const double *e_max)
+{
+    const char *entry = "dopf_set_generator_energy_budget_windows";
+    if (!(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: budgets per sub-window need DOPF_F2_GEN_ENERGY_BUDGET at dopf_create_ex", entry);
+    if (c->plan.genRampBudget)
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: not on a DOPF_F2_GEN_RAMP_BUDGET context (ramps couple neighbouring windows, so a row no longer "
+                                           "separates into one problem per window)", entry);
+    const int G = c->v.G, T = c->v.T;
+    if (n_win < 0 || n_win > T) return fail(c, DOPF_E_INVALID, "%s: n_win = %d outside [0, T = %d]", entry, n_win, T);
+    if (n_win == 0) {
+        if (win_end || e_min || e_max) return fail(c, DOPF_E_INVALID, "%s: n_win = 0 removes the table and takes NULL pointers only", entry);
+        return DOPF_OK;
+    }
+    if (!win_end) return fail(c, DOPF_E_INVALID, "%s: win_end is NULL with n_win = %d", entry, n_win);
+    for (int j = 0; j < n_win; ++j)
+        if (win_end[j] <= (j > 0 ? win_end[j - 1] : 0))
+            return fail(c, DOPF_E_INVALID, "%s: win_end[j = %d] = %d is not above %d (the ends are strictly increasing from above 0)", entry, j, win_end[j],
+                        j > 0 ? win_end[j - 1] : 0);
+    if (win_end[n_win - 1] != T)
+        return fail(c, DOPF_E_INVALID, "%s: the last end win_end[j = %d] = %d is not T = %d", entry, n_win - 1, win_end[n_win - 1], T);
+    for (int i = 0; i < G; ++i)
+        if (c->gen_budget_h[(size_t)G + i] != 0.0 || c->gen_budget_h[2 * (size_t)G + i] != INFINITY)
+            return fail(c, DOPF_E_INVALID, "%s: generator g = %d holds a whole-horizon budget [%g, %g]; call dopf_set_generator_energy_budget(ctx, NULL, NULL) "
+                                           "first (one description of the budgets at a time)", entry, c->gen_perm[i], c->gen_budget_h[(size_t)G + i],
+                        c->gen_budget_h[2 * (size_t)G + i]);
+    for (int i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        const int k = c->gen_prof_h.empty() ? -1 : c->gen_prof_h[i];
+        const double *f = k >= 0 ? c->gen_avail_h.data() + (size_t)k * T : nullptr;
+        for (int j = 0; j < n_win; ++j) {
+            const size_t at = (size_t)j + (size_t)n_win * a;
+            const double lo = e_min ? e_min[at] : 0.0, hi = e_max ? e_max[at] : INFINITY;
+            if (std::isnan(lo) || std::isinf(lo) || lo < 0.0)
+                return fail(c, DOPF_E_INVALID, "%s: e_min of g = %d, j = %d is %g (finite and >= 0 wanted)", entry, a, j, lo);
+            if (std::isnan(hi) || hi < 0.0) return fail(c, DOPF_E_INVALID, "%s: e_max of g = %d, j = %d is %g (>= 0 wanted)", entry, a, j, hi);
+            if (lo > hi) return fail(c, DOPF_E_INVALID, "%s: e_min = %g exceeds e_max = %g at g = %d, j = %d", entry, lo, hi, a, j);
+            if (int rc = budget_win_min_fits(c, entry, a, j, j > 0 ? win_end[j - 1] : 0, win_end[j], c->gen_budget_h[i], lo, f)) return rc;
+        }
+    }
+    return DOPF_OK;
+}
+
 // dopf_set_generator_energy_budget's checks: the flag, no NaN, e_min finite and >= 0, e_max >= 0, e_min <= e_max, and every minimum
 // deliverable under the caps (the stored availability table)
 int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double *e_max)
 {
     if (!(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
         return fail(c, DOPF_E_UNSUPPORTED, "generator energy budgets need DOPF_F2_GEN_ENERGY_BUDGET at dopf_create_ex");
+    if ((e_min || e_max) && !c->gen_bw_end_h.empty())
+        return fail(c, DOPF_E_INVALID, "dopf_set_generator_energy_budget: the context holds budgets per sub-window (n_win = %d); remove them with "
+                                       "dopf_set_generator_energy_budget_windows(ctx, 0, NULL, NULL, NULL) first (one description of the budgets at a time)",
+                    (int)c->gen_bw_end_h.size());
     if (int rc = check_generator_energy_budget_values(c, "dopf_set_generator_energy_budget", c->gen_budget_h.data(), c->gen_avail_h.data(), e_min, e_max))
         return rc;
     // DOPF_F2_GEN_RAMP_BUDGET: ... and every row jointly feasible with its stored ramps and anchor
@@ -380,6 +442,15 @@ int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles,
             if (int rc = budget_min_fits(c, "dopf_set_generator_availability", a, c->gen_budget_h[i], c->gen_budget_h[(size_t)G + i],
                                          k >= 0 ? profiles + (size_t)k * T : nullptr)) return rc;
         }
+    // the minima of dopf_set_generator_energy_budget_windows, window by window under the new table
+    const int nw = (int)c->gen_bw_end_h.size();
+    for (int i = 0; i < G && nw > 0; ++i) {
+        const int a = c->gen_perm[i], k = profile_of ? profile_of[a] : -1;
+        for (int j = 0; j < nw; ++j)
+            if (int rc = budget_win_min_fits(c, "dopf_set_generator_availability", a, j, j > 0 ? c->gen_bw_end_h[(size_t)j - 1] : 0, c->gen_bw_end_h[(size_t)j],
+                                             c->gen_budget_h[i], c->gen_bw_h[(size_t)j + (size_t)nw * i], k >= 0 ? profiles + (size_t)k * T : nullptr))
+                return rc;
+    }
     // DOPF_F2_GEN_RAMP_BUDGET: the stored ramps and budgets together, under the new table
     return ramp_budget_rows_fit(c, "dopf_set_generator_availability", false, nullptr, nullptr, nullptr, false, nullptr, nullptr, true, profiles,
                                 profile_of);
@@ -1921,6 +1992,9 @@ int dopf_get_generator_budget_price(dopf_ctx *c, double *nu)
     if (!c) return DOPF_E_INVALID;
     if (!(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
         return fail(c, DOPF_E_UNSUPPORTED, "dopf_get_generator_budget_price: the context was created without DOPF_F2_GEN_ENERGY_BUDGET");
+    if (!c->gen_bw_end_h.empty())
+        return fail(c, DOPF_E_INVALID, "dopf_get_generator_budget_price: the context holds budgets per sub-window (n_win = %d), whose prices "
+                                       "dopf_get_generator_budget_window_price returns", (int)c->gen_bw_end_h.size());
     const size_t G = (size_t)c->v.G;
     if (G == 0) return DOPF_OK;
     if (!nu) return fail(c, DOPF_E_INVALID, "dopf_get_generator_budget_price: nu is NULL");
@@ -2005,6 +2079,116 @@ int dopf_set_generator_energy_budget(dopf_ctx *c, const double *e_min, const dou
     HIPCHK(c, hipGetLastError());
     if (int rc = read_status(c)) return rc;          // (synchronises: h may go)
     std::copy(h.begin(), h.end(), c->gen_budget_h.begin() + G);
+    return DOPF_OK;
+}
+
+// the device block of a table of n_win windows: prices | e_min | e_max (n_win x G doubles each, sorted order) | the ends (n_win ints)
+static void budget_win_view(dopf::BudgetWinView *bw, void *blk, size_t G, int n_win)
+{
+    const size_t n = G * (size_t)n_win;
+    double *d = (double *)blk;
+    bw->nu = d;
+    bw->emin = d + n;
+    bw->emax = d + 2 * n;
+    bw->end = (const int *)(d + 3 * n);
+    bw->n_win = n_win;
+}
+
+static void budget_win_release(dopf_ctx *c)
+{
+    if (!c->gen_bw_base) return;
+    auto it = std::find(c->allocs.begin(), c->allocs.end(), c->gen_bw_base);
+    if (it != c->allocs.end()) c->allocs.erase(it);
+    hipFree(c->gen_bw_base);
+    c->gen_bw_base = nullptr;
+}
+
+int dopf_set_generator_energy_budget_windows(dopf_ctx *c, int32_t n_win, const int32_t *win_end, const double *e_min, const double *e_max)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_generator_energy_budget_windows(c, n_win, win_end, e_min, e_max)) return rc;
+    const size_t G = (size_t)c->v.G;
+    if (G == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    const int stored = (int)c->gen_bw_end_h.size();
+    const size_t n = G * (size_t)n_win;
+    std::vector<double> h(2 * n);
+    for (size_t i = 0; i < G; ++i) {
+        const size_t a = (size_t)c->gen_perm[i];
+        for (size_t j = 0; j < (size_t)n_win; ++j) {
+            h[j + n_win * i] = e_min ? e_min[j + n_win * a] + 0.0 : 0.0;
+            h[n + j + n_win * i] = e_max ? e_max[j + n_win * a] + 0.0 : INFINITY;
+        }
+    }
+    if (n_win != stored) {
+        // another kernel (the first table, none) or other arrays behind its second argument: the stream drains, the block is replaced
+        // and the iteration graphs are captured again at the next dopf_iterate
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        void *blk = nullptr;
+        if (n_win > 0) {
+            const unsigned long long need = 3ull * n * sizeof(double) + (unsigned long long)n_win * sizeof(int);
+            size_t freeb = 0, totalb = 0;
+            HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
+            if (need > freeb)
+                return fail(c, DOPF_E_NOMEM, "dopf_set_generator_energy_budget_windows: the table (n_win = %d ends, 3 x n_win x G doubles) needs %llu bytes, "
+                                             "the device has %llu free", n_win, need, (unsigned long long)freeb);
+            char *q = nullptr;
+            if (int rc = dev_alloc(c, &q, (size_t)need, false)) return rc;
+            blk = c->allocs.back();
+            budget_win_release(c);
+            c->gen_bw_base = blk;
+            budget_win_view(&c->plan.genBudgetWin, q, G, n_win);
+            HIPCHK(c, hipMemsetAsync(c->plan.genBudgetWin.nu, 0, n * sizeof(double), c->main));
+        } else {
+            budget_win_release(c);
+            c->plan.genBudgetWin = dopf::BudgetWinView{};
+        }
+        drop_graphs(c);
+    }
+    // ordered on the context's stream behind what is queued there; with the same n_win the graphs read the same device arrays (no
+    // capture again). The state stays; the stop test starts over, as after dopf_set_generator_energy_budget
+    if (n_win > 0) {
+        const dopf::BudgetWinView &bw = c->plan.genBudgetWin;
+        HIPCHK(c, hipMemcpyAsync(const_cast<double *>(bw.emin), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->main));
+        HIPCHK(c, hipMemcpyAsync(const_cast<int *>(bw.end), win_end, (size_t)n_win * sizeof(int), hipMemcpyHostToDevice, c->main));
+    }
+    launch_reset_status(c->v, c->main);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = read_status(c)) return rc;          // (synchronises: h and win_end may go)
+    c->gen_bw_end_h.assign(win_end, win_end + n_win);
+    c->gen_bw_h = h;
+    return DOPF_OK;
+}
+
+// the stored table from the host mirrors (no device call)
+int dopf_get_generator_energy_budget_windows(dopf_ctx *c, int32_t *n_win, int32_t *win_end, double *e_min, double *e_max)
+{
+    if (!c) return DOPF_E_INVALID;
+    const size_t nw = c->gen_bw_end_h.size(), G = (size_t)c->v.G, n = nw * G;
+    if (n_win) *n_win = (int32_t)nw;
+    if (win_end) std::copy(c->gen_bw_end_h.begin(), c->gen_bw_end_h.end(), win_end);
+    for (size_t i = 0; i < G && nw > 0; ++i) {
+        const size_t a = (size_t)c->gen_perm[i];
+        if (e_min) std::copy(c->gen_bw_h.begin() + nw * i, c->gen_bw_h.begin() + nw * (i + 1), e_min + nw * a);
+        if (e_max) std::copy(c->gen_bw_h.begin() + n + nw * i, c->gen_bw_h.begin() + n + nw * (i + 1), e_max + nw * a);
+    }
+    return DOPF_OK;
+}
+
+// the windows' multipliers of the last computed x-update, as k_gen_budget_win stored them (sorted order on the device)
+int dopf_get_generator_budget_window_price(dopf_ctx *c, double *nu)
+{
+    if (!c) return DOPF_E_INVALID;
+    const size_t G = (size_t)c->v.G, nw = c->gen_bw_end_h.size();
+    if (G == 0) return DOPF_OK;
+    if (nw == 0)
+        return fail(c, DOPF_E_INVALID, "dopf_get_generator_budget_window_price: no table is set (dopf_set_generator_energy_budget_windows first)");
+    if (!nu) return fail(c, DOPF_E_INVALID, "dopf_get_generator_budget_window_price: nu is NULL");
+    DeviceGuard guard(c->device);
+    std::vector<double> h(G * nw);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->plan.genBudgetWin.nu, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->main));
+    HIPCHK(c, hipStreamSynchronize(c->main));
+    for (size_t i = 0; i < G; ++i) std::copy(h.begin() + nw * i, h.begin() + nw * (i + 1), nu + nw * (size_t)c->gen_perm[i]);
     return DOPF_OK;
 }
 
@@ -2198,6 +2382,10 @@ int dopf_roll_horizon_coupled(dopf_ctx *c, int32_t k, const double *demand_tail,
     if (!c) return DOPF_E_INVALID;
     const char *entry = "dopf_roll_horizon_coupled";
     if (c->comm) return roll_checks(c, entry, "demand_tail", demand_tail, 0, c->v.N, 0);
+    if (!c->gen_bw_end_h.empty())
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: the context holds budgets per sub-window (n_win = %d), which do not roll on the device: remove the table "
+                                           "(dopf_set_generator_energy_budget_windows with n_win = 0), roll, and set the next window's table", entry,
+                    (int)c->gen_bw_end_h.size());
     if (n_profiles < -1) return fail(c, DOPF_E_INVALID, "%s: n_profiles = %d < -1 (-1: the stored table stays)", entry, n_profiles);
     if (n_profiles >= 0 && !(c->q.flags & DOPF_F_GEN_AVAILABILITY))
         return fail(c, DOPF_E_UNSUPPORTED, "%s: an availability table (n_profiles = %d) needs DOPF_F_GEN_AVAILABILITY at dopf_create", entry, n_profiles);

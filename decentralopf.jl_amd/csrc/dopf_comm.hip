@@ -790,6 +790,24 @@ int dopf_multi_get_generator_budget_price(dopf_multi *m, double *nu)
     return DOPF_OK;
 }
 
+// (the ends are replicated; a generator's n_win budgets are consecutive: shard i's slice begins at n_win * g0[i])
+int dopf_multi_set_generator_energy_budget_windows(dopf_multi *m, int32_t n_win, const int32_t *win_end, const double *e_min, const double *e_max)
+{
+    const size_t nw = n_win > 0 ? (size_t)n_win : 0;
+    return multi_set(m, check_generator_energy_budget_windows, dopf_set_generator_energy_budget_windows,
+                     [&](auto f, int i) { return f(m->ctx[i], n_win, win_end, from(e_min, nw * m->g0[i]), from(e_max, nw * m->g0[i])); });
+}
+
+int dopf_multi_get_generator_budget_window_price(dopf_multi *m, double *nu)
+{
+    if (!m) return DOPF_E_INVALID;
+    for (int i = 0; i < m->n; ++i) {
+        const size_t nw = m->ctx[i]->gen_bw_end_h.size();
+        if (const int rc = dopf_get_generator_budget_window_price(m->ctx[i], from(nu, nw * m->g0[i]))) return shard_fail(m, i, rc);
+    }
+    return DOPF_OK;
+}
+
 // (rows are T long: shard i's slice begins at row g0[i])
 int dopf_multi_get_generator_ramp_price(dopf_multi *m, double *rp)
 {

@@ -393,6 +393,7 @@ void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_gen_ramp(const DevView &v, const Plan &p, hipStream_t s);       // gen_ramp.h: the generators of a DOPF_F_GEN_RAMP context
 void launch_gen_ramp_net(const DevView &v, const Plan &p, hipStream_t s);   // gen_ramp_net.h: ... on a network (DOPF_F_GEN_RAMP_NETWORK)
 void launch_gen_budget(const DevView &v, const Plan &p, hipStream_t s);     // gen_budget.h: the generators of a DOPF_F2_GEN_ENERGY_BUDGET context
+void launch_gen_budget_win(const DevView &v, const Plan &p, hipStream_t s); // gen_budget_win.h: ... while dopf_set_generator_energy_budget_windows holds a table
 void launch_gen_ramp_budget(const DevView &v, const Plan &p, hipStream_t s);   // gen_ramp_budget.h: ... of a DOPF_F2_GEN_RAMP_BUDGET context
 void launch_sto_update(const DevView &v, const Plan &p, hipStream_t s);
 void launch_net_agents(const DevView &v, const Plan &p, hipStream_t s);

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/dopf.h"
+#include "budget_win_map.h"
 
 namespace dopf {
 
@@ -71,6 +72,9 @@ struct Plan {
     double *genRampPrice;           // non-null: the RP instantiations of k_gen_ramp / k_gen_ramp_budget store the rows' ramp multipliers
                                     // there (T x G doubles of the context's own, the kernels' second argument). Like genMinOut never set by plan_chain:
                                     // the first dopf_get_generator_ramp_price allocates it on a copper-plate genRamp context (and drops the graphs)
+    BudgetWinView genBudgetWin;     // n_win > 0: k_gen_budget_win<LINES, AV, QC> (gen_budget_win.h) runs for k_gen_budget, with this as its second
+                                    // argument: the window ends, budgets and prices of the context's own. Like genMinOut never set by plan_chain:
+                                    // dopf_set_generator_energy_budget_windows sets and clears it on a genBudget context (and drops the graphs)
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those

@@ -885,6 +885,7 @@ void launch_gen_update(const DevView &v, const Plan &p, hipStream_t s)
 {
     if (v.nGenItems == 0) return;
     if (p.genRampBudget) { launch_gen_ramp_budget(v, p, s); return; }      // DOPF_F2_GEN_RAMP_BUDGET: k_gen_ramp_budget<AV, QC> (gen_ramp_budget.h)
+    if (p.genBudgetWin.n_win > 0) { launch_gen_budget_win(v, p, s); return; }      // ... with a table of budgets per sub-window: k_gen_budget_win<LINES, AV, QC> (gen_budget_win.h)
     if (p.genBudget) { launch_gen_budget(v, p, s); return; }       // DOPF_F2_GEN_ENERGY_BUDGET: k_gen_budget<LINES, AV, QC> (gen_budget.h)
     if (p.genRampNet) { launch_gen_ramp_net(v, p, s); return; }    // ... on a network: k_gen_ramp_net<AV, QC> (gen_ramp_net.h)
     if (p.genRamp) { launch_gen_ramp(v, p, s); return; }       // DOPF_F_GEN_RAMP: k_gen_ramp<AV, QC> (gen_ramp.h)
@@ -2397,6 +2398,7 @@ __device__ __forceinline__ int sto_warm_body(const DevView &v, const int blk, co
 #include "gen_ramp.h"
 #include "gen_ramp_net.h"
 #include "gen_budget.h"
+#include "gen_budget_win.h"
 #include "gen_ramp_budget.h"
 namespace dopf {
 

@@ -468,6 +468,80 @@ function budget_price(admm::ADMM)
 end
 
 """
+    set_energy_budget_windows!(admm, win_end, e_min, e_max)
+
+One energy budget per generator and sub-window of the horizon (`dopf_set_generator_energy_budget_windows`; a multi-GPU ADMM:
+`dopf_multi_set_generator_energy_budget_windows`). `win_end` holds the windows' ends as the C ABI counts them: window j covers the
+0-based timesteps `win_end[j-1] <= t < win_end[j]` (0 in front of the first), strictly increasing, the last one T. `e_min` and `e_max`
+are `n_win x G` matrices in the order of `generators` (`nothing` = all 0 / all `Inf`): `e_min[j,g] <= sum over window j of P[g,t] <=
+e_max[j,g]` — a daily allotment inside a weekly horizon. `win_end === nothing` removes the table. The ADMM must have been created with
+`flags2 = DOPF_F2_GEN_ENERGY_BUDGET` (without ramps) and hold no whole-horizon budget. The state and the iteration counter stay; takes
+effect at the next iteration.
+"""
+function set_energy_budget_windows!(admm::ADMM, win_end::Union{Nothing, Vector{Cint}}, e_min::Union{Nothing, Matrix{Float64}}=nothing,
+                                    e_max::Union{Nothing, Matrix{Float64}}=nothing)
+    G = length(admm.generators)
+    nw = win_end === nothing ? 0 : length(win_end)
+    for a in (e_min, e_max)
+        a === nothing || (win_end !== nothing && size(a) == (nw, G)) || error("set_energy_budget_windows!: expected a $nw x $G matrix, got $(size(a))")
+    end
+    pend = win_end === nothing ? Ptr{Cint}(C_NULL) : pointer(win_end)
+    plo = e_min === nothing ? Ptr{Cdouble}(C_NULL) : pointer(e_min)
+    phi = e_max === nothing ? Ptr{Cdouble}(C_NULL) : pointer(e_max)
+    GC.@preserve win_end e_min e_max begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_generator_energy_budget_windows, DOPF_LIB), Cint,
+                                   (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}), admm.multi, nw, pend, plo, phi), admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_generator_energy_budget_windows, DOPF_LIB), Cint,
+                             (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}), admm.ctx, nw, pend, plo, phi), admm.ctx)
+        end
+    end
+    return nothing
+end
+
+"""
+    energy_budget_windows(admm)
+
+The stored table (`dopf_get_generator_energy_budget_windows`, from the context's host copies): `(win_end, e_min, e_max)` with two
+`n_win x G` matrices, or `nothing` while no table is set. One GPU only (`n_gpus == 1`).
+"""
+function energy_budget_windows(admm::ADMM)
+    admm.multi == C_NULL || error("energy_budget_windows: one GPU only (no dopf_multi_* wrapper)")
+    G, T = length(admm.generators), length(admm.T)
+    nw = Ref{Cint}(0)
+    ends = zeros(Cint, T)
+    dopf_check(ccall((:dopf_get_generator_energy_budget_windows, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}),
+                     admm.ctx, nw, ends, C_NULL, C_NULL), admm.ctx)
+    nw[] == 0 && return nothing
+    lo, hi = zeros(Float64, nw[], G), zeros(Float64, nw[], G)
+    dopf_check(ccall((:dopf_get_generator_energy_budget_windows, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}),
+                     admm.ctx, nw, ends, lo, hi), admm.ctx)
+    return ends[1:nw[]], lo, hi
+end
+
+"""
+    budget_window_price(admm, n_win)
+
+The water values per sub-window (`dopf_get_generator_budget_window_price`; a multi-GPU ADMM:
+`dopf_multi_get_generator_budget_window_price`): an `n_win x G` matrix, `nu[j,g]` the multiplier the last computed iteration put on
+generator g's budget of window j, with `budget_price`'s sign convention. Always recorded while a table is set; `n_win` is the stored
+table's number of windows.
+"""
+function budget_window_price(admm::ADMM, n_win::Int)
+    out = zeros(Float64, n_win, length(admm.generators))
+    GC.@preserve out begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_get_generator_budget_window_price, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi,
+                                   pointer(out)), admm.multi)
+        else
+            dopf_check(ccall((:dopf_get_generator_budget_window_price, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, pointer(out)), admm.ctx)
+        end
+    end
+    return out
+end
+
+"""
     ramp_price(admm)
 
 The ramp prices of the run (`dopf_get_generator_ramp_price`; a multi-GPU ADMM: `dopf_multi_get_generator_ramp_price`): a `G x T`

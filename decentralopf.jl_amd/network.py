@@ -152,6 +152,8 @@ class PackedProblem:
     gen_ramp: Optional[tuple] = None            # ((G,), (G,)) Generator.ramp_up, ramp_down; None = all inf
     gen_budget: Optional[tuple] = None          # ((G,), (G,)) Generator.energy_min, energy_max; None = all (0, inf)
     gen_min_output: Optional[np.ndarray] = None     # (G,) Generator.min_generation; None = all 0
+    gen_budget_windows: Optional[tuple] = None  # (win_end (n_win,), e_min (G, n_win) or None, e_max (G, n_win) or None): energy budgets per
+                                                # sub-window of the horizon (window j: win_end[j-1] <= t < win_end[j]); None = no table
 
     @property
     def G(self):
@@ -188,7 +190,21 @@ class PackedProblem:
             kw["gen_budget"] = self.budget()
         if self.gen_min_output is not None and np.any(np.asarray(self.gen_min_output) != 0.0):
             kw["gen_min_output"] = self.min_output()      # (engines then run with F_GEN_RAMP: the floors run on the ramp kernels)
+        if self.has_budget_windows():      # (engines then run with F2_GEN_ENERGY_BUDGET and set the table behind everything else)
+            kw["gen_budget_windows"] = self.budget_windows()
         return kw
+
+    def budget_windows(self):
+        """(win_end int32 (n_win,), e_min, e_max float64 (G, n_win)), the defaults filled in: all 0, all inf. Needs a table."""
+        ends, lo, hi = self.gen_budget_windows
+        ends = np.asarray(ends, dtype=np.int32).reshape(-1)
+        lo = np.zeros((self.G, ends.size)) if lo is None else np.asarray(lo, dtype=np.float64).reshape(self.G, ends.size)
+        hi = np.full((self.G, ends.size), np.inf) if hi is None else np.asarray(hi, dtype=np.float64).reshape(self.G, ends.size)
+        return ends, lo, hi
+
+    def has_budget_windows(self) -> bool:
+        """The problem carries a table of energy budgets per sub-window (a shard: the whole problem does, and the shard holds its rows)."""
+        return self.gen_budget_windows is not None
 
     def min_output(self):
         """min_generation, float64 (G,), the default filled in: all 0."""
@@ -289,7 +305,9 @@ class PackedProblem:
             gen_c2=None if self.gen_c2 is None else self.gen_c2[g0:g1],
             gen_ramp=None if self.gen_ramp is None else tuple(np.asarray(r)[g0:g1] for r in self.gen_ramp),
             gen_budget=None if self.gen_budget is None else tuple(np.asarray(b)[g0:g1] for b in self.gen_budget),
-            gen_min_output=None if self.gen_min_output is None else np.asarray(self.gen_min_output)[g0:g1])
+            gen_min_output=None if self.gen_min_output is None else np.asarray(self.gen_min_output)[g0:g1],
+            gen_budget_windows=None if self.gen_budget_windows is None else tuple(
+                b if i == 0 or b is None else np.asarray(b).reshape(self.G, -1)[g0:g1] for i, b in enumerate(self.gen_budget_windows)))
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],

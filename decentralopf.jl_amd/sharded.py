@@ -146,6 +146,44 @@ class ShardedADMM:
         move). Needs F2_GEN_ENERGY_BUDGET in the second flag word; every rank calls it between the same two steps."""
         self.engine.set_energy_budget(self._mine(e_min, "gen"), self._mine(e_max, "gen"))
 
+    def set_energy_budget_windows(self, win_end=None, e_min=None, e_max=None) -> None:
+        """All generators' energy budgets per sub-window (win_end: the windows' ends, the same on every rank; e_min / e_max:
+        (problem.G, n_win), global order, None = all 0 / all inf; win_end None removes the table): this rank sets the ends and its rows
+        (dopf_set_generator_energy_budget_windows; the constraint is local to the rank's agents, no sums move). Needs
+        F2_GEN_ENERGY_BUDGET in the second flag word; every rank calls it between the same two steps."""
+        self.engine.set_energy_budget_windows(win_end, self._mine_rows(e_min), self._mine_rows(e_max))
+
+    def _mine_rows(self, x):
+        """This rank's rows of a global (problem.G, n) array; None stays None."""
+        if x is None:
+            return None
+        a, b = self.shard.meta["gen_range"]
+        return np.asarray(x, dtype=np.float64).reshape(self.problem.G, -1)[a:b]
+
+    def energy_budget_windows(self):
+        """This rank's (win_end, e_min, e_max) as its context holds them (its generators' rows), or None while no table is set."""
+        return self.engine.energy_budget_windows()
+
+    def budget_window_price(self, all_reduce: Optional[Callable[[np.ndarray], np.ndarray]] = None) -> np.ndarray:
+        """All generators' window prices ((problem.G, n_win), global order): this rank's rows (dopf_get_generator_budget_window_price)
+        in an array of zeros, summed over the ranks as budget_price does: torch.distributed on the product path (every rank must
+        call), a caller's all_reduce (array -> the ranks' sum) otherwise; one rank needs neither."""
+        a, b = self.shard.meta["gen_range"]
+        mine = np.asarray(self.engine.budget_window_price(), dtype=np.float64)
+        out = np.zeros((self.problem.G, mine.shape[1]))
+        out[a:b] = mine
+        if all_reduce is not None:
+            return np.asarray(all_reduce(out), dtype=np.float64)
+        if self.world == 1:
+            return out
+        if self._tensor is None:
+            raise ValueError("a host library needs an all_reduce callable")
+        import torch
+        import torch.distributed as dist
+        t = torch.from_numpy(out).to(self._tensor.device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t.cpu().numpy()
+
     def budget_price(self, all_reduce: Optional[Callable[[np.ndarray], np.ndarray]] = None) -> np.ndarray:
         """All generators' budget prices (problem.G values, global order): this rank's slice (dopf_get_generator_budget_price; the
         price is local to the rank's agents) in a vector of zeros, summed over the ranks — every entry has one owner, so the sum

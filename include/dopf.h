@@ -259,7 +259,9 @@ typedef struct dopf_params {
                                   * dopf_roll_horizon_coupled's on the device);
                                   * dopf_central_solve, _ex and _lossy take no budgets and ignore the bit. dopf_central_solve_coupled
                                   * takes the budgets as arguments, together with ramps if the caller has both. On a copper plate
-                                  * DOPF_F2_GEN_RAMP_BUDGET lifts that refusal: the pair then runs in one context. */
+                                  * DOPF_F2_GEN_RAMP_BUDGET lifts that refusal: the pair then runs in one context. A context with this flag
+                                  * and without DOPF_F2_GEN_RAMP_BUDGET also takes one budget per sub-window of the horizon
+                                  * (dopf_set_generator_energy_budget_windows, k_gen_budget_win). */
 #define DOPF_F2_GEN_RAMP_BUDGET 8 /* ramp limits and energy budgets on the same generators (copper plates, L == 0); meaningful only together
                                   * with DOPF_F_GEN_RAMP and DOPF_F2_GEN_ENERGY_BUDGET, and an opt-in of its own because the step needs
                                   * scratch that grows with T. The generator's step keeps its objective and its box (cap[g,t] under
@@ -530,7 +532,8 @@ int dopf_get_generator_min_output(dopf_ctx *ctx, double *p_min /* G */);
  * the rank's agents). DOPF_E_UNSUPPORTED without the flag; DOPF_E_INVALID, naming the entry and storing nothing, for a NaN,
  * e_min < 0, an infinite e_min, e_max < 0, e_min > e_max, or e_min[g] > sum_t cap[g,t] (the stored availability table). In contexts
  * with this flag dopf_set_generator_availability repeats the last check under its new table. With G == 0 the call returns DOPF_OK
- * and does nothing. */
+ * and does nothing. While dopf_set_generator_energy_budget_windows holds a table a call with an array is DOPF_E_INVALID (one
+ * description of the budgets at a time); (NULL, NULL) stays allowed. */
 int dopf_set_generator_energy_budget(dopf_ctx *ctx, const double *e_min /* G; NULL = 0 */, const double *e_max /* G; NULL = +inf */);
 /* The budget prices (water values) of the decentral run: nu[g] is the multiplier the last computed x-update put on
  * generator g's budget row e_min[g] <= sum_t P[g,t] <= e_max[g] — the number the generator kernels add to gen_mc[g] to form the
@@ -553,8 +556,46 @@ int dopf_set_generator_energy_budget(dopf_ctx *ctx, const double *e_min /* G; NU
  * before it), and so does a dopf_iterate on a halted context, whose launches compute nothing. The trace (dopf_trace_*) does not
  * record the budget prices, and the multipliers of the ramp rows are not returned (on a DOPF_F2_GEN_RAMP_BUDGET context nu is the
  * budget row's multiplier alone). DOPF_E_UNSUPPORTED without DOPF_F2_GEN_ENERGY_BUDGET; DOPF_E_INVALID for a NULL pointer with
- * G > 0; with G == 0 the call returns DOPF_OK and does nothing. */
+ * G > 0; with G == 0 the call returns DOPF_OK and does nothing. While dopf_set_generator_energy_budget_windows holds a table the
+ * entry returns DOPF_E_INVALID: the prices are per window then, dopf_get_generator_budget_window_price. */
 int dopf_get_generator_budget_price(dopf_ctx *ctx, double *nu /* G */);
+/* Energy budgets per sub-window of the horizon, on a context created with DOPF_F2_GEN_ENERGY_BUDGET and without
+ * DOPF_F2_GEN_RAMP_BUDGET: copper plates, networks, the wide chain and DOPF_F_LONG_HORIZON (no flag of its own). Window j of n_win
+ * covers the timesteps win_end[j-1] <= t < win_end[j] with win_end[-1] = 0; the ends are strictly increasing, the last one is T and
+ * 1 <= n_win <= T. The table of ends is shared by all generators; the budgets are per generator and window, [j + n_win*g] in the
+ * caller's generator order (e_min NULL: all 0, e_max NULL: all +inf). While a table is set every generator's x-update keeps its
+ * objective and its box and obeys e_min[g,j] <= sum_{t in window j} P[g,t] <= e_max[g,j] for every j: the windows are disjoint, so
+ * the row separates into n_win problems of dopf_set_generator_energy_budget's kind, one multiplier each, and the step is the exact
+ * minimiser (k_gen_budget_win: a wave per (row, window)). One window with end T is dopf_set_generator_energy_budget, bit for bit.
+ * The first call with n_win >= 1 switches the context to that kernel and allocates device arrays of the context's own (the ends,
+ * the two tables and n_win x G prices, zeroed; DOPF_E_NOMEM, naming the bytes, where they do not fit). A call with another n_win
+ * than the stored one synchronises the stream, reallocates and drops the captured graphs; one with the same n_win copies, in order
+ * on the context's stream, into the arrays the graphs read (the graphs stay valid). n_win == 0 with all pointers NULL removes the
+ * table: the context is back on k_gen_budget and the graphs are dropped. Status as for dopf_set_generator_energy_budget: P, D, C,
+ * the duals and the iteration counter are kept, converged becomes 0. One description of the budgets at a time: the entry returns
+ * DOPF_E_INVALID while a non-default whole-horizon budget is stored (call dopf_set_generator_energy_budget(ctx, NULL, NULL)
+ * first), and while a table is set dopf_set_generator_energy_budget with an array and dopf_get_generator_budget_price return
+ * DOPF_E_INVALID and dopf_roll_horizon_coupled DOPF_E_UNSUPPORTED. Every refusal names the entry, g and j and stores nothing:
+ * DOPF_E_UNSUPPORTED without the flag and on a DOPF_F2_GEN_RAMP_BUDGET context (ramps couple neighbouring windows: the rows no
+ * longer separate); DOPF_E_INVALID for n_win < 0 or > T, a NULL win_end with n_win > 0, pointers with n_win == 0, ends that are
+ * not strictly increasing or do not end at T, a NaN, a negative or infinite e_min, e_max < 0, e_min > e_max, and
+ * e_min[g,j] > sum_{t in window j} cap[g,t] (the sum formed in t order under the stored availability table;
+ * dopf_set_generator_availability repeats that check window by window under its new table). With G == 0 the call returns DOPF_OK
+ * and does nothing. */
+int dopf_set_generator_energy_budget_windows(dopf_ctx *ctx, int32_t n_win, const int32_t *win_end /* n_win */,
+                                             const double *e_min /* n_win x G, [j + n_win*g]; NULL = all 0 */,
+                                             const double *e_max /* n_win x G, [j + n_win*g]; NULL = all +inf */);
+/* The stored table from the context's host copies (no device call); any pointer may be NULL. *n_win is 0 while no table is set, and
+ * nothing else is written then. win_end needs room for T values, e_min and e_max for n_win x G. */
+int dopf_get_generator_energy_budget_windows(dopf_ctx *ctx, int32_t *n_win, int32_t *win_end /* room for T */, double *e_min,
+                                             double *e_max);
+/* The window prices: nu[j + n_win*g] is the multiplier the last computed x-update put on window j's row of generator g, with the
+ * sign convention of dopf_get_generator_budget_price: 0 for a free window, for one whose clamped step keeps its budget and for one
+ * whose search gave up. k_gen_budget_win always stores them (no opt-in); before the first iteration after a set the values are what
+ * is stored, zeros after an allocation. At convergence nu[g,j] is minus the central LP's dual of that row wherever it is unique.
+ * Works while a trace is active; the trace does not record the prices. DOPF_E_INVALID while no table is set and for a NULL
+ * pointer; with G == 0 the call returns DOPF_OK and does nothing. */
+int dopf_get_generator_budget_window_price(dopf_ctx *ctx, double *nu /* n_win x G, [j + n_win*g] */);
 /* The ramp prices of the decentral run: rp[t + T*g] is the multiplier the last computed x-update put on generator
  * g's ramp row -ramp_down <= P[g,t] - P[g,t-1] <= ramp_up between t-1 and t (t = 0: the anchor's row against p_prev, 0 without an
  * anchor) — what one more unit per step of flexibility of unit g is worth at step t, in the unit of gen_mc, in the caller's
@@ -633,7 +674,8 @@ int dopf_roll_horizon(dopf_ctx *ctx, int32_t k, const double *demand_tail /* N x
  * n_profiles == -1 and set_budget == 0, the entry is dopf_roll_horizon bit for bit; with G == 0 the generator part does nothing.
  * Status, the warm-start summaries and timing as after dopf_roll_horizon; the graphs stay valid (a table larger than any before
  * follows dopf_set_generator_availability's rule: a new allocation, and the graphs are captured again). While a trace is active the
- * entry works as the setters do. There is no dopf_multi_* wrapper. */
+ * entry works as the setters do. There is no dopf_multi_* wrapper. While dopf_set_generator_energy_budget_windows holds a table
+ * the entry returns DOPF_E_UNSUPPORTED with nothing changed: remove the table, roll, and set the next window's table. */
 int dopf_roll_horizon_coupled(dopf_ctx *ctx, int32_t k, const double *demand_tail /* N x k, [n + N*j] */,
                               int32_t n_profiles /* -1: the table stays */, const double *profiles /* n_profiles x T, [t + T*p] */,
                               const int32_t *profile_of /* G */, int32_t set_budget, const double *e_min /* G; NULL = 0 */,
@@ -853,6 +895,12 @@ int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, c
 int dopf_multi_set_generator_min_output(dopf_multi *m, const double *p_min);
 /* dopf_get_generator_budget_price of all shards' rows in the caller's order, like dopf_multi_get_primal: G values */
 int dopf_multi_get_generator_budget_price(dopf_multi *m, double *nu /* G */);
+/* dopf_set_generator_energy_budget_windows for all G generators: the ends are replicated, each shard gets the rows of its
+ * generators ([j + n_win*g]: a slice); all or nothing, as the other dopf_multi_set_* entries */
+int dopf_multi_set_generator_energy_budget_windows(dopf_multi *m, int32_t n_win, const int32_t *win_end, const double *e_min,
+                                                   const double *e_max);
+/* dopf_get_generator_budget_window_price of all shards' rows in the caller's order: n_win x G values */
+int dopf_multi_get_generator_budget_window_price(dopf_multi *m, double *nu /* n_win x G */);
 /* dopf_get_generator_ramp_price of all shards' rows in the caller's order, like dopf_multi_get_primal: T*G values */
 int dopf_multi_get_generator_ramp_price(dopf_multi *m, double *rp /* T*G, [t + T*g] */);
 /* Shard i's context: duals, consensus state, residuals and prices are replicated, read them from
