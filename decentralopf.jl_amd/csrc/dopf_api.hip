@@ -2035,19 +2035,15 @@ int dopf_get_generator_ramp_price(dopf_ctx *c, double *rp)
         HIPCHK(c, hipStreamSynchronize(c->main));
         size_t freeb = 0, totalb = 0;
         HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
-        void *p = nullptr;
-        hipError_t e = need > freeb ? hipErrorOutOfMemory : hipMalloc(&p, need);
-        if (e == hipSuccess) {
-            c->allocs.push_back(p);
-            e = hipMemset(p, 0, need);
-        }
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, e == hipErrorOutOfMemory ? DOPF_E_NOMEM : DOPF_E_DEVICE,
-                        "dopf_get_generator_ramp_price: the ramp prices (T x G doubles) need %llu bytes, the device has %llu free: %s", need,
-                        (unsigned long long)freeb, hipGetErrorString(e));
-        }
-        c->plan.genRampPrice = (double *)p;
+        if (need > freeb)
+            return fail(c, DOPF_E_NOMEM, "dopf_get_generator_ramp_price: the ramp prices (T x G doubles) need %llu bytes, the device has %llu free",
+                        need, (unsigned long long)freeb);
+        // dev_alloc, as every other array of the context: under DOPF_GUARD the block ends on the last bytes of its own mapping, and it
+        // is zeroed on the context's stream — c->main does not wait for the null stream (hipStreamNonBlocking), so a hipMemset there
+        // would not be ordered before the copy below, which then returns what the block held before
+        double *p = nullptr;
+        if (int rc = dev_alloc(c, &p, G * T, true)) return rc;
+        c->plan.genRampPrice = p;
         drop_graphs(c);
     }
     std::vector<double> h(G * T);

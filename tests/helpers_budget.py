@@ -184,3 +184,49 @@ def budget_kkt_violation(P, grad, cap, e_min, e_max, tol=1e-9):
     mid = 0.5 * (Lb + Ub) if np.isfinite(Lb) and np.isfinite(Ub) else (Lb if np.isfinite(Lb) else Ub if np.isfinite(Ub) else 0.0)
     nu = min(max(mid, A), B)
     return infeas, max(Lb - nu, nu - Ub, 0.0), nu
+
+
+def stationarity_at(P, grad, cap, nu, tol=1e-9):
+    """the largest violation of  grad_t + nu = 0 inside the box, >= 0 at 0, <= 0 at the cap  with nu GIVEN (helpers_budget's
+    budget_kkt_violation fits a nu; this one does not); a box of one point asks nothing"""
+    scale = max(1.0, float(np.max(cap)))
+    r = np.asarray(grad, dtype=np.float64) + nu
+    at_lo, at_hi = P <= tol * scale, P >= cap - tol * scale
+    worst = 0.0
+    if np.any(~at_hi):
+        worst = max(worst, float(np.max(-r[~at_hi])))            # may not want to go up
+    if np.any(~at_lo):
+        worst = max(worst, float(np.max(r[~at_lo])))             # may not want to go down
+    return max(worst, 0.0)
+
+
+# ---- budgets per sub-window ---------------------------------------------------------------------------------------------------------------
+
+def _slices(ends):
+    return [slice(0 if j == 0 else ends[j - 1], ends[j]) for j in range(len(ends))]
+
+
+def _unit_budgets(pp, steps, cap, ends):
+    """(e_min, e_max) of shape (G, n_win): every (row, window) unit's class dealt by draw_budgets_by_state from the unit's own clamped-step
+    sum and cap sum (both added in t order). Two deals are formed — one over all units, rows outermost, and one window by window — and
+    the one whose smallest class (binding above, binding below, free: by the reference alone) is larger is taken. Neither serves every
+    shape: one deal over six units gives 3xT600 a single free unit whatever the state, and window by window the one-step windows of 7x5
+    leave six of 35 units to bind below (the CPU oracle's warm-up state gives the same counts as the device's)"""
+    sl = _slices(ends)
+    x0 = [budget_project(steps[g], cap[g]) for g in range(pp.G)]
+    S = np.array([[row_sums([x0[g][s]])[0] for s in sl] for g in range(pp.G)])
+    room = np.array([[row_sums([cap[g][s]])[0] for s in sl] for g in range(pp.G)])
+    lo, hi, _ = draw_budgets_by_state(S.ravel(), room.ravel())
+    deals = [(lo.reshape(S.shape), hi.reshape(S.shape)), (np.zeros(S.shape), np.full(S.shape, np.inf))]
+    for j in range(len(ends)):
+        deals[1][0][:, j], deals[1][1][:, j], _ = draw_budgets_by_state(S[:, j], room[:, j])
+
+    def smallest_class(deal):
+        sides = []
+        for g in range(pp.G):
+            for j, s in enumerate(sl):
+                info = {}
+                budget_project(steps[g][s], cap[g][s], deal[0][g, j], deal[1][g, j], info)
+                sides.append(info["side"])
+        return min(sides.count(k) for k in (1, -1, 0))
+    return max(deals, key=smallest_class)

@@ -1,8 +1,9 @@
 """Bounded, seeded slices of the two fuzzers of the later features in guard mode (DOPF_GUARD=1: every device array of the library
 ends on the last bytes of its own mapping, so an access past an array's end is a fault that names it): scripts/fuzz_lossy_rated.py
 (storage efficiencies and line ratings against the oracle) and scripts/fuzz_gen_coupling.py (quadratic costs, ramps on plates and
-networks, energy budgets, and ramps with budgets: rows against the NumPy references, the whole state against a forced-step oracle
-twin, iterate(n) against single steps, shards against one context). Each slice runs in a fresh child process with fixed seeds, as
+networks, energy budgets, ramps with budgets, must-run floors and budgets per sub-window, with the budget and ramp prices recorded in
+every second case: rows against the NumPy references, the prices against their certificates and NumPy twins, the whole state against
+a forced-step oracle twin, iterate(n) against single steps, shards against one context). Each slice runs in a fresh child process with fixed seeds, as
 tests/test_gpu_fuzz.py's do, and passes when the script exits 0 and reports `bad 0` with no MISMATCH and no SOLVER FAILURES line.
 tests/test_fuzz_reference_only.py settles on the CPU that the coupling slices' first steps leave and keep the kernels' fast paths
 often enough."""
@@ -18,14 +19,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # script, families (fuzz_gen_coupling's --families), cases, seed, seconds measured on an MI355X (library load included)
 SLICES = [
     ("fuzz_lossy_rated", None, 30, 431, 5.2),
-    ("fuzz_gen_coupling", "c2", 12, 456, 1.7),
-    ("fuzz_gen_coupling", "ramp-plate", 12, 442, 4.0),
-    ("fuzz_gen_coupling", "ramp-net", 12, 443, 3.8),
-    ("fuzz_gen_coupling", "budget-plate", 12, 444, 2.6),
-    ("fuzz_gen_coupling", "budget-net", 12, 445, 5.1),
-    ("fuzz_gen_coupling", "pair", 4, 446, 7.1),            # (the pair's twelve cases in three slices: its reference bisects)
-    ("fuzz_gen_coupling", "pair", 4, 447, 5.9),
-    ("fuzz_gen_coupling", "pair", 4, 448, 7.9),
+    ("fuzz_gen_coupling", "c2", 12, 456, 2.1),
+    ("fuzz_gen_coupling", "ramp-plate", 12, 442, 4.6),
+    ("fuzz_gen_coupling", "ramp-net", 12, 443, 4.3),
+    ("fuzz_gen_coupling", "budget-plate", 12, 444, 3.6),
+    ("fuzz_gen_coupling", "budget-net", 12, 445, 6.1),
+    ("fuzz_gen_coupling", "pair", 4, 446, 8.0),            # (the pair's twelve cases in three slices: its reference bisects)
+    ("fuzz_gen_coupling", "pair", 4, 447, 6.5),
+    ("fuzz_gen_coupling", "pair", 4, 448, 9.1),
+    ("fuzz_gen_coupling", "ramp-plate", 12, 500, 4.3),     # (ramp prices at T = 1, 2 and 127..130, which seed 442 does not draw)
+    ("fuzz_gen_coupling", "floor-plate", 12, 549, 5.5),
+    ("fuzz_gen_coupling", "floor-net", 12, 500, 3.3),
+    ("fuzz_gen_coupling", "window-plate", 12, 500, 4.0),
+    ("fuzz_gen_coupling", "window-net", 12, 501, 3.4),
 ]
 COUPLING = [s for s in SLICES if s[0] == "fuzz_gen_coupling"]
 

@@ -10,7 +10,8 @@ import pytest
 from conftest import pkg
 from decentralopf_jl_amd import _capi, central, synth
 from helpers import draw_profiles, make_engine, set_from, state_of
-from helpers_budget import BUDGET, CHAIN, budget_engine, budget_project, draw_budgets, draw_budgets_by_state, plate_steps, row_sums
+from helpers_budget import (BUDGET, CHAIN, budget_engine, budget_project, draw_budgets, draw_budgets_by_state, plate_steps, row_sums,
+                            stationarity_at)
 from helpers_min_output import all_state, same_bits
 from helpers_quadratic import QC, draw_c2, params_of
 from helpers_ramp import ramp_infeasibility, ramp_project, step_centres
@@ -57,20 +58,6 @@ def _grad(pp, c2, before, prm, P):
         return phi_gen(pp, c2, before, GAMMA, W_FLOW, P)
     d = P - before["P"]
     return pp.gen_mc[:, None] + np.asarray(c2)[:, None] * P + before["lam"][None, :] + prm["gamma"] * (before["inj"].sum(axis=0)[None, :] + d) + d
-
-
-def stationarity_at(P, grad, cap, nu, tol=1e-9):
-    """the largest violation of  grad_t + nu = 0 inside the box, >= 0 at 0, <= 0 at the cap  with nu GIVEN (helpers_budget's
-    budget_kkt_violation fits a nu; this one does not); a box of one point asks nothing"""
-    scale = max(1.0, float(np.max(cap)))
-    r = np.asarray(grad, dtype=np.float64) + nu
-    at_lo, at_hi = P <= tol * scale, P >= cap - tol * scale
-    worst = 0.0
-    if np.any(~at_hi):
-        worst = max(worst, float(np.max(-r[~at_hi])))            # may not want to go up
-    if np.any(~at_lo):
-        worst = max(worst, float(np.max(r[~at_lo])))             # may not want to go down
-    return max(worst, 0.0)
 
 
 def check_sign(nu, P, lo, hi, cap, free):

@@ -15,12 +15,11 @@ import pytest
 
 from decentralopf_jl_amd import _capi, central, synth
 from helpers import make_engine, set_from, state_of
-from helpers_budget import (BUDGET, CHAIN, budget_engine, budget_kkt_violation, budget_project, budget_violation, draw_budgets_by_state,
-                            row_sums)
+from helpers_budget import (BUDGET, CHAIN, _slices, _unit_budgets, budget_engine, budget_kkt_violation, budget_project, budget_violation,
+                            draw_budgets_by_state, row_sums, stationarity_at)
 from helpers_quadratic import QC, draw_c2, params_of
 from helpers_budget import x_of
 from test_gpu_gen_budget import CONV, EXTRAS, SHAPES, _chain, _close, _grad, _prm, _profiles, _steps, swing
-from test_gpu_gen_budget_price import stationarity_at
 
 pytestmark = pytest.mark.gpu
 AV = _capi.F_GEN_AVAILABILITY
@@ -38,10 +37,6 @@ WINDOWS = {
     "net-12xT4-wide-chain": ("net-12xT4-wide-chain", (1, 4)),
 }
 PAIRS = ("plain", "availability+c2")
-
-
-def _slices(ends):
-    return [slice(0 if j == 0 else ends[j - 1], ends[j]) for j in range(len(ends))]
 
 
 def _window_profiles(pp, rng, ends):
@@ -84,32 +79,6 @@ def _setup(hip_api, shape, extra, eager, ends=()):
     before = state_of(h)
     steps = _steps(pp, c2, before, prm)
     return pp, prm, h, twin, c2, cap, steps, before, (st, it, flags)
-
-
-def _unit_budgets(pp, steps, cap, ends):
-    """(e_min, e_max) of shape (G, n_win): every (row, window) unit's class dealt by draw_budgets_by_state from the unit's own clamped-step
-    sum and cap sum (both added in t order). Two deals are formed — one over all units, rows outermost, and one window by window — and
-    the one whose smallest class (binding above, binding below, free: by the reference alone) is larger is taken. Neither serves every
-    shape: one deal over six units gives 3xT600 a single free unit whatever the state, and window by window the one-step windows of 7x5
-    leave six of 35 units to bind below (the CPU oracle's warm-up state gives the same counts as the device's)"""
-    sl = _slices(ends)
-    x0 = [budget_project(steps[g], cap[g]) for g in range(pp.G)]
-    S = np.array([[row_sums([x0[g][s]])[0] for s in sl] for g in range(pp.G)])
-    room = np.array([[row_sums([cap[g][s]])[0] for s in sl] for g in range(pp.G)])
-    lo, hi, _ = draw_budgets_by_state(S.ravel(), room.ravel())
-    deals = [(lo.reshape(S.shape), hi.reshape(S.shape)), (np.zeros(S.shape), np.full(S.shape, np.inf))]
-    for j in range(len(ends)):
-        deals[1][0][:, j], deals[1][1][:, j], _ = draw_budgets_by_state(S[:, j], room[:, j])
-
-    def smallest_class(deal):
-        sides = []
-        for g in range(pp.G):
-            for j, s in enumerate(sl):
-                info = {}
-                budget_project(steps[g][s], cap[g][s], deal[0][g, j], deal[1][g, j], info)
-                sides.append(info["side"])
-        return min(sides.count(k) for k in (1, -1, 0))
-    return max(deals, key=smallest_class)
 
 
 CASES = [(n, x) for n in WINDOWS for x in PAIRS]

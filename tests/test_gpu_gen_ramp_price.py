@@ -206,6 +206,24 @@ def test_the_getter_moves_nothing(hip_api, which):
     assert same_bits(all_state(a), all_state(c)) and np.array_equal(a.ramp_price(), c.ramp_price()) and np.any(c.ramp_price() != 0.0)
 
 
+@pytest.mark.parametrize("name", ["7x5", "3x130"])
+def test_the_first_call_returns_zeros_in_a_block_that_held_prices(hip_api, name):
+    """Four contexts of one shape, one after the other: each records a step's prices and is destroyed, so the next one's first call
+    is handed a block of the size just freed. Its zeros must be the call's own — ordered on the context's stream before the copy that
+    returns them. (scripts/fuzz_gen_coupling.py's floor-plate slice found the first call returning what the block held before: the
+    array was zeroed on the null stream, which the context's non-blocking stream does not wait for.)"""
+    d = price_plate(name, False, 11)
+    pp = d["pp"]
+    for k in range(4):
+        h = _engine(hip_api, d, False, True)
+        first = h.ramp_price()
+        assert np.array_equal(first, np.zeros((pp.G, pp.T))), (k, int(np.count_nonzero(first)))
+        set_from(h, d["st"], 2)
+        h.iterate(1)
+        assert np.any(h.ramp_price() != 0.0)
+        h.close()
+
+
 # ---- 4. the status rules -----------------------------------------------------------------------------------------------------------------
 
 def _small():
