@@ -172,6 +172,11 @@ class CApi:
         self._opt("get_generator_budget_window_price", C.c_int, [ctxp, c_double_p])
         self._opt("multi_set_generator_energy_budget_windows", C.c_int, [ctxp, C.c_int32, c_int32_p, c_double_p, c_double_p])
         self._opt("multi_get_generator_budget_window_price", C.c_int, [ctxp, c_double_p])
+        # must-run floors on budget contexts (Engine.set_budget_min_output, .budget_min_output and MultiEngine's): no flag of their own
+        # either, and the extension tables are full — beside them, as the window entries
+        self._opt("set_generator_budget_min_output", C.c_int, [ctxp, c_double_p])
+        self._opt("get_generator_budget_min_output", C.c_int, [ctxp, c_double_p])
+        self._opt("multi_set_generator_budget_min_output", C.c_int, [ctxp, c_double_p])
         # the ramp rows' multipliers of the last x-update (Engine.ramp_price, MultiEngine.ramp_price)
         self._opt("get_generator_ramp_price", C.c_int, [ctxp, c_double_p])
         self._opt("multi_get_generator_ramp_price", C.c_int, [ctxp, c_double_p])
@@ -569,6 +574,25 @@ class _ExtensionSetters:
         self._mirror["gen_budget_windows"] = (ends.copy(), None if lo is None else lo.reshape(self.G, ends.size).copy(),
                                               None if hi is None else hi.reshape(self.G, ends.size).copy())
 
+    def set_budget_min_output(self, p_min=None):
+        """dopf_set_generator_budget_min_output (MultiEngine: dopf_multi_...): must-run floors on a budget context — every row's box
+        becomes min(p_min, cap) <= P <= cap, the budgets' multiplier search runs inside it, and rows and windows without a budget are
+        clamped to it too. p_min: G values in [0, gen_pmax] in the caller's order; None removes the floors (the context runs the
+        kernels without them again). An array of zeros is an array: the floor kernels with nothing to hold. Needs F2_GEN_ENERGY_BUDGET
+        and no F_GEN_RAMP (ramp contexts have set_min_output). A row whose floors sum above its e_max (or a window's) is refused,
+        here and by the budget, window, availability and coupled-roll entries under their new values. P, D, C, the duals and the
+        iteration counter stay; converged becomes False. A backend without the entry: DopfError."""
+        name = self._entry_prefix + "set_generator_budget_min_output"
+        fn = getattr(self.api, name, None)
+        if fn is None:
+            raise DopfError(f"{self.api.prefix}*: this API has no {name}")
+        a = None if p_min is None else _f64(p_min, self.G)
+        self._chk(fn(self._handle(), _dp(a)))
+        if a is None:
+            self._mirror.pop("gen_budget_min_output", None)
+        else:
+            self._mirror["gen_budget_min_output"] = a.copy()
+
     def _budget_window_price(self, handle, n_win: int) -> np.ndarray:
         name = self._entry_prefix + "get_generator_budget_window_price"
         if not hasattr(self.api, name):
@@ -598,13 +622,15 @@ class Engine(_ExtensionSetters):
     [0, gen_pmax]): the generators' must-run floors — sets F_GEN_RAMP (on a network F_GEN_RAMP_NETWORK too: the floors run on the ramp
     kernels) and calls dopf_set_generator_min_output behind the ramps; all zeros is what None says. gen_budget_windows = (win_end,
     e_min, e_max) (optional; (G, n_win) budgets, either may be None): energy budgets per sub-window — sets F2_GEN_ENERGY_BUDGET and calls
-    dopf_set_generator_energy_budget_windows behind everything else."""
+    dopf_set_generator_energy_budget_windows behind everything else. gen_budget_min_output (optional, G values in [0, gen_pmax]): must-run
+    floors on a budget context — sets F2_GEN_ENERGY_BUDGET and calls dopf_set_generator_budget_min_output last of all (its check reads the
+    budgets and the window table)."""
 
     def __init__(self, api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None,
                  mode: Optional[int] = None, sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None,
                  sto_eta=None, line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0,
-                 gen_min_output=None, gen_budget_windows=None):
+                 gen_min_output=None, gen_budget_windows=None, gen_budget_min_output=None):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
@@ -615,7 +641,9 @@ class Engine(_ExtensionSetters):
             gen_min_output=gen_min_output))
         self.params = params if params is not None else default_params()
         # (a table of budgets per sub-window runs on a budget context: it asks for the budgets' flag)
-        self.flags2 = int(flags2) | _flags2(todo, self.L) | (F2_GEN_ENERGY_BUDGET if gen_budget_windows is not None else 0)
+        # (and so do floors on budget rows)
+        self.flags2 = int(flags2) | _flags2(todo, self.L) | (
+            F2_GEN_ENERGY_BUDGET if gen_budget_windows is not None or gen_budget_min_output is not None else 0)
         _needs_create_ex(api, self.flags2)
         # what a window change needs of the problem: the arrays as handed to create, and the inputs of the setters as they stand
         # (by constructor keyword, in the form the constructor takes them)
@@ -634,6 +662,8 @@ class Engine(_ExtensionSetters):
         self._apply(todo)
         if gen_budget_windows is not None:          # (behind the tables' to-do list: its check reads the availability's caps)
             self.set_energy_budget_windows(*gen_budget_windows)
+        if gen_budget_min_output is not None:       # (last: its check reads the budgets and the window table)
+            self.set_budget_min_output(gen_budget_min_output)
 
     def _handle(self):
         return self._ctx
@@ -819,6 +849,15 @@ class Engine(_ExtensionSetters):
         duals and the iteration counter stay; converged becomes False. Takes effect at the next x-update. A backend without the
         entry: DopfError (unsupported)."""
         self._mirror.update(self._set("set_min_output", p_min))
+
+    def budget_min_output(self) -> np.ndarray:
+        """dopf_get_generator_budget_min_output: the floors of set_budget_min_output as the context holds them, G values (zeros while
+        none are set). A backend without the entry: DopfError."""
+        if not hasattr(self.api, "get_generator_budget_min_output"):
+            raise DopfError(f"{self.api.prefix}*: this API has no get_generator_budget_min_output")
+        out = np.zeros(self.G)
+        self._chk(self.api.get_generator_budget_min_output(self._ctx, _dp(out)))
+        return out
 
     def min_output(self) -> np.ndarray:
         """dopf_get_generator_min_output: the floors as the context holds them, G values. A backend without the entry: DopfError."""
@@ -1151,7 +1190,8 @@ class MultiEngine(_ExtensionSetters):
     def __init__(self, api: CApi, n_gpus: int, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
                  sto_mc, sto_pmax, sto_emax, sto_node, params: Optional[DopfParams] = None, devices=None, sto_e0=None,
                  sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None, line_rating=None, gen_c2=None,
-                 gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0, gen_min_output=None, gen_budget_windows=None):
+                 gen_ramp=None, gen_prev=None, gen_budget=None, flags2: int = 0, gen_min_output=None, gen_budget_windows=None,
+                 gen_budget_min_output=None):
         self.api = api
         self.N, self.L, self.T = int(N), int(L), int(T)
         prob, keep, self.G, self.S = _problem(self.N, self.L, self.T, demand, ptdf, f_max, gen_mc, gen_pmax, gen_node,
@@ -1161,7 +1201,9 @@ class MultiEngine(_ExtensionSetters):
             sto_eta=sto_eta, line_rating=line_rating, gen_c2=gen_c2, gen_ramp=gen_ramp, gen_prev=gen_prev, gen_budget=gen_budget,
             gen_min_output=gen_min_output))
         self.params = params if params is not None else default_params()
-        self.flags2 = int(flags2) | _flags2(todo, self.L) | (F2_GEN_ENERGY_BUDGET if gen_budget_windows is not None else 0)
+        # (and so do floors on budget rows)
+        self.flags2 = int(flags2) | _flags2(todo, self.L) | (
+            F2_GEN_ENERGY_BUDGET if gen_budget_windows is not None or gen_budget_min_output is not None else 0)
         _needs_create_ex(api, self.flags2)
         dev = None if devices is None else _i32(devices, n_gpus)
         self._m = C.c_void_p()
@@ -1175,6 +1217,8 @@ class MultiEngine(_ExtensionSetters):
         self._apply(todo)
         if gen_budget_windows is not None:
             self.set_energy_budget_windows(*gen_budget_windows)
+        if gen_budget_min_output is not None:
+            self.set_budget_min_output(gen_budget_min_output)
 
     def _handle(self):
         return self._m
@@ -1289,6 +1333,13 @@ class MultiEngine(_ExtensionSetters):
         return _ShardView(self.api, ctx, self.N, self.L, self.T, cut(self.G), cut(self.S))
 
 
+def _no_budget_floors(gen_budget_min_output) -> None:
+    """The device LP's front ends refuse floors on budget rows as they refuse gen_min_output."""
+    if gen_budget_min_output is not None and np.any(np.asarray(gen_budget_min_output, dtype=np.float64) != 0.0):
+        raise DopfError("dopf_central_solve*: the device LP takes no generator minimum output (its generators' lower bound is 0); use "
+                        "central.solve_central_packed(..., gen_budget=, gen_min_output=) for a budget case with a floor")
+
+
 def _no_budget_windows(gen_budget_windows) -> None:
     """The device LP's front ends refuse a case with budgets per sub-window, as they refuse floors."""
     if gen_budget_windows is not None:
@@ -1300,7 +1351,7 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
                   sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                   sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
                   line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, gen_min_output=None,
-                  gen_budget_windows=None) -> dict:
+                  gen_budget_windows=None, gen_budget_min_output=None) -> dict:
     """dopf_central_solve: the central reference (src/opf_central_reference.jl) as one LP solved on the GPU by a first-order
     primal-dual method. Arguments as Engine (PackedProblem.engine_kwargs()). Returns objective, gap, iterations and the
     reference script's outputs in Julia shapes: P (G,T), D/C/E (S,T), system_price (T), nodal_price (N,T),
@@ -1316,11 +1367,13 @@ def central_solve(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, gen_pmax, 
     gen_budget: nor energy budgets; an e_min above 0 or a finite e_max raises DopfError.
     gen_min_output: nor must-run floors; a value above 0 raises DopfError.
     gen_budget_windows: nor budgets per sub-window; a table raises DopfError.
+    gen_budget_min_output: nor floors on budget rows; a value above 0 raises DopfError.
     T: any horizon. Beyond 512 timesteps the storages run on the long sweep (kc_sto_long); the entry sets DOPF_F_LONG_HORIZON on its own
     context, so params needs no flag, and with F_LONG_HORIZON in params the result is the same bits. F_DEBUG_LONG_STO in params runs
     that sweep at T <= 512 too (tests)."""
     N, L, T = int(N), int(L), int(T)
     _no_budget_windows(gen_budget_windows)
+    _no_budget_floors(gen_budget_min_output)
     if gen_min_output is not None and np.any(np.asarray(gen_min_output, dtype=np.float64) != 0.0):
         raise DopfError("dopf_central_solve*: the device LP takes no generator minimum output (its generators' lower bound is 0); use "
                         "central.solve_central_packed(..., gen_min_output=) for a case with a floor")
@@ -1373,7 +1426,7 @@ def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, ge
                           sto_node, tol: float = 1e-8, max_iters: int = 200000, params: Optional[DopfParams] = None,
                           sto_e0=None, sto_end_lo=None, sto_end_hi=None, gen_avail=None, gen_avail_of=None, sto_eta=None,
                           line_rating=None, gen_c2=None, gen_ramp=None, gen_prev=None, gen_budget=None, gen_min_output=None,
-                          gen_budget_windows=None) -> dict:
+                          gen_budget_windows=None, gen_budget_min_output=None) -> dict:
     """dopf_central_solve_coupled: central_solve's LP with the constraints that couple a generator's timesteps and with per-timestep
     line limits. Arguments as Engine (PackedProblem.engine_kwargs()); beyond central_solve's:
     line_rating (L, T): the limits of the flow rows, as Engine takes them (None: f_max in every timestep).
@@ -1388,6 +1441,7 @@ def central_solve_coupled(api: CApi, *, N, L, T, demand, ptdf, f_max, gen_mc, ge
     params needs no flag for it. F_DEBUG_LONG_STO in params runs those sweeps at T <= 512 too (tests)."""
     N, L, T = int(N), int(L), int(T)
     _no_budget_windows(gen_budget_windows)
+    _no_budget_floors(gen_budget_min_output)
     if gen_c2 is not None and np.any(np.asarray(gen_c2, dtype=np.float64) != 0.0):
         raise DopfError("dopf_central_solve_coupled: the device LP takes no quadratic generator costs (it solves with gen_mc alone)")
     if gen_min_output is not None and np.any(np.asarray(gen_min_output, dtype=np.float64) != 0.0):

@@ -256,6 +256,20 @@ class ADMM:
         self.engine.set_min_output(p_min)
         self._replaced("gen_min_output", p_min, (self.packed.G,))
 
+    def set_budget_min_output(self, p_min=None) -> None:
+        """Must-run floors on a run with energy budgets (G values in [0, max_generation] in the order of `generators`; None removes
+        them): min(p_min, cap[t]) <= P[t] <= cap[t] inside the budgets' own step — a reservoir's minimum flow beside its water
+        allotment. The floor holds for every generator, budgeted or not, whole-horizon budgets and budgets per sub-window alike. Not in
+        the reference. Needs F2_GEN_ENERGY_BUDGET and no F_GEN_RAMP (there set_min_output serves); a generator whose floors sum above
+        its energy_max (or a window's) is refused. The state and the iteration counter stay, the run is no longer converged; takes
+        effect at the next iteration. budget_price and budget_window_price keep their meaning."""
+        self.engine.set_budget_min_output(p_min)
+        self._replaced("gen_budget_min_output", p_min, (self.packed.G,))
+
+    def budget_min_output(self) -> np.ndarray:
+        """The floors of set_budget_min_output as the context holds them, G values (zeros while none are set)."""
+        return self.engine.budget_min_output()
+
     def _replaced(self, field_: str, value, shape) -> None:
         """the packed problem follows an input that was replaced under a kept state, and the run is no longer converged"""
         setattr(self.packed, field_, None if value is None else np.asarray(value, dtype=np.float64).reshape(shape).copy())

@@ -107,6 +107,8 @@ def solve_central_packed(pp: PackedProblem, *, duals: bool = True, initial_level
         ub[:nP] = np.where((of >= 0)[:, None], pm[:, None] * f, pm[:, None]).reshape(-1)      # one multiply, as the kernels
     if gen_min_output is None and pp.has_min_output():
         gen_min_output = pp.min_output()
+    if gen_min_output is None and getattr(pp, "gen_budget_min_output", None) is not None:
+        gen_min_output = pp.gen_budget_min_output          # (floors on a budget context are the same lower bounds to the LP)
     if gen_min_output is not None and G > 0:
         lb = np.array(lb, dtype=np.float64)
         lb[:nP] = np.minimum(np.repeat(np.asarray(gen_min_output, dtype=np.float64).reshape(G), T), ub[:nP])

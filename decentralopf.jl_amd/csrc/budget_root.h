@@ -41,7 +41,18 @@ DOPF_BR_FN int budget_piece(double u, double cap, int interval)
     return 2 + interval;
 }
 
-// a running summary of the pieces of a probe (the row's own loop over t feeds it; a wave then reduces the four flags with AND)
+// ... of a timestep whose box is [floor, cap] (dopf_set_generator_budget_min_output; floor = fmin(p_min, cap) >= 0): one
+// point where !(cap > floor), piece 0 on the floor, piece 1 on the cap. At floor = 0 the three-argument function's values
+DOPF_BR_FN int budget_piece(double u, double floor, double cap, int interval)
+{
+    if (!(cap > floor)) return kBudgetFixed;
+    if (u <= floor) return 0;
+    if (u >= cap) return 1;
+    return 2 + interval;
+}
+
+// a running summary of the pieces of a probe (the row's own loop over t feeds it; a wave then reduces the four flags with AND).
+// With floors "atLo" reads "every step on its floor" (piece 0 is the box's lower end, whatever it is): nothing changes here
 struct BudgetSame {
     bool sameA = true, sameB = true, atLo = true, atHi = true;
     DOPF_BR_FN void add(int pa, int pm, int pb)
@@ -61,7 +72,8 @@ struct BudgetSame {
 // A probe that meets the bound exactly ends the search: it is a root (e_max = 0 and e_min = sum cap end this way).
 // 1. bracket: a = 0, b = +-step, doubled until phi(b) crosses the bound (a follows: phi(a) stays strictly beyond it). A probe at
 //    which nothing can move further (atLo going up, atHi going down) ends the search there: the bound is the box's own sum, up to
-//    the rounding of that sum.
+//    the rounding of that sum. With floors (the four-argument budget_piece) a search going up that ends this way ends on
+//    e_max = sum floor, the smallest bound dopf_set_generator_budget_min_output allows: the search itself needs no change.
 // 2. refinement: while some timestep changes its piece between a and b, probe a point strictly inside — the midpoint and the secant
 //    point in turn — and keep the half that holds the root. The pieces' breakpoints are finitely many and the midpoint steps halve
 //    the bracket, so either no breakpoint is left strictly inside (phi is linear on [a, b]: one division) or no double is left

@@ -307,6 +307,86 @@ static int ramp_budget_rows_fit(dopf_ctx *c, const char *entry, bool given_ramp,
     return DOPF_OK;
 }
 
+// dopf_set_generator_budget_min_output: a row with a floor must be able to stay under its maximum — the sum of
+// floor[g,t] = min(p_min, cap[g,t]) over t0 <= t < t1, formed in t order, is at most e_max. With e_min <= sum cap (budget_min_fits,
+// budget_win_min_fits) the test is exact: every step's box is non-empty, so the reachable sums are exactly [sum floor, sum cap].
+// g: the caller's index (the message's); j: the window, -1 for the whole horizon; f: the generator's profile, or null
+static int budget_floor_fits(dopf_ctx *c, const char *entry, int g, int j, int t0, int t1, double pm, double p_min, double e_max, const double *f)
+{
+    if (e_max == INFINITY) return DOPF_OK;
+    double need = 0.0;
+    for (int t = t0; t < t1; ++t) need += std::min(p_min, f ? pm * f[t] : pm);
+    if (need <= e_max) return DOPF_OK;
+    if (j < 0)
+        return fail(c, DOPF_E_INVALID, "%s: generator g = %d cannot stay under e_max = %g on its floors (p_min = %g: sum_t min(p_min, cap[g,t]) = %g)",
+                    entry, g, e_max, p_min, need);
+    return fail(c, DOPF_E_INVALID, "%s: generator g = %d cannot stay under e_max = %g in window j = %d (t = %d .. %d) on its floors (p_min = %g: their "
+                                   "sum is %g)", entry, g, e_max, j, t0, t1 - 1, p_min, need);
+}
+
+// what a caller of budget_floor_rows_fit replaces of the stored values (all in the caller's order; a `given` flag says whether the call
+// sets that part — a NULL behind it then means the default)
+struct BudgetFloorGiven {
+    const double *p_min = nullptr;                                  // the floors (null: the stored ones)
+    bool budget = false; const double *e_max = nullptr;             // dopf_set_generator_energy_budget
+    bool windows = false; int n_win = 0; const int32_t *win_end = nullptr; const double *win_max = nullptr;   // ..._energy_budget_windows
+    bool table = false; const double *profiles = nullptr; const int32_t *profile_of = nullptr;                // dopf_set_generator_availability
+};
+
+// ... for every row with a floor above 0, against its whole-horizon e_max and every window's
+static int budget_floor_rows_fit(dopf_ctx *c, const char *entry, const BudgetFloorGiven &n)
+{
+    if (!c->plan.genBudget || c->plan.genRamp || (!n.p_min && !c->plan.genBudgetMinOut)) return DOPF_OK;
+    const size_t G = (size_t)c->v.G;
+    const int T = c->v.T;
+    const int nw = n.windows ? n.n_win : (int)c->gen_bw_end_h.size();
+    const int32_t *ends = n.windows ? n.win_end : c->gen_bw_end_h.data();
+    for (size_t i = 0; i < G; ++i) {
+        const int a = c->gen_perm[i];
+        const double pmn = n.p_min ? n.p_min[a] : c->gen_bmin_h[i];
+        if (!(pmn > 0.0)) continue;
+        const double pm = c->gen_budget_h[i];
+        const double *f = nullptr;
+        if (n.table) {
+            const int k = n.profile_of ? n.profile_of[a] : -1;
+            if (k >= 0) f = n.profiles + (size_t)k * T;
+        } else {
+            const int k = c->gen_prof_h.empty() ? -1 : c->gen_prof_h[i];
+            if (k >= 0) f = c->gen_avail_h.data() + (size_t)k * T;
+        }
+        const double hi = n.budget ? (n.e_max ? n.e_max[a] : INFINITY) : c->gen_budget_h[2 * G + i];
+        if (int rc = budget_floor_fits(c, entry, a, -1, 0, T, pm, pmn, hi, f)) return rc;
+        for (int j = 0; j < nw; ++j) {
+            const double wh = n.windows ? (n.win_max ? n.win_max[(size_t)j + (size_t)nw * a] : INFINITY)
+                                        : c->gen_bw_h[G * (size_t)nw + (size_t)j + (size_t)nw * i];
+            if (int rc = budget_floor_fits(c, entry, a, j, j > 0 ? ends[j - 1] : 0, ends[j], pm, pmn, wh, f)) return rc;
+        }
+    }
+    return DOPF_OK;
+}
+
+// dopf_set_generator_budget_min_output's checks: the budget flag, no ramps, 0 <= p_min <= gen_pmax (finite), and every row with a floor
+// able to stay under its stored e_max (whole horizon and per window) under the stored availability table
+int check_generator_budget_min_output(dopf_ctx *c, const double *p_min)
+{
+    const char *entry = "dopf_set_generator_budget_min_output";
+    if (!(c->flags2 & DOPF_F2_GEN_ENERGY_BUDGET))
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: floors on budget rows need DOPF_F2_GEN_ENERGY_BUDGET at dopf_create_ex (a DOPF_F_GEN_RAMP context "
+                                           "has dopf_set_generator_min_output)", entry);
+    if (c->q.flags & DOPF_F_GEN_RAMP)
+        return fail(c, DOPF_E_UNSUPPORTED, "%s: not on a DOPF_F_GEN_RAMP context (plain ramp contexts have dopf_set_generator_min_output; floors "
+                                           "inside the pair's ramp programme, DOPF_F2_GEN_RAMP_BUDGET, are not built)", entry);
+    if (!p_min) return DOPF_OK;
+    for (int i = 0; i < c->v.G; ++i) {
+        const int a = c->gen_perm[i];
+        if (!(std::isfinite(p_min[a]) && p_min[a] >= 0.0 && p_min[a] <= c->gen_budget_h[i]))
+            return fail(c, DOPF_E_INVALID, "%s: p_min[g = %d] is %g, outside [0, gen_pmax = %g]", entry, a, p_min[a], c->gen_budget_h[i]);
+    }
+    BudgetFloorGiven n;
+    n.p_min = p_min;
+    return budget_floor_rows_fit(c, entry, n);
+}
+
 // dopf_set_generator_energy_budget_windows: window j's minimum must be deliverable under the window's caps — e_min <= sum of cap[g,t]
 // over t0 <= t < t1, formed in t order. g: the caller's index (the message's); f: the generator's profile, or null
 static int budget_win_min_fits(dopf_ctx *c, const char *entry, int g, int j, int t0, int t1, double pm, double e_min, const double *f)
@@ -362,7 +442,10 @@ int check_generator_energy_budget_windows(dopf_ctx *c, int32_t n_win, const int3
             if (int rc = budget_win_min_fits(c, entry, a, j, j > 0 ? win_end[j - 1] : 0, win_end[j], c->gen_budget_h[i], lo, f)) return rc;
         }
     }
-    return DOPF_OK;
+    // dopf_set_generator_budget_min_output: ... and every row with a stored floor able to stay under each window's new e_max
+    BudgetFloorGiven n;
+    n.windows = true; n.n_win = n_win; n.win_end = win_end; n.win_max = e_max;
+    return budget_floor_rows_fit(c, entry, n);
 }
 
 // dopf_set_generator_energy_budget's checks: the flag, no NaN, e_min finite and >= 0, e_max >= 0, e_min <= e_max, and every minimum
@@ -377,6 +460,10 @@ int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double
                     (int)c->gen_bw_end_h.size());
     if (int rc = check_generator_energy_budget_values(c, "dopf_set_generator_energy_budget", c->gen_budget_h.data(), c->gen_avail_h.data(), e_min, e_max))
         return rc;
+    // dopf_set_generator_budget_min_output: ... and every row with a stored floor able to stay under its new e_max
+    BudgetFloorGiven n;
+    n.budget = true; n.e_max = e_max;
+    if (int rc = budget_floor_rows_fit(c, "dopf_set_generator_energy_budget", n)) return rc;
     // DOPF_F2_GEN_RAMP_BUDGET: ... and every row jointly feasible with its stored ramps and anchor
     return ramp_budget_rows_fit(c, "dopf_set_generator_energy_budget", false, nullptr, nullptr, nullptr, true, e_min, e_max, false, nullptr, nullptr);
 }
@@ -451,6 +538,10 @@ int check_generator_availability(dopf_ctx *c, int32_t K, const double *profiles,
                                              c->gen_budget_h[i], c->gen_bw_h[(size_t)j + (size_t)nw * i], k >= 0 ? profiles + (size_t)k * T : nullptr))
                 return rc;
     }
+    // the floors of dopf_set_generator_budget_min_output against the stored maxima, under the new table
+    BudgetFloorGiven n;
+    n.table = true; n.profiles = profiles; n.profile_of = profile_of;
+    if (int rc = budget_floor_rows_fit(c, "dopf_set_generator_availability", n)) return rc;
     // DOPF_F2_GEN_RAMP_BUDGET: the stored ramps and budgets together, under the new table
     return ramp_budget_rows_fit(c, "dopf_set_generator_availability", false, nullptr, nullptr, nullptr, false, nullptr, nullptr, true, profiles,
                                 profile_of);
@@ -1986,6 +2077,60 @@ int dopf_get_generator_min_output(dopf_ctx *c, double *p_min)
     return DOPF_OK;
 }
 
+// the floors of a budget context. The device array is the context's own, allocated and zeroed at the first call with an
+// array and kept from then on (Plan::genBudgetMinOut points at it while floors are set)
+int dopf_set_generator_budget_min_output(dopf_ctx *c, const double *p_min)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (int rc = check_generator_budget_min_output(c, p_min)) return rc;
+    const size_t G = (size_t)c->v.G;
+    if (G == 0) return DOPF_OK;
+    DeviceGuard guard(c->device);
+    if (!p_min && !c->gen_bmin_d) {                        // (no floors were ever set: nothing to take back but the stop test)
+        launch_reset_status(c->v, c->main);
+        HIPCHK(c, hipGetLastError());
+        return read_status(c);
+    }
+    std::vector<double> h(G, 0.0);
+    if (p_min)
+        for (size_t i = 0; i < G; ++i) h[i] = p_min[c->gen_perm[i]] + 0.0;
+    if (!c->gen_bmin_d) {
+        const unsigned long long need = (unsigned long long)G * sizeof(double);
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        size_t freeb = 0, totalb = 0;
+        HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
+        if (need > freeb)
+            return fail(c, DOPF_E_NOMEM, "dopf_set_generator_budget_min_output: the floors (G doubles) need %llu bytes, the device has %llu free", need,
+                        (unsigned long long)freeb);
+        if (int rc = dev_alloc(c, &c->gen_bmin_d, G, true)) return rc;      // (zeroed on the context's stream, as the ramp prices are)
+    }
+    // the first array switches the context to the MN instantiations of its generator kernel, NULL switches back: other kernels, so the
+    // iteration graphs are captured again at the next dopf_iterate. Between two arrays the graphs read the same device array
+    const bool on = p_min != nullptr;
+    if (on != (c->plan.genBudgetMinOut != nullptr)) {
+        HIPCHK(c, hipStreamSynchronize(c->main));
+        c->plan.genBudgetMinOut = on ? c->gen_bmin_d : nullptr;
+        drop_graphs(c);
+    }
+    // ordered on the context's stream behind what is queued there. The state stays (a P below its floor is a proximal centre: the next
+    // x-update clamps it); the stop test starts over, as after dopf_set_generator_min_output
+    HIPCHK(c, hipMemcpyAsync(c->gen_bmin_d, h.data(), G * sizeof(double), hipMemcpyHostToDevice, c->main));
+    launch_reset_status(c->v, c->main);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = read_status(c)) return rc;          // (synchronises: h may go)
+    c->gen_bmin_h = h;
+    return DOPF_OK;
+}
+
+// the stored floors from the host mirror (no device call); a context that never set any holds none: zeros
+int dopf_get_generator_budget_min_output(dopf_ctx *c, double *p_min)
+{
+    if (!c) return DOPF_E_INVALID;
+    if (!p_min) return c->v.G == 0 ? DOPF_OK : fail(c, DOPF_E_INVALID, "dopf_get_generator_budget_min_output: p_min is NULL");
+    for (int i = 0; i < c->v.G; ++i) p_min[c->gen_perm[i]] = c->gen_bmin_h.empty() ? 0.0 : c->gen_bmin_h[(size_t)i];
+    return DOPF_OK;
+}
+
 // the multipliers of the last computed x-update, as k_gen_budget<.., PR = true> / k_gen_ramp_budget stored them (sorted order on the device)
 int dopf_get_generator_budget_price(dopf_ctx *c, double *nu)
 {
@@ -2273,6 +2418,7 @@ static int check_gen_window(dopf_ctx *c, const char *entry, GenWindow &w)
     if (ramp) rc = check_generator_ramp_values(c, entry, c->gen_ramp_h.data(), c->gen_avail_h.data(), up.data(), down.data(), prev.data());
     if (!rc && budget) rc = check_generator_energy_budget_values(c, entry, c->gen_budget_h.data(), c->gen_avail_h.data(), lo.data(), hi.data());
     if (!rc) rc = ramp_floor_rows_fit(c, entry, nullptr, false, nullptr, nullptr, nullptr, false, nullptr, nullptr);     // (the stored floors stay)
+    if (!rc) rc = budget_floor_rows_fit(c, entry, BudgetFloorGiven{});     // (the stored floors of dopf_set_generator_budget_min_output stay too)
     if (!rc) rc = ramp_budget_rows_fit(c, entry, false, nullptr, nullptr, nullptr, false, nullptr, nullptr, false, nullptr, nullptr);
     w.swap(c);
     return rc;

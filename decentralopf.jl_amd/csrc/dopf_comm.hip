@@ -765,6 +765,12 @@ int dopf_multi_set_generator_min_output(dopf_multi *m, const double *p_min)
                      [&](auto f, int i) { return f(m->ctx[i], from(p_min, m->g0[i])); });
 }
 
+int dopf_multi_set_generator_budget_min_output(dopf_multi *m, const double *p_min)
+{
+    return multi_set(m, check_generator_budget_min_output, dopf_set_generator_budget_min_output,
+                     [&](auto f, int i) { return f(m->ctx[i], from(p_min, m->g0[i])); });
+}
+
 int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, const double *e_max)
 {
     return multi_set(m, check_generator_energy_budget, dopf_set_generator_energy_budget,

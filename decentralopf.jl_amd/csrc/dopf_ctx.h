@@ -49,6 +49,9 @@ struct dopf_ctx {
     std::vector<int32_t> gen_bw_end_h;     // dopf_set_generator_energy_budget_windows: the window ends (empty: no table), and
     std::vector<double> gen_bw_h;          //     e_min | e_max, n_win x G each as on the device (sorted order, [j + n_win*i])
     void *gen_bw_base = nullptr;           // ... the device block behind plan.genBudgetWin (an entry of allocs; freed when n_win changes)
+    std::vector<double> gen_bmin_h;        // dopf_set_generator_budget_min_output: the floors p_min as on the device (sorted order; empty until the first
+                                           //     array: no floors), behind plan.genBudgetMinOut, and that array (kept across a NULL call, zeroed)
+    double *gen_bmin_d = nullptr;
     dopf::Status host_st{};
     dopf::Status *host_pin = nullptr;       // page-locked landing area of the status read-back (a pageable target is staged: slower)
     unsigned long long solver_fail_seen = 0;   // failures already reported through DOPF_E_SOLVER
@@ -97,6 +100,8 @@ int check_generator_energy_budget(dopf_ctx *c, const double *e_min, const double
 // those of dopf_set_generator_energy_budget_windows (flag, no pair, no whole-horizon budget, the ends, the values, every window's
 // e_min <= the window's sum of caps)
 int check_generator_energy_budget_windows(dopf_ctx *c, int32_t n_win, const int32_t *win_end, const double *e_min, const double *e_max);
+// those of dopf_set_generator_budget_min_output (the budget flag, no ramps, 0 <= p_min <= gen_pmax finite, sum floor <= e_max per row or window)
+int check_generator_budget_min_output(dopf_ctx *c, const double *p_min);
 // the two without their flag checks, for a caller that keeps the arrays itself (dopf_central_solve_coupled; `entry`: the name the
 // messages carry). pmax: capacities in sorted order; table: the availability profiles [t + T*k] the context's gen_prof_h refers to
 int check_generator_ramp_values(dopf_ctx *c, const char *entry, const double *pmax, const double *table, const double *up, const double *down,

@@ -75,6 +75,9 @@ struct Plan {
     BudgetWinView genBudgetWin;     // n_win > 0: k_gen_budget_win<LINES, AV, QC> (gen_budget_win.h) runs for k_gen_budget, with this as its second
                                     // argument: the window ends, budgets and prices of the context's own. Like genMinOut never set by plan_chain:
                                     // dopf_set_generator_energy_budget_windows sets and clears it on a genBudget context (and drops the graphs)
+    double *genBudgetMinOut;        // non-null: the MN instantiations of k_gen_budget / k_gen_budget_win read the rows' floors there (G
+                                    // doubles of the context's own, sorted order; the kernels' last argument). Like genMinOut never set by plan_chain:
+                                    // dopf_set_generator_budget_min_output sets it with an array and clears it with NULL (and drops the graphs)
     bool stoE0;                     // DOPF_F_STO_INITIAL_LEVEL: initial levels in sto_e0(v) (k_derive_level reads them)
     int stoLV;                      // the storage bodies' level mode: 0 none, 1 initial levels (DOPF_F_STO_INITIAL_LEVEL), 2 initial levels
                                     // and terminal bands (DOPF_F_STO_TERMINAL_LEVEL; sto_e0(v) holds zeros without the first flag), 3 those

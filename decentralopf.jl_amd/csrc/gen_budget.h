@@ -27,12 +27,15 @@ namespace dopf {
 
 constexpr int kBudgetWaves = 8;
 
-// a row's step at one timestep with the marginal cost mce (gen_mc[g] + nu; at nu = 0 gen_mc[g] itself): copper plate
-template <bool AV, bool QC>
+// a row's step at one timestep with the marginal cost mce (gen_mc[g] + nu; at nu = 0 gen_mc[g] itself): copper plate.
+// MN (dopf_set_generator_budget_min_output): the box of step t is [fmin(pmn, cap_t), cap_t] — a floor that follows the cap
+// down; pmn is the row's p_min (not read without MN: every expression is the one of before)
+template <bool AV, bool QC, bool MN = false>
 struct BudgetRowPlate {
     const double *price, *s, *Prow, *ftab;
     double gam, inv, c2, iq, pm;
     int node, N, T, prof;
+    double pmn = 0.0;
     __device__ __forceinline__ double cap(int t) const { return AV ? avail_cap(ftab, T, prof, pm, t) : pm; }
     // the expressions of gen_update_body, LINES = false (as k_gen_ramp forms them); piece: the clip state of the unclamped step.
     // Without QC gen_update_body writes mc * inv + shift, shift = psum * inv, which the compiler contracts into fma(mc, inv, shift):
@@ -46,21 +49,28 @@ struct BudgetRowPlate {
         if constexpr (QC) c = p0 - fma(mce + c2 * p0, iq, psum * iq);
         else c = p0 - fma(mce, inv, psum * inv);
         const double cp = cap(t);
-        piece = budget_piece(c, cp, 0);
-        return clampd(c, 0.0, cp);
+        if constexpr (MN) {
+            const double fl = fmin(pmn, cp);
+            piece = budget_piece(c, fl, cp, 0);
+            return clampd(c, fl, cp);
+        } else {
+            piece = budget_piece(c, cp, 0);
+            return clampd(c, 0.0, cp);
+        }
     }
     // the largest slope |dx_t / dnu| of a timestep
     __device__ __forceinline__ double slope() const { return QC ? iq : inv; }
 };
 
 // ... on a network: the step of gen_lines_body, one binary search over the node's table and one linear solve; piece: the clip state
-// and, inside the box, the table's interval
-template <bool AV, bool QC>
+// and, inside the box, the table's interval. MN: as BudgetRowPlate's
+template <bool AV, bool QC, bool MN = false>
 struct BudgetRowNet {
     const DevView *v;
     const double *Prow, *ftab;
     double w, c2, pm;
     int node, N, T, prof;
+    double pmn = 0.0;
     __device__ __forceinline__ double cap(int t) const { return AV ? avail_cap(ftab, T, prof, pm, t) : pm; }
     __device__ __forceinline__ double step(int t, double mce, double &p0, int &piece) const
     {
@@ -99,8 +109,14 @@ struct BudgetRowNet {
             dl = beta[a] - (mce + psi[a] + w * beta[a]) * rcp64(slope[lo] + w);
         }
         const double cp = cap(t);
-        piece = budget_piece(p0 + dl, cp, lo);
-        return clampd(p0 + dl, 0.0, cp);
+        if constexpr (MN) {
+            const double fl = fmin(pmn, cp);
+            piece = budget_piece(p0 + dl, fl, cp, lo);
+            return clampd(p0 + dl, fl, cp);
+        } else {
+            piece = budget_piece(p0 + dl, cp, lo);
+            return clampd(p0 + dl, 0.0, cp);
+        }
     }
     // (Psi is non-decreasing: every piece's slope is at most 1 / (w + c2))
     __device__ __forceinline__ double slope() const { return 1.0 / (w + c2); }
@@ -114,9 +130,13 @@ __device__ __forceinline__ double budget_wave_sum(double x)
 
 // PR: lane 0 stores every row's multiplier for dopf_get_generator_budget_price. The store measured 0.75 us per iteration on config2
 // with default budgets, so it is an instantiation of its own, which a context runs from its first call of that entry on
-// (Plan::genBudgetPrice); the PR = false instantiations are the code of before
-template <bool LINES, bool AV, bool QC, bool PR>
-__global__ __launch_bounds__(512) void k_gen_budget(DevView v)
+// (Plan::genBudgetPrice); the PR = false instantiations are the code of before.
+// MN: the rows' floors are read from mnv (Plan::genBudgetMinOut: G doubles of the context's own, sorted order) and the box is
+// [fmin(p_min, cap), cap] in the clamped step, the search and the stored row alike — a row with default budgets stores
+// clampd(c, floor, cap). p_min is one value per row, the wave's scalar like mc and pm. The MN = false instantiations never read
+// mnv (null then) and are the code of before
+template <bool LINES, bool AV, bool QC, bool PR, bool MN>
+__global__ __launch_bounds__(512) void k_gen_budget(DevView v, const double *mnv)
 {
     if (v.st->halt) return;
     __shared__ double red[512];
@@ -138,10 +158,12 @@ __global__ __launch_bounds__(512) void k_gen_budget(DevView v)
         const int pr = AV ? prof[g] : -1;
         double c2 = 0.0, iq = inv;
         if constexpr (QC) { c2 = c2v[g]; iq = 1.0 / ((w + gam) + c2); }
+        double pmn = 0.0;
+        if constexpr (MN) pmn = mnv[g];
         double *Prow = v.P + (size_t)g * T;
         // (both row types are cheap to fill; the one the kernel does not use folds away)
-        const BudgetRowPlate<AV, QC> plate{v.price, v.s, Prow, ftab, gam, inv, c2, iq, pm, it.node, N, T, pr};
-        const BudgetRowNet<AV, QC> net{&v, Prow, ftab, w, c2, pm, it.node, N, T, pr};
+        const BudgetRowPlate<AV, QC, MN> plate{v.price, v.s, Prow, ftab, gam, inv, c2, iq, pm, it.node, N, T, pr, pmn};
+        const BudgetRowNet<AV, QC, MN> net{&v, Prow, ftab, w, c2, pm, it.node, N, T, pr, pmn};
         auto step = [&](int t, double mce, double &p0, int &piece) {
             if constexpr (LINES) return net.step(t, mce, p0, piece);
             else return plate.step(t, mce, p0, piece);
@@ -243,8 +265,11 @@ void launch_gen_budget(const DevView &v, const Plan &p, hipStream_t s)
         with_bool(p.genAvail, [&](auto av) {
             with_bool(p.genQuad, [&](auto qc) {
                 with_bool(p.genBudgetPrice, [&](auto pr) {
-                    hipLaunchKernelGGL((k_gen_budget<decltype(ln)::value, decltype(av)::value, decltype(qc)::value, decltype(pr)::value>),
-                                       dim3(v.nGenItems), dim3(512), 0, s, v);
+                    with_bool(p.genBudgetMinOut != nullptr, [&](auto mn) {
+                        hipLaunchKernelGGL((k_gen_budget<decltype(ln)::value, decltype(av)::value, decltype(qc)::value, decltype(pr)::value,
+                                                         decltype(mn)::value>),
+                                           dim3(v.nGenItems), dim3(512), 0, s, v, (const double *)p.genBudgetMinOut);
+                    });
                 });
             });
         });

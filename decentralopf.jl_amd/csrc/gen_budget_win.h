@@ -22,8 +22,11 @@
 
 namespace dopf {
 
-template <bool LINES, bool AV, bool QC>
-__global__ __launch_bounds__(512) void k_gen_budget_win(DevView v, BudgetWinView bw)
+// MN: as k_gen_budget's — the rows' floors behind mnv, the box [fmin(p_min, cap), cap] (dopf_set_generator_budget_min_output),
+// in free windows too. The one-step closed form keeps its shape: the clamped step is at or above the floor already, and the setter
+// has made sure that e_max >= floor. The MN = false instantiations never read mnv and are the code of before
+template <bool LINES, bool AV, bool QC, bool MN>
+__global__ __launch_bounds__(512) void k_gen_budget_win(DevView v, BudgetWinView bw, const double *mnv)
 {
     if (v.st->halt) return;
     __shared__ double red[512];
@@ -50,9 +53,11 @@ __global__ __launch_bounds__(512) void k_gen_budget_win(DevView v, BudgetWinView
         const int pr = AV ? prof[g] : -1;
         double c2 = 0.0, iq = inv;
         if constexpr (QC) { c2 = c2v[g]; iq = 1.0 / ((w + gam) + c2); }
+        double pmn = 0.0;
+        if constexpr (MN) pmn = mnv[g];
         double *Prow = v.P + (size_t)g * T;
-        const BudgetRowPlate<AV, QC> plate{v.price, v.s, Prow, ftab, gam, inv, c2, iq, pm, it.node, N, T, pr};
-        const BudgetRowNet<AV, QC> net{&v, Prow, ftab, w, c2, pm, it.node, N, T, pr};
+        const BudgetRowPlate<AV, QC, MN> plate{v.price, v.s, Prow, ftab, gam, inv, c2, iq, pm, it.node, N, T, pr, pmn};
+        const BudgetRowNet<AV, QC, MN> net{&v, Prow, ftab, w, c2, pm, it.node, N, T, pr, pmn};
         auto step = [&](int t, double mce, double &p0, int &piece) {
             if constexpr (LINES) return net.step(t, mce, p0, piece);
             else return plate.step(t, mce, p0, piece);
@@ -154,8 +159,10 @@ void launch_gen_budget_win(const DevView &v, const Plan &p, hipStream_t s)
     with_bool(v.L > 0, [&](auto ln) {
         with_bool(p.genAvail, [&](auto av) {
             with_bool(p.genQuad, [&](auto qc) {
-                hipLaunchKernelGGL((k_gen_budget_win<decltype(ln)::value, decltype(av)::value, decltype(qc)::value>), dim3(v.nGenItems),
-                                   dim3(512), 0, s, v, p.genBudgetWin);
+                with_bool(p.genBudgetMinOut != nullptr, [&](auto mn) {
+                    hipLaunchKernelGGL((k_gen_budget_win<decltype(ln)::value, decltype(av)::value, decltype(qc)::value, decltype(mn)::value>),
+                                       dim3(v.nGenItems), dim3(512), 0, s, v, p.genBudgetWin, (const double *)p.genBudgetMinOut);
+                });
             });
         });
     });

@@ -418,6 +418,43 @@ function min_output(admm::ADMM)
 end
 
 """
+    set_budget_min_output!(admm, p_min)
+
+Must-run floors on an ADMM with energy budgets (`0 <= p_min[g] <= max_generation`, in the order of `generators`; `nothing` removes
+them): `min(p_min[g], cap[g,t]) <= P[g,t] <= cap[g,t]` inside the budgets' own step, for every generator, budgeted or not — a
+reservoir's minimum flow beside its water allotment. The ADMM must have been created with `flags2 = DOPF_F2_GEN_ENERGY_BUDGET` and
+without `DOPF_F_GEN_RAMP` (there `set_min_output!` serves). A generator whose floors sum above its `energy_max` (or a window's) is
+refused. The state and the iteration counter stay; takes effect at the next iteration.
+"""
+function set_budget_min_output!(admm::ADMM, p_min::Union{Nothing, Vector{Float64}})
+    G = length(admm.generators)
+    p_min === nothing || length(p_min) == G || error("set_budget_min_output!: expected $G values, got $(length(p_min))")
+    p = p_min === nothing ? Ptr{Cdouble}(C_NULL) : pointer(p_min)
+    GC.@preserve p_min begin
+        if admm.multi != C_NULL
+            dopf_check_multi(ccall((:dopf_multi_set_generator_budget_min_output, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.multi, p),
+                             admm.multi)
+        else
+            dopf_check(ccall((:dopf_set_generator_budget_min_output, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, p), admm.ctx)
+        end
+    end
+    return admm
+end
+
+"""
+    budget_min_output(admm)
+
+The floors of `set_budget_min_output!` as the context holds them (`dopf_get_generator_budget_min_output`; a multi-GPU ADMM: not
+available).
+"""
+function budget_min_output(admm::ADMM)
+    admm.multi == C_NULL || error("budget_min_output: not on a multi-GPU ADMM")
+    out = zeros(Float64, length(admm.generators))
+    GC.@preserve out dopf_check(ccall((:dopf_get_generator_budget_min_output, DOPF_LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), admm.ctx, pointer(out)), admm.ctx)
+    return out
+end
+
+"""
     set_energy_budget!(admm, e_min, e_max)
 
 The energy budget of each generator over the window (`e_min[g] >= 0` finite, `e_max[g] >= e_min[g]`, `Inf` = no limit, in the order

@@ -154,6 +154,7 @@ class PackedProblem:
     gen_min_output: Optional[np.ndarray] = None     # (G,) Generator.min_generation; None = all 0
     gen_budget_windows: Optional[tuple] = None  # (win_end (n_win,), e_min (G, n_win) or None, e_max (G, n_win) or None): energy budgets per
                                                 # sub-window of the horizon (window j: win_end[j-1] <= t < win_end[j]); None = no table
+    gen_budget_min_output: Optional[np.ndarray] = None  # (G,) must-run floors on a budget context (dopf_set_generator_budget_min_output); None = not set
 
     @property
     def G(self):
@@ -192,6 +193,8 @@ class PackedProblem:
             kw["gen_min_output"] = self.min_output()      # (engines then run with F_GEN_RAMP: the floors run on the ramp kernels)
         if self.has_budget_windows():      # (engines then run with F2_GEN_ENERGY_BUDGET and set the table behind everything else)
             kw["gen_budget_windows"] = self.budget_windows()
+        if self.gen_budget_min_output is not None:      # (engines then run with F2_GEN_ENERGY_BUDGET and set the floors last of all)
+            kw["gen_budget_min_output"] = np.asarray(self.gen_budget_min_output, dtype=np.float64)
         return kw
 
     def budget_windows(self):
@@ -307,7 +310,8 @@ class PackedProblem:
             gen_budget=None if self.gen_budget is None else tuple(np.asarray(b)[g0:g1] for b in self.gen_budget),
             gen_min_output=None if self.gen_min_output is None else np.asarray(self.gen_min_output)[g0:g1],
             gen_budget_windows=None if self.gen_budget_windows is None else tuple(
-                b if i == 0 or b is None else np.asarray(b).reshape(self.G, -1)[g0:g1] for i, b in enumerate(self.gen_budget_windows)))
+                b if i == 0 or b is None else np.asarray(b).reshape(self.G, -1)[g0:g1] for i, b in enumerate(self.gen_budget_windows)),
+            gen_budget_min_output=None if self.gen_budget_min_output is None else np.asarray(self.gen_budget_min_output)[g0:g1])
 
 
 def pack(nodes: Sequence[Node], generators: Sequence[Generator], storages: Sequence[Storage],

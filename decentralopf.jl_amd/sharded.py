@@ -134,6 +134,12 @@ class ShardedADMM:
         (dopf_set_generator_min_output; the bound is local to the rank's agents, no exchange). Every rank must call it."""
         self.engine.set_min_output(self._mine(p_min, "gen"))
 
+    def set_budget_min_output(self, p_min=None) -> None:
+        """All generators' must-run floors on a run with energy budgets (problem.G values, global order; None removes them): this
+        rank sets its slice (dopf_set_generator_budget_min_output; the bound is local to the rank's agents, no exchange). Needs
+        F2_GEN_ENERGY_BUDGET in the second flag word and no F_GEN_RAMP; every rank calls it between the same two steps."""
+        self.engine.set_budget_min_output(self._mine(p_min, "gen"))
+
     def set_ramp(self, up=None, down=None, prev=None) -> None:
         """All generators' ramp limits and (optionally) anchors (problem.G values each, global order; both ramps None = all inf,
         prev None = no anchor): this rank sets its slice (dopf_set_generator_ramp; the constraint is local to the rank's agents, no

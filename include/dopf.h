@@ -596,6 +596,32 @@ int dopf_get_generator_energy_budget_windows(dopf_ctx *ctx, int32_t *n_win, int3
  * Works while a trace is active; the trace does not record the prices. DOPF_E_INVALID while no table is set and for a NULL
  * pointer; with G == 0 the call returns DOPF_OK and does nothing. */
 int dopf_get_generator_budget_window_price(dopf_ctx *ctx, double *nu /* n_win x G, [j + n_win*g] */);
+/* Must-run floors on a budget context: on a context created with DOPF_F2_GEN_ENERGY_BUDGET and without DOPF_F_GEN_RAMP
+ * — copper plates, networks, the wide chain and DOPF_F_LONG_HORIZON, with or without a table of budgets per sub-window — every row's
+ * box becomes floor[g,t] <= P[g,t] <= cap[g,t] with floor[g,t] = min(p_min[g], cap[g,t]) and cap[g,t] = gen_pmax[g] (times the
+ * availability factor under DOPF_F_GEN_AVAILABILITY): the rules of dopf_set_generator_min_output — the floor follows an outage down,
+ * p_min = gen_pmax means must-take. The floor holds for every row of the context, rows with default budgets and free windows
+ * included; the objective, the budget rows e_min <= sum P <= e_max (whole-horizon or per window) and the consensus step are
+ * untouched, and the multiplier search of the budget kernels runs with [floor, cap] for [0, cap] (the MN instantiations of
+ * k_gen_budget and k_gen_budget_win). dopf_get_generator_budget_price and dopf_get_generator_budget_window_price keep their
+ * definitions and sign rule: nu is the multiplier of the row whose box has the floor as its lower end, at convergence minus the dual
+ * of the central LP with the same floors wherever that is unique. p_min in the caller's generator order; NULL: all 0.
+ * Callable between any two calls that iterate; the values are copied in order on the context's stream and take effect at the next
+ * x-update; P, D, C, the duals and the iteration counter are kept (a P below its floor handed in by dopf_set_state is only the
+ * proximal centre), converged becomes 0 and the residual maxima are cleared. The floors live in a device array of the context's
+ * own, allocated and zeroed at the first call with an array (DOPF_E_NOMEM, naming the bytes, where it does not fit). The first call
+ * with an array switches the context to the floor instantiations and drops the captured graphs, a NULL call switches back (and
+ * drops them); between two arrays the graphs stay valid. Every refusal names this entry and stores nothing: DOPF_E_UNSUPPORTED
+ * without DOPF_F2_GEN_ENERGY_BUDGET and on any DOPF_F_GEN_RAMP context (plain ramp contexts have dopf_set_generator_min_output; the
+ * pair DOPF_F2_GEN_RAMP_BUDGET has no floors); DOPF_E_INVALID, naming g (and j), for a NaN, an infinite or negative value,
+ * p_min[g] > gen_pmax[g], and a row that cannot stay under its maximum: sum_t floor[g,t] > e_max[g], or the same over a window of the
+ * stored table (sums formed in t order under the stored availability table; with e_min <= sum cap, which the budget setters check,
+ * the test is exact). dopf_set_generator_energy_budget, dopf_set_generator_energy_budget_windows, dopf_set_generator_availability
+ * and dopf_roll_horizon_coupled repeat that test for every row with a stored floor > 0 under their new values before they overwrite
+ * anything (the roll leaves p_min alone); their messages name the calling entry. With G == 0 the call returns DOPF_OK. */
+int dopf_set_generator_budget_min_output(dopf_ctx *ctx, const double *p_min /* G; NULL = all 0 */);
+/* The stored floors of dopf_set_generator_budget_min_output from the context's host copy (no device call); zeros while none are set */
+int dopf_get_generator_budget_min_output(dopf_ctx *ctx, double *p_min /* G */);
 /* The ramp prices of the decentral run: rp[t + T*g] is the multiplier the last computed x-update put on generator
  * g's ramp row -ramp_down <= P[g,t] - P[g,t-1] <= ramp_up between t-1 and t (t = 0: the anchor's row against p_prev, 0 without an
  * anchor) — what one more unit per step of flexibility of unit g is worth at step t, in the unit of gen_mc, in the caller's
@@ -893,6 +919,9 @@ int dopf_multi_set_generator_energy_budget(dopf_multi *m, const double *e_min, c
 /* dopf_set_generator_min_output for all G generators, p_min in the caller's order (NULL as there): each shard gets its slice; every
  * shard is checked before any stores */
 int dopf_multi_set_generator_min_output(dopf_multi *m, const double *p_min);
+/* dopf_set_generator_budget_min_output for all G generators, p_min in the caller's order (NULL as there): each shard gets its
+ * slice; every shard is checked before any stores */
+int dopf_multi_set_generator_budget_min_output(dopf_multi *m, const double *p_min);
 /* dopf_get_generator_budget_price of all shards' rows in the caller's order, like dopf_multi_get_primal: G values */
 int dopf_multi_get_generator_budget_price(dopf_multi *m, double *nu /* G */);
 /* dopf_set_generator_energy_budget_windows for all G generators: the ends are replicated, each shard gets the rows of its
